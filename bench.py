@@ -10,7 +10,10 @@ units, sharded over ranks with no per-step collective (weak scaling: batch_per_g
 
 Usage (driver contract):  python bench.py --gpus N --steps K --warmup W
   N>1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the time of one timed step.
+  --dump-outputs DIR  writes the final latents and decoded images of the last timed step to DIR/{latents,images}.npy (float32, at most
+  64 MB in all: beyond that a fixed, seeded sample of the elements); the inputs depend on the arguments only, so two builds can be
+  compared output for output.
 """
 import argparse
 import ctypes
@@ -58,7 +61,12 @@ def parse():
     ap.add_argument("--transport", default="rccl", choices=("rccl", "host"),
                     help="N > 1 exchange steps: rccl = device buffers over RCCL / xGMI (the product path); host = the library's communicator over a host transport "
                          "(torch.distributed gloo), so that the world > 1 branch runs where RCCL cannot (several ranks sharing one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (final latents, decoded images) to DIR/<name>.npy, float32, at most 64 MB in all")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def pmc_files(workload, B, kind):
@@ -202,6 +210,31 @@ def run_extra(engine, text, Lh, _lib, workload, tae, steps, cfg, denoise_steps, 
     aux = {"plist": g.unet_ctx().param_list(), "unet_flops_b1": info["unet_flops"] / (2 * B if cfg > 1 else B), "decode_flops_b1": info["decode_flops"] / B, "flop_per_img": flop_per_img}
     g.destroy()
     return res, aux
+
+
+DUMP_BYTES = 64 * 10**6      # files on disk, .npy headers included
+NPY_HEADER = 128
+
+
+def dump_outputs(d, arrays):
+    """Writes each float32 array of `arrays` ({name: array}) to d/<name>.npy, at most DUMP_BYTES in all: arrays are taken whole, smallest first,
+    while they fit their share of what is left; one that does not is replaced by a sample of its flattened elements, the indices drawn with a
+    fixed seed from its size alone (the same elements on every run and every build).  Returns {name: {shape, sampled elements or None}}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left, info = DUMP_BYTES, {}
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, x) in enumerate(items):
+        x = np.ascontiguousarray(x, np.float32)
+        share = left // (len(items) - i) - NPY_HEADER
+        sample = None
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // 4, replace=False))
+            x, sample = x.reshape(-1)[idx], int(idx.size)
+        np.save(os.path.join(d, name + ".npy"), x)
+        left -= x.nbytes + NPY_HEADER
+        info[name] = {"shape": list(arrays[name].shape), "sampled_elements": sample}
+    return info
 
 
 def cpu_sample(model, width, height, cfg, denoise_steps, threads, nfe, plist):
@@ -456,6 +489,17 @@ def run(a, world, rank, local_rank):
     fence()
     el = time.perf_counter() - t0
     el = mdist.max_over_ranks(el, tdev)
+    # --dump-outputs, outside the timed region and before the next step overwrites them: what a caller of the timed path receives from its
+    # last step -- the final latents (N>1: every rank's, as gathered on rank 0) and the decoded images of this rank
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        if d_gather:
+            lat = d_gather.download((world * B, 4, height // 8, width // 8), np.float32)
+        else:
+            lat = np.empty((B, 4, height // 8, width // 8), np.float32)
+            _lib.check(L.mlsd_memcpy(lat.ctypes.data_as(_lib.vp), _lib.vp(g.latent_ptr()), ctypes.c_size_t(lat.nbytes), 1, None), "memcpy d2h")
+            _lib.check(L.mlsd_device_sync(), "sync")
+        dumped = dump_outputs(a.dump_outputs, {"latents": lat, "images": g.image()})
     # PCIe-inclusive variant (the reference's mlis_generate ends with host pixels): one more step that also copies the fp32
     # images of this rank to host memory; reported beside `value`, never as `value`
     fence()
@@ -490,6 +534,8 @@ def run(a, world, rank, local_rank):
         "unet_eval_ms": round(unet_ms / (a.steps * a.denoise_steps), 3),
         "images_per_s_with_d2h_of_fp32_images": round(B * world / el_host, 4),
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if world > 1:
         out["transport"] = a.transport
         out["rccl_ranks" if comm_kind.value == 0 else "host_transport_ranks"] = comm_ranks.value      # the communicator's world as the transport reports it (ncclCommCount)

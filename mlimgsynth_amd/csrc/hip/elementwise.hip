@@ -259,6 +259,8 @@ MLSD_API int mlsd_synth_fill(void* dst, int dtype, int64_t n, uint64_t key, floa
                              int64_t p0, int64_t p1, int64_t p2, int64_t p3, int64_t p4, void* stream)
 {
     if (n <= 0) return 0;
+    // the dry runtime's buffers are host memory: refuse before the launch (the check after it would let the kernel fault on a real GPU)
+    if (mlsd_runtime_is_dry()) return mlsd_check_launch("synth_fill");
     hipLaunchKernelGGL(synth_fill_kernel, dim3(nblocks((long)n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dst, dtype, (long)n,
                        key, offset, kf, layout, (long)p0, (long)p1, (long)p2, (long)p3, (long)p4);
     return mlsd_check_launch("synth_fill");

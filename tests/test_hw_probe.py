@@ -1,14 +1,11 @@
 """gfx950 lane-map probes: pin the MFMA f16 fragment layouts and the transposed
 LDS read the attention / GEMM kernels rely on, with exact integer data."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
 
 
 def _c_map(raw):
@@ -33,7 +30,7 @@ def test_runtime_shared_with_torch():
     assert torch.equal(x, y)
 
 
-def test_mfma_32x32x16_f16_layout():
+def test_mfma_32x32x16_f16_layout(tmp_path):
     from mlimgsynth_amd import _lib
     L = _lib.lib()
     rng = np.random.default_rng(0)
@@ -43,13 +40,12 @@ def test_mfma_32x32x16_f16_layout():
     dC = _lib.DeviceBuffer(64 * 16 * 4)
     _lib.check(L.mlsd_probe_mfma_raw(_lib.vp(dA.ptr), _lib.vp(dB.ptr), _lib.vp(dC.ptr), None))
     raw = dC.download((64, 16), np.float32)
-    os.makedirs(OUT, exist_ok=True)
-    np.save(os.path.join(OUT, "probe_mfma_raw.npy"), raw)
+    np.save(tmp_path / "probe_mfma_raw.npy", raw)
     ref = A.astype(np.float32) @ B.astype(np.float32)
     assert np.array_equal(_c_map(raw), ref)
 
 
-def test_mfma_accumulator_as_b_operand():
+def test_mfma_accumulator_as_b_operand(tmp_path):
     from mlimgsynth_amd import _lib
     L = _lib.lib()
     rng = np.random.default_rng(1)
@@ -60,13 +56,13 @@ def test_mfma_accumulator_as_b_operand():
     dY = _lib.DeviceBuffer(64 * 16 * 4)
     _lib.check(L.mlsd_probe_mfma_chain(_lib.vp(d[0].ptr), _lib.vp(d[1].ptr), _lib.vp(d[2].ptr), _lib.vp(dY.ptr), None))
     raw = dY.download((64, 16), np.float32)
-    np.save(os.path.join(OUT, "probe_mfma_chain.npy"), raw)
+    np.save(tmp_path / "probe_mfma_chain.npy", raw)
     X = A1.astype(np.float32) @ B1.astype(np.float32)
     ref = A2.astype(np.float32) @ X
     assert np.array_equal(_c_map(raw), ref)
 
 
-def test_ds_read_tr16_b64():
+def test_ds_read_tr16_b64(tmp_path):
     from mlimgsynth_amd import _lib
     L = _lib.lib()
     T = (np.arange(8)[:, None] * 64 + np.arange(32)[None, :]).astype(np.float16)  # value = row*64+col (exact)
@@ -74,7 +70,7 @@ def test_ds_read_tr16_b64():
     dO = _lib.DeviceBuffer(64 * 4 * 4)
     _lib.check(L.mlsd_probe_tr_read(_lib.vp(dT.ptr), 32, _lib.vp(dO.ptr), None))
     out = dO.download((64, 4), np.float32)
-    np.save(os.path.join(OUT, "probe_tr_read.npy"), out)
+    np.save(tmp_path / "probe_tr_read.npy", out)
     # expectation: lane L (g=L>>4, i=L&15) receives T[4*(g>>1) + j][16*(g&1) + i], j=0..3
     exp = np.zeros((64, 4), np.float32)
     for l in range(64):
@@ -84,7 +80,7 @@ def test_ds_read_tr16_b64():
     assert np.array_equal(out, exp), (out[:20], exp[:20])
 
 
-def test_hbm_copy_bandwidth_sane():
+def test_hbm_copy_bandwidth_sane(tmp_path):
     """A plain float4 copy should stream at TB/s on HBM3E (guide: ~6.3 TB/s achievable)."""
     from mlimgsynth_amd import _lib
     L = _lib.lib()
@@ -104,7 +100,7 @@ def test_hbm_copy_bandwidth_sane():
     _lib.check(L.mlsd_event_elapsed_ms(ev[0], ev[1], ctypes.byref(ms)))
     gbs = 5 * 2 * n / (ms.value * 1e-3) / 1e9
     print(f"copy bandwidth {gbs:.0f} GB/s")
-    with open(os.path.join(OUT, "probe_copy_bw.txt"), "w") as f:
+    with open(tmp_path / "probe_copy_bw.txt", "w") as f:
         f.write(f"{gbs:.1f} GB/s\n")
     assert gbs > 1000
 

@@ -1,5 +1,5 @@
 """Checkpoint loading, CPU part: tensor-name conversion against vectors produced by the
-REFERENCE's own tensor_name_conv.c (tests/golden/name_conv.json.gz, and live against oracle/_ref when it is built), the
+REFERENCE's own tensor_name_conv.c (tests/golden/name_conv.json.gz, and tests/reference_answers.py), the
 safetensors index, the open_clip in_proj split, model identification and dtype conversion.  The upload itself runs in
 the dry runtime (device memory served from host memory)."""
 import ctypes
@@ -57,22 +57,16 @@ def test_name_conversion_matches_reference_vectors(L):
 
 
 def test_name_conversion_live_against_reference_build(L):
-    so = os.path.join(ROOT, "oracle", "_ref", "libtnconv_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libtnconv_ref.so not built (the reference is only present in the build container)")
-    ref = ctypes.CDLL(so)
-    buf = ctypes.create_string_buffer(1024)
-    import ckpt_names as CN
+    """every parameter name of the tiny / tinyxl checkpoints against the reference's tnconv_sd (oracle/_ref, or its stored answers)"""
+    import reference_answers as RA
+    ref = RA.tnconv()
     n = 0
-    for model in ("tiny", "tinyxl"):
-        for k, _, _ in LC.model_params(model):
-            e = CN.external_name(k, "sd1" if model == "tiny" else "sdxl")
-            e = e[1] if isinstance(e, tuple) else e
-            r = ref.ref_tnconv_sd(e.encode(), buf, 1024)
-            assert conv(L, e) == [r, buf.value.decode()], e
-            if r == 1:
-                assert buf.value.decode() == k          # and the generator's inverse mapping round-trips
-            n += 1
+    for e, k in RA.tiny_checkpoint_names():
+        r, out = ref(e)
+        assert conv(L, e) == [r, out], e
+        if r == 1:
+            assert out == k          # and the generator's inverse mapping round-trips
+        n += 1
     assert n > 500
 
 

@@ -334,6 +334,31 @@ def test_bench_json_contract_on_tiny_workload():
     assert abs(sum(v["share"] for v in m["by_family"].values()) - 1) < 0.35       # (top six families)
 
 
+def test_bench_dump_outputs_repeat_bit_identically(tmp_path):
+    """bench.py --dump-outputs: the final latents and decoded images of the last timed step, float32, the same bits from two processes
+    with the same arguments (the inputs depend on the arguments only); with one more timed step the dump is that step's (other seeds)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for name, steps in (("a", 2), ("b", 2), ("c", 3)):
+        d = tmp_path / name
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--workload", "tiny",
+                              "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["dump_outputs"]["dir"] == str(d)
+        runs.append({k: np.load(d / f"{k}.npy") for k in ("latents", "images")})
+    a, b, c = runs
+    assert a["latents"].shape == (2, 4, 8, 8) and a["images"].shape == (2, 3, 64, 64)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and a[k].std() > 0
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    assert not np.array_equal(a["latents"], c["latents"])           # the last timed step of run c draws other seeds (image indices 4, 5)
+
+
 def test_bench_line_carries_the_whole_baseline_metric():
     """beside the unchanged headline value the one JSON line holds SD1.5 512x512 b1 (BASELINE configs[1]) and
     SDXL + TAESD as extra keys, each with its own roofline, and the CPU sample of BASELINE.md section 3 (one SD1.5 evaluation).

@@ -1,17 +1,15 @@
 """CLIP tokenizer (csrc/host/clip_tokenizer.c) against the reference's 14 known-answer tests
 (src/test_text_tokenize_clip.c:41-66, committed as data in tests/golden/reference_kats.json).
 
-The BPE merge table is user-supplied data in this engine (the reference compiles src/clip_merges.c.h in).  It is
-not committed; where /root/reference is mounted (this container, never the GPU box) the tests read the id pairs
-from it at run time, and also spell them out in OpenAI's public vocabulary format to exercise the text loader."""
+The BPE merge table is user-supplied data in this engine (the reference compiles src/clip_merges.c.h in).  The tests
+read its id pairs from tests/golden/clip_merges.npz (tests/reference_answers.py), and also spell them out in OpenAI's
+public vocabulary format to exercise the text loader."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
-REF_MERGES = "/root/reference/src/clip_merges.c.h"
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_kats.json")))["clip_tokenize_kats"]["cases"]
 
 
@@ -23,10 +21,8 @@ def T():
 
 @pytest.fixture(scope="module")
 def pairs():
-    if not os.path.exists(REF_MERGES):
-        pytest.skip("merge table data not available (needs /root/reference)")
-    nums = re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*\}", open(REF_MERGES).read())
-    p = np.array(nums, np.int32)
+    import reference_answers as RA
+    p = RA.clip_merges()
     assert p.shape == (48894, 2)
     return p
 

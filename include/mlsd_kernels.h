@@ -124,8 +124,9 @@ typedef struct mlsd_gemm_args {
 	size_t ws_bytes;
 	/* column statistics of the fp32 output for a consuming GroupNorm (its first pass disappears): per block of
 	 * mlsd_gemm_colstats_rows(args) consecutive rows and per column the sum and the sum of squares of C32, written as
-	 * colstats[block][0][n] and colstats[block][1][n] (floats, 2*N per block).  Only the launches for which
-	 * mlsd_gemm_colstats_rows() > 0 honour it (ping-pong tiles, fp32 output without activation); NULL = off. */
+	 * colstats[block][0][n] and colstats[block][1][n] (floats, 2*N per block); with colstats_shift (below) the sums of
+	 * (x - K) and (x - K)^2 instead.  Only the launches for which mlsd_gemm_colstats_rows() > 0 honour it (ping-pong tiles,
+	 * fp32 output without activation); NULL = off. */
 	float* colstats;
 	int colstats_rows;      /* > 0: the consumer was wired for statistics blocks of this many rows: mlsd_gemm FAILS unless this
 	                         * launch writes exactly those (a tile / epilogue knob changed between planning and launching) */
@@ -170,6 +171,11 @@ typedef struct mlsd_gemm_args {
 	const void* xa_vt;
 	void* xa_out; int64_t xa_ldo;
 	int xa_Tq, xa_Tk;
+	/* 1: colstats holds SHIFTED sums, sum (x - K) and sum (x - K)^2 with K = C32[first row of the block][n], which the consuming
+	 * GroupNorm reads back from C32 (mlsd_gn_args.cs_shifted).  0: the plain sums of x and x^2.  Plain fp32 sums of squares lose
+	 * ~2^-24 sqrt(rows) r^2 of a group's variance (r = |mean| / std: percents at r = 300), which no later double arithmetic recovers;
+	 * the plan builder always asks for 1, 0 keeps the meaning the field had for callers that do not set it. */
+	int colstats_shift;
 } mlsd_gemm_args;
 
 int mlsd_gemm(const mlsd_gemm_args* a, void* stream);
@@ -265,6 +271,8 @@ typedef struct mlsd_gn_args {
 	 * over x: used when every source has them (rb_rows_i > 0) and HW is a multiple of rb_rows_i */
 	const float *cs1, *cs2;
 	int rb_rows1, rb_rows2;
+	int cs_shifted;                       /* 1: cs1 / cs2 were written with mlsd_gemm_args.colstats_shift = 1; x_i must then be the C32
+	                                       * they were written with (the finalize reads each block's shift back from it) */
 } mlsd_gn_args;
 
 size_t mlsd_groupnorm_ws_bytes(int n_img, int HW, int n_grp);

@@ -73,6 +73,7 @@ struct GemmP {
     int gw;    // tile-order panel width (0: row-major)
     unsigned long long* tbuf;   // diagnostics: per-block cycle stamps of the ping-pong kernels (tools/gemm_trace.py), or null
     float* colstats;            // ping-pong kernels built with a *_STATS epilogue: [row block][2][N] column sums / sums of squares
+    int cs_shift;               // 1: of (x - K), K = the column's value in the block's first row (mlsd_gemm_args.colstats_shift); 0: of x
     // stream-K (gemm_pp.hpp, SK): K-tile units per block, slabs [block][BM*BN] fp32, one flag per block
     int sk_L;
     float* sk_ws;
@@ -486,8 +487,9 @@ void gemm_kernel(const GemmP p, const GemmP pe)
             return v;
         };
         // column statistics for a consuming GroupNorm (GemmP::colstats, round 4 on these tiles): per 64-column slab, the lane's 4 columns summed over the wave's WM rows
-        // (8 rows per 32-row block in the lane, then the 4 row groups of the wave by shuffles): one partial per (block of WM rows, column), fixed order
-        float4 st_s[ST ? (TN + 1) / 2 : 1], st_q[ST ? (TN + 1) / 2 : 1];
+        // (8 rows per 32-row block in the lane, then the 4 row groups of the wave by shuffles): one partial per (block of WM rows, column), fixed order.  Shifted sums
+        // of (x - K), K = the column's value in the block's first row, or of x (K = 0): mlsd_gemm_args.colstats_shift
+        float4 st_s[ST ? (TN + 1) / 2 : 1], st_q[ST ? (TN + 1) / 2 : 1], st_k[ST ? (TN + 1) / 2 : 1];
         if constexpr (ST) {
 #pragma unroll
             for (int q = 0; q < (TN + 1) / 2; ++q) { st_s[q] = make_float4(0, 0, 0, 0); st_q[q] = make_float4(0, 0, 0, 0); }
@@ -517,11 +519,24 @@ void gemm_kernel(const GemmP p, const GemmP pe)
                         const float4 v = *reinterpret_cast<const float4*>(stg + row * 64 + c4);
                         float4 rp = make_float4(0, 0, 0, 0);
                         if constexpr (PRE) rp = rpre[SLAB0 + it];
-                        if (m >= p.M || n >= p.N) continue;
-                        const float4 o = finish4(m, n, v, bv, rp, PRE && pre);
-                        if constexpr (ST) {
-                            st_s[jc / 2].x += o.x; st_s[jc / 2].y += o.y; st_s[jc / 2].z += o.z; st_s[jc / 2].w += o.w;
-                            st_q[jc / 2].x += o.x * o.x; st_q[jc / 2].y += o.y * o.y; st_q[jc / 2].z += o.z * o.z; st_q[jc / 2].w += o.w * o.w;
+                        if constexpr (!ST) {
+                            if (m >= p.M || n >= p.N) continue;
+                            finish4(m, n, v, bv, rp, PRE && pre);
+                        } else {
+                            const bool in = m < p.M && n < p.N;
+                            float4 o = make_float4(0, 0, 0, 0);
+                            if (in) o = finish4(m, n, v, bv, rp, PRE && pre);
+                            if (i == 0 && it == 0) {      // the shift: the block's first row, held by lanes 0..15 (the consuming finalize reads it back from the output)
+                                const int src = lane & 15;
+                                const float4 k = make_float4(__shfl(o.x, src, 64), __shfl(o.y, src, 64), __shfl(o.z, src, 64), __shfl(o.w, src, 64));
+                                st_k[jc / 2] = p.cs_shift ? k : make_float4(0, 0, 0, 0);
+                            }
+                            if (in) {
+                                const float4 k = st_k[jc / 2];
+                                const float dx = o.x - k.x, dy = o.y - k.y, dz = o.z - k.z, dw = o.w - k.w;
+                                st_s[jc / 2].x += dx; st_s[jc / 2].y += dy; st_s[jc / 2].z += dz; st_s[jc / 2].w += dw;
+                                st_q[jc / 2].x += dx * dx; st_q[jc / 2].y += dy * dy; st_q[jc / 2].z += dz * dz; st_q[jc / 2].w += dw * dw;
+                            }
                         }
                     }
                 } else if (!geglu) {
@@ -750,7 +765,7 @@ __global__ __launch_bounds__(256) void splitk_reduce(const GemmP p, const float*
     }
 }
 
-// ---- split-K second pass that ALSO emits the column statistics of the rows it finishes (GemmP::colstats: [block of 32 rows][2][N] sums / sums of squares, for a
+// ---- split-K second pass that ALSO emits the column statistics of the rows it finishes (GemmP::colstats: [block of 32 rows][2][N] (shifted) sums / sums of squares, for a
 // consuming GroupNorm: its first pass over the fp32 map disappears).  A block = 32 rows x 256 columns: thread (row lane rl = t / 64, column group t % 64) finishes
 // rows rl, rl + 4, ... with the operations of splitk_reduce in its order (bit-identical output, the slices' loads of the 8 rows in flight together), sums its 4
 // columns over its 8 rows, and the 4 row lanes are combined through LDS in fixed order.
@@ -776,7 +791,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats(const GemmP p, const 
 #pragma unroll
         for (int k = 0; k < 8; ++k) { v[k].x += u[k].x; v[k].y += u[k].y; v[k].z += u[k].z; v[k].w += u[k].w; }
     }
-    float4 cs = make_float4(0, 0, 0, 0), cq = cs;
+    __shared__ float4 sh_k[64];
     float4 bv = make_float4(0, 0, 0, 0);
     if (p.bias && colok) bv = *reinterpret_cast<const float4*>(p.bias + n);
 #pragma unroll
@@ -806,8 +821,21 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats(const GemmP p, const 
             f16x4 h = {(_Float16)x.x, (_Float16)x.y, (_Float16)x.z, (_Float16)x.w};
             *reinterpret_cast<f16x4*>(p.C16 + (long)m * p.ldc16 + n) = h;
         }
-        cs.x += x.x; cs.y += x.y; cs.z += x.z; cs.w += x.w;
-        cq.x += x.x * x.x; cq.y += x.y * x.y; cq.z += x.z * x.z; cq.w += x.w * x.w;
+        v[k] = x;
+    }
+    // shifted sums (mlsd_gemm_args.colstats_shift; the consuming finalize reads the shift back from the output): K = the block's first row,
+    // finished by row lane 0; K = 0: plain sums
+    if (rl == 0) sh_k[cgi] = p.cs_shift ? v[0] : make_float4(0, 0, 0, 0);
+    __syncthreads();
+    const float4 K = sh_k[cgi];
+    float4 cs = make_float4(0, 0, 0, 0), cq = cs;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int m = mb + rl + 4 * k;
+        if (!colok || m >= p.M) continue;
+        const float4 d = make_float4(v[k].x - K.x, v[k].y - K.y, v[k].z - K.z, v[k].w - K.w);
+        cs.x += d.x; cs.y += d.y; cs.z += d.z; cs.w += d.w;
+        cq.x += d.x * d.x; cq.y += d.y * d.y; cq.z += d.z * d.z; cq.w += d.w * d.w;
     }
     sh_s[rl][cgi] = cs; sh_q[rl][cgi] = cq;
     __syncthreads();
@@ -1059,7 +1087,7 @@ int launch(const mlsd_gemm_args* a, hipStream_t st)
                 (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) && (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) &&
                 (!a->bias || !((uintptr_t)a->bias & 15)) && (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
     }
-    p.dbg = g_gemm_dbg; p.tbuf = nullptr; p.colstats = nullptr; p.sk_L = 0; p.sk_ws = nullptr; p.sk_flag = nullptr;
+    p.dbg = g_gemm_dbg; p.tbuf = nullptr; p.colstats = nullptr; p.cs_shift = a->colstats_shift ? 1 : 0; p.sk_L = 0; p.sk_ws = nullptr; p.sk_flag = nullptr;
     p.gw = g_gemm_panel;
     int kt_per;
     const int nsplit = p.vec ? splitk_slices(a, BK, &kt_per) : 1;
@@ -1292,6 +1320,7 @@ int launch_pp(const mlsd_gemm_args* a, hipStream_t st)
     // the epilogue the kernel is built with (gemm_pp.hpp): the bulk launches of the UNet / VAE have no activation in the GEMM
     const int epi = pp_epilogue_kind(a, BN);
     p.colstats = (epi == PP_EPI_F32_STATS || epi == PP_EPI_F32_RES_STATS) ? a->colstats : nullptr;
+    p.cs_shift = a->colstats_shift ? 1 : 0;
     if constexpr (SK) {       // the stream-K builds: the fp32 epilogues of the long-K convs / feed-forward outputs, fp16 for the fused projections
         if (a->conv) {
             switch (epi) {

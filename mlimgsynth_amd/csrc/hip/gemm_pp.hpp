@@ -436,8 +436,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
         constexpr int NR = 2 * RA;                               // 16-row blocks of the wave's slab: r = qa * RA + i
         constexpr int PF = !ST ? (BM == 128 ? NR : 2) : (BM == 128 ? NR : 1);  // (the statistics need 2 * NCB * 4 registers of their own)
         // ST: per column, sum and sum of squares over the wave's WM rows (a lane accumulates its 2*RA rows, the 16 lanes of a
-        // DPP row are the 16 rows of a block) -> one deterministic partial per (tile row, wave row, column): GemmP::colstats
-        f32x4 cs[ST ? NCB : 1], cq[ST ? NCB : 1];
+        // DPP row are the 16 rows of a block) -> one deterministic partial per (tile row, wave row, column): GemmP::colstats.
+        // With colstats_shift, sums of (v - K), K = the column's value in the block's first row (lane l15 == 0 of the DPP row, r == 0), which
+        // the consuming finalize reads back from C32: fp32 sums of squares of the raw values lose 2^-24 r^2 of the variance (r = |mean| / std).
+        // Without it K = 0: the plain sums.
+        f32x4 cs[ST ? NCB : 1], cq[ST ? NCB : 1], ck[ST ? NCB : 1];
         if constexpr (ST) {
 #pragma unroll
             for (int c = 0; c < NCB; ++c) { cs[c] = f32x4{0.f, 0.f, 0.f, 0.f}; cq[c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -486,7 +489,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
             for (int c = 0; c < NCB; ++c) {
                 f32x4 v = acc[qa][i][c] + cb[c];
                 if constexpr (RES) v += rr[r][c];
-                if constexpr (ST) { cs[c] += v; cq[c] += v * v; }
+                if constexpr (ST) {
+                    if (r == 0) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { const float k = __shfl(v[e], lane & 48, 64); ck[c][e] = p.cs_shift ? k : 0.f; }
+                    }
+                    const f32x4 d = v - ck[c];
+                    cs[c] += d; cq[c] += d * d;
+                }
                 if constexpr (S32) *reinterpret_cast<f32x4*>(c32b + (long)row_of(r) * p.ldc32 + c * 16) = v;
                 if constexpr (S16) {
                     f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};

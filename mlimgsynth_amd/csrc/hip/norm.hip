@@ -39,6 +39,7 @@ struct GnP {
     // is gn_finalize over these few KB..MB instead of gn_stats over the whole fp32 map
     const float *cs1, *cs2;
     int rb1, rb2;
+    int cs_shift;     // the statistics are shifted sums (mlsd_gn_args.cs_shifted): the finalize reads each block's shift from the map
     const float* mr;  // [n_img][G][2] mean, rstd (gn_finalize -> gn_apply), or null
 };
 
@@ -236,9 +237,20 @@ __global__ __launch_bounds__(256) void gn_apply(const GnP p)
     }
 }
 
+// The plan's producers write SHIFTED column statistics: per block of rb rows and column, S = sum (x - K) and Q = sum (x - K)^2 with
+// K = the column's value in the block's first row (mlsd_kernels.h, mlsd_gemm_args.colstats_shift).  The fp32 partials are then sums of
+// terms of the size of the spread, not of the mean: unshifted fp32 sums of x^2 lose 2^-24 sqrt(rb) r^2 of the variance
+// (r = |mean| / std; percents at r = 300), which no later double arithmetic recovers.  K is read back from the map; in double,
+// sum x = rb K + S and sum x^2 = rb K^2 + 2 K S + Q are exact to 2^-53 relative, so E[x^2] - mean^2 costs 2^-53 r^2.
+// Plain statistics (cs_shift 0, callers that do not ask for the shift) are taken as they are.
+__device__ __forceinline__ void gn_unshift(double K, double S, double Q, int rb, double& s, double& q)
+{
+    s += (double)rb * K + S;
+    q += ((double)rb * K + 2.0 * S) * K + Q;
+}
+
 // Mean / rstd of one (image, group) from the producers' column statistics: sums over the image's row blocks and the
-// group's channels, in double, fixed order (thread t takes items t, t+256, ..; then a fixed tree).  Unshifted sums: the
-// partials are fp32 sums of 64..128 values, the cancellation in E[x^2] - mean^2 happens in double.
+// group's channels, in double, fixed order (thread t takes items t, t+256, ..; then a fixed tree).
 __global__ __launch_bounds__(256) void gn_finalize(const GnP p, float* __restrict__ mr)
 {
     __shared__ double rs[256], rq[256];
@@ -253,10 +265,13 @@ __global__ __launch_bounds__(256) void gn_finalize(const GnP p, float* __restric
         const int Ci = src ? p.C2 : p.C1, rb = src ? p.rb2 : p.rb1, off = src ? p.C1 : 0;
         const int nrb = p.HW / rb, ncc = hi - lo;
         const float* base = cs + (long)img * nrb * 2 * Ci + (lo - off);
+        const float* xb = (src ? p.x2 : p.x1) + (long)img * p.HW * (src ? p.ld2 : p.ld1) + (lo - off);
+        const long xstep = (long)rb * (src ? p.ld2 : p.ld1);
         for (int idx = tid; idx < nrb * ncc; idx += 256) {
             const int k = idx / ncc, cc = idx - k * ncc;
             const float* e = base + (long)k * 2 * Ci + cc;
-            s += (double)e[0]; q += (double)e[Ci];
+            if (p.cs_shift) gn_unshift(xb[k * xstep + cc], e[0], e[Ci], rb, s, q);
+            else { s += (double)e[0]; q += (double)e[Ci]; }
         }
     }
     rs[tid] = s; rq[tid] = q;
@@ -291,8 +306,11 @@ __global__ __launch_bounds__(256) void gn_finalize_l1(const GnP p, double* __res
         const int nrb = p.HW / rb;
         const int k0 = (int)((long)chunk * nrb / nch), k1 = (int)((long)(chunk + 1) * nrb / nch);
         const float* e = cs + ((long)img * nrb + k0) * 2 * Ci + cc;
+        const long ldx = src ? p.ld2 : p.ld1, xstep = (long)rb * ldx;
+        const float* xk = (src ? p.x2 : p.x1) + ((long)img * p.HW + (long)k0 * rb) * ldx + cc;     // the shifts: row k * rb of the map
         double s = 0, q = 0;
-        for (int k = k0; k < k1; ++k, e += 2 * Ci) { s += (double)e[0]; q += (double)e[Ci]; }
+        if (p.cs_shift) { for (int k = k0; k < k1; ++k, e += 2 * Ci, xk += xstep) gn_unshift(*xk, e[0], e[Ci], rb, s, q); }
+        else for (int k = k0; k < k1; ++k, e += 2 * Ci) { s += (double)e[0]; q += (double)e[Ci]; }
         cs_[c] = s; cq_[c] = q;
     }
     __syncthreads();
@@ -620,7 +638,7 @@ MLSD_API int mlsd_groupnorm(const mlsd_gn_args* a, void* stream)
     p.pix_per_chunk = (a->HW + p.nchunk - 1) / p.nchunk;
     p.nchunk = (a->HW + p.pix_per_chunk - 1) / p.pix_per_chunk;
     const dim3 grid(p.nchunk, a->n_img);
-    p.cs1 = a->cs1; p.cs2 = a->cs2; p.rb1 = a->rb_rows1; p.rb2 = a->rb_rows2; p.mr = nullptr;
+    p.cs1 = a->cs1; p.cs2 = a->cs2; p.rb1 = a->rb_rows1; p.rb2 = a->rb_rows2; p.cs_shift = a->cs_shifted ? 1 : 0; p.mr = nullptr;
     const bool from_producers = a->cs1 && a->rb_rows1 > 0 && !(a->HW % a->rb_rows1) &&
                                 (a->C2 == 0 || (a->cs2 && a->rb_rows2 > 0 && !(a->HW % a->rb_rows2)));
     int rc;

@@ -1122,9 +1122,11 @@ static void wire_gn_stats(MLCtx* C)
 		for (int k=0;k<2 && ok;++k) if (pr[k] && !pr[k]->u.gemm.colstats) {     /* one buffer per producer, shared by its consumers */
 			mlsd_gemm_args *pg = &pr[k]->u.gemm;
 			pg->colstats = (float*)mlctx_dalloc(C, (size_t)(pg->M / (k ? r2 : r1)) * 2 * pg->N * sizeof(float), 1);
+			pg->colstats_shift = 1;                                      /* sums of (x - the block's first row): well conditioned at any mean / std */
 			if (!pg->colstats) ok = 0;
 		}
 		if (!ok) continue;
+		g->cs_shifted = 1;
 		g->cs1 = p1->u.gemm.colstats; g->rb_rows1 = r1;
 		g->cs2 = p2 ? p2->u.gemm.colstats : NULL; g->rb_rows2 = r2;
 		/* the promise the launcher checks at every launch (mlsd_gemm fails if its tile / epilogue no longer writes these blocks) */

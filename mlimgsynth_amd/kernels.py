@@ -20,7 +20,8 @@ class GemmArgs(ctypes.Structure):
                 ("ln_y16", vp), ("ldln", ctypes.c_int64), ("ln_gamma", vp), ("ln_beta", vp), ("ln_eps", ctypes.c_float), ("ln_ws", vp), ("ln_cnt", vp), ("ln_slot", c_int),
                 ("gn_y16", vp), ("gn_ldy", ctypes.c_int64), ("gn_gamma", vp), ("gn_beta", vp), ("gn_eps", ctypes.c_float), ("gn_groups", c_int), ("gn_hw", c_int),
                 ("gn_silu", c_int),
-                ("xa_k", vp), ("xa_ldk", c_i64), ("xa_vt", vp), ("xa_out", vp), ("xa_ldo", c_i64), ("xa_Tq", c_int), ("xa_Tk", c_int)]
+                ("xa_k", vp), ("xa_ldk", c_i64), ("xa_vt", vp), ("xa_out", vp), ("xa_ldo", c_i64), ("xa_Tq", c_int), ("xa_Tk", c_int),
+                ("colstats_shift", c_int)]
 
 
 class AttnArgs(ctypes.Structure):
@@ -32,7 +33,8 @@ class AttnArgs(ctypes.Structure):
 class GnArgs(ctypes.Structure):
     _fields_ = [("x1", vp), ("x2", vp), ("ld1", c_i64), ("ld2", c_i64), ("C1", c_int), ("C2", c_int),
                 ("n_img", c_int), ("HW", c_int), ("n_grp", c_int), ("eps", c_f), ("gamma", vp), ("beta", vp),
-                ("silu", c_int), ("y16", vp), ("raw16", vp), ("ws", vp), ("cs1", vp), ("cs2", vp), ("rb_rows1", c_int), ("rb_rows2", c_int)]
+                ("silu", c_int), ("y16", vp), ("raw16", vp), ("ws", vp), ("cs1", vp), ("cs2", vp), ("rb_rows1", c_int), ("rb_rows2", c_int),
+                ("cs_shifted", c_int)]
 
 
 def gemm(args, stream=None):

@@ -60,11 +60,13 @@ int unet_denoise_run(UnetState* S, const LocalTensor* x, const LocalTensor* cond
 /* builds the batch-N graph on C (prefix "unet"); weights are loaded afterwards with
  * mlctx_params_synth / mlctx_param_set */
 int unet_denoise_init_n(UnetState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch);
+/* the same with a context of n_ctx_tok rows (77 x W, windowed prompt; 0 = 77): input "c" is [n_ctx, n_ctx_tok, N] */
+int unet_denoise_init_nc(UnetState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch, int n_ctx_tok);
 /* second half of the init: records the graph and calls mlctx_prep (split so that the x input can first be
  * bound to a device-resident latent with mlctx_input_bind) */
 int unet_denoise_build(UnetState* S);
 /* host-boundary evaluation (tests, drop-in for src/unet.c:460-498 with a batch): x [N][4][lh][lw] NCHW,
- * cond [N][77][n_ctx], label [N][adm] or NULL, sigma[N] -> dx like x.  Applies c_in, sigma->t, v-param. */
+ * cond [N][77][n_ctx] (N x the plan's n_ctx_tok rows), label [N][adm] or NULL, sigma[N] -> dx like x.  Applies c_in, sigma->t, v-param. */
 int unet_denoise_run_n(UnetState* S, const float* x, const float* cond, const float* label,
 	const float* sigma, float* dx);
 
@@ -168,6 +170,23 @@ int mlis_amd_textcond_encode_pair(MLIS_AmdTextCond* T, const int32_t* toks, int 
 const void* mlis_amd_cond_device(MLIS_AmdCtx* S, int what);   /* the plan's conditioning inputs (0: cond, 1: label), read-only */
 int mlis_amd_textcond_apply(MLIS_AmdTextCond* T, MLIS_AmdCtx* E, const int32_t* toks, int n_tok, const int32_t* neg, int n_neg);
 
+/* Prompts longer than 75 tokens: the token list is cut, in order, into WINDOWS of 75 tokens (the last one holds the rest; no
+ * comma backtracking, no BREAK keyword).  Each window is encoded as its own 77-token CLIP sequence (BOS, its tokens, EOS,
+ * padding) and the windows' embeddings are concatenated along the token axis: [77 W][n_ctx].  A prompt of <= 75 tokens is W = 1
+ * and encodes exactly as the functions above. */
+#define MLIS_AMD_MAX_WINDOWS 4
+#define MLIS_AMD_WINDOW_TOKENS 75
+/* the split of n_tok tokens: returns W (1 for an empty prompt) and fills start[W], len[W] (either may be NULL); -1 above 300 tokens */
+int mlis_amd_prompt_windows(int n_tok, int* start, int* len);
+int mlis_amd_n_ctx_tok(const MLIS_AmdCtx* S);        /* context rows the engine's UNet plan was built for (77 W) */
+/* windowed encodings; they return W.  cond [77 W][n_ctx] (the caller sizes it with mlis_amd_prompt_windows), label [n_label] from
+ * window 0 at its EOS without weights; weights (emphasis, may be NULL) scale rows 1..len of each window.  The pair pads the
+ * side with fewer windows to the other's W with encodings of the empty window; cond and ncond then both hold [77 W][n_ctx].
+ * An empty SDXL negative prompt gives ncond = 0 over all 77 W rows (as mlis_amd_textcond_encode_pair). */
+int mlis_amd_textcond_encode_ex(MLIS_AmdTextCond* T, const int32_t* toks, const float* weights, int n_tok, float* cond, float* label);
+int mlis_amd_textcond_encode_pair_ex(MLIS_AmdTextCond* T, const int32_t* toks, const float* w, int n_tok,
+	const int32_t* neg, const float* nw, int n_neg, float* cond, float* label, float* ncond, float* nlabel);
+
 /* ---- CLIP BPE tokenizer (host).  Replaces clip_tokenize and helpers, src/clip.c:59-278 (public entry
  * mlis_text_tokenize, include/mlimgsynth.h); pinned by the 14 KATs of src/test_text_tokenize_clip.c:41-66.
  * The merge table is run-time data here (the reference compiles src/clip_merges.c.h in): id pairs in rank order
@@ -261,6 +280,7 @@ typedef struct {
 	int unet_split;          /* > 0: the UNet's weights are STREAMED (the reference's --unet-split / MLIS_OPT_UNET_SPLIT, src/unet.c:390-458): master copy in pinned host
 	                          * memory, three to five device slabs (3 for SDXL) of `unet_split` MiB each (1 = the default 512 MiB: 1.5 GiB of slabs + 0.68 GB of resident step-invariant
 	                          * weights instead of 4.8 GiB) filled under the launches; excludes use_hipgraph */
+	int n_ctx_tok;           /* rows of the text context: 77 x W for a prompt of W 75-token windows (W <= 4); 0 = 77 */
 } MLIS_AmdConfig;
 
 /* progress callback (MLIS_Callback, include/mlimgsynth.h:405): called after every COMPLETED step (the stream is
@@ -269,7 +289,7 @@ typedef int (*mlis_amd_progress_fn)(void* user, int step, int n_step, int nfe);
 
 MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream);
 void mlis_amd_destroy(MLIS_AmdCtx* S);
-/* conditioning for the whole batch (shared prompt, as generate.sh): cond/uncond [77][n_ctx] fp32 host,
+/* conditioning for the whole batch (shared prompt, as generate.sh): cond/uncond [n_ctx_tok][n_ctx] fp32 host (77 rows unless the config says otherwise),
  * label/unlabel [adm] or NULL */
 int mlis_amd_set_cond(MLIS_AmdCtx* S, const float* cond, const float* label, const float* uncond, const float* unlabel);
 /* device-resident variant used after an RCCL broadcast: pointers are DEVICE pointers of the same shapes */

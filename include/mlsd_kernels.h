@@ -237,6 +237,13 @@ typedef struct mlsd_attn_args {
 } mlsd_attn_args;
 
 int mlsd_attention(const mlsd_attn_args* a, void* stream);
+/* The same attention over 96 < Tk <= 320 keys (cross attention of a windowed text context, 77 x W rows), no causal mask, d_head in
+ * {32,40,64,80,160}: groups of up to 96 keys in one pass each, merged by an online softmax (attn_ctx_kernel).  q, k, v 16-byte aligned with
+ * ldq / ldk / ldv and their batch strides multiples of 8; out 8-byte aligned with ldo and bso multiples of 4.
+ * Outside that range: an error.  mlsd_attention's dispatch is not affected. */
+int mlsd_attention_ctx(const mlsd_attn_args* a, void* stream);
+int mlsd_attention_ctx_takes(const mlsd_attn_args* a);   /* 1 where the plan runs a Tk > 96 cross attention on mlsd_attention_ctx (measured not slower than mlsd_attention) */
+void mlsd_attention_ctx_mode(int mode);    /* A-B timing: 0 (default) = keys resident in LDS where they take <= 64 KiB, else one 96-key slot restaged per group; 1 = the slot always */
 /* diagnostics / A-B timing: 1 = the d_head 64 problems also run on the general kernel instead of the 64-rows-per-wave one */
 void mlsd_attention_force_old(int on);
 void mlsd_attention_x2_min_tq(int tq);     /* smallest Tq (multiple of 256) the 64-rows-per-wave kernel takes (default 2048) */

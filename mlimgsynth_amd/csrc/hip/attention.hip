@@ -1060,6 +1060,208 @@ __global__ __launch_bounds__(256, WPS) void attn_tk96_kernel(const AttnP p, cons
 }
 
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 96 < Tk <= 320, no causal mask (cross attention over a windowed text context: 154, 231, 308 keys): attn_tk96_kernel's one
+//   pass per GROUP of up to 96 keys, the groups merged with an online softmax (running max / sum in fp32, ONE rescale of the O
+//   accumulators per group instead of per 64-key tile).  A group is what attn_tk96_kernel does for the whole key set: S^T = K.Q^T
+//   over its 32-key sub-tiles, the group's row maximum, exp2, O^T += V^T.P over its 16-key steps; Q stays in registers across
+//   the groups, the next block's Q is fetched after the last group's QK^T.
+//   RES (d_head <= 80): the whole key set (rows past Tk: duplicates of the last key, masked) is staged ONCE per workgroup in
+//     dynamic LDS, ceil32(Tk) x (KSTR + VSTR) bytes (320 keys: 95 / 105 / 115 KiB at d 40 / 64 / 80).
+//   !RES (d_head 160, 320 keys would need 205 KiB): one 96-key slot (63 KiB), restaged per group and query block between two
+//     barriers; the query blocks per workgroup are walked in lockstep so that every wave reaches every barrier.
+template <int DH, int WPS, bool RES>
+__global__ __launch_bounds__(256, WPS) void attn_ctx_kernel(const AttnP p, const int QB)
+{
+    constexpr int DQK = (DH + 15) / 16 * 16, NKS = DQK / 16, NDV = (DH + 31) / 32;
+    constexpr int KSTR = DQK * 2 + 16;             // bytes; conflict-free b128 row reads (see attn_kernel)
+    constexpr int VSTR = ((NDV & 1) ? NDV : NDV + 1) * 64;
+    constexpr int CH = DH / 8, NK = 96;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int Tk = p.Tk, NG = (Tk + NK - 1) / NK;
+    const int nrow_lds = RES ? ((Tk + 31) & ~31) : NK;
+    unsigned char* Ks = smem;
+    unsigned char* Vs = smem + nrow_lds * KSTR;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 31, lh = lane >> 5;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;         // all blocks of one (batch, head) group on one XCD (see attn_kernel)
+    const int gk = slot / p.nq, qb = slot - gk * p.nq;
+    const int grp = gk * 8 + xcd;
+    if (grp >= p.G) return;
+    const int head = grp % p.n_head, b = grp / p.n_head;
+    const _Float16* Qg = p.q + (long)b * p.bsq + (long)head * DH;
+    const _Float16* Kg = p.k + (long)b * p.bsk + (long)head * DH;
+    const _Float16* Vg = p.v + (long)b * p.bsv + (long)head * DH;
+
+    auto load_q = [&](f16x8 (&qf)[NKS], int qrow) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const int c = 16 * ks + 8 * lh;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (qrow < p.Tq && c < DH) v = *reinterpret_cast<const uint4*>(Qg + (long)qrow * p.ldq + c);
+            qf[ks] = __builtin_bit_cast(f16x8, v);
+        }
+    };
+    // keys k0 .. k0 + nrow - 1 (global rows >= Tk: duplicates of the last key) -> LDS rows r0 ..
+    auto stage = [&](int k0, int nrow, int r0) __attribute__((always_inline)) {
+        for (int idx = tid; idx < nrow * CH; idx += 256) {
+            const int row = idx / CH, ch = idx - row * CH;
+            const long r = min(k0 + row, Tk - 1);
+            const uint4 a = *reinterpret_cast<const uint4*>(Kg + r * p.ldk + ch * 8);
+            const uint4 c = *reinterpret_cast<const uint4*>(Vg + r * p.ldv + ch * 8);
+            *reinterpret_cast<uint4*>(Ks + (r0 + row) * KSTR + ch * 16) = a;
+            *reinterpret_cast<uint4*>(Vs + (r0 + row) * VSTR + ch * 16) = c;
+        }
+    };
+    const int q_first = qb * QB * 128 + wave * 32 + lr;
+    f16x8 qf[NKS];
+    load_q(qf, q_first);                                             // in flight while the keys are staged
+
+    // padding columns (d_head not a multiple of 16 / 32) zeroed once: the staging never writes them
+    if constexpr (DQK != DH || NDV * 32 != DH) {
+        for (int i = tid * 16; i < nrow_lds * (KSTR + VSTR); i += 256 * 16) *reinterpret_cast<uint4*>(smem + i) = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+    }
+    if constexpr (RES) {
+        stage(0, nrow_lds, 0);
+        __syncthreads();
+    }
+
+    const int tg = lane >> 4, ti = lane & 15;                        // transposed-read lane pattern (see attn_kernel)
+    const int tr_row = 4 * (tg >> 1) + (ti >> 2);
+    const int tr_col = 16 * (tg & 1) + 4 * (ti & 3);
+
+    for (int it = 0; it < QB; ++it) {
+        if (qb * QB * 128 + it * 128 >= p.Tq) break;                 // workgroup-uniform: no row of the block is left
+        const int qrow = q_first + it * 128;
+        const bool act = qrow - lr < p.Tq;                           // wave-uniform: the wave's 32 rows hold at least one query
+        if (RES && !act) break;
+        float m_run = -1.0e30f, l_run = 0.f;                         // running maximum (score units) / this lane's partial sum
+        f32x16 oacc[NDV];
+#pragma unroll
+        for (int d = 0; d < NDV; ++d)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) oacc[d][e] = 0.f;
+        for (int g = 0; g < NG; ++g) {
+            const int k0 = g * NK, tkg = min(NK, Tk - k0);           // the group's keys: k0 .. k0 + tkg - 1
+            if constexpr (!RES) {
+                __syncthreads();                                     // the slot's last readers are done
+                stage(k0, (tkg + 31) & ~31, 0);
+                __syncthreads();
+            }
+            if (!act) continue;
+            const unsigned char* Kb = Ks + (RES ? k0 : 0) * KSTR;
+            const unsigned char* Vb = Vs + (RES ? k0 : 0) * VSTR;
+            // ---- S^T = K . Q^T for the group's sub-tiles that hold keys
+            f32x16 sacc[3];
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt) {
+                f32x16 r = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (32 * kt < tkg) {
+#pragma unroll
+                    for (int ks = 0; ks < NKS; ++ks) {
+                        const f16x8 kf = *reinterpret_cast<const f16x8*>(Kb + (32 * kt + lr) * KSTR + (16 * ks + 8 * lh) * 2);
+                        r = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], r, 0, 0, 0);
+                    }
+                }
+                sacc[kt] = r;
+            }
+            if (g == NG - 1 && it + 1 < QB) load_q(qf, qrow + 128);  // next block's Q: lands under the last group's softmax / P.V
+            // ---- mask the clamped duplicates, the group's row maximum, merge with the running one
+            float mx = -1.0e30f;
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt) {
+                if (32 * kt < tkg) {
+                    if (32 * kt + 32 > tkg) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e)
+                            if (32 * kt + (e & 3) + 8 * (e >> 2) + 4 * lh >= tkg) sacc[kt][e] = -1.0e30f;
+                    }
+#pragma unroll
+                    for (int e = 0; e < 16; e += 2) mx = fmaxf(mx, fmaxf(sacc[kt][e], sacc[kt][e + 1]));
+                }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, mx);
+            if (g) {                                                 // one rescale per group (the first has nothing to rescale)
+                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.sc);
+                l_run *= alpha;
+#pragma unroll
+                for (int d = 0; d < NDV; ++d) oacc[d] *= alpha;
+            }
+            m_run = m_new;
+            const float msc = -m_new * p.sc;
+            f32x2 vsum = {0.f, 0.f};
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                         // register quad j: keys 32 kt + 8 j + {0..3} + 4 lh
+                    if (32 * kt + 16 * (j >> 1) < tkg) {             // (whole 16-key steps: what the P.V MFMAs below consume; masked scores give P = 0)
+#pragma unroll
+                        for (int e = 4 * j; e < 4 * j + 4; e += 2) {
+                            const f32x2 r = exp2_pair(sacc[kt][e], sacc[kt][e + 1], p.sc, msc);
+                            sacc[kt][e] = r.x; sacc[kt][e + 1] = r.y;
+                            vsum += r;
+                        }
+                    }
+                }
+            }
+            l_run += vsum.x + vsum.y;
+            // ---- O^T += V^T . P over the group's 16-key steps that hold keys
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int kb = 32 * kt + 16 * s;
+                    if (kb < tkg) {
+                        f16x8 pf;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) pf[j] = (_Float16)sacc[kt][8 * s + j];
+#pragma unroll
+                        for (int d = 0; d < NDV; ++d) {
+                            const unsigned char* a0 = Vb + (kb + tr_row) * VSTR + (32 * d + tr_col) * 2;
+                            union { h16x4 h[2]; f16x8 f; } vf;
+                            vf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h16x4*)a0);
+                            vf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h16x4*)(a0 + 8 * VSTR));
+                            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf.f, pf, oacc[d], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        if (!act) continue;
+        // ---- O = O^T / l, heads merged (as attn_tk96_kernel's epilogue)
+        const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
+        if (qrow < p.Tq) {
+            _Float16* og = p.o + (long)b * p.bso + (long)qrow * p.ldo + (long)head * DH;
+            auto piece = [&](int d, int eg) __attribute__((always_inline)) {
+                const f16x4 h = {(_Float16)(oacc[d][4 * eg + 0] * inv), (_Float16)(oacc[d][4 * eg + 1] * inv),
+                                 (_Float16)(oacc[d][4 * eg + 2] * inv), (_Float16)(oacc[d][4 * eg + 3] * inv)};
+                return __builtin_bit_cast(u32x2, h);
+            };
+#pragma unroll
+            for (int d = 0; d < NDV; ++d)
+#pragma unroll
+                for (int eg = 0; eg < 4; eg += 2) {
+                    if (p.wide_o && 32 * d + 8 * eg + 16 <= DH) {
+                        u32x2 a = piece(d, eg), c = piece(d, eg + 1);
+                        const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
+                        const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
+                        *reinterpret_cast<u32x4*>(og + 32 * d + 8 * eg + 8 * lh) = u32x4{r0[0], r1[0], r0[1], r1[1]};
+                    } else {
+#pragma unroll
+                        for (int e2 = eg; e2 < eg + 2; ++e2) {
+                            const int dbase = 32 * d + 8 * e2 + 4 * lh;
+                            if (dbase < DH) *reinterpret_cast<u32x2*>(og + dbase) = piece(d, e2);
+                        }
+                    }
+                }
+        }
+    }
+}
+
+
 #ifdef MLSD_GEMM_EXPERIMENTS   /* built, correct and SLOWER than the tile-loop kernels (profiles/NOTES.md "ping-pong attention"): kept reproducible, not in the product build */
 // ---------------------------------------------------------------------------------------------------------------------
 // d_head = 64, no causal mask: the PING-PONG kernel.
@@ -1500,6 +1702,36 @@ int launch_attn_tk96(const mlsd_attn_args* a, hipStream_t st)
     return mlsd_check_launch("attn_tk96_kernel");
 }
 
+// 96 < Tk <= 320 (mlsd_attention_ctx): attn_ctx_kernel, workgroups as launch_attn_tk96 chooses them
+int g_attn_ctx_mode = 0;    // mlsd_attention_ctx: 0 = all keys resident in LDS where they take <= 64 KiB (2 workgroups per CU), else one restaged 96-key slot; 1 = the slot always (A/B timing)
+// (profiles/long_prompt_kernels.txt: resident at 105 KiB -- d 64, 308 keys, one workgroup per CU -- was 1.45 x the slot's time)
+
+template <int DH, bool RES>
+int launch_attn_ctx(const mlsd_attn_args* a, hipStream_t st)
+{
+    constexpr int DQK = (DH + 15) / 16 * 16, NDV = (DH + 31) / 32;
+    constexpr int ROWB = DQK * 2 + 16 + ((NDV & 1) ? NDV : NDV + 1) * 64;    // KSTR + VSTR of the kernel
+    AttnP p; p.tbuf = nullptr;
+    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
+    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
+    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
+    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = 0;
+    p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
+    p.G = a->n_head * a->n_batch;
+    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
+    const int G8 = 8 * ((p.G + 7) / 8), nblk128 = (a->Tq + 127) / 128;
+    int QB = 8;
+    while (QB > 1 && (long)G8 * ((nblk128 + QB - 1) / QB) < 512) QB >>= 1;
+    p.nq = (nblk128 + QB - 1) / QB;
+    const dim3 grid((unsigned)(G8 * p.nq));
+    const size_t lds = (size_t)(RES ? (a->Tk + 31) & ~31 : 96) * ROWB;
+    auto kfn = attn_ctx_kernel<DH, (DH == 64 || DH == 80 ? 3 : 2), RES>;     // (d 40 at 3 waves per SIMD: 20 bytes of scratch)
+    static bool lds_set = false;        // the largest key set (320 rows) once per instantiation
+    if (!lds_set) { MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((RES ? 320 : 96) * ROWB))); lds_set = true; }
+    hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, p, QB);
+    return mlsd_check_launch("attn_ctx_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1544,6 +1776,37 @@ MLSD_API int mlsd_attention(const mlsd_attn_args* a, void* stream)
     }
 }
 
+MLSD_API int mlsd_attention_ctx(const mlsd_attn_args* a, void* stream)
+{
+    if (!a || !a->q || !a->k || !a->v || !a->out) return mlsd_set_error(-1, "mlsd_attention_ctx: null operand");
+    if (a->Tq <= 0 || a->n_batch <= 0 || a->n_head <= 0) return mlsd_set_error(-1, "mlsd_attention_ctx: empty problem");
+    if (a->Tk <= 96 || a->Tk > 320) return mlsd_set_error(-1, "mlsd_attention_ctx: Tk %d outside 97..320", a->Tk);
+    if (a->causal) return mlsd_set_error(-1, "mlsd_attention_ctx: no causal mask");
+    if ((a->ldq & 7) || (a->ldk & 7) || (a->ldv & 7) || (a->ldo & 3)) return mlsd_set_error(-1, "mlsd_attention_ctx: strides must be multiples of 8");
+    if ((a->bsq & 7) || (a->bsk & 7) || (a->bsv & 7) || (a->bso & 3) || (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) || ((uintptr_t)a->out & 7))
+        return mlsd_set_error(-1, "mlsd_attention_ctx: misaligned operand");
+    hipStream_t st = (hipStream_t)stream;
+    const int dqk = (a->d_head + 15) / 16 * 16, ndv = (a->d_head + 31) / 32;
+    const long rowb = dqk * 2 + 16 + ((ndv & 1) ? ndv : ndv + 1) * 64;
+    const bool slot = g_attn_ctx_mode == 1 || (long)((a->Tk + 31) & ~31) * rowb > 65536;
+    switch (a->d_head) {
+    case 32: return slot ? launch_attn_ctx<32, false>(a, st) : launch_attn_ctx<32, true>(a, st);      /* (the test models' towers) */
+    case 40: return slot ? launch_attn_ctx<40, false>(a, st) : launch_attn_ctx<40, true>(a, st);
+    case 64: return slot ? launch_attn_ctx<64, false>(a, st) : launch_attn_ctx<64, true>(a, st);
+    case 80: return slot ? launch_attn_ctx<80, false>(a, st) : launch_attn_ctx<80, true>(a, st);
+    case 160: return launch_attn_ctx<160, false>(a, st);      /* (ceil32(Tk) x 656 B > 64 KiB for every Tk > 96) */
+    default: return mlsd_set_error(-1, "mlsd_attention_ctx: unsupported d_head %d (supported: 32,40,64,80,160)", a->d_head);
+    }
+}
+
+MLSD_API void mlsd_attention_ctx_mode(int mode) { g_attn_ctx_mode = mode == 1; }
+/* the plan's choice for a cross attention over Tk > 96 context rows: mlsd_attention_ctx where it measured at least even with the
+ * tile loop (profiles/long_prompt_kernels.txt: Tk <= 160 at d_head 40 / 80 / 160, 0.91 - 1.00 x), mlsd_attention elsewhere (the tile
+ * loop measured 1.1 - 1.4 x faster from 231 keys on and 1.02 - 1.08 x at d_head 64, 154 keys) */
+MLSD_API int mlsd_attention_ctx_takes(const mlsd_attn_args* a)
+{
+    return a && !a->causal && a->Tk > 96 && a->Tk <= 160 && (a->d_head == 40 || a->d_head == 80 || a->d_head == 160);
+}
 MLSD_API void mlsd_attention_force_old(int on) { g_attn_force_old = on; }
 MLSD_API void mlsd_attention_x2_min_tq(int tq) { g_attn_x2_min_tq = tq; }
 MLSD_API void mlsd_attention_sp(int mode) { g_attn_sp = (mode >= 0 && mode <= 2) ? mode : -1; }

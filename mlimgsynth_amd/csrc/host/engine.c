@@ -145,6 +145,8 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream)
 	if (S->c.n_step < 1) S->c.n_step = 20;
 	if (S->c.n_step >= MAX_STEPS) { fail("too many steps (max 1000)"); goto err; }
 	if (S->c.n_batch < 1) S->c.n_batch = 1;
+	if (!S->c.n_ctx_tok) S->c.n_ctx_tok = 77;
+	if (S->c.n_ctx_tok < 0 || S->c.n_ctx_tok % 77 || S->c.n_ctx_tok > 77 * MLIS_AMD_MAX_WINDOWS) { mlsd_set_error(-1, "n_ctx_tok %d: 77 x W context rows, W <= %d", S->c.n_ctx_tok, MLIS_AMD_MAX_WINDOWS); goto err; }
 	if (S->c.n_batch > MAX_BATCH) { fail("n_batch > 64 not supported"); goto err; }
 	if (!(S->c.cfg_scale > 0)) S->c.cfg_scale = 7;          /* default cfg 7, src/mlimgsynth.c:474 */
 	if (!S->c.sched) S->c.sched = DNSAMP_SCHED_UNIFORM;
@@ -177,7 +179,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream)
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
-	if (unet_denoise_init_n(&S->unet, S->unet_ctx, &S->unet_p, S->lw, S->lh, N) < 0) goto err;
+	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, S->lw, S->lh, N, S->c.n_ctx_tok) < 0) goto err;
 	if (mlctx_input_bind(S->unet.t_x, S->d_xin, B, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
 	if (unet_denoise_build(&S->unet) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
@@ -237,7 +239,7 @@ static int fill_cond(MLIS_AmdCtx* S, MLTensor* t, const void* a, const void* b, 
 static int set_cond(MLIS_AmdCtx* S, const void* cond, const void* label, const void* uncond, const void* unlabel, int kind)
 {
 	const UnetParams *P = &S->unet_p;
-	if (fill_cond(S, S->unet.t_c, cond, uncond, (size_t)77*P->n_ctx*4, kind) < 0) return -1;
+	if (fill_cond(S, S->unet.t_c, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
 	if (P->ch_adm_in && fill_cond(S, S->unet.t_l, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
 	if (mlsd_stream_sync(S->stream)) return -1;
 	S->cond_set = 1;
@@ -260,7 +262,7 @@ MLB_API int mlis_amd_set_cond_device(MLIS_AmdCtx* S, const void* cond, const voi
 MLB_API int mlis_amd_bcast_cond(MLIS_AmdCtx* S, void* comm, int root)
 {
 	const UnetParams *P = &S->unet_p;
-	if (mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_c), (size_t)S->N*77*P->n_ctx*4, root, S->stream)) return -1;
+	if (mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_c), (size_t)S->N*S->c.n_ctx_tok*P->n_ctx*4, root, S->stream)) return -1;
 	if (P->ch_adm_in && mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_l), (size_t)S->N*P->ch_adm_in*4, root, S->stream)) return -1;
 	S->cond_set = 1;
 	return 1;
@@ -274,7 +276,7 @@ MLB_API int mlis_amd_gather_results(MLIS_AmdCtx* S, void* comm, int what, void* 
 	return mlsd_rccl_all_gather(comm, what ? (void*)S->d_img : (void*)S->d_x, recv_dev, nb, S->stream) ? -1 : 1;
 }
 
-/* read-only view of the conditioning the UNet plan will use (what = 0: cond [N][77][n_ctx] fp32, 1: label [N][adm]): tests */
+/* read-only view of the conditioning the UNet plan will use (what = 0: cond [N][n_ctx_tok][n_ctx] fp32, 1: label [N][adm]): tests */
 MLB_API const void* mlis_amd_cond_device(MLIS_AmdCtx* S, int what)
 {
 	MLTensor *t = what ? S->unet.t_l : S->unet.t_c;
@@ -914,6 +916,7 @@ MLB_API MLCtx* mlis_amd_decoder_ctx(MLIS_AmdCtx* S) { return S->dec_ctx; }
 MLB_API MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S) { return S->enc_ctx; }
 MLB_API float mlis_amd_last_unet_ms(MLIS_AmdCtx* S) { return S->last_unet_ms; }
 MLB_API int mlis_amd_last_nfe(MLIS_AmdCtx* S) { return S->last_nfe; }
+MLB_API int mlis_amd_n_ctx_tok(const MLIS_AmdCtx* S) { return S ? S->c.n_ctx_tok : -1; }     /* context rows of the UNet plan: 77 W */
 MLB_API int mlis_amd_last_n_step(MLIS_AmdCtx* S) { return S->last_n_step; }
 
 MLB_API int mlis_amd_info(MLIS_AmdCtx* S, double* unet_flops, double* dec_flops, int* unet_ops, size_t* mem_params, size_t* mem_compute)

@@ -645,6 +645,7 @@ static int run_op(MLCtx* C, MLOp* op)
 	switch (op->kind) {
 	case OP_GEMM: return mlsd_gemm(&op->u.gemm, st);
 	case OP_ATTN: return mlsd_attention(&op->u.attn, st);
+	case OP_ATTN_CTX: return mlsd_attention_ctx(&op->u.attn, st);   /* cross attention over more than 96 context rows (windowed prompt) */
 	case OP_GN:   if (op->fused) return 0;                    /* its producer's reduce pass ends with it (wire_gn_fold) */
 	              return mlsd_groupnorm(&op->u.gn, st);
 	case OP_LN:   if (op->fused) return 0;                    /* its producer ends with it (wire_ln_fold) */
@@ -1057,7 +1058,7 @@ static int op_outputs(const MLOp* o, const void* out[3])
 		if (o->u.gemm.gn_y16 && n < 3) out[n++] = o->u.gemm.gn_y16;
 		if (o->u.gemm.xa_k && n < 3) out[n++] = o->u.gemm.xa_out;
 		break;
-	case OP_ATTN: out[n++] = o->u.attn.out; break;
+	case OP_ATTN: case OP_ATTN_CTX: out[n++] = o->u.attn.out; break;
 	case OP_GN: out[n++] = o->u.gn.y16; if (o->u.gn.raw16) out[n++] = o->u.gn.raw16; break;
 	case OP_LN: if (o->u.ln.y16) out[n++] = o->u.ln.y16; if (o->u.ln.y32) out[n++] = o->u.ln.y32; break;
 	case OP_NCHW2NHWC: out[n++] = o->u.n2h.dst; break;
@@ -1658,7 +1659,7 @@ MLB_API int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flo
 				snprintf(buf + l, sizeof(buf) - l, "%dx%dx%d%s%s", g->M, g->N, g->K, g->C32 ? " f32" : "", g->resid ? "+res" : "");
 			}
 			*label = buf;
-		} else if (op->kind == OP_ATTN && (C->flags & MLB_F_OPSHAPES)) {
+		} else if ((op->kind == OP_ATTN || op->kind == OP_ATTN_CTX) && (C->flags & MLB_F_OPSHAPES)) {
 			const mlsd_attn_args *a = &op->u.attn;
 			snprintf(buf, sizeof(buf), "%s b%d h%d d%d %dx%d", op->label, a->n_batch, a->n_head, a->d_head, a->Tq, a->Tk);
 			*label = buf;
@@ -1695,7 +1696,7 @@ MLB_API double mlctx_op_bytes(const MLCtx* C, int i)
 		if (g->xa_k) b += 2.0 * g->M * nout + 2.0 * 2.0 * (g->M / g->xa_Tq) * (double)g->xa_Tk * g->N;      /* the attention's output + the images' K and V */
 		return b;
 	}
-	case OP_ATTN: {
+	case OP_ATTN: case OP_ATTN_CTX: {
 		const mlsd_attn_args *a = &op->u.attn;
 		const double D = (double)a->n_head * a->d_head;
 		return 2.0 * a->n_batch * D * (2.0 * a->Tq + 2.0 * a->Tk);

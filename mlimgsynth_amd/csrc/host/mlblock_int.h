@@ -12,7 +12,7 @@ int mlsd_set_error(int code, const char* fmt, ...);
 
 typedef enum {
 	OP_GEMM, OP_ATTN, OP_GN, OP_LN, OP_NCHW2NHWC, OP_NHWC2NCHW, OP_TEMB, OP_ACT, OP_CLIP_EMBED, OP_SOFTMAX,
-	OP_COPY_F32, OP_XA_VT,
+	OP_COPY_F32, OP_XA_VT, OP_ATTN_CTX,
 } MLOpKind;
 
 typedef struct MLOp {

@@ -318,13 +318,16 @@ MLB_API MLTensor* mlb_feed_forward(MLCtx* C, MLTensor* x, int d_out, int mult) {
 
 /* ------------------------------------------------------------------ multi-head attention (src/mlblock_nn.c:190-231) */
 static void record_attn(MLCtx* C, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-	void* out, int64_t ldo, int nb, int Tq, int Tk, int n_head, int d_head, int causal)
+	void* out, int64_t ldo, int nb, int Tq, int Tk, int n_head, int d_head, int causal, int cross)
 {
 	MLOp *op = mlctx_op_new(C, OP_ATTN, "attention");
 	mlsd_attn_args *a = &op->u.attn;
 	a->q = q; a->k = k; a->v = v; a->out = out; a->ldq = ldq; a->ldk = ldk; a->ldv = ldv; a->ldo = ldo;
 	a->bsq = (int64_t)Tq*ldq; a->bsk = (int64_t)Tk*ldk; a->bsv = (int64_t)Tk*ldv; a->bso = (int64_t)Tq*ldo;
 	a->n_batch = nb; a->n_head = n_head; a->d_head = d_head; a->Tq = Tq; a->Tk = Tk; a->causal = causal;
+	/* cross attention over a windowed text context (77 x W > 96 rows): the key-group kernel (mlsd_attention_ctx) where it measured
+	 * at least even with the tile loop, the tile loop of mlsd_attention elsewhere; 77-row contexts as before */
+	if (cross && Tk > 96 && mlsd_attention_ctx_takes(a)) op->kind = OP_ATTN_CTX;
 	op->flops = 4.0 * nb * (double)Tq * Tk * n_head * d_head;
 }
 
@@ -400,7 +403,7 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 		if (!qkv) return NULL;
 		const char *p = (const char*)mlt_need16(C, qkv);
 		record_attn(C, p, 3*d_embed, p + (size_t)d_embed*2, 3*d_embed, p + (size_t)d_embed*4, 3*d_embed, a->d16, d_embed,
-			nb, Tq, Tk, n_head, d_head, mask);
+			nb, Tq, Tk, n_head, d_head, mask, 0);
 		mlb_release(C, qkv);
 	} else {
 		if (k != v) { mlctx_fail(C, "attention: k and v must share their input"); return NULL; }
@@ -444,7 +447,7 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 			if (!qo) {
 				const char *pq = (const char*)mlt_need16(C, qp);
 				record_attn(C, pq, d_embed, pk, C->kvb.n_total, pk + (size_t)d_embed*2, C->kvb.n_total, a->d16, d_embed,
-					nb, Tq, Tk, n_head, d_head, mask);
+					nb, Tq, Tk, n_head, d_head, mask, 1);
 			}
 			mlb_release(C, qp);
 		} else {
@@ -452,7 +455,7 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 			if (!kv) return NULL;
 			const char *pq = (const char*)mlt_need16(C, qp), *pk = (const char*)mlt_need16(C, kv);
 			record_attn(C, pq, d_embed, pk, 2*d_embed, pk + (size_t)d_embed*2, 2*d_embed, a->d16, d_embed,
-				nb, Tq, Tk, n_head, d_head, mask);
+				nb, Tq, Tk, n_head, d_head, mask, 1);
 			mlb_release(C, qp); mlb_release(C, kv);
 		}
 	}

@@ -51,6 +51,7 @@ struct MLIS_Ctx {
 	uint64_t synth_seed; int synth;
 	MLTStore *ts, *ts_tae;
 	MLIS_AmdCtx* eng; char eng_key[96];
+	int ctx_tok;            /* rows of the conditioning the engine is built for: 77 W (windowed prompt); 0 = 77 */
 	MLIS_AmdTextCond* tc; char tc_key[64];
 	ClipTokenizer* tok;
 	MLIS_Tensor image, mask, latent, lmask, cond, label, ncond, nlabel, tmp[N_TMP_TENSORS];
@@ -644,8 +645,9 @@ static int sampler_defaults(MLIS_Ctx* S, int* n_step, int* method, int* sched)
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
+	const int ctx_tok = S->ctx_tok > 0 ? S->ctx_tok : 77;
 	char key[96];
-	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT));
+	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	if (!S->eng || strcmp(key, S->eng_key)) {
@@ -655,6 +657,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_ancestral = S->s_ancestral; c.sched = sched; c.use_tae = tae; c.weight_seed = S->synth_seed; c.method = method;
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
+		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
 		S->eng = mlis_amd_create(&c, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
@@ -789,16 +792,22 @@ static int text_cond_encode(MLIS_Ctx* S, int with_neg, int w, int h)
 	if ((n[0] = prompt_tokens(S, 0, &tok[0], &tw[0])) < 0) { r = n[0]; goto end; }
 	if (with_neg && (n[1] = prompt_tokens(S, 1, &tok[1], &tw[1])) < 0) { r = n[1]; goto end; }
 	if (textcond_get(S, w, h) < 0) goto end;
-	int n_ctx = 0, n_label = 0;
+	int n_ctx = 0, n_label = 0, W = 0;
 	mlis_amd_textcond_dims(S->tc, &n_ctx, &n_label);
-	mlis_tensor_resize(&S->cond, n_ctx, 77, 1, 1);
+	/* prompts of more than 75 tokens: 75-token windows, cond / ncond [n_ctx, 77 W] with the same W on both sides (CFG batches them) */
+	for (int p=0; p<1+!!with_neg; ++p) {
+		const int Wp = mlis_amd_prompt_windows(n[p], NULL, NULL);
+		if (Wp < 0) { r = api_error_lib(S, MLIS_E_UNKNOWN); goto end; }
+		if (Wp > W) W = Wp;
+	}
+	mlis_tensor_resize(&S->cond, n_ctx, 77 * W, 1, 1);
 	if (n_label) mlis_tensor_resize(&S->label, n_label, 1, 1, 1);
 	if (with_neg) {
-		mlis_tensor_resize(&S->ncond, n_ctx, 77, 1, 1);
+		mlis_tensor_resize(&S->ncond, n_ctx, 77 * W, 1, 1);
 		if (n_label) mlis_tensor_resize(&S->nlabel, n_label, 1, 1, 1);
-		r = mlis_amd_textcond_encode_pair_w(S->tc, tok[0], tw[0], n[0], tok[1], tw[1], n[1], S->cond.d, n_label ? S->label.d : NULL,
+		r = mlis_amd_textcond_encode_pair_ex(S->tc, tok[0], tw[0], n[0], tok[1], tw[1], n[1], S->cond.d, n_label ? S->label.d : NULL,
 			S->ncond.d, n_label ? S->nlabel.d : NULL);
-	} else r = mlis_amd_textcond_encode_w(S->tc, tok[0], tw[0], n[0], S->cond.d, n_label ? S->label.d : NULL);
+	} else r = mlis_amd_textcond_encode_ex(S->tc, tok[0], tw[0], n[0], S->cond.d, n_label ? S->label.d : NULL);
 	if (r < 0) r = api_error_lib(S, MLIS_E_UNKNOWN);
 end:
 	free(tok[0]); free(tw[0]); free(tok[1]); free(tw[1]);
@@ -953,26 +962,9 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	}
 	if (S->tuflags & MLIS_TUF_LATENT) { w = S->latent.n[0]; h = S->latent.n[1]; }
 	if (w < 1 || h < 1) return api_error(S, MLIS_E_OPT_VALUE, "image size not set");
-	if (engine_get(S, w, h) < 0) return -1;
-	if (S->tuflags & MLIS_TUF_LATENT) {
-		if (S->latent.n[2] != 4) return api_error(S, MLIS_E_UNKNOWN, "latent must have 4 channels");
-		const size_t per = (size_t)4*w*h;
-		float *l = (float*)malloc(per * B * 4);
-		for (int b=0;b<B;++b) memcpy(l + per*b, S->latent.d + (S->latent.n[3] == B ? per*b : 0), per*4);
-		r = mlis_amd_set_init_latent(S->eng, l);
-		free(l);
-		if (r < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
-	} else mlis_amd_set_init_latent(S->eng, NULL);
 	const int w_img = w * 8, h_img = h * 8;
 
-	/* mask -> latent mask (:1673-1686) */
-	if (S->tuflags & MLIS_TUF_MASK) { mlis_mask_encode(S, &S->mask, &S->lmask, 0); S->tuflags |= MLIS_TUF_LMASK; }
-	if ((S->tuflags & MLIS_TUF_LMASK) && tensor_good(&S->lmask)) {
-		if (S->lmask.n[0] != w || S->lmask.n[1] != h) return api_error(S, MLIS_E_IMAGE, "latent mask %dx%d does not match the latent %dx%d", S->lmask.n[0], S->lmask.n[1], w, h);
-		if (mlis_amd_set_lmask(S->eng, S->lmask.d) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
-	} else { mlis_amd_set_lmask(S->eng, NULL); if (!(S->tuflags & MLIS_TUF_LMASK)) mlis_tensor_free(&S->lmask); }
-
-	/* conditioning (:1688-1707) */
+	/* conditioning (:1688-1707), before the engine: its length (77 W rows) is part of the UNet plan */
 	if (!(S->tuflags & MLIS_TUF_CONDITIONING)) {
 		if ((r = text_cond_encode(S, S->cfg_scale > 1, w_img, h_img)) < 0) return r;
 		if (S->cfg_scale > 1) {
@@ -983,6 +975,32 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 		if ((r = progress(S, MLIS_STAGE_COND_ENCODE, 1, 1)) < 0) return r;
 	}
 	if (!tensor_good(&S->cond) || (S->cfg_scale > 1 && !tensor_good(&S->ncond))) return api_error(S, MLIS_E_UNKNOWN, "conditioning tensors are not set");
+	{
+		const int T = S->cond.n[1];
+		if (T < 77 || T % 77 || T > 77 * MLIS_AMD_MAX_WINDOWS)
+			return api_error(S, MLIS_E_UNKNOWN, "conditioning of %d tokens (77 x W, W <= %d)", T, MLIS_AMD_MAX_WINDOWS);
+		if (S->cfg_scale > 1 && S->ncond.n[1] != T)
+			return api_error(S, MLIS_E_UNKNOWN, "conditioning lengths differ: cond %d, ncond %d tokens", T, S->ncond.n[1]);
+		S->ctx_tok = T;
+	}
+	if (engine_get(S, w, h) < 0) return -1;
+	if (S->tuflags & MLIS_TUF_LATENT) {
+		if (S->latent.n[2] != 4) return api_error(S, MLIS_E_UNKNOWN, "latent must have 4 channels");
+		const size_t per = (size_t)4*w*h;
+		float *l = (float*)malloc(per * B * 4);
+		for (int b=0;b<B;++b) memcpy(l + per*b, S->latent.d + (S->latent.n[3] == B ? per*b : 0), per*4);
+		r = mlis_amd_set_init_latent(S->eng, l);
+		free(l);
+		if (r < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+	} else mlis_amd_set_init_latent(S->eng, NULL);
+
+	/* mask -> latent mask (:1673-1686) */
+	if (S->tuflags & MLIS_TUF_MASK) { mlis_mask_encode(S, &S->mask, &S->lmask, 0); S->tuflags |= MLIS_TUF_LMASK; }
+	if ((S->tuflags & MLIS_TUF_LMASK) && tensor_good(&S->lmask)) {
+		if (S->lmask.n[0] != w || S->lmask.n[1] != h) return api_error(S, MLIS_E_IMAGE, "latent mask %dx%d does not match the latent %dx%d", S->lmask.n[0], S->lmask.n[1], w, h);
+		if (mlis_amd_set_lmask(S->eng, S->lmask.d) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+	} else { mlis_amd_set_lmask(S->eng, NULL); if (!(S->tuflags & MLIS_TUF_LMASK)) mlis_tensor_free(&S->lmask); }
+
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	S->image.flags &= ~LT_F_READY;

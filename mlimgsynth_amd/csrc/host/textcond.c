@@ -186,13 +186,91 @@ MLB_API int mlis_amd_textcond_encode_pair_w(MLIS_AmdTextCond* T, const int32_t* 
 /* mlis_text_cond_encode for prompt + negative prompt straight into an engine's conditioning inputs (no caller-side staging):
  * what mlis_generate does between :1688 and :1707, as one library call for launchers (bench.py, multi-GPU rank 0) */
 MLB_API int mlis_amd_textcond_apply(MLIS_AmdTextCond* T, MLIS_AmdCtx* E, const int32_t* toks, int n_tok, const int32_t* neg, int n_neg)
-{
-	const size_t nc = (size_t)77 * T->n_ctx, nl = (size_t)(T->n_label > 0 ? T->n_label : 1);
+{	/* the engine's plan fixes the context length: 77 W rows, W the windows of the longer prompt (a prompt of <= 75 tokens: 77) */
+	if (!T || !E) return mlsd_set_error(-1, "textcond_apply: bad arguments");
+	const int Wp = mlis_amd_prompt_windows(n_tok, NULL, NULL), Wn = mlis_amd_prompt_windows(n_neg, NULL, NULL);
+	if (Wp < 0 || Wn < 0) return -1;
+	const int W = Wp > Wn ? Wp : Wn, rows = mlis_amd_n_ctx_tok(E);
+	if (rows != 77 * W) return mlsd_set_error(-1, "textcond_apply: the prompts need %d context rows, the engine was built for %d (MLIS_AmdConfig.n_ctx_tok)", 77 * W, rows);
+	const size_t nc = (size_t)rows * T->n_ctx, nl = (size_t)(T->n_label > 0 ? T->n_label : 1);
 	float *buf = (float*)malloc(sizeof(float) * 2 * (nc + nl));
 	if (!buf) return mlsd_set_error(-1, "textcond_apply: out of memory");
 	float *cond = buf, *ncond = buf + nc, *label = buf + 2*nc, *nlabel = label + nl;
-	int r = mlis_amd_textcond_encode_pair(T, toks, n_tok, neg, n_neg, cond, T->n_label ? label : NULL, ncond, T->n_label ? nlabel : NULL);
+	int r = mlis_amd_textcond_encode_pair_ex(T, toks, NULL, n_tok, neg, NULL, n_neg, cond, T->n_label ? label : NULL, ncond, T->n_label ? nlabel : NULL);
 	if (r > 0) r = mlis_amd_set_cond(E, cond, T->n_label ? label : NULL, ncond, T->n_label ? nlabel : NULL);
 	free(buf);
 	return r;
+}
+
+/* ------------------------------------------------------------------ prompts longer than 75 tokens (windows of 75 tokens) */
+MLB_API int mlis_amd_prompt_windows(int n_tok, int* start, int* len)
+{
+	if (n_tok < 0) return mlsd_set_error(-1, "prompt_windows: bad arguments");
+	if (n_tok > MLIS_AMD_MAX_WINDOWS * MLIS_AMD_WINDOW_TOKENS)
+		return mlsd_set_error(-1, "prompt too long (max: %d)", MLIS_AMD_MAX_WINDOWS * MLIS_AMD_WINDOW_TOKENS);
+	const int W = n_tok ? (n_tok + MLIS_AMD_WINDOW_TOKENS - 1) / MLIS_AMD_WINDOW_TOKENS : 1;
+	for (int i=0;i<W;++i) {
+		const int s0 = i * MLIS_AMD_WINDOW_TOKENS, l = n_tok - s0 < MLIS_AMD_WINDOW_TOKENS ? n_tok - s0 : MLIS_AMD_WINDOW_TOKENS;
+		if (start) start[i] = s0;
+		if (len) len[i] = l;
+	}
+	return W;
+}
+
+/* n (1 or 2) prompts, each cut into windows and padded with empty windows to the larger W; W = 1 is encode_n itself (bit for
+ * bit).  Above that the n W windows go through each tower two at a time (the sequences its plan was built for): a sequence's
+ * encoding does not depend on the other slot, so every window's rows are those of its own single-sequence encoding. */
+static int encode_windows(MLIS_AmdTextCond* T, int n, const int32_t* const* toks, const float* const* w, const int* n_tok,
+	float* const* cond, float* const* label)
+{
+	int st[2][MLIS_AMD_MAX_WINDOWS], ln[2][MLIS_AMD_MAX_WINDOWS], Wp[2] = {0, 0}, W = 1;
+	for (int p=0;p<n;++p) {
+		if (!cond[p] || n_tok[p] < 0 || (n_tok[p] && !toks[p])) return mlsd_set_error(-1, "textcond_encode: bad arguments");
+		if ((Wp[p] = mlis_amd_prompt_windows(n_tok[p], st[p], ln[p])) < 0) return -1;
+		if (Wp[p] > W) W = Wp[p];
+	}
+	for (int p=0;p<n;++p) for (int i=Wp[p]; i<W; ++i) { st[p][i] = 0; ln[p][i] = 0; }      /* padding: the empty window */
+	const size_t rows = (size_t)77 * T->n_ctx, nl = T->n_label > 0 ? (size_t)T->n_label : 1;
+	if (W == 1) {
+		if (encode_n(T, n, toks, n_tok, cond, label) < 0) return -1;
+	} else {
+		float *scratch = (float*)malloc(sizeof(float) * 2 * nl);          /* labels of windows past the first: not used */
+		if (!scratch) return mlsd_set_error(-1, "textcond: out of memory");
+		int r = 1;
+		for (int s=0; s<n*W && r>0; s+=2) {
+			const int m = n*W - s < 2 ? n*W - s : 2;
+			const int32_t *tp[2]; int nt[2]; float *c[2], *l[2];
+			for (int j=0;j<m;++j) {
+				const int p = (s + j) / W, i = (s + j) % W;
+				tp[j] = toks[p] ? toks[p] + st[p][i] : NULL; nt[j] = ln[p][i];
+				c[j] = cond[p] + (size_t)i * rows;
+				l[j] = (i == 0 && label[p]) ? label[p] : scratch + (size_t)j * nl;
+			}
+			r = encode_n(T, m, tp, nt, c, l);
+		}
+		free(scratch);
+		if (r < 0) return -1;
+	}
+	for (int p=0;p<n;++p)
+		for (int i=0;i<W && w[p];++i) apply_token_weights(cond[p] + (size_t)i * rows, T->n_ctx, ln[p][i], w[p] + st[p][i]);
+	return W;
+}
+
+MLB_API int mlis_amd_textcond_encode_ex(MLIS_AmdTextCond* T, const int32_t* toks, const float* weights, int n_tok, float* cond, float* label)
+{
+	if (!T) return mlsd_set_error(-1, "textcond_encode: bad arguments");
+	const int32_t *tp[1] = { toks }; const float *wp[1] = { weights }; float *c[1] = { cond }, *l[1] = { label };
+	return encode_windows(T, 1, tp, wp, &n_tok, c, l);
+}
+
+MLB_API int mlis_amd_textcond_encode_pair_ex(MLIS_AmdTextCond* T, const int32_t* toks, const float* w, int n_tok,
+	const int32_t* neg, const float* nw, int n_neg, float* cond, float* label, float* ncond, float* nlabel)
+{
+	if (!T) return mlsd_set_error(-1, "textcond_encode: bad arguments");
+	const int32_t *tp[2] = { toks, neg }; const float *wp[2] = { w, nw }; const int nt[2] = { n_tok, n_neg };
+	float *c[2] = { cond, ncond }, *l[2] = { label, nlabel };
+	const int W = encode_windows(T, 2, tp, wp, nt, c, l);
+	if (W < 0) return -1;
+	if (T->xl && n_neg == 0) memset(ncond, 0, sizeof(float) * 77 * W * (size_t)T->n_ctx);
+	return W;
 }

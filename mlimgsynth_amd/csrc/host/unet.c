@@ -280,13 +280,20 @@ MLB_API float unet_t_to_sigma(const UnetParams* P, float t)
 /* ------------------------------------------------------------------ graph setup / host-boundary run */
 MLB_API int unet_denoise_init_n(UnetState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch)
 {
+	return unet_denoise_init_nc(S, C, P, lw, lh, n_batch, 77);
+}
+
+MLB_API int unet_denoise_init_nc(UnetState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch, int n_ctx_tok)
+{
+	if (!n_ctx_tok) n_ctx_tok = 77;
+	if (n_ctx_tok < 0 || n_ctx_tok % 77 || n_ctx_tok > 77 * MLIS_AMD_MAX_WINDOWS) return mlsd_set_error(-1, "unet: context of %d rows (77 x W, W <= %d)", n_ctx_tok, MLIS_AMD_MAX_WINDOWS);
 	unet_params_init();
 	memset(S, 0, sizeof(*S));
 	mlctx_begin(C, "UNet");
 	mlctx_set_tprefix(C, "unet");
 	S->t_x = mlctx_input_new_img(C, "x", lw, lh, P->n_ch_in, n_batch);
 	S->t_t = mlctx_input_new_seq(C, "t", MLT_F32, n_batch, 1, 1);
-	S->t_c = mlctx_input_new_seq(C, "c", MLT_F32, P->n_ctx, 77, n_batch);
+	S->t_c = mlctx_input_new_seq(C, "c", MLT_F32, P->n_ctx, n_ctx_tok, n_batch);
 	if (P->ch_adm_in) S->t_l = mlctx_input_new_seq(C, "l", MLT_F32, P->ch_adm_in, 1, n_batch);
 	S->ctx = C; S->par = P; S->lw = lw; S->lh = lh; S->n_batch = n_batch;
 	return 1;
@@ -319,7 +326,7 @@ MLB_API int unet_denoise_run_n(UnetState* S, const float* x, const float* cond, 
 	int R = 1;
 	if (mlctx_input_set(C, S->t_x, xs, nx*4) < 0) R = -1;
 	if (R > 0 && mlctx_input_set(C, S->t_t, ts, N*4) < 0) R = -1;
-	if (R > 0 && mlctx_input_set(C, S->t_c, cond, (size_t)N*77*P->n_ctx*4) < 0) R = -1;
+	if (R > 0 && mlctx_input_set(C, S->t_c, cond, (size_t)N*S->t_c->w*P->n_ctx*4) < 0) R = -1;    /* (w: the plan's context rows) */
 	if (R > 0 && S->t_l && mlctx_input_set(C, S->t_l, label, (size_t)N*P->ch_adm_in*4) < 0) R = -1;
 	if (R > 0 && mlctx_compute_checked(C) < 0) R = -1;            /* (re-runs on the hand-off-free plan after a timed-out in-launch hand-off) */
 	if (R > 0 && mlctx_output_get(C, S->t_out, dx, nx*4) < 0) R = -1;

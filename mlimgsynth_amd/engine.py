@@ -46,7 +46,7 @@ class AmdConfig(ctypes.Structure):
     _fields_ = [("model", ctypes.c_char_p), ("width", c_int), ("height", c_int), ("n_batch", c_int), ("n_step", c_int),
                 ("cfg_scale", c_f), ("s_ancestral", c_f), ("sched", c_int), ("use_tae", c_int), ("use_hipgraph", c_int),
                 ("weight_seed", c_u64), ("method", c_int), ("s_noise", c_f), ("f_t_ini", c_f), ("f_t_end", c_f),
-                ("defer_weights", c_int), ("unet_split", c_int)]
+                ("defer_weights", c_int), ("unet_split", c_int), ("n_ctx_tok", c_int)]
 
 
 _proto_done = False
@@ -73,6 +73,7 @@ def L():
         l.mlctx_sync.argtypes = [vp]
         l.unet_params_get.argtypes = [ctypes.c_char_p, ctypes.POINTER(UnetParams)]
         l.unet_denoise_init_n.argtypes = [ctypes.POINTER(UnetState), vp, ctypes.POINTER(UnetParams), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]
+        l.unet_denoise_init_nc.argtypes = [ctypes.POINTER(UnetState), vp, ctypes.POINTER(UnetParams), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_int]
         l.unet_denoise_build.argtypes = [ctypes.POINTER(UnetState)]
         l.unet_denoise_run_n.argtypes = [ctypes.POINTER(UnetState), FP, FP, FP, FP, FP]
         l.unet_sigma_to_t.restype = c_f
@@ -193,7 +194,7 @@ def unet_params(model):
 class Unet:
     """unet_denoise_init_n / unet_denoise_run_n (src/unet.c:336-498) with a batch dimension."""
 
-    def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0):
+    def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0, n_ctx_tok=77):
         self.P = unet_params(model)
         self.ctx = MLCtx(stream, flags)
         if stream_weights_mib:          # the reference's --unet-split: weights in pinned host memory, three device slabs of this size
@@ -201,17 +202,23 @@ class Unet:
             f.argtypes = [vp, ctypes.c_size_t]
             check1(f(self.ctx.h, int(stream_weights_mib) << 20), "mlctx_set_weight_streaming")
         self.S = UnetState()
-        check1(L().unet_denoise_init_n(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch), "unet_denoise_init_n")
+        if n_ctx_tok == 77:
+            check1(L().unet_denoise_init_n(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch), "unet_denoise_init_n")
+        else:                           # windowed prompt: cond [N][77 W][n_ctx]
+            check1(L().unet_denoise_init_nc(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch, int(n_ctx_tok)),
+                   "unet_denoise_init_nc")
         check1(L().unet_denoise_build(ctypes.byref(self.S)), "unet_denoise_build")
         if synth:
             self.ctx.params_synth(seed)
-        self.lw, self.lh, self.n = lw, lh, n_batch
+        self.lw, self.lh, self.n, self.n_ctx_tok = lw, lh, n_batch, int(n_ctx_tok)
 
     def run(self, x, cond, label, sigma):
         x = np.ascontiguousarray(x, np.float32)
         cond = np.ascontiguousarray(cond, np.float32)
         sigma = np.ascontiguousarray(sigma, np.float32)
         lab = np.ascontiguousarray(label, np.float32) if label is not None else None
+        if cond.size != self.n * self.n_ctx_tok * self.P.n_ctx:
+            raise ValueError(f"conditioning of {cond.size} values, the plan takes {self.n} x {self.n_ctx_tok} x {self.P.n_ctx}")
         dx = np.empty_like(x)
         check1(L().unet_denoise_run_n(ctypes.byref(self.S), fptr(x), fptr(cond), fptr(lab), fptr(sigma), fptr(dx)), "unet_denoise_run_n")
         return dx
@@ -339,11 +346,11 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77):
         l = _proto2()
         self.cfg = AmdConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
-                             int(defer_weights), int(unet_split))
+                             int(defer_weights), int(unet_split), int(n_ctx_tok))    # n_ctx_tok: context rows, 77 x W (windowed prompt)
         self.h = l.mlis_amd_create(ctypes.byref(self.cfg), vp(stream))
         if not self.h:
             from ._lib import MlsdError, last_error
@@ -353,6 +360,9 @@ class Generator:
 
     def set_cond(self, cond, label=None, uncond=None, unlabel=None):
         a = [np.ascontiguousarray(x, np.float32) if x is not None else None for x in (cond, label, uncond, unlabel)]
+        for x in (a[0], a[2]):          # [n_ctx_tok][n_ctx]: the C side copies that many floats
+            if x is not None and x.size != self.cfg.n_ctx_tok * self.P.n_ctx:
+                raise ValueError(f"conditioning of {x.size} values, the plan takes {self.cfg.n_ctx_tok} x {self.P.n_ctx}")
         check1(_proto2().mlis_amd_set_cond(self.h, *[fptr(x) for x in a]), "mlis_amd_set_cond")
 
     def set_cond_device(self, cond, label=None, uncond=None, unlabel=None):

@@ -57,6 +57,11 @@ def attention(args, stream=None):
     check(lib().mlsd_attention(ctypes.byref(args), vp(stream)), "mlsd_attention")
 
 
+def attention_ctx(args, stream=None):
+    """mlsd_attention_ctx: cross attention over 96 < Tk <= 320 keys (windowed text context)."""
+    check(lib().mlsd_attention_ctx(ctypes.byref(args), vp(stream)), "mlsd_attention_ctx")
+
+
 def groupnorm(args, stream=None):
     check(lib().mlsd_groupnorm(ctypes.byref(args), vp(stream)), "mlsd_groupnorm")
 

@@ -70,6 +70,16 @@ def sdxl_label(feat, width, height):
     return out
 
 
+MAX_WINDOWS, WINDOW_TOKENS = 4, 75     # MLIS_AMD_MAX_WINDOWS, MLIS_AMD_WINDOW_TOKENS (include/mlimgsynth_amd.h)
+
+
+def prompt_windows(n_tok):
+    """mlis_amd_prompt_windows: the 75-token windows of an n_tok-token prompt -> [(start, length)]; an error above 300 tokens."""
+    st, ln = (c_int * MAX_WINDOWS)(), (c_int * MAX_WINDOWS)()
+    w = check1(_l().mlis_amd_prompt_windows(int(n_tok), st, ln), "mlis_amd_prompt_windows")
+    return [(st[i], ln[i]) for i in range(w)]
+
+
 class TextConditioner:
     """mlis_text_cond_encode (src/mlimgsynth.c:1501-1563) on resident encoders: thin wrapper over the C object
     MLIS_AmdTextCond (csrc/host/textcond.c), which holds the towers and does the SD1.5 / SDXL assembly."""
@@ -85,6 +95,8 @@ class TextConditioner:
         l.mlis_amd_textcond_flops.restype = ctypes.c_double
         l.mlis_amd_textcond_encode.argtypes = [vp, I32P, c_int, FP, FP]
         l.mlis_amd_textcond_encode_pair.argtypes = [vp, I32P, c_int, I32P, c_int, FP, FP, FP, FP]
+        l.mlis_amd_textcond_encode_ex.argtypes = [vp, I32P, FP, c_int, FP, FP]
+        l.mlis_amd_textcond_encode_pair_ex.argtypes = [vp, I32P, FP, c_int, I32P, FP, c_int, FP, FP, FP, FP]
         self._l, self.model = l, model
         h = l.mlis_amd_textcond_create(model.encode(), width, height, seed, vp(stream))
         if not h:
@@ -99,23 +111,36 @@ class TextConditioner:
         t = np.ascontiguousarray(np.asarray(t, np.int32).reshape(-1))
         return t, t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if t.size else None
 
-    def encode(self, toks):
-        """-> (cond [77][n_ctx], label [n_label] or None)"""
+    @staticmethod
+    def _weights(w, n):
+        if w is None:
+            return None
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1))
+        if w.size != n:
+            raise ValueError(f"{w.size} weights for {n} tokens")
+        return w
+
+    def encode(self, toks, weights=None):
+        """-> (cond [77 W][n_ctx], label [n_label] or None); W = the prompt's 75-token windows (1 up to 75 tokens)"""
         t, tp = self._toks(toks)
-        cond = np.empty((77, self.n_ctx), np.float32)
+        w = self._weights(weights, t.size)
+        cond = np.empty((77 * len(prompt_windows(t.size)), self.n_ctx), np.float32)
         label = np.empty(self.n_label, np.float32) if self.n_label else None
-        check1(self._l.mlis_amd_textcond_encode(self.h, tp, t.size, fptr(cond), fptr(label)), "mlis_amd_textcond_encode")
+        check1(self._l.mlis_amd_textcond_encode_ex(self.h, tp, fptr(w), t.size, fptr(cond), fptr(label)), "mlis_amd_textcond_encode_ex")
         return cond, label
 
-    def encode_pair(self, toks, neg_toks=()):
-        """cond/label for the prompt and the (usually empty) negative prompt, with the SDXL zeroing rule."""
+    def encode_pair(self, toks, neg_toks=(), weights=None, neg_weights=None):
+        """cond/label for the prompt and the (usually empty) negative prompt, with the SDXL zeroing rule; both [77 W][n_ctx] with the
+        larger side's W (the other padded with empty windows)."""
         t, tp = self._toks(toks)
         n, np_ = self._toks(neg_toks)
-        cond, ncond = np.empty((77, self.n_ctx), np.float32), np.empty((77, self.n_ctx), np.float32)
+        w, nw = self._weights(weights, t.size), self._weights(neg_weights, n.size)
+        W = max(len(prompt_windows(t.size)), len(prompt_windows(n.size)))
+        cond, ncond = np.empty((77 * W, self.n_ctx), np.float32), np.empty((77 * W, self.n_ctx), np.float32)
         label = np.empty(self.n_label, np.float32) if self.n_label else None
         nlabel = np.empty(self.n_label, np.float32) if self.n_label else None
-        check1(self._l.mlis_amd_textcond_encode_pair(self.h, tp, t.size, np_, n.size, fptr(cond), fptr(label), fptr(ncond), fptr(nlabel)),
-               "mlis_amd_textcond_encode_pair")
+        check1(self._l.mlis_amd_textcond_encode_pair_ex(self.h, tp, fptr(w), t.size, np_, fptr(nw), n.size, fptr(cond), fptr(label),
+                                                        fptr(ncond), fptr(nlabel)), "mlis_amd_textcond_encode_pair_ex")
         return cond, label, ncond, nlabel
 
     def flops(self):

@@ -19,7 +19,7 @@ TT_EPI = {1: "f16", 2: "f32", 3: "f32+res", 4: "f32+ln", 5: "f32+res+ln", 6: "f3
 
 # every GEMM / attention kernel family of csrc/hip: a name that contains one of these MUST be parsed by its family rule in known()
 FAMILIES = ("gemm_pp_kernel", "gemm_tt_kernel", "gemm_w4_kernel", "gemm_skinny_kernel", "gemm_kernel", "attn64x2s_kernel", "attn64x2_kernel", "attn64pp_kernel",
-            "attn_tk96_kernel", "attn_q_kernel", "attn_kernel", "conv_smalln_kernel")
+            "attn_tk96_kernel", "attn_ctx_kernel", "attn_q_kernel", "attn_kernel", "conv_smalln_kernel")
 
 
 def _ident(name):
@@ -108,6 +108,8 @@ def known(name):
                 return f"attention<{a[0]},queue>", ""
             if fn == "attn_tk96_kernel":
                 return f"attention<{a[0]},one pass>", ""
+            if fn == "attn_ctx_kernel":                  # mlsd_attention_ctx: windowed text context, 96 < Tk <= 320
+                return f"attention<{a[0]},key groups>", "keys in LDS" if a[2] else "keys streamed"
             if fn == "conv_smalln_kernel":
                 return "gemm<conv3x3n16,conv>", f"cin {a[0]}, ring {a[1]}"
             if fn == "attn64x2s_kernel":

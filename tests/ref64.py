@@ -20,6 +20,25 @@ Bounds (u32 = 2^-24, u16 = 2^-11):
                     + C_ATTN * sum_j p_j dq_j (|v_j| + |o|),  dq_j = u16 * scale * sum_i |q_i k_ji|
                                                               (kernels that round the scaled Q to fp16 before the QK product: an error of
                                                               dq_j in score j moves o by p_j dq_j (v_j - o))
+  GEMM / implicit-GEMM convolution, per output element (tests/test_gemm_float64_gpu.py, tests/test_ref64_gemm_cpu.py):
+                    acc:  C_GEMM * u32 * D * S,   S = sum_k |a_k w_k| in float64 (|A| @ |W|^T).
+                          The products of fp16 operands are exact in fp32 (11 + 11 significant bits).  Every kernel sums them in MFMA steps of
+                          k_step = 16 (v_mfma_f32_32x32x16_f16: gemm_kernel, the general tiles) or 32 (v_mfma_f32_16x16x32_f16: the ping-pong,
+                          stream-K, two-tiles-per-CU, skinny and small-Cout kernels), each added to ONE fp32 accumulator in K order; split-K and
+                          stream-K add their nsplit slice sums one after another.  A sequential fp32 sum of n terms is off by at most
+                          (n - 1) u32 sum|terms| to first order, so  D = ceil(K / k_step) + nsplit + 5,  the 5 covering the MFMA's own sum
+                          of 16 / 32 products (a tree of depth <= 5).
+                    epilogue adds (bias, rowbias, bias_m, residual): C_EPI * u32 * (|bias| + |rowbias| + |bias_m| + |resid| + |y|)
+                          (four fp32 adds at most, each rounding a partial sum; the |acc| part of those partial sums is in the acc term);
+                    activation of an argument z known to +-e_z:
+                          |act'(z)| e_z + C_ACT * u32 * (1 + |eta(z)|) |act(z)| + min(|act(z)|, ACT_TINY),
+                          eta = the argument of the exponential the kernel evaluates (common.hpp: v_exp_f32 on an fp32 argument, whose rounding
+                          moves the exponential by u32 |eta| relative): silu z, quick-GELU 1.702 z, tanh-GELU 2 sqrt(2/pi) (z + 0.044715 z^3).
+                          The last term: where the exponential overflows fp32 (eta < -88.7) the kernels return 0 for a value below 2^-120;
+                          ACT_TINY = 2^-100 bounds that without touching any value a test can see.
+                          GEGLU y = a gelu(g): |gelu(g)| e_a + |a| |gelu'(g)| e_g + C_ACT u32 (1 + |eta(g)|) |y| + u32 |y| + min(|y|, ACT_TINY).
+                    fp16 outputs: the fp32 bound b32 + half_ulp16(|y| + b32); where a launch writes both C32 and C16, C16 must also be
+                          fp16_rne(C32) bit for bit (the epilogues round the one fp32 value).  An fp16 output is +-inf exactly where fp16(C32) is.
 """
 import numpy as np
 
@@ -159,3 +178,171 @@ def attention_worst(got, want, bound):
     ratio = (np.abs(got - want) / (half_ulp16(want) + bound)).max(1)
     ratio[~np.isfinite(got).all(1)] = np.inf
     return ratio
+
+
+# ------------------------------------------------------------------ GEMM / implicit-GEMM convolution
+# 2: twice the first-order worst case of a sequential sum.  Typical errors are ~sqrt(D) times smaller than D u32 S; a 64-wide K tile dropped,
+# a slice added twice, an fp16 partial sum or a flushed subnormal operand are > 2^-12 S-relative and fail by orders of magnitude.
+C_GEMM = 2.0
+# 4: bias, row bias, per-row bias and residual, one fp32 add each (see the docstring).
+C_EPI = 4.0
+# 8: v_exp_f32 and v_rcp_f32 (~1 ulp each), the add and multiplies of the sigmoid form, and the rounding of the argument eta itself.
+C_ACT = 8.0
+ACT_TINY = 2.0 ** -100
+K_STEP_GENERAL, K_STEP_MFMA16 = 16, 32
+
+
+def fp16_rne(x):
+    """fp32 -> fp16 with round-to-nearest-even, overflow to +-inf and fp16 subnormals (numpy's conversion)."""
+    return np.asarray(x, np.float32).astype(np.float16)
+
+
+def gemm_depth(K, k_step, nsplit=1):
+    """D of the accumulation bound (module docstring)."""
+    return -(-K // k_step) + nsplit + 5
+
+
+def im2col64(x, n_img, H, W, Cin, KH, KW, stride, pad, ups, OH, OW, rows=None):
+    """Implicit-GEMM A operand in float64: x is the NHWC image [n_img * H * W][Cin] (the fp16 values the kernel reads, Cin already padded
+    to the kernel's multiple of 8); row m = (image, oy, ox), column k = (kh, kw, cin) with cin fastest; zero outside the (nearest-2x upsampled
+    when ups) image.  rows: the output rows wanted (default all)."""
+    x = np.asarray(x, np.float64).reshape(n_img, H, W, Cin)
+    if ups:
+        x = x.repeat(2, axis=1).repeat(2, axis=2)
+        H, W = 2 * H, 2 * W
+    m = np.arange(n_img * OH * OW) if rows is None else np.asarray(rows)
+    b, oy, ox = m // (OH * OW), (m // OW) % OH, m % OW
+    out = np.zeros((len(m), KH, KW, Cin))
+    for kh in range(KH):
+        iy = oy * stride - pad + kh
+        for kw in range(KW):
+            ix = ox * stride - pad + kw
+            ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+            out[ok, kh, kw] = x[b[ok], iy[ok], ix[ok]]
+    return out.reshape(len(m), KH * KW * Cin)
+
+
+def gemm64(A, Wt):
+    """C = A . W^T and S = |A| . |W|^T in float64, from the fp16 operand values."""
+    A, Wt = np.asarray(A, np.float64), np.asarray(Wt, np.float64)
+    return A @ Wt.T, np.abs(A) @ np.abs(Wt).T
+
+
+def sigmoid64(x):
+    """1 / (1 + e^-x) without cancellation: tiny values for very negative x stay tiny (not 0)"""
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore"):
+        e = np.exp(-np.abs(x))
+    return np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def act_eta(z, act):
+    """argument of the exponential of the kernels' fast activation (0 where there is none)"""
+    z = np.asarray(z, np.float64)
+    if act == 1:
+        return z
+    if act in (2, 5):
+        return 2.0 * np.sqrt(2.0 / np.pi) * (z + 0.044715 * z ** 3)
+    if act == 3:
+        return 1.702 * z
+    return np.zeros_like(z)
+
+
+def act64(z, act):
+    """the epilogue activations in float64: SiLU, tanh-GELU (ggml_gelu; also the GEGLU gate), quick-GELU, ReLU"""
+    z = np.asarray(z, np.float64)
+    if act == 0:
+        return z
+    if act == 4:
+        return np.maximum(z, 0.0)
+    return z * sigmoid64(act_eta(z, act))
+
+
+def dact64(z, act):
+    """|act'(z)|"""
+    z = np.asarray(z, np.float64)
+    if act == 0:
+        return np.ones_like(z)
+    if act == 4:
+        return (z > 0).astype(np.float64)
+    e = act_eta(z, act)
+    s = sigmoid64(e)
+    de = {1: np.ones_like(z), 3: np.full_like(z, 1.702)}.get(act)
+    if de is None:
+        de = 2.0 * np.sqrt(2.0 / np.pi) * (1.0 + 3 * 0.044715 * z ** 2)
+    return np.abs(s + z * s * (1.0 - s) * de)
+
+
+def act_bound(z, ez, act):
+    """bound of act(z) computed in fp32 from an argument known to +-ez (module docstring)"""
+    y = np.abs(act64(z, act))
+    return dact64(z, act) * ez + C_ACT * U32 * (1.0 + np.abs(act_eta(z, act))) * y + np.minimum(y, ACT_TINY)
+
+
+def geglu_cols(nout):
+    """GEMM columns of the value and the gate of GEGLU output column j: W rows interleaved in blocks of 32 (value, gate)"""
+    j = np.arange(nout)
+    v = (j >> 5) * 64 + (j & 31)
+    return v, v + 32
+
+
+def gemm_epilogue64(acc, S, D, rows, cols, bias=None, rowbias=None, rows_per_batch=1, bias_m=None, act=0, resid=None, act_after_resid=False):
+    """y and its fp32 bound for the output elements [rows][cols] (global indices into the output) of a launch whose float64 accumulators are
+    acc [len(rows)][GEMM columns] and S alike (for GEGLU every GEMM column of the rows, in the interleaved order; otherwise the columns
+    `cols`).  The epilogue terms in the order of include/mlsd_kernels.h: bias [N], rowbias [batch][N] (row m uses batch m // rows_per_batch),
+    bias_m [M], activation, resid [M][Nout] (or before the activation with act_after_resid)."""
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    f = lambda a: np.asarray(a, np.float64)
+    z, ez = f(acc).copy(), C_GEMM * U32 * D * f(S)
+    gcols = np.arange(z.shape[1]) if act == 5 else cols
+    mag = np.zeros_like(z)
+    for t in ([] if bias is None else [f(bias)[gcols][None, :]]) + \
+             ([] if rowbias is None else [f(rowbias)[rows // max(rows_per_batch, 1)][:, gcols]]) + \
+             ([] if bias_m is None else [f(bias_m)[rows][:, None]]):
+        z = z + t
+        mag = mag + np.abs(t)
+    r = None if resid is None else f(resid)[rows][:, cols]
+    if act == 5:
+        vc, gc = geglu_cols(z.shape[1] // 2)
+        vc, gc = vc[cols], gc[cols]
+        a, g = z[:, vc], z[:, gc]
+        ea = ez[:, vc] + C_EPI * U32 * (mag[:, vc] + np.abs(a))
+        eg = ez[:, gc] + C_EPI * U32 * (mag[:, gc] + np.abs(g))
+        gel = act64(g, 2)
+        y = a * gel
+        b = np.abs(gel) * ea + np.abs(a) * dact64(g, 2) * eg + C_ACT * U32 * (1.0 + np.abs(act_eta(g, 2))) * np.abs(y) + U32 * np.abs(y) \
+            + np.minimum(np.abs(y), ACT_TINY)
+    else:
+        if r is not None and act_after_resid:
+            z = z + r
+            mag = mag + np.abs(r)
+        ez = ez + C_EPI * U32 * (mag + np.abs(z))
+        y, b = act64(z, act), (act_bound(z, ez, act) if act else ez)
+    if r is not None and not (act_after_resid and act != 5):
+        y = y + r
+        b = b + C_EPI * U32 * (np.abs(r) + np.abs(y))
+    return y, b
+
+
+def gemm_ratio32(got, want, b32):
+    """per-element |got - want| / b32 (inf where got is not finite)"""
+    got = np.asarray(got, np.float64)
+    err = np.abs(got - want)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.where(err == 0, 0.0, err / b32)
+    r[~np.isfinite(got)] = np.inf
+    return r
+
+
+def gemm_ratio16(got16, want, b32):
+    """per-element ratio of an fp16 output to half_ulp16 + b32.  An infinite output passes (ratio 0) where want +- b32 reaches the fp16
+    overflow threshold 65520 with the same sign; a finite output that should have overflowed fails through its distance to want."""
+    g = np.asarray(got16, np.float64)
+    b = b32 + half_ulp16(np.abs(want) + b32)
+    fin = np.isfinite(g)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        err = np.abs(g - want)
+        r = np.where(fin & (err > 0), err / b, 0.0)
+    inf_ok = (np.sign(g) == np.sign(want)) & (np.abs(want) + b32 >= 65520.0)
+    r[~fin & ~inf_ok] = np.inf
+    return r

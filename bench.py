@@ -11,6 +11,9 @@ units, sharded over ranks with no per-step collective (weak scaling: batch_per_g
 Usage (driver contract):  python bench.py --gpus N --steps K --warmup W
   N>1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL).
 Prints ONE JSON line on rank 0; `ms_per_step` is the time of one timed step.
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, the dump below, the line.
+  --full  also measures what the headline does not need, each after the timed region: the PCIe-inclusive rate, the per-kernel
+  roofline of one UNet evaluation and the sustained-MFMA probe, the secondary workloads (N=1) and the CPU baseline (N=1).
   --dump-outputs DIR  writes the final latents and decoded images of the last timed step to DIR/{latents,images}.npy (float32, at most
   64 MB in all: beyond that a fixed, seeded sample of the elements); the inputs depend on the arguments only, so two builds can be
   compared output for output.
@@ -49,6 +52,8 @@ def parse():
     ap.add_argument("--cfg", type=float, default=7.0)
     ap.add_argument("--tae", action="store_true", help="decode with TAESD instead of the KL-VAE")
     ap.add_argument("--hipgraph", type=int, default=-1, help="replay each UNet evaluation as a hipGraph (default: auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline does not need (PCIe-inclusive rate, roofline, secondary workloads, CPU baseline); the options below refine it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-nfe", type=int, default=2, help="(kept for compatibility: the CPU baseline sample times one sampler step = 2 UNet evaluations)")
@@ -66,6 +71,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if (a.kernel_table or a.extras) and not a.full:
+        ap.error("--kernel-table and --extras are parts of --full")
     return a
 
 
@@ -500,13 +507,15 @@ def run(a, world, rank, local_rank):
             _lib.check(L.mlsd_memcpy(lat.ctypes.data_as(_lib.vp), _lib.vp(g.latent_ptr()), ctypes.c_size_t(lat.nbytes), 1, None), "memcpy d2h")
             _lib.check(L.mlsd_device_sync(), "sync")
         dumped = dump_outputs(a.dump_outputs, {"latents": lat, "images": g.image()})
-    # PCIe-inclusive variant (the reference's mlis_generate ends with host pixels): one more step that also copies the fp32
+    # --full: PCIe-inclusive variant (the reference's mlis_generate ends with host pixels): one more step that also copies the fp32
     # images of this rank to host memory; reported beside `value`, never as `value`
-    fence()
-    t1 = time.perf_counter()
-    one_step(a.steps + a.warmup, want_images=True)
-    fence()
-    el_host = mdist.max_over_ranks(time.perf_counter() - t1, tdev)
+    el_host = None
+    if a.full:
+        fence()
+        t1 = time.perf_counter()
+        one_step(a.steps + a.warmup, want_images=True)
+        fence()
+        el_host = mdist.max_over_ranks(time.perf_counter() - t1, tdev)
 
     if rank != 0:
         if world > 1:
@@ -532,8 +541,9 @@ def run(a, world, rank, local_rank):
         "job_tflops": round(value * flop_per_img / 1e12, 1),
         "job_frac_of_mfma_peak": round(value * flop_per_img / 1e12 / (world * PEAK_MFMA_F16_TFLOPS), 4),
         "unet_eval_ms": round(unet_ms / (a.steps * a.denoise_steps), 3),
-        "images_per_s_with_d2h_of_fp32_images": round(B * world / el_host, 4),
     }
+    if el_host is not None:
+        out["images_per_s_with_d2h_of_fp32_images"] = round(B * world / el_host, 4)
     if dumped is not None:
         out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if world > 1:
@@ -541,28 +551,29 @@ def run(a, world, rank, local_rank):
         out["rccl_ranks" if comm_kind.value == 0 else "host_transport_ranks"] = comm_ranks.value      # the communicator's world as the transport reports it (ncclCommCount)
         out["gpus_visible"] = torch.cuda.device_count()
 
-    roof, agg, ms = kernel_roofline(g, a.workload, B)
-    if rank == 0 and roof.get("bound") == "mfma":
-        try:       # the power-limited ceiling of THIS box, measured: pure-MFMA loop on random operands (see sustained_mfma_probe)
-            sus = sustained_mfma_probe(_lib)
-            roof["sustained_mfma_tflops_measured"] = round(sus, 1)
-            roof["frac_of_sustained_measured"] = round(roof["achieved"] / sus, 4)
-        except Exception as e:
-            roof["sustained_mfma_tflops_measured"] = None; roof["sustained_probe_error"] = str(e)
-    out["roofline"] = roof
-    out["unet_eval_mfma"] = eval_mfma(agg)
+    # ---- --full: roofline of one UNet evaluation (a profiling pass of its own, per-launch HIP events) and the sustained-MFMA probe
+    if a.full:
+        roof, agg, ms = kernel_roofline(g, a.workload, B)
+        if rank == 0 and roof.get("bound") == "mfma":
+            try:       # the power-limited ceiling of THIS box, measured: pure-MFMA loop on random operands (see sustained_mfma_probe)
+                sus = sustained_mfma_probe(_lib)
+                roof["sustained_mfma_tflops_measured"] = round(sus, 1)
+                roof["frac_of_sustained_measured"] = round(roof["achieved"] / sus, 4)
+            except Exception as e:
+                roof["sustained_mfma_tflops_measured"] = None; roof["sustained_probe_error"] = str(e)
+        out["roofline"] = roof
+        out["unet_eval_mfma"] = eval_mfma(agg)
     out["tile_table_misses"] = g.unet_ctx().tune_misses()     # GEMM shapes of this plan not in the compiled-in tile table (0 on the bench plans)
-    if a.kernel_table:
+    if a.kernel_table:         # (a part of --full: parse() refuses it alone)
         with open(a.kernel_table, "w") as f:
             f.write(f"# one UNet evaluation, {a.workload} batch {B} (N={2 * B if a.cfg > 1 else B}); per-launch HIP events\n")
             f.write(f"# {'kernel':44s} {'launches':>8s} {'total_ms':>10s} {'TFLOP':>9s} {'TFLOP/s':>9s} {'alg_GB':>9s} {'GB/s':>9s}\n")
             for k, (c, t, fl_, nb_) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
                 f.write(f"{k:46s} {c:8d} {t:10.3f} {fl_ / 1e12:9.3f} {fl_ / max(t, 1e-9) / 1e9:9.1f} {nb_ / 1e9:9.3f} {nb_ / max(t, 1e-9) / 1e6:9.1f}\n")
 
-    # ---- secondary workloads of the BASELINE metric (N=1 only, after the headline's timed region; the headline `value` is
+    # ---- --full: secondary workloads of the BASELINE metric (N=1 only, after the headline's timed region; the headline `value` is
     # untouched): SD1.5 512x512 batch 1 (configs[1]) and SDXL with the TAESD decoder (configs[4] without weight streaming)
-    plist = g.unet_ctx().param_list()
-    extras = world == 1 and not a.no_extras and ((a.workload == "sdxl" and not a.tae) or a.extras)
+    extras = a.full and world == 1 and not a.no_extras and ((a.workload == "sdxl" and not a.tae) or a.extras)
     aux15 = None
     if extras:
         g.destroy()
@@ -579,9 +590,9 @@ def run(a, world, rank, local_rank):
             except Exception as e:
                 out[key] = {"value": None, "error": str(e)}
 
-    # ---- CPU baseline (rank 0, N=1 only): the oracle = CPU restatement of the reference path, bounded samples of the WHOLE path (towers, sampler step, decode), each in
+    # ---- --full: CPU baseline (rank 0, N=1 only): the oracle = CPU restatement of the reference path, bounded samples of the WHOLE path (towers, sampler step, decode), each in
     # a child process with a hard timeout
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         threads = a.cpu_threads or host_threads()
         try:
             out["cpu_baseline"] = cpu_record(model, width, height, a.cfg, a.denoise_steps, threads, a.cpu_decode_budget, a.cpu_timeout, flop_per_img, info["decode_flops"] / B, f"one {a.workload} {width}x{height} image")

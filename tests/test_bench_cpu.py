@@ -1,4 +1,4 @@
-"""bench.py parts that need no GPU: the --dump-outputs writer (size limit, fixed sample) and the --steps check."""
+"""bench.py parts that need no GPU: the --dump-outputs writer (size limit, fixed sample), the --steps check and the options that only --full takes."""
 import os
 import subprocess
 import sys
@@ -40,3 +40,9 @@ def test_dump_outputs_samples_the_same_elements_under_the_limit(tmp_path):
 def test_steps_below_one_are_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_parts_of_full_are_refused_alone():
+    for opt in (["--kernel-table", "t.txt"], ["--extras"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + opt, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, opt

@@ -283,7 +283,7 @@ def test_bench_world2_branch_on_one_gpu_over_the_host_transport():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--transport", "host", "--workload", "tiny",
-                          "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=800, env=env)
+                          "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=800, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])          # torch.distributed.run returns non-zero when ANY rank does
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]                                      # rank 0 alone prints
@@ -301,15 +301,15 @@ def test_bench_world2_branch_on_one_gpu_over_the_host_transport():
 
 
 def test_bench_json_contract_on_tiny_workload():
-    """bench.py prints ONE JSON line with the driver's contract keys plus the `roofline` and `cpu_baseline` objects (run on the
+    """bench.py --full prints ONE JSON line with the driver's contract keys plus the `roofline` and `cpu_baseline` objects (run on the
     tiny workload so that the CPU leg takes a second); values are sane and the metric / config follow BASELINE.json's wording"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny"],
-                         capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny",
+                          "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -332,6 +332,26 @@ def test_bench_json_contract_on_tiny_workload():
     m = d["unet_eval_mfma"]                                                       # time-weighted matrix-pipe fraction of one whole evaluation
     assert 0 < m["frac_of_mfma_peak"] < 1 and abs(m["frac_of_mfma_peak"] - m["tflops"] / 2500.0) < 1e-3 and m["by_family"]
     assert abs(sum(v["share"] for v in m["by_family"].values()) - 1) < 0.35       # (top six families)
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full bench.py runs set-up, warm-up and the timed steps and prints the contract keys; the PCIe-inclusive step, the roofline
+    pass, the secondary workloads and the CPU baseline are --full's."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny"],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "images/s" and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert abs(d["value"] - d["config"]["global_batch"] * 1e3 / d["ms_per_step"]) / d["value"] < 0.02
+    for k in ("roofline", "unet_eval_mfma", "cpu_baseline", "images_per_s_with_d2h_of_fp32_images", "sd15", "sdxl_tae"):
+        assert k not in d, k
 
 
 def test_bench_dump_outputs_repeat_bit_identically(tmp_path):
@@ -360,7 +380,7 @@ def test_bench_dump_outputs_repeat_bit_identically(tmp_path):
 
 
 def test_bench_line_carries_the_whole_baseline_metric():
-    """beside the unchanged headline value the one JSON line holds SD1.5 512x512 b1 (BASELINE configs[1]) and
+    """beside the unchanged headline value the one JSON line of --full holds SD1.5 512x512 b1 (BASELINE configs[1]) and
     SDXL + TAESD as extra keys, each with its own roofline, and the CPU sample of BASELINE.md section 3 (one SD1.5 evaluation).
     Run with the tiny model as the headline (--extras) so that the test is about the keys, not about minutes of SDXL."""
     import json
@@ -369,7 +389,7 @@ def test_bench_line_carries_the_whole_baseline_metric():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--workload", "tiny",
-                          "--extras", "--extra-steps", "1"], capture_output=True, text=True, timeout=1500)
+                          "--full", "--extras", "--extra-steps", "1"], capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     for key, cfg in (("sd15", "sd15-512x512"), ("sdxl_tae", "sdxl-1024x1024")):

@@ -7,7 +7,7 @@ WL=${1:-sdxl}; B=${2:-4}; TAG=${3:-r2}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_$TAG; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp PYTHONPATH=$R
-ARGS="--workload $WL --batch-per-gpu $B --steps 1 --warmup 1 --no-cpu-baseline"
+ARGS="--workload $WL --batch-per-gpu $B --steps 1 --warmup 1 --full --no-cpu-baseline"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$WL -- python3 $R/bench.py $ARGS > $OUT/kt_$WL.log 2>&1 < /dev/null
 for f in $(find $OUT/kt_$WL -name "*kernel_stats.csv" | head -1); do cp $f $OUT/${TAG}_${WL}_b${B}_rocprofv3_kernel_stats.csv; done
 find $OUT/kt_$WL -name "*kernel_trace.csv" -delete
@@ -35,7 +35,7 @@ timeout 240 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_
 for f in $(find $OUT/pmc_mfma_$WL -name "*counter_collection.csv" | head -1); do python3 $R/tools/pmc_mfma_summary.py $OUT/${TAG}_${WL}_b${B}_pmc_mfma.json "$f"; done
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*counter_collection.csv" -delete
 cd $R
-timeout 600 python3 bench.py --workload $WL --batch-per-gpu $B --kernel-table $OUT/${TAG}_${WL}_b${B}_unet_eval_kernel_table.txt > $OUT/${TAG}_${WL}_b${B}_bench.json 2> $OUT/bench_$WL.log < /dev/null
+timeout 600 python3 bench.py --workload $WL --batch-per-gpu $B --full --kernel-table $OUT/${TAG}_${WL}_b${B}_unet_eval_kernel_table.txt > $OUT/${TAG}_${WL}_b${B}_bench.json 2> $OUT/bench_$WL.log < /dev/null
 tail -1 $OUT/${TAG}_${WL}_b${B}_bench.json
 # per-SHAPE tables (UNet evaluation and VAE / TAE decode) and, for sdxl, the phase stamps of the single-round GEMMs
 case $WL in sdxl) M=sdxl; LAT=128;; sd15) M=sd1; LAT=64;; *) M=$WL; LAT=8;; esac
@@ -48,5 +48,5 @@ if [ "$WL" = "sdxl" ]; then
   timeout 300 python3 tools/gemm_ksweep.py 8192 1280 > $OUT/${TAG}_gemm_ksweep_8192x1280.txt 2>> $OUT/bench_$WL.log
   timeout 120 python3 tools/attn_bench.py 20 > $OUT/${TAG}_attention_variants.txt 2>> $OUT/bench_$WL.log
   # BASELINE.json configs[4]: TAE decode instead of the KL-VAE
-  timeout 600 python3 bench.py --workload $WL --batch-per-gpu $B --tae --no-cpu-baseline > $OUT/${TAG}_${WL}_b${B}_tae_bench.json 2>> $OUT/bench_$WL.log < /dev/null
+  timeout 600 python3 bench.py --workload $WL --batch-per-gpu $B --tae --full --no-cpu-baseline > $OUT/${TAG}_${WL}_b${B}_tae_bench.json 2>> $OUT/bench_$WL.log < /dev/null
 fi

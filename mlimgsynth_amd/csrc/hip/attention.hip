@@ -1611,6 +1611,19 @@ int g_attn_tk96 = 1;        // Tk <= 96 without a causal mask: the one-pass kern
 int g_attn_tk96_qb = 0;     // query blocks of 128 rows per workgroup (0 = by the launch size)
 int g_attn_vsum = 1;        // row sums on the VALU (v_pk_add_f32) instead of ones.P MFMAs: +4..7 % on the SDXL shapes (tools/attn_bench.py); 0 = matrix-pipe sums
 
+// the AttnP fields every launcher fills alike; each launcher sets nq, sc, causal and tbuf
+AttnP attn_params(const mlsd_attn_args* a)
+{
+    AttnP p;
+    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
+    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
+    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
+    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk;
+    p.G = a->n_head * a->n_batch;
+    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
+    return p;
+}
+
 bool attn_sp_takes(const mlsd_attn_args* a)
 {
     if (g_attn_sp < 0) { const char* e = getenv("MLSD_ATTN_SP"); g_attn_sp = (e && *e >= '0' && *e <= '2') ? *e - '0' : 1; }
@@ -1620,14 +1633,9 @@ bool attn_sp_takes(const mlsd_attn_args* a)
 
 int launch_attn64x2(const mlsd_attn_args* a, hipStream_t st)
 {
-    AttnP p; p.tbuf = nullptr;
-    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
-    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = 0;
+    AttnP p = attn_params(a); p.causal = 0; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt(64.0));
-    p.nq = a->Tq / 256; p.G = a->n_head * a->n_batch;
-    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
+    p.nq = a->Tq / 256;
     const dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * p.nq));
     if (attn_sp_takes(a)) {      // whole key tiles: the software-pipelined form
         if (a->d_head == 40) { p.sc = (float)(1.4426950408889634 / sqrt(40.0)); hipLaunchKernelGGL(attn64x2s_kernel<40>, grid, dim3(256), 0, st, p); }
@@ -1642,14 +1650,9 @@ int launch_attn64x2(const mlsd_attn_args* a, hipStream_t st)
 template <int DH>
 int launch_attn(const mlsd_attn_args* a, hipStream_t st)
 {
-    AttnP p; p.tbuf = nullptr;
-    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
-    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = a->causal;
+    AttnP p = attn_params(a); p.causal = a->causal; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
-    p.nq = (a->Tq + 127) / 128; p.G = a->n_head * a->n_batch;
-    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
+    p.nq = (a->Tq + 127) / 128;
     const dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * p.nq));
     if (g_attn_vsum) hipLaunchKernelGGL((attn_kernel<DH, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_kernel<DH, false>), grid, dim3(256), 0, st, p);
@@ -1663,14 +1666,9 @@ int g_attn_pp_prio = 0, g_attn_pp_dbg = 0;
 template <int NB, int WPS>
 int launch_attn64pp(const mlsd_attn_args* a, hipStream_t st)
 {
-    AttnP p; p.tbuf = nullptr;
-    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
-    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = g_attn_pp_dbg; p.tbuf = g_attn_tbuf;
+    AttnP p = attn_params(a); p.causal = g_attn_pp_dbg; p.tbuf = g_attn_tbuf;
     p.sc = (float)(1.4426950408889634 / sqrt(64.0));
-    p.nq = a->Tq / (256 * NB); p.G = a->n_head * a->n_batch;
-    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
+    p.nq = a->Tq / (256 * NB);
     const dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * p.nq));
     if (g_attn_pp_prio == 1) hipLaunchKernelGGL((attn64pp_kernel<NB, WPS, 1>), grid, dim3(512), 0, st, p);
     else if (g_attn_pp_prio == 2) hipLaunchKernelGGL((attn64pp_kernel<NB, WPS, 2>), grid, dim3(512), 0, st, p);
@@ -1682,14 +1680,8 @@ int launch_attn64pp(const mlsd_attn_args* a, hipStream_t st)
 template <int DH>
 int launch_attn_tk96(const mlsd_attn_args* a, hipStream_t st)
 {
-    AttnP p; p.tbuf = nullptr;
-    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
-    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = 0;
+    AttnP p = attn_params(a); p.causal = 0; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
-    p.G = a->n_head * a->n_batch;
-    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
     const int G8 = 8 * ((p.G + 7) / 8), nblk128 = (a->Tq + 127) / 128;
     // query blocks per workgroup: the keys are staged once per workgroup, so fewer, longer workgroups stage less -- as long as
     // the launch still holds >= 2 workgroups per CU to hide the Q / O latency of one behind the arithmetic of another
@@ -1711,14 +1703,8 @@ int launch_attn_ctx(const mlsd_attn_args* a, hipStream_t st)
 {
     constexpr int DQK = (DH + 15) / 16 * 16, NDV = (DH + 31) / 32;
     constexpr int ROWB = DQK * 2 + 16 + ((NDV & 1) ? NDV : NDV + 1) * 64;    // KSTR + VSTR of the kernel
-    AttnP p; p.tbuf = nullptr;
-    p.q = (const _Float16*)a->q; p.k = (const _Float16*)a->k; p.v = (const _Float16*)a->v; p.o = (_Float16*)a->out;
-    p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
-    p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
-    p.n_head = a->n_head; p.Tq = a->Tq; p.Tk = a->Tk; p.causal = 0;
+    AttnP p = attn_params(a); p.causal = 0; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
-    p.G = a->n_head * a->n_batch;
-    p.wide_o = g_attn_wide_o && !(a->ldo & 7) && !(a->bso & 7) && !((uintptr_t)a->out & 15);
     const int G8 = 8 * ((p.G + 7) / 8), nblk128 = (a->Tq + 127) / 128;
     int QB = 8;
     while (QB > 1 && (long)G8 * ((nblk128 + QB - 1) / QB) < 512) QB >>= 1;

@@ -1018,6 +1018,24 @@ int splitk_slices(const mlsd_gemm_args* a, int BK, int* kt_per_out)
     return (nkt + per - 1) / per;
 }
 
+// What one mlsd_gemm launch runs, decided once by resolve(): the launch and every query (mlsd_gemm_variant, _colstats_rows, _ln_fused,
+// _gn_fused, _xattn_fused, _splitk_parallel) read the same answer.
+enum GemmFamily { FAM_GENERAL, FAM_PP, FAM_PP_SK, FAM_SKINNY, FAM_TT, FAM_W4, FAM_SMALLN };
+enum SplitKForm { SPLITK_NONE, SPLITK_TWO_LAUNCH, SPLITK_INLINE, SPLITK_PAR };   // slices added by a second launch / by the last block of a tile / by all blocks of a tile
+struct GemmRoute {
+    int pick;               // pick_variant's answer: the tile asked for
+    int v;                  // kVariants index of the tile that launches, after every fall-back
+    GemmFamily fam;
+    int bk;
+    bool vec;               // general tiles: the wide (LDS-transposed) epilogue
+    int nsplit, kt_per;     // K slices over the grid (general tiles, skinny-M) and K tiles per slice
+    SplitKForm splitk;
+    int epi;                // ping-pong tiles: pp_epilogue_kind; 128x160: mlsd_gemm_tt_eligible's form
+    int stats_rows;         // rows per column-statistics block the launch writes (0: none)
+    int ln;                 // LayerNorm of the output: 1 at the end of the launch, 2 in the split-K reduce pass
+    bool gn, xattn;         // GroupNorm in the split-K reduce pass; cross attention at the end of the q projection
+};
+
 int g_gemm_ncu = 256;   // CUs a persistent launch may occupy (mlsd_gemm_set_cus: half-chip partitions run 128-block grids)
 int g_gemm_dbg = 0;
 unsigned long long* g_gemm_tbuf = nullptr;   // device buffer of 8 stamps per block (mlsd_gemm_set_trace)
@@ -1050,27 +1068,17 @@ bool splitk_par_ok(const mlsd_gemm_args* a, int BM, int nsplit, long tiles)
     return tiles * nsplit <= (long)cus * (BM == 64 ? 3 : 2);
 }
 
-// Rows per column-statistics block a launch of the GENERAL tiles would write for `a` (0: none).  Non-split: the wide epilogue of gemm_kernel sums per wave (WM rows);
-// split-K: splitk_reduce_stats (32 rows).  Needs the wide epilogue (alignment), an fp32 output, whole 64-column slabs per wave (even TN) and no fused norm.
-int general_stats_rows(const mlsd_gemm_args* a, int WM, int TN, int BK)
+// The operand alignment of the wide epilogues (16-byte fp32 / 8-byte fp16 rows, strides in multiples of 4 elements).  Each caller adds its own
+// terms: the output width (nout, N) and the g_gemm_epi switch.
+bool wide_epilogue_ok(const mlsd_gemm_args* a)
 {
-    if (!a->colstats || ((uintptr_t)a->colstats & 15) || !a->C32 || a->act == MLSD_ACT_GEGLU || a->ln_y16 || a->gn_y16 || (TN & 1) || (a->N & 3)) return 0;
-    const bool vec = !(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15) && (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) &&
-                     (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) && (!a->bias || !((uintptr_t)a->bias & 15)) &&
-                     (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
-    if (!vec || g_gemm_sk_inline) return 0;
-    const int nsplit = splitk_slices(a, BK, nullptr);
-    if (nsplit > 1) {
-#ifdef MLSD_GEMM_EXPERIMENTS
-        if (sk_par_on()) return 0;          // (the slices may be added inside the launch: no reduce pass)
-#endif
-        return 32;
-    }
-    return WM;
+    return (!a->C32 || (!(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15))) && (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) &&
+           (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) && (!a->bias || !((uintptr_t)a->bias & 15)) &&
+           (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15)));
 }
 
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, bool REG = false>
-int launch(const mlsd_gemm_args* a, hipStream_t st)
+int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 {
     GemmP p;
     p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
@@ -1081,28 +1089,18 @@ int launch(const mlsd_gemm_args* a, hipStream_t st)
     p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
     p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
     p.nbm = (a->M + BM - 1) / BM; p.nbn = (a->N + BN - 1) / BN;
-    {
-        const int nout = a->act == MLSD_ACT_GEGLU ? a->N / 2 : a->N;
-        p.vec = !(nout & 3) && !(a->N & 3) && (!a->C32 || (!(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15))) &&
-                (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) && (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) &&
-                (!a->bias || !((uintptr_t)a->bias & 15)) && (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
-    }
+    p.vec = r.vec;
     p.dbg = g_gemm_dbg; p.tbuf = nullptr; p.colstats = nullptr; p.cs_shift = a->colstats_shift ? 1 : 0; p.sk_L = 0; p.sk_ws = nullptr; p.sk_flag = nullptr;
     p.gw = g_gemm_panel;
-    int kt_per;
-    const int nsplit = p.vec ? splitk_slices(a, BK, &kt_per) : 1;
-    p.kt_per = nsplit > 1 ? kt_per : (a->K + BK - 1) / BK;
+    const int nsplit = r.nsplit;
+    p.kt_per = r.kt_per;
     p.ws_stride = 0;
-    // column statistics for a consuming GroupNorm (general_stats_rows: the same conditions mlsd_gemm_colstats_rows promised the planner): one K slice -> this kernel's
-    // epilogue (blocks of WM rows); split-K -> the reduce pass (blocks of 32 rows)
-    const int st_rows = a->colstats ? general_stats_rows(a, BM / WAVES_M, (BN / WAVES_N) / 32, BK) : 0;
-    if (st_rows > 0 && nsplit == 1) p.colstats = a->colstats;
+    // column statistics for a consuming GroupNorm: one K slice -> this kernel's epilogue (blocks of WM rows); split-K -> the reduce pass (blocks of 32 rows)
+    if (r.stats_rows > 0 && nsplit == 1) p.colstats = a->colstats;
     GemmP pe = p;                                  // the epilogue as requested (second pass of a split-K launch)
-    if (st_rows > 0 && nsplit > 1) pe.colstats = a->colstats;
+    if (r.stats_rows > 0 && nsplit > 1) pe.colstats = a->colstats;
     // reduced inside the launch: one counter per output tile (a->sk_flags, 4096 words, zero between launches), one slab per (tile, slice)
-    const bool inl = nsplit > 1 && g_gemm_sk_inline && a->sk_flags && (long)p.nbm * p.nbn <= 4095 &&        /* (word 4095 is the sticky give-up indicator of the stream-K hand-offs) */
-                     !((uintptr_t)a->ws & 15) &&
-                     a->ws_bytes >= (size_t)nsplit * p.nbm * p.nbn * BM * BN * sizeof(float);
+    const bool inl = r.splitk == SPLITK_INLINE;
     if (inl) { p.sk_L = nsplit; p.sk_ws = (float*)a->ws; p.sk_flag = a->sk_flags; }
     else if (nsplit > 1) {
         const size_t need = (size_t)nsplit * a->M * a->N * sizeof(float);
@@ -1120,7 +1118,7 @@ int launch(const mlsd_gemm_args* a, hipStream_t st)
     // ---- slices added in the launch by the blocks of the tile together (gemm_kernel PAR): the small tiles of the split-K launches, whole grid resident
 #ifdef MLSD_GEMM_EXPERIMENTS   /* measured SLOWER than the second launch (SD1.5 b1 evaluation 7.17 -> 7.76 ms, profiles/NOTES.md): a dispatch boundary is the cheaper grid barrier */
     if constexpr ((BM == 64 || BM == 128) && BN == 128 && BK == 64 && NSTAGE == 2 && !REG) {
-        if (nsplit > 1 && !inl && splitk_par_ok(a, BM, nsplit, p.nbm * p.nbn)) {
+        if (r.splitk == SPLITK_PAR) {
             p.sk_flag = a->sk_flags;
             auto kfn = a->conv ? gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, true> : gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, false, true>;
             if (LDS > 65536) MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
@@ -1132,17 +1130,17 @@ int launch(const mlsd_gemm_args* a, hipStream_t st)
     auto go = [&](auto kfn) -> int {
         if (LDS > 65536) MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
         hipLaunchKernelGGL(kfn, grid, block, LDS, st, p, pe);
-        if (nsplit > 1 && !inl) {
+        if (r.splitk == SPLITK_TWO_LAUNCH) {
             const long n = (long)a->M * (a->N >> 2);
 #ifdef MLSD_GEMM_EXPERIMENTS
-            if (a->gn_y16) {       // the reduce pass ends with the GroupNorm of its (image, group) slabs (mlsd_gemm_gn_fused; mlsd_gemm checked that this launch qualifies)
+            if (r.gn) {            // the reduce pass ends with the GroupNorm of its (image, group) slabs
                 GemmP pl = pe;
                 pl.ln_g = a->gn_gamma; pl.ln_b = a->gn_beta; pl.ln_eps = a->gn_eps; pl.ln_y = (_Float16*)a->gn_y16; pl.ldln = a->gn_ldy;
                 pl.gn_G = a->gn_groups; pl.gn_hw = a->gn_hw; pl.gn_silu = a->gn_silu;
                 hipLaunchKernelGGL(splitk_reduce_gn, dim3((unsigned)a->gn_groups, (unsigned)(a->M / a->gn_hw)), dim3(256), 0, st, pl, (const float*)a->ws, nsplit);
             } else
 #endif
-            if (a->ln_y16) {       // the reduce pass ends with the LayerNorm of its rows (mlsd_gemm_ln_fused == 2; mlsd_gemm checked that this launch qualifies)
+            if (r.ln == 2) {       // the reduce pass ends with the LayerNorm of its rows
                 GemmP pl = pe;
                 pl.ln_g = a->ln_gamma; pl.ln_b = a->ln_beta; pl.ln_eps = a->ln_eps; pl.ln_y = (_Float16*)a->ln_y16; pl.ldln = a->ldln;
                 hipLaunchKernelGGL(splitk_reduce_ln, dim3((unsigned)a->M), dim3((unsigned)(((a->N >> 2) + 63) / 64 * 64)), 0, st, pl, (const float*)a->ws, nsplit);
@@ -1160,7 +1158,6 @@ int launch(const mlsd_gemm_args* a, hipStream_t st)
     if constexpr (((BN / WAVES_N) / 32) % 2 == 0 && !REG) {       // the statistics builds (whole 64-column wave slabs)
         if (p.colstats) return a->conv ? go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, false, true>) : go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, false, false, true>);
     }
-    p.colstats = nullptr;
     return a->conv ? go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, REG>) : go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, REG>);
 }
 
@@ -1194,9 +1191,7 @@ bool pp_eligible(const mlsd_gemm_args* a, int BM, int BN)
     if (a->rowbias && ((a->rows_per_batch > 0 ? a->rows_per_batch : 1) % BM)) return false;
     if (a->act == MLSD_ACT_GEGLU && BN != 256) return false;
     const int nout = a->act == MLSD_ACT_GEGLU ? a->N / 2 : a->N;
-    return !(nout & 3) && (!a->C32 || (!(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15))) && (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) &&
-           (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) && (!a->bias || !((uintptr_t)a->bias & 15)) &&
-           (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
+    return !(nout & 3) && wide_epilogue_ok(a) && g_gemm_epi != 1;
 }
 
 // launches that can END with the LayerNorm of their output (gemm_pp.hpp *_LN): linear, 128 x 320 ping-pong tile made of WHOLE tiles, all of them resident at
@@ -1275,7 +1270,7 @@ bool sk_eligible(const mlsd_gemm_args* a, int BM, int BN, bool ignore_stats = fa
 }
 
 template <int BM, int BN, int CB0, int CB1, bool RESBATCH, bool SK = false, int NPH = 4, int SCH = 0>
-int launch_pp(const mlsd_gemm_args* a, hipStream_t st)
+int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 {
     constexpr int BK = 64;
     GemmP p;
@@ -1318,7 +1313,7 @@ int launch_pp(const mlsd_gemm_args* a, hipStream_t st)
         return mlsd_check_launch("gemm_pp_kernel(+attention)");
     };
     // the epilogue the kernel is built with (gemm_pp.hpp): the bulk launches of the UNet / VAE have no activation in the GEMM
-    const int epi = pp_epilogue_kind(a, BN);
+    const int epi = r.epi;
     p.colstats = (epi == PP_EPI_F32_STATS || epi == PP_EPI_F32_RES_STATS) ? a->colstats : nullptr;
     p.cs_shift = a->colstats_shift ? 1 : 0;
     if constexpr (SK) {       // the stream-K builds: the fp32 epilogues of the long-K convs / feed-forward outputs, fp16 for the fused projections
@@ -1381,9 +1376,7 @@ bool skinny_eligible(const mlsd_gemm_args* a)
 {
     if (a->M > 128 || a->act == MLSD_ACT_GEGLU || (a->K & 63) || a->K < 128 || (a->N & 3) || !a->ws || ((uintptr_t)a->ws & 15)) return false;
     if (a->conv && (a->upsample || (a->Cin & 63) || a->KH * a->KW > 9)) return false;
-    return (!a->C32 || (!(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15))) && (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) &&
-           (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) && (!a->bias || !((uintptr_t)a->bias & 15)) &&
-           (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15)));
+    return wide_epilogue_ok(a);
 }
 
 int skinny_slices(const mlsd_gemm_args* a, int* kt_per_out)
@@ -1398,7 +1391,7 @@ int skinny_slices(const mlsd_gemm_args* a, int* kt_per_out)
     return (nkt + per - 1) / per;
 }
 
-int launch_skinny(const mlsd_gemm_args* a, hipStream_t st)
+int launch_skinny(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 {
     GemmP p;
     memset(&p, 0, sizeof(p));
@@ -1407,11 +1400,10 @@ int launch_skinny(const mlsd_gemm_args* a, hipStream_t st)
     p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
     p.stride = a->stride; p.pad = a->pad; p.ups = 0;
     p.rows_per_batch = 1; p.vec = 1; p.gw = 0;
-    int kt_per;
-    const int nsplit = skinny_slices(a, &kt_per);
+    const int nsplit = r.nsplit;
     const size_t need = (size_t)nsplit * a->M * a->N * sizeof(float);
     if (a->ws_bytes < need) return mlsd_set_error(-1, "mlsd_gemm: skinny-M workspace too small (%zu < %zu)", (size_t)a->ws_bytes, need);
-    p.kt_per = kt_per; p.C32 = (float*)a->ws; p.ldc32 = a->N; p.ws_stride = (long)a->M * a->N;
+    p.kt_per = r.kt_per; p.C32 = (float*)a->ws; p.ldc32 = a->N; p.ws_stride = (long)a->M * a->N;
     GemmP pe = p;                                  // the epilogue as requested: applied by splitk_reduce
     pe.bias = a->bias; pe.biasm = a->bias_m; pe.act_post = a->act_after_resid; pe.rowbias = a->rowbias; pe.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
     pe.ldrb = a->ldrb; pe.resid = a->resid; pe.ldr = a->ldr; pe.act = a->act;
@@ -1461,42 +1453,43 @@ extern "C" int mlsd_conv_smalln(const mlsd_gemm_args* a, void* stream);
 // more than the device has (a partitioned device); the dry runtime has no device and plans for the full part
 static int tt_ncu() { if (mlsd_runtime_is_dry()) return g_gemm_ncu; const int c = device_cus(); return c < g_gemm_ncu ? c : g_gemm_ncu; }
 
-struct Variant { const char* name; int bm, bn, slots; };
+// bk: K tile; wave_m x wave_n: the rows x columns of one wave (general tiles, 0 otherwise); reg: register-staged (no column-statistics build)
+struct Variant { const char* name; int bm, bn, slots, bk, wave_m, wave_n; bool reg; };
 const Variant kVariants[] = {
-    {"128x128x64s2", 128, 128, 512},   // 0: 64 KB ring, 2 blocks/CU
-    {"64x128x64s2", 64, 128, 768},     // 1: small M
-    {"128x128x32s4", 128, 128, 512},   // 2: 4-deep ring of 16 KB stages, 2 blocks/CU
-    {"256x128x64s2", 256, 128, 256},   // 3: 8 waves, 96 KB, 1 block/CU
-    {"256x128x32s3", 256, 128, 512},   // 4: 8 waves, 3-deep ring of 24 KB stages (72 KB), 2 blocks/CU
-    {"128x128x64s3", 128, 128, 256},   // 5: 3-deep ring, 96 KB, 1 block/CU
-    {"256x256x32s3", 256, 256, 256},   // 6: 8 waves (wave tile 128x64), 96 KB
-    {"256x128x32s4", 256, 128, 256},   // 7: 4-deep, 96 KB
-    {"256x256x32s3w16", 256, 256, 256}, // 8: 16 waves (4x4, wave tile 64x64), 96 KB ring, 1 block/CU
-    {"256x256x64s2w16", 256, 256, 256}, // 9: 16 waves, 128 KB ring
-    {"256x256x32s4w16", 256, 256, 256}, // 10: 16 waves, 4-deep 128 KB ring
-    {"256x256x64s2w8", 256, 256, 256},  // 11: 8 waves (2x4, wave tile 128x64), 128 KB ring
-    {"256x256x32s4w8", 256, 256, 256},  // 12: 8 waves, 4-deep ring of 32 KB stages
-    {"256x256x64r2w16", 256, 256, 256}, // 13: as 9 but register-staged tiles (global_load -> ds_write)
-    {"128x128x64r2", 128, 128, 512},    // 14: as 0 but register-staged
-    {"256x128x64r2", 256, 128, 256},    // 15: as 3 but register-staged
-    {"128x320x64s2", 128, 320, 256},    // 16: 8 waves (4x2, wave tile 32x160): N = 1280 / 640 outputs in exactly 4 / 2 tile columns
-    {"256x256x64pp", 256, 256, 256},    // 17: 8 waves in two ping-pong groups, 16x16x32 MFMA, 4 phases per K tile (gemm_pp.hpp)
-    {"128x320x64pp", 128, 320, 256},    // 18: the same structure on the 128x320 tile (wave 64x80)
-    {"256x256x64ppsk", 256, 256, 256},  // 19: variant 17 as STREAM-K: the launch's K-tile units dealt evenly over the 256 blocks, partial tiles combined in-launch
-    {"128x320x64pp2", 128, 320, 256},   // 20: variant 18 with TWO phases per K tile (20 MFMAs per barrier-to-barrier section instead of 8 / 12)
-    {"256x256x64pp2", 256, 256, 256},   // 21: variant 17 with two phases per K tile (32 MFMAs per section)
-    {"128x320x64ppb", 128, 320, 256},   // 22: variant 18 on the re-balanced staging schedule (gemm_pp.hpp SCH = 1)
-    {"64x128x64s3", 64, 128, 512},      // 23: variant 1 with a 3-deep ring (72 KB, 2 blocks/CU): two K tiles in flight per block for grids that leave CUs half empty
-    {"64x128x64r2", 64, 128, 768},      // 24: variant 1 register-staged (global_load -> ds_write): small grids are bound by the per-CU LDS-DMA issue rate
-    {"256x128x64pp2", 256, 128, 256},   // 25: ping-pong tile for NARROW outputs (N = 128: the VAE's full-resolution convolutions), wave 128 x 32, two phases per K tile (16 MFMAs per section)
-    {"256x256x64w4", 256, 256, 256},    // 26: ONE wave per SIMD (4 waves of 128 x 128, accumulators in AGPRs, software-pipelined inside the wave): gemm_w4.hip
-    {"128x320x64w4", 128, 320, 256},    // 27: the same on the 128 x 320 tile (4 waves of 64 x 160)
-    {"128x320x64ppsk", 128, 320, 256},  // 28: variant 18 as STREAM-K (round 4): N = 320 / 640 / 1280 outputs with FEW tiles and long K -- the 3x3 convolutions of SD1.5 batch 1
+    {"128x128x64s2", 128, 128, 512, 64, 64, 64},   // 0: 64 KB ring, 2 blocks/CU
+    {"64x128x64s2", 64, 128, 768, 64, 32, 64},     // 1: small M
+    {"128x128x32s4", 128, 128, 512, 32, 64, 64},   // 2: 4-deep ring of 16 KB stages, 2 blocks/CU
+    {"256x128x64s2", 256, 128, 256, 64, 64, 64},   // 3: 8 waves, 96 KB, 1 block/CU
+    {"256x128x32s3", 256, 128, 512, 32, 64, 64},   // 4: 8 waves, 3-deep ring of 24 KB stages (72 KB), 2 blocks/CU
+    {"128x128x64s3", 128, 128, 256, 64, 64, 64},   // 5: 3-deep ring, 96 KB, 1 block/CU
+    {"256x256x32s3", 256, 256, 256, 32, 128, 64},   // 6: 8 waves (wave tile 128x64), 96 KB
+    {"256x128x32s4", 256, 128, 256, 32, 64, 64},   // 7: 4-deep, 96 KB
+    {"256x256x32s3w16", 256, 256, 256, 32, 64, 64}, // 8: 16 waves (4x4, wave tile 64x64), 96 KB ring, 1 block/CU
+    {"256x256x64s2w16", 256, 256, 256, 64, 64, 64}, // 9: 16 waves, 128 KB ring
+    {"256x256x32s4w16", 256, 256, 256, 32, 64, 64}, // 10: 16 waves, 4-deep 128 KB ring
+    {"256x256x64s2w8", 256, 256, 256, 64, 128, 64},  // 11: 8 waves (2x4, wave tile 128x64), 128 KB ring
+    {"256x256x32s4w8", 256, 256, 256, 32, 128, 64},  // 12: 8 waves, 4-deep ring of 32 KB stages
+    {"256x256x64r2w16", 256, 256, 256, 64, 64, 64, true}, // 13: as 9 but register-staged tiles (global_load -> ds_write)
+    {"128x128x64r2", 128, 128, 512, 64, 64, 64, true},    // 14: as 0 but register-staged
+    {"256x128x64r2", 256, 128, 256, 64, 64, 64, true},    // 15: as 3 but register-staged
+    {"128x320x64s2", 128, 320, 256, 64, 32, 160},    // 16: 8 waves (4x2, wave tile 32x160): N = 1280 / 640 outputs in exactly 4 / 2 tile columns
+    {"256x256x64pp", 256, 256, 256, 64, 0, 0},    // 17: 8 waves in two ping-pong groups, 16x16x32 MFMA, 4 phases per K tile (gemm_pp.hpp)
+    {"128x320x64pp", 128, 320, 256, 64, 0, 0},    // 18: the same structure on the 128x320 tile (wave 64x80)
+    {"256x256x64ppsk", 256, 256, 256, 64, 0, 0},  // 19: variant 17 as STREAM-K: the launch's K-tile units dealt evenly over the 256 blocks, partial tiles combined in-launch
+    {"128x320x64pp2", 128, 320, 256, 64, 0, 0},   // 20: variant 18 with TWO phases per K tile (20 MFMAs per barrier-to-barrier section instead of 8 / 12)
+    {"256x256x64pp2", 256, 256, 256, 64, 0, 0},   // 21: variant 17 with two phases per K tile (32 MFMAs per section)
+    {"128x320x64ppb", 128, 320, 256, 64, 0, 0},   // 22: variant 18 on the re-balanced staging schedule (gemm_pp.hpp SCH = 1)
+    {"64x128x64s3", 64, 128, 512, 64, 32, 64},      // 23: variant 1 with a 3-deep ring (72 KB, 2 blocks/CU): two K tiles in flight per block for grids that leave CUs half empty
+    {"64x128x64r2", 64, 128, 768, 64, 32, 64, true},      // 24: variant 1 register-staged (global_load -> ds_write): small grids are bound by the per-CU LDS-DMA issue rate
+    {"256x128x64pp2", 256, 128, 256, 64, 0, 0},   // 25: ping-pong tile for NARROW outputs (N = 128: the VAE's full-resolution convolutions), wave 128 x 32, two phases per K tile (16 MFMAs per section)
+    {"256x256x64w4", 256, 256, 256, 64, 0, 0},    // 26: ONE wave per SIMD (4 waves of 128 x 128, accumulators in AGPRs, software-pipelined inside the wave): gemm_w4.hip
+    {"128x320x64w4", 128, 320, 256, 64, 0, 0},    // 27: the same on the 128 x 320 tile (4 waves of 64 x 160)
+    {"128x320x64ppsk", 128, 320, 256, 64, 0, 0},  // 28: variant 18 as STREAM-K (round 4): N = 320 / 640 / 1280 outputs with FEW tiles and long K -- the 3x3 convolutions of SD1.5 batch 1
                                         //     (8192x320x2880: 64 tiles, 2048x640x5760: 32, 512x1280x11520: 16) -- dealt over all 256 CUs in K-tile units
-    {"skinny128x64", 128, 64, 512},     // 29: M <= 128 weight streaming (gemm_skinny.hpp): all rows in one block, weights global -> registers, 7 K steps in flight, K slices + fixed-order reduce
-    {"128x160x64tt", 128, 160, 512},    // 30: TWO tiles in flight per CU (gemm_tt.hip, round 5): 4-wave blocks, two resident per CU in two priority classes, so that one tile's residual
+    {"skinny128x64", 128, 64, 512, 64, 0, 0},     // 29: M <= 128 weight streaming (gemm_skinny.hpp): all rows in one block, weights global -> registers, 7 K steps in flight, K slices + fixed-order reduce
+    {"128x160x64tt", 128, 160, 512, 64, 0, 0},    // 30: TWO tiles in flight per CU (gemm_tt.hip, round 5): 4-wave blocks, two resident per CU in two priority classes, so that one tile's residual
                                         //     read / output burst runs under the other tile's K loop -- the single-round 8192 x 1280 outputs of the SDXL transformer blocks
-    {"conv3x3n16", 64, 16, 512},        // 31: 3x3 convolutions with Cout <= 16 over full-resolution maps (the VAE / TAESD output layers) as a STREAMING op (conv_smalln.hip, round 6): every wave walks
+    {"conv3x3n16", 64, 16, 512, 64, 0, 0},        // 31: 3x3 convolutions with Cout <= 16 over full-resolution maps (the VAE / TAESD output layers) as a STREAMING op (conv_smalln.hip, round 6): every wave walks
                                         //     a 16-pixel strip with a ring of input rows in its own LDS slice, weights in registers, one pass over the activations
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
@@ -1521,6 +1514,104 @@ int pick_variant(const mlsd_gemm_args* a)
     return 0;
 }
 
+// Rows per column-statistics block a general tile writes for `a` (0: none).  One K slice: the wide epilogue of gemm_kernel's ST build sums per wave (wave_m
+// rows; whole 64-column wave slabs, not register-staged); split-K: splitk_reduce_stats (32 rows).  Needs the wide epilogue, an fp32 output and no fused norm.
+int general_stats_rows(const mlsd_gemm_args* a, const GemmRoute& r, const Variant& t)
+{
+    if (!a->colstats || ((uintptr_t)a->colstats & 15) || !a->C32 || a->act == MLSD_ACT_GEGLU || a->ln_y16 || a->gn_y16 || ((t.wave_n / 32) & 1) || (a->N & 3)) return 0;
+    if (!r.vec || g_gemm_sk_inline) return 0;
+    if (r.nsplit > 1) {
+#ifdef MLSD_GEMM_EXPERIMENTS
+        if (sk_par_on()) return 0;          // (the slices may be added inside the launch: no reduce pass)
+#endif
+        return 32;
+    }
+    return t.reg ? 0 : t.wave_m;
+}
+
+// The one place that decides what a launch of `a` runs: the tile pick_variant asks for, then the fall-back chain down to a tile that takes the arguments
+// in this build, then everything that tile's launcher does with them.
+GemmRoute resolve(const mlsd_gemm_args* a)
+{
+    GemmRoute r{};
+    r.pick = pick_variant(a);
+    int v = r.pick;
+    GemmFamily fam = FAM_GENERAL;
+    switch (v) {
+    case 26: case 27:       // one wave per SIMD (EXPERIMENTS builds); anything else: the ping-pong tile of the same shape
+        if (mlsd_gemm_w4_eligible(a, v - 26)) fam = FAM_W4; else v = v == 26 ? 17 : 18;
+        break;
+    case 19: if (sk_eligible(a, 256, 256)) fam = FAM_PP_SK; else v = 17; break;
+    case 28: if (sk_eligible(a, 128, 320)) fam = FAM_PP_SK; else v = 18; break;
+    case 29: if (skinny_eligible(a)) fam = FAM_SKINNY; else v = 1; break;
+    case 30: if ((r.epi = mlsd_gemm_tt_eligible(a, tt_ncu()))) fam = FAM_TT; else v = 18; break;      // (else: the ping-pong tile nearest in shape)
+    case 31: if (mlsd_conv_smalln_eligible(a)) fam = FAM_SMALLN; else v = 0; break;
+#ifndef MLSD_GEMM_EXPERIMENTS   /* variants that lost their study on MI355X are not in the product build: the product tile nearest in shape runs */
+    case 22: v = 18; break;
+    case 25: v = 3; break;
+    case 2: case 5: case 6: case 7: case 8: case 10: case 11: case 12: case 13: case 14: case 15: case 23: case 24: v = 0; break;
+#endif
+    default: break;
+    }
+    if (fam == FAM_GENERAL && (v == 17 || v == 18 || v == 20 || v == 21 || v == 22 || v == 25)) {     // ping-pong tiles: else the general tile of the same shape
+        if (pp_eligible(a, kVariants[v].bm, kVariants[v].bn)) fam = FAM_PP;
+        else v = kVariants[v].bn == 256 ? 9 : kVariants[v].bn == 320 ? 16 : 3;
+    }
+    const Variant& t = kVariants[v];
+    r.v = v; r.fam = fam; r.bk = t.bk;
+    r.nsplit = 1; r.kt_per = (a->K + t.bk - 1) / t.bk;
+    switch (fam) {
+    case FAM_GENERAL: {
+        const int nout = a->act == MLSD_ACT_GEGLU ? a->N / 2 : a->N;
+        r.vec = !(nout & 3) && !(a->N & 3) && wide_epilogue_ok(a) && g_gemm_epi != 1;
+        int per;
+        if (r.vec && (r.nsplit = splitk_slices(a, t.bk, &per)) > 1) {
+            r.kt_per = per;
+            const long tiles = (long)((a->M + t.bm - 1) / t.bm) * ((a->N + t.bn - 1) / t.bn);
+            if (g_gemm_sk_inline && a->sk_flags && tiles <= 4095 && !((uintptr_t)a->ws & 15) &&        /* (word 4095 is the sticky give-up indicator of the stream-K hand-offs) */
+                a->ws_bytes >= (size_t)r.nsplit * tiles * t.bm * t.bn * sizeof(float))
+                r.splitk = SPLITK_INLINE;
+            else if ((v == 0 || v == 1) && splitk_par_ok(a, t.bm, r.nsplit, tiles)) r.splitk = SPLITK_PAR;   // (the two tiles built with PAR)
+            else r.splitk = SPLITK_TWO_LAUNCH;
+        }
+        r.stats_rows = general_stats_rows(a, r, t);
+        // the reduce pass of a split-K launch on tiles 0 / 1 can end with the LayerNorm of its rows (splitk_reduce_ln: one block per row; no in-launch hand-off)
+        const bool reduce_norm = (v == 0 || v == 1) && r.splitk == SPLITK_TWO_LAUNCH && !g_gemm_sk_inline && a->C32 && !a->C16;
+        if (reduce_norm && a->ln_y16 && a->ln_gamma && a->ln_beta && a->N <= 4096 && !(a->ldln & 3) && !((uintptr_t)a->ln_y16 & 7) &&
+            !((uintptr_t)a->ln_gamma & 15) && !((uintptr_t)a->ln_beta & 15))
+            r.ln = 2;
+#ifdef MLSD_GEMM_EXPERIMENTS
+        /* ... or with the GroupNorm of its (image, group) slabs.  Measured SLOWER than splitk_reduce + the one-dispatch GroupNorm on every map size of the SD1.5 b1
+         * plan (evaluation 6.84 -> 6.88 / 6.90 ms, profiles/NOTES.md): the reduce then runs on 64 blocks (one per image and group) instead of 640.  Only in EXPERIMENTS builds. */
+        if (reduce_norm && a->gn_y16 && !a->ln_y16 && !a->colstats && a->gn_gamma && a->gn_beta && a->gn_groups > 0 && a->gn_hw > 0 && !(a->N % a->gn_groups) && !(a->M % a->gn_hw)) {
+            const int cg = a->N / a->gn_groups;
+            r.gn = !(cg & 3) && (long)a->gn_hw * (cg >> 2) <= 256L * GNR_MAXI && !(a->gn_ldy & 3) && !((uintptr_t)a->gn_y16 & 7) && !((uintptr_t)a->gn_gamma & 15) &&
+                   !((uintptr_t)a->gn_beta & 15);
+        }
+#endif
+        break;
+    }
+    case FAM_PP: case FAM_PP_SK:
+        r.epi = pp_epilogue_kind(a, t.bn);
+        if (r.epi == PP_EPI_F32_STATS || r.epi == PP_EPI_F32_RES_STATS) r.stats_rows = t.bm / 2;
+        // the *_LN and cross-attention endings are built for the four-phase 128x320 tile only, and are fused where that tile was asked for (a tile that
+        // falls back to it keeps the separate launch); a forced tile never fuses the attention
+        r.ln = fam == FAM_PP && r.pick == 18 && (r.epi == PP_EPI_F32_LN || r.epi == PP_EPI_F32_RES_LN);
+        r.xattn = fam == FAM_PP && r.pick == 18 && r.epi == PP_EPI_XATTN && g_gemm_variant < 0;
+        break;
+    case FAM_SKINNY:        // the K slices always go through the workspace and splitk_reduce, one slice included
+        r.nsplit = skinny_slices(a, &r.kt_per);
+        r.splitk = SPLITK_TWO_LAUNCH;
+        break;
+    case FAM_TT: r.ln = r.epi >= 4 && r.epi <= 7; break;      // (TT_F32_LN / TT_F32_RES_LN / TT_CHAIN_*)
+    case FAM_W4: case FAM_SMALLN: break;
+    }
+    /* a stream-K convolution and the 128x160 tile have no statistics epilogue: handing them a GroupNorm's statistics would silently turn them into a plain ping-pong
+     * launch (round 3 shipped exactly that: 24 tiles on 256 CUs, SD1.5's 2048x640x17280 at 366 us).  They keep their tile; the GroupNorm keeps its first pass. */
+    if (((r.pick == 19 || r.pick == 28) && a->conv && sk_eligible(a, kVariants[r.pick].bm, kVariants[r.pick].bn, true)) || r.pick == 30) r.stats_rows = 0;
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1538,88 +1629,61 @@ MLSD_API int mlsd_gemm(const mlsd_gemm_args* a, void* stream)
     }
     if (a->act == MLSD_ACT_GEGLU && (a->N & 63)) return mlsd_set_error(-1, "mlsd_gemm: GEGLU needs N %% 64 == 0");
     if (!a->C32 && !a->C16 && !a->xa_k) return mlsd_set_error(-1, "mlsd_gemm: no output");
-    if (a->colstats && a->colstats_rows > 0 && mlsd_gemm_colstats_rows(a) != a->colstats_rows)
+    const GemmRoute r = resolve(a);
+    if (a->colstats && a->colstats_rows > 0 && r.stats_rows != a->colstats_rows)
         return mlsd_set_error(-1, "mlsd_gemm: a GroupNorm was planned on this launch's column statistics (blocks of %d rows) but the launch "
-                              "would write %d-row blocks / none: tile or epilogue settings changed after planning", a->colstats_rows, mlsd_gemm_colstats_rows(a));
-    if (a->gn_y16 && !mlsd_gemm_gn_fused(a))
+                              "would write %d-row blocks / none: tile or epilogue settings changed after planning", a->colstats_rows, r.stats_rows);
+    if (a->gn_y16 && !r.gn)
         return mlsd_set_error(-1, "mlsd_gemm: the plan dropped a GroupNorm for this launch's reduce pass but the launch would not run it (tile or K-split settings changed after planning)");
-    if (a->xa_k && !mlsd_gemm_xattn_fused(a))
+    if (a->xa_k && !r.xattn)
         return mlsd_set_error(-1, "mlsd_gemm: the plan dropped a cross attention for this projection's launch but the launch would not run it (tile settings changed after planning)");
-    if (a->ln_y16 && !mlsd_gemm_ln_fused(a))
+    if (a->ln_y16 && !r.ln)
         return mlsd_set_error(-1, "mlsd_gemm: the plan dropped a LayerNorm for this launch's *_LN epilogue but the launch would not run it (tile or epilogue settings changed after planning)");
     hipStream_t st = (hipStream_t)stream;
-    switch (pick_variant(a)) {
-    case 1: return launch<64, 128, 64, 2, 2, 2>(a, st);
-    case 3: return launch<256, 128, 64, 4, 2, 2>(a, st);
-    case 4: return launch<256, 128, 32, 4, 2, 3>(a, st);
-    case 9: return launch<256, 256, 64, 4, 4, 2>(a, st);
-    case 27:
-        if (mlsd_gemm_w4_eligible(a, 1)) return mlsd_gemm_w4(a, 1, st, g_gemm_ncu);
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true>(a, st);      // anything else: the ping-pong tile of the same shape
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
-    case 26:
-        if (mlsd_gemm_w4_eligible(a, 0)) return mlsd_gemm_w4(a, 0, st, g_gemm_ncu);
-        [[fallthrough]];                                                    // anything else: the ping-pong tile of the same shape
-    case 17: return pp_eligible(a, 256, 256) ? launch_pp<256, 256, 2, 2, false>(a, st) : launch<256, 256, 64, 4, 4, 2>(a, st);
-    case 19:
-        if (sk_eligible(a, 256, 256)) return launch_pp<256, 256, 2, 2, false, true>(a, st);
-        return pp_eligible(a, 256, 256) ? launch_pp<256, 256, 2, 2, false>(a, st) : launch<256, 256, 64, 4, 4, 2>(a, st);
-    case 29:
-        if (skinny_eligible(a)) return launch_skinny(a, st);
-        return launch<64, 128, 64, 2, 2, 2>(a, st);
-    case 30:
-        if (mlsd_gemm_tt_eligible(a, tt_ncu())) return mlsd_gemm_tt(a, st, tt_ncu());
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true>(a, st);      // anything else: the ping-pong tile nearest in shape
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
-    case 31:
-        if (mlsd_conv_smalln_eligible(a)) return mlsd_conv_smalln(a, st);
-        return launch<128, 128, 64, 2, 2, 2>(a, st);
-    case 28:
-        if (sk_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true, true>(a, st);
-        [[fallthrough]];
-    case 18:
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true>(a, st);
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
-    case 20:
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true, false, 2>(a, st);
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
+    switch (r.fam) {
+    case FAM_W4: return mlsd_gemm_w4(a, r.v - 26, st, g_gemm_ncu);
+    case FAM_TT: return mlsd_gemm_tt(a, st, tt_ncu());
+    case FAM_SMALLN: return mlsd_conv_smalln(a, st);
+    case FAM_SKINNY: return launch_skinny(a, r, st);
+    case FAM_PP_SK: return r.v == 19 ? launch_pp<256, 256, 2, 2, false, true>(a, r, st) : launch_pp<128, 320, 3, 2, true, true>(a, r, st);
+    case FAM_PP:
+        switch (r.v) {
+        case 17: return launch_pp<256, 256, 2, 2, false>(a, r, st);
+        case 20: return launch_pp<128, 320, 3, 2, true, false, 2>(a, r, st);
+        case 21: return launch_pp<256, 256, 2, 2, false, false, 2>(a, r, st);
 #ifdef MLSD_GEMM_EXPERIMENTS   /* measured and not adopted (profiles/NOTES.md): the re-balanced staging schedule, the narrow 256x128 ping-pong tile */
-    case 22:
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true, false, 4, 1>(a, st);
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
-    case 25: return pp_eligible(a, 256, 128) ? launch_pp<256, 128, 1, 1, false, false, 2>(a, st) : launch<256, 128, 64, 4, 2, 2>(a, st);
-#else
-    case 22:
-        if (pp_eligible(a, 128, 320)) return launch_pp<128, 320, 3, 2, true>(a, st);
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: the 128x320 tiles do not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
-    case 25: return launch<256, 128, 64, 4, 2, 2>(a, st);
+        case 22: return launch_pp<128, 320, 3, 2, true, false, 4, 1>(a, r, st);
+        case 25: return launch_pp<256, 128, 1, 1, false, false, 2>(a, r, st);
 #endif
-    case 21: return pp_eligible(a, 256, 256) ? launch_pp<256, 256, 2, 2, false, false, 2>(a, st) : launch<256, 256, 64, 4, 4, 2>(a, st);
+        default: return launch_pp<128, 320, 3, 2, true>(a, r, st);      // 18
+        }
+    case FAM_GENERAL: break;
+    }
+    switch (r.v) {
+    case 1: return launch<64, 128, 64, 2, 2, 2>(a, r, st);
+    case 3: return launch<256, 128, 64, 4, 2, 2>(a, r, st);
+    case 4: return launch<256, 128, 32, 4, 2, 3>(a, r, st);
+    case 9: return launch<256, 256, 64, 4, 4, 2>(a, r, st);
     case 16:
-        if (a->act == MLSD_ACT_GEGLU) return mlsd_set_error(-1, "mlsd_gemm: tile variant 16 (odd slab count) does not support GEGLU");
-        return launch<128, 320, 64, 4, 2, 2>(a, st);
+        if (a->act == MLSD_ACT_GEGLU)
+            return mlsd_set_error(-1, "%s", r.pick == 16 ? "mlsd_gemm: tile variant 16 (odd slab count) does not support GEGLU" : "mlsd_gemm: the 128x320 tiles do not support GEGLU");
+        return launch<128, 320, 64, 4, 2, 2>(a, r, st);
 #ifdef MLSD_GEMM_EXPERIMENTS   /* variants that lost the tile study on MI355X (kept reproducible, not built by default) */
-    case 2: return launch<128, 128, 32, 2, 2, 4>(a, st);
-    case 5: return launch<128, 128, 64, 2, 2, 3>(a, st);
-    case 14: return launch<128, 128, 64, 2, 2, 2, true>(a, st);
-    case 23: return launch<64, 128, 64, 2, 2, 3>(a, st);      /* round 3 small-M study (profiles/r3_gemm_smallm_rings.txt): no gain */
-    case 24: return launch<64, 128, 64, 2, 2, 2, true>(a, st);
-    case 6: return launch<256, 256, 32, 2, 4, 3>(a, st);
-    case 7: return launch<256, 128, 32, 4, 2, 4>(a, st);
-    case 8: return launch<256, 256, 32, 4, 4, 3>(a, st);
-    case 10: return launch<256, 256, 32, 4, 4, 4>(a, st);
-    case 11: return launch<256, 256, 64, 2, 4, 2>(a, st);
-    case 12: return launch<256, 256, 32, 2, 4, 4>(a, st);
-    case 13: return launch<256, 256, 64, 4, 4, 2, true>(a, st);
-    case 15: return launch<256, 128, 64, 4, 2, 2, true>(a, st);
+    case 2: return launch<128, 128, 32, 2, 2, 4>(a, r, st);
+    case 5: return launch<128, 128, 64, 2, 2, 3>(a, r, st);
+    case 14: return launch<128, 128, 64, 2, 2, 2, true>(a, r, st);
+    case 23: return launch<64, 128, 64, 2, 2, 3>(a, r, st);      /* round 3 small-M study (profiles/r3_gemm_smallm_rings.txt): no gain */
+    case 24: return launch<64, 128, 64, 2, 2, 2, true>(a, r, st);
+    case 6: return launch<256, 256, 32, 2, 4, 3>(a, r, st);
+    case 7: return launch<256, 128, 32, 4, 2, 4>(a, r, st);
+    case 8: return launch<256, 256, 32, 4, 4, 3>(a, r, st);
+    case 10: return launch<256, 256, 32, 4, 4, 4>(a, r, st);
+    case 11: return launch<256, 256, 64, 2, 4, 2>(a, r, st);
+    case 12: return launch<256, 256, 32, 2, 4, 4>(a, r, st);
+    case 13: return launch<256, 256, 64, 4, 4, 2, true>(a, r, st);
+    case 15: return launch<256, 128, 64, 4, 2, 2, true>(a, r, st);
 #endif
-    default: return launch<128, 128, 64, 2, 2, 2>(a, st);
+    default: return launch<128, 128, 64, 2, 2, 2>(a, r, st);
     }
 }
 
@@ -1654,19 +1718,7 @@ MLSD_API int mlsd_has_experiments(void)
 }
 MLSD_API void mlsd_gemm_set_splitk_parallel(int on) { g_gemm_sk_par = on ? 1 : 0; }
 /* 1 if this split-K launch would add its K slices inside the launch (all blocks of a tile wait for each other: an in-launch hand-off the plan has to check) */
-MLSD_API int mlsd_gemm_splitk_parallel(const mlsd_gemm_args* a)
-{
-    if (!a || a->ksplit < 2 || !a->sk_flags) return 0;
-    const int v = pick_variant(a);
-    if (v != 0 && v != 1) return 0;
-    const int BM = v == 1 ? 64 : 128;
-    const int nout = a->N;
-    const bool vec = !(nout & 3) && (!a->C32 || (!(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15))) && (!a->C16 || (!(a->ldc16 & 3) && !((uintptr_t)a->C16 & 7))) &&
-                     (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) && (!a->bias || !((uintptr_t)a->bias & 15)) &&
-                     (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
-    const int ns = vec ? splitk_slices(a, 64, nullptr) : 1;
-    return ns > 1 && splitk_par_ok(a, BM, ns, (long)((a->M + BM - 1) / BM) * ((a->N + 127) / 128)) ? 1 : 0;
-}
+MLSD_API int mlsd_gemm_splitk_parallel(const mlsd_gemm_args* a) { return a && a->ksplit >= 2 && a->sk_flags && resolve(a).splitk == SPLITK_PAR; }
 MLSD_API void mlsd_gemm_set_cus(int n) { g_gemm_ncu = n > 0 && n <= 256 ? n : 256; }
 /* diagnostics: device buffer of 8 x uint64 per block (256 blocks) that the ping-pong kernels fill with s_memtime stamps:
  * [0] kernel entry, [1] prologue done, [2] first epilogue begins, [3] first epilogue issued, [4] last epilogue begins,
@@ -1682,113 +1734,31 @@ MLSD_API size_t mlsd_gemm_splitk_ws_bytes(int M, int N, int ksplit)
 
 MLSD_API size_t mlsd_gemm_streamk_ws_bytes(void) { return (size_t)256 * 256 * 256 * sizeof(float); }
 
-MLSD_API int mlsd_gemm_colstats_rows(const mlsd_gemm_args* a)
-{
-    if (!a || !a->colstats) return 0;
-    const int v = pick_variant(a);
-    int bm, bn;
-    /* a stream-K convolution has no statistics epilogue: handing it a GroupNorm's statistics would silently turn it into the plain 256 x 256 launch (round 3 shipped
-     * exactly that: 24 tiles on 256 CUs, SD1.5's 2048x640x17280 at 366 us).  It keeps its tile; the GroupNorm keeps its first pass. */
-    if (v == 19 && a->conv && sk_eligible(a, 256, 256, true)) return 0;
-    if (v == 28 && a->conv && sk_eligible(a, 128, 320, true)) return 0;
-    if ((v == 17 || v == 19 || v == 21 || v == 26) && pp_eligible(a, 256, 256)) { bm = 256; bn = 256; }   // (26 never takes a launch that has colstats set: it runs as 17)
-    else if ((v == 18 || v == 20 || v == 22 || v == 27 || v == 28) && pp_eligible(a, 128, 320)) { bm = 128; bn = 320; }
-#ifdef MLSD_GEMM_EXPERIMENTS
-    else if (v == 25 && pp_eligible(a, 256, 128)) { bm = 256; bn = 128; }
-#endif
-    else {      // the general tiles that mlsd_gemm launches directly (round 4): {variant -> wave rows, BK}; every one of them has 64-column wave slabs
-        switch (v) {
-        case 0: return general_stats_rows(a, 64, 2, 64);       // 128x128x64, 2x2 waves
-        case 1: return general_stats_rows(a, 32, 2, 64);       // 64x128x64, 2x2
-        case 3: return general_stats_rows(a, 64, 2, 64);       // 256x128x64, 4x2
-        case 4: return general_stats_rows(a, 64, 2, 32);       // 256x128x32s3, 4x2
-        case 9: return general_stats_rows(a, 64, 2, 64);       // 256x256x64, 4x4
-        default: return 0;
-        }
-    }
-    const int e = pp_epilogue_kind(a, bn);
-    return (e == PP_EPI_F32_STATS || e == PP_EPI_F32_RES_STATS) ? bm / 2 : 0;
-}
+MLSD_API int mlsd_gemm_colstats_rows(const mlsd_gemm_args* a) { return a && a->colstats ? resolve(a).stats_rows : 0; }
 
-/* 1 if this launch (with its ln_* fields set) would end with the LayerNorm of its output: the plan builder then drops the LayerNorm launch */
-MLSD_API int mlsd_gemm_ln_fused(const mlsd_gemm_args* a)
-{
-    if (!a || !a->ln_y16) return 0;
-    const int v = pick_variant(a);
-    // 2: a split-K launch on the general tiles whose REDUCE pass ends with the LayerNorm (splitk_reduce_ln: one block per row; no in-launch hand-off)
-    if ((v == 0 || v == 1) && a->ksplit > 1 && a->ws && a->C32 && !a->C16 && a->ln_gamma && a->ln_beta && !(a->N & 3) && a->N <= 4096 && !(a->ldln & 3) &&
-        !((uintptr_t)a->ln_y16 & 7) && !((uintptr_t)a->ln_gamma & 15) && !((uintptr_t)a->ln_beta & 15) && a->act != MLSD_ACT_GEGLU && !g_gemm_sk_inline) {
-        const bool vec = !(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15) && (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) &&
-                         (!a->bias || !((uintptr_t)a->bias & 15)) && (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
-        if (vec && splitk_slices(a, 64, nullptr) > 1 && !splitk_par_ok(a, v == 1 ? 64 : 128, splitk_slices(a, 64, nullptr), (long)((a->M + (v == 1 ? 63 : 127)) / (v == 1 ? 64 : 128)) * ((a->N + 127) / 128)))
-            return 2;
-    }
-    if (v == 30) { const int e = mlsd_gemm_tt_eligible(a, tt_ncu()); return (e >= 4 && e <= 7) ? 1 : 0; }      // (TT_F32_LN / TT_F32_RES_LN / TT_CHAIN_*)
-    if (v != 18 || !ln_eligible(a)) return 0;
-    const int e = pp_epilogue_kind(a, 320);
-    return (e == PP_EPI_F32_LN || e == PP_EPI_F32_RES_LN) ? 1 : 0;
-}
+/* 1 if this launch (with its ln_* fields set) would end with the LayerNorm of its output, 2 if its split-K reduce pass would: the plan builder then drops the LayerNorm launch */
+MLSD_API int mlsd_gemm_ln_fused(const mlsd_gemm_args* a) { return a && a->ln_y16 ? resolve(a).ln : 0; }
 
-/* 1 if this launch (gn_* fields set) ends its split-K reduce pass with the GroupNorm of its output: the plan builder then drops the GroupNorm launch */
-MLSD_API int mlsd_gemm_gn_fused(const mlsd_gemm_args* a)
-{
-#ifndef MLSD_GEMM_EXPERIMENTS
-    /* measured SLOWER than splitk_reduce + the one-dispatch GroupNorm on every map size of the SD1.5 b1 plan (evaluation 6.84 -> 6.88 / 6.90 ms, profiles/NOTES.md): the
-     * reduce then runs on 64 blocks (one per image and group) instead of 640.  Only in EXPERIMENTS builds. */
-    (void)a;
-    return 0;
-#else
-    if (!a || !a->gn_y16 || a->ln_y16 || a->colstats) return 0;
-    const int v = pick_variant(a);
-    if ((v != 0 && v != 1) || a->ksplit < 2 || !a->ws || !a->C32 || a->C16 || !a->gn_gamma || !a->gn_beta || a->act == MLSD_ACT_GEGLU || g_gemm_sk_inline) return 0;
-    if (a->gn_groups <= 0 || a->gn_hw <= 0 || (a->N % a->gn_groups) || (a->M % a->gn_hw)) return 0;
-    const int cg = a->N / a->gn_groups;
-    if ((cg & 3) || (long)a->gn_hw * (cg >> 2) > 256L * GNR_MAXI || (a->gn_ldy & 3) || ((uintptr_t)a->gn_y16 & 7) || ((uintptr_t)a->gn_gamma & 15) || ((uintptr_t)a->gn_beta & 15)) return 0;
-    const bool vec = !(a->N & 3) && !(a->ldc32 & 3) && !((uintptr_t)a->C32 & 15) && (!a->resid || (!(a->ldr & 3) && !((uintptr_t)a->resid & 15))) &&
-                     (!a->bias || !((uintptr_t)a->bias & 15)) && (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15))) && g_gemm_epi != 1;
-    if (!vec || splitk_slices(a, 64, nullptr) < 2) return 0;
-    return splitk_par_ok(a, v == 1 ? 64 : 128, splitk_slices(a, 64, nullptr), (long)((a->M + (v == 1 ? 63 : 127)) / (v == 1 ? 64 : 128)) * ((a->N + 127) / 128)) ? 0 : 1;
-#endif
-}
+/* 1 if this launch (gn_* fields set) ends its split-K reduce pass with the GroupNorm of its output (EXPERIMENTS builds): the plan builder then drops the GroupNorm launch */
+MLSD_API int mlsd_gemm_gn_fused(const mlsd_gemm_args* a) { return a && a->gn_y16 && resolve(a).gn; }
 
 MLSD_API void mlsd_gemm_set_xattn(int mode) { g_xattn_mode = (mode >= 0 && mode <= 2) ? mode : -1; }
 
 /* 1 if this launch (xa_* fields set) ends with the cross attention of the q it projects: the plan builder then records no attention launch */
-MLSD_API int mlsd_gemm_xattn_fused(const mlsd_gemm_args* a)
-{
-    if (!a || !a->xa_k || g_gemm_variant >= 0) return 0;
-    return (xattn_eligible(a) && pp_eligible(a, 128, 320) && pick_variant(a) == 18) ? 1 : 0;
-}
+MLSD_API int mlsd_gemm_xattn_fused(const mlsd_gemm_args* a) { return a && a->xa_k && resolve(a).xattn; }
 
 MLSD_API const char* mlsd_gemm_variant(const mlsd_gemm_args* a)
 {
     static thread_local char buf[64];
-    int v = pick_variant(a);
-    if (v == 19 && !sk_eligible(a, 256, 256)) v = 17;
-    if (v == 28 && !sk_eligible(a, 128, 320)) v = 18;
-    if (v == 29 && !skinny_eligible(a)) v = 1;
-    if (v == 29) {
-        snprintf(buf, sizeof(buf), "gemm<%s,%s,k/%d>", kVariants[v].name, a->conv ? "conv" : "linear", skinny_slices(a, nullptr));
-        return buf;
-    }
-    if (v == 30 && !mlsd_gemm_tt_eligible(a, tt_ncu())) v = 18;
-    if (v == 31 && !mlsd_conv_smalln_eligible(a)) v = 0;
-    if (v == 26 && !mlsd_gemm_w4_eligible(a, 0)) v = 17;
-    if (v == 27 && !mlsd_gemm_w4_eligible(a, 1)) v = 18;
-    if ((v == 17 || v == 21) && !pp_eligible(a, 256, 256)) v = 9;
-    if ((v == 18 || v == 20 || v == 22) && !pp_eligible(a, 128, 320)) v = 16;
-#ifdef MLSD_GEMM_EXPERIMENTS
-    if (v == 25 && !pp_eligible(a, 256, 128)) v = 3;
-#else
-    if (v == 25) v = 3;
-    if (v == 22) v = 18;
-#endif
-    const int bk = strstr(kVariants[v].name, "x32s") ? 32 : 64;
-    const int ns = ((v >= 17 && v <= 22) || v >= 25) ? 1 : splitk_slices(a, bk, nullptr);   /* (the persistent tiles never split K over the grid) */
-    if (ns > 1) snprintf(buf, sizeof(buf), "gemm<%s,%s%s,k/%d%s>", kVariants[v].name, a->conv ? "conv" : "linear", mlsd_gemm_ln_fused(a) == 2 ? "+layernorm" : (mlsd_gemm_gn_fused(a) ? "+groupnorm" : ""), ns, mlsd_gemm_splitk_parallel(a) ? "p" : "");
-    else if (mlsd_gemm_xattn_fused(a)) snprintf(buf, sizeof(buf), "gemm<%s,linear+attention>", kVariants[v].name);      /* the q projection of a cross attention that ends with it */
-    else if (mlsd_gemm_ln_fused(a)) snprintf(buf, sizeof(buf), "gemm<%s,linear+layernorm>", kVariants[v].name);      /* the launch ends with the LayerNorm of its output */
-    else snprintf(buf, sizeof(buf), "gemm<%s,%s>", kVariants[v].name, a->conv ? "conv" : "linear");
+    const GemmRoute r = resolve(a);
+    const char *name = kVariants[r.v].name, *op = a->conv ? "conv" : "linear";
+    /* K slices of a general tile as the args ask for them (a launch without the wide epilogue runs them as one); the persistent tiles never split K over the grid */
+    const int ns = r.fam == FAM_GENERAL ? splitk_slices(a, r.bk, nullptr) : 1;
+    if (r.fam == FAM_SKINNY) snprintf(buf, sizeof(buf), "gemm<%s,%s,k/%d>", name, op, r.nsplit);
+    else if (ns > 1) snprintf(buf, sizeof(buf), "gemm<%s,%s%s,k/%d%s>", name, op, r.ln == 2 ? "+layernorm" : (r.gn ? "+groupnorm" : ""), ns, r.splitk == SPLITK_PAR ? "p" : "");
+    else if (r.xattn) snprintf(buf, sizeof(buf), "gemm<%s,linear+attention>", name);      /* the q projection of a cross attention that ends with it */
+    else if (r.ln) snprintf(buf, sizeof(buf), "gemm<%s,linear+layernorm>", name);         /* the launch ends with the LayerNorm of its output */
+    else snprintf(buf, sizeof(buf), "gemm<%s,%s>", name, op);
     return buf;
 }
 

@@ -87,6 +87,32 @@ int mlsd_rccl_all_gather(void* comm, const void* send, void* recv, size_t nbytes
 enum { MLSD_ACT_NONE = 0, MLSD_ACT_SILU = 1, MLSD_ACT_GELU = 2, MLSD_ACT_GELU_QUICK = 3, MLSD_ACT_RELU = 4,
        MLSD_ACT_GEGLU = 5 };
 
+/* Tile variants of mlsd_gemm that the plan builder or the launcher name (the index in the launcher's variant table; mlsd_gemm_variant
+ * prints the label in the comment).  The numbers never change: the tuning table, mlsd_gemm_force_variant and the tools that force
+ * variants use them.  mlsd_gemm_args.tile_variant holds MLSD_TILE_ARG(v). */
+enum {
+	MLSD_TILE_128x128 = 0,          /* 128x128x64s2 */
+	MLSD_TILE_64x128 = 1,           /* 64x128x64s2 */
+	MLSD_TILE_256x128 = 3,          /* 256x128x64s2 */
+	MLSD_TILE_256x128_S3 = 4,       /* 256x128x32s3 */
+	MLSD_TILE_256x256 = 9,          /* 256x256x64s2w16 */
+	MLSD_TILE_128x320 = 16,         /* 128x320x64s2 */
+	MLSD_TILE_PP_256x256 = 17,      /* 256x256x64pp: ping-pong */
+	MLSD_TILE_PP_128x320 = 18,      /* 128x320x64pp */
+	MLSD_TILE_PPSK_256x256 = 19,    /* 256x256x64ppsk: stream-K */
+	MLSD_TILE_PP2_128x320 = 20,     /* 128x320x64pp2: two phases per K tile */
+	MLSD_TILE_PP2_256x256 = 21,     /* 256x256x64pp2 */
+	MLSD_TILE_PPB_128x320 = 22,     /* 128x320x64ppb (EXPERIMENTS builds) */
+	MLSD_TILE_PP2_256x128 = 25,     /* 256x128x64pp2 (EXPERIMENTS builds) */
+	MLSD_TILE_W4_256x256 = 26,      /* 256x256x64w4 (EXPERIMENTS builds) */
+	MLSD_TILE_W4_128x320 = 27,      /* 128x320x64w4 (EXPERIMENTS builds) */
+	MLSD_TILE_PPSK_128x320 = 28,    /* 128x320x64ppsk */
+	MLSD_TILE_SKINNY = 29,          /* skinny128x64: M <= 128 weight streaming */
+	MLSD_TILE_TT = 30,              /* 128x160x64tt: two tiles in flight per CU */
+	MLSD_TILE_CONV_SMALLN = 31      /* conv3x3n16: small-Cout streaming convolution */
+};
+#define MLSD_TILE_ARG(v) ((v) + 1)      /* mlsd_gemm_args.tile_variant that asks for tile variant v */
+
 typedef struct mlsd_gemm_args {
 	/* A operand: fp16 activations */
 	const void* A;
@@ -114,7 +140,7 @@ typedef struct mlsd_gemm_args {
 	int64_t ldc16;
 	const float* bias_m;    /* [M] per-row bias (operands swapped: V^T = Wv . x^T in the VAE attention) or NULL */
 	int act_after_resid;    /* 1: activation applied after the residual add (TAESD block: relu(conv + x), src/tae.c:36-37) */
-	int tile_variant;       /* 0 = automatic choice; k+1 = use tile variant k (set by the plan's autotuner) */
+	int tile_variant;       /* 0 = automatic choice; MLSD_TILE_ARG(k) = use tile variant k (set by the plan's autotuner) */
 	/* split-K (small-M, long-K problems that cannot fill 256 CUs with output tiles: the SD1.5 batch-1 convs):
 	 * ksplit > 1 slices K over gridDim.y, each slice writes fp32 partial sums to ws, a second kernel sums the
 	 * slices in fixed order and applies the epilogue.  Ignored (no split) for GEGLU, when ws is NULL, or when
@@ -194,6 +220,21 @@ int mlsd_xattn_pack_vt(const void* v, int64_t ldv, int n_img, int Tk, int N, voi
 /* 1 if this launch (gn_* fields set) ends its split-K reduce pass with the GroupNorm of its output (see mlsd_gemm_args.gn_y16) */
 int mlsd_gemm_gn_fused(const mlsd_gemm_args* a);
 const char* mlsd_gemm_variant(const mlsd_gemm_args* a);
+/* What mlsd_gemm would run for these args, in one answer (the queries above read the same decision) */
+typedef struct mlsd_gemm_route_info {
+	int variant;            /* tile variant that launches, after every fall-back */
+	int asked;              /* 1 if that is the tile the launch asked for (forced variant, shape rule, tile_variant or the static choice) */
+	int nsplit;             /* K slices over the grid (1: none) */
+	int stats_rows;         /* as mlsd_gemm_colstats_rows */
+	int ln;                 /* as mlsd_gemm_ln_fused */
+	int gn;                 /* as mlsd_gemm_gn_fused */
+	int xattn;              /* as mlsd_gemm_xattn_fused */
+	int handoff;            /* 1 if blocks of the launch wait for other blocks of the same launch (stream-K, LayerNorm ending, split-K added in the launch) */
+	int stats_rows_if;      /* stats_rows if the args asked for column statistics (colstats set) */
+	int ln_if;              /* ln if a LayerNorm were attached (ln_* fields set) */
+	size_t ln_ws_bytes_if;  /* the ln_ws scratch that ending needs (0: none) */
+} mlsd_gemm_route_info;
+int mlsd_gemm_route(const mlsd_gemm_args* a, mlsd_gemm_route_info* out);     /* 0, or -1 for a NULL argument */
 /* tile order inside an XCD's range: column panels `mode` tiles wide (default 8; 0 = row-major).  A/B timing knob. */
 void mlsd_gemm_set_panel(int width);
 void mlsd_gemm_set_mode(int mode);     /* older name of mlsd_gemm_set_panel */

@@ -1018,8 +1018,8 @@ int splitk_slices(const mlsd_gemm_args* a, int BK, int* kt_per_out)
     return (nkt + per - 1) / per;
 }
 
-// What one mlsd_gemm launch runs, decided once by resolve(): the launch and every query (mlsd_gemm_variant, _colstats_rows, _ln_fused,
-// _gn_fused, _xattn_fused, _splitk_parallel) read the same answer.
+// What one mlsd_gemm launch runs, decided once by resolve(): the launch, mlsd_gemm_route and every query (mlsd_gemm_variant, _colstats_rows,
+// _ln_fused, _gn_fused, _xattn_fused, _splitk_parallel) read the same answer.
 enum GemmFamily { FAM_GENERAL, FAM_PP, FAM_PP_SK, FAM_SKINNY, FAM_TT, FAM_W4, FAM_SMALLN };
 enum SplitKForm { SPLITK_NONE, SPLITK_TWO_LAUNCH, SPLITK_INLINE, SPLITK_PAR };   // slices added by a second launch / by the last block of a tile / by all blocks of a tile
 struct GemmRoute {
@@ -1497,10 +1497,10 @@ constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 int pick_variant(const mlsd_gemm_args* a)
 {
     if (g_gemm_variant >= 0 && g_gemm_variant < kNumVariants) return g_gemm_variant;
-    if (a->xa_k && xattn_eligible(a) && pp_eligible(a, 128, 320)) return 18;      // the one tile that ends with the attention
-    if (mlsd_conv_smalln_eligible(a)) return 31;      // a SHAPE rule above the table (A/B: MLSD_CONV_SMALLN=0): no GEMM tile is the right tool for Cout = 3
+    if (a->xa_k && xattn_eligible(a) && pp_eligible(a, 128, 320)) return MLSD_TILE_PP_128x320;      // the one tile that ends with the attention
+    if (mlsd_conv_smalln_eligible(a)) return MLSD_TILE_CONV_SMALLN;      // a SHAPE rule above the table (A/B: MLSD_CONV_SMALLN=0): no GEMM tile is the right tool for Cout = 3
     if (a->tile_variant > 0 && a->tile_variant <= kNumVariants) return a->tile_variant - 1;
-    if (a->M <= 64) return 1;
+    if (a->M <= 64) return MLSD_TILE_64x128;
     // 128x128 (2 blocks/CU) vs 256x128 (1 block/CU): the bigger tile moves 25 % fewer operand bytes per
     // FLOP (measured +8..15 % on wide outputs) but quantises worse.  Pick by the fill of the last round
     // of blocks over the 256 CUs.
@@ -1510,8 +1510,8 @@ int pick_variant(const mlsd_gemm_args* a)
         return (double)blocks / (double)(rounds * slots);
     };
     const double e0 = fill(128, 128, 512), e3 = 1.08 * fill(256, 128, 256);
-    if (a->M >= 2048 && a->N >= 1920 && e3 > e0) return 3;
-    return 0;
+    if (a->M >= 2048 && a->N >= 1920 && e3 > e0) return MLSD_TILE_256x128;
+    return MLSD_TILE_128x128;
 }
 
 // Rows per column-statistics block a general tile writes for `a` (0: none).  One K slice: the wide epilogue of gemm_kernel's ST build sums per wave (wave_m
@@ -1538,24 +1538,24 @@ GemmRoute resolve(const mlsd_gemm_args* a)
     int v = r.pick;
     GemmFamily fam = FAM_GENERAL;
     switch (v) {
-    case 26: case 27:       // one wave per SIMD (EXPERIMENTS builds); anything else: the ping-pong tile of the same shape
-        if (mlsd_gemm_w4_eligible(a, v - 26)) fam = FAM_W4; else v = v == 26 ? 17 : 18;
+    case MLSD_TILE_W4_256x256: case MLSD_TILE_W4_128x320:       // one wave per SIMD (EXPERIMENTS builds); anything else: the ping-pong tile of the same shape
+        if (mlsd_gemm_w4_eligible(a, v - MLSD_TILE_W4_256x256)) fam = FAM_W4; else v = v == MLSD_TILE_W4_256x256 ? MLSD_TILE_PP_256x256 : MLSD_TILE_PP_128x320;
         break;
-    case 19: if (sk_eligible(a, 256, 256)) fam = FAM_PP_SK; else v = 17; break;
-    case 28: if (sk_eligible(a, 128, 320)) fam = FAM_PP_SK; else v = 18; break;
-    case 29: if (skinny_eligible(a)) fam = FAM_SKINNY; else v = 1; break;
-    case 30: if ((r.epi = mlsd_gemm_tt_eligible(a, tt_ncu()))) fam = FAM_TT; else v = 18; break;      // (else: the ping-pong tile nearest in shape)
-    case 31: if (mlsd_conv_smalln_eligible(a)) fam = FAM_SMALLN; else v = 0; break;
+    case MLSD_TILE_PPSK_256x256: if (sk_eligible(a, 256, 256)) fam = FAM_PP_SK; else v = MLSD_TILE_PP_256x256; break;
+    case MLSD_TILE_PPSK_128x320: if (sk_eligible(a, 128, 320)) fam = FAM_PP_SK; else v = MLSD_TILE_PP_128x320; break;
+    case MLSD_TILE_SKINNY: if (skinny_eligible(a)) fam = FAM_SKINNY; else v = MLSD_TILE_64x128; break;
+    case MLSD_TILE_TT: if ((r.epi = mlsd_gemm_tt_eligible(a, tt_ncu()))) fam = FAM_TT; else v = MLSD_TILE_PP_128x320; break;      // (else: the ping-pong tile nearest in shape)
+    case MLSD_TILE_CONV_SMALLN: if (mlsd_conv_smalln_eligible(a)) fam = FAM_SMALLN; else v = MLSD_TILE_128x128; break;
 #ifndef MLSD_GEMM_EXPERIMENTS   /* variants that lost their study on MI355X are not in the product build: the product tile nearest in shape runs */
-    case 22: v = 18; break;
-    case 25: v = 3; break;
-    case 2: case 5: case 6: case 7: case 8: case 10: case 11: case 12: case 13: case 14: case 15: case 23: case 24: v = 0; break;
+    case MLSD_TILE_PPB_128x320: v = MLSD_TILE_PP_128x320; break;
+    case MLSD_TILE_PP2_256x128: v = MLSD_TILE_256x128; break;
+    case 2: case 5: case 6: case 7: case 8: case 10: case 11: case 12: case 13: case 14: case 15: case 23: case 24: v = MLSD_TILE_128x128; break;
 #endif
     default: break;
     }
-    if (fam == FAM_GENERAL && (v == 17 || v == 18 || v == 20 || v == 21 || v == 22 || v == 25)) {     // ping-pong tiles: else the general tile of the same shape
+    if (fam == FAM_GENERAL && !kVariants[v].wave_m) {     // a ping-pong tile (the other families were settled above): else the general tile of the same shape
         if (pp_eligible(a, kVariants[v].bm, kVariants[v].bn)) fam = FAM_PP;
-        else v = kVariants[v].bn == 256 ? 9 : kVariants[v].bn == 320 ? 16 : 3;
+        else v = kVariants[v].bn == 256 ? MLSD_TILE_256x256 : kVariants[v].bn == 320 ? MLSD_TILE_128x320 : MLSD_TILE_256x128;
     }
     const Variant& t = kVariants[v];
     r.v = v; r.fam = fam; r.bk = t.bk;
@@ -1571,12 +1571,12 @@ GemmRoute resolve(const mlsd_gemm_args* a)
             if (g_gemm_sk_inline && a->sk_flags && tiles <= 4095 && !((uintptr_t)a->ws & 15) &&        /* (word 4095 is the sticky give-up indicator of the stream-K hand-offs) */
                 a->ws_bytes >= (size_t)r.nsplit * tiles * t.bm * t.bn * sizeof(float))
                 r.splitk = SPLITK_INLINE;
-            else if ((v == 0 || v == 1) && splitk_par_ok(a, t.bm, r.nsplit, tiles)) r.splitk = SPLITK_PAR;   // (the two tiles built with PAR)
+            else if ((v == MLSD_TILE_128x128 || v == MLSD_TILE_64x128) && splitk_par_ok(a, t.bm, r.nsplit, tiles)) r.splitk = SPLITK_PAR;   // (the two tiles built with PAR)
             else r.splitk = SPLITK_TWO_LAUNCH;
         }
         r.stats_rows = general_stats_rows(a, r, t);
         // the reduce pass of a split-K launch on tiles 0 / 1 can end with the LayerNorm of its rows (splitk_reduce_ln: one block per row; no in-launch hand-off)
-        const bool reduce_norm = (v == 0 || v == 1) && r.splitk == SPLITK_TWO_LAUNCH && !g_gemm_sk_inline && a->C32 && !a->C16;
+        const bool reduce_norm = (v == MLSD_TILE_128x128 || v == MLSD_TILE_64x128) && r.splitk == SPLITK_TWO_LAUNCH && !g_gemm_sk_inline && a->C32 && !a->C16;
         if (reduce_norm && a->ln_y16 && a->ln_gamma && a->ln_beta && a->N <= 4096 && !(a->ldln & 3) && !((uintptr_t)a->ln_y16 & 7) &&
             !((uintptr_t)a->ln_gamma & 15) && !((uintptr_t)a->ln_beta & 15))
             r.ln = 2;
@@ -1596,8 +1596,8 @@ GemmRoute resolve(const mlsd_gemm_args* a)
         if (r.epi == PP_EPI_F32_STATS || r.epi == PP_EPI_F32_RES_STATS) r.stats_rows = t.bm / 2;
         // the *_LN and cross-attention endings are built for the four-phase 128x320 tile only, and are fused where that tile was asked for (a tile that
         // falls back to it keeps the separate launch); a forced tile never fuses the attention
-        r.ln = fam == FAM_PP && r.pick == 18 && (r.epi == PP_EPI_F32_LN || r.epi == PP_EPI_F32_RES_LN);
-        r.xattn = fam == FAM_PP && r.pick == 18 && r.epi == PP_EPI_XATTN && g_gemm_variant < 0;
+        r.ln = fam == FAM_PP && r.pick == MLSD_TILE_PP_128x320 && (r.epi == PP_EPI_F32_LN || r.epi == PP_EPI_F32_RES_LN);
+        r.xattn = fam == FAM_PP && r.pick == MLSD_TILE_PP_128x320 && r.epi == PP_EPI_XATTN && g_gemm_variant < 0;
         break;
     case FAM_SKINNY:        // the K slices always go through the workspace and splitk_reduce, one slice included
         r.nsplit = skinny_slices(a, &r.kt_per);
@@ -1608,8 +1608,19 @@ GemmRoute resolve(const mlsd_gemm_args* a)
     }
     /* a stream-K convolution and the 128x160 tile have no statistics epilogue: handing them a GroupNorm's statistics would silently turn them into a plain ping-pong
      * launch (round 3 shipped exactly that: 24 tiles on 256 CUs, SD1.5's 2048x640x17280 at 366 us).  They keep their tile; the GroupNorm keeps its first pass. */
-    if (((r.pick == 19 || r.pick == 28) && a->conv && sk_eligible(a, kVariants[r.pick].bm, kVariants[r.pick].bn, true)) || r.pick == 30) r.stats_rows = 0;
+    if (((r.pick == MLSD_TILE_PPSK_256x256 || r.pick == MLSD_TILE_PPSK_128x320) && a->conv && sk_eligible(a, kVariants[r.pick].bm, kVariants[r.pick].bn, true)) || r.pick == MLSD_TILE_TT) r.stats_rows = 0;
     return r;
+}
+
+// The args of a launch that also asks for column statistics (`stats`) or ends with a LayerNorm (`ln`) where they do not already: the unset fields
+// point at an aligned placeholder that no launch reads (the route tests those pointers for null and alignment only), ldln = N as the plan sets it.
+mlsd_gemm_args what_if(const mlsd_gemm_args* a, bool stats, bool ln)
+{
+    alignas(256) static float ph[64];
+    mlsd_gemm_args w = *a;
+    if (stats && !w.colstats) w.colstats = ph;
+    if (ln && !w.ln_y16) { w.ln_y16 = ph; w.ldln = w.N; w.ln_gamma = w.ln_beta = w.ln_ws = ph; w.ln_cnt = (unsigned*)ph; }
+    return w;
 }
 
 }  // namespace
@@ -1641,32 +1652,32 @@ MLSD_API int mlsd_gemm(const mlsd_gemm_args* a, void* stream)
         return mlsd_set_error(-1, "mlsd_gemm: the plan dropped a LayerNorm for this launch's *_LN epilogue but the launch would not run it (tile or epilogue settings changed after planning)");
     hipStream_t st = (hipStream_t)stream;
     switch (r.fam) {
-    case FAM_W4: return mlsd_gemm_w4(a, r.v - 26, st, g_gemm_ncu);
+    case FAM_W4: return mlsd_gemm_w4(a, r.v - MLSD_TILE_W4_256x256, st, g_gemm_ncu);
     case FAM_TT: return mlsd_gemm_tt(a, st, tt_ncu());
     case FAM_SMALLN: return mlsd_conv_smalln(a, st);
     case FAM_SKINNY: return launch_skinny(a, r, st);
-    case FAM_PP_SK: return r.v == 19 ? launch_pp<256, 256, 2, 2, false, true>(a, r, st) : launch_pp<128, 320, 3, 2, true, true>(a, r, st);
+    case FAM_PP_SK: return r.v == MLSD_TILE_PPSK_256x256 ? launch_pp<256, 256, 2, 2, false, true>(a, r, st) : launch_pp<128, 320, 3, 2, true, true>(a, r, st);
     case FAM_PP:
         switch (r.v) {
-        case 17: return launch_pp<256, 256, 2, 2, false>(a, r, st);
-        case 20: return launch_pp<128, 320, 3, 2, true, false, 2>(a, r, st);
-        case 21: return launch_pp<256, 256, 2, 2, false, false, 2>(a, r, st);
+        case MLSD_TILE_PP_256x256: return launch_pp<256, 256, 2, 2, false>(a, r, st);
+        case MLSD_TILE_PP2_128x320: return launch_pp<128, 320, 3, 2, true, false, 2>(a, r, st);
+        case MLSD_TILE_PP2_256x256: return launch_pp<256, 256, 2, 2, false, false, 2>(a, r, st);
 #ifdef MLSD_GEMM_EXPERIMENTS   /* measured and not adopted (profiles/NOTES.md): the re-balanced staging schedule, the narrow 256x128 ping-pong tile */
-        case 22: return launch_pp<128, 320, 3, 2, true, false, 4, 1>(a, r, st);
-        case 25: return launch_pp<256, 128, 1, 1, false, false, 2>(a, r, st);
+        case MLSD_TILE_PPB_128x320: return launch_pp<128, 320, 3, 2, true, false, 4, 1>(a, r, st);
+        case MLSD_TILE_PP2_256x128: return launch_pp<256, 128, 1, 1, false, false, 2>(a, r, st);
 #endif
-        default: return launch_pp<128, 320, 3, 2, true>(a, r, st);      // 18
+        default: return launch_pp<128, 320, 3, 2, true>(a, r, st);      // MLSD_TILE_PP_128x320
         }
     case FAM_GENERAL: break;
     }
     switch (r.v) {
-    case 1: return launch<64, 128, 64, 2, 2, 2>(a, r, st);
-    case 3: return launch<256, 128, 64, 4, 2, 2>(a, r, st);
-    case 4: return launch<256, 128, 32, 4, 2, 3>(a, r, st);
-    case 9: return launch<256, 256, 64, 4, 4, 2>(a, r, st);
-    case 16:
+    case MLSD_TILE_64x128: return launch<64, 128, 64, 2, 2, 2>(a, r, st);
+    case MLSD_TILE_256x128: return launch<256, 128, 64, 4, 2, 2>(a, r, st);
+    case MLSD_TILE_256x128_S3: return launch<256, 128, 32, 4, 2, 3>(a, r, st);
+    case MLSD_TILE_256x256: return launch<256, 256, 64, 4, 4, 2>(a, r, st);
+    case MLSD_TILE_128x320:
         if (a->act == MLSD_ACT_GEGLU)
-            return mlsd_set_error(-1, "%s", r.pick == 16 ? "mlsd_gemm: tile variant 16 (odd slab count) does not support GEGLU" : "mlsd_gemm: the 128x320 tiles do not support GEGLU");
+            return mlsd_set_error(-1, "%s", r.pick == MLSD_TILE_128x320 ? "mlsd_gemm: tile variant 16 (odd slab count) does not support GEGLU" : "mlsd_gemm: the 128x320 tiles do not support GEGLU");
         return launch<128, 320, 64, 4, 2, 2>(a, r, st);
 #ifdef MLSD_GEMM_EXPERIMENTS   /* variants that lost the tile study on MI355X (kept reproducible, not built by default) */
     case 2: return launch<128, 128, 32, 2, 2, 4>(a, r, st);
@@ -1734,18 +1745,29 @@ MLSD_API size_t mlsd_gemm_splitk_ws_bytes(int M, int N, int ksplit)
 
 MLSD_API size_t mlsd_gemm_streamk_ws_bytes(void) { return (size_t)256 * 256 * 256 * sizeof(float); }
 
-MLSD_API int mlsd_gemm_colstats_rows(const mlsd_gemm_args* a) { return a && a->colstats ? resolve(a).stats_rows : 0; }
+MLSD_API int mlsd_gemm_route(const mlsd_gemm_args* a, mlsd_gemm_route_info* out)
+{
+    if (!a || !out) return -1;
+    const mlsd_gemm_args ws = what_if(a, true, false), wl = what_if(a, false, true);
+    const GemmRoute r = resolve(a), rs = resolve(&ws), rl = resolve(&wl);
+    *out = {r.v, r.v == r.pick, r.nsplit, a->colstats ? r.stats_rows : 0, a->ln_y16 ? r.ln : 0, a->gn_y16 && r.gn, a->xa_k && r.xattn,
+            r.fam == FAM_PP_SK || r.ln == 1 || r.splitk == SPLITK_PAR, rs.stats_rows, rl.ln,
+            rl.ln == 1 ? (size_t)a->M * (a->N / kVariants[rl.v].bn) * 16 : 0};      // (LayerNorm scratch: 16 bytes per row and column tile)
+    return 0;
+}
+
+MLSD_API int mlsd_gemm_colstats_rows(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.stats_rows; }
 
 /* 1 if this launch (with its ln_* fields set) would end with the LayerNorm of its output, 2 if its split-K reduce pass would: the plan builder then drops the LayerNorm launch */
-MLSD_API int mlsd_gemm_ln_fused(const mlsd_gemm_args* a) { return a && a->ln_y16 ? resolve(a).ln : 0; }
+MLSD_API int mlsd_gemm_ln_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.ln; }
 
 /* 1 if this launch (gn_* fields set) ends its split-K reduce pass with the GroupNorm of its output (EXPERIMENTS builds): the plan builder then drops the GroupNorm launch */
-MLSD_API int mlsd_gemm_gn_fused(const mlsd_gemm_args* a) { return a && a->gn_y16 && resolve(a).gn; }
+MLSD_API int mlsd_gemm_gn_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.gn; }
 
 MLSD_API void mlsd_gemm_set_xattn(int mode) { g_xattn_mode = (mode >= 0 && mode <= 2) ? mode : -1; }
 
 /* 1 if this launch (xa_* fields set) ends with the cross attention of the q it projects: the plan builder then records no attention launch */
-MLSD_API int mlsd_gemm_xattn_fused(const mlsd_gemm_args* a) { return a && a->xa_k && resolve(a).xattn; }
+MLSD_API int mlsd_gemm_xattn_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.xattn; }
 
 MLSD_API const char* mlsd_gemm_variant(const mlsd_gemm_args* a)
 {

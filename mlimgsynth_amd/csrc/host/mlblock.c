@@ -19,13 +19,10 @@
 #define BIG_BYTES     ((size_t)8 << 20)
 #define ALIGN_UP(x,a) (((x) + (a) - 1) / (a) * (a))
 
-#define VARIANT_STREAMK 20      /* tile_variant (1-based) of the stream-K ping-pong tile (256 x 256) */
-#define VARIANT_STREAMK2 29     /* the same on the 128 x 320 tile (round 4) */
-#define IS_STREAMK(v) ((v) == VARIANT_STREAMK || (v) == VARIANT_STREAMK2)
-#define VARIANT_TT 31           /* two tiles in flight per CU (gemm_tt.hip, round 5) */
-#define VARIANT_SKINNY 30       /* the skinny-M weight-streaming kernel (gemm_skinny.hpp): always runs through the split-K workspace */
 #define SK_FLAG_WORDS 4096      /* stream-K: a flag per persistent block (256); split-K reduced in the launch: a ticket counter per output tile; word 4095: sticky give-up */
 #define LN_CNT_WORDS 8192       /* LayerNorm fold: word 8191 = sticky give-up (round 6: self-tagged records instead of arrival / departure counters; a tile takes its tag from its own record of the op's previous launch: nothing else lives here) */
+
+static mlsd_gemm_route_info route_of(const mlsd_gemm_args* g) { mlsd_gemm_route_info r; mlsd_gemm_route(g, &r); return r; }
 
 #define VEC_PUSH(C, arr, n, cap, T) \
 	(((n) == (cap) ? ((cap) = (cap) ? (cap)*2 : 64, (arr) = (T*)realloc((arr), sizeof(T)*(cap))) : 0), &(arr)[(n)++])
@@ -151,8 +148,7 @@ MLB_API int mlctx_handoff_ops(const MLCtx* C)
 	if (!C || !C->prepared) return 0;
 	for (int i=0;i<C->n_ops;++i) {
 		const MLOp *o = &C->ops[i];
-		if (o->kind != OP_GEMM) continue;
-		if ((o->u.gemm.ln_y16 && mlsd_gemm_ln_fused(&o->u.gemm) == 1) || (IS_STREAMK(o->u.gemm.tile_variant) && o->u.gemm.sk_flags) || mlsd_gemm_splitk_parallel(&o->u.gemm)) ++n;
+		if (o->kind == OP_GEMM && route_of(&o->u.gemm).handoff) ++n;
 	}
 	return n;
 }
@@ -173,13 +169,15 @@ MLB_API int mlctx_handoffs_off(MLCtx* C)
 		MLOp *o = &C->ops[i];
 		if (o->kind != OP_GEMM) continue;
 		mlsd_gemm_args *g = &o->u.gemm;
-		if (g->ln_y16 && mlsd_gemm_ln_fused(g) == 1) {      /* (a LayerNorm in a split-K reduce pass waits for nobody: it stays) */
+		const mlsd_gemm_route_info r = route_of(g);
+		if (!r.handoff) continue;
+		if (r.ln == 1) {      /* (a LayerNorm in a split-K reduce pass waits for nobody: it stays) */
 			g->ln_y16 = NULL; g->ln_gamma = g->ln_beta = NULL; g->ln_ws = NULL; g->ln_cnt = NULL;
 			if (i + 1 < C->n_ops && C->ops[i+1].kind == OP_LN && C->ops[i+1].fused) { C->ops[i+1].fused = 0; C->n_ln_fused--; }
 			++n;
 			if (o->folded_from) { g->tile_variant = o->folded_from < 0 ? 0 : o->folded_from; o->folded_from = 0; }      /* moved to the 128 x 160 kernel only for this LayerNorm: back to its own tile */
 		}
-		if ((IS_STREAMK(g->tile_variant) || g->ksplit > 1) && g->sk_flags) { g->sk_flags = NULL; ++n; }     /* (split-K: back to the two-launch form) */
+		if (g->sk_flags) { g->sk_flags = NULL; ++n; }     /* (stream-K: the plain tile of its shape; split-K: the two-launch form) */
 	}
 	if (n && C->graph_exec) { mlsd_graph_destroy(C->graph_exec); C->graph_exec = NULL; }
 	C->static_valid = 0;      /* the timed-out launch may have been a hoisted step-invariant op (stream-K is not excluded for `once` ops): every caller's re-run recomputes them */
@@ -799,11 +797,27 @@ static int streamk_get(MLCtx* C, mlsd_gemm_args* g)
 	return 0;
 }
 
+static int workspace_get(MLCtx* C, mlsd_gemm_args* g)
+{	/* the plan's split-K workspace and flag words for a launch that asks for a K split, stream-K or the skinny-M kernel (which always runs through the workspace) */
+	const int a = g->tile_variant;
+	return g->ksplit > 1 || a == MLSD_TILE_ARG(MLSD_TILE_PPSK_256x256) || a == MLSD_TILE_ARG(MLSD_TILE_PPSK_128x320) || a == MLSD_TILE_ARG(MLSD_TILE_SKINNY) ? streamk_get(C, g) : 0;
+}
+
+static int runs_on(const mlsd_gemm_args* g, int v, int ks)
+{	/* 1 if g, asked for tile v with K split ks, launches on that tile, split where ks > 1 (no fall-back) */
+	mlsd_gemm_args t = *g;
+	t.tile_variant = MLSD_TILE_ARG(v); t.ksplit = ks;
+	const mlsd_gemm_route_info r = route_of(&t);
+	return r.variant == v && (r.nsplit > 1) == (ks > 1);
+}
+
+static int cu_masked(const MLCtx* C) { return C->cu_budget > 0 && C->cu_budget < 256; }    /* a CU-masked stream (mlctx_set_cus): no in-launch hand-offs */
+
 /* prep-time selection: table hit -> its variant / K split; miss -> the launcher's static choice (tile_variant 0) */
 static int select_gemm(MLCtx* C, MLOp* op)
 {
 	mlsd_gemm_args *g = &op->u.gemm;
-	if (g->xa_k && mlsd_gemm_xattn_fused(g) == 1) { g->tile_variant = 19; g->ksplit = 1; return 1; }      /* a q projection that ends with its cross attention: one tile does that (a shape rule above the table, not a miss) */
+	if (g->xa_k && mlsd_gemm_xattn_fused(g) == 1) { g->tile_variant = MLSD_TILE_ARG(MLSD_TILE_PP_128x320); g->ksplit = 1; return 1; }      /* a q projection that ends with its cross attention: one tile does that (a shape rule above the table, not a miss) */
 	if (mlsd_conv_smalln_eligible(g)) { g->tile_variant = 0; g->ksplit = 1; return 1; }                       /* likewise the small-Cout streaming convolution */
 	const TuneKey k = tune_key(g);
 	int best = 0, ks = 1;
@@ -813,23 +827,22 @@ static int select_gemm(MLCtx* C, MLOp* op)
 		{	/* MLSD_NO_TT=1 (A/B, debugging): table entries of the 128 x 160 kernel run on the 128 x 320 ping-pong tile */
 			static int no_tt = -1;
 			if (no_tt < 0) { const char *e = getenv("MLSD_NO_TT"); no_tt = (e && *e && *e != '0') ? 1 : 0; }
-			if (no_tt && best == VARIANT_TT) best = 19;
+			if (no_tt && best == MLSD_TILE_ARG(MLSD_TILE_TT)) best = MLSD_TILE_ARG(MLSD_TILE_PP_128x320);
 		}
-		/* a plan on a CU-masked stream (mlctx_set_cus): no in-launch hand-offs -- a stream-K entry runs as the plain tile of its shape */
-		if (IS_STREAMK(best) && C->cu_budget > 0 && C->cu_budget < 256) best = best == VARIANT_STREAMK ? 18 : 19;
+		if (cu_masked(C) && best == MLSD_TILE_ARG(MLSD_TILE_PPSK_256x256)) best = MLSD_TILE_ARG(MLSD_TILE_PP_256x256);      /* stream-K entries: the plain tile of their shape */
+		if (cu_masked(C) && best == MLSD_TILE_ARG(MLSD_TILE_PPSK_128x320)) best = MLSD_TILE_ARG(MLSD_TILE_PP_128x320);
 		g->tile_variant = best; g->ksplit = ks;
 		if (ks > 1 && (size_t)ks * g->M * g->N * sizeof(float) > SPLITK_WS_BYTES) g->ksplit = 1;
-		if (g->ksplit > 1 && streamk_get(C, g)) return -1;
-		if ((IS_STREAMK(best) || best == VARIANT_SKINNY) && streamk_get(C, g)) return -1;
+		if (workspace_get(C, g)) return -1;
 		/* The 128 x 160 two-tiles-per-CU kernel (gemm_tt.hip, round 5) instead of the 128 x 320 ping-pong tile WHERE THAT TILE FILLS AT MOST HALF OF THE CUs (a pure function
 		 * of the shape).  In-plan A/B, same box (profiles/r5_gemm_tt_inplan.txt): SDXL b2 evaluation -2.4 %, b1 -0.9 %, SD1.5 b2 -1.1 %; on the full-chip single-round
 		 * launches of SDXL b4 it LOSES (+0.4 .. +0.7 %: its loop is 25 % slower than the ping-pong loop, which eats the overlap it buys) and is not used there.
 		 * MLSD_TT: 0 = never, 1 = also where K >= 2560, 2 = on every shape it takes (the A/B settings of that study), 3 / unset = the rule above. */
 		static int tt_mode = -1;
 		if (tt_mode < 0) { const char *e = getenv("MLSD_TT"); tt_mode = e && *e ? atoi(e) : 3; }
-		if (tt_mode > 0 && (best == 19 || best == 21) && !g->conv && g->act == MLSD_ACT_NONE && !(g->M % 128) && !(g->N % 160) && !(g->K & 63) && g->ksplit <= 1 &&
-		    !g->rowbias && !g->bias_m && (tt_mode == 2 || (tt_mode == 1 && g->K >= 2560) || (tt_mode >= 1 && (long)(g->M / 128) * ((g->N + 319) / 320) <= 128)) &&
-		    !(C->cu_budget > 0 && C->cu_budget < 256)) g->tile_variant = VARIANT_TT;
+		const int wanted = tt_mode == 2 || (tt_mode == 1 && g->K >= 2560) || (tt_mode >= 1 && (long)(g->M / 128) * ((g->N + 319) / 320) <= 128);
+		if (wanted && !g->conv /* (policy: 1x1 convolutions, which the kernel also takes, keep the table's tile) */ && !cu_masked(C) && (best == MLSD_TILE_ARG(MLSD_TILE_PP_128x320) || best == MLSD_TILE_ARG(MLSD_TILE_PP2_128x320)) &&
+		    runs_on(g, MLSD_TILE_TT, g->ksplit)) g->tile_variant = MLSD_TILE_ARG(MLSD_TILE_TT);
 		return exact;
 	}
 	g->tile_variant = 0; g->ksplit = 1;
@@ -852,12 +865,13 @@ static int time_gemm(MLCtx* C, mlsd_gemm_args* g, void* e0, void* e1, float* ms_
 	return 0;
 }
 
-/* candidates of one GEMM: (tile variant, K slices), in order of preference; returns their number (<= 32) */
+/* candidates of one GEMM: (tile variant, K slices), in order of preference; returns their number (<= 32).  A candidate that would not launch on its own
+ * tile (with a K split where it asks for one) is dropped. */
 static int gemm_candidates(MLCtx* C, mlsd_gemm_args* g, int cv[32], int cs[32])
 {
 	int nc = 0;
-	/* skinny-M weight streaming (variant 29): K slices so that (N / 64) x slices is about one / two blocks per CU */
-	if (g->M <= 128 && !(g->K & 63) && g->K >= 256 && g->act != MLSD_ACT_GEGLU && !(g->N & 3) && (!g->conv || (!g->upsample && !(g->Cin & 63))) && !streamk_get(C, g)) {
+	/* skinny-M weight streaming: K slices so that (N / 64) x slices is about one / two blocks per CU */
+	if (g->K >= 256 && !streamk_get(C, g)) {
 		const int nb = (g->N + 63) / 64, nkt = g->K / 64;
 		int last = 0;
 		for (int t = 256; t <= 1024 && nc < 6; t *= 2) {
@@ -866,47 +880,43 @@ static int gemm_candidates(MLCtx* C, mlsd_gemm_args* g, int cv[32], int cs[32])
 			if (s > nkt / 2) s = nkt / 2;
 			while (s > 1 && (size_t)s * g->M * g->N * sizeof(float) > SPLITK_WS_BYTES) --s;
 			if (s == last) continue;
-			cv[nc] = 29; cs[nc++] = s; last = s;
+			cv[nc] = MLSD_TILE_SKINNY; cs[nc++] = s; last = s;
 		}
 	}
-	if (g->M <= 64) { cv[nc]=1; cs[nc++]=1; cv[nc]=0; cs[nc++]=1; }
+	if (g->M <= 64) { cv[nc]=MLSD_TILE_64x128; cs[nc++]=1; cv[nc]=MLSD_TILE_128x128; cs[nc++]=1; }
 	else {
-		/* persistent ping-pong tiles (gemm_pp.hpp): problems made of whole wave blocks; convs whose K tiles lie inside
-		 * one filter tap (anything else they would hand to the LDS-transposing tile of the same shape anyway) */
-		const int pp_ok = !(g->K & 63) && g->K >= 192 && (!g->conv || (!(g->Cin & 63) && (!g->upsample || (g->stride == 1 && g->C32 && !g->C16 && !g->resid && g->act == MLSD_ACT_NONE))));      /* (upsampled sources: round 5, gemm_pp.hpp CONV == 2) */
-		if (pp_ok && g->M >= 256 && g->N >= 256 && !(g->M & 127) && !(g->N & 63)) {
-			cv[nc]=17; cs[nc++]=1; cv[nc]=21; cs[nc++]=1;
+		/* persistent ping-pong tiles (gemm_pp.hpp) */
+		if (g->M >= 256 && g->N >= 256) {
+			cv[nc]=MLSD_TILE_PP_256x256; cs[nc++]=1; cv[nc]=MLSD_TILE_PP2_256x256; cs[nc++]=1;
 			/* stream-K on the same tile where the tiles do not fill whole rounds of the 256 blocks */
 			const long t256 = (long)((g->M + 255) / 256) * ((g->N + 255) / 256);
-			if (t256 % 256 && t256 * (g->K / 64) >= 256 * 4 && g->act != MLSD_ACT_GEGLU && !(g->conv && g->upsample) && !streamk_get(C, g)) { cv[nc]=19; cs[nc++]=1; }
+			if (t256 % 256 && t256 * (g->K / 64) >= 256 * 4 && g->act != MLSD_ACT_GEGLU && !streamk_get(C, g)) { cv[nc]=MLSD_TILE_PPSK_256x256; cs[nc++]=1; }
 		}
-		if (pp_ok && g->M >= 128 && !(g->M & 63) && !(g->N % 80) && g->act != MLSD_ACT_GEGLU) {
-			cv[nc]=18; cs[nc++]=1; cv[nc]=20; cs[nc++]=1;   /* four / two phases per K tile */
+		if (g->M >= 128) {
+			cv[nc]=MLSD_TILE_PP_128x320; cs[nc++]=1; cv[nc]=MLSD_TILE_PP2_128x320; cs[nc++]=1;   /* four / two phases per K tile */
 			/* stream-K on that tile: few tiles (not whole rounds of the 256 blocks) and K long enough to deal out */
 			const long t320 = (long)((g->M + 127) / 128) * ((g->N + 319) / 320);
-			if (t320 % 256 && t320 < 256 && t320 * (g->K / 64) >= 256 * 4 && !(g->conv && g->upsample) && !streamk_get(C, g)) { cv[nc]=28; cs[nc++]=1; }
+			if (t320 % 256 && t320 < 256 && t320 * (g->K / 64) >= 256 * 4 && !streamk_get(C, g)) { cv[nc]=MLSD_TILE_PPSK_128x320; cs[nc++]=1; }
 		}
-		/* two tiles in flight per CU (gemm_tt.hip, round 5): linear / 1x1 problems made of whole 128 x 160 tiles */
-		if (!(g->M % 128) && !(g->N % 160) && !(g->K & 63) && g->K >= 128 && g->act == MLSD_ACT_NONE && !g->rowbias && !g->bias_m &&
-		    (!g->conv || (g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && !g->upsample)) && !(g->C32 && g->C16)) { cv[nc]=30; cs[nc++]=1; }
+		cv[nc]=MLSD_TILE_TT; cs[nc++]=1;      /* two tiles in flight per CU (gemm_tt.hip, round 5) */
 		/* (the narrow 256x128 ping-pong tile, variant 25, is NOT a candidate: it wins this warm, back-to-back timing on the VAE's N = 128
 		 * convolutions (+9..16 %) and loses in the plan (-16 %, profiles/r3_gemm_narrow_tile.txt): those launches are bound by their fp32
 		 * output + residual traffic, which two co-resident blocks overlap with each other's K loops and one persistent block cannot) */
-		cv[nc]=9; cs[nc++]=1; cv[nc]=3; cs[nc++]=1; cv[nc]=4; cs[nc++]=1; cv[nc]=0; cs[nc++]=1;
+		cv[nc]=MLSD_TILE_256x256; cs[nc++]=1; cv[nc]=MLSD_TILE_256x128; cs[nc++]=1; cv[nc]=MLSD_TILE_256x128_S3; cs[nc++]=1; cv[nc]=MLSD_TILE_128x128; cs[nc++]=1;
 	}
 	const long t128 = (long)((g->M + 127) / 128) * ((g->N + 127) / 128);
-	if (g->M > 64 && t128 < 512) { cv[nc]=1; cs[nc++]=1; }
+	if (g->M > 64 && t128 < 512) { cv[nc]=MLSD_TILE_64x128; cs[nc++]=1; }
 	/* 128x320: outputs whose width is a multiple of 320 (N = 1280, 640) in whole tile columns, e.g. 8192x1280 =
 	 * 256 tiles = one per CU where 256x256 tiles give 160 */
-	if (g->M > 64 && g->N >= 320 && g->act != MLSD_ACT_GEGLU) { cv[nc]=16; cs[nc++]=1; }   /* short problems: more, smaller blocks hide the fill latency */
+	if (g->M > 64 && g->N >= 320 && g->act != MLSD_ACT_GEGLU) { cv[nc]=MLSD_TILE_128x320; cs[nc++]=1; }   /* short problems: more, smaller blocks hide the fill latency (mlsd_gemm refuses GEGLU there) */
 	/* split-K: output tiles alone cannot occupy the 256 CUs (2 resident blocks each) and K is long enough to slice */
 	const int nkt = (g->K + 63) / 64;
-	if (t128 <= 192 && nkt >= 8 && g->act != MLSD_ACT_GEGLU && !(g->N & 3)) {
+	if (t128 <= 192 && nkt >= 8 && !splitk_ws_get(C, g)) {
 		static const int targets[] = {256, 512, 1024};
 		for (int vi=0; vi<2; ++vi) {
-			const int v = vi ? 1 : 0;                       /* 128x128 and 64x128 tiles */
-			if (v == 1 && g->M > 512) continue;
-			const long tiles = (long)((g->M + (v ? 63 : 127)) / (v ? 64 : 128)) * ((g->N + 127) / 128);
+			const int v = vi ? MLSD_TILE_64x128 : MLSD_TILE_128x128;
+			if (v == MLSD_TILE_64x128 && g->M > 512) continue;
+			const long tiles = (long)((g->M + (vi ? 63 : 127)) / (vi ? 64 : 128)) * ((g->N + 127) / 128);
 			int last = 1;
 			for (int ti=0; ti<3; ++ti) {
 				int s = (int)((targets[ti] + tiles / 2) / tiles);
@@ -917,7 +927,9 @@ static int gemm_candidates(MLCtx* C, mlsd_gemm_args* g, int cv[32], int cs[32])
 			}
 		}
 	}
-	return nc;
+	int n = 0;
+	for (int c=0;c<nc;++c) if (runs_on(g, cv[c], cs[c])) { cv[n] = cv[c]; cs[n++] = cs[c]; }
+	return n;
 }
 
 /* offline timing mode (tools/tune_all.py): called for shapes the table does not hold */
@@ -925,32 +937,25 @@ static int tune_gemm(MLCtx* C, MLOp* op)
 {
 	mlsd_gemm_args *g = &op->u.gemm;
 	TuneKey k = tune_key(g);
-	{
-		int best = 0, ks = 1;
-		if (tune_lookup(&k, &best, &ks)) {
-			g->tile_variant = best; g->ksplit = ks;
-			if (g->ksplit > 1 && streamk_get(C, g)) return -1;
-			if ((IS_STREAMK(best) || best == VARIANT_SKINNY) && streamk_get(C, g)) return -1;
-			return 1;
-		}
-	}
+	int best = 0, ks = 1;
+	if (tune_lookup(&k, &best, &ks)) { g->tile_variant = best; g->ksplit = ks; return workspace_get(C, g) ? -1 : 1; }
 	/* candidates: (tile variant, K slices) */
 	int cv[32], cs[32];
 	const int nc = gemm_candidates(C, g, cv, cs);
 	void *e0 = NULL, *e1 = NULL;
 	if (mlsd_event_create(&e0) || mlsd_event_create(&e1)) return -1;
-	float best_ms = 1e30f; int best = 0, best_s = 1;
+	float best_ms = 1e30f;
 	for (int c=0;c<nc;++c) {
-		g->tile_variant = cv[c] + 1; g->ksplit = cs[c];
+		g->tile_variant = MLSD_TILE_ARG(cv[c]); g->ksplit = cs[c];
 		float ms;
-		if ((cs[c] > 1 && streamk_get(C, g)) || time_gemm(C, g, e0, e1, &ms)) { mlsd_event_destroy(e0); mlsd_event_destroy(e1); return -1; }
+		if (workspace_get(C, g) || time_gemm(C, g, e0, e1, &ms)) { mlsd_event_destroy(e0); mlsd_event_destroy(e1); return -1; }
 		/* candidates are listed in order of preference: a later one must win by 3 % (keeps the choice, and with
 		 * it the kernel mix of a profile, stable against timing noise between near-equal variants) */
-		if (ms < (c ? 0.97f : 1.f) * best_ms) { best_ms = ms; best = cv[c] + 1; best_s = cs[c]; }
+		if (ms < (c ? 0.97f : 1.f) * best_ms) { best_ms = ms; best = MLSD_TILE_ARG(cv[c]); ks = cs[c]; }
 	}
 	mlsd_event_destroy(e0); mlsd_event_destroy(e1);
-	g->tile_variant = best; g->ksplit = best_s;
-	k.best = best; k.ksplit = best_s;
+	g->tile_variant = best; g->ksplit = ks;
+	k.best = best; k.ksplit = ks;
 	pthread_mutex_lock(&g_tune_mu);
 	if (g_ntune < 1024) g_tune[g_ntune++] = k;
 	pthread_mutex_unlock(&g_tune_mu);
@@ -1001,8 +1006,8 @@ MLB_API int mlctx_tune_inplan(MLCtx* C, int reps)
 			if (j < 0) continue;
 			const int c = r < sh[j].nc ? r : 0;
 			mlsd_gemm_args *g = &C->ops[i].u.gemm;
-			g->tile_variant = sh[j].cv[c] + 1; g->ksplit = sh[j].cs[c];
-			if ((g->ksplit > 1 || IS_STREAMK(g->tile_variant) || g->tile_variant == VARIANT_SKINNY) && streamk_get(C, g)) goto done;
+			g->tile_variant = MLSD_TILE_ARG(sh[j].cv[c]); g->ksplit = sh[j].cs[c];
+			if (workspace_get(C, g)) goto done;
 		}
 		for (int j=0;j<ns;++j) if (r < sh[j].nc) sh[j].t[r] = 1e30;
 		for (int rep=0; rep<reps+1; ++rep) {             /* (the first pass warms the instruction caches of this round's kernels) */
@@ -1017,7 +1022,7 @@ MLB_API int mlctx_tune_inplan(MLCtx* C, int reps)
 	for (int j=0;j<ns;++j) {
 		int best = 0;
 		for (int c=1;c<sh[j].nc;++c) if (sh[j].t[c] < 0.97 * sh[j].t[0] && sh[j].t[c] < sh[j].t[best]) best = c;
-		sh[j].k.best = sh[j].cv[best] + 1; sh[j].k.ksplit = sh[j].cs[best];
+		sh[j].k.best = MLSD_TILE_ARG(sh[j].cv[best]); sh[j].k.ksplit = sh[j].cs[best];
 		if (best) {
 			++changed;
 			pthread_mutex_lock(&g_tune_mu);
@@ -1034,7 +1039,7 @@ MLB_API int mlctx_tune_inplan(MLCtx* C, int reps)
 		if (j < 0) continue;
 		mlsd_gemm_args *g = &C->ops[i].u.gemm;
 		g->tile_variant = sh[j].k.best; g->ksplit = sh[j].k.ksplit;
-		if ((g->ksplit > 1 || IS_STREAMK(g->tile_variant) || g->tile_variant == VARIANT_SKINNY) && streamk_get(C, g)) { changed = -1; break; }
+		if (workspace_get(C, g)) { changed = -1; break; }
 	}
 done:
 	free(sh); free(op_shape); free(ms);
@@ -1094,14 +1099,10 @@ static MLOp* gn_producer(MLCtx* C, int gn_idx, int src, const float* x, int64_t 
 	return o;
 }
 
-static int gn_producer_rows(MLOp* o)
-{	/* rows per statistics block this producer's kernel would use, 0 if it cannot emit statistics (no side effect) */
-	mlsd_gemm_args *g = &o->u.gemm;
-	float *keep = g->colstats;
-	if (!keep) g->colstats = (float*)(uintptr_t)64;                  /* probe value: alignment is part of the test */
-	const int r = mlsd_gemm_colstats_rows(g);
-	g->colstats = keep;
-	return (r > 0 && !(g->M % r)) ? r : 0;
+static int gn_producer_rows(const MLOp* o)
+{	/* rows per statistics block this producer's kernel would use, 0 if it cannot emit statistics */
+	const int r = route_of(&o->u.gemm).stats_rows_if;
+	return (r > 0 && !(o->u.gemm.M % r)) ? r : 0;
 }
 
 static void wire_gn_stats(MLCtx* C)
@@ -1146,95 +1147,86 @@ static int tt_ln_on(void)
 	if (on < 0) { const char *e = getenv("MLSD_TT_LN"); on = (e && *e == '0') ? 0 : 1; }
 	return on;
 }
-/* producers moved to the 128 x 160 kernel for a LayerNorm that then could not be handed over (alias rule, scratch) go back to the table's tile */
-static void restore_unfolded_promotions(MLCtx* C)
+/* How the LayerNorm op l can end its producer o: the launch's LayerNorm form (mlsd_gemm_ln_fused: 1 inside the launch, 2 in the split-K reduce pass; 0 none, -1 refused
+ * by the alias rule below) on the tile *tile it would run, and the scratch *need that form takes.  No side effect. */
+static int ln_fold_form(const MLOp* l, const MLOp* o, int slot, int* tile, size_t* need)
 {
-	for (int i=0;i<C->n_ops;++i) {
-		MLOp *o = &C->ops[i];
-		if (o->kind == OP_GEMM && o->saved_variant) { o->u.gemm.tile_variant = o->saved_variant < 0 ? 0 : o->saved_variant; o->saved_variant = 0; }
+	const mlsd_gemm_args *g = &o->u.gemm;
+	if (o->kind != OP_GEMM || o->once || g->C32 != l->u.ln.x || g->ldc32 != l->u.ln.ldx || g->N != l->u.ln.d || g->M != l->u.ln.rows || g->ln_y16) return 0;
+	mlsd_gemm_args t = *g;
+	t.ln_slot = slot;
+	mlsd_gemm_route_info r = route_of(&t);
+	/* Round 5: a producer whose tile cannot end with the LayerNorm (the general tiles of SD1.5's 8192 x 320 / 2048 x 640 projections: 30 of its 48 LayerNorms kept a
+	 * dispatch of their own) moves to the 128 x 160 two-tiles-per-CU kernel when that kernel takes the launch: its N / 160 partner tiles exchange the row statistics.
+	 * Only for N <= 640 (at most 4 partner tiles): in-plan A/B, same box (profiles/r5_gemm_tt_ln_inplan.txt): SD1.5 b1 evaluation -0.8 %, b2 -0.9 % (30 dispatches
+	 * fewer); at N = 1280 (8 partners; SDXL b1 / b2's 2048 x 1280 projections) the same move cost +1.0 / +1.2 % and is not made.  A table entry of the 128 x 320 ping-pong
+	 * tile on whole 128 x 320 tiles keeps that tile.  MLSD_TT_LN=0 keeps the table's tile and the separate LayerNorm. */
+	if (tt_ln_on() && g->tile_variant != MLSD_TILE_ARG(MLSD_TILE_TT) && g->N <= 640 && !(g->tile_variant == MLSD_TILE_ARG(MLSD_TILE_PP_128x320) && !(g->N % 320))) {
+		mlsd_gemm_args m = t;
+		m.tile_variant = MLSD_TILE_ARG(MLSD_TILE_TT);
+		const mlsd_gemm_route_info rm = route_of(&m);
+		if (rm.variant == MLSD_TILE_TT && rm.ln_if) { t = m; r = rm; }
 	}
+	/* (policy: on the 128 x 160 kernel, grids of at most two blocks per CU, where all partner tiles are resident together; MLSD_TT_LN_ANYGRID=1 is for the soak only) */
+	if (!r.ln_if || (r.variant == MLSD_TILE_TT && (long)(g->M / 128) * (g->N / 160) > 512)) return 0;
+	/* the fp16 rows are written one op EARLIER now, by a launch that is still reading its operands: they must not land in a block the arena lent to one of
+	 * them (the attention output `a`, A operand of out_proj, is released right after out_proj is recorded and has exactly the size of the next LayerNorm's
+	 * output: ADVICE r3) */
+	const char *y0 = (const char*)l->u.ln.y16, *y1 = y0 + (size_t)g->M * g->N * 2;
+	const struct { const void* p; size_t n; } rd[4] = {
+		{ g->A, (size_t)g->M * (size_t)g->lda * 2 }, { g->resid, g->resid ? (size_t)g->M * (size_t)g->ldr * 4 : 0 },
+		{ g->W_, (size_t)g->N * (size_t)g->ldb * 2 }, { g->bias, g->bias ? (size_t)g->N * 4 : 0 } };
+	int clash = 0;
+	for (int q=0;q<4;++q) if (rd[q].p && rd[q].n && (const char*)rd[q].p < y1 && y0 < (const char*)rd[q].p + rd[q].n) clash = 1;
+	/* ONE overlap is sound and common (135 of the 199 folds of the SDXL b4 plan): the rows land EXACTLY on the A operand, row for row (same base, K == N,
+	 * same stride).  A tile writes fp16 rows [m0, m0 + 128) only after every tile of that row block has published its statistics, i.e. finished its K
+	 * loop, and those tiles are the only readers of A rows [m0, m0 + 128).  Any other overlap is refused. */
+	if (clash && !(y0 == (const char*)g->A && g->K == g->N && g->lda == g->N && g->resid != (const float*)g->A &&
+	               !((const char*)g->W_ < y1 && y0 < (const char*)g->W_ + rd[2].n))) return -1;
+	*tile = t.tile_variant; *need = (r.ln_ws_bytes_if + 255) & ~(size_t)255;
+	return r.ln_if;
 }
 
 static void wire_ln_fold(MLCtx* C)
 {
 	const char *e = getenv("MLSD_NO_LN_FOLD");
 	if (e && *e && *e != '0') return;
-	if (C->cu_budget > 0 && C->cu_budget < 256) return;      /* the tiles of a row block must be resident together: not on a CU-masked stream */
-	/* pass 0 sizes the scratch (round 6: a region PER folded launch -- its tiles exchange self-tagged records there, and a tag only has to tell this launch's own
-	 * generations apart: 16 bytes per row and column tile, 512 KB for 8192 x 1280), pass 1 hands the LayerNorms over: one region each (the region is what makes a tag unambiguous: it must never be shared between ops) */
+	if (cu_masked(C)) return;      /* the tiles of a row block must be resident together: not on a CU-masked stream */
+	/* pass 0 sizes the scratch of the folds, pass 1 hands the LayerNorms over (round 6: a region PER folded launch -- its tiles exchange self-tagged records there,
+	 * and a tag only has to tell this launch's own generations apart: 16 bytes per row and column tile, 512 KB for 8192 x 1280; the region is what makes a tag
+	 * unambiguous: it must never be shared between ops) */
 	for (int pass=0; pass<2; ++pass) {
-		size_t need_max = 0, ws_off = 0;
-		int any_splitk = 0, slot = 0;
+		size_t ws_off = 0;
+		int slot = 0;
 		for (int i=1;i<C->n_ops;++i) {
-			MLOp *l = &C->ops[i];
-			if (l->kind != OP_LN || !l->u.ln.y16 || l->u.ln.y32 || !l->u.ln.b) continue;
-			const int j = l->gn_src[0];
-			if (j != i - 1) continue;                                /* adjacent ops only: the fp16 output is written one op EARLIER now, and the arena may have lent that
-			                                                          * block to something that runs in between */
-			MLOp *o = &C->ops[j];
-			mlsd_gemm_args *g = &o->u.gemm;
-			if (o->kind != OP_GEMM || o->once || g->C32 != l->u.ln.x || g->ldc32 != l->u.ln.ldx || g->N != l->u.ln.d || g->M != l->u.ln.rows || g->ln_y16) continue;
-			/* two forms (mlsd_gemm_ln_fused): inside a single-round launch of the 128x320 ping-pong tile (needs scratch for the row statistics), or -- round 4 -- in the
-			 * reduce pass of a split-K launch (no scratch, no hand-off) */
-			/* Round 5: a producer whose tile cannot end with the LayerNorm (the general tiles of SD1.5's 8192 x 320 / 2048 x 640 projections: 30 of its 48 LayerNorms kept a
-			 * dispatch of their own) moves to the 128 x 160 two-tiles-per-CU kernel when that kernel takes the shape: its N / 160 partner tiles exchange the row statistics.
-			 * Only for N <= 640 (at most 4 partner tiles): in-plan A/B, same box (profiles/r5_gemm_tt_ln_inplan.txt): SD1.5 b1 evaluation -0.8 %, b2 -0.9 % (30 dispatches
-			 * fewer); at N = 1280 (8 partners; SDXL b1 / b2's 2048 x 1280 projections) the same move cost +1.0 / +1.2 % and is not made.
-			 * MLSD_TT_LN=0 keeps the table's tile and the separate LayerNorm. */
-			if (!pass && tt_ln_on() && g->tile_variant != VARIANT_TT && !(g->ksplit > 1) && (!(g->tile_variant == 19 && !(g->N % 320)) && g->N <= 640) &&
-			    !(g->M % 128) && !(g->N % 160) && !(g->K & 63) && g->K >= 128 && g->act == MLSD_ACT_NONE && !g->rowbias && !g->bias_m && !g->colstats && !g->C16 &&
-			    (!g->conv || (g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && !g->upsample)) && (long)(g->M / 128) * (g->N / 160) <= 512) {
-				o->saved_variant = g->tile_variant ? g->tile_variant : -1;
-				g->tile_variant = VARIANT_TT;
+			MLOp *l = &C->ops[i], *o = &C->ops[i - 1];
+			/* (adjacent ops only: the fp16 output is written one op EARLIER now, and the arena may have lent that block to something that runs in between) */
+			if (l->kind != OP_LN || !l->u.ln.y16 || l->u.ln.y32 || !l->u.ln.b || l->gn_src[0] != i - 1) continue;
+			int tile; size_t need;
+			const int form = ln_fold_form(l, o, slot, &tile, &need);
+			if (form < 0) C->n_ln_alias += pass;
+			if (form <= 0) continue;
+			if (pass) {
+				mlsd_gemm_args *g = &o->u.gemm;
+				if (tile != g->tile_variant) { o->folded_from = g->tile_variant ? g->tile_variant : -1; g->tile_variant = tile; }
+				g->ln_y16 = l->u.ln.y16; g->ldln = g->N; g->ln_gamma = l->u.ln.g; g->ln_beta = l->u.ln.b; g->ln_eps = l->u.ln.eps; g->ln_ws = (float*)((char*)C->ln_ws + ws_off); g->ln_cnt = C->ln_cnt; g->ln_slot = slot;
+				l->fused = 1; C->n_ln_fused++;
 			}
-			const int tt_form = g->tile_variant == VARIANT_TT && !(g->M % 128) && !(g->N % 160) && !(g->ksplit > 1) &&
-			                    (long)(g->M / 128) * (g->N / 160) <= 512;      /* (N / 160 partner tiles per row block; at most two blocks per CU: all resident together, gemm_tt.hip) */
-			const int pp_form = tt_form || (g->tile_variant != VARIANT_TT && !(g->M % 128) && !(g->N % 320) && !(g->ksplit > 1));
-			const size_t need = tt_form ? (size_t)(g->M / 128) * (g->N / 160) * 128 * 16 : pp_form ? (size_t)(g->M / 128) * (g->N / 320) * 128 * 16 : 0;
-			if (!pass) { need_max += (need + 255) & ~(size_t)255; if (!pp_form && g->ksplit > 1) any_splitk = 1; continue; }      /* (need_max: the SUM over the candidates) */
-			if (ws_off + need > C->ln_ws_bytes || slot >= LN_CNT_WORDS - 1) continue;
-			if (!pp_form && !(g->ksplit > 1)) continue;
-			{	/* the fp16 rows are written one op EARLIER now, by a launch that is still reading its operands: they must not land in a block the arena lent to one of
-				 * them (the attention output `a`, A operand of out_proj, is released right after out_proj is recorded and has exactly the size of the next LayerNorm's
-				 * output: ADVICE r3) */
-				const char *y0 = (const char*)l->u.ln.y16, *y1 = y0 + (size_t)g->M * g->N * 2;
-				const struct { const void* p; size_t n; } rd[4] = {
-					{ g->A, (size_t)g->M * (size_t)g->lda * 2 }, { g->resid, g->resid ? (size_t)g->M * (size_t)g->ldr * 4 : 0 },
-					{ g->W_, (size_t)g->N * (size_t)g->ldb * 2 }, { g->bias, g->bias ? (size_t)g->N * 4 : 0 } };
-				int clash = 0;
-				for (int q=0;q<4;++q) if (rd[q].p && rd[q].n && (const char*)rd[q].p < y1 && y0 < (const char*)rd[q].p + rd[q].n) clash = 1;
-				/* ONE overlap is sound and common (135 of the 199 folds of the SDXL b4 plan): the rows land EXACTLY on the A operand, row for row (same base, K == N,
-				 * same stride).  A tile writes fp16 rows [m0, m0 + 128) only after every tile of that row block has published its statistics, i.e. finished its K
-				 * loop, and those tiles are the only readers of A rows [m0, m0 + 128).  Any other overlap is refused. */
-				if (clash && !(y0 == (const char*)g->A && g->K == g->N && g->lda == g->N && g->resid != (const float*)g->A &&
-				               !((const char*)g->W_ < y1 && y0 < (const char*)g->W_ + rd[2].n))) { C->n_ln_alias++; continue; }
-			}
-			g->ln_y16 = l->u.ln.y16; g->ldln = g->N; g->ln_gamma = l->u.ln.g; g->ln_beta = l->u.ln.b; g->ln_eps = l->u.ln.eps; g->ln_ws = (float*)((char*)C->ln_ws + ws_off); g->ln_cnt = C->ln_cnt; g->ln_slot = slot;
-			if (mlsd_gemm_ln_fused(g) >= 1) {
-				l->fused = 1; C->n_ln_fused++; o->folded_from = o->saved_variant; o->saved_variant = 0;
-				if (need) { ws_off += (need + 255) & ~(size_t)255; ++slot; }      /* (a LayerNorm in a split-K reduce pass needs neither) */
-			}
-			else { g->ln_y16 = NULL; g->ln_gamma = g->ln_beta = NULL; g->ln_ws = NULL; g->ln_cnt = NULL; }
+			if (need) { ws_off += need; ++slot; }      /* (a LayerNorm in a split-K reduce pass needs neither) */
 		}
-		if (!pass) {
-			/* (every way out of pass 0 still reaches restore_unfolded_promotions: a producer that pass 0 moved to the 128x160 kernel for a fold that then does not
-			 * happen -- nothing to fold, or the counter / workspace allocation failed -- gets the table's tile back) */
-			if (!need_max && !any_splitk) break;
-			if (!need_max) continue;
-			if (!C->ln_cnt) {
-				if (mlsd_malloc((void**)&C->ln_cnt, LN_CNT_WORDS * 4)) break;
-				if (mlsd_memset(C->ln_cnt, 0, LN_CNT_WORDS * 4, C->stream) || mlsd_stream_sync(C->stream)) break;
-			}
-			if (C->ln_ws_bytes < need_max) {
-				if (C->ln_ws) { mlsd_free(C->ln_ws); C->mem_compute -= C->ln_ws_bytes; }
-				C->ln_ws = NULL; C->ln_ws_bytes = 0;
-				if (mlsd_malloc((void**)&C->ln_ws, need_max)) break;
-				if (mlsd_memset(C->ln_ws, 0, need_max, C->stream) || mlsd_stream_sync(C->stream)) { mlsd_free(C->ln_ws); C->ln_ws = NULL; break; }      /* tags 0: no launch ever writes that one */
-				C->ln_ws_bytes = need_max; C->mem_compute += need_max;
-			}
+		if (pass || !ws_off) continue;
+		if (!C->ln_cnt) {
+			if (mlsd_malloc((void**)&C->ln_cnt, LN_CNT_WORDS * 4)) return;
+			if (mlsd_memset(C->ln_cnt, 0, LN_CNT_WORDS * 4, C->stream) || mlsd_stream_sync(C->stream)) return;
+		}
+		if (C->ln_ws_bytes < ws_off) {
+			if (C->ln_ws) { mlsd_free(C->ln_ws); C->mem_compute -= C->ln_ws_bytes; }
+			C->ln_ws = NULL; C->ln_ws_bytes = 0;
+			if (mlsd_malloc((void**)&C->ln_ws, ws_off)) return;
+			if (mlsd_memset(C->ln_ws, 0, ws_off, C->stream) || mlsd_stream_sync(C->stream)) { mlsd_free(C->ln_ws); C->ln_ws = NULL; return; }      /* tags 0: no launch ever writes that one */
+			C->ln_ws_bytes = ws_off; C->mem_compute += ws_off;
 		}
 	}
-	restore_unfolded_promotions(C);
 }
 
 static int hoist_on(void);

@@ -8,6 +8,22 @@ c_i64, c_int, c_f = ctypes.c_int64, ctypes.c_int, ctypes.c_float
 
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_GELU_QUICK, ACT_RELU, ACT_GEGLU = range(6)
 
+# tile variants (MLSD_TILE_*) and the labels mlsd_gemm_variant prints for them
+TILE_128x128, TILE_64x128, TILE_256x128, TILE_256x128_S3, TILE_256x256, TILE_128x320 = 0, 1, 3, 4, 9, 16
+TILE_PP_256x256, TILE_PP_128x320, TILE_PPSK_256x256, TILE_PP2_128x320, TILE_PP2_256x256, TILE_PPB_128x320 = 17, 18, 19, 20, 21, 22
+TILE_PP2_256x128, TILE_W4_256x256, TILE_W4_128x320, TILE_PPSK_128x320, TILE_SKINNY, TILE_TT, TILE_CONV_SMALLN = 25, 26, 27, 28, 29, 30, 31
+TILE_LABELS = {TILE_128x128: "128x128x64s2", TILE_64x128: "64x128x64s2", TILE_256x128: "256x128x64s2", TILE_256x128_S3: "256x128x32s3",
+               TILE_256x256: "256x256x64s2w16", TILE_128x320: "128x320x64s2", TILE_PP_256x256: "256x256x64pp", TILE_PP_128x320: "128x320x64pp",
+               TILE_PPSK_256x256: "256x256x64ppsk", TILE_PP2_128x320: "128x320x64pp2", TILE_PP2_256x256: "256x256x64pp2",
+               TILE_PPB_128x320: "128x320x64ppb", TILE_PP2_256x128: "256x128x64pp2", TILE_W4_256x256: "256x256x64w4",
+               TILE_W4_128x320: "128x320x64w4", TILE_PPSK_128x320: "128x320x64ppsk", TILE_SKINNY: "skinny128x64", TILE_TT: "128x160x64tt",
+               TILE_CONV_SMALLN: "conv3x3n16"}
+
+
+def tile_arg(v):
+    """MLSD_TILE_ARG: the mlsd_gemm_args.tile_variant that asks for tile variant v."""
+    return v + 1
+
 
 class GemmArgs(ctypes.Structure):
     _fields_ = [("A", vp), ("lda", c_i64), ("conv", c_int), ("n_img", c_int), ("H", c_int), ("W", c_int),
@@ -22,6 +38,11 @@ class GemmArgs(ctypes.Structure):
                 ("gn_silu", c_int),
                 ("xa_k", vp), ("xa_ldk", c_i64), ("xa_vt", vp), ("xa_out", vp), ("xa_ldo", c_i64), ("xa_Tq", c_int), ("xa_Tk", c_int),
                 ("colstats_shift", c_int)]
+
+
+class GemmRouteInfo(ctypes.Structure):
+    _fields_ = [("variant", c_int), ("asked", c_int), ("nsplit", c_int), ("stats_rows", c_int), ("ln", c_int), ("gn", c_int), ("xattn", c_int),
+                ("handoff", c_int), ("stats_rows_if", c_int), ("ln_if", c_int), ("ln_ws_bytes_if", ctypes.c_size_t)]
 
 
 class AttnArgs(ctypes.Structure):
@@ -51,6 +72,12 @@ def gemm_variant(args):
     f = lib().mlsd_gemm_variant
     f.restype = ctypes.c_char_p
     return f(ctypes.byref(args)).decode()
+
+
+def gemm_route(args):
+    r = GemmRouteInfo()
+    check(lib().mlsd_gemm_route(ctypes.byref(args), ctypes.byref(r)), "mlsd_gemm_route")
+    return r
 
 
 def attention(args, stream=None):

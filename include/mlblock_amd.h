@@ -45,6 +45,8 @@ void   mlctx_set_tprefix(MLCtx* C, const char* prefix);   /* C->c.tprefix */
 void   mlctx_set_flags(MLCtx* C, int flags);
 void   mlctx_set_wtype(MLCtx* C, int wtype);               /* linear weight type of the CHECKPOINT (MLT_F16 | MLT_F32 | MLT_BF16, src/mlimgsynth.c:1242);
                                                               * device storage and MFMA operands are always F16 */
+void   mlctx_set_conv_wrap(MLCtx* C, int mode);         /* circular padding of the convolutions built from now on (seamless tiling): 0 none, 1 columns (x),
+                                                              * 2 rows (y), 3 both; a tap outside the image reads the pixel modulo the image size */
 int    mlctx_prep(MLCtx* C);              /* resolve parameter names, finish the plan (result = last tensor) */
 int    mlctx_compute(MLCtx* C);           /* replay the plan on the context's stream (asynchronous) */
 int    mlctx_sync(MLCtx* C);
@@ -159,6 +161,7 @@ typedef struct MLCtxInfo {
 void mlctx_info(const MLCtx* C, MLCtxInfo* out);
 /* per-op listing for profiling: returns kernel label, flops of op i */
 int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flops);
+const struct mlsd_gemm_args* mlctx_op_gemm_args(const MLCtx* C, int i);   /* op i's launch arguments if it is a GEMM / convolution, else NULL */
 /* algorithmic HBM bytes of op i (operands read once, outputs written once) */
 double mlctx_op_bytes(const MLCtx* C, int i);
 /* time every op individually with HIP events (diagnostics; synchronises) */

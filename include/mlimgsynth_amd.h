@@ -287,7 +287,11 @@ typedef struct {
  * synchronised first); a negative return aborts the generation and is returned by mlis_amd_denoise/generate */
 typedef int (*mlis_amd_progress_fn)(void* user, int step, int n_step, int nfe);
 
-MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream);
+MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream);        /* = mlis_amd_create_ex(cfg, 0, stream) */
+/* seamless tiling: every spatial convolution of the UNet, decoder and encoder plans pads circularly (mlctx_set_conv_wrap): 0 none, 1 x (left and right edges
+ * meet), 2 y, 3 xy.  The tiled KL-VAE plans (mlis_amd_set_vae_tile) do not wrap: tiles cannot see the opposite edge. */
+MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream);
+int mlis_amd_tiling(const MLIS_AmdCtx* S);
 void mlis_amd_destroy(MLIS_AmdCtx* S);
 /* conditioning for the whole batch (shared prompt, as generate.sh): cond/uncond [n_ctx_tok][n_ctx] fp32 host (77 rows unless the config says otherwise),
  * label/unlabel [adm] or NULL */

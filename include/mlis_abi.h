@@ -50,7 +50,9 @@ typedef enum {
 	MLIS_OPT_IMAGE_MASK = 21, MLIS_OPT_NO_DECODE = 22, MLIS_OPT_TENSOR_USE_FLAGS = 23, MLIS_OPT_SEED = 24, MLIS_OPT_VAE_TILE = 25,
 	MLIS_OPT_UNET_SPLIT = 26, MLIS_OPT_THREADS = 27, MLIS_OPT_DUMP_FLAGS = 28, MLIS_OPT_AUX_DIR = 29, MLIS_OPT_CALLBACK = 30,
 	MLIS_OPT_ERROR_HANDLER = 31, MLIS_OPT_LOG_LEVEL = 32, MLIS_OPT_MODEL_TYPE = 33, MLIS_OPT_WEIGHT_TYPE = 34,
-	MLIS_OPT_NO_PROMPT_PARSE = 35, MLIS_OPT__LAST = 35
+	MLIS_OPT_NO_PROMPT_PARSE = 35, MLIS_OPT__LAST = 35,
+	/* extensions of this implementation (ids from 101, as MLIS_MODEL_TYPE_AMD_*; MLIS_OPT__LAST stays the reference's last option) */
+	MLIS_OPT_AMD_TILING = 101      /* "tiling": seamless tiling, none|x|y|xy or 0..3 (int); the UNet and codec convolutions pad circularly */
 } MLIS_Option;
 
 typedef struct MLIS_Ctx MLIS_Ctx;                                                                            /* :352 */

@@ -202,6 +202,10 @@ typedef struct mlsd_gemm_args {
 	 * ~2^-24 sqrt(rows) r^2 of a group's variance (r = |mean| / std: percents at r = 300), which no later double arithmetic recovers;
 	 * the plan builder always asks for 1, 0 keeps the meaning the field had for callers that do not set it. */
 	int colstats_shift;
+	/* conv: circular padding (seamless tiling).  Bit 0 wraps columns, bit 1 rows: a tap outside the (upsampled) source image reads the pixel at
+	 * that coordinate modulo the extent, in the same image, instead of zero.  Needs pad <= the extent of each wrapped axis (one fold); mlsd_gemm
+	 * fails otherwise.  A launch none of whose taps can leave the image runs exactly as with 0. */
+	int wrap;
 } mlsd_gemm_args;
 
 int mlsd_gemm(const mlsd_gemm_args* a, void* stream);

@@ -31,6 +31,7 @@ struct SNP {
     const float* bias;
     float* C32; long ldc32;
     int n_img, H, W, N, TR, tiles_x, tiles_y;
+    int wrap;                           // mlsd_gemm_args.wrap (the WRAP builds): bit 0 columns, bit 1 rows
 };
 
 __device__ uint4 g_sn_zero[1];           // 16 zero bytes: source of every padded / unused 16-byte chunk (LDS-DMA has no bounds check and no zero fill)
@@ -42,7 +43,9 @@ __device__ __forceinline__ void sn_wait_vmcnt()
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int CIN, int NR>
+// WRAP: circular padding (SNP::wrap): the halo rows -1 / H and columns -1 / W are read from the opposite edge of the same image (the ragged right edge of a strip,
+// columns beyond W, still reads zeros: those outputs are never stored)
+template <int CIN, int NR, bool WRAP = false>
 __global__ __launch_bounds__(256, 2) void conv_smalln_kernel(const SNP p)
 {
     constexpr int PIXB = CIN * 2;                    // bytes per pixel
@@ -81,11 +84,13 @@ __global__ __launch_bounds__(256, 2) void conv_smalln_kernel(const SNP p)
     }
     const uintptr_t zaddr = (uintptr_t)zsrc;
     auto issue_row = [&](int yi, int slot) {
+        if constexpr (WRAP) { if ((p.wrap & 2) && (yi == -1 || yi == p.H)) yi = yi < 0 ? p.H - 1 : 0; }
         const bool rowok = (unsigned)yi < (unsigned)p.H;
         const uintptr_t rowa = (uintptr_t)(Aimg + (long)yi * p.W * p.lda);
 #pragma unroll
         for (int t = 0; t < NI; ++t) {
-            const int gx = x0 - 2 + d_pxl[t];
+            int gx = x0 - 2 + d_pxl[t];
+            if constexpr (WRAP) { if ((p.wrap & 1) && (gx == -1 || gx == p.W)) gx = gx < 0 ? p.W - 1 : 0; }
             const bool ok = rowok && (unsigned)gx < (unsigned)p.W && d_pxl[t] >= 1 && d_pxl[t] <= 18;
             // ONE instruction per piece whatever the lanes need: the address is blended arithmetically (as a branch the compiler emitted two DMA instructions per piece,
             // one per side, and the counted waits below count instructions)
@@ -199,7 +204,7 @@ extern "C" int mlsd_conv_smalln(const mlsd_gemm_args* a, void* stream)
     if (!mlsd_conv_smalln_eligible(a)) return mlsd_set_error(-1, "mlsd_conv_smalln: launch not eligible for the small-Cout streaming convolution");
     SNP p;
     p.A = (const _Float16*)a->A; p.lda = a->lda; p.Wt = (const _Float16*)a->W_; p.ldb = a->ldb; p.bias = a->bias; p.C32 = a->C32; p.ldc32 = a->ldc32;
-    p.n_img = a->n_img; p.H = a->H; p.W = a->W; p.N = a->N;
+    p.n_img = a->n_img; p.H = a->H; p.W = a->W; p.N = a->N; p.wrap = a->wrap & 3;
     p.tiles_x = (a->W + 63) / 64;
     /* strip height: every strip re-reads 2 halo rows and pays one pipeline fill, so the tallest strip that still leaves >= 512 blocks (two per CU) -- measured on SDXL b4
      * (4 x 1024 x 1024 x 128): 240 us at 128 rows (512 blocks), 246 at 64, 254 at 16; on one 512 x 512 image: 21 us at 16 rows (256 blocks), 31 at 32, 96 at 128
@@ -222,6 +227,10 @@ extern "C" int mlsd_conv_smalln(const mlsd_gemm_args* a, void* stream)
         hipLaunchKernelGGL(kfn, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
         return mlsd_check_launch("conv_smalln_kernel");
     };
+    if (p.wrap) {       // circular padding: the default ring depths only
+        if (a->Cin == 128) return go(conv_smalln_kernel<128, 4, true>, 4 * 4 * 5120);
+        return go(conv_smalln_kernel<64, 5, true>, 4 * 5 * 3072);
+    }
     if (a->Cin == 128) {
         switch (nr) {
         case 4: return go(conv_smalln_kernel<128, 4>, 4 * 4 * 5120);

@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
+#include <stddef.h>
 #include <type_traits>
 #include "common.hpp"
 #include "mlsd_kernels.h"
@@ -53,6 +54,7 @@ struct GemmP {
     const float* bias;
     const float* biasm;
     int act_post;
+    int wrap;     // conv: mlsd_gemm_args.wrap of the kernels built with the wrap (in act_post's padding: no other field moves)
     const float* rowbias;
     int rows_per_batch;
     long ldrb;
@@ -95,6 +97,11 @@ struct GemmP {
     float xa_sc;
 };
 
+static_assert(offsetof(GemmP, wrap) + sizeof(int) == offsetof(GemmP, rowbias), "GemmP::wrap must fill act_post's padding");
+
+// wrap (circular padding): a coordinate at most one extent outside [0, e) folded into it
+__device__ __forceinline__ int wrap_fold(int v, int e) { return v < 0 ? v + e : (v >= e ? v - e : v); }
+
 // LDS tile: rows of BK halfs (128 B at BK=64, 64 B at BK=32); the 16-byte chunk c of row r lives at slot
 // c ^ swz(r) so that a ds_read_b128 fragment read (32 lanes = 32 consecutive rows, one logical chunk)
 // touches every bank once (64 banks x 4 B; 16-lane service groups).
@@ -125,7 +132,8 @@ __device__ __forceinline__ void wait_vmcnt()
 // ST: the build whose wide epilogue also emits column statistics (GemmP::colstats).  A build of its own: the 8 + 8 running sums push the 512- / 1024-thread tiles over
 // 128 registers (120 -> 130: three waves per SIMD instead of four, the VAE's 256x128 convolutions +5 % -- measured with the sums in the common build); here the ST builds
 // of those tiles are held to four waves per SIMD and spill a few registers in the epilogue instead.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool CONV, int NSTAGE, int DBG = 0, bool REG = false, bool PAR = false, bool ST = false>
+// WRAP: a convolution with circular padding (GemmP::wrap): the tap coordinates are folded into the image before the bounds check
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, bool CONV, int NSTAGE, int DBG = 0, bool REG = false, bool PAR = false, bool ST = false, bool WRAP = false>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) __attribute__((amdgpu_waves_per_eu((ST && WAVES_M * WAVES_N >= 8) ? 4 : 1, (ST && WAVES_M * WAVES_N >= 8) ? 4 : 10)))
 void gemm_kernel(const GemmP p, const GemmP pe)
 {
@@ -218,7 +226,11 @@ void gemm_kernel(const GemmP p, const GemmP pe)
         for (int i = 0; i < A_IT; ++i) {
             const _Float16* src = zsrc;
             if (CONV) {
-                const int ih = row_ih0[i] + g_kh, iw = row_iw0[i] + g_kw;
+                int ih = row_ih0[i] + g_kh, iw = row_iw0[i] + g_kw;
+                if constexpr (WRAP) {
+                    if (p.wrap & 2) ih = wrap_fold(ih, He);
+                    if (p.wrap & 1) iw = wrap_fold(iw, We);
+                }
                 if (row_ok[i] && g_kh < p.KH && (unsigned)ih < (unsigned)He && (unsigned)iw < (unsigned)We) {
                     const int sh = p.ups ? (ih >> 1) : ih, sw = p.ups ? (iw >> 1) : iw;
                     src = p.A + (long)(row_pix[i] + sh * p.W + sw) * p.lda + g_cin;
@@ -254,7 +266,7 @@ void gemm_kernel(const GemmP p, const GemmP pe)
         for (int i = 0; i < A_IT; ++i) {
             uint4 v = make_uint4(0, 0, 0, 0);
             if (CONV) {
-                const int ih = row_ih0[i] + g_kh, iw = row_iw0[i] + g_kw;
+                const int ih = row_ih0[i] + g_kh, iw = row_iw0[i] + g_kw;      // (no wrap build of the register-staged path: resolve() keeps wrap launches off REG tiles)
                 if (row_ok[i] && g_kh < p.KH && (unsigned)ih < (unsigned)He && (unsigned)iw < (unsigned)We) {
                     const int sh = p.ups ? (ih >> 1) : ih, sw = p.ups ? (iw >> 1) : iw;
                     v = *reinterpret_cast<const uint4*>(p.A + (long)(row_pix[i] + sh * p.W + sw) * p.lda + g_cin);
@@ -1034,7 +1046,29 @@ struct GemmRoute {
     int stats_rows;         // rows per column-statistics block the launch writes (0: none)
     int ln;                 // LayerNorm of the output: 1 at the end of the launch, 2 in the split-K reduce pass
     bool gn, xattn;         // GroupNorm in the split-K reduce pass; cross attention at the end of the q projection
+    int wrap;               // conv_wrap(): the axes along which the launch's taps wrap (0: zero padding, the kernels without the wrap)
 };
+
+// The axes (mlsd_gemm_args.wrap bits) along which a wrap launch's taps can actually leave the source image: 0 for a linear launch, a 1x1 convolution, pad = 0 without
+// an end overhang.  Only these decide the route and the kernel; the rest of a->wrap changes nothing.
+int conv_wrap(const mlsd_gemm_args* a)
+{
+    if (!a->conv || !(a->wrap & 3)) return 0;
+    const int He = a->upsample ? 2 * a->H : a->H, We = a->upsample ? 2 * a->W : a->W;
+    int w = 0;
+    if ((a->wrap & 2) && (a->pad > 0 || (a->OH - 1) * a->stride - a->pad + a->KH > He)) w |= 2;
+    if ((a->wrap & 1) && (a->pad > 0 || (a->OW - 1) * a->stride - a->pad + a->KW > We)) w |= 1;
+    return w;
+}
+
+// 1 if one fold brings every tap of a wrap launch back into the image: no tap lies more than one extent before or after it
+bool wrap_foldable(const mlsd_gemm_args* a, int wrap)
+{
+    const int He = a->upsample ? 2 * a->H : a->H, We = a->upsample ? 2 * a->W : a->W;
+    if ((wrap & 2) && (a->pad > He || (a->OH - 1) * a->stride - a->pad + a->KH > 2 * He)) return false;
+    if ((wrap & 1) && (a->pad > We || (a->OW - 1) * a->stride - a->pad + a->KW > 2 * We)) return false;
+    return true;
+}
 
 int g_gemm_ncu = 256;   // CUs a persistent launch may occupy (mlsd_gemm_set_cus: half-chip partitions run 128-block grids)
 int g_gemm_dbg = 0;
@@ -1062,7 +1096,7 @@ bool splitk_par_ok(const mlsd_gemm_args* a, int BM, int nsplit, long tiles)
 #ifndef MLSD_GEMM_EXPERIMENTS
     return false;       // (the kernels are not in the product build)
 #endif
-    if (!sk_par_on() || !a->sk_flags || nsplit < 2 || tiles > 2047) return false;
+    if (!sk_par_on() || !a->sk_flags || nsplit < 2 || tiles > 2047 || a->wrap) return false;      // (no wrap build of the PAR kernels)
     const int cus = device_cus();
     if (cus < g_gemm_ncu || g_gemm_ncu < 256) return false;
     return tiles * nsplit <= (long)cus * (BM == 64 ? 3 : 2);
@@ -1084,7 +1118,7 @@ int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
     p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
     p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = 0;
+    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = 0; p.wrap = r.wrap;
     p.bias = a->bias; p.biasm = a->bias_m; p.act_post = a->act_after_resid; p.rowbias = a->rowbias; p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
     p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
     p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
@@ -1155,6 +1189,12 @@ int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     if (!a->conv && g_gemm_dbg == 1) return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 1, REG>);
     if (!a->conv && g_gemm_dbg == 2) return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 2, REG>);
 #endif
+    if (r.wrap) {       // circular padding: the LDS-DMA builds only (resolve() never sends a wrap launch to a register-staged tile)
+        if constexpr (((BN / WAVES_N) / 32) % 2 == 0) {
+            if (p.colstats) return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, false, true, true>);
+        }
+        return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, false, false, true>);
+    }
     if constexpr (((BN / WAVES_N) / 32) % 2 == 0 && !REG) {       // the statistics builds (whole 64-column wave slabs)
         if (p.colstats) return a->conv ? go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, false, true>) : go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, false, false, true>);
     }
@@ -1187,6 +1227,10 @@ bool pp_eligible(const mlsd_gemm_args* a, int BM, int BN)
     if (a->conv && a->upsample) {       // nearest-2x upsampled source (round 5): stride 1, and the two epilogues the upsampling convolutions of the UNets / decoders use
         const int e = pp_epilogue_kind(a, BN);
         if (a->stride != 1 || a->pad > 16 || a->H > 16000 || a->W > 16000 || (e != 2 /* PP_EPI_F32 */ && e != 5 /* PP_EPI_F32_STATS */)) return false;
+    }
+    if (a->conv && a->wrap) {           // circular padding (built with the four fp32 epilogues; the row keeps (oh - pad, ow - pad) in 16-bit halves as the upsampling form does)
+        const int e = pp_epilogue_kind(a, BN);
+        if (a->pad > 16 || a->H > 16000 || a->W > 16000 || (e != PP_EPI_F32 && e != PP_EPI_F32_STATS && e != PP_EPI_F32_RES && e != PP_EPI_F32_RES_STATS)) return false;
     }
     if (a->rowbias && ((a->rows_per_batch > 0 ? a->rows_per_batch : 1) % BM)) return false;
     if (a->act == MLSD_ACT_GEGLU && BN != 256) return false;
@@ -1264,6 +1308,7 @@ bool sk_eligible(const mlsd_gemm_args* a, int BM, int BN, bool ignore_stats = fa
 {
     if (!pp_eligible(a, BM, BN) || !a->ws || !a->sk_flags || ((uintptr_t)a->ws & 15) || device_cus() < g_gemm_ncu || (a->conv && a->upsample)) return false;
     if (a->conv && a->colstats && !ignore_stats) return false;      // (the conv builds with the statistics epilogue do not fit the register budget beside the hand-off code)
+    if (a->conv && a->wrap && !a->colstats && pp_epilogue_kind(a, BN) != PP_EPI_F32 && pp_epilogue_kind(a, BN) != PP_EPI_F32_RES) return false;     // (the wrap builds: F32, F32_RES)
     const long tiles = (long)((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN), nkt = a->K / 64;
     const long L = sk_share(tiles, (int)nkt, g_gemm_ncu);
     return nkt >= 3 && L >= 4 && L < nkt && a->ws_bytes >= (size_t)g_gemm_ncu * BM * BN * sizeof(float);    // (L == nkt: nothing to split)
@@ -1277,7 +1322,7 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
     p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
     p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = g_gemm_korder;
+    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = g_gemm_korder; p.wrap = r.wrap;
     p.bias = a->bias; p.biasm = a->bias_m; p.act_post = a->act_after_resid; p.rowbias = a->rowbias; p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
     p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
     p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
@@ -1317,6 +1362,11 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     p.colstats = (epi == PP_EPI_F32_STATS || epi == PP_EPI_F32_RES_STATS) ? a->colstats : nullptr;
     p.cs_shift = a->colstats_shift ? 1 : 0;
     if constexpr (SK) {       // the stream-K builds: the fp32 epilogues of the long-K convs / feed-forward outputs, fp16 for the fused projections
+        if (r.wrap) {         // (sk_eligible admits these two epilogues only)
+            if (epi == PP_EPI_F32) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32, true>);
+            if (epi == PP_EPI_F32_RES) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32_RES, true>);
+            return mlsd_set_error(-1, "mlsd_gemm: stream-K tile: wrap convolution with epilogue %d", epi);
+        }
         if (a->conv) {
             switch (epi) {
             case PP_EPI_F32: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, true, PP_EPI_F32, true>);
@@ -1332,6 +1382,21 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
         case PP_EPI_F32_RES: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, false, PP_EPI_F32_RES, true>);
         default: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, false, PP_EPI_GENERIC, true>);
         }
+    }
+    if (r.wrap) {                       // circular padding (CONV | 4; pp_eligible admits these epilogues only)
+        if (a->upsample) {
+            if (epi == PP_EPI_F32_STATS) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 6, PP_EPI_F32_STATS, false, NPH, SCH>);
+            if (epi == PP_EPI_F32) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 6, PP_EPI_F32, false, NPH, SCH>);
+        } else {
+            switch (epi) {
+            case PP_EPI_F32: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32, false, NPH, SCH>);
+            case PP_EPI_F32_RES: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32_RES, false, NPH, SCH>);
+            case PP_EPI_F32_STATS: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32_STATS, false, NPH, SCH>);
+            case PP_EPI_F32_RES_STATS: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32_RES_STATS, false, NPH, SCH>);
+            default: break;
+            }
+        }
+        return mlsd_set_error(-1, "mlsd_gemm: ping-pong tile: wrap convolution with epilogue %d", epi);
     }
     if (a->conv && a->upsample) {       // (pp_eligible admits these two epilogues only)
         if (epi == PP_EPI_F32_STATS) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 2, PP_EPI_F32_STATS, false, NPH, SCH>);
@@ -1376,6 +1441,7 @@ bool skinny_eligible(const mlsd_gemm_args* a)
 {
     if (a->M > 128 || a->act == MLSD_ACT_GEGLU || (a->K & 63) || a->K < 128 || (a->N & 3) || !a->ws || ((uintptr_t)a->ws & 15)) return false;
     if (a->conv && (a->upsample || (a->Cin & 63) || a->KH * a->KW > 9)) return false;
+    if (a->conv && a->wrap && (a->pad > 16 || a->H > 16000 || a->W > 16000)) return false;     // (the wrap build keeps (oh - pad, ow - pad) in 16-bit halves)
     return wide_epilogue_ok(a);
 }
 
@@ -1398,7 +1464,7 @@ int launch_skinny(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
     p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
     p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = 0;
+    p.stride = a->stride; p.pad = a->pad; p.ups = 0; p.wrap = r.wrap;
     p.rows_per_batch = 1; p.vec = 1; p.gw = 0;
     const int nsplit = r.nsplit;
     const size_t need = (size_t)nsplit * a->M * a->N * sizeof(float);
@@ -1431,6 +1497,11 @@ int launch_skinny(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     if (g_gemm_dbg == 32) return a->conv ? go(gemm_skinny_kernel<true, 8, 7>, 128, 7) : go(gemm_skinny_kernel<false, 8, 7>, 128, 7);
     if (g_gemm_dbg == 48) return a->conv ? go(gemm_skinny_kernel<true, 8, 3, 1>, 128, 3) : go(gemm_skinny_kernel<false, 8, 3, 1>, 128, 3);
 #endif
+    if (r.wrap) {       // circular padding (conv only)
+        if (a->M <= 16) return go(gemm_skinny_kernel<true, 1, PF, 0, true>, 32);
+        if (a->M <= 64) return go(gemm_skinny_kernel<true, 4, PF, 0, true>, 64);
+        return go(gemm_skinny_kernel<true, 8, PF, 0, true>, 128);
+    }
     if (a->M <= 16) return a->conv ? go(gemm_skinny_kernel<true, 1, PF>, 32) : go(gemm_skinny_kernel<false, 1, PF>, 32);
     if (a->M <= 64) return a->conv ? go(gemm_skinny_kernel<true, 4, PF>, 64) : go(gemm_skinny_kernel<false, 4, PF>, 64);
     return a->conv ? go(gemm_skinny_kernel<true, 8, PF>, 128) : go(gemm_skinny_kernel<false, 8, PF>, 128);
@@ -1534,6 +1605,9 @@ int general_stats_rows(const mlsd_gemm_args* a, const GemmRoute& r, const Varian
 GemmRoute resolve(const mlsd_gemm_args* a)
 {
     GemmRoute r{};
+    mlsd_gemm_args aw;          // a wrap launch is routed on its EFFECTIVE wrap: the axes along which a tap can leave the image (none: exactly as wrap = 0)
+    if (a->wrap) { aw = *a; aw.wrap = conv_wrap(a); a = &aw; }
+    r.wrap = a->wrap;
     r.pick = pick_variant(a);
     int v = r.pick;
     GemmFamily fam = FAM_GENERAL;
@@ -1550,6 +1624,10 @@ GemmRoute resolve(const mlsd_gemm_args* a)
     case MLSD_TILE_PPB_128x320: v = MLSD_TILE_PP_128x320; break;
     case MLSD_TILE_PP2_256x128: v = MLSD_TILE_256x128; break;
     case 2: case 5: case 6: case 7: case 8: case 10: case 11: case 12: case 13: case 14: case 15: case 23: case 24: v = MLSD_TILE_128x128; break;
+#else                           /* the wrap is built into the product tiles only: a wrap launch asked of another one runs on the product tile nearest in shape */
+    case MLSD_TILE_PPB_128x320: if (r.wrap) v = MLSD_TILE_PP_128x320; break;
+    case MLSD_TILE_PP2_256x128: if (r.wrap) v = MLSD_TILE_256x128; break;
+    case 2: case 5: case 6: case 7: case 8: case 10: case 11: case 12: case 13: case 14: case 15: case 23: case 24: if (r.wrap) v = MLSD_TILE_128x128; break;
 #endif
     default: break;
     }
@@ -1637,6 +1715,9 @@ MLSD_API int mlsd_gemm(const mlsd_gemm_args* a, void* stream)
         if (a->K != a->KH * a->KW * a->Cin) return mlsd_set_error(-1, "mlsd_gemm: conv K mismatch");
         if (a->Cin & 7) return mlsd_set_error(-1, "mlsd_gemm: conv Cin must be a multiple of 8");
         if (a->M != a->n_img * a->OH * a->OW) return mlsd_set_error(-1, "mlsd_gemm: conv M mismatch");
+        if (a->wrap & ~3) return mlsd_set_error(-1, "mlsd_gemm: wrap %d is not a mode (bit 0: columns, bit 1: rows)", a->wrap);
+        if (!wrap_foldable(a, conv_wrap(a)))
+            return mlsd_set_error(-1, "mlsd_gemm: wrap: a tap lies more than one image extent outside the %dx%d source (pad %d)", a->H, a->W, a->pad);
     }
     if (a->act == MLSD_ACT_GEGLU && (a->N & 63)) return mlsd_set_error(-1, "mlsd_gemm: GEGLU needs N %% 64 == 0");
     if (!a->C32 && !a->C16 && !a->xa_k) return mlsd_set_error(-1, "mlsd_gemm: no output");

@@ -199,8 +199,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
     // CONV == 2 (round 5): the source is read through a nearest-2x upsample (ggml_upscale + conv, src/mlblock_nn.c:122; stride 1): tap (kh, kw) of output pixel (oh, ow) is
     // source pixel ((oh - pad + kh) >> 1, (ow - pad + kw) >> 1), so the tap offset depends on the parity of the row's pixel: the row keeps its image base and its
     // (oh - pad, ow - pad) pair, and the source address is formed per row and K tile (a handful of VALU operations per LDS-DMA instruction) instead of once per tile.
-    constexpr bool UPS = CONV == 2;
-    struct SeqA { int kt, par; const _Float16* ptr[NU1]; int mask[CONV ? NU1 : 1]; int pos[UPS ? NU1 : 1]; int kh, kw, cin; };
+    // CONV & 4 (WRAP): circular padding (GemmP::wrap; with or without the upsample): the row keeps its image base and (oh - pad, ow - pad) as the upsampling form does,
+    // its mask admits every tap along a wrapped axis, and the tap's coordinates are folded into the image per row and K tile (taps of an axis that does not wrap are in
+    // the image whenever their mask bit is set: the fold leaves them alone).
+    constexpr bool UPS = (CONV & 3) == 2, WRAP = (CONV & 4) != 0, POS = UPS || WRAP;
+    struct SeqA { int kt, par; const _Float16* ptr[NU1]; int mask[CONV ? NU1 : 1]; int pos[POS ? NU1 : 1]; int kh, kw, cin; };
     struct SeqB2 { int kt, par; const _Float16* ptr[NU2]; };
     struct SeqB3 { int kt, par; const _Float16* ptr[NU3]; };
     SeqA sa[2];    // [0] = U1, [1] = U4
@@ -232,11 +235,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
                 const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
                 const int He = UPS ? 2 * p.H : p.H, We = UPS ? 2 * p.W : p.W;
                 int mk = 0;
+                if constexpr (WRAP) {
+                    const bool wy = p.wrap & 2, wx = p.wrap & 1;
+                    for (int kh = 0; kh < p.KH; ++kh)
+                        for (int kw = 0; kw < p.KW; ++kw)
+                            if ((wy || (unsigned)(ih0 + kh) < (unsigned)He) && (wx || (unsigned)(iw0 + kw) < (unsigned)We)) mk |= 1 << (kh * p.KW + kw);
+                } else
                 for (int kh = 0; kh < p.KH; ++kh)
                     for (int kw = 0; kw < p.KW; ++kw)
                         if ((unsigned)(ih0 + kh) < (unsigned)He && (unsigned)(iw0 + kw) < (unsigned)We) mk |= 1 << (kh * p.KW + kw);
                 s.mask[it] = mk;
-                if constexpr (UPS) {
+                if constexpr (POS) {
                     s.pos[it] = ((ih0 + 16) << 16) | (iw0 + 16);                  // (pad <= 16: both halves stay non-negative)
                     s.ptr[it] = p.A + (long)img * p.H * p.W * p.lda + chunk_of(r);
                 } else
@@ -270,6 +279,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
         for (int it = 0; it < NU1; ++it) {
             unsigned char* dst = stage + a_row0(it, second) * RB;                  // wave-uniform: 8 rows, lane-linear
             const _Float16* src = s.ptr[it];
+            if constexpr (WRAP) {
+                const int He = UPS ? 2 * p.H : p.H, We = UPS ? 2 * p.W : p.W;
+                int ih = wrap_fold((s.pos[it] >> 16) - 16 + s.kh, He), iw = wrap_fold((s.pos[it] & 0xffff) - 16 + s.kw, We);
+                if constexpr (UPS) { ih >>= 1; iw >>= 1; }
+                src = (s.mask[it] & tbit) ? s.ptr[it] + ((long)ih * p.W + iw) * p.lda + s.cin : zsrc;
+            } else
             if constexpr (UPS) {
                 const int ih = (s.pos[it] >> 16) - 16 + s.kh, iw = (s.pos[it] & 0xffff) - 16 + s.kw;
                 src = (s.mask[it] & tbit) ? s.ptr[it] + ((long)(ih >> 1) * p.W + (iw >> 1)) * p.lda + s.cin : zsrc;

@@ -43,7 +43,8 @@ __device__ __forceinline__ void skinny_groups(int nkt, F&& f)
     }
 }
 
-template <bool CONV, int RG, int PF, int DBG = 0>      // DBG (timing-only builds: wrong results): 1 = no activation staging / LDS reads / MFMAs (the weight stream alone)
+template <bool CONV, int RG, int PF, int DBG = 0, bool WRAP = false>      // DBG (timing-only builds: wrong results): 1 = no activation staging / LDS reads / MFMAs (the weight stream alone)
+// WRAP: circular padding (GemmP::wrap): a row keeps its image base and (oh - pad, ow - pad), and the tap's coordinates are folded into the image per K step
 // RG: 16-row groups of the tile (8: M <= 128, 4: M <= 64, 1: M <= 16); PF: K steps in flight per thread beyond the one consumed
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmP p)
 {
@@ -74,12 +75,14 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmP p)
     const _Float16* zsrc = reinterpret_cast<const _Float16*>(g_zero_page);
     const _Float16* arow[A_IT];
     int amask[A_IT];
+    int apos[WRAP ? A_IT : 1];
     int a_kh = 0, a_kw = 0, a_cin = 0;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
         const int r = sr + i * 32;
         const int ch = ((tid & 7) ^ ((r >> 1) & 7)) * 8;
         arow[i] = zsrc; amask[i] = 0;
+        if constexpr (WRAP) apos[i] = 0;
         if (r < BM && r < p.M) {
             if constexpr (CONV) {
                 const int ohw = p.OH * p.OW;
@@ -87,11 +90,20 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmP p)
                 const int oh = rem / p.OW, ow = rem - oh * p.OW;
                 const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
                 int mk = 0;
+                if constexpr (WRAP) {       // (a tap along a wrapped axis is always in)
+                    const bool wy = p.wrap & 2, wx = p.wrap & 1;
+                    for (int kh = 0; kh < p.KH; ++kh)
+                        for (int kw = 0; kw < p.KW; ++kw)
+                            if ((wy || (unsigned)(ih0 + kh) < (unsigned)p.H) && (wx || (unsigned)(iw0 + kw) < (unsigned)p.W)) mk |= 1 << (kh * p.KW + kw);
+                    apos[i] = ((ih0 + 16) << 16) | (iw0 + 16);              // (pad <= 16: both halves stay non-negative)
+                    arow[i] = p.A + (long)img * p.H * p.W * p.lda + ch;
+                } else {
                 for (int kh = 0; kh < p.KH; ++kh)
                     for (int kw = 0; kw < p.KW; ++kw)
                         if ((unsigned)(ih0 + kh) < (unsigned)p.H && (unsigned)(iw0 + kw) < (unsigned)p.W) mk |= 1 << (kh * p.KW + kw);
-                amask[i] = mk;
                 arow[i] = p.A + ((long)img * p.H * p.W + (long)ih0 * p.W + iw0) * p.lda + ch;
+                }
+                amask[i] = mk;
             } else {
                 amask[i] = 1;
                 arow[i] = p.A + (long)r * p.lda + ch + (long)kt0 * BK;
@@ -116,7 +128,12 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmP p)
         const int tbit = (CONV ? 1 << (a_kh * p.KW + a_kw) : 1) & (real ? -1 : 0);
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
-            const _Float16* src = (amask[i] & tbit) ? arow[i] + toff : zsrc;
+            const _Float16* src;
+            if constexpr (WRAP) {
+                const int ih = wrap_fold((apos[i] >> 16) - 16 + a_kh, p.H), iw = wrap_fold((apos[i] & 0xffff) - 16 + a_kw, p.W);
+                src = (amask[i] & tbit) ? arow[i] + ((long)ih * p.W + iw) * p.lda + a_cin : zsrc;
+            } else
+            src = (amask[i] & tbit) ? arow[i] + toff : zsrc;
             unsigned char* dst = As + (wave * 8 + i * 32) * RB;                  // wave-uniform: 8 rows, lane-linear
             if constexpr (DBG & 1) src = zsrc;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,

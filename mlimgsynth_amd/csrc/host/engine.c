@@ -39,6 +39,7 @@ struct MLIS_AmdCtx {
 	VaeParams vae_p;
 	int lw, lh, hw, B, N;
 	MLCtx *unet_ctx, *dec_ctx, *enc_ctx;
+	int tiling;                 /* seamless tiling: mlctx_set_conv_wrap mode of the UNet, decoder and encoder plans (0 none, 1 x, 2 y, 3 xy) */
 	UnetState unet;
 	MLTensor *t_lat_dec, *t_img_enc;
 	/* device state */
@@ -130,10 +131,16 @@ static int solver_nfe(int method)
 	return (method == SOLVER_METHOD_HEUN || method == SOLVER_METHOD_DPMPP2S) ? 2 : 1;
 }
 
-MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream)
+MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream) { return mlis_amd_create_ex(cfg, 0, stream); }
+
+MLB_API int mlis_amd_tiling(const MLIS_AmdCtx* S) { return S ? S->tiling : 0; }
+
+MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream)
 {
+	if (tiling < 0 || tiling > 3) { mlsd_set_error(-1, "tiling mode %d: 0 none, 1 x, 2 y, 3 xy", tiling); return NULL; }
 	MLIS_AmdCtx *S = (MLIS_AmdCtx*)calloc(1, sizeof(*S));
 	if (!S) { fail("out of memory"); return NULL; }
+	S->tiling = tiling;
 	S->c = *cfg; S->stream = stream;
 	if (!stream) {   /* own non-default stream: stream capture (hipGraph) is not permitted on the NULL stream */
 		if (mlsd_stream_create(&S->stream)) { free(S); return NULL; }
@@ -176,6 +183,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream)
 
 	/* ---- UNet plan, x bound to the resident evaluation point (c_in scaling + cond/uncond duplication in the gather) */
 	S->unet_ctx = mlctx_new(stream);
+	mlctx_set_conv_wrap(S->unet_ctx, S->tiling);
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
@@ -186,6 +194,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream)
 
 	/* ---- decoder plan, latent input bound to the same resident latent */
 	S->dec_ctx = mlctx_new(stream);
+	mlctx_set_conv_wrap(S->dec_ctx, S->tiling);
 	if (S->c.use_tae) {
 		if (sdtae_decode_init(S->dec_ctx, S->lw, S->lh, B, &S->t_lat_dec) < 0) goto err;
 		if (mlctx_input_bind(S->t_lat_dec, S->d_x, B, NULL, 1.0f, 1) < 0) goto err;
@@ -834,6 +843,7 @@ MLB_API MLCtx* mlis_amd_encoder_prepare(MLIS_AmdCtx* S)
 	void *st = S->stream;
 	if (!S->d_img_in && mlsd_malloc((void**)&S->d_img_in, (size_t)B*3*W*H*4)) return NULL;
 	MLCtx *C = mlctx_new(st);
+	mlctx_set_conv_wrap(C, S->tiling);
 	int ok = 0;
 	if (S->c.use_tae) {
 		ok = sdtae_encode_init(C, W, H, B, &S->t_img_enc) >= 0 && mlctx_input_bind(S->t_img_enc, S->d_img_in, B, NULL, 1.0f, 0) >= 0 &&

@@ -110,6 +110,7 @@ MLB_API void mlctx_end(MLCtx* C) { mlsd_stream_sync(C->stream); ctx_reset(C); }
 MLB_API void mlctx_set_tprefix(MLCtx* C, const char* p) { snprintf(C->tprefix, sizeof(C->tprefix), "%s", p ? p : ""); }
 MLB_API void mlctx_set_flags(MLCtx* C, int f) { C->flags = f; }
 MLB_API void mlctx_set_wtype(MLCtx* C, int t) { C->wtype = t; }
+MLB_API void mlctx_set_conv_wrap(MLCtx* C, int mode) { C->conv_wrap = mode & 3; }
 MLB_API MLTensor* mlctx_result(MLCtx* C) { return C->result; }
 MLB_API int mlctx_sync(MLCtx* C) { return mlsd_stream_sync(C->stream) ? -1 : 1; }
 
@@ -1635,6 +1636,13 @@ MLB_API void mlctx_info(const MLCtx* C, MLCtxInfo* out)
 {
 	*out = C->info;
 	out->mem_params = C->mem_params; out->mem_compute = C->mem_compute; out->mem_total = C->mem_params + C->mem_compute;
+}
+
+/* the launch arguments of op i if it is a GEMM / convolution (diagnostics and plan censuses: what the launcher will be asked), else NULL */
+MLB_API const mlsd_gemm_args* mlctx_op_gemm_args(const MLCtx* C, int i)
+{
+	if (!C || i < 0 || i >= C->n_ops || C->ops[i].kind != OP_GEMM) return NULL;
+	return &C->ops[i].u.gemm;
 }
 
 MLB_API int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flops)

@@ -82,6 +82,7 @@ struct MLCtx {
 	char name[64];
 	char tprefix[32];
 	int flags, wtype;
+	int conv_wrap;          /* mlctx_set_conv_wrap: mlsd_gemm_args.wrap of the convolutions built from now on */
 	int err;
 	/* plan */
 	MLOp* ops; int n_ops, cap_ops;

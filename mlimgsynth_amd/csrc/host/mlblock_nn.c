@@ -70,7 +70,8 @@ MLTensor* mlb_conv2d_ex(MLCtx* C, MLTensor* x, int ch_out, int k, int s, int p, 
 }
 
 /* p = zero padding before the first row/column, p_end = after the last (ggml_pad(x,1,1,0,0) + conv p=0 of the VAE
- * encoder's downsample, src/mlblock_nn.c:109-111, is p = 0, p_end = 1: the gather's bounds check supplies the zeros) */
+ * encoder's downsample, src/mlblock_nn.c:109-111, is p = 0, p_end = 1: the gather's bounds check supplies the zeros).
+ * With mlctx_set_conv_wrap the padding on both sides is circular instead (the kernels fold the tap into the image). */
 MLTensor* mlb_conv2d_ex2(MLCtx* C, MLTensor* x, int ch_out, int k, int s, int p, int p_end, int upsample, bool bias, const MLEpilogue* ep)
 {
 	if (!x || C->err) return NULL;
@@ -99,7 +100,7 @@ MLTensor* mlb_conv2d_ex2(MLCtx* C, MLTensor* x, int ch_out, int k, int s, int p,
 	MLOp *op = mlctx_op_new(C, OP_GEMM, "");
 	mlsd_gemm_args *g = &op->u.gemm;
 	g->A = xd; g->lda = x->ld16; g->conv = 1; g->n_img = x->n; g->H = H; g->W = W; g->Cin = cpad; g->OH = OH; g->OW = OW;
-	g->KH = k; g->KW = k; g->stride = s; g->pad = p; g->upsample = upsample;
+	g->KH = k; g->KW = k; g->stride = s; g->pad = p; g->upsample = upsample; g->wrap = C->conv_wrap;
 	g->W_ = wd; g->ldb = (int64_t)k*k*cpad; g->M = x->n*OH*OW; g->N = ch_out; g->K = k*k*cpad;
 	g->bias = bd; g->rowbias = rb; g->rows_per_batch = OH*OW; g->ldrb = (ep && ep->rowbias) ? ep->rowbias->ld32 : ch_out; g->resid = rd; g->ldr = ldr;
 	g->act = ep ? ep->act : MLSD_ACT_NONE;

@@ -38,6 +38,7 @@ struct MLIS_Ctx {
 	MLISPrompt prompt, nprompt;
 	int32_t *ptok[2]; float *ptokw[2]; int n_ptok[2], have_ptok[2];     /* mlis_amd_prompt_tokens_set */
 	int model_type, width, height, n_batch, clip_skip, vae_tile, n_thread, dump_flags, flags, tuflags, wtype;
+	int tiling;             /* MLIS_OPT_AMD_TILING: 0 none, 1 x, 2 y, 3 xy */
 	float cfg_scale;
 	int method, sched, n_step;
 	float f_t_ini, f_t_end, s_noise, s_ancestral;
@@ -118,8 +119,17 @@ MLB_API const char* mlis_sched_str(MLIS_Scheduler x) { return (x >= 0 && x < COU
 MLB_API MLIS_Scheduler mlis_sched_fromz(const char* s) { return (MLIS_Scheduler)from_list(k_sched, COUNTOF(k_sched), 1, s, strlen(s)); }
 MLB_API const char* mlis_loglvl_str(MLIS_LogLvl id) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (k_loglvl[i].id == (int)id) return k_loglvl[i].n; return "???"; }
 MLB_API MLIS_LogLvl mlis_loglvl_fromz(const char* s) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (id_eq(s, strlen(s), k_loglvl[i].n)) return (MLIS_LogLvl)k_loglvl[i].id; return (MLIS_LogLvl)-1; }
-MLB_API const char* mlis_option_str(MLIS_Option x) { return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???"; }
-MLB_API MLIS_Option mlis_option_fromz(const char* s) { return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s)); }
+static const char* const k_tiling[] = { "none", "x", "y", "xy" };
+MLB_API const char* mlis_option_str(MLIS_Option x)
+{
+	if (x == MLIS_OPT_AMD_TILING) return "tiling";
+	return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???";
+}
+MLB_API MLIS_Option mlis_option_fromz(const char* s)
+{
+	if (id_eq(s, strlen(s), "tiling")) return MLIS_OPT_AMD_TILING;
+	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
+}
 
 static const char* model_name(int mt)
 {
@@ -442,6 +452,18 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		} else S->seed = va_arg(*A->ap, uint64_t);
 		break;
 	case MLIS_OPT_VAE_TILE: if (!arg_int(A, 0, 65535, 0, &i)) BAD_VALUE; S->vae_tile = i; break;
+	case MLIS_OPT_AMD_TILING:      /* none|x|y|xy or 0..3; a changed mode rebuilds the engine (engine_get key) */
+		if (A->is_str) {
+			next_str_arg(A);
+			i = from_list(k_tiling, COUNTOF(k_tiling), 1, A->arg_b, A->arg_n);
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i > 3) BAD_VALUE;
+		S->tiling = i;
+		break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (A->is_str) {
@@ -499,6 +521,7 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	switch ((int)id) {
 	case MLIS_OPT_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_model ? S->path_model : ""; } break;
 	case MLIS_OPT_MODEL_TYPE: { int *p = va_arg(ap, int*); if (p) *p = S->model_type; } break;
+	case MLIS_OPT_AMD_TILING: { int *p = va_arg(ap, int*); if (p) *p = S->tiling; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -647,7 +670,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
 	const int ctx_tok = S->ctx_tok > 0 ? S->ctx_tok : 77;
 	char key[96];
-	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok);
+	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	if (!S->eng || strcmp(key, S->eng_key)) {
@@ -658,7 +681,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		S->eng = mlis_amd_create(&c, NULL);
+		S->eng = mlis_amd_create_ex(&c, S->tiling, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
 		if (ctx_weights(S, mlis_amd_unet_ctx(S->eng), 0) < 0 || ctx_weights(S, mlis_amd_decoder_ctx(S->eng), tae) < 0) { engine_drop(S); return -1; }
@@ -842,6 +865,14 @@ MLB_API int mlis_mask_encode(MLIS_Ctx* S, const MLIS_Tensor* mask, MLIS_Tensor* 
 	return 1;
 }
 
+/* seamless tiling needs the whole image in one plan: the tiles of VAE_TILE cannot see the opposite edge (TAESD is never tiled) */
+static int tiling_check(MLIS_Ctx* S)
+{
+	if (S->tiling && S->vae_tile > 0 && !(S->flags & CF_USE_TAE))
+		return api_error(S, MLIS_E_OPT_VALUE, "tiling '%s' cannot be combined with vae_tile %d (tiled VAE decoding / encoding does not wrap)", k_tiling[S->tiling], S->vae_tile);
+	return 1;
+}
+
 static int engine_for_image(MLIS_Ctx* S, int w, int h)
 {
 	if (w % 8 || h % 8 || w < 8 || h < 8) return api_error(S, MLIS_E_IMAGE, "invalid input image shape: %dx%d", w, h);
@@ -855,6 +886,7 @@ MLB_API int mlis_image_encode(MLIS_Ctx* S, const MLIS_Tensor* image, MLIS_Tensor
 	int r = mlis_setup(S); if (r < 0) return r;
 	if (image->n[2] != 3 || image->n[3] != 1) return api_error(S, MLIS_E_IMAGE, "invalid input image shape: %dx%dx%dx%d", image->n[0], image->n[1], image->n[2], image->n[3]);
 	const int w = image->n[0], h = image->n[1];
+	if ((r = tiling_check(S)) < 0) return r;
 	if (engine_for_image(S, w, h) < 0) return -1;
 	MLCtx *ec = mlis_amd_encoder_tile_prepare(S->eng);          /* VAE_TILE: the tile-sized encoder, when tiling applies */
 	if (!ec) ec = mlis_amd_encoder_ctx(S->eng);
@@ -895,6 +927,7 @@ MLB_API int mlis_image_decode(MLIS_Ctx* S, const MLIS_Tensor* latent, MLIS_Tenso
 	int r = mlis_setup(S); if (r < 0) return r;
 	if (latent->n[2] != 4) return api_error(S, MLIS_E_UNKNOWN, "latent must have 4 channels");
 	const int lw = latent->n[0], lh = latent->n[1], B = S->n_batch > 0 ? S->n_batch : 1;
+	if ((r = tiling_check(S)) < 0) return r;
 	if (engine_get(S, lw, lh) < 0) return -1;
 	const size_t per = (size_t)4*lw*lh;
 	float *l = (float*)malloc(per * B * 4);
@@ -940,6 +973,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h)
 		ADD(", Model: %.*s", (int)(e - b), b);
 	}
 	if (S->flags & CF_USE_TAE) ADD(", VAE: tae");
+	if (S->tiling) ADD(", Tiling: %s", k_tiling[S->tiling]);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -951,6 +985,7 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	int r = mlis_setup(S); if (r < 0) return r;
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
+	if ((r = tiling_check(S)) < 0) return r;
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	const double t_start = S->t_last; (void)t_start;
 	int w = S->width / 8, h = S->height / 8;

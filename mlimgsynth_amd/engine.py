@@ -92,6 +92,14 @@ def fptr(a):
     return a.ctypes.data_as(FP) if a is not None else None
 
 
+def set_conv_wrap(ctx, mode):
+    """mlctx_set_conv_wrap: circular padding (0 none, 1 x, 2 y, 3 xy) of the convolutions the context builds from now on."""
+    f = L().mlctx_set_conv_wrap
+    f.argtypes = [vp, c_int]
+    f.restype = None
+    f(ctx.h if isinstance(ctx, MLCtx) else vp(ctx), int(mode))
+
+
 class MLCtx:
     """Owns one MLCtx (one model graph + its device-resident parameters)."""
 
@@ -194,9 +202,11 @@ def unet_params(model):
 class Unet:
     """unet_denoise_init_n / unet_denoise_run_n (src/unet.c:336-498) with a batch dimension."""
 
-    def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0, n_ctx_tok=77):
+    def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0, n_ctx_tok=77, tiling=0):
         self.P = unet_params(model)
         self.ctx = MLCtx(stream, flags)
+        if tiling:                      # seamless tiling: 1 x, 2 y, 3 xy (circular padding of every convolution built below)
+            set_conv_wrap(self.ctx, tiling)
         if stream_weights_mib:          # the reference's --unet-split: weights in pinned host memory, three device slabs of this size
             f = L().mlctx_set_weight_streaming
             f.argtypes = [vp, ctypes.c_size_t]
@@ -243,6 +253,10 @@ def _proto2():
     l.dnsamp_ancestral.argtypes = [c_f, c_f, c_f, FP, FP]
     l.mlis_amd_create.restype = vp
     l.mlis_amd_create.argtypes = [ctypes.POINTER(AmdConfig), vp]
+    l.mlis_amd_create_ex.restype = vp
+    l.mlis_amd_create_ex.argtypes = [ctypes.POINTER(AmdConfig), c_int, vp]
+    l.mlis_amd_tiling.restype = c_int
+    l.mlis_amd_tiling.argtypes = [vp]
     l.mlis_amd_destroy.argtypes = [vp]
     l.mlis_amd_set_cond.argtypes = [vp, FP, FP, FP, FP]
     l.mlis_amd_set_cond_device.argtypes = [vp, vp, vp, vp, vp]
@@ -299,9 +313,11 @@ def schedule(model, n_step, sched=1, f_t_ini=1.0, f_t_end=0.0):
 class Decoder:
     """sdvae_decode / sdtae_decode (src/vae.c:318-411, src/tae.c:117-136), batched, no tiling."""
 
-    def __init__(self, model, lw, lh, n_batch, tae=False, stream=None, seed=1234, flags=0):
+    def __init__(self, model, lw, lh, n_batch, tae=False, stream=None, seed=1234, flags=0, tiling=0):
         l = _proto2()
         self.ctx = MLCtx(stream, flags)
+        if tiling:
+            set_conv_wrap(self.ctx, tiling)
         self.tae, self.lw, self.lh, self.n = tae, lw, lh, n_batch
         self.t_lat = vp()
         if tae:
@@ -346,12 +362,12 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0, n_ctx_tok=77):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77, tiling=0):
         l = _proto2()
         self.cfg = AmdConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
                              int(defer_weights), int(unet_split), int(n_ctx_tok))    # n_ctx_tok: context rows, 77 x W (windowed prompt)
-        self.h = l.mlis_amd_create(ctypes.byref(self.cfg), vp(stream))
+        self.h = l.mlis_amd_create_ex(ctypes.byref(self.cfg), int(tiling), vp(stream))    # tiling: 0 none, 1 x, 2 y, 3 xy (seamless)
         if not self.h:
             from ._lib import MlsdError, last_error
             raise MlsdError("mlis_amd_create failed: " + last_error())

@@ -41,7 +41,7 @@ _define("MLIS_MODEL_", ["NONE", "UNET", "VAE", "TAE", "CLIP", "CLIP2"])
 _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LORA_CLEAR", "PROMPT", "NPROMPT", "IMAGE_DIM", "BATCH_SIZE",
                       "CLIP_SKIP", "CFG_SCALE", "METHOD", "SCHEDULER", "STEPS", "F_T_INI", "F_T_END", "S_NOISE", "S_ANCESTRAL", "IMAGE",
                       "IMAGE_MASK", "NO_DECODE", "TENSOR_USE_FLAGS", "SEED", "VAE_TILE", "UNET_SPLIT", "THREADS", "DUMP_FLAGS", "AUX_DIR",
-                      "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35))
+                      "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101))
 MLIS_CTEF_NO_NORM = 1
 
 

@@ -1,15 +1,22 @@
 """Per-kernel breakdown of one latent decode (KL-VAE or TAESD) plan (diagnostics, not the bench).
-usage: python3 tools/quick_decode_perf.py <model> <latent_side> <n_batch> [tae] [flags]"""
+usage: python3 tools/quick_decode_perf.py <model> <latent_side> <n_batch> [tae] [flags] [--tiling none|x|y|xy]"""
 import os, sys, ctypes, collections
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mlimgsynth_amd import engine, _lib
 
+TILING = {"none": 0, "x": 1, "y": 2, "xy": 3}
+tiling = 0
+if "--tiling" in sys.argv:          # --tiling none|x|y|xy: the plan's convolutions pad circularly (seamless tiling)
+    i = sys.argv.index("--tiling")
+    tiling = TILING[sys.argv[i + 1]]
+    del sys.argv[i:i + 2]
 model, lat, n = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 tae = len(sys.argv) > 4 and sys.argv[4] == "tae"
 flags = int(sys.argv[5]) if len(sys.argv) > 5 else 16
 L = _lib.lib()
-dec = engine.Decoder(model, lat, lat, n, tae=tae)
+dec = engine.Decoder(model, lat, lat, n, tae=tae, tiling=tiling)
+print(f"tiling {tiling}")
 _lib.lib().mlctx_set_flags(dec.ctx.h, flags)
 info = dec.ctx.info()
 print(f"ops={info.n_ops} flops={info.flops/1e12:.3f} TFLOP params={info.mem_params/2**20:.1f} MiB act={info.mem_compute/2**30:.2f} GiB")

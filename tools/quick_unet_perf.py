@@ -4,12 +4,19 @@ import numpy as np
 sys.path.insert(0, ".")
 from mlimgsynth_amd import engine, _lib
 
+TILING = {"none": 0, "x": 1, "y": 2, "xy": 3}
+tiling = 0
+if "--tiling" in sys.argv:          # --tiling none|x|y|xy: the plan's convolutions pad circularly (seamless tiling)
+    i = sys.argv.index("--tiling")
+    tiling = TILING[sys.argv[i + 1]]
+    del sys.argv[i:i + 2]
 model, lat, n = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 flags = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 import os
 _lib.lib().mlsd_gemm_set_panel(int(os.environ.get('GEMM_MODE', '8')))
 t0 = time.time()
-un = engine.Unet(model, lat, lat, n, flags=flags)
+un = engine.Unet(model, lat, lat, n, flags=flags, tiling=tiling)
+print(f"tiling {tiling}")
 info = un.ctx.info()
 print(f"build+synth {time.time()-t0:.1f}s ops={info.n_ops} flops/eval={info.flops/1e12:.3f} TFLOP params={info.mem_params/2**30:.2f} GiB act={info.mem_compute/2**30:.2f} GiB")
 L = _lib.lib()

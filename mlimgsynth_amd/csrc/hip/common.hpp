@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "mlsd_kernels.h"
 
 #define MLSD_API __attribute__((visibility("default")))
 
@@ -49,6 +50,21 @@ __device__ __forceinline__ float gelu_tanh_f(float x)
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 __device__ __forceinline__ float gelu_quick_f(float x) { return x * fast_sigmoid(1.702f * x); }
+// The one activation switch (mlsd_kernels.h MLSD_ACT_*; GEGLU is a gating of two columns, not a function of one value: its epilogues are written where they run),
+// on x, y, z, w in that order: ONE switch around the four applications, so that a kernel branches once per 4 columns.  The scalar form is its first lane (the
+// other three fold away).
+__device__ __forceinline__ float4 act_apply(int act, float4 v)
+{
+    switch (act) {
+    case MLSD_ACT_SILU: v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); break;
+    case MLSD_ACT_GELU: v.x = gelu_tanh_f(v.x); v.y = gelu_tanh_f(v.y); v.z = gelu_tanh_f(v.z); v.w = gelu_tanh_f(v.w); break;
+    case MLSD_ACT_GELU_QUICK: v.x = gelu_quick_f(v.x); v.y = gelu_quick_f(v.y); v.z = gelu_quick_f(v.z); v.w = gelu_quick_f(v.w); break;
+    case MLSD_ACT_RELU: v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); break;
+    default: break;
+    }
+    return v;
+}
+__device__ __forceinline__ float act_apply(int act, float v) { return act_apply(act, make_float4(v, 0.f, 0.f, 0.f)).x; }
 
 __device__ __forceinline__ float wave_sum(float v)
 {

@@ -58,15 +58,7 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ t, int n, in
 __global__ void act_f32_to_f16_kernel(const float* __restrict__ x, _Float16* __restrict__ y, size_t n, int act)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float v = x[i];
-        switch (act) {
-        case MLSD_ACT_SILU: v = silu_f(v); break;
-        case MLSD_ACT_GELU: v = gelu_tanh_f(v); break;
-        case MLSD_ACT_GELU_QUICK: v = gelu_quick_f(v); break;
-        case MLSD_ACT_RELU: v = fmaxf(v, 0.f); break;
-        default: break;
-        }
-        y[i] = (_Float16)v;
+        y[i] = (_Float16)act_apply(act, x[i]);
     }
 }
 

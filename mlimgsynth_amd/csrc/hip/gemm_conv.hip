@@ -39,94 +39,18 @@
 #include <type_traits>
 #include "common.hpp"
 #include "mlsd_kernels.h"
+#include "gemm_params.hpp"
+#include "gemm_epilogue.hpp"
+#include "gemm_pp.hpp"
+#include "gemm_skinny.hpp"
 
 namespace {
-
-struct GemmP {
-    const _Float16* A;
-    const _Float16* B;
-    long lda, ldb;
-    int M, N, K;
-    // conv geometry
-    int H, W, Cin, OH, OW, KH, KW, stride, pad, ups;
-    int korder;   // conv, Cin % 64 == 0: 0 = K runs (kh, kw, cin), 1 = (cin / 64, kh, kw, cin % 64): the KH KW taps of a 64-channel slab are consecutive K tiles (mlsd_gemm_args.conv_korder)
-    // epilogue
-    const float* bias;
-    const float* biasm;
-    int act_post;
-    int wrap;     // conv: mlsd_gemm_args.wrap of the kernels built with the wrap (in act_post's padding: no other field moves)
-    const float* rowbias;
-    int rows_per_batch;
-    long ldrb;
-    const float* resid;
-    long ldr;
-    int act;
-    float* C32;
-    long ldc32;
-    _Float16* C16;
-    long ldc16;
-    int nbm, nbn;
-    int vec;   // 1: every row stride and N are multiples of 4 -> wide (LDS-transposed) epilogue
-    int dbg;   // diagnostics (timing-only builds of the loop): bit0 = no refills in the loop, bit1 = no MFMA/ds_read
-    // split-K: blockIdx.y = slice z owns K tiles [z*kt_per, (z+1)*kt_per) and writes its raw fp32 partial sums to
-    // C32 + z*ws_stride (the epilogue fields are cleared by the launcher; splitk_reduce applies them)
-    int kt_per;
-    long ws_stride;
-    int gw;    // tile-order panel width (0: row-major)
-    unsigned long long* tbuf;   // diagnostics: per-block cycle stamps of the ping-pong kernels (tools/gemm_trace.py), or null
-    float* colstats;            // ping-pong kernels built with a *_STATS epilogue: [row block][2][N] column sums / sums of squares
-    int cs_shift;               // 1: of (x - K), K = the column's value in the block's first row (mlsd_gemm_args.colstats_shift); 0: of x
-    // stream-K (gemm_pp.hpp, SK): K-tile units per block, slabs [block][BM*BN] fp32, one flag per block
-    int sk_L;
-    float* sk_ws;
-    unsigned* sk_flag;
-    // LayerNorm at the end of the launch (gemm_pp.hpp *_LN epilogues): gamma, beta, eps, fp16 output, per-(row block, tile column, row) partials, counters
-    const float *ln_g, *ln_b;
-    float ln_eps;
-    _Float16* ln_y;
-    long ldln;
-    float* ln_ws;
-    unsigned* ln_cnt;
-    int ln_slot;                // index of this launch's epoch word in ln_cnt (round 6: self-tagged records, no counters)
-    int gn_G, gn_hw, gn_silu;   // splitk_reduce_gn: groups, rows per image, SiLU (gamma / beta / eps / output in the ln_* fields)
-    // cross attention at the end of its q projection (gemm_pp.hpp PP_EPI_XATTN): K [n_img * Tk][ldk], V^T [n_img][N][96], output, rows per image, keys, log2(e) / sqrt(64)
-    const _Float16 *xa_k, *xa_vt;
-    _Float16* xa_out;
-    long xa_ldk, xa_ldo;
-    int xa_Tq, xa_Tk;
-    float xa_sc;
-};
-
-static_assert(offsetof(GemmP, wrap) + sizeof(int) == offsetof(GemmP, rowbias), "GemmP::wrap must fill act_post's padding");
-
-// wrap (circular padding): a coordinate at most one extent outside [0, e) folded into it
-__device__ __forceinline__ int wrap_fold(int v, int e) { return v < 0 ? v + e : (v >= e ? v - e : v); }
-
-// LDS tile: rows of BK halfs (128 B at BK=64, 64 B at BK=32); the 16-byte chunk c of row r lives at slot
-// c ^ swz(r) so that a ds_read_b128 fragment read (32 lanes = 32 consecutive rows, one logical chunk)
-// touches every bank once (64 banks x 4 B; 16-lane service groups).
-template <int BK>
-__device__ __forceinline__ int row_swz(int row) { return BK == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
-template <int BK>
-__device__ __forceinline__ int lds_off(int row, int chunk) { return row * (BK * 2) + ((chunk ^ row_swz<BK>(row)) << 4); }
-
-// 16 zero bytes in global memory: the source of every padded / out-of-range 16-byte chunk
-// (global_load_lds has no bounds check and no zero-fill)
-__device__ uint4 g_zero_page[4];
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt immediate range");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // PAR (round 4): a split-K launch that REDUCES ITS SLICES ITSELF, in parallel.  SD1.5 batch 1 is bound by its dispatch count (~4.5 us per dependent dispatch, 498 per
 // evaluation, 96 of them splitk_reduce).  Every block writes its raw partial tile to its slice of the workspace with write-through stores (as the two-launch form does),
 // takes a ticket on the TILE's arrival counter, and one thread waits (bounded) until all K slices of the tile have arrived -- the whole grid is resident: the launcher
 // checks tiles x slices against the occupancy of this kernel.  Then the blocks of the tile SHARE the reduction: block z adds, for its 1/nsl of the tile's 4-column
-// groups, the slices in order 0, 1, ... (agent-scope loads) and applies the epilogue -- the same operations in the same order as splitk_reduce: bit-identical to the
-// two-launch form.  (The round-3 variant let the LAST block reduce the whole tile alone at one CU's load bandwidth and lost to the second launch; profiles/NOTES.md.)
+// groups, the slices in order 0, 1, ... (agent-scope loads) and applies the epilogue (epilogue4, gemm_epilogue.hpp: why this equals the two-launch form to the bit).  (The round-3 variant let the LAST block reduce the whole tile alone at one CU's load bandwidth and lost to the second launch; profiles/NOTES.md.)
 // A departure counter clears both words for the next launch; a give-up raises the sticky word sk_flag[4095] (mlctx_handoff_check -> retry on the two-launch plan).
 // `pe` = the epilogue as requested (p carries the raw-partial form).
 // ST: the build whose wide epilogue also emits column statistics (GemmP::colstats).  A build of its own: the 8 + 8 running sums push the 512- / 1024-thread tiles over
@@ -467,35 +391,15 @@ void gemm_kernel(const GemmP p, const GemmP pe)
         // (fp16) accesses, 16 lanes cover 256 contiguous bytes of a row; 16 store instructions per 32x64 slab
         // instead of 64 scalar ones.
         float* stg = reinterpret_cast<float*>(smem) + wave * (32 * 64);
-        // bias, row bias, residual, activation and both stores for 4 consecutive columns of row m
+        // bias, row bias, residual, activation (epilogue4: the bias preloaded per slab, the residual prefetched in PRE builds) and both stores for 4 consecutive columns of row m
         auto finish4 = [&](int m, int n, float4 v, const float4 bv, const float4 rs_pre, const bool have_pre) -> float4 {
-            v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-            if (p.biasm) { const float b = p.biasm[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
-            if (p.rowbias) {
-                const float4 r = *reinterpret_cast<const float4*>(p.rowbias + (long)(m / p.rows_per_batch) * p.ldrb + n);
-                v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-            }
-            float4 rs = make_float4(0, 0, 0, 0);
-            if (have_pre) rs = rs_pre;
-            else if (p.resid) rs = *reinterpret_cast<const float4*>(p.resid + (long)m * p.ldr + n);
-            if (p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-            switch (p.act) {
-            case MLSD_ACT_SILU: v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); break;
-            case MLSD_ACT_GELU: v.x = gelu_tanh_f(v.x); v.y = gelu_tanh_f(v.y); v.z = gelu_tanh_f(v.z); v.w = gelu_tanh_f(v.w); break;
-            case MLSD_ACT_GELU_QUICK: v.x = gelu_quick_f(v.x); v.y = gelu_quick_f(v.y); v.z = gelu_quick_f(v.z); v.w = gelu_quick_f(v.w); break;
-            case MLSD_ACT_RELU: v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); break;
-            default: break;
-            }
-            if (!p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
+            v = epilogue4(p, m, n, v, true, bv, have_pre, rs_pre);
             if constexpr (PAR) {      // raw partial sums, written through to the agent-coherent level (other XCDs' blocks read them in this launch)
                 const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void*)C32, 0, 0x7fffffff, 0x00020000);
                 const f32x4 w = {v.x, v.y, v.z, v.w};
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), rsw, (int)(((long)m * p.ldc32 + n) * 4), 0, 16);   // aux 16 = sc1
-            } else if (C32) *reinterpret_cast<float4*>(C32 + (long)m * p.ldc32 + n) = v;
-            if (p.C16) {
-                f16x4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-                *reinterpret_cast<f16x4*>(p.C16 + (long)m * p.ldc16 + n) = h;
-            }
+                store4(nullptr, 0, p.C16, p.ldc16, m, n, v);
+            } else store4(C32, p.ldc32, p.C16, p.ldc16, m, n, v);
             return v;
         };
         // column statistics for a consuming GroupNorm (GemmP::colstats, round 4 on these tiles): per 64-column slab, the lane's 4 columns summed over the wave's WM rows
@@ -641,7 +545,7 @@ void gemm_kernel(const GemmP p, const GemmP pe)
                 const int r = it / c4, m = m0 + r, n = n0 + ((it - r * c4) << 2);
                 const int off = (int)(((long)m * p.N + n) * 4);
                 float4 v = make_float4(0, 0, 0, 0);
-                for (int z0 = 0; z0 < nsl; z0 += 4) {                // 4 slices in flight, added in slice order (the order of splitk_reduce)
+                for (int z0 = 0; z0 < nsl; z0 += 4) {                // 4 slices in flight, added in slice order (the order of sum_slices4)
                     f32x4 t[4];
 #pragma unroll
                     for (int b = 0; b < 4; ++b)
@@ -653,29 +557,8 @@ void gemm_kernel(const GemmP p, const GemmP pe)
                             else { v.x += t[b][0]; v.y += t[b][1]; v.z += t[b][2]; v.w += t[b][3]; }
                         }
                 }
-                // the requested epilogue: the operations of splitk_reduce, in its order
-                if (pe.bias) { const float4 b = *reinterpret_cast<const float4*>(pe.bias + n); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-                if (pe.biasm) { const float b = pe.biasm[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
-                if (pe.rowbias) {
-                    const float4 rb = *reinterpret_cast<const float4*>(pe.rowbias + (long)(m / pe.rows_per_batch) * pe.ldrb + n);
-                    v.x += rb.x; v.y += rb.y; v.z += rb.z; v.w += rb.w;
-                }
-                float4 rs = make_float4(0, 0, 0, 0);
-                if (pe.resid) rs = *reinterpret_cast<const float4*>(pe.resid + (long)m * pe.ldr + n);
-                if (pe.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-                switch (pe.act) {
-                case MLSD_ACT_SILU: v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); break;
-                case MLSD_ACT_GELU: v.x = gelu_tanh_f(v.x); v.y = gelu_tanh_f(v.y); v.z = gelu_tanh_f(v.z); v.w = gelu_tanh_f(v.w); break;
-                case MLSD_ACT_GELU_QUICK: v.x = gelu_quick_f(v.x); v.y = gelu_quick_f(v.y); v.z = gelu_quick_f(v.z); v.w = gelu_quick_f(v.w); break;
-                case MLSD_ACT_RELU: v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); break;
-                default: break;
-                }
-                if (!pe.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-                if (pe.C32) *reinterpret_cast<float4*>(pe.C32 + (long)m * pe.ldc32 + n) = v;
-                if (pe.C16) {
-                    f16x4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-                    *reinterpret_cast<f16x4*>(pe.C16 + (long)m * pe.ldc16 + n) = h;
-                }
+                v = epilogue4(pe, m, n, v);      // the requested epilogue
+                store4(pe.C32, pe.ldc32, pe.C16, pe.ldc16, m, n, v);
             }
             // departures: the last block to leave the tile clears both counters for the next launch (nobody can still be polling: every block has passed the wait)
             if (tid == 0) {
@@ -706,13 +589,7 @@ void gemm_kernel(const GemmP p, const GemmP pe)
                     if (p.biasm) v += p.biasm[m];
                     if (rbias) v += rbias[n];
                     if (p.act_post && p.resid) v += p.resid[(long)m * p.ldr + n];
-                    switch (p.act) {
-                    case MLSD_ACT_SILU: v = silu_f(v); break;
-                    case MLSD_ACT_GELU: v = gelu_tanh_f(v); break;
-                    case MLSD_ACT_GELU_QUICK: v = gelu_quick_f(v); break;
-                    case MLSD_ACT_RELU: v = fmaxf(v, 0.f); break;
-                    default: break;
-                    }
+                    v = act_apply(p.act, v);
                     if (!p.act_post && p.resid) v += p.resid[(long)m * p.ldr + n];
                     if (C32) C32[(long)m * p.ldc32 + n] = v;
                     if (p.C16) p.C16[(long)m * p.ldc16 + n] = (_Float16)v;
@@ -737,10 +614,7 @@ void gemm_kernel(const GemmP p, const GemmP pe)
     }
 }
 
-#include "gemm_pp.hpp"
-#include "gemm_skinny.hpp"
-
-// ---- split-K second pass: sum the slices in fixed order (deterministic), then the same epilogue as above.
+// ---- split-K second pass: sum the slices in fixed order (deterministic), then the epilogue (epilogue4, gemm_epilogue.hpp).
 // One thread per 4 consecutive columns; only launched when the wide-epilogue alignment conditions hold.
 __global__ __launch_bounds__(256) void splitk_reduce(const GemmP p, const float* __restrict__ ws, int nsplit)
 {
@@ -748,38 +622,13 @@ __global__ __launch_bounds__(256) void splitk_reduce(const GemmP p, const float*
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)p.M * n4) return;
     const int m = (int)(idx / n4), n = (int)(idx - (long)m * n4) * 4;
-    float4 v = *reinterpret_cast<const float4*>(ws + (long)m * p.N + n);
-    for (int z = 1; z < nsplit; ++z) {
-        const float4 t = *reinterpret_cast<const float4*>(ws + z * p.ws_stride + (long)m * p.N + n);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-    }
-    if (p.bias) { const float4 b = *reinterpret_cast<const float4*>(p.bias + n); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-    if (p.biasm) { const float b = p.biasm[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
-    if (p.rowbias) {
-        const float4 r = *reinterpret_cast<const float4*>(p.rowbias + (long)(m / p.rows_per_batch) * p.ldrb + n);
-        v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-    }
-    float4 rs = make_float4(0, 0, 0, 0);
-    if (p.resid) rs = *reinterpret_cast<const float4*>(p.resid + (long)m * p.ldr + n);
-    if (p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-    switch (p.act) {
-    case MLSD_ACT_SILU: v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); break;
-    case MLSD_ACT_GELU: v.x = gelu_tanh_f(v.x); v.y = gelu_tanh_f(v.y); v.z = gelu_tanh_f(v.z); v.w = gelu_tanh_f(v.w); break;
-    case MLSD_ACT_GELU_QUICK: v.x = gelu_quick_f(v.x); v.y = gelu_quick_f(v.y); v.z = gelu_quick_f(v.z); v.w = gelu_quick_f(v.w); break;
-    case MLSD_ACT_RELU: v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); break;
-    default: break;
-    }
-    if (!p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-    if (p.C32) *reinterpret_cast<float4*>(p.C32 + (long)m * p.ldc32 + n) = v;
-    if (p.C16) {
-        f16x4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        *reinterpret_cast<f16x4*>(p.C16 + (long)m * p.ldc16 + n) = h;
-    }
+    const float4 v = epilogue4(p, m, n, sum_slices4(ws, p.ws_stride, (long)m * p.N + n, nsplit));
+    store4(p.C32, p.ldc32, p.C16, p.ldc16, m, n, v);
 }
 
 // ---- split-K second pass that ALSO emits the column statistics of the rows it finishes (GemmP::colstats: [block of 32 rows][2][N] (shifted) sums / sums of squares, for a
 // consuming GroupNorm: its first pass over the fp32 map disappears).  A block = 32 rows x 256 columns: thread (row lane rl = t / 64, column group t % 64) finishes
-// rows rl, rl + 4, ... with the operations of splitk_reduce in its order (bit-identical output, the slices' loads of the 8 rows in flight together), sums its 4
+// rows rl, rl + 4, ... (slices in slice order, the slices' loads of the 8 rows in flight together; epilogue4), sums its 4
 // columns over its 8 rows, and the 4 row lanes are combined through LDS in fixed order.
 __global__ __launch_bounds__(256) void splitk_reduce_stats(const GemmP p, const float* __restrict__ ws, int nsplit)
 {
@@ -810,30 +659,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats(const GemmP p, const 
     for (int k = 0; k < 8; ++k) {
         const int m = mb + rl + 4 * k;
         if (!colok || m >= p.M) continue;
-        float4 x = v[k];
-        if (p.bias) { x.x += bv.x; x.y += bv.y; x.z += bv.z; x.w += bv.w; }
-        if (p.biasm) { const float b = p.biasm[m]; x.x += b; x.y += b; x.z += b; x.w += b; }
-        if (p.rowbias) {
-            const float4 r = *reinterpret_cast<const float4*>(p.rowbias + (long)(m / p.rows_per_batch) * p.ldrb + n);
-            x.x += r.x; x.y += r.y; x.z += r.z; x.w += r.w;
-        }
-        float4 rs = make_float4(0, 0, 0, 0);
-        if (p.resid) rs = *reinterpret_cast<const float4*>(p.resid + (long)m * p.ldr + n);
-        if (p.act_post) { x.x += rs.x; x.y += rs.y; x.z += rs.z; x.w += rs.w; }
-        switch (p.act) {
-        case MLSD_ACT_SILU: x.x = silu_f(x.x); x.y = silu_f(x.y); x.z = silu_f(x.z); x.w = silu_f(x.w); break;
-        case MLSD_ACT_GELU: x.x = gelu_tanh_f(x.x); x.y = gelu_tanh_f(x.y); x.z = gelu_tanh_f(x.z); x.w = gelu_tanh_f(x.w); break;
-        case MLSD_ACT_GELU_QUICK: x.x = gelu_quick_f(x.x); x.y = gelu_quick_f(x.y); x.z = gelu_quick_f(x.z); x.w = gelu_quick_f(x.w); break;
-        case MLSD_ACT_RELU: x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); break;
-        default: break;
-        }
-        if (!p.act_post) { x.x += rs.x; x.y += rs.y; x.z += rs.z; x.w += rs.w; }
-        if (p.C32) *reinterpret_cast<float4*>(p.C32 + (long)m * p.ldc32 + n) = x;
-        if (p.C16) {
-            f16x4 h = {(_Float16)x.x, (_Float16)x.y, (_Float16)x.z, (_Float16)x.w};
-            *reinterpret_cast<f16x4*>(p.C16 + (long)m * p.ldc16 + n) = h;
-        }
-        v[k] = x;
+        v[k] = epilogue4(p, m, n, v[k], p.bias != nullptr, bv);
+        store4(p.C32, p.ldc32, p.C16, p.ldc16, m, n, v[k]);
     }
     // shifted sums (mlsd_gemm_args.colstats_shift; the consuming finalize reads the shift back from the output): K = the block's first row,
     // finished by row lane 0; K = 0: plain sums
@@ -866,7 +693,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats(const GemmP p, const 
 
 // ---- split-K second pass that ENDS WITH THE LAYERNORM of the rows it finishes (round 4).  SD1.5 batch 1 is bound by its dispatch count; where the producer of a
 // LayerNorm's input is a split-K launch, its reduce pass already holds every finished row: one block per row (N / 4 threads, a thread owns 4 consecutive columns)
-// adds the slices in slice order and applies the epilogue exactly like splitk_reduce (bit-identical fp32 output), then takes the row's mean and centred sum of squares
+// adds the slices in slice order and applies the epilogue (sum_slices4, epilogue4), then takes the row's mean and centred sum of squares
 // with two block reductions (fixed order) and writes fp16((v - mean) rstd gamma + beta): the LayerNorm launch (ggml_norm + mul + add, src/mlblock_nn.c:65-71)
 // disappears.  No cross-block hand-off: nothing to time out.
 __global__ __launch_bounds__(1024) void splitk_reduce_ln(const GemmP p, const float* __restrict__ ws, int nsplit)
@@ -877,29 +704,8 @@ __global__ __launch_bounds__(1024) void splitk_reduce_ln(const GemmP p, const fl
     const bool in = n < p.N;
     float4 v = make_float4(0, 0, 0, 0);
     if (in) {
-        v = *reinterpret_cast<const float4*>(ws + (long)m * p.N + n);
-        for (int z = 1; z < nsplit; ++z) {
-            const float4 t = *reinterpret_cast<const float4*>(ws + z * p.ws_stride + (long)m * p.N + n);
-            v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-        }
-        if (p.bias) { const float4 b = *reinterpret_cast<const float4*>(p.bias + n); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-        if (p.biasm) { const float b = p.biasm[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
-        if (p.rowbias) {
-            const float4 r = *reinterpret_cast<const float4*>(p.rowbias + (long)(m / p.rows_per_batch) * p.ldrb + n);
-            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-        }
-        float4 rs = make_float4(0, 0, 0, 0);
-        if (p.resid) rs = *reinterpret_cast<const float4*>(p.resid + (long)m * p.ldr + n);
-        if (p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-        switch (p.act) {
-        case MLSD_ACT_SILU: v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); break;
-        case MLSD_ACT_GELU: v.x = gelu_tanh_f(v.x); v.y = gelu_tanh_f(v.y); v.z = gelu_tanh_f(v.z); v.w = gelu_tanh_f(v.w); break;
-        case MLSD_ACT_GELU_QUICK: v.x = gelu_quick_f(v.x); v.y = gelu_quick_f(v.y); v.z = gelu_quick_f(v.z); v.w = gelu_quick_f(v.w); break;
-        case MLSD_ACT_RELU: v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); break;
-        default: break;
-        }
-        if (!p.act_post) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-        if (p.C32) *reinterpret_cast<float4*>(p.C32 + (long)m * p.ldc32 + n) = v;
+        v = epilogue4(p, m, n, sum_slices4(ws, p.ws_stride, (long)m * p.N + n, nsplit));
+        store4(p.C32, p.ldc32, nullptr, 0, m, n, v);      // (no fp16 copy of the raw output: the normalised one is the fp16 output)
     }
     // LayerNorm of the finished row: mean, then the centred sum of squares (two passes over the registers: no cancellation), waves combined in wave order
     float s = in ? (v.x + v.y) + (v.z + v.w) : 0.f;
@@ -927,8 +733,8 @@ __global__ __launch_bounds__(1024) void splitk_reduce_ln(const GemmP p, const fl
 
 #ifdef MLSD_GEMM_EXPERIMENTS
 // ---- split-K second pass that ends with the GROUPNORM (+ SiLU) of what it finishes (round 4): one block per (image, group), the slab of HW rows x N / G columns in
-// registers (<= GNR_MAXI float4 per thread: the sizes for which the one-dispatch GroupNorm of norm.hip wins).  Slices added in slice order + epilogue as splitk_reduce
-// (bit-identical fp32 output), then mean / centred variance of the slab by two block reductions, normalise, affine, SiLU, fp16.  The GroupNorm launch that follows a
+// registers (<= GNR_MAXI float4 per thread: the sizes for which the one-dispatch GroupNorm of norm.hip wins).  Slices added in slice order + epilogue4,
+// then mean / centred variance of the slab by two block reductions, normalise, affine, SiLU, fp16.  The GroupNorm launch that follows a
 // split-K convolution in every resnet of SD1.5's 8x8 / 16x16 levels (ggml_group_norm + mul + add + silu, src/mlblock_nn.c:86-99,135-136,146-147) disappears.
 constexpr int GNR_MAXI = 10;
 __global__ __launch_bounds__(256) void splitk_reduce_gn(const GemmP p, const float* __restrict__ ws, int nsplit)
@@ -962,25 +768,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn(const GemmP p, const flo
         const int it = tid + i * 256;
         if (i < NI && it < items) {
             const int pix = it / Q4, n = c0 + 4 * (it - pix * Q4), m = img * p.gn_hw + pix;
-            float4 x = v[i];
-            if (p.bias) { const float4 b = *reinterpret_cast<const float4*>(p.bias + n); x.x += b.x; x.y += b.y; x.z += b.z; x.w += b.w; }
-            if (p.biasm) { const float b = p.biasm[m]; x.x += b; x.y += b; x.z += b; x.w += b; }
-            if (p.rowbias) {
-                const float4 r = *reinterpret_cast<const float4*>(p.rowbias + (long)(m / p.rows_per_batch) * p.ldrb + n);
-                x.x += r.x; x.y += r.y; x.z += r.z; x.w += r.w;
-            }
-            float4 rs = make_float4(0, 0, 0, 0);
-            if (p.resid) rs = *reinterpret_cast<const float4*>(p.resid + (long)m * p.ldr + n);
-            if (p.act_post) { x.x += rs.x; x.y += rs.y; x.z += rs.z; x.w += rs.w; }
-            switch (p.act) {
-            case MLSD_ACT_SILU: x.x = silu_f(x.x); x.y = silu_f(x.y); x.z = silu_f(x.z); x.w = silu_f(x.w); break;
-            case MLSD_ACT_GELU: x.x = gelu_tanh_f(x.x); x.y = gelu_tanh_f(x.y); x.z = gelu_tanh_f(x.z); x.w = gelu_tanh_f(x.w); break;
-            case MLSD_ACT_GELU_QUICK: x.x = gelu_quick_f(x.x); x.y = gelu_quick_f(x.y); x.z = gelu_quick_f(x.z); x.w = gelu_quick_f(x.w); break;
-            case MLSD_ACT_RELU: x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); break;
-            default: break;
-            }
-            if (!p.act_post) { x.x += rs.x; x.y += rs.y; x.z += rs.z; x.w += rs.w; }
-            if (p.C32) *reinterpret_cast<float4*>(p.C32 + (long)m * p.ldc32 + n) = x;
+            const float4 x = epilogue4(p, m, n, v[i]);
+            store4(p.C32, p.ldc32, nullptr, 0, m, n, x);      // (no fp16 copy of the raw output: the normalised one is the fp16 output)
             v[i] = x;
             s += (x.x + x.y) + (x.z + x.w);
         }
@@ -1111,28 +900,46 @@ bool wide_epilogue_ok(const mlsd_gemm_args* a)
            (!a->rowbias || (!(a->ldrb & 3) && !((uintptr_t)a->rowbias & 15)));
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, bool REG = false>
-int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
+// The kernel parameter block of a launch of `a` on route `r`: every field that is a plain copy of an argument, filled once; the rest zero.  The launchers set what is
+// theirs: nbm / nbn, vec, korder, the diagnostics (dbg, gw, tbuf), the split-K redirection to the workspace (split_to_workspace), stream-K, colstats, ln_*, gn_*, xa_*.
+GemmP gemm_params_from(const mlsd_gemm_args* a, const GemmRoute& r)
 {
-    GemmP p;
+    GemmP p{};
     p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
     p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
     p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = 0; p.wrap = r.wrap;
+    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.wrap = r.wrap;
     p.bias = a->bias; p.biasm = a->bias_m; p.act_post = a->act_after_resid; p.rowbias = a->rowbias; p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
     p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
     p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
+    p.cs_shift = a->colstats_shift ? 1 : 0;
+    return p;
+}
+
+// Split-K with a pass that adds the slices: `p` becomes the raw-partial form (no epilogue; slice z = fp32 [M][N] at ws + z * ws_stride).  Returns the epilogue as
+// requested, for that pass.
+GemmP split_to_workspace(GemmP& p, const mlsd_gemm_args* a)
+{
+    GemmP pe = p;
+    p.bias = p.biasm = p.rowbias = p.resid = nullptr; p.act = 0; p.act_post = 0;
+    p.C16 = nullptr; p.C32 = (float*)a->ws; p.ldc32 = a->N; p.ws_stride = (long)a->M * a->N;
+    pe.ws_stride = p.ws_stride;
+    return pe;
+}
+
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NSTAGE, bool REG = false>
+int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
+{
+    GemmP p = gemm_params_from(a, r);
     p.nbm = (a->M + BM - 1) / BM; p.nbn = (a->N + BN - 1) / BN;
     p.vec = r.vec;
-    p.dbg = g_gemm_dbg; p.tbuf = nullptr; p.colstats = nullptr; p.cs_shift = a->colstats_shift ? 1 : 0; p.sk_L = 0; p.sk_ws = nullptr; p.sk_flag = nullptr;
+    p.dbg = g_gemm_dbg;
     p.gw = g_gemm_panel;
     const int nsplit = r.nsplit;
     p.kt_per = r.kt_per;
-    p.ws_stride = 0;
     // column statistics for a consuming GroupNorm: one K slice -> this kernel's epilogue (blocks of WM rows); split-K -> the reduce pass (blocks of 32 rows)
     if (r.stats_rows > 0 && nsplit == 1) p.colstats = a->colstats;
     GemmP pe = p;                                  // the epilogue as requested (second pass of a split-K launch)
-    if (r.stats_rows > 0 && nsplit > 1) pe.colstats = a->colstats;
     // reduced inside the launch: one counter per output tile (a->sk_flags, 4096 words, zero between launches), one slab per (tile, slice)
     const bool inl = r.splitk == SPLITK_INLINE;
     if (inl) { p.sk_L = nsplit; p.sk_ws = (float*)a->ws; p.sk_flag = a->sk_flags; }
@@ -1140,28 +947,15 @@ int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
         const size_t need = (size_t)nsplit * a->M * a->N * sizeof(float);
         if (a->ws_bytes < need || ((uintptr_t)a->ws & 15))
             return mlsd_set_error(-1, "mlsd_gemm: split-K workspace too small or misaligned (%zu < %zu)", (size_t)a->ws_bytes, need);
-        p.bias = p.biasm = p.rowbias = p.resid = nullptr; p.act = 0; p.act_post = 0;
-        p.C16 = nullptr; p.C32 = (float*)a->ws; p.ldc32 = a->N; p.ws_stride = (long)a->M * a->N;
-        pe.ws_stride = p.ws_stride;
+        pe = split_to_workspace(p, a);
+        if (r.stats_rows > 0) pe.colstats = a->colstats;
     }
     constexpr int THREADS = WAVES_M * WAVES_N * 64;
     constexpr size_t RING = (size_t)NSTAGE * (BM + BN) * BK * 2;
     constexpr size_t EPI = (size_t)WAVES_M * WAVES_N * 32 * 64 * 4;      // 8 KiB per wave
     constexpr size_t LDS = RING > EPI ? RING : EPI;
     const dim3 grid(p.nbm * p.nbn, nsplit), block(THREADS);
-    // ---- slices added in the launch by the blocks of the tile together (gemm_kernel PAR): the small tiles of the split-K launches, whole grid resident
-#ifdef MLSD_GEMM_EXPERIMENTS   /* measured SLOWER than the second launch (SD1.5 b1 evaluation 7.17 -> 7.76 ms, profiles/NOTES.md): a dispatch boundary is the cheaper grid barrier */
-    if constexpr ((BM == 64 || BM == 128) && BN == 128 && BK == 64 && NSTAGE == 2 && !REG) {
-        if (r.splitk == SPLITK_PAR) {
-            p.sk_flag = a->sk_flags;
-            auto kfn = a->conv ? gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, true> : gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, false, true>;
-            if (LDS > 65536) MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            hipLaunchKernelGGL(kfn, grid, block, LDS, st, p, pe);
-            return mlsd_check_launch("gemm_kernel(split-K, reduced in the launch)");
-        }
-    }
-#endif
-    auto go = [&](auto kfn) -> int {
+    auto go = [&](auto kfn, const char* what = "gemm_kernel") -> int {
         if (LDS > 65536) MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
         hipLaunchKernelGGL(kfn, grid, block, LDS, st, p, pe);
         if (r.splitk == SPLITK_TWO_LAUNCH) {
@@ -1183,8 +977,18 @@ int launch(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
             else
             hipLaunchKernelGGL(splitk_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pe, (const float*)a->ws, nsplit);
         }
-        return mlsd_check_launch("gemm_kernel");
+        return mlsd_check_launch(what);
     };
+    // ---- slices added in the launch by the blocks of the tile together (gemm_kernel PAR): the small tiles of the split-K launches, whole grid resident
+#ifdef MLSD_GEMM_EXPERIMENTS   /* measured SLOWER than the second launch (SD1.5 b1 evaluation 7.17 -> 7.76 ms, profiles/NOTES.md): a dispatch boundary is the cheaper grid barrier */
+    if constexpr ((BM == 64 || BM == 128) && BN == 128 && BK == 64 && NSTAGE == 2 && !REG) {
+        if (r.splitk == SPLITK_PAR) {
+            p.sk_flag = a->sk_flags;
+            const char* what = "gemm_kernel(split-K, reduced in the launch)";
+            return a->conv ? go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true, NSTAGE, 0, false, true>, what) : go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 0, false, true>, what);
+        }
+    }
+#endif
 #ifdef MLSD_GEMM_EXPERIMENTS   /* timing-only builds of the loop: no refills (1) / no MFMA (2); see DESIGN.md */
     if (!a->conv && g_gemm_dbg == 1) return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 1, REG>);
     if (!a->conv && g_gemm_dbg == 2) return go(gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false, NSTAGE, 2, REG>);
@@ -1318,21 +1122,14 @@ template <int BM, int BN, int CB0, int CB1, bool RESBATCH, bool SK = false, int 
 int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 {
     constexpr int BK = 64;
-    GemmP p;
-    p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
-    p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
-    p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = a->upsample; p.korder = g_gemm_korder; p.wrap = r.wrap;
-    p.bias = a->bias; p.biasm = a->bias_m; p.act_post = a->act_after_resid; p.rowbias = a->rowbias; p.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
-    p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
-    p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
+    GemmP p = gemm_params_from(a, r);
+    p.korder = g_gemm_korder;
     p.nbm = (a->M + BM - 1) / BM; p.nbn = (a->N + BN - 1) / BN;
     p.vec = 1;                                             // pp_eligible() checked the alignment
-    p.dbg = g_gemm_dbg; p.gw = g_gemm_panel; p.tbuf = g_gemm_tbuf; p.colstats = nullptr;
-    p.kt_per = (a->K + BK - 1) / BK; p.ws_stride = 0;      // no split-K on these tiles
+    p.dbg = g_gemm_dbg; p.gw = g_gemm_panel; p.tbuf = g_gemm_tbuf;
+    p.kt_per = (a->K + BK - 1) / BK;                       // no split-K on these tiles
     constexpr size_t LDS = 2 * (size_t)(BM + BN) * BK * 2; // the ring; the epilogue needs no LDS
     const int ntiles = p.nbm * p.nbn;
-    p.sk_L = 0; p.sk_ws = nullptr; p.sk_flag = nullptr;
     p.ln_g = a->ln_gamma; p.ln_b = a->ln_beta; p.ln_eps = a->ln_eps; p.ln_y = (_Float16*)a->ln_y16; p.ldln = a->ldln; p.ln_ws = a->ln_ws; p.ln_cnt = a->ln_cnt; p.ln_slot = a->ln_slot;
     if constexpr (SK) {
         p.sk_L = sk_share(ntiles, a->K / BK, g_gemm_ncu);
@@ -1360,7 +1157,6 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
     // the epilogue the kernel is built with (gemm_pp.hpp): the bulk launches of the UNet / VAE have no activation in the GEMM
     const int epi = r.epi;
     p.colstats = (epi == PP_EPI_F32_STATS || epi == PP_EPI_F32_RES_STATS) ? a->colstats : nullptr;
-    p.cs_shift = a->colstats_shift ? 1 : 0;
     if constexpr (SK) {       // the stream-K builds: the fp32 epilogues of the long-K convs / feed-forward outputs, fp16 for the fused projections
         if (r.wrap) {         // (sk_eligible admits these two epilogues only)
             if (epi == PP_EPI_F32) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32, true>);
@@ -1459,21 +1255,13 @@ int skinny_slices(const mlsd_gemm_args* a, int* kt_per_out)
 
 int launch_skinny(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 {
-    GemmP p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const _Float16*)a->A; p.B = (const _Float16*)a->W_;
-    p.lda = a->lda; p.ldb = a->ldb; p.M = a->M; p.N = a->N; p.K = a->K;
-    p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.OH = a->OH; p.OW = a->OW; p.KH = a->KH; p.KW = a->KW;
-    p.stride = a->stride; p.pad = a->pad; p.ups = 0; p.wrap = r.wrap;
-    p.rows_per_batch = 1; p.vec = 1; p.gw = 0;
+    GemmP p = gemm_params_from(a, r);
+    p.vec = 1;
     const int nsplit = r.nsplit;
     const size_t need = (size_t)nsplit * a->M * a->N * sizeof(float);
     if (a->ws_bytes < need) return mlsd_set_error(-1, "mlsd_gemm: skinny-M workspace too small (%zu < %zu)", (size_t)a->ws_bytes, need);
-    p.kt_per = r.kt_per; p.C32 = (float*)a->ws; p.ldc32 = a->N; p.ws_stride = (long)a->M * a->N;
-    GemmP pe = p;                                  // the epilogue as requested: applied by splitk_reduce
-    pe.bias = a->bias; pe.biasm = a->bias_m; pe.act_post = a->act_after_resid; pe.rowbias = a->rowbias; pe.rows_per_batch = a->rows_per_batch > 0 ? a->rows_per_batch : 1;
-    pe.ldrb = a->ldrb; pe.resid = a->resid; pe.ldr = a->ldr; pe.act = a->act;
-    pe.C32 = a->C32; pe.ldc32 = a->ldc32; pe.C16 = (_Float16*)a->C16; pe.ldc16 = a->ldc16;
+    p.kt_per = r.kt_per;
+    const GemmP pe = split_to_workspace(p, a);     // the epilogue as requested: applied by splitk_reduce
     // K steps in flight per thread.  Measured (profiles/r4_gemm_skinny_ablation.txt, 128x1280x11520 conv, cold weights): PF = 7 (128 KB of LDS, one block per CU) 30.2 us,
     // PF = 3 (64 KB, two blocks per CU: one block's barrier / LDS / MFMA chain overlaps the other's) 23.9 us; the weight stream alone 19.2 / 16.1 us
     constexpr int PF = 3;

@@ -1,5 +1,5 @@
-// Persistent "ping-pong" GEMM tiles (256x256x64 and 128x320x64) for gfx950 — included by gemm_conv.hip (inside
-// its anonymous namespace; uses GemmP, wait_vmcnt, g_zero_page and the activation helpers).
+// Persistent "ping-pong" GEMM tiles (256x256x64 and 128x320x64) for gfx950, launched by gemm_conv.hip (launch_pp).
+// GemmP, wait_vmcnt and g_zero_page come from gemm_params.hpp, the activation helpers from common.hpp.
 //
 // 8 waves = 2 groups (wave rows wr = 0,1) x 4 wave columns; a wave owns a 128x64 output = 4 quadrants of
 // 64x32, accumulated with v_mfma_f32_16x16x32_f16 (128 accumulator registers).  One wave of each group
@@ -29,6 +29,11 @@
 // product: a lane holds 4 consecutive columns) without touching LDS or draining anything, and the next main
 // loop starts on landed data.  With K = 1280 (20 K tiles per output tile) the exposed prologue + epilogue was a third of
 // the tile time.  Units past the end of the stream are staged from the zero page (uniform counts).
+#pragma once
+#include "gemm_params.hpp"
+
+namespace {
+
 struct PPTile { int m0, n0; };
 
 template <int BM, int BN>
@@ -1217,3 +1222,5 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
     stamp(6);
     if (p.tbuf && tid == 0) p.tbuf[(long)blockIdx.x * 8 + 7] = ntile;
 }
+
+}  // namespace

@@ -1,5 +1,5 @@
-// Skinny-M weight-streaming GEMM / implicit-GEMM conv for gfx950 (round 4) -- included by gemm_conv.hip inside its anonymous
-// namespace (uses GemmP, lds_off, wait_vmcnt, g_zero_page).
+// Skinny-M weight-streaming GEMM / implicit-GEMM conv for gfx950 (round 4), launched by gemm_conv.hip (launch_skinny).
+// GemmP, lds_off, wait_vmcnt and g_zero_page come from gemm_params.hpp.
 //
 //   C[M,N] = A[M,K] . W[N,K]^T   with M <= 128: the 8x8 level of SD1.5 at batch 1 (cond + uncond = 128 rows), the time-embedding
 //   projections (M = 2).  Replaces ggml_mul_mat / ggml_conv_2d (/root/reference/src/mlblock_nn.c:16-55) at the sizes of
@@ -28,6 +28,12 @@
 // a lane stores 4 consecutive columns (16 bytes).
 //
 // Algorithmic bytes per launch: N K 2 (weights) + A once + S M N 4 (partials, written and read once).
+#pragma once
+#include <type_traits>
+#include "gemm_params.hpp"
+
+namespace {
+
 template <int I, int N, class F>
 __device__ __forceinline__ void skinny_static_for(F&& f)
 {
@@ -198,3 +204,5 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmP p)
         }
     }
 }
+
+}  // namespace

@@ -52,8 +52,14 @@ typedef enum {
 	MLIS_OPT_ERROR_HANDLER = 31, MLIS_OPT_LOG_LEVEL = 32, MLIS_OPT_MODEL_TYPE = 33, MLIS_OPT_WEIGHT_TYPE = 34,
 	MLIS_OPT_NO_PROMPT_PARSE = 35, MLIS_OPT__LAST = 35,
 	/* extensions of this implementation (ids from 101, as MLIS_MODEL_TYPE_AMD_*; MLIS_OPT__LAST stays the reference's last option) */
-	MLIS_OPT_AMD_TILING = 101      /* "tiling": seamless tiling, none|x|y|xy or 0..3 (int); the UNet and codec convolutions pad circularly */
+	MLIS_OPT_AMD_TILING = 101,     /* "tiling": seamless tiling, none|x|y|xy or 0..3 (int); the UNet and codec convolutions pad circularly */
+	/* hires fix (two-pass txt2img): generate at IMAGE_DIM, upscale the latent, denoise again at the larger size.  The four persist across generations. */
+	MLIS_OPT_AMD_HIRES_SCALE = 102,    /* "hires_scale" (float): 0 or 1 = off, else 1 < s <= 4; target latent = floor(l s + 0.5) per side */
+	MLIS_OPT_AMD_HIRES_DENOISE = 103,  /* "hires_denoise" (float, default 0.7): 0 < d <= 1, the second pass's f_t_ini */
+	MLIS_OPT_AMD_HIRES_STEPS = 104,    /* "hires_steps" (int): step count the second pass is scheduled with, 0 = the STEPS value (it runs the last hires_denoise share of them) */
+	MLIS_OPT_AMD_HIRES_UPSCALER = 105  /* "hires_upscaler": nearest|bilinear|bicubic or 0..2 (int; MLIS_AMD_RESAMPLE_*), default bilinear */
 } MLIS_Option;
+enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 
 typedef struct MLIS_Ctx MLIS_Ctx;                                                                            /* :352 */
 typedef struct MLIS_Image { uint8_t* d; size_t sz; unsigned w, h, c; int flags; } MLIS_Image;                /* :356-363 */
@@ -116,6 +122,13 @@ float mlis_tensor_similarity(const MLIS_Tensor*, const MLIS_Tensor*);
 int mlis_amd_prompt_tokens_set(MLIS_Ctx* ctx, const int32_t* tokens, const float* weights, int n, int negative);
 /* the engine behind the context (NULL before the first setup/generate): for multi-GPU drivers and profiling */
 struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* ctx);
+/* engines constructed by this context so far.  A context keeps its two most recently used engines (one per model / size / batch / ... key),
+ * so a workflow that alternates between two sizes -- the hires fix -- rebuilds nothing; mlis_amd_engine_get returns the one used last. */
+int mlis_amd_engine_builds(MLIS_Ctx* ctx);
+/* dst = src resampled to w x h on the GPU (pixel centres, no antialiasing; mode MLIS_AMD_RESAMPLE_*): every n[2] * n[3] plane of src on its own.
+ * Tap indices outside a plane are clamped to the border, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed.
+ * Returns 1, MLIS_E_OPT_VALUE for a bad mode or size. */
+int mlis_amd_tensor_resample(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int mode);
 
 #ifdef __cplusplus
 }

@@ -396,6 +396,19 @@ int mlsd_latent_sample_nchw(const float* moments /* NCHW [B][2cz][HW] */, const 
 /* ltensor_copy_slice2 (src/localtensor.h:84-94; VAE tiling, src/vae.c:283-297,368-382) on NCHW fp32 [planes][h][w] tensors */
 int mlsd_copy_slice2(float* dst, int dw, int dh, const float* src, int sw, int sh, int n0, int n1, int di0, int di1,
                      int si0, int si1, int planes, void* stream);
+/* Resampling of NCHW fp32 planes [planes][sh][sw] -> [planes][dh][dw] (the latent upscaler of the two-pass "hires fix"; not in the reference).
+ * Pixel centres: output pixel d samples the source at (d + 0.5) s_in / s_out - 0.5 on each axis (torch's F.interpolate(align_corners=False)
+ * for nearest-exact / bilinear / bicubic, no antialiasing).  The tap index and the fractional position come from the exact integer quotient
+ * and remainder of ((2 d + 1) s_in - s_out) / (2 s_out); weights and sums are fp32 (tap weights first along the row, then the rows).
+ *   MLSD_RESAMPLE_NEAREST   index floor((d + 0.5) s_in / s_out)
+ *   MLSD_RESAMPLE_BILINEAR  2 x 2 taps
+ *   MLSD_RESAMPLE_BICUBIC   4 x 4 taps, Keys kernel with a = -0.75
+ * A tap index outside the plane is clamped to the border; along an axis named in `wrap` (bit 0 columns, bit 1 rows, as mlsd_gemm_args.wrap) it
+ * is taken modulo the extent.  Every extent is 1 .. MLSD_RESAMPLE_MAX_EXTENT (the fractional position is in [0, 1) only while 2 s_out is exact
+ * in fp32) and planes * dh * dw < 2^31; anything else returns -1.  Equal sizes copy the planes bit for bit.  src and dst must not overlap. */
+enum { MLSD_RESAMPLE_NEAREST = 0, MLSD_RESAMPLE_BILINEAR = 1, MLSD_RESAMPLE_BICUBIC = 2 };
+enum { MLSD_RESAMPLE_MAX_EXTENT = 1 << 22 };
+int mlsd_resample2d(const float* src, int sw, int sh, float* dst, int dw, int dh, int planes, int mode, int wrap, void* stream);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

@@ -318,6 +318,7 @@ static const char k_usage[] =
 "Generation:  -p --prompt TEXT   -n --nprompt TEXT   -d --image-dim W,H   -i --input PATH   --imask PATH\n"
 "             --ilatent PATH   --ilmask PATH   -o --output PATH   --olatent PATH   --no-prompt-parse BOOL\n"
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
+"Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic\n"
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"

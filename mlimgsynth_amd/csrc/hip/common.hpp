@@ -34,6 +34,10 @@ int mlsd_check_launch(const char* what);
         }                                                                                   \
     } while (0)
 
+// ---- elementwise launches: 256 threads per block, at most 4096 blocks, each thread striding over the elements
+inline unsigned nblk(long n) { long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
+#define GRID_LOOP(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
+
 // ---- small device helpers -------------------------------------------------
 // Activations on the fast hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each): they sit in GEMM
 // epilogues where a libm-grade tanhf (~30 VALU instructions) costs a quarter of a short-K main loop.

@@ -10,9 +10,6 @@
 
 namespace {
 
-inline unsigned nblk(long n) { long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
-#define GRID_LOOP(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
-
 // dx = mix(vparam(eps_c), vparam(eps_u)); eps NHWC [N][HW][ld] (cond rows 0..B-1, uncond B..2B-1), x / dx NCHW [B][C][HW]
 __global__ void dxdt_cfg_kernel(const float* __restrict__ eps, long ld, const float* __restrict__ x, float* __restrict__ dx,
                                 int B, int C, int HW, float cfg, int vparam, float c_out, float c_skip)

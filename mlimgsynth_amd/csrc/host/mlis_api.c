@@ -39,6 +39,7 @@ struct MLIS_Ctx {
 	int32_t *ptok[2]; float *ptokw[2]; int n_ptok[2], have_ptok[2];     /* mlis_amd_prompt_tokens_set */
 	int model_type, width, height, n_batch, clip_skip, vae_tile, n_thread, dump_flags, flags, tuflags, wtype;
 	int tiling;             /* MLIS_OPT_AMD_TILING: 0 none, 1 x, 2 y, 3 xy */
+	float hires_scale, hires_denoise; int hires_steps, hires_upscaler;      /* MLIS_OPT_AMD_HIRES_*: the two-pass generation of mlis_generate */
 	float cfg_scale;
 	int method, sched, n_step;
 	float f_t_ini, f_t_end, s_noise, s_ancestral;
@@ -51,7 +52,9 @@ struct MLIS_Ctx {
 	char mname[16];
 	uint64_t synth_seed; int synth;
 	MLTStore *ts, *ts_tae;
-	MLIS_AmdCtx* eng; char eng_key[96];
+	MLIS_AmdCtx* eng; char eng_key[96];       /* the engine used last */
+	MLIS_AmdCtx* eng2; char eng2_key[96];     /* the one used before it (engine_get): a two-size workflow rebuilds nothing */
+	int n_eng_builds;
 	int ctx_tok;            /* rows of the conditioning the engine is built for: 77 W (windowed prompt); 0 = 77 */
 	MLIS_AmdTextCond* tc; char tc_key[64];
 	ClipTokenizer* tok;
@@ -62,7 +65,8 @@ struct MLIS_Ctx {
 	char errstr[600];
 	char* infotext;
 	int32_t* tokens; float* tokens_w; int n_tokens;
-	int last_n_step, last_nfe;
+	int last_n_step, last_nfe;      /* of the generation as the infotext reports it: after a hires generation the steps of its FIRST pass ("Steps:") and the evaluations of both */
+	int nfe_base;           /* evaluations of the first hires pass while the second one runs: progress and last_nfe count both */
 };
 
 /* ------------------------------------------------------------------ small helpers */
@@ -119,15 +123,18 @@ MLB_API const char* mlis_sched_str(MLIS_Scheduler x) { return (x >= 0 && x < COU
 MLB_API MLIS_Scheduler mlis_sched_fromz(const char* s) { return (MLIS_Scheduler)from_list(k_sched, COUNTOF(k_sched), 1, s, strlen(s)); }
 MLB_API const char* mlis_loglvl_str(MLIS_LogLvl id) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (k_loglvl[i].id == (int)id) return k_loglvl[i].n; return "???"; }
 MLB_API MLIS_LogLvl mlis_loglvl_fromz(const char* s) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (id_eq(s, strlen(s), k_loglvl[i].n)) return (MLIS_LogLvl)k_loglvl[i].id; return (MLIS_LogLvl)-1; }
+static const char* const k_option_amd[] = { "tiling", "hires_scale", "hires_denoise", "hires_steps", "hires_upscaler" };   /* ids from MLIS_OPT_AMD_TILING */
 static const char* const k_tiling[] = { "none", "x", "y", "xy" };
+static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
-	if (x == MLIS_OPT_AMD_TILING) return "tiling";
+	if (x >= MLIS_OPT_AMD_TILING && x < MLIS_OPT_AMD_TILING + COUNTOF(k_option_amd)) return k_option_amd[x - MLIS_OPT_AMD_TILING];
 	return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???";
 }
 MLB_API MLIS_Option mlis_option_fromz(const char* s)
 {
-	if (id_eq(s, strlen(s), "tiling")) return MLIS_OPT_AMD_TILING;
+	const int i = from_list(k_option_amd, COUNTOF(k_option_amd), 1, s, strlen(s));
+	if (i >= 0) return (MLIS_Option)(MLIS_OPT_AMD_TILING + i);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -187,6 +194,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->wtype = MLT_F16;
 	S->cfg_scale = 7;
 	S->f_t_ini = 1;
+	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -197,6 +205,7 @@ static void engine_drop(MLIS_Ctx* S)
 	/* (the context's Philox offset is copied back after every SEEDED use of an engine -- generate / image encode -- and nowhere else:
 	 * an engine that was only built for mlis_image_decode still has offset 0 and must not reset the context's running offset) */
 	if (S->eng) { mlis_amd_destroy(S->eng); S->eng = NULL; S->eng_key[0] = 0; }
+	if (S->eng2) { mlis_amd_destroy(S->eng2); S->eng2 = NULL; S->eng2_key[0] = 0; }
 }
 static void textcond_drop(MLIS_Ctx* S) { if (S->tc) { mlis_amd_textcond_destroy(S->tc); S->tc = NULL; S->tc_key[0] = 0; } }
 static void model_drop(MLIS_Ctx* S)
@@ -230,6 +239,7 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 
 MLB_API const char* mlis_errstr_get(const MLIS_Ctx* S) { return S ? S->errstr : mlsd_last_error(); }
 MLB_API struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* S) { return S ? S->eng : NULL; }
+MLB_API int mlis_amd_engine_builds(MLIS_Ctx* S) { return (S && S->signature == CTX_SIGNATURE) ? S->n_eng_builds : -1; }
 
 /* ------------------------------------------------------------------ options */
 /* by_option: the type comes from MLIS_OPT_MODEL_TYPE (it then survives a checkpoint whose type cannot be detected); a type that
@@ -464,6 +474,21 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (i < 0 || i > 3) BAD_VALUE;
 		S->tiling = i;
 		break;
+	case MLIS_OPT_AMD_HIRES_SCALE: if (!arg_float(A, 0, 4, NAN, &f) || (f > 0 && f < 1)) BAD_VALUE; S->hires_scale = f; break;   /* 0 and 1: off */
+	case MLIS_OPT_AMD_HIRES_DENOISE: if (!arg_float(A, 0, 1, NAN, &f) || !(f > 0)) BAD_VALUE; S->hires_denoise = f; break;
+	case MLIS_OPT_AMD_HIRES_STEPS: if (!arg_int(A, 0, 1000, 0, &i)) BAD_VALUE; S->hires_steps = i; break;
+	case MLIS_OPT_AMD_HIRES_UPSCALER:      /* nearest|bilinear|bicubic or 0..2 */
+		if (A->is_str) {
+			next_str_arg(A);
+			i = from_list(k_resample, COUNTOF(k_resample), 1, A->arg_b, A->arg_n);
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i >= COUNTOF(k_resample)) BAD_VALUE;
+		S->hires_upscaler = i;
+		break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (A->is_str) {
@@ -522,6 +547,10 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_model ? S->path_model : ""; } break;
 	case MLIS_OPT_MODEL_TYPE: { int *p = va_arg(ap, int*); if (p) *p = S->model_type; } break;
 	case MLIS_OPT_AMD_TILING: { int *p = va_arg(ap, int*); if (p) *p = S->tiling; } break;
+	case MLIS_OPT_AMD_HIRES_SCALE: { float *p = va_arg(ap, float*); if (p) *p = S->hires_scale; } break;
+	case MLIS_OPT_AMD_HIRES_DENOISE: { float *p = va_arg(ap, float*); if (p) *p = S->hires_denoise; } break;
+	case MLIS_OPT_AMD_HIRES_STEPS: { int *p = va_arg(ap, int*); if (p) *p = S->hires_steps; } break;
+	case MLIS_OPT_AMD_HIRES_UPSCALER: { int *p = va_arg(ap, int*); if (p) *p = S->hires_upscaler; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -559,9 +588,8 @@ MLB_API const MLIS_BackendInfo* mlis_backend_info_get(MLIS_Ctx* S, unsigned idx,
 
 static int file_exists(const char* p) { struct stat st; return p && *p && !stat(p, &st); }
 
-MLB_API int mlis_setup(MLIS_Ctx* S)
+static int backend_setup(MLIS_Ctx* S)
 {
-	if (!S || S->signature != CTX_SIGNATURE) return -1;
 	if (!(S->rflags & READY_BACKEND)) {
 		/* mlis_backend_init :1119-1161: "" / "HIP" / "HIPn" select a device; anything else is an unknown backend */
 		int dev = 0;
@@ -575,6 +603,13 @@ MLB_API int mlis_setup(MLIS_Ctx* S)
 		}
 		S->rflags |= READY_BACKEND;
 	}
+	return 1;
+}
+
+MLB_API int mlis_setup(MLIS_Ctx* S)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	int rb = backend_setup(S); if (rb < 0) return rb;
 	if (!(S->rflags & READY_MODEL)) {
 		if (str_empty(S->path_model)) return api_error(S, MLIS_E_FILE_NOT_FOUND, "no model set (option MODEL)");
 		if (S->ts) { mlts_close(S->ts); S->ts = NULL; }               /* left over from a set-up that failed after opening the file */
@@ -664,7 +699,8 @@ static int sampler_defaults(MLIS_Ctx* S, int* n_step, int* method, int* sched)
 	return 1;
 }
 
-/* the engine for (model, size, batch, guidance on/off, codec); rebuilt only when one of these changes */
+/* the engine for (model, size, batch, guidance on/off, codec), built when none of the two resident ones has that key: the context keeps the
+ * engine used last (S->eng) and the one used before it; a third key takes the place of the latter */
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
@@ -673,8 +709,17 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
+	if ((!S->eng || strcmp(key, S->eng_key)) && S->eng2 && !strcmp(key, S->eng2_key)) {      /* the other resident engine: they change places */
+		MLIS_AmdCtx *e = S->eng; char k[sizeof(S->eng_key)]; memcpy(k, S->eng_key, sizeof(k));
+		S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(k));
+		S->eng2 = e; memcpy(S->eng2_key, k, sizeof(k));
+	}
 	if (!S->eng || strcmp(key, S->eng_key)) {
-		engine_drop(S);
+		if (S->eng) {           /* the engine used last moves to the second slot; what was there, the least recently used one, goes */
+			if (S->eng2) mlis_amd_destroy(S->eng2);
+			S->eng2 = S->eng; memcpy(S->eng2_key, S->eng_key, sizeof(S->eng_key));
+			S->eng = NULL; S->eng_key[0] = 0;
+		}
 		MLIS_AmdConfig c; memset(&c, 0, sizeof(c));
 		c.model = S->mname; c.width = lw * f; c.height = lh * f; c.n_batch = B; c.n_step = n_step; c.cfg_scale = S->cfg_scale;
 		c.s_ancestral = S->s_ancestral; c.sched = sched; c.use_tae = tae; c.weight_seed = S->synth_seed; c.method = method;
@@ -683,8 +728,9 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
 		S->eng = mlis_amd_create_ex(&c, S->tiling, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
+		S->n_eng_builds++;
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
-		if (ctx_weights(S, mlis_amd_unet_ctx(S->eng), 0) < 0 || ctx_weights(S, mlis_amd_decoder_ctx(S->eng), tae) < 0) { engine_drop(S); return -1; }
+		if (ctx_weights(S, mlis_amd_unet_ctx(S->eng), 0) < 0 || ctx_weights(S, mlis_amd_decoder_ctx(S->eng), tae) < 0) { mlis_amd_destroy(S->eng); S->eng = NULL; return -1; }
 		snprintf(S->eng_key, sizeof(S->eng_key), "%s", key);
 		if (S->dump_flags & 4) {   /* MLIS_DUMP_GRAPH (src/mlimgsynth.c:432,1298 -> MLB_F_DUMP -> "dump-graph-<name>.txt", src/mlblock.c:111-116) */
 			mlctx_block_graph_dump_path(mlis_amd_unet_ctx(S->eng), "dump-graph-unet.txt");
@@ -940,15 +986,48 @@ MLB_API int mlis_image_decode(MLIS_Ctx* S, const MLIS_Tensor* latent, MLIS_Tenso
 	return progress(S, MLIS_STAGE_IMAGE_DECODE, 1, 1);
 }
 
+/* ------------------------------------------------------------------ resampling */
+/* host tensor -> device, mlsd_resample2d, -> host tensor; src may be dst (it is on the device before dst is resized) */
+static int tensor_resample(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int mode)
+{
+	if (mode < MLIS_AMD_RESAMPLE_NEAREST || mode > MLIS_AMD_RESAMPLE_BICUBIC) return api_error(S, MLIS_E_OPT_VALUE, "invalid resampling mode %d", mode);
+	if (!src || !dst || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || src->n[2] < 1 || src->n[3] < 1)
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor to resample");
+	const int sw = src->n[0], sh = src->n[1], c = src->n[2], b = src->n[3];
+	const size_t n_src = mlis_tensor_count(src), n_dst = (size_t)c * b * (w > 0 ? w : 0) * (h > 0 ? h : 0);
+	if (w < 1 || h < 1 || w > 65535 || h > 65535 || n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid size to resample to: %dx%d", w, h);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_dst = NULL;
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+			|| mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w, h, c * b, mode, S->tiling, NULL))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, w, h, c, b);
+		if (mlsd_memcpy(dst->d, d_dst, n_dst * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	return r;
+}
+
+MLB_API int mlis_amd_tensor_resample(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int mode)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_resample(S, src, dst, w, h, mode);
+}
+
 /* ------------------------------------------------------------------ generation */
 static int denoise_cb(void* user, int step, int n_step, int nfe)
 {
 	MLIS_Ctx *S = (MLIS_Ctx*)user;
-	S->prg.nfe = nfe;
+	S->prg.nfe = S->nfe_base + nfe;
 	return progress(S, MLIS_STAGE_DENOISE, step, n_step);
 }
 
-static void infotext_update(MLIS_Ctx* S, int w, int h)
+static int hires_on(const MLIS_Ctx* S) { return S->hires_scale > 1; }
+
+static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 {	/* mlis_infotext_update :1589-1632 (imitates stable-diffusion-webui create_infotext) */
 	char buf[4096]; int n = 0;
 #define ADD(...) n += snprintf(buf + n, sizeof(buf) - n > 0 ? sizeof(buf) - n : 0, __VA_ARGS__)
@@ -974,20 +1053,19 @@ static void infotext_update(MLIS_Ctx* S, int w, int h)
 	}
 	if (S->flags & CF_USE_TAE) ADD(", VAE: tae");
 	if (S->tiling) ADD(", Tiling: %s", k_tiling[S->tiling]);
+	if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
+		k_resample[S->hires_upscaler], S->hires_denoise);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
 }
 
-MLB_API int mlis_generate(MLIS_Ctx* S)
+/* one generation from the options as they stand (the whole of mlis_generate but its first checks and its clean-up): conditioning, engine,
+ * sampling, the latent fetched, the decode when `decode`; *pw_img x *ph_img = the size generated */
+static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 {
-	if (!S || S->signature != CTX_SIGNATURE) return -1;
-	int r = mlis_setup(S); if (r < 0) return r;
+	int r;
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
-	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
-	if ((r = tiling_check(S)) < 0) return r;
-	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
-	const double t_start = S->t_last; (void)t_start;
 	int w = S->width / 8, h = S->height / 8;
 
 	/* img2img source (:1652-1657) */
@@ -998,6 +1076,7 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	if (S->tuflags & MLIS_TUF_LATENT) { w = S->latent.n[0]; h = S->latent.n[1]; }
 	if (w < 1 || h < 1) return api_error(S, MLIS_E_OPT_VALUE, "image size not set");
 	const int w_img = w * 8, h_img = h * 8;
+	*pw_img = w_img; *ph_img = h_img;
 
 	/* conditioning (:1688-1707), before the engine: its length (77 W rows) is part of the UNet plan */
 	if (!(S->tuflags & MLIS_TUF_CONDITIONING)) {
@@ -1046,7 +1125,7 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	mlis_amd_set_callback(S->eng, S->callback ? denoise_cb : NULL, S);
 	r = mlis_amd_denoise(S->eng, NULL);
 	S->rng_offset = mlis_amd_rng_offset(S->eng);
-	S->last_n_step = mlis_amd_last_n_step(S->eng); S->last_nfe = mlis_amd_last_nfe(S->eng); S->prg.nfe = S->last_nfe;
+	S->last_n_step = mlis_amd_last_n_step(S->eng); S->last_nfe = S->nfe_base + mlis_amd_last_nfe(S->eng); S->prg.nfe = S->last_nfe;
 	if (r < 0) {
 		if (r < -1 && r != MLIS_E_NAN) return r;                                  /* the callback's abort code */
 		return api_error_lib(S, r == MLIS_E_NAN || strstr(mlsd_last_error(), "NaN") ? MLIS_E_NAN : MLIS_E_UNKNOWN);
@@ -1055,12 +1134,56 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	if (mlsd_memcpy(S->latent.d, mlis_amd_latent_device(S->eng), (size_t)B*4*w*h*4, 1, NULL) || mlsd_device_sync()) return api_error_lib(S, MLIS_E_UNKNOWN);
 
 	/* decode (:1752-1756) */
-	if (!(S->flags & CF_NO_DECODE)) {
+	if (decode) {
 		if (mlis_amd_decode(S->eng) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 		if ((r = image_fetch(S, &S->image, w_img, h_img)) < 0) return r;
 		if ((r = progress(S, MLIS_STAGE_IMAGE_DECODE, 1, 1)) < 0) return r;
 	}
-	infotext_update(S, w_img, h_img);
+	return 1;
+}
+
+/* hires fix: the txt2img pass at IMAGE_DIM (never decoded), its latent upscaled, then the img2img-from-latent pass at the target size with
+ * f_t_ini = hires_denoise -- what a caller gets from generate (NO_DECODE) + mlis_amd_tensor_resample + generate (MLIS_TUF_LATENT), with the
+ * prompt, the token ids and the prompt's LoRAs in place until the end and the Philox streams running on from the first pass */
+static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int* hires_n_step)
+{
+	static const struct { int flag; const char* what; } inputs[] = { {MLIS_TUF_IMAGE, "an input image (image)"}, {MLIS_TUF_LATENT, "an input latent (tensor_use_flags latent)"},
+		{MLIS_TUF_MASK, "a mask (image_mask)"}, {MLIS_TUF_LMASK, "a latent mask (tensor_use_flags lmask)"} };
+	for (int i=0;i<COUNTOF(inputs);++i) if (S->tuflags & inputs[i].flag)
+		return api_error(S, MLIS_E_OPT_VALUE, "hires_scale %g cannot be combined with %s: the hires fix is a txt2img feature", S->hires_scale, inputs[i].what);
+	const float f_t_ini = S->f_t_ini; const int n_step = S->n_step, tuflags = S->tuflags;
+	int r = generate_pass(S, 0, pw_img, ph_img);
+	if (r >= 0) {
+		const int steps1 = S->last_n_step, lw = S->latent.n[0], lh = S->latent.n[1];
+		r = tensor_resample(S, &S->latent, &S->latent, (int)floor((double)lw * S->hires_scale + 0.5), (int)floor((double)lh * S->hires_scale + 0.5), S->hires_upscaler);
+		if (r >= 0) {
+			S->tuflags = (tuflags & MLIS_TUF_CONDITIONING) | MLIS_TUF_LATENT;
+			S->f_t_ini = S->hires_denoise;
+			if (S->hires_steps > 0) S->n_step = S->hires_steps;
+			int method, sched; sampler_defaults(S, hires_n_step, &method, &sched);   /* "Hires steps": the count asked for (as "Steps" does, webui's convention); with f_t_ini < 1 the pass runs fewer */
+			S->nfe_base = S->last_nfe;
+			r = generate_pass(S, decode, pw_img, ph_img);
+			S->nfe_base = 0;
+			S->last_n_step = steps1;        /* "Steps" of the infotext: the first pass, the second one is "Hires steps" */
+		}
+	}
+	S->f_t_ini = f_t_ini; S->n_step = n_step; S->tuflags = tuflags;
+	return r;
+}
+
+MLB_API int mlis_generate(MLIS_Ctx* S)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	int r = mlis_setup(S); if (r < 0) return r;
+	const int B = S->n_batch > 0 ? S->n_batch : 1;
+	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
+	if ((r = tiling_check(S)) < 0) return r;
+	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
+	int w_img = 0, h_img = 0, hires_n_step = 0;
+	const int decode = !(S->flags & CF_NO_DECODE);
+	r = hires_on(S) ? generate_hires(S, decode, &w_img, &h_img, &hires_n_step) : generate_pass(S, decode, &w_img, &h_img);
+	if (r < 0) return r;
+	infotext_update(S, w_img, h_img, hires_n_step);
 	/* mlis_prompt_clear :692-709 */
 	str_set(&S->prompt_raw, ""); str_set(&S->nprompt_raw, "");
 	mlis_prompt_free(&S->prompt); mlis_prompt_free(&S->nprompt);

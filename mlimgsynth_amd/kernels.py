@@ -7,6 +7,7 @@ from ._lib import check, lib, vp
 c_i64, c_int, c_f = ctypes.c_int64, ctypes.c_int, ctypes.c_float
 
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_GELU_QUICK, ACT_RELU, ACT_GEGLU = range(6)
+RESAMPLE_NEAREST, RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = range(3)
 
 # tile variants (MLSD_TILE_*) and the labels mlsd_gemm_variant prints for them
 TILE_128x128, TILE_64x128, TILE_256x128, TILE_256x128_S3, TILE_256x256, TILE_128x320 = 0, 1, 3, 4, 9, 16
@@ -102,6 +103,11 @@ def groupnorm_ws_bytes(n_img, hw, n_grp):
 def layernorm(x, ldx, rows, d, eps, gamma, beta, y16, y32=None, stream=None):
     check(lib().mlsd_layernorm(vp(x), c_i64(ldx), rows, d, c_f(eps), vp(gamma), vp(beta), vp(y16), vp(y32), vp(stream)),
           "mlsd_layernorm")
+
+
+def resample2d(src, sw, sh, dst, dw, dh, planes, mode, wrap=0, stream=None):
+    """mlsd_resample2d: fp32 planes [planes][sh][sw] -> [planes][dh][dw] (device pointers); wrap bit 0 columns, bit 1 rows."""
+    check(lib().mlsd_resample2d(vp(src), sw, sh, vp(dst), dw, dh, planes, mode, wrap, vp(stream)), "mlsd_resample2d")
 
 
 def sync():

@@ -41,7 +41,9 @@ _define("MLIS_MODEL_", ["NONE", "UNET", "VAE", "TAE", "CLIP", "CLIP2"])
 _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LORA_CLEAR", "PROMPT", "NPROMPT", "IMAGE_DIM", "BATCH_SIZE",
                       "CLIP_SKIP", "CFG_SCALE", "METHOD", "SCHEDULER", "STEPS", "F_T_INI", "F_T_END", "S_NOISE", "S_ANCESTRAL", "IMAGE",
                       "IMAGE_MASK", "NO_DECODE", "TENSOR_USE_FLAGS", "SEED", "VAE_TILE", "UNET_SPLIT", "THREADS", "DUMP_FLAGS", "AUX_DIR",
-                      "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101))
+                      "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101, AMD_HIRES_SCALE=102, AMD_HIRES_DENOISE=103,
+                                                                            AMD_HIRES_STEPS=104, AMD_HIRES_UPSCALER=105))
+_define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 MLIS_CTEF_NO_NORM = 1
 
 
@@ -71,6 +73,7 @@ _PROTOTYPES = {
     "mlis_tensor_similarity": (_F, [_TP, _TP]), "mlis_image_encode": (_I, [_V, _TP, _TP, _I]), "mlis_image_decode": (_I, [_V, _TP, _TP, _I]),
     "mlis_mask_encode": (_I, [_V, _TP, _TP, _I]), "mlis_text_tokenize": (_I, [_V, _S, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), _I]),
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
+    "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
 }
 
 mlis_lib = None
@@ -173,7 +176,8 @@ class MLImgSynth:
 
     def option_get(self, option, out):
         """out: a ctypes object receiving the value (c_char_p for MODEL / PROMPT / NPROMPT, c_int for MODEL_TYPE: the four options
-        mlis_option_get implements, as in the reference)."""
+        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER, c_float for
+        AMD_HIRES_SCALE / AMD_HIRES_DENOISE)."""
         r = self._lib.mlis_option_get(self._ctx, option, ctypes.byref(out))
         if r < 0:
             raise RuntimeError("Failed to get option %s: %s" % (option, self.errstr_get()))
@@ -260,6 +264,30 @@ class MLImgSynth:
     def mask_encode(self, mask, flags=0):
         "Reduce a pixel mask to latent resolution."
         return self._transform(self._lib.mlis_mask_encode, "encode the mask", mask, flags)
+
+    # ---- hires fix
+    def hires_set(self, scale, denoise=None, steps=None, upscaler=None):
+        """Two-pass generation: scale 0 or 1 switches it off, else 1 < scale <= 4; denoise in (0, 1] is the second pass's strength,
+        steps its step count (0 = the STEPS value), upscaler 'nearest' | 'bilinear' | 'bicubic'.  The options persist."""
+        self.option_set("hires_scale", scale)
+        if denoise is not None:
+            self.option_set("hires_denoise", denoise)
+        if steps is not None:
+            self.option_set("hires_steps", steps)
+        if upscaler is not None:
+            self.option_set("hires_upscaler", upscaler)
+
+    def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
+        "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."
+        tin = tensor._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_resample(self._ctx, ctypes.byref(tin), tout, w, h, mode) < 0:
+            raise RuntimeError("Failed to resample the tensor: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
+
+    def engine_builds(self):
+        "Engines this context has constructed so far (it keeps the two used last)."
+        return int(self._lib.mlis_amd_engine_builds(self._ctx))
 
 
 def tensor_from_numpy(a):

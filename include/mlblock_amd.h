@@ -141,12 +141,20 @@ void mlctx_tensor_shape(const MLTensor* t, int64_t ne[4]);
 
 /* ---- parameters (tstore_tensor_read / mlctx_tstore_load: src/mlblock.c:232-292) */
 int mlctx_param_count(const MLCtx* C);
+void mlctx_params_unload(MLCtx* C);            /* marks every parameter as not set: the plan's weights are loaded again before it runs */
 int mlctx_params_loaded(const MLCtx* C);       /* 1 when every parameter has been set (synth / param_set / tstore_load) */
 /* key = full dotted name as the reference derives it (src/mlblock.c:67-105) */
 int mlctx_param_info(const MLCtx* C, int i, const char** key, int* type, int64_t ne[4]);
 /* load one parameter from host memory in the REFERENCE layout/shape (element count is what is checked,
  * src/mlblock.c:243); src_type MLT_F32 | MLT_F16 | MLT_BF16 | MLT_F64; converted/repacked to the engine's device layout */
 int mlctx_param_set(MLCtx* C, const char* key, int src_type, const void* host_data, int64_t n_elem);
+/* index of the parameter `key` for mlctx_param_info, or -1 */
+int mlctx_param_find(const MLCtx* C, const char* key);
+/* LoRA update of one loaded parameter in place on the device: W += (up . down) scale, up [n1][r] and down [r][n0] host fp32 already rounded to the operand
+ * precision of the host merge (mlts_lora_apply), whose arithmetic the kernel repeats operation for operation: the parameter ends up bit-identical to one
+ * loaded from a merged store.  Resident parameters are patched on the context's stream, streamed ones through their host master copy.
+ * Returns 1, 0 when the context holds no such parameter, < 0 on error ("NaN in LoRA result": a resident parameter must then be set again). */
+int mlctx_param_lora(MLCtx* C, const char* key, const float* up, const float* down, int64_t n0, int64_t n1, int r, float scale);
 /* deterministic synthetic weights (bench/tests: no checkpoints exist): same generator as oracle/o_core.c */
 int mlctx_params_synth(MLCtx* C, uint64_t seed);
 

@@ -223,6 +223,12 @@ void mlts_close(MLTStore* S);
  * model store: W += (scale | alpha/rank | 1) * mult * up.down for every "<X>.lora_down.weight"; returns the number of tensors patched */
 MLTStore* mlts_open_lora(const char* path);
 int mlts_lora_apply(MLTStore* model, const MLTStore* lora, float mult, int wtype);
+/* the two halves of mlts_lora_apply, for the path that patches weights already on the device (mlctx_param_lora): the same validation, the same error texts.
+ * mlts_lora_resolve: entry i of the adapter -> 0 (not a "<X>.lora_down.weight"), 1 with the item filled, < 0 on error.  mlts_lora_operands: up [n1][n_inner] and
+ * down [n_inner][n0] as the merge reads them (fp32, rounded to F16 values unless wtype is F32). */
+typedef struct { char key[600]; /* "<X>.weight" */ const MLTSEntry *down, *up; int64_t n0, n1, n_inner; float scale; /* (scale | alpha / n_inner | 1) * mult */ } MLTSLoraItem;
+int mlts_lora_resolve(const MLTStore* model, const MLTStore* lora, int i, float mult, MLTSLoraItem* item);
+int mlts_lora_operands(const MLTSLoraItem* item, int wtype, float* up, float* down);
 int mlts_count(const MLTStore* S);
 const MLTSEntry* mlts_at(const MLTStore* S, int i);
 const MLTSEntry* mlts_find(const MLTStore* S, const char* name);
@@ -231,6 +237,7 @@ int mlts_stats(const MLTStore* S, int* n_unused, int* n_split);
 const char* mlts_model_identify(const MLTStore* S, int* wtype);
 /* mlctx_tstore_load (src/mlblock.c:266-292): every parameter of the prepared plan by name; element count checked */
 int mlctx_tstore_load(MLCtx* C, const MLTStore* S);
+int mlctx_tstore_load_key(MLCtx* C, const MLTStore* S, const char* key);      /* one of them */
 
 /* ---------------------------------------------------------------- prompt pre-processing (src/prompt_preproc.h:104-209)
  * text = the prompt with emphasis marks / options removed; chunks index into it; loras name into lora_names */
@@ -320,6 +327,7 @@ int mlis_amd_set_lmask(MLIS_AmdCtx* S, const float* lmask);
 int mlis_amd_encode(MLIS_AmdCtx* S, const float* images, int sample);
 MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S);                                /* NULL before the first encode / prepare */
 MLCtx* mlis_amd_encoder_prepare(MLIS_AmdCtx* S);
+MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i);     /* every plan of the engine: 0 UNet, 1 decoder, 2 encoder, 3 tile decoder, 4 tile encoder; NULL where there is none */
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

@@ -125,6 +125,12 @@ struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* ctx);
 /* engines constructed by this context so far.  A context keeps its two most recently used engines (one per model / size / batch / ... key),
  * so a workflow that alternates between two sizes -- the hires fix -- rebuilds nothing; mlis_amd_engine_get returns the one used last. */
 int mlis_amd_engine_builds(MLIS_Ctx* ctx);
+/* LoRA bookkeeping, cumulative like mlis_amd_engine_builds.  A change of the LoRA set or of a multiplier while engines or text towers are resident is applied
+ * to their weights in place on the GPU: every weight the old set had patched is restored from the checkpoint (n_restored counts weights per plan), the new
+ * set's adapters are applied in option order by a kernel that repeats the host merge's arithmetic (n_patched, per plan and adapter tensor).  With nothing
+ * resident the adapters are merged into the tensor store on the host before the first engine is built (n_cold_merges counts adapters).  The same list of
+ * (file, multiplier) as the one applied costs nothing.  Any pointer may be NULL.  Returns 1. */
+int mlis_amd_lora_stats(MLIS_Ctx* ctx, int* n_restored, int* n_patched, int* n_cold_merges);
 /* dst = src resampled to w x h on the GPU (pixel centres, no antialiasing; mode MLIS_AMD_RESAMPLE_*): every n[2] * n[3] plane of src on its own.
  * Tap indices outside a plane are clamped to the border, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed.
  * Returns 1, MLIS_E_OPT_VALUE for a bad mode or size. */

@@ -418,6 +418,14 @@ int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream)
  * dtype: 0 fp32, 1 fp16.  The destination must be zero-initialised when padding is present. */
 int mlsd_synth_fill(void* dst, int dtype, int64_t n, uint64_t key, float offset, float kf, int layout,
                     int64_t p0, int64_t p1, int64_t p2, int64_t p3, int64_t p4, void* stream);
+/* LoRA update of a device weight in place (hip/lora.hip): for the reference element i = o n0 + c, o < n1, c < n0,
+ *   W[dst(i)] = W[dst(i)] + (sum over r ascending of up[o][r] * down[r][c]) * scale,  rounded to nearest even at the weight's type,
+ * with dst the layout rule of mlsd_synth_fill (layouts 0, 1, 2; p0..p4 as there; padding elements are never written) and the host merge's arithmetic
+ * (mlts_lora_apply: separate multiply and add, one rounding of the result), so that the weight equals the one merged on the host bit for bit.
+ * up [n1][r] and down [r][n0] are fp32 on the device, already rounded to the operand precision of the merge.  *flag (device) is set to 1 when any
+ * result is not finite (the weight then holds that result: the caller restores it).  dtype: 0 fp32, 1 fp16. */
+int mlsd_lora_apply(void* W, int dtype, int64_t n0, int64_t n1, const float* up, const float* down, int r, float scale, int layout,
+                    int64_t p0, int64_t p1, int64_t p2, int64_t p3, int64_t p4, int* flag, void* stream);
 
 /* co-issue probe (round 6, tools/coissue_probe.py): 8 x {one 32x32x16 MFMA if mf, nv (3 / 6) vector instructions of kind vk (1 fma, 2 exp, 3 pk_fma, 4 cvt_pk, 5 max3, 6 pk_add, 7 add,
  * 8 dot2_f32_f16, 9 pk_mul, 10 pk_fma_f16, 11 exp_f16)} per iteration; nthreads 256 / 512 = one / two waves per SIMD; clocks[nblocks] */

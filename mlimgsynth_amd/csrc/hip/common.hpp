@@ -38,6 +38,30 @@ int mlsd_check_launch(const char* what);
 inline unsigned nblk(long n) { long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 #define GRID_LOOP(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
+// ---- device layout of a parameter (param_dst_index of host/mlblock.c): reference element i -> element of the engine's buffer.
+//   layout 1: conv weight i = k0 + K0 (k1 + K1 (cin + Cin cout)), p0=K0 p1=K1 p2=Cin p3=Cout p4=Cin_pad -> [cout][kh][kw][cin_pad]
+//   layout 2: GEGLU linear weight [n_in=p0, 2 d], d=p1: row j<d is value j, row d+j is gate j -> 32-row interleave
+//   layout 3: the same interleave for its bias;  anything else: row-major, i
+__device__ __forceinline__ long param_dst_index(int layout, long i, long p0, long p1, long p2, long p4)
+{
+    if (layout == 1) {
+        const long k0 = i % p0; long t = i / p0;
+        const long k1 = t % p1; t /= p1;
+        const long ci = t % p2; const long co = t / p2;
+        return ((co * p1 + k1) * p0 + k0) * p4 + ci;
+    }
+    if (layout == 2) {
+        const long k = i % p0, row = i / p0;
+        const long j = row < p1 ? row : row - p1;
+        return ((j >> 5) * 64 + (row < p1 ? 0 : 32) + (j & 31)) * p0 + k;
+    }
+    if (layout == 3) {
+        const long j = i < p1 ? i : i - p1;
+        return (j >> 5) * 64 + (i < p1 ? 0 : 32) + (j & 31);
+    }
+    return i;
+}
+
 // ---- small device helpers -------------------------------------------------
 // Activations on the fast hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each): they sit in GEMM
 // epilogues where a libm-grade tanhf (~30 VALU instructions) costs a quarter of a short-K main loop.

@@ -128,23 +128,7 @@ __global__ void synth_fill_kernel(void* __restrict__ dst, int dtype, long n, uin
         const uint64_t u = mix64(key + (uint64_t)i * 0x9E3779B97F4A7C15ULL);
         const int s = (int)(u & 0xFFFF) + (int)((u >> 16) & 0xFFFF) + (int)((u >> 32) & 0xFFFF) + (int)(u >> 48);
         const float v = __fadd_rn(offset, __fmul_rn((float)(s - 131070), kf));
-        long o = i;
-        if (layout == 1) {
-            // reference conv weight index i = k0 + K0*(k1 + K1*(cin + Cin*cout)); p0=K0 p1=K1 p2=Cin p3=Cout p4=Cin_pad
-            const long k0 = i % p0; long t = i / p0;
-            const long k1 = t % p1; t /= p1;
-            const long ci = t % p2; const long co = t / p2;
-            o = ((co * p1 + k1) * p0 + k0) * p4 + ci;     // [cout][kh][kw][cin_pad]
-        } else if (layout == 2) {
-            // GEGLU linear weight [n_in=p0, 2*d], d=p1: row j<d is value j, row d+j is gate j.
-            const long k = i % p0, row = i / p0;
-            const long j = row < p1 ? row : row - p1;
-            const long nr = (j >> 5) * 64 + (row < p1 ? 0 : 32) + (j & 31);
-            o = nr * p0 + k;
-        } else if (layout == 3) {
-            const long row = i, j = row < p1 ? row : row - p1;
-            o = (j >> 5) * 64 + (row < p1 ? 0 : 32) + (j & 31);
-        }
+        const long o = param_dst_index(layout, i, p0, p1, p2, p4);
         if (dtype == 1) ((_Float16*)dst)[o] = (_Float16)v;
         else ((float*)dst)[o] = v;
     }

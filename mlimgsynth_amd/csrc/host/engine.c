@@ -924,6 +924,13 @@ MLB_API void* mlis_amd_image_device(MLIS_AmdCtx* S) { return S->d_img; }
 MLB_API MLCtx* mlis_amd_unet_ctx(MLIS_AmdCtx* S) { return S->unet_ctx; }
 MLB_API MLCtx* mlis_amd_decoder_ctx(MLIS_AmdCtx* S) { return S->dec_ctx; }
 MLB_API MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S) { return S->enc_ctx; }
+/* every plan the engine holds, built or not yet: UNet, decoder, encoder, tile decoder, tile encoder (i < 5; NULL where there is none) */
+MLB_API MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i)
+{
+	if (!S) return NULL;
+	switch (i) { case 0: return S->unet_ctx; case 1: return S->dec_ctx; case 2: return S->enc_ctx; case 3: return S->dect_ctx; case 4: return S->enct_ctx; }
+	return NULL;
+}
 MLB_API float mlis_amd_last_unet_ms(MLIS_AmdCtx* S) { return S->last_unet_ms; }
 MLB_API int mlis_amd_last_nfe(MLIS_AmdCtx* S) { return S->last_nfe; }
 MLB_API int mlis_amd_n_ctx_tok(const MLIS_AmdCtx* S) { return S ? S->c.n_ctx_tok : -1; }     /* context rows of the UNet plan: 77 W */

@@ -77,6 +77,7 @@ static void ctx_reset_(MLCtx* C)
 	if (C->sk_flags) { mlsd_free(C->sk_flags); C->sk_flags = NULL; }
 	if (C->ln_cnt) { mlsd_free(C->ln_cnt); C->ln_cnt = NULL; }
 	if (C->ln_ws) { mlsd_free(C->ln_ws); C->ln_ws = NULL; C->ln_ws_bytes = 0; }
+	if (C->lora_buf) { mlsd_free(C->lora_buf); C->lora_buf = NULL; C->lora_buf_bytes = 0; }
 	wstream_free(C);
 	C->n_chunks = 0; C->cur = NULL; C->cur_left = 0; C->n_free = 0;
 	C->mem_compute = C->mem_params = C->mem_live = C->mem_peak_live = 0;
@@ -1750,6 +1751,7 @@ MLB_API int mlctx_profile_ops(MLCtx* C, float* ms_out, int n_out)
 /* ------------------------------------------------------------------ parameters */
 MLB_API int mlctx_param_count(const MLCtx* C) { return C->n_params; }
 MLB_API int mlctx_params_loaded(const MLCtx* C) { for (int i=0;i<C->n_params;++i) if (!C->params[i].loaded) return 0; return 1; }
+MLB_API void mlctx_params_unload(MLCtx* C) { for (int i=0; C && i<C->n_params; ++i) C->params[i].loaded = 0; }   /* the weights are to be loaded again before the plan runs */
 
 MLB_API int mlctx_param_info(const MLCtx* C, int i, const char** key, int* type, int64_t ne[4])
 {
@@ -1853,6 +1855,67 @@ MLB_API int mlctx_param_set(MLCtx* C, const char* key, int src_type, const void*
 	free(buf);
 	if (rc) return -1;
 	p->loaded = 1;
+	C->static_valid = 0;      /* a step-invariant op (the cross attentions' K / V projection) may read this weight */
+	return 1;
+}
+
+MLB_API int mlctx_param_find(const MLCtx* C, const char* key)
+{
+	for (int i=0; C && key && i<C->n_params; ++i) if (C->params[i].key && !strcmp(C->params[i].key, key)) return i;
+	return -1;
+}
+
+/* device scratch of at least nbytes (grown in MiB steps); the stream is drained before a smaller one is released */
+static int scratch_need(MLCtx* C, void** buf, size_t* have, size_t nbytes)
+{
+	if (*have >= nbytes) return 0;
+	if (mlsd_stream_sync(C->stream)) return -1;
+	if (*buf) mlsd_free(*buf);
+	*buf = NULL; *have = 0;
+	if (mlsd_malloc(buf, ALIGN_UP(nbytes, (size_t)1 << 20))) return -1;
+	*have = ALIGN_UP(nbytes, (size_t)1 << 20);
+	return 0;
+}
+
+/* LoRA update of one parameter of a prepared, loaded context, in place: W += (up . down) scale with the host merge's arithmetic (mlsd_lora_apply), so that the
+ * parameter ends up with the bits mlctx_param_set would have uploaded from a store merged by mlts_lora_apply.  up [n1][r], down [r][n0]: host fp32, already rounded
+ * to the merge's operand precision.  A resident parameter is patched on the context's stream; a streamed one (weight streaming) goes through the device scratch --
+ * master in, kernel, master out -- like mlctx_params_synth, and the segments uploaded ahead are dropped like in mlctx_param_set.  Nothing else in a plan is derived
+ * from a weight's VALUES (prep and the wire_* passes read shapes and pointers only) except the outputs of the step-invariant ops, which are marked stale here.
+ * Returns 1, 0 when the context holds no parameter `key` (a text-tower adapter is not in the UNet's context), < 0 on error; "NaN in LoRA result" when a result is
+ * not finite: a resident parameter then holds those results and has to be set again, a streamed one is unchanged. */
+MLB_API int mlctx_param_lora(MLCtx* C, const char* key, const float* up, const float* down, int64_t n0, int64_t n1, int r, float scale)
+{
+	if (!C) return -1;
+	if (!C->prepared) return mlctx_fail(C, "mlctx_param_lora before mlctx_prep (names are resolved at prep)");
+	const int ip = mlctx_param_find(C, key);
+	if (ip < 0) return 0;
+	MLParam *p = &C->params[ip];
+	const int64_t n = p->ne[0]*p->ne[1]*p->ne[2]*p->ne[3];
+	if (!up || !down || r < 1 || n0 < 1 || n1 < 1 || n0 > n || n % n0 || n / n0 != n1)
+		return mlctx_fail(C, "parameter '%s': LoRA of %lld x %lld, rank %d, for %lld elements", key, (long long)n1, (long long)n0, r, (long long)n);
+	if (!p->loaded) return mlctx_fail(C, "parameter '%s': LoRA before the weight is loaded", key);
+	if (p->type != MLT_F16 && p->type != MLT_F32) return mlctx_fail(C, "parameter '%s': unsupported type %d", key, p->type);
+	const size_t nu = (size_t)n1 * (size_t)r, nd = (size_t)r * (size_t)n0, pbytes = p->dev_elems * (p->type == MLT_F16 ? 2 : 4);
+	if (scratch_need(C, &C->lora_buf, &C->lora_buf_bytes, 256 + (nu + nd) * 4)) return -1;
+	int *d_flag = (int*)C->lora_buf;
+	float *d_up = (float*)((char*)C->lora_buf + 256), *d_down = d_up + nu;
+	void *W = p->dev;
+	char *pm = param_master(C, p);
+	if (pm) {       /* streamed weight: an evaluation in flight may be uploading from the master */
+		if (C->copy_stream) { mlsd_stream_sync(C->stream); mlsd_stream_sync(C->copy_stream); }
+		C->pf_valid = 0;
+		if (scratch_need(C, &C->pscratch, &C->pscratch_bytes, pbytes)) return -1;
+		W = C->pscratch;
+		if (mlsd_memcpy(W, pm, pbytes, 0, C->stream)) return -1;
+	}
+	int bad = 0;
+	if (mlsd_memset(d_flag, 0, 4, C->stream) || mlsd_memcpy(d_up, up, nu * 4, 0, C->stream) || mlsd_memcpy(d_down, down, nd * 4, 0, C->stream)) return -1;
+	if (mlsd_lora_apply(W, p->type == MLT_F16 ? 1 : 0, n0, n1, d_up, d_down, r, scale, p->layout, p->lp[0], p->lp[1], p->lp[2], p->lp[3], p->lp[4], d_flag, C->stream)) return -1;
+	if (mlsd_memcpy(&bad, d_flag, 4, 1, C->stream) || mlsd_stream_sync(C->stream)) return -1;
+	C->static_valid = 0;
+	if (bad) return mlsd_set_error(-1, "NaN in LoRA result");
+	if (pm && (mlsd_memcpy(pm, W, pbytes, 1, C->stream) || mlsd_stream_sync(C->stream))) return -1;
 	return 1;
 }
 

@@ -122,7 +122,8 @@ struct MLCtx {
 	int pf_valid;                           /* the first segments of the NEXT evaluation are already uploaded / in flight (compute_streamed) */
 	struct MLWSeg* segs; int n_segs;
 	void* copy_stream; void **ev_up, **ev_done;   /* per segment */
-	void* pscratch; size_t pscratch_bytes;  /* device scratch for the synthetic fill */
+	void* pscratch; size_t pscratch_bytes;  /* device scratch for the synthetic fill and the LoRA update of a streamed weight */
+	void* lora_buf; size_t lora_buf_bytes;  /* device staging of a LoRA update's flag and operands (mlctx_param_lora) */
 	size_t stream_bytes_per_eval; int stream_copies_per_eval;
 	MLCtxInfo info;
 };

@@ -9,7 +9,8 @@
  * and re-uploads them inside every mlis_generate); BATCH_SIZE > 1 works (image i uses seed + i, generate.sh:56-59);
  * the CLIP vocabulary is data found through AUX_DIR (the reference compiles src/clip_merges.c.h in); MODEL may be
  * "synth:<sd1|sd2|sdxl|tiny|tinyxl|tinyv>[:seed]" for the synthetic-weight models used by the benchmark and the tests.
- * LoRA files (kohya naming) are merged into the weights at load time on the host (src/lora.c:9-138).
+ * LoRA files (kohya naming) are merged into the weights at load time on the host (src/lora.c:9-138) when nothing is resident yet; a change of the LoRA set or of a
+ * multiplier while engines or text towers are resident patches their weights in place on the GPU, with the host merge's arithmetic (loras_apply_warm).
  */
 #include "mlblock_int.h"
 #include "mlimgsynth_amd.h"
@@ -48,7 +49,13 @@ struct MLIS_Ctx {
 	MLIS_ErrorHandler errh; void* errh_ud;
 	/* state */
 	int rflags;
-	struct { char* path; float mult; int flags; } loras[MAX_LORAS]; int n_lora, n_lora_applied;
+	struct { char* path; float mult; int flags; } loras[MAX_LORAS]; int n_lora;
+	/* what the weights reflect: the adapters merged into S->ts (ts_merged) or patched into the resident plans on the device, in order; the keys they patched */
+	struct { char* path; float mult; } applied[MAX_LORAS]; int n_applied;
+	char** lkeys; int n_lkeys, cap_lkeys;
+	int ts_merged;          /* S->ts holds host-merged tensors: plans built from it need no patch; 0: S->ts is the checkpoint, new plans are loaded and then patched */
+	int ts_partial;         /* a host merge failed midway: S->ts is neither */
+	int n_lora_restored, n_lora_patched, n_lora_cold;      /* mlis_amd_lora_stats */
 	char mname[16];
 	uint64_t synth_seed; int synth;
 	MLTStore *ts, *ts_tae;
@@ -208,9 +215,24 @@ static void engine_drop(MLIS_Ctx* S)
 	if (S->eng2) { mlis_amd_destroy(S->eng2); S->eng2 = NULL; S->eng2_key[0] = 0; }
 }
 static void textcond_drop(MLIS_Ctx* S) { if (S->tc) { mlis_amd_textcond_destroy(S->tc); S->tc = NULL; S->tc_key[0] = 0; } }
+static void applied_clear(MLIS_Ctx* S)
+{
+	for (int i=0;i<S->n_applied;++i) free(S->applied[i].path);
+	S->n_applied = 0;
+}
+static void lkeys_clear(MLIS_Ctx* S) { for (int i=0;i<S->n_lkeys;++i) free(S->lkeys[i]); S->n_lkeys = 0; }
+static void lkey_add(MLIS_Ctx* S, const char* key)
+{
+	for (int i=0;i<S->n_lkeys;++i) if (!strcmp(S->lkeys[i], key)) return;
+	if (S->n_lkeys == S->cap_lkeys) { S->cap_lkeys = S->cap_lkeys ? S->cap_lkeys*2 : 64; S->lkeys = (char**)realloc(S->lkeys, sizeof(char*) * (size_t)S->cap_lkeys); }
+	S->lkeys[S->n_lkeys++] = strdup(key);
+}
+static void lora_state_reset(MLIS_Ctx* S) { applied_clear(S); lkeys_clear(S); S->ts_merged = S->ts_partial = 0; }
+
 static void model_drop(MLIS_Ctx* S)
 {
 	engine_drop(S); textcond_drop(S);
+	lora_state_reset(S);
 	if (S->ts) { mlts_close(S->ts); S->ts = NULL; }
 	if (S->ts_tae) { mlts_close(S->ts_tae); S->ts_tae = NULL; }
 	S->rflags &= ~READY_MODEL;
@@ -232,6 +254,7 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 	for (int i=0;i<MAX_IMAGES;++i) if (S->imgex[i].flags & LT_F_OWNMEM) free(S->imgex[i].d);
 	free(S->infotext); free(S->tokens); free(S->tokens_w);
 	loras_remove(S, 0);
+	free(S->lkeys);
 	S->signature = 0;
 	free(S);
 	*pctx = NULL;
@@ -240,6 +263,14 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 MLB_API const char* mlis_errstr_get(const MLIS_Ctx* S) { return S ? S->errstr : mlsd_last_error(); }
 MLB_API struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* S) { return S ? S->eng : NULL; }
 MLB_API int mlis_amd_engine_builds(MLIS_Ctx* S) { return (S && S->signature == CTX_SIGNATURE) ? S->n_eng_builds : -1; }
+MLB_API int mlis_amd_lora_stats(MLIS_Ctx* S, int* n_restored, int* n_patched, int* n_cold_merges)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	if (n_restored) *n_restored = S->n_lora_restored;
+	if (n_patched) *n_patched = S->n_lora_patched;
+	if (n_cold_merges) *n_cold_merges = S->n_lora_cold;
+	return 1;
+}
 
 /* ------------------------------------------------------------------ options */
 /* by_option: the type comes from MLIS_OPT_MODEL_TYPE (it then survives a checkpoint whose type cannot be detected); a type that
@@ -491,6 +522,7 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
+		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
 		if (A->is_str) {
 			next_str_arg(A);
 			static const struct { const char* n; int t; } wt[] = { {"f32", MLT_F32}, {"f16", MLT_F16}, {"bf16", MLT_BF16} };
@@ -606,6 +638,166 @@ static int backend_setup(MLIS_Ctx* S)
 	return 1;
 }
 
+/* ------------------------------------------------------------------ LoRA */
+static int loras_same_as_applied(const MLIS_Ctx* S)
+{
+	if (S->n_lora != S->n_applied) return 0;
+	for (int i=0;i<S->n_lora;++i) if (strcmp(S->loras[i].path, S->applied[i].path) || S->loras[i].mult != S->applied[i].mult) return 0;
+	return 1;
+}
+static void applied_from_options(MLIS_Ctx* S)
+{
+	applied_clear(S);
+	for (int i=0;i<S->n_lora;++i) { S->applied[i].path = strdup(S->loras[i].path); S->applied[i].mult = S->loras[i].mult; }
+	S->n_applied = S->n_lora;
+}
+
+/* every plan with weights on the device: both engine slots' UNet, decoder, encoder and tile plans, the text towers (a plan built but not loaded yet is
+ * patched when it is loaded, ctx_weights) */
+#define MAX_RESIDENT 16
+static int resident_ctxs(MLIS_Ctx* S, MLCtx** out)
+{
+	int n = 0;
+	MLIS_AmdCtx *eng[2] = { S->eng, S->eng2 };
+	for (int e=0;e<2;++e) for (int i=0; eng[e] && i<5; ++i) {
+		MLCtx *c = mlis_amd_ctx_at(eng[e], i);
+		if (c && mlctx_params_loaded(c)) out[n++] = c;
+	}
+	for (int i=0; S->tc && i<mlis_amd_textcond_n_towers(S->tc) && n<MAX_RESIDENT; ++i) {
+		MLCtx *c = mlis_amd_textcond_ctx(S->tc, i);
+		if (c && mlctx_params_loaded(c)) out[n++] = c;
+	}
+	return n;
+}
+
+/* The device path gives the host merge's bits when the weight on the device IS the value the merge starts from: an F16 parameter with F16 operand rounding
+ * (weight types F16 and BF16), or an F32 parameter with weight type F32.  The engine keeps every matrix weight in F16, so a checkpoint used at weight type F32
+ * -- the host merge then adds to the unrounded fp32 weight and rounds once -- cannot be patched on the device: such a change goes the cold way. */
+static int lora_exact_on_device(const MLIS_Ctx* S, const MLCtx* C, int ip)
+{
+	int type = -1;
+	mlctx_param_info(C, ip, NULL, &type, NULL);
+	return S->wtype != MLT_F32 ? type == MLT_F16 : type == MLT_F32;
+}
+
+/* one adapter onto the plans of `ctxs` that hold its targets; the keys are noted BEFORE they are patched (a failure restores them).  S->ts is the checkpoint. */
+static int lora_patch(MLIS_Ctx* S, const MLTStore* L, float mult, MLCtx** ctxs, int nc)
+{
+	MLTSLoraItem it;
+	const int n = mlts_count(L);
+	for (int i=0;i<n;++i) {
+		int r = mlts_lora_resolve(S->ts, L, i, mult, &it);
+		if (r < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+		if (!r) continue;
+		float *up = NULL, *down = NULL;
+		for (int k=0; k<nc && r>0; ++k) {
+			const int ip = mlctx_param_find(ctxs[k], it.key);
+			if (ip < 0) continue;
+			if (!lora_exact_on_device(S, ctxs[k], ip)) { r = api_error(S, MLIS_E_UNKNOWN, "lora: '%s' cannot be patched on the device at this weight type", it.key); break; }
+			if (!up) {
+				up = (float*)malloc(sizeof(float) * (size_t)(it.n1 * it.n_inner)); down = (float*)malloc(sizeof(float) * (size_t)(it.n_inner * it.n0));
+				if (!up || !down || it.n_inner > 0x7fffffff) { r = api_error(S, MLIS_E_UNKNOWN, "lora: out of memory"); break; }
+				mlts_lora_operands(&it, S->wtype, up, down);
+			}
+			lkey_add(S, it.key);
+			if (mlctx_param_lora(ctxs[k], it.key, up, down, it.n0, it.n1, (int)it.n_inner, it.scale) < 0) { r = api_error_lib(S, MLIS_E_UNKNOWN); break; }
+			S->n_lora_patched++;
+		}
+		free(up); free(down);
+		if (r < 0) return r;
+	}
+	return 1;
+}
+
+/* every key an adapter patched back to the checkpoint's weight, in every plan that holds it */
+static int lora_restore(MLIS_Ctx* S, MLCtx** ctxs, int nc)
+{
+	for (int i=0;i<S->n_lkeys;++i) for (int k=0;k<nc;++k) {
+		if (mlctx_param_find(ctxs[k], S->lkeys[i]) < 0) continue;
+		if (mlctx_tstore_load_key(ctxs[k], S->ts, S->lkeys[i]) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+		S->n_lora_restored++;
+	}
+	lkeys_clear(S);
+	return 1;
+}
+
+static int ts_reopen(MLIS_Ctx* S)
+{	/* the checkpoint again: the header parsed over an mmap, no data copied */
+	MLTStore *p = mlts_open_safetensors(S->path_model, 1);
+	if (!p) return api_error_lib(S, MLIS_E_UNKNOWN);
+	mlts_close(S->ts);
+	S->ts = p; S->ts_merged = S->ts_partial = 0;
+	return 1;
+}
+
+/* The LoRA list changed while plans are resident: nothing is dropped or rebuilt.  All adapters are opened and validated first (mlts_lora_resolve: the host
+ * merge's checks and error texts), so that a missing tensor or a bad shape leaves the device untouched; then every weight the old set patched is restored from
+ * the checkpoint and the new set is applied in option order -- F16 weights round between adapters exactly as the host merge stores F16 between them.  A failure
+ * midway (a non-finite result) restores what was touched: the plans then hold the checkpoint's weights.  Returns 1, 0 when this change has to go the cold way. */
+static int loras_apply_warm(MLIS_Ctx* S)
+{
+	MLCtx *ctxs[MAX_RESIDENT];
+	const int nc = resident_ctxs(S, ctxs);
+	MLTStore *L[MAX_LORAS] = { NULL };
+	int R = 1;
+	if (S->ts_merged && ts_reopen(S) < 0) return -1;
+	for (int i=0; i<S->n_lora && R>0; ++i) {
+		if (!(L[i] = mlts_open_lora(S->loras[i].path))) { R = api_error_lib(S, MLIS_E_UNKNOWN); break; }
+		MLTSLoraItem it;
+		for (int j=0; j<mlts_count(L[i]) && R>0; ++j) {
+			const int r = mlts_lora_resolve(S->ts, L[i], j, S->loras[i].mult, &it);
+			if (r < 0) R = api_error_lib(S, MLIS_E_UNKNOWN);
+			for (int k=0; k<nc && r>0 && R>0; ++k) {
+				const int ip = mlctx_param_find(ctxs[k], it.key);
+				if (ip >= 0 && !lora_exact_on_device(S, ctxs[k], ip)) R = 0;
+			}
+		}
+	}
+	if (R > 0) {
+		if (lora_restore(S, ctxs, nc) < 0) R = -1;
+		else {
+			applied_clear(S);
+			for (int i=0; i<S->n_lora && R>0; ++i)
+				if (lora_patch(S, L[i], S->loras[i].mult, ctxs, nc) < 0) {
+					char why[sizeof(S->errstr)]; snprintf(why, sizeof(why), "%s", S->errstr);
+					R = lora_restore(S, ctxs, nc) < 0 ? -2 : -1;
+					snprintf(S->errstr, sizeof(S->errstr), "%s", why);
+				}
+		}
+		if (R == -2 || (R < 0 && S->n_lkeys)) {          /* a restore failed: the plans' weights are unknown, they go */
+			engine_drop(S); textcond_drop(S); lkeys_clear(S); applied_clear(S);
+		}
+		if (R > 0) applied_from_options(S);
+	}
+	for (int i=0;i<S->n_lora;++i) if (L[i]) mlts_close(L[i]);
+	if (!R) {       /* the cold way: the plans are rebuilt from a merged store */
+		engine_drop(S); textcond_drop(S);
+	}
+	return R < 0 ? MLIS_E_UNKNOWN : R;
+}
+
+/* nothing resident: every active adapter is merged into a freshly read store on the host (:1276-1296); the plans built later load the merged weights */
+static int loras_apply_cold(MLIS_Ctx* S)
+{
+	engine_drop(S); textcond_drop(S);
+	if ((S->ts_merged || S->ts_partial) && ts_reopen(S) < 0) { S->rflags &= ~READY_MODEL; return MLIS_E_UNKNOWN; }
+	applied_clear(S); lkeys_clear(S);
+	for (int i=0;i<S->n_lora;++i) {
+		MLTStore *L = mlts_open_lora(S->loras[i].path);
+		if (!L) return api_error_lib(S, MLIS_E_UNKNOWN);
+		MLTSLoraItem it;
+		for (int j=0;j<mlts_count(L);++j) if (mlts_lora_resolve(S->ts, L, j, S->loras[i].mult, &it) > 0) lkey_add(S, it.key);
+		S->ts_partial = 1;
+		int r = mlts_lora_apply(S->ts, L, S->loras[i].mult, S->wtype);
+		mlts_close(L);
+		if (r < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+		S->ts_partial = 0; S->ts_merged = 1;
+		S->n_lora_cold++;
+		S->applied[S->n_applied].path = strdup(S->loras[i].path); S->applied[S->n_applied].mult = S->loras[i].mult; S->n_applied++;
+	}
+	return 1;
+}
+
 MLB_API int mlis_setup(MLIS_Ctx* S)
 {
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
@@ -639,28 +831,17 @@ MLB_API int mlis_setup(MLIS_Ctx* S)
 		}
 		S->rflags |= READY_MODEL;
 		S->rflags &= ~READY_LORAS;
-		S->n_lora_applied = 0;
+		lora_state_reset(S);
 	}
 	if (!(S->rflags & READY_LORAS)) {
-		/* :1276-1296: patched tensors are dropped (the store is re-read) and every active LoRA is merged again; the resident
-		 * engine and text towers hold the old weights, so they are rebuilt */
-		if (S->n_lora || S->n_lora_applied) {
+		/* :1276-1296 merges every active LoRA into a freshly read store and rebuilds what is resident.  Here: the same list of (file, multiplier) as the one the
+		 * weights reflect costs nothing (a prompt's <lora:> two generations running); with engines or text towers resident they are patched in place; with
+		 * nothing resident, or where the device cannot repeat the host's arithmetic (loras_apply_warm), the adapters are merged on the host like there */
+		if (S->ts_partial || !loras_same_as_applied(S)) {
 			if (S->synth) return api_error(S, MLIS_E_UNKNOWN, "LoRA needs a checkpoint file (the synthetic models have no tensor store)");
-			engine_drop(S); textcond_drop(S);
-			if (S->n_lora_applied) {
-				mlts_close(S->ts);
-				S->ts = mlts_open_safetensors(S->path_model, 1);
-				if (!S->ts) { S->rflags &= ~READY_MODEL; return api_error_lib(S, MLIS_E_UNKNOWN); }
-			}
-			S->n_lora_applied = 0;
-			for (int i=0;i<S->n_lora;++i) {
-				MLTStore *L = mlts_open_lora(S->loras[i].path);
-				if (!L) return api_error_lib(S, MLIS_E_UNKNOWN);
-				int r = mlts_lora_apply(S->ts, L, S->loras[i].mult, S->wtype);
-				mlts_close(L);
-				if (r < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
-				S->n_lora_applied++;
-			}
+			int r = 0;
+			if (!S->ts_partial && (S->eng || S->eng2 || S->tc) && (r = loras_apply_warm(S)) < 0) return r;
+			if (!r && (r = loras_apply_cold(S)) < 0) return r;
 		}
 		S->rflags |= READY_LORAS;
 	}
@@ -688,7 +869,15 @@ static int ctx_weights(MLIS_Ctx* S, MLCtx* C, int is_tae)
 {
 	if (S->synth) return mlctx_params_synth(C, S->synth_seed) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
 	if (is_tae) { if (!S->ts_tae) return api_error(S, MLIS_E_FILE_NOT_FOUND, "no TAE model set (option TAE)"); return tae_load(S, C); }
-	return mlctx_tstore_load(C, S->ts) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
+	if (mlctx_tstore_load(C, S->ts) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+	/* the store is the checkpoint and adapters are active on the device: a plan built now gets them the same way, and so the same weights */
+	for (int i=0; !S->ts_merged && i<S->n_applied; ++i) {
+		MLTStore *L = mlts_open_lora(S->applied[i].path);
+		int r = L ? lora_patch(S, L, S->applied[i].mult, &C, 1) : api_error_lib(S, MLIS_E_UNKNOWN);
+		if (L) mlts_close(L);
+		if (r < 0) { mlctx_params_unload(C); return r; }
+	}
+	return 1;
 }
 
 static int sampler_defaults(MLIS_Ctx* S, int* n_step, int* method, int* sched)

@@ -423,27 +423,37 @@ MLB_API const char* mlts_model_identify(const MLTStore* S, int* wtype)
 
 /* mlctx_tstore_load, src/mlblock.c:266-292.  `optional_prefix`: parameters under it may be absent (a checkpoint without
  * the VAE encoder, say); everything else must be present.  Returns the number of parameters loaded. */
+MLB_API int mlctx_tstore_load_key(MLCtx* C, const MLTStore* S, const char* key)
+{	/* one parameter of the plan from the store */
+	const int ip = mlctx_param_find(C, key);
+	if (ip < 0) return mlsd_set_error(-1, "unknown parameter '%s'", key);
+	int64_t ne[4];
+	mlctx_param_info(C, ip, NULL, NULL, ne);
+	const MLTSEntry *e = mlts_find(S, key);
+	if (!e) return mlsd_set_error(-1, "tensor '%s' not found", key);                 /* mlblock.c:276-277 */
+	const int64_t cnt = e->shape[0]*e->shape[1]*e->shape[2]*e->shape[3];
+	if (cnt != ne[0]*ne[1]*ne[2]*ne[3])                                              /* tstore_tensor_read :243 */
+		return mlsd_set_error(-1, "tensor '%s': %lld elements in the file, %lld expected", key, (long long)cnt,
+			(long long)(ne[0]*ne[1]*ne[2]*ne[3]));
+	if (qblock_elems(e->dtype)) {                                                    /* data_convert through to_float, tensorstore.c:205-214 */
+		float *f = (float*)malloc(sizeof(float) * (size_t)cnt);
+		dequant_blocks(e->dtype, (const unsigned char*)e->data, cnt, f);
+		const int r = mlctx_param_set(C, key, MLT_F32, f, cnt);
+		free(f);
+		if (r < 0) return -1;
+	}
+	else if (mlctx_param_set(C, key, e->dtype, e->data, cnt) < 0) return -1;
+	return 1;
+}
+
 MLB_API int mlctx_tstore_load(MLCtx* C, const MLTStore* S)
 {
 	int n = 0;
 	const int np = mlctx_param_count(C);
 	for (int i=0;i<np;++i) {
-		const char *key; int type; int64_t ne[4];
-		mlctx_param_info(C, i, &key, &type, ne);
-		const MLTSEntry *e = mlts_find(S, key);
-		if (!e) return mlsd_set_error(-1, "tensor '%s' not found", key);                 /* mlblock.c:276-277 */
-		const int64_t cnt = e->shape[0]*e->shape[1]*e->shape[2]*e->shape[3];
-		if (cnt != ne[0]*ne[1]*ne[2]*ne[3])                                              /* tstore_tensor_read :243 */
-			return mlsd_set_error(-1, "tensor '%s': %lld elements in the file, %lld expected", key, (long long)cnt,
-				(long long)(ne[0]*ne[1]*ne[2]*ne[3]));
-		if (qblock_elems(e->dtype)) {                                                    /* data_convert through to_float, tensorstore.c:205-214 */
-			float *f = (float*)malloc(sizeof(float) * (size_t)cnt);
-			dequant_blocks(e->dtype, (const unsigned char*)e->data, cnt, f);
-			const int r = mlctx_param_set(C, key, MLT_F32, f, cnt);
-			free(f);
-			if (r < 0) return -1;
-		}
-		else if (mlctx_param_set(C, key, e->dtype, e->data, cnt) < 0) return -1;
+		const char *key;
+		mlctx_param_info(C, i, &key, NULL, NULL);
+		if (mlctx_tstore_load_key(C, S, key) < 0) return -1;
 		n++;
 	}
 	return n;
@@ -489,47 +499,73 @@ MLB_API int mlts_entry_to_f32(const MLTSEntry* e, float* out, int64_t n)
 	return 1;
 }
 
-MLB_API int mlts_lora_apply(MLTStore* D, const MLTStore* L, float mult, int wtype)
+/* The merge in two parts, so that the device path (mlis_setup on resident engines, mlctx_param_lora) validates an adapter with the same code and the same
+ * error texts as the host merge.  RESOLVE: entry i of the adapter; 0 when it is not a "<X>.lora_down.weight", 1 with the target key "<X>.weight", the
+ * up / down entries, n0, n1, n_inner and scale = (X.scale | X.alpha / n_inner | 1) * mult, < 0 on error. */
+MLB_API int mlts_lora_resolve(const MLTStore* D, const MLTStore* L, int i, float mult, MLTSLoraItem* it)
 {
-	int n_applied = 0;
-	const int r16 = wtype != MLT_F32;
+	if (!D || !L || !it || i < 0 || i >= L->n) return mlsd_set_error(-1, "mlts_lora_resolve: bad arguments");
 	char key[600];
-	for (int i=0; i<L->n; ++i) {
-		const MLTSEntry *ld = &L->e[i];
-		const size_t ln = strlen(ld->name);
-		if (ln < 17 || strcmp(ld->name + ln - 17, ".lora_down.weight")) continue;
-		const int bl = (int)(ln - 17);
-		snprintf(key, sizeof(key), "%.*s.weight", bl, ld->name);
-		MLTSEntry *dst = (MLTSEntry*)mlts_find(D, key);
-		if (!dst) return mlsd_set_error(-1, "lora tensor not found in model: %s", key);
-		snprintf(key, sizeof(key), "%.*s.lora_up.weight", bl, ld->name);
-		const MLTSEntry *lu = mlts_find(L, key);
-		if (!lu) return mlsd_set_error(-1, "lora up tensor not found: %s", key);
-		snprintf(key, sizeof(key), "%.*s.scale", bl, ld->name);
-		const MLTSEntry *ls = mlts_find(L, key);
-		snprintf(key, sizeof(key), "%.*s.alpha", bl, ld->name);
-		const MLTSEntry *la = mlts_find(L, key);
-		/* the file is untrusted input (the reference's arithmetic here is unchecked, src/lora.c:30-50): a 0-dimensional or
-		 * zero-sized tensor must not index shape[-1] or divide by zero, and the element counts must factor exactly */
-		if (ld->n_dim < 2 || lu->n_dim < 2 || dst->n_dim < 2 || ld->n_dim > 4 || lu->n_dim > 4)
-			return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
-		const int64_t n_inner = ld->shape[ld->n_dim - 1];
-		const int64_t cd = ld->shape[0]*ld->shape[1]*ld->shape[2]*ld->shape[3], cu = lu->shape[0]*lu->shape[1]*lu->shape[2]*lu->shape[3];
-		const int64_t cw = dst->shape[0]*dst->shape[1]*dst->shape[2]*dst->shape[3];
-		if (n_inner <= 0 || cd <= 0 || cu <= 0 || cw <= 0 || cd % n_inner || cu % n_inner)
-			return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
-		const int64_t n0 = cd / n_inner, n1 = cu / n_inner;
-		if (!(ld->n_dim == dst->n_dim && lu->n_dim == dst->n_dim && cw == n0 * n1))
-			return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
-		if (ld->dtype == MLT_I32 || ld->dtype == MLT_I64 || lu->dtype == MLT_I32 || lu->dtype == MLT_I64 || dst->dtype == MLT_I32 || dst->dtype == MLT_I64)
-			return mlsd_set_error(-1, "lora: integer tensor in %.*s", bl, ld->name);
-		float scale = 1;
-		if (ls && ls->shape[0]*ls->shape[1]*ls->shape[2]*ls->shape[3] < 1) ls = NULL;
-		if (la && la->shape[0]*la->shape[1]*la->shape[2]*la->shape[3] < 1) la = NULL;
-		if (ls) { float *t = entry_to_f32(ls, 0); scale = t[0]; free(t); }
-		else if (la) { float *t = entry_to_f32(la, 0); scale = t[0] / n_inner; free(t); }
-		scale *= mult;
-		float *down = entry_to_f32(ld, r16), *up = entry_to_f32(lu, r16), *w = entry_to_f32(dst, r16);
+	const MLTSEntry *ld = &L->e[i];
+	const size_t ln = strlen(ld->name);
+	if (ln < 17 || strcmp(ld->name + ln - 17, ".lora_down.weight")) return 0;
+	const int bl = (int)(ln - 17);
+	snprintf(key, sizeof(key), "%.*s.weight", bl, ld->name);
+	const MLTSEntry *dst = mlts_find(D, key);
+	if (!dst) return mlsd_set_error(-1, "lora tensor not found in model: %s", key);
+	snprintf(it->key, sizeof(it->key), "%s", key);
+	snprintf(key, sizeof(key), "%.*s.lora_up.weight", bl, ld->name);
+	const MLTSEntry *lu = mlts_find(L, key);
+	if (!lu) return mlsd_set_error(-1, "lora up tensor not found: %s", key);
+	snprintf(key, sizeof(key), "%.*s.scale", bl, ld->name);
+	const MLTSEntry *ls = mlts_find(L, key);
+	snprintf(key, sizeof(key), "%.*s.alpha", bl, ld->name);
+	const MLTSEntry *la = mlts_find(L, key);
+	/* the file is untrusted input (the reference's arithmetic here is unchecked, src/lora.c:30-50): a 0-dimensional or
+	 * zero-sized tensor must not index shape[-1] or divide by zero, and the element counts must factor exactly */
+	if (ld->n_dim < 2 || lu->n_dim < 2 || dst->n_dim < 2 || ld->n_dim > 4 || lu->n_dim > 4)
+		return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
+	const int64_t n_inner = ld->shape[ld->n_dim - 1];
+	const int64_t cd = ld->shape[0]*ld->shape[1]*ld->shape[2]*ld->shape[3], cu = lu->shape[0]*lu->shape[1]*lu->shape[2]*lu->shape[3];
+	const int64_t cw = dst->shape[0]*dst->shape[1]*dst->shape[2]*dst->shape[3];
+	if (n_inner <= 0 || cd <= 0 || cu <= 0 || cw <= 0 || cd % n_inner || cu % n_inner)
+		return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
+	const int64_t n0 = cd / n_inner, n1 = cu / n_inner;
+	if (!(ld->n_dim == dst->n_dim && lu->n_dim == dst->n_dim && cw == n0 * n1))
+		return mlsd_set_error(-1, "lora up/down invalid shapes for %.*s", bl, ld->name);
+	if (ld->dtype == MLT_I32 || ld->dtype == MLT_I64 || lu->dtype == MLT_I32 || lu->dtype == MLT_I64 || dst->dtype == MLT_I32 || dst->dtype == MLT_I64)
+		return mlsd_set_error(-1, "lora: integer tensor in %.*s", bl, ld->name);
+	float scale = 1;
+	if (ls && ls->shape[0]*ls->shape[1]*ls->shape[2]*ls->shape[3] < 1) ls = NULL;
+	if (la && la->shape[0]*la->shape[1]*la->shape[2]*la->shape[3] < 1) la = NULL;
+	if (ls) { float *t = entry_to_f32(ls, 0); scale = t[0]; free(t); }
+	else if (la) { float *t = entry_to_f32(la, 0); scale = t[0] / n_inner; free(t); }
+	scale *= mult;
+	it->down = ld; it->up = lu; it->n0 = n0; it->n1 = n1; it->n_inner = n_inner; it->scale = scale;
+	return 1;
+}
+
+/* the operands of a resolved item as the merge reads them: fp32, rounded to F16 values unless the weight type is F32; up [n1][n_inner], down [n_inner][n0] */
+MLB_API int mlts_lora_operands(const MLTSLoraItem* it, int wtype, float* up, float* down)
+{
+	if (!it || !it->up || !it->down || !up || !down) return mlsd_set_error(-1, "mlts_lora_operands: bad arguments");
+	const int r16 = wtype != MLT_F32;
+	float *d = entry_to_f32(it->down, r16), *u = entry_to_f32(it->up, r16);
+	memcpy(down, d, sizeof(float) * (size_t)(it->n_inner * it->n0));
+	memcpy(up, u, sizeof(float) * (size_t)(it->n1 * it->n_inner));
+	free(d); free(u);
+	return 1;
+}
+
+/* APPLY: the merge of one resolved item into the store */
+static int lora_merge(MLTStore* D, const MLTSLoraItem* it, int wtype)
+{
+	const int r16 = wtype != MLT_F32;
+	MLTSEntry *dst = (MLTSEntry*)mlts_find(D, it->key);
+	const int64_t n0 = it->n0, n1 = it->n1, n_inner = it->n_inner, cw = n0 * n1;
+	const float scale = it->scale;
+	{
+		float *down = entry_to_f32(it->down, r16), *up = entry_to_f32(it->up, r16), *w = entry_to_f32(dst, r16);
 		float *delta = (float*)malloc(sizeof(float) * (size_t)n0);
 		for (int64_t o=0;o<n1;++o) {       /* up.down accumulated in fp32, scaled, then added to W (src/lora.c:57-61) */
 			for (int64_t c=0;c<n0;++c) delta[c] = 0;
@@ -557,6 +593,19 @@ MLB_API int mlts_lora_apply(MLTStore* D, const MLTStore* L, float mult, int wtyp
 		dst->data = buf;
 		if (D->n_owned == D->cap_owned) { D->cap_owned = D->cap_owned ? D->cap_owned*2 : 64; D->owned = (void**)realloc(D->owned, sizeof(void*)*D->cap_owned); }
 		D->owned[D->n_owned++] = buf;
+	}
+	return 1;
+}
+
+MLB_API int mlts_lora_apply(MLTStore* D, const MLTStore* L, float mult, int wtype)
+{
+	int n_applied = 0;
+	MLTSLoraItem it;
+	for (int i=0; i<L->n; ++i) {
+		const int r = mlts_lora_resolve(D, L, i, mult, &it);
+		if (r < 0) return r;
+		if (!r) continue;
+		if (lora_merge(D, &it, wtype) < 0) return -1;
 		n_applied++;
 	}
 	return n_applied;

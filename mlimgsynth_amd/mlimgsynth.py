@@ -74,6 +74,7 @@ _PROTOTYPES = {
     "mlis_mask_encode": (_I, [_V, _TP, _TP, _I]), "mlis_text_tokenize": (_I, [_V, _S, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), _I]),
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
+    "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
 }
 
 mlis_lib = None
@@ -288,6 +289,14 @@ class MLImgSynth:
     def engine_builds(self):
         "Engines this context has constructed so far (it keeps the two used last)."
         return int(self._lib.mlis_amd_engine_builds(self._ctx))
+
+    def lora_stats(self):
+        """(restored, patched, cold_merges), cumulative: weights set back to the checkpoint's and adapter tensors applied in place on the GPU
+        (per resident plan) when the LoRA set or a multiplier changed, and adapters merged on the host before anything was resident."""
+        a, b, c = _I(), _I(), _I()
+        if self._lib.mlis_amd_lora_stats(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) < 0:
+            raise RuntimeError("Failed to read the LoRA statistics: %s" % self.errstr_get())
+        return a.value, b.value, c.value
 
 
 def tensor_from_numpy(a):

@@ -299,6 +299,22 @@ MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream);        /*
  * meet), 2 y, 3 xy.  The tiled KL-VAE plans (mlis_amd_set_vae_tile) do not wrap: tiles cannot see the opposite edge. */
 MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream);
 int mlis_amd_tiling(const MLIS_AmdCtx* S);
+/* Tiled diffusion (MultiDiffusion): cfg->width x height is the CANVAS (sampler state, noise, mask, decoder, encoder), the UNet plan is built for one window of
+ * min(tile, canvas) per axis.  Every evaluation cuts the canvas into overlapping windows (mlis_amd_window_starts per axis, row-major, y outer), runs the plan on each
+ * -- window j of every image of the batch in one evaluation -- and blends the raw outputs by a weighted average (mlsd_window_blend) before the CFG mix; the solvers
+ * never notice.  tile_w, tile_h, overlap in pixels: multiples of 8, 2 x overlap <= tile.  tile 0, or a tile that covers the canvas on both axes: mlis_amd_create_ex.
+ * With `tiling`, the plan's convolutions wrap only along an axis its window spans; along the others the windows form a ring and one straddles the seam.
+ * use_hipgraph and unet_split work (with unet_split every window streams the weights again). */
+MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream);
+/* window starts along one axis: canvas extent L, window extent T, minimum overlap O (latent pixels), wrap != 0: the canvas tiles along the axis.  T >= L: one window
+ * at 0.  Else n = ceil((L - O) / (T - O)) windows at floor(i (L - T) / (n - 1)), or on a wrapped axis n = ceil(L / (T - O)) at floor(i L / n), window i covering
+ * (starts[i] + k) mod L.  Returns n; -1 for O < 0, 2 O > T, T < 1, L < 1 or n > cap. */
+int mlis_amd_window_starts(int L, int T, int O, int wrap, int* starts, int cap);
+int mlis_amd_tile_info(const MLIS_AmdCtx* S, int* n_win, int* win_w, int* win_h);   /* windows per evaluation (0 = not tiled), window size in latent pixels; any may be NULL */
+int mlis_amd_tile_windows(const MLIS_AmdCtx* S, int* xs, int* ys, int cap);          /* start of every window in evaluation order (latent pixels); returns the count */
+/* one evaluation, for tests and tools: x host [B][4][lh][lw], dx = dxdt(x, sigma) host (UNet evaluation + CFG mix + v-prediction rescale, as one solver stage sees
+ * it).  Needs the conditioning; plain and tiled engines alike; the engine's latent is not touched. */
+int mlis_amd_dxdt(MLIS_AmdCtx* S, const float* x_host, float sigma, float* dx_host);
 void mlis_amd_destroy(MLIS_AmdCtx* S);
 /* conditioning for the whole batch (shared prompt, as generate.sh): cond/uncond [n_ctx_tok][n_ctx] fp32 host (77 rows unless the config says otherwise),
  * label/unlabel [adm] or NULL */

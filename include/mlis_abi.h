@@ -57,7 +57,12 @@ typedef enum {
 	MLIS_OPT_AMD_HIRES_SCALE = 102,    /* "hires_scale" (float): 0 or 1 = off, else 1 < s <= 4; target latent = floor(l s + 0.5) per side */
 	MLIS_OPT_AMD_HIRES_DENOISE = 103,  /* "hires_denoise" (float, default 0.7): 0 < d <= 1, the second pass's f_t_ini */
 	MLIS_OPT_AMD_HIRES_STEPS = 104,    /* "hires_steps" (int): step count the second pass is scheduled with, 0 = the STEPS value (it runs the last hires_denoise share of them) */
-	MLIS_OPT_AMD_HIRES_UPSCALER = 105  /* "hires_upscaler": nearest|bilinear|bicubic or 0..2 (int; MLIS_AMD_RESAMPLE_*), default bilinear */
+	MLIS_OPT_AMD_HIRES_UPSCALER = 105, /* "hires_upscaler": nearest|bilinear|bicubic or 0..2 (int; MLIS_AMD_RESAMPLE_*), default bilinear */
+	/* tiled diffusion (MultiDiffusion): a pass whose size exceeds the tile on an axis evaluates the UNet in overlapping windows of the tile's size and blends their
+	 * outputs; a pass that fits runs as ever (the first pass of a hires generation, typically).  Both persist across generations.  (A block of its own from 111.) */
+	MLIS_OPT_AMD_UNET_TILE = 111,          /* "unet_tile" (int, pixels): 0 = off (default), else a multiple of 8 -- the size the model was trained at: 512 SD1, 1024 SDXL */
+	MLIS_OPT_AMD_UNET_TILE_OVERLAP = 112   /* "unet_tile_overlap" (int, pixels): minimum overlap of neighbouring windows, a multiple of 8 with 2 x overlap <= tile; 0 is allowed;
+	                                        * -1 = auto (default): a quarter of the tile, rounded down to a multiple of 8 */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 

@@ -409,6 +409,22 @@ int mlsd_copy_slice2(float* dst, int dw, int dh, const float* src, int sw, int s
 enum { MLSD_RESAMPLE_NEAREST = 0, MLSD_RESAMPLE_BILINEAR = 1, MLSD_RESAMPLE_BICUBIC = 2 };
 enum { MLSD_RESAMPLE_MAX_EXTENT = 1 << 22 };
 int mlsd_resample2d(const float* src, int sw, int sh, float* dst, int dw, int dh, int planes, int mode, int wrap, void* stream);
+/* Tiled diffusion (MultiDiffusion; not in the reference): the canvas latent is evaluated in overlapping windows of the UNet plan's size, the windows'
+ * outputs are blended by a weighted average.  Window pixel (v, u) of a ww x wh window that starts at (x0, y0) lies on canvas pixel
+ * ((y0 + v) mod H, (x0 + u) mod W): a window may straddle the seam of a wrapped axis; on an axis that does not wrap the caller keeps x0 + ww <= W.
+ * Its weight is r_y(v) r_x(u), r(i) = min(i + 1, T - i, O + 1) / (O + 1) with the window's extent T and the overlap O of that axis (fp32 from integers).
+ * All three return -1 before any launch for non-positive extents, a window larger than the canvas, a start outside the canvas, 2^31 elements or more,
+ * or buffers that overlap.
+ *   gather: win [planes][wh][ww] <- canvas [planes][H][W] (NCHW fp32), a copy of the bits.
+ *   blend:  eps_canvas[n][q][c] += (w(v, u) / wsum[q]) * eps_win[n][v ww + u][c] for the first C = 4 channels of eps_win NHWC [N][wh ww][ld_win]; eps_canvas NHWC
+ *           [N][H W][4] dense (16-byte aligned), wsum [H W].  No atomics: a window touches a canvas pixel once, the windows of one evaluation are blended by
+ *           successive launches on one stream into a canvas zeroed before the first.
+ *   wsum:   wsum[q] = sum of the weights of the nx x ny windows (starts xs, ys: HOST arrays, at most MLSD_WINDOW_MAX_AXIS each) that cover q, y outer. */
+enum { MLSD_WINDOW_MAX_AXIS = 64 };
+int mlsd_window_gather(const float* canvas, int W, int H, float* win, int ww, int wh, int x0, int y0, int planes, void* stream);
+int mlsd_window_blend(const float* eps_win, int64_t ld_win, float* eps_canvas, const float* wsum, int W, int H, int ww, int wh,
+                      int x0, int y0, int ox, int oy, int N, int C, void* stream);
+int mlsd_window_wsum(float* wsum, int W, int H, int ww, int wh, const int* xs, int nx, const int* ys, int ny, int ox, int oy, void* stream);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

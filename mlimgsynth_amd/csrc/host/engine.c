@@ -75,6 +75,13 @@ struct MLIS_AmdCtx {
 	MLCtx *dect_ctx, *enct_ctx;
 	MLTensor *t_lat_dect, *t_img_enct;
 	float *d_lat_tile, *d_img_tile, *d_imgin_tile, *d_mom_tile, *d_mom;
+	/* tiled diffusion (mlis_amd_create_tiled): the UNet plan has the size of one window, lw x lh above is the canvas */
+	int n_win;                  /* windows per evaluation; 0: the plan takes the whole latent */
+	int win_w, win_h, win_ox, win_oy;       /* window extent and overlap per axis, latent pixels */
+	int tile_px, tile_overlap_px;           /* as asked for (pixels, square): infotext, engine key */
+	int n_win_x, n_win_y, *win_xs, *win_ys; /* starts per axis (mlis_amd_window_starts); window j = (xs[j % n_win_x], ys[j / n_win_x]) */
+	float *d_eps_canvas;        /* blended UNet output NHWC [N][hw][4] */
+	float *d_wsum;              /* [hw] sum of the blend weights of the windows covering a pixel */
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -90,6 +97,7 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	if (S->enct_ctx) mlctx_destroy(S->enct_ctx);
 	mlsd_free(S->d_lat_tile); mlsd_free(S->d_img_tile); mlsd_free(S->d_imgin_tile); mlsd_free(S->d_mom_tile); mlsd_free(S->d_mom);
 	mlsd_free(S->d_xin); mlsd_free(S->d_xsave);
+	mlsd_free(S->d_eps_canvas); mlsd_free(S->d_wsum); free(S->win_xs); free(S->win_ys);
 	mlsd_free(S->d_x); mlsd_free(S->d_dx); mlsd_free(S->d_x0); mlsd_free(S->d_lmask); mlsd_free(S->d_img); mlsd_free(S->d_img_in);
 	for (int i=0;i<N_TMP;++i) mlsd_free(S->d_tmp[i]);
 	mlsd_free(S->d_cin); mlsd_free(S->d_noise); mlsd_free(S->d_nan);
@@ -135,8 +143,68 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream) { 
 
 MLB_API int mlis_amd_tiling(const MLIS_AmdCtx* S) { return S ? S->tiling : 0; }
 
-MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream)
+MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream) { return mlis_amd_create_tiled(cfg, tiling, 0, 0, 0, stream); }
+
+/* ------------------------------------------------------------------ tiled diffusion: window geometry
+ * Starts of the windows along one axis: canvas extent L, window extent T, minimum overlap O (latent pixels), wrap != 0 if the canvas tiles along the axis.
+ *   T >= L          one window at 0 (its extent is L)
+ *   T < L, no wrap  n = ceil((L - O) / (T - O)), starts[i] = floor(i (L - T) / (n - 1)): the first touches 0, the last touches L, the rest are spread evenly
+ *   T < L, wrap     n = ceil(L / (T - O)), starts[i] = floor(i L / n): a ring, window i covers (starts[i] + k) mod L for k < T, one of them straddles the seam
+ * Neighbours are at most T - O apart, so they share at least O pixels.  Returns n, or -1 for O < 0, 2 O > T, T < 1, L < 1 or n > cap. */
+MLB_API int mlis_amd_window_starts(int L, int T, int O, int wrap, int* starts, int cap)
 {
+	if (!starts || O < 0 || T < 1 || L < 1 || 2 * (long)O > T) return -1;
+	const long step = T - O;
+	const long n = T >= L ? 1 : (wrap ? (L + step - 1) / step : (L - O + step - 1) / step);
+	if (n > cap) return -1;
+	for (long i=0; i<n; ++i) starts[i] = n == 1 ? 0 : (int)(wrap ? i * L / n : i * (L - T) / (n - 1));
+	return (int)n;
+}
+
+/* the windows of a tiled engine: lists per axis, the weight-sum plane, the blended output */
+static int windows_init(MLIS_AmdCtx* S, int tile_lw, int tile_lh, int overlap)
+{
+	int xs[MLSD_WINDOW_MAX_AXIS], ys[MLSD_WINDOW_MAX_AXIS];
+	const int nx = mlis_amd_window_starts(S->lw, tile_lw, overlap, S->tiling & 1, xs, MLSD_WINDOW_MAX_AXIS);
+	const int ny = mlis_amd_window_starts(S->lh, tile_lh, overlap, S->tiling & 2, ys, MLSD_WINDOW_MAX_AXIS);
+	if (nx < 1 || ny < 1) return mlsd_set_error(-1, "tiled diffusion: no window layout for a %dx%d latent with %dx%d windows, overlap %d (2 x overlap <= window, at most %d windows per axis)",
+		S->lw, S->lh, tile_lw, tile_lh, overlap, MLSD_WINDOW_MAX_AXIS);
+	S->win_w = tile_lw < S->lw ? tile_lw : S->lw; S->win_h = tile_lh < S->lh ? tile_lh : S->lh;
+	S->win_ox = S->win_oy = overlap;
+	S->n_win_x = nx; S->n_win_y = ny; S->n_win = nx * ny;
+	S->win_xs = (int*)malloc(sizeof(int) * (size_t)nx); S->win_ys = (int*)malloc(sizeof(int) * (size_t)ny);
+	if (!S->win_xs || !S->win_ys) return fail("out of memory");
+	memcpy(S->win_xs, xs, sizeof(int) * (size_t)nx); memcpy(S->win_ys, ys, sizeof(int) * (size_t)ny);
+	if (mlsd_malloc((void**)&S->d_eps_canvas, (size_t)S->N * S->hw * 4 * 4) || mlsd_malloc((void**)&S->d_wsum, (size_t)S->hw * 4)) return -1;
+	if (mlsd_window_wsum(S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, xs, nx, ys, ny, S->win_ox, S->win_oy, S->stream)) return -1;
+	return 1;
+}
+
+MLB_API int mlis_amd_tile_info(const MLIS_AmdCtx* S, int* n_win, int* win_w, int* win_h)
+{	/* windows per evaluation (0: not tiled) and their size in latent pixels (not tiled: the latent's) */
+	if (!S) return -1;
+	if (n_win) *n_win = S->n_win;
+	if (win_w) *win_w = S->n_win ? S->win_w : S->lw;
+	if (win_h) *win_h = S->n_win ? S->win_h : S->lh;
+	return 1;
+}
+
+MLB_API int mlis_amd_tile_windows(const MLIS_AmdCtx* S, int* xs, int* ys, int cap)
+{	/* start of every window in evaluation order (row-major, y outer), latent pixels; returns their count, -1 if cap is too small */
+	if (!S || S->n_win > cap) return -1;
+	for (int j=0; j<S->n_win; ++j) { if (xs) xs[j] = S->win_xs[j % S->n_win_x]; if (ys) ys[j] = S->win_ys[j / S->n_win_x]; }
+	return S->n_win;
+}
+
+/* Tiled diffusion (MultiDiffusion): cfg->width x height is the CANVAS -- sampler state, noise, mask, decoder and encoder have its size -- and the UNet plan is built
+ * for one window of min(tile, canvas) per axis.  Every evaluation runs the plan on each window and blends the outputs (unet_eval).  tile_w, tile_h, overlap in
+ * pixels (multiples of 8, 2 x overlap <= tile); a tile of 0, or one that covers the canvas on both axes, gives the plain engine of mlis_amd_create_ex. */
+MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream)
+{
+	const int tiled = tile_w > 0 && tile_h > 0 && (tile_w < cfg->width || tile_h < cfg->height);
+	if (tiled && (tile_w % 8 || tile_h % 8 || overlap < 0 || overlap % 8 || 2 * overlap > tile_w || 2 * overlap > tile_h)) {
+		mlsd_set_error(-1, "tiled diffusion: tile %dx%d, overlap %d: multiples of 8 with 2 x overlap <= tile", tile_w, tile_h, overlap); return NULL;
+	}
 	if (tiling < 0 || tiling > 3) { mlsd_set_error(-1, "tiling mode %d: 0 none, 1 x, 2 y, 3 xy", tiling); return NULL; }
 	MLIS_AmdCtx *S = (MLIS_AmdCtx*)calloc(1, sizeof(*S));
 	if (!S) { fail("out of memory"); return NULL; }
@@ -180,14 +248,24 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, v
 	if (mlsd_malloc((void**)&S->d_cin, B*4)) goto err;
 	if (mlsd_malloc((void**)&S->d_nan, 256)) goto err;
 	if (ensure_steps(S, ns) < 0) goto err;
+	/* tiled: the plan takes one window.  It wraps only along an axis its window spans; elsewhere the ring of windows carries the wrap and a window edge pads with zeros */
+	int ulw = S->lw, ulh = S->lh, unet_wrap = S->tiling;
+	if (tiled) {
+		S->tile_px = tile_w; S->tile_overlap_px = overlap;
+		if (windows_init(S, tile_w / S->vae_p.f_down, tile_h / S->vae_p.f_down, overlap / S->vae_p.f_down) < 0) goto err;
+		ulw = S->win_w; ulh = S->win_h;
+		unet_wrap = S->tiling & ((ulw == S->lw ? 1 : 0) | (ulh == S->lh ? 2 : 0));
+		mlsd_free(S->d_xin); S->d_xin = NULL;
+		if (mlsd_malloc((void**)&S->d_xin, (size_t)B * 4 * ulw * ulh * 4)) goto err;
+	}
 
 	/* ---- UNet plan, x bound to the resident evaluation point (c_in scaling + cond/uncond duplication in the gather) */
 	S->unet_ctx = mlctx_new(stream);
-	mlctx_set_conv_wrap(S->unet_ctx, S->tiling);
+	mlctx_set_conv_wrap(S->unet_ctx, unet_wrap);
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
-	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, S->lw, S->lh, N, S->c.n_ctx_tok) < 0) goto err;
+	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, N, S->c.n_ctx_tok) < 0) goto err;
 	if (mlctx_input_bind(S->unet.t_x, S->d_xin, B, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
 	if (unet_denoise_build(&S->unet) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
@@ -456,26 +534,77 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 	/* the same timestep for every row and the same c_in for every image: written by a kernel from its arguments.  (As two 64-byte copies they queued behind the copy
 	 * engine's current job -- with streamed weights a 500 MB upload: 10 ms gaps in front of 4 of 20 evaluations, MLSD_ENGINE_TRACE.) */
 	if (mlsd_fill2_f32(d_t_in, N, t, S->d_cin, B, c_in, st)) return -1;
+	int64_t ld = 0;
+	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
+	if (S->n_win) {
+		/* tiled diffusion: the plan runs on every window of the canvas, window j of every image in one evaluation; the raw outputs are blended into d_eps_canvas by
+		 * successive launches in window order (a fixed summation order).  Exact, not an approximation: the CFG mix and the v-prediction rescale that follow are
+		 * affine in eps with coefficients that depend only on sigma and on x_eval at the same pixel. */
+		const int whw = S->win_w * S->win_h;
+		mlsd_event_record(S->ev[S->i_eval][0], st);
+		if (mlsd_memset(S->d_eps_canvas, 0, (size_t)N * S->hw * 4 * 4, st)) return -1;
+		for (int j=0; j<S->n_win; ++j) {
+			const int x0 = S->win_xs[j % S->n_win_x], y0 = S->win_ys[j / S->n_win_x];
+			if (mlsd_window_gather(x_eval, S->lw, S->lh, S->d_xin, S->win_w, S->win_h, x0, y0, B*4, st)) return -1;
+			if (mlctx_compute(S->unet_ctx) < 0) return -1;
+			if (mlsd_window_blend(eps, ld, S->d_eps_canvas, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, x0, y0, S->win_ox, S->win_oy, N, 4, st)) return -1;
+			if (mlsd_count_nonfinite(eps, (size_t)N*whw*ld, S->d_nan, st)) return -1;
+			if (j == 0 && prefetch_upto >= 0 && !noise_gen(S, prefetch_upto)) return -1;
+		}
+		mlsd_event_record(S->ev[S->i_eval][1], st);
+		S->i_eval++;
+		S->last_nfe += N / B;
+		return 1;
+	}
 	if (x_eval != S->d_xin && mlsd_memcpy(S->d_xin, x_eval, (size_t)B*4*S->hw*4, 2, st)) return -1;
 	mlsd_event_record(S->ev[S->i_eval][0], st);
 	if (mlctx_compute(S->unet_ctx) < 0) return -1;               /* cond + uncond of all images: one evaluation */
 	mlsd_event_record(S->ev[S->i_eval][1], st);
 	S->i_eval++;
 	S->last_nfe += N / B;
-	int64_t ld = 0;
-	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
 	if (mlsd_count_nonfinite(eps, (size_t)N*S->hw*ld, S->d_nan, st)) return -1;   /* ltensor_finite_check, unet.c:487 */
 	if (prefetch_upto >= 0 && !noise_gen(S, prefetch_upto)) return -1;
 	return 1;
+}
+
+/* the UNet output the solvers read, NHWC [2B|B][hw][*ld]: the plan's result tensor, or the blend of the windows' */
+static const float* eps_get(MLIS_AmdCtx* S, int64_t* ld)
+{
+	if (S->n_win) { *ld = 4; return S->d_eps_canvas; }
+	return mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, ld);
 }
 
 /* dx = CFG mix (+ v-param rescale) of the evaluation just enqueued */
 static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* dx)
 {
 	int64_t ld = 0;
-	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
+	const float *eps = eps_get(S, &ld);
 	const float c_skip = sigma / (sigma*sigma + 1), c_out = 1 / sqrt(sigma*sigma + 1);   /* unet.c:491-492 */
 	return mlsd_dxdt_cfg(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
+}
+
+/* one evaluation for tests and tools: x host [B][4][lh][lw] -> dx = dxdt(x, sigma) host, through the very unet_eval + dxdt_finish the denoising loop uses (plain
+ * and tiled engines alike).  The latent of the engine is left alone. */
+MLB_API int mlis_amd_dxdt(MLIS_AmdCtx* S, const float* x_host, float sigma, float* dx_host)
+{
+	if (!S || !x_host || !dx_host || !(sigma >= 0)) return fail("mlis_amd_dxdt: bad argument");
+	if (!S->cond_set) return fail("mlis_amd_dxdt: conditioning not set");
+	const size_t nb = (size_t)S->B * 4 * S->hw * 4;
+	void *st = S->stream;
+	for (int attempt=0; ; ++attempt) {
+		S->i_eval = 0; S->last_nfe = 0;
+		if (mlsd_memset(S->d_nan, 0, 4, st) || mlsd_memcpy(S->d_tmp[0], x_host, nb, 0, st)) return -1;
+		if (unet_eval(S, S->d_tmp[0], sigma, -1) < 0 || dxdt_finish(S, S->d_tmp[0], sigma, S->d_dx) < 0) return -1;
+		int32_t nan_count = 0;
+		if (mlsd_memcpy(dx_host, S->d_dx, nb, 1, st) || mlsd_memcpy(&nan_count, S->d_nan, 4, 1, st) || mlsd_stream_sync(st)) return -1;
+		if (mlctx_handoff_check(S->unet_ctx) < 0) {      /* as mlis_amd_denoise: once more on the hand-off-free plan */
+			if (attempt) return -1;
+			mlctx_handoffs_off(S->unet_ctx); S->n_handoff_retries++;
+			continue;
+		}
+		if (nan_count) return mlsd_set_error(-7 /* MLIS_E_NAN */, "NaN found in UNet output (%d values)", nan_count);
+		return 1;
+	}
 }
 
 static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted)
@@ -543,7 +672,7 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 			if (unet_eval(S, S->d_x, t0, k_prefetch) < 0) return -1;
 			if (!P->vparam) {   /* fused: CFG mix, x += dx*dt and the ancestral noise of sampling.c:170-172 in one launch */
 				int64_t ld = 0;
-				const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
+				const float *eps = eps_get(S, &ld);
 				const float *nz = anc_noise ? noise_draw(S, S->k_draw) : NULL;
 				if (anc_noise && !nz) return -1;
 				if (mlsd_euler_cfg_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, t1 - t0, nz, s_up, st)) return -1;
@@ -940,7 +1069,7 @@ MLB_API int mlis_amd_info(MLIS_AmdCtx* S, double* unet_flops, double* dec_flops,
 {
 	MLCtxInfo a, b;
 	mlctx_info(S->unet_ctx, &a); mlctx_info(S->dec_ctx, &b);
-	if (unet_flops) *unet_flops = a.flops;
+	if (unet_flops) *unet_flops = a.flops * (S->n_win ? S->n_win : 1);     /* per evaluation of the whole latent */
 	if (dec_flops) *dec_flops = b.flops;
 	if (unet_ops) *unet_ops = (int)a.n_ops;
 	if (mem_params) *mem_params = a.mem_params + b.mem_params;

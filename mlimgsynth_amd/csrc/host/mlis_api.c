@@ -41,6 +41,8 @@ struct MLIS_Ctx {
 	int model_type, width, height, n_batch, clip_skip, vae_tile, n_thread, dump_flags, flags, tuflags, wtype;
 	int tiling;             /* MLIS_OPT_AMD_TILING: 0 none, 1 x, 2 y, 3 xy */
 	float hires_scale, hires_denoise; int hires_steps, hires_upscaler;      /* MLIS_OPT_AMD_HIRES_*: the two-pass generation of mlis_generate */
+	int unet_tile, unet_tile_overlap;       /* MLIS_OPT_AMD_UNET_TILE*: tiled diffusion, pixels; 0 = off, overlap -1 = auto */
+	int tiled_tile, tiled_overlap;          /* of the last generation, if one of its passes was tiled (infotext) */
 	float cfg_scale;
 	int method, sched, n_step;
 	float f_t_ini, f_t_end, s_noise, s_ancestral;
@@ -133,8 +135,10 @@ MLB_API MLIS_LogLvl mlis_loglvl_fromz(const char* s) { for (int i=0;i<COUNTOF(k_
 static const char* const k_option_amd[] = { "tiling", "hires_scale", "hires_denoise", "hires_steps", "hires_upscaler" };   /* ids from MLIS_OPT_AMD_TILING */
 static const char* const k_tiling[] = { "none", "x", "y", "xy" };
 static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
+static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };            /* ids from MLIS_OPT_AMD_UNET_TILE */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_UNET_TILE && x < MLIS_OPT_AMD_UNET_TILE + COUNTOF(k_option_amd2)) return k_option_amd2[x - MLIS_OPT_AMD_UNET_TILE];
 	if (x >= MLIS_OPT_AMD_TILING && x < MLIS_OPT_AMD_TILING + COUNTOF(k_option_amd)) return k_option_amd[x - MLIS_OPT_AMD_TILING];
 	return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???";
 }
@@ -142,6 +146,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 {
 	const int i = from_list(k_option_amd, COUNTOF(k_option_amd), 1, s, strlen(s));
 	if (i >= 0) return (MLIS_Option)(MLIS_OPT_AMD_TILING + i);
+	const int i2 = from_list(k_option_amd2, COUNTOF(k_option_amd2), 1, s, strlen(s));
+	if (i2 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE + i2);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -202,6 +208,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->cfg_scale = 7;
 	S->f_t_ini = 1;
 	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
+	S->unet_tile_overlap = -1;
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -520,6 +527,8 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (i < 0 || i >= COUNTOF(k_resample)) BAD_VALUE;
 		S->hires_upscaler = i;
 		break;
+	case MLIS_OPT_AMD_UNET_TILE: if (!arg_int(A, 0, 65535, 0, &i) || i % 8) BAD_VALUE; S->unet_tile = i; break;     /* 0: off; the relation to the overlap is checked when an engine is needed (unet_tile_check) */
+	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: if (!arg_int(A, -1, 65535, -1, &i) || (i > 0 && i % 8)) BAD_VALUE; S->unet_tile_overlap = i; break;      /* -1: auto */
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -583,6 +592,8 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_HIRES_DENOISE: { float *p = va_arg(ap, float*); if (p) *p = S->hires_denoise; } break;
 	case MLIS_OPT_AMD_HIRES_STEPS: { int *p = va_arg(ap, int*); if (p) *p = S->hires_steps; } break;
 	case MLIS_OPT_AMD_HIRES_UPSCALER: { int *p = va_arg(ap, int*); if (p) *p = S->hires_upscaler; } break;
+	case MLIS_OPT_AMD_UNET_TILE: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile; } break;
+	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_overlap; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -890,12 +901,25 @@ static int sampler_defaults(MLIS_Ctx* S, int* n_step, int* method, int* sched)
 
 /* the engine for (model, size, batch, guidance on/off, codec), built when none of the two resident ones has that key: the context keeps the
  * engine used last (S->eng) and the one used before it; a third key takes the place of the latter */
+/* tiled diffusion: the overlap in effect (auto: a quarter of the tile, rounded down to a multiple of 8), and the refusal of a pair the windows cannot be laid out with */
+static int unet_tile_overlap_eff(const MLIS_Ctx* S) { return S->unet_tile_overlap >= 0 ? S->unet_tile_overlap : S->unet_tile / 4 / 8 * 8; }
+static int unet_tile_check(MLIS_Ctx* S)
+{
+	if (S->unet_tile > 0 && 2 * unet_tile_overlap_eff(S) > S->unet_tile)
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid unet_tile_overlap %d for unet_tile %d: neighbouring windows can share at most half a tile", unet_tile_overlap_eff(S), S->unet_tile);
+	return 1;
+}
+
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
 	const int ctx_tok = S->ctx_tok > 0 ? S->ctx_tok : 77;
+	if (unet_tile_check(S) < 0) return MLIS_E_OPT_VALUE;
+	/* a size that fits in the tile on both axes gets the plain engine under the plain key: the first pass of a hires generation shares it with untiled use */
+	const int tile = (S->unet_tile > 0 && (S->unet_tile < lw * f || S->unet_tile < lh * f)) ? S->unet_tile : 0, overlap = tile ? unet_tile_overlap_eff(S) : 0;
 	char key[96];
-	snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
+	int nk = snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
+	if (tile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/u%do%d", tile, overlap);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	if ((!S->eng || strcmp(key, S->eng_key)) && S->eng2 && !strcmp(key, S->eng2_key)) {      /* the other resident engine: they change places */
@@ -915,7 +939,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		S->eng = mlis_amd_create_ex(&c, S->tiling, NULL);
+		S->eng = mlis_amd_create_tiled(&c, S->tiling, tile, tile, overlap, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
@@ -1244,6 +1268,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (S->tiling) ADD(", Tiling: %s", k_tiling[S->tiling]);
 	if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
 		k_resample[S->hires_upscaler], S->hires_denoise);
+	if (S->tiled_tile) ADD(", Tiled diffusion: %d, Tile overlap: %d", S->tiled_tile, S->tiled_overlap);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1286,7 +1311,12 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 			return api_error(S, MLIS_E_UNKNOWN, "conditioning lengths differ: cond %d, ncond %d tokens", T, S->ncond.n[1]);
 		S->ctx_tok = T;
 	}
-	if (engine_get(S, w, h) < 0) return -1;
+	if ((r = engine_get(S, w, h)) < 0) return r;
+	{	/* tiled diffusion: did this pass run in windows (infotext) */
+		int n_win = 0;
+		mlis_amd_tile_info(S->eng, &n_win, NULL, NULL);
+		if (n_win) { S->tiled_tile = S->unet_tile; S->tiled_overlap = unet_tile_overlap_eff(S); }
+	}
 	if (S->tuflags & MLIS_TUF_LATENT) {
 		if (S->latent.n[2] != 4) return api_error(S, MLIS_E_UNKNOWN, "latent must have 4 channels");
 		const size_t per = (size_t)4*w*h;
@@ -1367,6 +1397,8 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
 	if ((r = tiling_check(S)) < 0) return r;
+	if ((r = unet_tile_check(S)) < 0) return r;
+	S->tiled_tile = S->tiled_overlap = 0;
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	int w_img = 0, h_img = 0, hires_n_step = 0;
 	const int decode = !(S->flags & CF_NO_DECODE);

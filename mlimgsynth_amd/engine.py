@@ -255,6 +255,12 @@ def _proto2():
     l.mlis_amd_create.argtypes = [ctypes.POINTER(AmdConfig), vp]
     l.mlis_amd_create_ex.restype = vp
     l.mlis_amd_create_ex.argtypes = [ctypes.POINTER(AmdConfig), c_int, vp]
+    l.mlis_amd_create_tiled.restype = vp
+    l.mlis_amd_create_tiled.argtypes = [ctypes.POINTER(AmdConfig), c_int, c_int, c_int, c_int, vp]
+    l.mlis_amd_window_starts.argtypes = [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]
+    l.mlis_amd_tile_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    l.mlis_amd_tile_windows.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int]
+    l.mlis_amd_dxdt.argtypes = [vp, FP, c_f, FP]
     l.mlis_amd_tiling.restype = c_int
     l.mlis_amd_tiling.argtypes = [vp]
     l.mlis_amd_destroy.argtypes = [vp]
@@ -362,12 +368,16 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0, n_ctx_tok=77, tiling=0):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, tiling=0):
         l = _proto2()
         self.cfg = AmdConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
                              int(defer_weights), int(unet_split), int(n_ctx_tok))    # n_ctx_tok: context rows, 77 x W (windowed prompt)
-        self.h = l.mlis_amd_create_ex(ctypes.byref(self.cfg), int(tiling), vp(stream))    # tiling: 0 none, 1 x, 2 y, 3 xy (seamless)
+        if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h)
+            tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)
+            self.h = l.mlis_amd_create_tiled(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), vp(stream))
+        else:
+            self.h = l.mlis_amd_create_ex(ctypes.byref(self.cfg), int(tiling), vp(stream))    # tiling: 0 none, 1 x, 2 y, 3 xy (seamless)
         if not self.h:
             from ._lib import MlsdError, last_error
             raise MlsdError("mlis_amd_create failed: " + last_error())
@@ -407,6 +417,28 @@ class Generator:
 
     def last_n_step(self):
         return _proto2().mlis_amd_last_n_step(self.h)
+
+    def dxdt(self, x, sigma):
+        """mlis_amd_dxdt: one evaluation at x [B][4][lh][lw], sigma -> dx (UNet + CFG mix, as a solver stage sees it)"""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.shape != (self.B, 4, self.h_px // 8, self.w // 8):
+            raise ValueError(f"latent of shape {x.shape}, the engine takes {(self.B, 4, self.h_px // 8, self.w // 8)}")
+        dx = np.empty_like(x)
+        check1(_proto2().mlis_amd_dxdt(self.h, fptr(x), float(sigma), fptr(dx)), "mlis_amd_dxdt")
+        return dx
+
+    def tile_info(self):
+        """(windows per evaluation -- 0 when not tiled --, window width, window height) in latent pixels"""
+        n, w, h = c_int(), c_int(), c_int()
+        check1(_proto2().mlis_amd_tile_info(self.h, ctypes.byref(n), ctypes.byref(w), ctypes.byref(h)), "mlis_amd_tile_info")
+        return n.value, w.value, h.value
+
+    def tile_windows(self):
+        """[(x0, y0)] of every window in evaluation order, latent pixels"""
+        n = self.tile_info()[0]
+        xs, ys = (c_int * max(n, 1))(), (c_int * max(n, 1))()
+        check1(_proto2().mlis_amd_tile_windows(self.h, xs, ys, n), "mlis_amd_tile_windows")
+        return [(xs[i], ys[i]) for i in range(n)]
 
     def generate(self, seeds, want_latents=True, want_images=True):
         seeds = (c_u64 * self.B)(*[int(s) for s in seeds]) if seeds is not None else None

@@ -110,5 +110,31 @@ def resample2d(src, sw, sh, dst, dw, dh, planes, mode, wrap=0, stream=None):
     check(lib().mlsd_resample2d(vp(src), sw, sh, vp(dst), dw, dh, planes, mode, wrap, vp(stream)), "mlsd_resample2d")
 
 
+WINDOW_MAX_AXIS = 64
+
+
+def window_gather(canvas, W, H, win, ww, wh, x0, y0, planes, stream=None):
+    """mlsd_window_gather: win [planes][wh][ww] <- canvas [planes][H][W] at ((y0 + v) mod H, (x0 + u) mod W), a copy of the bits (device pointers)."""
+    check(lib().mlsd_window_gather(vp(canvas), W, H, vp(win), ww, wh, x0, y0, planes, vp(stream)), "mlsd_window_gather")
+
+
+def window_blend(eps_win, ld_win, eps_canvas, wsum, W, H, ww, wh, x0, y0, ox, oy, N, C=4, stream=None):
+    """mlsd_window_blend: eps_canvas [N][H W][4] += (w / wsum) * eps_win [N][wh ww][ld_win] (first 4 channels) of one window (device pointers)."""
+    check(lib().mlsd_window_blend(vp(eps_win), c_i64(ld_win), vp(eps_canvas), vp(wsum), W, H, ww, wh, x0, y0, ox, oy, N, C, vp(stream)), "mlsd_window_blend")
+
+
+def window_wsum(wsum, W, H, ww, wh, xs, ys, ox, oy, stream=None):
+    """mlsd_window_wsum: wsum [H W] (device) = sum of the blend weights of the windows starting at xs x ys (host lists)."""
+    ax, ay = (c_int * len(xs))(*xs), (c_int * len(ys))(*ys)
+    check(lib().mlsd_window_wsum(vp(wsum), W, H, ww, wh, ax, len(xs), ay, len(ys), ox, oy, vp(stream)), "mlsd_window_wsum")
+
+
+def window_starts(L, T, O, wrap=False, cap=256):
+    """mlis_amd_window_starts: the window starts along one axis (canvas extent L, window T, minimum overlap O, in latent pixels), or None if refused."""
+    out = (c_int * cap)()
+    n = lib().mlis_amd_window_starts(int(L), int(T), int(O), int(bool(wrap)), out, cap)
+    return None if n < 0 else [out[i] for i in range(n)]
+
+
 def sync():
     check(lib().mlsd_device_sync(), "sync")

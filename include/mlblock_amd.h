@@ -170,6 +170,8 @@ void mlctx_info(const MLCtx* C, MLCtxInfo* out);
 /* per-op listing for profiling: returns kernel label, flops of op i */
 int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flops);
 const struct mlsd_gemm_args* mlctx_op_gemm_args(const MLCtx* C, int i);   /* op i's launch arguments if it is a GEMM / convolution, else NULL */
+const struct mlsd_attn_args* mlctx_op_attn_args(const MLCtx* C, int i);   /* op i's launch arguments if it is an attention launch (mlsd_attention or mlsd_attention_ctx), else NULL */
+int mlctx_op_attn_is_ctx(const MLCtx* C, int i);   /* 1 if op i is an attention launch that runs on mlsd_attention_ctx */
 /* algorithmic HBM bytes of op i (operands read once, outputs written once) */
 double mlctx_op_bytes(const MLCtx* C, int i);
 /* time every op individually with HIP events (diagnostics; synchronises) */

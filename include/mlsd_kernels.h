@@ -287,6 +287,15 @@ int mlsd_attention(const mlsd_attn_args* a, void* stream);
  * ldq / ldk / ldv and their batch strides multiples of 8; out 8-byte aligned with ldo and bso multiples of 4.
  * Outside that range: an error.  mlsd_attention's dispatch is not affected. */
 int mlsd_attention_ctx(const mlsd_attn_args* a, void* stream);
+/* The kernel instantiation mlsd_attention (ctx = 0) or mlsd_attention_ctx (ctx = 1) would launch for these arguments under the current switches, from the
+ * route the launch itself switches on; NULL where the launch would refuse (mlsd_gemm_variant's counterpart; the string is valid until the thread's next call):
+ *   attn<tile,dD[,causal][,mfmasum]>   attn_kernel<D>, the 64-key tile loop (mfmasum: mlsd_attention_vsum(0))
+ *   attn<tk96,dD[,w4]>                 attn_tk96_kernel<D>, Tk <= 96 in one pass (w4: mlsd_attention_tk96(2, .))
+ *   attn<64x2[,mfmasum]>               attn64x2_kernel, d_head 64, 64 query rows per wave
+ *   attn<64x2s,dD>                     attn64x2s_kernel<D>, software-pipelined, D = 64 or 40
+ *   attn<ctx,dD,resident|slot>         attn_ctx_kernel<D>, 96 < Tk <= 320
+ *   attn<pp,Rrows,wW>                  attn64pp_kernel (EXPERIMENTS builds), R query rows per wave */
+const char* mlsd_attention_variant(const mlsd_attn_args* a, int ctx);
 int mlsd_attention_ctx_takes(const mlsd_attn_args* a);   /* 1 where the plan runs a Tk > 96 cross attention on mlsd_attention_ctx (measured not slower than mlsd_attention) */
 void mlsd_attention_ctx_mode(int mode);    /* A-B timing: 0 (default) = keys resident in LDS where they take <= 64 KiB, else one 96-key slot restaged per group; 1 = the slot always */
 /* diagnostics / A-B timing: 1 = the d_head 64 problems also run on the general kernel instead of the 64-rows-per-wave one */

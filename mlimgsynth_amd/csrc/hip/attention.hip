@@ -1609,6 +1609,7 @@ int g_attn_pp = 0;          // ping-pong kernel for d_head 64 (measured: parity 
 #endif
 int g_attn_tk96 = 1;        // Tk <= 96 without a causal mask: the one-pass kernel (0 = the general kernels; A/B timing)
 int g_attn_tk96_qb = 0;     // query blocks of 128 rows per workgroup (0 = by the launch size)
+int g_attn_ctx_mode = 0;    // mlsd_attention_ctx: 0 = all keys resident in LDS where they take <= 64 KiB (2 workgroups per CU), else one restaged 96-key slot; 1 = the slot always (A/B timing)
 int g_attn_vsum = 1;        // row sums on the VALU (v_pk_add_f32) instead of ones.P MFMAs: +4..7 % on the SDXL shapes (tools/attn_bench.py); 0 = matrix-pipe sums
 
 // the AttnP fields every launcher fills alike; each launcher sets nq, sc, causal and tbuf
@@ -1631,30 +1632,120 @@ bool attn_sp_takes(const mlsd_attn_args* a)
            (long)a->Tk * a->ldk < (1L << 30) && (long)a->Tk * a->ldv < (1L << 30) && !(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) && !((a->ldq | a->ldk | a->ldv) & 7);
 }
 
-int launch_attn64x2(const mlsd_attn_args* a, hipStream_t st)
+// What one mlsd_attention / mlsd_attention_ctx call runs, decided once by attn_resolve(): the launch switches on it and mlsd_attention_variant
+// prints it, so that neither holds a copy of the rules.
+enum AttnFam { AF_REFUSED = 0, AF_TILE, AF_TK96, AF_X2, AF_X2S, AF_CTX, AF_PP };
+struct AttnRoute {
+    AttnFam fam;        // AF_TILE attn_kernel, AF_TK96 attn_tk96_kernel, AF_X2 attn64x2_kernel, AF_X2S attn64x2s_kernel, AF_CTX attn_ctx_kernel, AF_PP attn64pp_kernel
+    int dh;             // the d_head instantiation = the caller's d_head (AF_X2 is reached at d_head 64 only)
+    bool causal;        // AF_TILE
+    bool vsum;          // AF_TILE, AF_X2: the VSUM instantiation (false and unread elsewhere)
+    int wps;            // AF_TK96, AF_CTX, AF_PP: the waves-per-SIMD template argument
+    bool res;           // AF_CTX: the keys resident in LDS (else one restaged 96-key slot)
+    int nb;             // AF_PP: 32-row query blocks per wave
+    char why[112];      // AF_REFUSED: the error the launch reports
+};
+constexpr int tk96_wps(int dh) { return dh <= 80 ? 3 : 2; }
+constexpr int ctx_wps(int dh) { return dh == 64 || dh == 80 ? 3 : 2; }     // (d 40 at 3 waves per SIMD: 20 bytes of scratch)
+
+#define ATTN_REFUSE(...) do { snprintf(r.why, sizeof(r.why), __VA_ARGS__); return r; } while (0)
+AttnRoute attn_resolve(const mlsd_attn_args* a, int ctx)
+{
+    AttnRoute r = {};
+    const char* fn = ctx ? "mlsd_attention_ctx" : "mlsd_attention";
+    if (!a || !a->q || !a->k || !a->v || !a->out) ATTN_REFUSE("%s: null operand", fn);
+    if (a->Tq <= 0 || (!ctx && a->Tk <= 0) || a->n_batch <= 0 || a->n_head <= 0) ATTN_REFUSE("%s: empty problem", fn);
+    r.dh = a->d_head;
+    if (ctx) {
+        if (a->Tk <= 96 || a->Tk > 320) ATTN_REFUSE("%s: Tk %d outside 97..320", fn, a->Tk);
+        if (a->causal) ATTN_REFUSE("%s: no causal mask", fn);
+        if ((a->ldq & 7) || (a->ldk & 7) || (a->ldv & 7) || (a->ldo & 3)) ATTN_REFUSE("%s: strides must be multiples of 8", fn);
+        if ((a->bsq & 7) || (a->bsk & 7) || (a->bsv & 7) || (a->bso & 3) || (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) || ((uintptr_t)a->out & 7))
+            ATTN_REFUSE("%s: misaligned operand", fn);
+        if (r.dh != 32 && r.dh != 40 && r.dh != 64 && r.dh != 80 && r.dh != 160) ATTN_REFUSE("%s: unsupported d_head %d (supported: 32,40,64,80,160)", fn, a->d_head);
+        const int dqk = (a->d_head + 15) / 16 * 16, ndv = (a->d_head + 31) / 32;
+        const long rowb = dqk * 2 + 16 + ((ndv & 1) ? ndv : ndv + 1) * 64;
+        r.fam = AF_CTX; r.wps = ctx_wps(r.dh);
+        r.res = !(g_attn_ctx_mode == 1 || (long)((a->Tk + 31) & ~31) * rowb > 65536);      /* (d_head 160: ceil32(Tk) x 656 B > 64 KiB for every Tk > 96: never resident) */
+        return r;
+    }
+    if ((a->ldq & 7) || (a->ldk & 7) || (a->ldv & 7) || (a->ldo & 3)) ATTN_REFUSE("%s: strides must be multiples of 8", fn);
+    if (g_attn_tk96 && !a->causal && a->Tk <= 96 && (r.dh == 40 || r.dh == 64 || r.dh == 80 || r.dh == 160)) {
+        r.fam = AF_TK96; r.wps = (r.dh == 64 && g_attn_tk96 == 2) ? 4 : tk96_wps(r.dh);
+        return r;
+    }
+    switch (a->d_head) {
+    case 32: case 80: case 160: break;
+    case 40:
+        if (!g_attn_force_old && attn_sp_takes(a)) { r.fam = AF_X2S; return r; }      // round 6: SD1.5's 4096-token level on the software-pipelined kernel, run as d = 64
+        break;
+    case 64:
+#ifdef MLSD_GEMM_EXPERIMENTS
+        if (g_attn_pp && !g_attn_force_old && !a->causal && !(a->Tq & 255) && !(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) &&
+            (long)a->Tk * a->ldk < (1L << 30) && (long)a->Tk * a->ldv < (1L << 30)) {
+            const bool big = !(a->Tq & 511) && a->Tq >= 2048;
+            r.fam = AF_PP;
+            if (g_attn_pp == 3 ? !(a->Tq & 511) : (g_attn_pp == 1 && big)) { r.nb = 2; r.wps = 2; }
+            else if (g_attn_pp == 4) { r.nb = 1; r.wps = 2; }
+            else { r.nb = 1; r.wps = 4; }
+            return r;
+        }
+#endif
+        // every q/k/v row must be 16-byte aligned for the LDS-DMA pieces (strides are multiples of 8 halfs: checked above)
+        if (!g_attn_force_old && !a->causal && (a->Tq >= g_attn_x2_min_tq || attn_sp_takes(a)) && !(a->Tq & 255) &&
+            !(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15)) {
+            if (attn_sp_takes(a)) r.fam = AF_X2S;      // (whole key tiles: the software-pipelined form)
+            else { r.fam = AF_X2; r.vsum = g_attn_vsum != 0; }
+            return r;
+        }
+        break;
+    default: ATTN_REFUSE("%s: unsupported d_head %d (supported: 32,40,64,80,160)", fn, a->d_head);
+    }
+    r.fam = AF_TILE; r.causal = a->causal != 0; r.vsum = g_attn_vsum != 0;
+    return r;
+}
+#undef ATTN_REFUSE
+
+// the label of a route (mlsd_kernels.h: mlsd_attention_variant), NULL for a refused launch
+const char* attn_label(const AttnRoute& r)
+{
+    static thread_local char buf[48];
+    switch (r.fam) {
+    case AF_TILE: snprintf(buf, sizeof(buf), "attn<tile,d%d%s%s>", r.dh, r.causal ? ",causal" : "", r.vsum ? "" : ",mfmasum"); break;
+    case AF_TK96: snprintf(buf, sizeof(buf), "attn<tk96,d%d%s>", r.dh, r.wps != tk96_wps(r.dh) ? ",w4" : ""); break;
+    case AF_X2: snprintf(buf, sizeof(buf), "attn<64x2%s>", r.vsum ? "" : ",mfmasum"); break;
+    case AF_X2S: snprintf(buf, sizeof(buf), "attn<64x2s,d%d>", r.dh); break;
+    case AF_CTX: snprintf(buf, sizeof(buf), "attn<ctx,d%d,%s>", r.dh, r.res ? "resident" : "slot"); break;
+    case AF_PP: snprintf(buf, sizeof(buf), "attn<pp,%drows,w%d>", 32 * r.nb, r.wps); break;
+    default: return nullptr;
+    }
+    return buf;
+}
+
+int launch_attn64x2(const mlsd_attn_args* a, const AttnRoute& r, hipStream_t st)
 {
     AttnP p = attn_params(a); p.causal = 0; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt(64.0));
     p.nq = a->Tq / 256;
     const dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * p.nq));
-    if (attn_sp_takes(a)) {      // whole key tiles: the software-pipelined form
-        if (a->d_head == 40) { p.sc = (float)(1.4426950408889634 / sqrt(40.0)); hipLaunchKernelGGL(attn64x2s_kernel<40>, grid, dim3(256), 0, st, p); }
+    if (r.fam == AF_X2S) {      // whole key tiles: the software-pipelined form
+        if (r.dh == 40) { p.sc = (float)(1.4426950408889634 / sqrt(40.0)); hipLaunchKernelGGL(attn64x2s_kernel<40>, grid, dim3(256), 0, st, p); }
         else hipLaunchKernelGGL(attn64x2s_kernel<64>, grid, dim3(256), 0, st, p);
         return mlsd_check_launch("attn64x2s_kernel");
     }
-    if (g_attn_vsum) hipLaunchKernelGGL(attn64x2_kernel<true>, grid, dim3(256), 0, st, p);
+    if (r.vsum) hipLaunchKernelGGL(attn64x2_kernel<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(attn64x2_kernel<false>, grid, dim3(256), 0, st, p);
     return mlsd_check_launch("attn64x2_kernel");
 }
 
 template <int DH>
-int launch_attn(const mlsd_attn_args* a, hipStream_t st)
+int launch_attn(const mlsd_attn_args* a, const AttnRoute& r, hipStream_t st)
 {
-    AttnP p = attn_params(a); p.causal = a->causal; p.tbuf = nullptr;
+    AttnP p = attn_params(a); p.causal = r.causal; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
     p.nq = (a->Tq + 127) / 128;
     const dim3 grid((unsigned)(8 * ((p.G + 7) / 8) * p.nq));
-    if (g_attn_vsum) hipLaunchKernelGGL((attn_kernel<DH, true>), grid, dim3(256), 0, st, p);
+    if (r.vsum) hipLaunchKernelGGL((attn_kernel<DH, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_kernel<DH, false>), grid, dim3(256), 0, st, p);
     return mlsd_check_launch("attn_kernel");
 }
@@ -1678,7 +1769,7 @@ int launch_attn64pp(const mlsd_attn_args* a, hipStream_t st)
 #endif
 
 template <int DH>
-int launch_attn_tk96(const mlsd_attn_args* a, hipStream_t st)
+int launch_attn_tk96(const mlsd_attn_args* a, const AttnRoute& r, hipStream_t st)
 {
     AttnP p = attn_params(a); p.causal = 0; p.tbuf = nullptr;
     p.sc = (float)(1.4426950408889634 / sqrt((double)a->d_head));
@@ -1689,13 +1780,12 @@ int launch_attn_tk96(const mlsd_attn_args* a, hipStream_t st)
     if (QB <= 0) { QB = 8; while (QB > 1 && (long)G8 * ((nblk128 + QB - 1) / QB) < 512) QB >>= 1; }
     p.nq = (nblk128 + QB - 1) / QB;
     const dim3 grid((unsigned)(G8 * p.nq));
-    if (DH == 64 && g_attn_tk96 == 2) hipLaunchKernelGGL((attn_tk96_kernel<DH, (DH == 64 ? 4 : 2)>), grid, dim3(256), 0, st, p, QB);   // (A/B: 127 registers + 2 spilled)
-    else hipLaunchKernelGGL((attn_tk96_kernel<DH, (DH <= 80 ? 3 : 2)>), grid, dim3(256), 0, st, p, QB);
+    if (DH == 64 && r.wps == 4) hipLaunchKernelGGL((attn_tk96_kernel<DH, (DH == 64 ? 4 : 2)>), grid, dim3(256), 0, st, p, QB);   // (A/B: 127 registers + 2 spilled)
+    else hipLaunchKernelGGL((attn_tk96_kernel<DH, tk96_wps(DH)>), grid, dim3(256), 0, st, p, QB);
     return mlsd_check_launch("attn_tk96_kernel");
 }
 
 // 96 < Tk <= 320 (mlsd_attention_ctx): attn_ctx_kernel, workgroups as launch_attn_tk96 chooses them
-int g_attn_ctx_mode = 0;    // mlsd_attention_ctx: 0 = all keys resident in LDS where they take <= 64 KiB (2 workgroups per CU), else one restaged 96-key slot; 1 = the slot always (A/B timing)
 // (profiles/long_prompt_kernels.txt: resident at 105 KiB -- d 64, 308 keys, one workgroup per CU -- was 1.45 x the slot's time)
 
 template <int DH, bool RES>
@@ -1711,7 +1801,7 @@ int launch_attn_ctx(const mlsd_attn_args* a, hipStream_t st)
     p.nq = (nblk128 + QB - 1) / QB;
     const dim3 grid((unsigned)(G8 * p.nq));
     const size_t lds = (size_t)(RES ? (a->Tk + 31) & ~31 : 96) * ROWB;
-    auto kfn = attn_ctx_kernel<DH, (DH == 64 || DH == 80 ? 3 : 2), RES>;     // (d 40 at 3 waves per SIMD: 20 bytes of scratch)
+    auto kfn = attn_ctx_kernel<DH, ctx_wps(DH), RES>;
     static bool lds_set = false;        // the largest key set (320 rows) once per instantiation
     if (!lds_set) { MLSD_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((RES ? 320 : 96) * ROWB))); lds_set = true; }
     hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, p, QB);
@@ -1724,66 +1814,53 @@ extern "C" {
 
 MLSD_API int mlsd_attention(const mlsd_attn_args* a, void* stream)
 {
-    if (!a || !a->q || !a->k || !a->v || !a->out) return mlsd_set_error(-1, "mlsd_attention: null operand");
-    if (a->Tq <= 0 || a->Tk <= 0 || a->n_batch <= 0 || a->n_head <= 0) return mlsd_set_error(-1, "mlsd_attention: empty problem");
-    if ((a->ldq & 7) || (a->ldk & 7) || (a->ldv & 7) || (a->ldo & 3)) return mlsd_set_error(-1, "mlsd_attention: strides must be multiples of 8");
+    const AttnRoute r = attn_resolve(a, 0);
+    if (r.fam == AF_REFUSED) return mlsd_set_error(-1, "%s", r.why);
+    if (mlsd_runtime_is_dry()) return mlsd_check_launch(attn_label(r));      // the dry runtime's buffers are host memory: refuse before the launch
     hipStream_t st = (hipStream_t)stream;
-    if (g_attn_tk96 && !a->causal && a->Tk <= 96) {
-        switch (a->d_head) {
-        case 40: return launch_attn_tk96<40>(a, st);
-        case 64: return launch_attn_tk96<64>(a, st);
-        case 80: return launch_attn_tk96<80>(a, st);
-        case 160: return launch_attn_tk96<160>(a, st);
-        default: break;
+    switch (r.fam) {
+    case AF_TK96:
+        switch (r.dh) {
+        case 40: return launch_attn_tk96<40>(a, r, st);
+        case 64: return launch_attn_tk96<64>(a, r, st);
+        case 80: return launch_attn_tk96<80>(a, r, st);
+        default: return launch_attn_tk96<160>(a, r, st);
         }
-    }
-    switch (a->d_head) {
-    case 32: return launch_attn<32>(a, st);
-    case 40:
-        if (!g_attn_force_old && attn_sp_takes(a)) return launch_attn64x2(a, st);      // round 6: SD1.5's 4096-token level on the software-pipelined kernel, run as d = 64
-        return launch_attn<40>(a, st);
-    case 64:
+    case AF_X2: case AF_X2S: return launch_attn64x2(a, r, st);
 #ifdef MLSD_GEMM_EXPERIMENTS
-        if (g_attn_pp && !g_attn_force_old && !a->causal && !(a->Tq & 255) && !(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) &&
-            (long)a->Tk * a->ldk < (1L << 30) && (long)a->Tk * a->ldv < (1L << 30)) {
-            const bool big = !(a->Tq & 511) && a->Tq >= 2048;
-            if (g_attn_pp == 3 ? !(a->Tq & 511) : (g_attn_pp == 1 && big)) return launch_attn64pp<2, 2>(a, st);
-            if (g_attn_pp == 4) return launch_attn64pp<1, 2>(a, st);
-            return launch_attn64pp<1, 4>(a, st);
-        }
+    case AF_PP:
+        if (r.nb == 2) return launch_attn64pp<2, 2>(a, st);
+        if (r.wps == 2) return launch_attn64pp<1, 2>(a, st);
+        return launch_attn64pp<1, 4>(a, st);
 #endif
-        // every q/k/v row must be 16-byte aligned for the LDS-DMA pieces (strides are multiples of 8 halfs: checked above)
-        if (!g_attn_force_old && !a->causal && (a->Tq >= g_attn_x2_min_tq || attn_sp_takes(a)) && !(a->Tq & 255) &&
-            !(((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15)) return launch_attn64x2(a, st);
-        return launch_attn<64>(a, st);
-    case 80: return launch_attn<80>(a, st);
-    case 160: return launch_attn<160>(a, st);
-    default: return mlsd_set_error(-1, "mlsd_attention: unsupported d_head %d (supported: 32,40,64,80,160)", a->d_head);
+    default:
+        switch (r.dh) {
+        case 32: return launch_attn<32>(a, r, st);
+        case 40: return launch_attn<40>(a, r, st);
+        case 64: return launch_attn<64>(a, r, st);
+        case 80: return launch_attn<80>(a, r, st);
+        default: return launch_attn<160>(a, r, st);
+        }
     }
 }
 
 MLSD_API int mlsd_attention_ctx(const mlsd_attn_args* a, void* stream)
 {
-    if (!a || !a->q || !a->k || !a->v || !a->out) return mlsd_set_error(-1, "mlsd_attention_ctx: null operand");
-    if (a->Tq <= 0 || a->n_batch <= 0 || a->n_head <= 0) return mlsd_set_error(-1, "mlsd_attention_ctx: empty problem");
-    if (a->Tk <= 96 || a->Tk > 320) return mlsd_set_error(-1, "mlsd_attention_ctx: Tk %d outside 97..320", a->Tk);
-    if (a->causal) return mlsd_set_error(-1, "mlsd_attention_ctx: no causal mask");
-    if ((a->ldq & 7) || (a->ldk & 7) || (a->ldv & 7) || (a->ldo & 3)) return mlsd_set_error(-1, "mlsd_attention_ctx: strides must be multiples of 8");
-    if ((a->bsq & 7) || (a->bsk & 7) || (a->bsv & 7) || (a->bso & 3) || (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) || ((uintptr_t)a->out & 7))
-        return mlsd_set_error(-1, "mlsd_attention_ctx: misaligned operand");
+    const AttnRoute r = attn_resolve(a, 1);
+    if (r.fam == AF_REFUSED) return mlsd_set_error(-1, "%s", r.why);
+    if (mlsd_runtime_is_dry()) return mlsd_check_launch(attn_label(r));
     hipStream_t st = (hipStream_t)stream;
-    const int dqk = (a->d_head + 15) / 16 * 16, ndv = (a->d_head + 31) / 32;
-    const long rowb = dqk * 2 + 16 + ((ndv & 1) ? ndv : ndv + 1) * 64;
-    const bool slot = g_attn_ctx_mode == 1 || (long)((a->Tk + 31) & ~31) * rowb > 65536;
-    switch (a->d_head) {
-    case 32: return slot ? launch_attn_ctx<32, false>(a, st) : launch_attn_ctx<32, true>(a, st);      /* (the test models' towers) */
-    case 40: return slot ? launch_attn_ctx<40, false>(a, st) : launch_attn_ctx<40, true>(a, st);
-    case 64: return slot ? launch_attn_ctx<64, false>(a, st) : launch_attn_ctx<64, true>(a, st);
-    case 80: return slot ? launch_attn_ctx<80, false>(a, st) : launch_attn_ctx<80, true>(a, st);
-    case 160: return launch_attn_ctx<160, false>(a, st);      /* (ceil32(Tk) x 656 B > 64 KiB for every Tk > 96) */
-    default: return mlsd_set_error(-1, "mlsd_attention_ctx: unsupported d_head %d (supported: 32,40,64,80,160)", a->d_head);
+    switch (r.dh) {
+    case 32: return r.res ? launch_attn_ctx<32, true>(a, st) : launch_attn_ctx<32, false>(a, st);      /* (the test models' towers) */
+    case 40: return r.res ? launch_attn_ctx<40, true>(a, st) : launch_attn_ctx<40, false>(a, st);
+    case 64: return r.res ? launch_attn_ctx<64, true>(a, st) : launch_attn_ctx<64, false>(a, st);
+    case 80: return r.res ? launch_attn_ctx<80, true>(a, st) : launch_attn_ctx<80, false>(a, st);
+    default: return launch_attn_ctx<160, false>(a, st);      /* (never resident: attn_resolve) */
     }
 }
+
+/* the kernel instantiation mlsd_attention (ctx = 0) or mlsd_attention_ctx (ctx = 1) would launch for these arguments under the current switches, NULL where it would refuse */
+MLSD_API const char* mlsd_attention_variant(const mlsd_attn_args* a, int ctx) { return attn_label(attn_resolve(a, ctx)); }
 
 MLSD_API void mlsd_attention_ctx_mode(int mode) { g_attn_ctx_mode = mode == 1; }
 /* the plan's choice for a cross attention over Tk > 96 context rows: mlsd_attention_ctx where it measured at least even with the

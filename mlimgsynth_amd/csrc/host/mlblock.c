@@ -1646,6 +1646,15 @@ MLB_API const mlsd_gemm_args* mlctx_op_gemm_args(const MLCtx* C, int i)
 	return &C->ops[i].u.gemm;
 }
 
+/* the launch arguments of op i if it is an attention launch (mlsd_attention, or mlsd_attention_ctx where mlctx_op_attn_is_ctx says so), else NULL */
+MLB_API const mlsd_attn_args* mlctx_op_attn_args(const MLCtx* C, int i)
+{
+	if (!C || i < 0 || i >= C->n_ops || (C->ops[i].kind != OP_ATTN && C->ops[i].kind != OP_ATTN_CTX)) return NULL;
+	return &C->ops[i].u.attn;
+}
+
+MLB_API int mlctx_op_attn_is_ctx(const MLCtx* C, int i) { return C && i >= 0 && i < C->n_ops && C->ops[i].kind == OP_ATTN_CTX; }
+
 MLB_API int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flops)
 {
 	if (i < 0 || i >= C->n_ops) return -1;

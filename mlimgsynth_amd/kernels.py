@@ -81,6 +81,15 @@ def gemm_route(args):
     return r
 
 
+def attention_variant(args, ctx=False):
+    """mlsd_attention_variant: the label of the kernel mlsd_attention (or, with ctx, mlsd_attention_ctx) would launch; None where it would refuse."""
+    f = lib().mlsd_attention_variant
+    f.restype = ctypes.c_char_p
+    f.argtypes = [ctypes.POINTER(AttnArgs), c_int]
+    lab = f(ctypes.byref(args), int(bool(ctx)))
+    return lab.decode() if lab is not None else None
+
+
 def attention(args, stream=None):
     check(lib().mlsd_attention(ctypes.byref(args), vp(stream)), "mlsd_attention")
 

@@ -304,8 +304,17 @@ int mlis_amd_tiling(const MLIS_AmdCtx* S);
  * -- window j of every image of the batch in one evaluation -- and blends the raw outputs by a weighted average (mlsd_window_blend) before the CFG mix; the solvers
  * never notice.  tile_w, tile_h, overlap in pixels: multiples of 8, 2 x overlap <= tile.  tile 0, or a tile that covers the canvas on both axes: mlis_amd_create_ex.
  * With `tiling`, the plan's convolutions wrap only along an axis its window spans; along the others the windows form a ring and one straddles the seam.
- * use_hipgraph and unet_split work (with unet_split every window streams the weights again). */
+ * use_hipgraph and unet_split work (with unet_split every plan evaluation streams the weights again).
+ * _packed: up to `pack` (1 .. MLSD_WINDOW_MAX_PACK = 16) windows of one evaluation run as ONE plan evaluation.  With the effective pack P of mlis_amd_tile_pack the
+ * UNet plan is that of a plain engine for P x n_batch images with the shared prompt (activation memory included), the windows are evaluated in groups of P in their
+ * order, the unused slots of a short last group repeat its last window, and the blend is the one of P = 1 bit for bit given the same plan outputs.  Everything else
+ * -- sampler state, noise, RNG streams, codecs, callback, NFE count -- keeps the canvas batch.  mlis_amd_create_tiled is pack = 1. */
 MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream);
+MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, void* stream);
+/* the pack rule (pure): P0 = min(pack, n_win, 16, 64 / n_batch), *n_eval = ceil(n_win / P0) plan evaluations per UNet evaluation, returns P = ceil(n_win / *n_eval);
+ * -1 for pack, n_win or n_batch below 1.  _info: the values of an engine; a plain engine reports 0, 1. */
+int mlis_amd_tile_pack(int n_win, int n_batch, int pack, int* n_eval);
+int mlis_amd_tile_pack_info(const MLIS_AmdCtx* S, int* pack, int* n_eval);
 /* window starts along one axis: canvas extent L, window extent T, minimum overlap O (latent pixels), wrap != 0: the canvas tiles along the axis.  T >= L: one window
  * at 0.  Else n = ceil((L - O) / (T - O)) windows at floor(i (L - T) / (n - 1)), or on a wrapped axis n = ceil(L / (T - O)) at floor(i L / n), window i covering
  * (starts[i] + k) mod L.  Returns n; -1 for O < 0, 2 O > T, T < 1, L < 1 or n > cap. */

@@ -61,8 +61,11 @@ typedef enum {
 	/* tiled diffusion (MultiDiffusion): a pass whose size exceeds the tile on an axis evaluates the UNet in overlapping windows of the tile's size and blends their
 	 * outputs; a pass that fits runs as ever (the first pass of a hires generation, typically).  Both persist across generations.  (A block of its own from 111.) */
 	MLIS_OPT_AMD_UNET_TILE = 111,          /* "unet_tile" (int, pixels): 0 = off (default), else a multiple of 8 -- the size the model was trained at: 512 SD1, 1024 SDXL */
-	MLIS_OPT_AMD_UNET_TILE_OVERLAP = 112   /* "unet_tile_overlap" (int, pixels): minimum overlap of neighbouring windows, a multiple of 8 with 2 x overlap <= tile; 0 is allowed;
+	MLIS_OPT_AMD_UNET_TILE_OVERLAP = 112,  /* "unet_tile_overlap" (int, pixels): minimum overlap of neighbouring windows, a multiple of 8 with 2 x overlap <= tile; 0 is allowed;
 	                                        * -1 = auto (default): a quarter of the tile, rounded down to a multiple of 8 */
+	/* packed windows: up to this many windows of a tiled pass run as one batched UNet evaluation (the effective count: mlis_amd_tile_pack).  Persists across
+	 * generations; costs the activation memory of a plan for that many windows x the batch.  (A block of its own from 121.) */
+	MLIS_OPT_AMD_UNET_TILE_BATCH = 121     /* "unet_tile_batch" (int): 1 .. 16, default 1 = one window per evaluation */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 

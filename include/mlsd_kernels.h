@@ -434,6 +434,17 @@ int mlsd_window_gather(const float* canvas, int W, int H, float* win, int ww, in
 int mlsd_window_blend(const float* eps_win, int64_t ld_win, float* eps_canvas, const float* wsum, int W, int H, int ww, int wh,
                       int x0, int y0, int ox, int oy, int N, int C, void* stream);
 int mlsd_window_wsum(float* wsum, int W, int H, int ww, int wh, const int* xs, int nx, const int* ys, int ny, int ox, int oy, void* stream);
+/* The same for the P windows of one batched plan evaluation (mlis_amd_tile_pack), one launch each.  xs, ys: HOST arrays of n_slots window starts, slot order.
+ *   gather_packed: win [n_slots][planes][wh][ww] <- for slot s, canvas [planes][H][W] at ((ys[s] + v) mod H, (xs[s] + u) mod W), a copy of the bits.
+ *   blend_packed:  eps_win is the packed plan's output, NHWC [G][n_slots][B][wh ww][ld_win] (G = 2 with guidance: cond of every slot, then uncond of every slot),
+ *                  eps_canvas [G][B][H W][4] dense.  Slots 0 .. n_used-1 are blended, slots n_used .. n_slots-1 are never read.  One thread per canvas pixel walks
+ *                  the slots in order, so the canvas holds, bit for bit, what n_used successive mlsd_window_blend launches in slot order leave.
+ * Both refuse, before any launch, what the single-window entry points refuse, n_slots outside 1 .. MLSD_WINDOW_MAX_PACK, n_used outside 1 .. n_slots, B < 1,
+ * G not 1 or 2, C != 4, 2^31 elements or more, and overlapping buffers. */
+enum { MLSD_WINDOW_MAX_PACK = 16 };
+int mlsd_window_gather_packed(const float* canvas, int W, int H, float* win, int ww, int wh, const int* xs, const int* ys, int n_slots, int planes, void* stream);
+int mlsd_window_blend_packed(const float* eps_win, int64_t ld_win, float* eps_canvas, const float* wsum, int W, int H, int ww, int wh, const int* xs, const int* ys,
+                             int n_used, int n_slots, int ox, int oy, int B, int G, int C, void* stream);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

@@ -321,7 +321,7 @@ static const char k_usage[] =
 "Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic\n"
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
-"             --unet-tile PX   --unet-tile-overlap PX\n"
+"             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";

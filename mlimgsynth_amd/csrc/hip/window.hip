@@ -4,6 +4,11 @@
 //   gather  reads a canvas row segment and writes a window row, both contiguous along the wave (a wrapped window splits the read in two);
 //   blend   reads the window's first four channels (NHWC with the plan's row stride: 16 bytes of every ld_win * 4) and updates one float4 of the dense canvas;
 //   wsum    walks the window lists of both axes per canvas pixel (a handful of windows: registers and the constant arguments only).
+// The packed pair (mlsd_window_gather_packed / _blend_packed) serves the P windows of one batched plan evaluation per launch; it is what the engine calls, P = 1
+// included, and the single-window pair stays exported as the statement the packed blend is tested against.  The windows of a group overlap, so
+// the packed blend runs one thread per CANVAS pixel that walks the group's windows in slot order: no two threads touch the same float4, the summation order is
+// the one of successive single-window launches, and the canvas is read and written once per group.  The gather takes its slot from blockIdx.y, so that the
+// index into the by-value start lists is uniform over a wave (scalar loads of the kernel arguments, no private copy of the lists).
 // The blend weight is a product of two integer ramps divided in fp32; blend and wsum compute it with the same function, so that where one window
 // covers a pixel w / wsum is exactly 1.
 #include <hip/hip_runtime.h>
@@ -82,6 +87,56 @@ __global__ void window_wsum_kernel(float* __restrict__ wsum, int W, int H, int w
     }
 }
 
+struct WindowSlots { int xs[MLSD_WINDOW_MAX_PACK], ys[MLSD_WINDOW_MAX_PACK]; };
+
+// win [n_slots][planes][wh][ww]: blockIdx.y is the slot, the x grid loops over one slot's planes * wh * ww elements
+__global__ void window_gather_packed_kernel(const uint32_t* __restrict__ canvas, int W, int H, uint32_t* __restrict__ win, int ww, int wh, WindowSlots L, int planes)
+{
+    const int s = (int)blockIdx.y;
+    const int x0 = L.xs[s], y0 = L.ys[s];
+    const long total = (long)planes * wh * ww;
+    uint32_t* __restrict__ dst = win + (long)s * total;
+    GRID_LOOP(i, total) {
+        const int u = (int)(i % ww);
+        const long r = i / ww;
+        const int v = (int)(r % wh);
+        const long p = r / wh;
+        dst[i] = canvas[(p * H + wrap_at(y0, v, H)) * W + wrap_at(x0, u, W)];      // bits, not values
+    }
+}
+
+// eps_win NHWC [G][n_slots][B][wh ww][ld_win], eps_canvas [G B][H W] float4.  Thread (n, q): for every slot whose window covers q, in slot order, exactly the
+// update of window_blend_kernel; the float4 is loaded at the first covering window and stored once after the last.
+template <bool VEC>
+__global__ void window_blend_packed_kernel(const float* __restrict__ eps_win, long ld_win, float4* __restrict__ eps_canvas, const float* __restrict__ wsum,
+                                           int W, int H, int ww, int wh, WindowSlots L, int n_used, int n_slots, int ox, int oy, int B, int GB)
+{
+    const long hw = (long)H * W, whw = (long)wh * ww, total = (long)GB * hw;
+    GRID_LOOP(i, total) {
+        const long q = i % hw;
+        const int n = (int)(i / hw), g = n / B, b = n - g * B;
+        const int x = (int)(q % W), y = (int)(q / W);
+        float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+        float ws = 0.f;
+        bool covered = false;
+        for (int s = 0; s < n_used; ++s) {
+            const int v = window_offset(y, L.ys[s], wh, H);
+            if (v < 0) continue;
+            const int u = window_offset(x, L.xs[s], ww, W);
+            if (u < 0) continue;
+            if (!covered) { c = eps_canvas[i]; ws = wsum[q]; covered = true; }
+            const float* src = eps_win + ((((long)g * n_slots + s) * B + b) * whw + (long)v * ww + u) * ld_win;
+            float4 e;
+            if (VEC) e = *reinterpret_cast<const float4*>(src);
+            else e = make_float4(src[0], src[1], src[2], src[3]);
+            const float f = __fdiv_rn(window_weight(u, v, ww, wh, ox, oy), ws);
+            c.x = __fadd_rn(c.x, __fmul_rn(f, e.x)); c.y = __fadd_rn(c.y, __fmul_rn(f, e.y));
+            c.z = __fadd_rn(c.z, __fmul_rn(f, e.z)); c.w = __fadd_rn(c.w, __fmul_rn(f, e.w));
+        }
+        if (covered) eps_canvas[i] = c;
+    }
+}
+
 int window_args_ok(const char* what, int W, int H, int ww, int wh, int x0, int y0)
 {
     if (W < 1 || H < 1 || ww < 1 || wh < 1 || ww > W || wh > H || x0 < 0 || x0 >= W || y0 < 0 || y0 >= H)
@@ -130,4 +185,53 @@ extern "C" MLSD_API int mlsd_window_wsum(float* wsum, int W, int H, int ww, int 
     for (int j = ny; j < MLSD_WINDOW_MAX_AXIS; ++j) L.ys[j] = 0;
     hipLaunchKernelGGL(window_wsum_kernel, dim3(nblk((long)H * W)), dim3(256), 0, (hipStream_t)stream, wsum, W, H, ww, wh, L, nx, ny, ox, oy);
     return mlsd_check_launch("window_wsum");
+}
+
+// the starts of n_slots windows, checked and copied into the by-value lists (unused entries 0)
+static int window_slots_get(const char* what, WindowSlots* L, int W, int H, int ww, int wh, const int* xs, const int* ys, int n_slots)
+{
+    if (!xs || !ys || n_slots < 1 || n_slots > MLSD_WINDOW_MAX_PACK)
+        return mlsd_set_error(-1, "%s: bad argument (%d slots, 1 .. %d)", what, n_slots, MLSD_WINDOW_MAX_PACK);
+    for (int s = 0; s < MLSD_WINDOW_MAX_PACK; ++s) {
+        if (s < n_slots && window_args_ok(what, W, H, ww, wh, xs[s], ys[s])) return -1;
+        L->xs[s] = s < n_slots ? xs[s] : 0; L->ys[s] = s < n_slots ? ys[s] : 0;
+    }
+    return 0;
+}
+
+extern "C" MLSD_API int mlsd_window_gather_packed(const float* canvas, int W, int H, float* win, int ww, int wh, const int* xs, const int* ys, int n_slots,
+                                                  int planes, void* stream)
+{
+    if (!canvas || !win || planes < 1) return mlsd_set_error(-1, "mlsd_window_gather_packed: bad argument (%d planes)", planes);
+    if (window_args_ok("mlsd_window_gather_packed", W, H, ww, wh, 0, 0)) return -1;
+    WindowSlots L;
+    if (window_slots_get("mlsd_window_gather_packed", &L, W, H, ww, wh, xs, ys, n_slots)) return -1;
+    const long n_src = (long)planes * H * W, n_one = (long)planes * wh * ww, n_dst = n_one * n_slots;
+    if (n_src >= (1L << 31) || n_dst >= (1L << 31)) return mlsd_set_error(-1, "mlsd_window_gather_packed: more than 2^31 elements");
+    if (canvas < win + n_dst && win < canvas + n_src) return mlsd_set_error(-1, "mlsd_window_gather_packed: canvas and window overlap");
+    hipLaunchKernelGGL(window_gather_packed_kernel, dim3(nblk(n_one), (unsigned)n_slots), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)canvas, W, H, (uint32_t*)win,
+                       ww, wh, L, planes);
+    return mlsd_check_launch("window_gather_packed");
+}
+
+extern "C" MLSD_API int mlsd_window_blend_packed(const float* eps_win, int64_t ld_win, float* eps_canvas, const float* wsum, int W, int H, int ww, int wh,
+                                                 const int* xs, const int* ys, int n_used, int n_slots, int ox, int oy, int B, int G, int C, void* stream)
+{
+    if (!eps_win || !eps_canvas || !wsum || B < 1 || (G != 1 && G != 2) || C != 4 || ld_win < C || ox < 0 || oy < 0 || ((uintptr_t)eps_canvas & 15))
+        return mlsd_set_error(-1, "mlsd_window_blend_packed: bad argument (B %d, G %d, C %d, ld %lld, overlap %d %d)", B, G, C, (long long)ld_win, ox, oy);
+    if (window_args_ok("mlsd_window_blend_packed", W, H, ww, wh, 0, 0)) return -1;
+    WindowSlots L;
+    if (window_slots_get("mlsd_window_blend_packed", &L, W, H, ww, wh, xs, ys, n_slots)) return -1;
+    if (n_used < 1 || n_used > n_slots) return mlsd_set_error(-1, "mlsd_window_blend_packed: %d used of %d slots", n_used, n_slots);
+    const long n_pix = (long)G * B * H * W, n_can = n_pix * C, n_win = (long)G * n_slots * B * wh * ww;
+    if (n_can >= (1L << 31) || n_win >= (1L << 31) || n_win * ld_win >= (1L << 31)) return mlsd_set_error(-1, "mlsd_window_blend_packed: more than 2^31 elements");
+    if (eps_win < eps_canvas + n_can && eps_canvas < eps_win + n_win * ld_win) return mlsd_set_error(-1, "mlsd_window_blend_packed: window and canvas overlap");
+    if (wsum < eps_canvas + n_can && eps_canvas < wsum + (long)H * W) return mlsd_set_error(-1, "mlsd_window_blend_packed: weight sum and canvas overlap");
+    const bool vec = !(ld_win & 3) && !((uintptr_t)eps_win & 15);
+    const dim3 grid(nblk(n_pix)), block(256);
+    if (vec) hipLaunchKernelGGL(window_blend_packed_kernel<true>, grid, block, 0, (hipStream_t)stream, eps_win, (long)ld_win, (float4*)eps_canvas, wsum, W, H, ww, wh, L,
+                                n_used, n_slots, ox, oy, B, G * B);
+    else hipLaunchKernelGGL(window_blend_packed_kernel<false>, grid, block, 0, (hipStream_t)stream, eps_win, (long)ld_win, (float4*)eps_canvas, wsum, W, H, ww, wh, L,
+                            n_used, n_slots, ox, oy, B, G * B);
+    return mlsd_check_launch("window_blend_packed");
 }

@@ -75,11 +75,13 @@ struct MLIS_AmdCtx {
 	MLCtx *dect_ctx, *enct_ctx;
 	MLTensor *t_lat_dect, *t_img_enct;
 	float *d_lat_tile, *d_img_tile, *d_imgin_tile, *d_mom_tile, *d_mom;
-	/* tiled diffusion (mlis_amd_create_tiled): the UNet plan has the size of one window, lw x lh above is the canvas */
+	/* tiled diffusion (mlis_amd_create_tiled_packed): the UNet plan has the size of one window (times `pack` in the batch), lw x lh above is the canvas */
 	int n_win;                  /* windows per evaluation; 0: the plan takes the whole latent */
 	int win_w, win_h, win_ox, win_oy;       /* window extent and overlap per axis, latent pixels */
 	int tile_px, tile_overlap_px;           /* as asked for (pixels, square): infotext, engine key */
 	int n_win_x, n_win_y, *win_xs, *win_ys; /* starts per axis (mlis_amd_window_starts); window j = (xs[j % n_win_x], ys[j / n_win_x]) */
+	int pack, n_eval;           /* windows per plan evaluation (mlis_amd_tile_pack; 0: not tiled) and plan evaluations per UNet evaluation */
+	int PB, PN;                 /* images and rows of the UNet plan: B and N, times pack when tiled */
 	float *d_eps_canvas;        /* blended UNet output NHWC [N][hw][4] */
 	float *d_wsum;              /* [hw] sum of the blend weights of the windows covering a pixel */
 };
@@ -143,7 +145,11 @@ MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream) { 
 
 MLB_API int mlis_amd_tiling(const MLIS_AmdCtx* S) { return S ? S->tiling : 0; }
 
-MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream) { return mlis_amd_create_tiled(cfg, tiling, 0, 0, 0, stream); }
+MLB_API MLIS_AmdCtx* mlis_amd_create_ex(const MLIS_AmdConfig* cfg, int tiling, void* stream) { return mlis_amd_create_tiled_packed(cfg, tiling, 0, 0, 0, 1, stream); }
+MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream)
+{
+	return mlis_amd_create_tiled_packed(cfg, tiling, tile_w, tile_h, overlap, 1, stream);
+}
 
 /* ------------------------------------------------------------------ tiled diffusion: window geometry
  * Starts of the windows along one axis: canvas extent L, window extent T, minimum overlap O (latent pixels), wrap != 0 if the canvas tiles along the axis.
@@ -159,6 +165,30 @@ MLB_API int mlis_amd_window_starts(int L, int T, int O, int wrap, int* starts, i
 	if (n > cap) return -1;
 	for (long i=0; i<n; ++i) starts[i] = n == 1 ? 0 : (int)(wrap ? i * L / n : i * (L - T) / (n - 1));
 	return (int)n;
+}
+
+/* The pack rule: n_win windows of n_batch images each, at most `pack` windows per plan evaluation.  P0 = min(pack, n_win, MLSD_WINDOW_MAX_PACK, MAX_BATCH / n_batch)
+ * (a packed plan never holds more images than a plain engine may), *n_eval = ceil(n_win / P0) plan evaluations, and the pack returned is ceil(n_win / n_eval): the
+ * smallest plan that reaches that count.  Group g holds windows g P .. min((g + 1) P, n_win) - 1 in evaluation order; only the last can be short.  -1 for an
+ * argument below 1. */
+MLB_API int mlis_amd_tile_pack(int n_win, int n_batch, int pack, int* n_eval)
+{
+	if (pack < 1 || n_win < 1 || n_batch < 1) return -1;
+	int p0 = pack < n_win ? pack : n_win;
+	if (p0 > MLSD_WINDOW_MAX_PACK) p0 = MLSD_WINDOW_MAX_PACK;
+	if (p0 > MAX_BATCH / n_batch) p0 = MAX_BATCH / n_batch;
+	if (p0 < 1) p0 = 1;
+	const int ne = (n_win + p0 - 1) / p0;
+	if (n_eval) *n_eval = ne;
+	return (n_win + ne - 1) / ne;
+}
+
+MLB_API int mlis_amd_tile_pack_info(const MLIS_AmdCtx* S, int* pack, int* n_eval)
+{	/* windows per plan evaluation and plan evaluations per UNet evaluation; a plain engine reports 0, 1 */
+	if (!S) return -1;
+	if (pack) *pack = S->n_win ? S->pack : 0;
+	if (n_eval) *n_eval = S->n_win ? S->n_eval : 1;
+	return 1;
 }
 
 /* the windows of a tiled engine: lists per axis, the weight-sum plane, the blended output */
@@ -197,10 +227,12 @@ MLB_API int mlis_amd_tile_windows(const MLIS_AmdCtx* S, int* xs, int* ys, int ca
 }
 
 /* Tiled diffusion (MultiDiffusion): cfg->width x height is the CANVAS -- sampler state, noise, mask, decoder and encoder have its size -- and the UNet plan is built
- * for one window of min(tile, canvas) per axis.  Every evaluation runs the plan on each window and blends the outputs (unet_eval).  tile_w, tile_h, overlap in
- * pixels (multiples of 8, 2 x overlap <= tile); a tile of 0, or one that covers the canvas on both axes, gives the plain engine of mlis_amd_create_ex. */
-MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream)
+ * for P windows of min(tile, canvas) per axis, P = mlis_amd_tile_pack(windows, n_batch, pack): the plan of a plain engine for P x n_batch images with the shared
+ * prompt.  Every evaluation runs the plan on each group of P windows and blends the outputs (unet_eval).  tile_w, tile_h, overlap in pixels (multiples of 8,
+ * 2 x overlap <= tile); a tile of 0, or one that covers the canvas on both axes, gives the plain engine of mlis_amd_create_ex. */
+MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, void* stream)
 {
+	if (pack < 1 || pack > MLSD_WINDOW_MAX_PACK) { mlsd_set_error(-1, "tiled diffusion: %d windows per evaluation: 1 .. %d", pack, MLSD_WINDOW_MAX_PACK); return NULL; }
 	const int tiled = tile_w > 0 && tile_h > 0 && (tile_w < cfg->width || tile_h < cfg->height);
 	if (tiled && (tile_w % 8 || tile_h % 8 || overlap < 0 || overlap % 8 || 2 * overlap > tile_w || 2 * overlap > tile_h)) {
 		mlsd_set_error(-1, "tiled diffusion: tile %dx%d, overlap %d: multiples of 8 with 2 x overlap <= tile", tile_w, tile_h, overlap); return NULL;
@@ -235,7 +267,8 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling
 	S->lw = S->c.width / S->vae_p.f_down; S->lh = S->c.height / S->vae_p.f_down; S->hw = S->lw * S->lh;
 	S->B = S->c.n_batch;
 	S->N = S->c.cfg_scale > 1 ? 2*S->B : S->B;
-	const int B = S->B, N = S->N, ns = S->c.n_step;
+	S->PB = S->B; S->PN = S->N;
+	const int B = S->B, ns = S->c.n_step;
 	const size_t lat_elems = (size_t)B * 4 * S->hw;
 
 	if (mlsd_malloc((void**)&S->d_x, lat_elems*4)) goto err;
@@ -245,19 +278,21 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling
 	if (mlsd_malloc((void**)&S->d_x0, lat_elems*4)) goto err;
 	if (mlsd_malloc((void**)&S->d_lmask, (size_t)S->hw*4)) goto err;
 	if (mlsd_malloc((void**)&S->d_img, (size_t)B*3*S->c.width*S->c.height*4)) goto err;
-	if (mlsd_malloc((void**)&S->d_cin, B*4)) goto err;
 	if (mlsd_malloc((void**)&S->d_nan, 256)) goto err;
 	if (ensure_steps(S, ns) < 0) goto err;
-	/* tiled: the plan takes one window.  It wraps only along an axis its window spans; elsewhere the ring of windows carries the wrap and a window edge pads with zeros */
+	/* tiled: the plan takes `pack` windows of every image.  It wraps only along an axis its window spans; elsewhere the ring of windows carries the wrap and a window edge pads with zeros */
 	int ulw = S->lw, ulh = S->lh, unet_wrap = S->tiling;
 	if (tiled) {
 		S->tile_px = tile_w; S->tile_overlap_px = overlap;
 		if (windows_init(S, tile_w / S->vae_p.f_down, tile_h / S->vae_p.f_down, overlap / S->vae_p.f_down) < 0) goto err;
 		ulw = S->win_w; ulh = S->win_h;
 		unet_wrap = S->tiling & ((ulw == S->lw ? 1 : 0) | (ulh == S->lh ? 2 : 0));
+		S->pack = mlis_amd_tile_pack(S->n_win, B, pack, &S->n_eval);
+		S->PB = S->pack * B; S->PN = S->pack * S->N;
 		mlsd_free(S->d_xin); S->d_xin = NULL;
-		if (mlsd_malloc((void**)&S->d_xin, (size_t)B * 4 * ulw * ulh * 4)) goto err;
+		if (mlsd_malloc((void**)&S->d_xin, (size_t)S->PB * 4 * ulw * ulh * 4)) goto err;
 	}
+	if (mlsd_malloc((void**)&S->d_cin, (size_t)S->PB*4)) goto err;
 
 	/* ---- UNet plan, x bound to the resident evaluation point (c_in scaling + cond/uncond duplication in the gather) */
 	S->unet_ctx = mlctx_new(stream);
@@ -265,8 +300,8 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
-	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, N, S->c.n_ctx_tok) < 0) goto err;
-	if (mlctx_input_bind(S->unet.t_x, S->d_xin, B, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
+	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
+	if (mlctx_input_bind(S->unet.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
 	if (unet_denoise_build(&S->unet) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
 
@@ -313,10 +348,10 @@ MLB_API int mlis_amd_set_callback(MLIS_AmdCtx* S, mlis_amd_progress_fn fn, void*
 }
 
 static int fill_cond(MLIS_AmdCtx* S, MLTensor* t, const void* a, const void* b, size_t per_bytes, int kind)
-{	/* rows 0..B-1 <- a (cond), rows B..2B-1 <- b (uncond); the shared prompt is replicated per image */
+{	/* rows 0..PB-1 <- a (cond), rows PB..2PB-1 <- b (uncond); the shared prompt is replicated per image (of every window of a packed plan) */
 	char *dst = (char*)mlctx_input_device_ptr(t);
-	for (int n=0; n<S->N; ++n) {
-		const void *src = n < S->B ? a : b;
+	for (int n=0; n<S->PN; ++n) {
+		const void *src = n < S->PB ? a : b;
 		if (!src) return fail("missing (un)conditioning");
 		if (mlsd_memcpy(dst + (size_t)n*per_bytes, src, per_bytes, kind, S->stream)) return -1;
 	}
@@ -349,8 +384,8 @@ MLB_API int mlis_amd_set_cond_device(MLIS_AmdCtx* S, const void* cond, const voi
 MLB_API int mlis_amd_bcast_cond(MLIS_AmdCtx* S, void* comm, int root)
 {
 	const UnetParams *P = &S->unet_p;
-	if (mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_c), (size_t)S->N*S->c.n_ctx_tok*P->n_ctx*4, root, S->stream)) return -1;
-	if (P->ch_adm_in && mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_l), (size_t)S->N*P->ch_adm_in*4, root, S->stream)) return -1;
+	if (mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_c), (size_t)S->PN*S->c.n_ctx_tok*P->n_ctx*4, root, S->stream)) return -1;
+	if (P->ch_adm_in && mlsd_rccl_bcast(comm, mlctx_input_device_ptr(S->unet.t_l), (size_t)S->PN*P->ch_adm_in*4, root, S->stream)) return -1;
 	S->cond_set = 1;
 	return 1;
 }
@@ -533,23 +568,29 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 	float *d_t_in = (float*)mlctx_input_device_ptr(S->unet.t_t);
 	/* the same timestep for every row and the same c_in for every image: written by a kernel from its arguments.  (As two 64-byte copies they queued behind the copy
 	 * engine's current job -- with streamed weights a 500 MB upload: 10 ms gaps in front of 4 of 20 evaluations, MLSD_ENGINE_TRACE.) */
-	if (mlsd_fill2_f32(d_t_in, N, t, S->d_cin, B, c_in, st)) return -1;
+	if (mlsd_fill2_f32(d_t_in, S->PN, t, S->d_cin, S->PB, c_in, st)) return -1;
 	int64_t ld = 0;
 	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
 	if (S->n_win) {
-		/* tiled diffusion: the plan runs on every window of the canvas, window j of every image in one evaluation; the raw outputs are blended into d_eps_canvas by
-		 * successive launches in window order (a fixed summation order).  Exact, not an approximation: the CFG mix and the v-prediction rescale that follow are
-		 * affine in eps with coefficients that depend only on sigma and on x_eval at the same pixel. */
-		const int whw = S->win_w * S->win_h;
+		/* tiled diffusion: the plan runs on every window of the canvas, a group of `pack` windows of every image in one evaluation; the raw outputs are blended into
+		 * d_eps_canvas group after group, and inside a group in slot order (a fixed summation order: that of one launch per window).  The unused slots of a short
+		 * last group repeat its last window -- the plan sees real inputs everywhere -- and the blend skips them.  Exact, not an approximation: the CFG mix and the
+		 * v-prediction rescale that follow are affine in eps with coefficients that depend only on sigma and on x_eval at the same pixel. */
+		const int whw = S->win_w * S->win_h, P = S->pack;
 		mlsd_event_record(S->ev[S->i_eval][0], st);
 		if (mlsd_memset(S->d_eps_canvas, 0, (size_t)N * S->hw * 4 * 4, st)) return -1;
-		for (int j=0; j<S->n_win; ++j) {
-			const int x0 = S->win_xs[j % S->n_win_x], y0 = S->win_ys[j / S->n_win_x];
-			if (mlsd_window_gather(x_eval, S->lw, S->lh, S->d_xin, S->win_w, S->win_h, x0, y0, B*4, st)) return -1;
+		for (int g=0; g<S->n_eval; ++g) {
+			const int n_used = S->n_win - g*P < P ? S->n_win - g*P : P;
+			int xs[MLSD_WINDOW_MAX_PACK], ys[MLSD_WINDOW_MAX_PACK];
+			for (int s=0; s<P; ++s) {
+				const int j = g*P + (s < n_used ? s : n_used - 1);
+				xs[s] = S->win_xs[j % S->n_win_x]; ys[s] = S->win_ys[j / S->n_win_x];
+			}
+			if (mlsd_window_gather_packed(x_eval, S->lw, S->lh, S->d_xin, S->win_w, S->win_h, xs, ys, P, B*4, st)) return -1;
 			if (mlctx_compute(S->unet_ctx) < 0) return -1;
-			if (mlsd_window_blend(eps, ld, S->d_eps_canvas, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, x0, y0, S->win_ox, S->win_oy, N, 4, st)) return -1;
-			if (mlsd_count_nonfinite(eps, (size_t)N*whw*ld, S->d_nan, st)) return -1;
-			if (j == 0 && prefetch_upto >= 0 && !noise_gen(S, prefetch_upto)) return -1;
+			if (mlsd_window_blend_packed(eps, ld, S->d_eps_canvas, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, xs, ys, n_used, P, S->win_ox, S->win_oy, B, N / B, 4, st)) return -1;
+			if (mlsd_count_nonfinite(eps, (size_t)S->PN*whw*ld, S->d_nan, st)) return -1;
+			if (g == 0 && prefetch_upto >= 0 && !noise_gen(S, prefetch_upto)) return -1;
 		}
 		mlsd_event_record(S->ev[S->i_eval][1], st);
 		S->i_eval++;
@@ -1069,7 +1110,7 @@ MLB_API int mlis_amd_info(MLIS_AmdCtx* S, double* unet_flops, double* dec_flops,
 {
 	MLCtxInfo a, b;
 	mlctx_info(S->unet_ctx, &a); mlctx_info(S->dec_ctx, &b);
-	if (unet_flops) *unet_flops = a.flops * (S->n_win ? S->n_win : 1);     /* per evaluation of the whole latent */
+	if (unet_flops) *unet_flops = a.flops * (S->n_win ? S->n_eval : 1);    /* per evaluation of the whole latent: the work done, padded slots of a packed plan included */
 	if (dec_flops) *dec_flops = b.flops;
 	if (unet_ops) *unet_ops = (int)a.n_ops;
 	if (mem_params) *mem_params = a.mem_params + b.mem_params;

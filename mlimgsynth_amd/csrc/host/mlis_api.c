@@ -43,6 +43,7 @@ struct MLIS_Ctx {
 	float hires_scale, hires_denoise; int hires_steps, hires_upscaler;      /* MLIS_OPT_AMD_HIRES_*: the two-pass generation of mlis_generate */
 	int unet_tile, unet_tile_overlap;       /* MLIS_OPT_AMD_UNET_TILE*: tiled diffusion, pixels; 0 = off, overlap -1 = auto */
 	int tiled_tile, tiled_overlap;          /* of the last generation, if one of its passes was tiled (infotext) */
+	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
 	int method, sched, n_step;
 	float f_t_ini, f_t_end, s_noise, s_ancestral;
@@ -136,8 +137,10 @@ static const char* const k_option_amd[] = { "tiling", "hires_scale", "hires_deno
 static const char* const k_tiling[] = { "none", "x", "y", "xy" };
 static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
 static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };            /* ids from MLIS_OPT_AMD_UNET_TILE */
+static const char* const k_option_amd3[] = { "unet_tile_batch" };                           /* ids from MLIS_OPT_AMD_UNET_TILE_BATCH */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_UNET_TILE_BATCH && x < MLIS_OPT_AMD_UNET_TILE_BATCH + COUNTOF(k_option_amd3)) return k_option_amd3[x - MLIS_OPT_AMD_UNET_TILE_BATCH];
 	if (x >= MLIS_OPT_AMD_UNET_TILE && x < MLIS_OPT_AMD_UNET_TILE + COUNTOF(k_option_amd2)) return k_option_amd2[x - MLIS_OPT_AMD_UNET_TILE];
 	if (x >= MLIS_OPT_AMD_TILING && x < MLIS_OPT_AMD_TILING + COUNTOF(k_option_amd)) return k_option_amd[x - MLIS_OPT_AMD_TILING];
 	return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???";
@@ -148,6 +151,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i >= 0) return (MLIS_Option)(MLIS_OPT_AMD_TILING + i);
 	const int i2 = from_list(k_option_amd2, COUNTOF(k_option_amd2), 1, s, strlen(s));
 	if (i2 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE + i2);
+	const int i3 = from_list(k_option_amd3, COUNTOF(k_option_amd3), 1, s, strlen(s));
+	if (i3 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE_BATCH + i3);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -209,6 +214,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->f_t_ini = 1;
 	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
 	S->unet_tile_overlap = -1;
+	S->unet_tile_batch = 1;
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -529,6 +535,7 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		break;
 	case MLIS_OPT_AMD_UNET_TILE: if (!arg_int(A, 0, 65535, 0, &i) || i % 8) BAD_VALUE; S->unet_tile = i; break;     /* 0: off; the relation to the overlap is checked when an engine is needed (unet_tile_check) */
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: if (!arg_int(A, -1, 65535, -1, &i) || (i > 0 && i % 8)) BAD_VALUE; S->unet_tile_overlap = i; break;      /* -1: auto */
+	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -594,6 +601,7 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_HIRES_UPSCALER: { int *p = va_arg(ap, int*); if (p) *p = S->hires_upscaler; } break;
 	case MLIS_OPT_AMD_UNET_TILE: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile; } break;
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_overlap; } break;
+	case MLIS_OPT_AMD_UNET_TILE_BATCH: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_batch; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -919,7 +927,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	const int tile = (S->unet_tile > 0 && (S->unet_tile < lw * f || S->unet_tile < lh * f)) ? S->unet_tile : 0, overlap = tile ? unet_tile_overlap_eff(S) : 0;
 	char key[96];
 	int nk = snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
-	if (tile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/u%do%d", tile, overlap);
+	if (tile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/u%do%dp%d", tile, overlap, S->unet_tile_batch);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	if ((!S->eng || strcmp(key, S->eng_key)) && S->eng2 && !strcmp(key, S->eng2_key)) {      /* the other resident engine: they change places */
@@ -939,7 +947,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		S->eng = mlis_amd_create_tiled(&c, S->tiling, tile, tile, overlap, NULL);
+		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
@@ -1269,6 +1277,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
 		k_resample[S->hires_upscaler], S->hires_denoise);
 	if (S->tiled_tile) ADD(", Tiled diffusion: %d, Tile overlap: %d", S->tiled_tile, S->tiled_overlap);
+	if (S->tiled_tile && S->tiled_pack > 1) ADD(", Tile batch: %d", S->tiled_pack);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1315,7 +1324,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	{	/* tiled diffusion: did this pass run in windows (infotext) */
 		int n_win = 0;
 		mlis_amd_tile_info(S->eng, &n_win, NULL, NULL);
-		if (n_win) { S->tiled_tile = S->unet_tile; S->tiled_overlap = unet_tile_overlap_eff(S); }
+		if (n_win) { S->tiled_tile = S->unet_tile; S->tiled_overlap = unet_tile_overlap_eff(S); mlis_amd_tile_pack_info(S->eng, &S->tiled_pack, NULL); }
 	}
 	if (S->tuflags & MLIS_TUF_LATENT) {
 		if (S->latent.n[2] != 4) return api_error(S, MLIS_E_UNKNOWN, "latent must have 4 channels");
@@ -1398,7 +1407,7 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
 	if ((r = tiling_check(S)) < 0) return r;
 	if ((r = unet_tile_check(S)) < 0) return r;
-	S->tiled_tile = S->tiled_overlap = 0;
+	S->tiled_tile = S->tiled_overlap = S->tiled_pack = 0;
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	int w_img = 0, h_img = 0, hires_n_step = 0;
 	const int decode = !(S->flags & CF_NO_DECODE);

@@ -257,6 +257,10 @@ def _proto2():
     l.mlis_amd_create_ex.argtypes = [ctypes.POINTER(AmdConfig), c_int, vp]
     l.mlis_amd_create_tiled.restype = vp
     l.mlis_amd_create_tiled.argtypes = [ctypes.POINTER(AmdConfig), c_int, c_int, c_int, c_int, vp]
+    l.mlis_amd_create_tiled_packed.restype = vp
+    l.mlis_amd_create_tiled_packed.argtypes = [ctypes.POINTER(AmdConfig), c_int, c_int, c_int, c_int, c_int, vp]
+    l.mlis_amd_tile_pack.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int)]
+    l.mlis_amd_tile_pack_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_window_starts.argtypes = [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]
     l.mlis_amd_tile_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_tile_windows.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int]
@@ -368,14 +372,14 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, tiling=0):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, tiling=0):
         l = _proto2()
         self.cfg = AmdConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
                              int(defer_weights), int(unet_split), int(n_ctx_tok))    # n_ctx_tok: context rows, 77 x W (windowed prompt)
-        if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h)
-            tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)
-            self.h = l.mlis_amd_create_tiled(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), vp(stream))
+        if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
+            tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)      # times up to unet_tile_batch windows per evaluation
+            self.h = l.mlis_amd_create_tiled_packed(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), vp(stream))
         else:
             self.h = l.mlis_amd_create_ex(ctypes.byref(self.cfg), int(tiling), vp(stream))    # tiling: 0 none, 1 x, 2 y, 3 xy (seamless)
         if not self.h:
@@ -432,6 +436,12 @@ class Generator:
         n, w, h = c_int(), c_int(), c_int()
         check1(_proto2().mlis_amd_tile_info(self.h, ctypes.byref(n), ctypes.byref(w), ctypes.byref(h)), "mlis_amd_tile_info")
         return n.value, w.value, h.value
+
+    def tile_pack_info(self):
+        """(windows per plan evaluation, plan evaluations per UNet evaluation); (0, 1) when not tiled"""
+        p, n = c_int(), c_int()
+        check1(_proto2().mlis_amd_tile_pack_info(self.h, ctypes.byref(p), ctypes.byref(n)), "mlis_amd_tile_pack_info")
+        return p.value, n.value
 
     def tile_windows(self):
         """[(x0, y0)] of every window in evaluation order, latent pixels"""

@@ -138,6 +138,30 @@ def window_wsum(wsum, W, H, ww, wh, xs, ys, ox, oy, stream=None):
     check(lib().mlsd_window_wsum(vp(wsum), W, H, ww, wh, ax, len(xs), ay, len(ys), ox, oy, vp(stream)), "mlsd_window_wsum")
 
 
+WINDOW_MAX_PACK = 16
+
+
+def window_gather_packed(canvas, W, H, win, ww, wh, xs, ys, planes, stream=None):
+    """mlsd_window_gather_packed: win [len(xs)][planes][wh][ww] <- for slot s, canvas [planes][H][W] at ((ys[s] + v) mod H, (xs[s] + u) mod W) (xs, ys: host lists)."""
+    ax, ay = (c_int * max(len(xs), 1))(*xs), (c_int * max(len(ys), 1))(*ys)
+    check(lib().mlsd_window_gather_packed(vp(canvas), W, H, vp(win), ww, wh, ax, ay, len(xs), planes, vp(stream)), "mlsd_window_gather_packed")
+
+
+def window_blend_packed(eps_win, ld_win, eps_canvas, wsum, W, H, ww, wh, xs, ys, n_used, ox, oy, B, G, C=4, stream=None):
+    """mlsd_window_blend_packed: eps_canvas [G][B][H W][4] += (w / wsum) * eps_win [G][len(xs)][B][wh ww][ld_win] (first 4 channels) for slots 0 .. n_used-1 in
+    order, one launch; the canvas ends as after n_used window_blend launches (xs, ys: host lists of the slots' starts)."""
+    ax, ay = (c_int * max(len(xs), 1))(*xs), (c_int * max(len(ys), 1))(*ys)
+    check(lib().mlsd_window_blend_packed(vp(eps_win), c_i64(ld_win), vp(eps_canvas), vp(wsum), W, H, ww, wh, ax, ay, n_used, len(xs), ox, oy, B, G, C, vp(stream)),
+          "mlsd_window_blend_packed")
+
+
+def tile_pack(n_win, n_batch, pack):
+    """mlis_amd_tile_pack: (windows per plan evaluation, plan evaluations) for n_win windows of n_batch images and at most `pack` windows per evaluation; None if refused."""
+    n_eval = c_int()
+    p = lib().mlis_amd_tile_pack(int(n_win), int(n_batch), int(pack), ctypes.byref(n_eval))
+    return None if p < 0 else (p, n_eval.value)
+
+
 def window_starts(L, T, O, wrap=False, cap=256):
     """mlis_amd_window_starts: the window starts along one axis (canvas extent L, window T, minimum overlap O, in latent pixels), or None if refused."""
     out = (c_int * cap)()

@@ -43,7 +43,7 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                       "IMAGE_MASK", "NO_DECODE", "TENSOR_USE_FLAGS", "SEED", "VAE_TILE", "UNET_SPLIT", "THREADS", "DUMP_FLAGS", "AUX_DIR",
                       "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101, AMD_HIRES_SCALE=102, AMD_HIRES_DENOISE=103,
                                                                             AMD_HIRES_STEPS=104, AMD_HIRES_UPSCALER=105, AMD_UNET_TILE=111,
-                                                                           AMD_UNET_TILE_OVERLAP=112))
+                                                                           AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 MLIS_CTEF_NO_NORM = 1
 
@@ -178,7 +178,7 @@ class MLImgSynth:
 
     def option_get(self, option, out):
         """out: a ctypes object receiving the value (c_char_p for MODEL / PROMPT / NPROMPT, c_int for MODEL_TYPE: the four options
-        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER / AMD_UNET_TILE / AMD_UNET_TILE_OVERLAP, c_float for
+        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER / AMD_UNET_TILE / AMD_UNET_TILE_OVERLAP / AMD_UNET_TILE_BATCH, c_float for
         AMD_HIRES_SCALE / AMD_HIRES_DENOISE)."""
         r = self._lib.mlis_option_get(self._ctx, option, ctypes.byref(out))
         if r < 0:
@@ -280,13 +280,16 @@ class MLImgSynth:
             self.option_set("hires_upscaler", upscaler)
 
     # ---- tiled diffusion
-    def unet_tile_set(self, tile, overlap=None):
+    def unet_tile_set(self, tile, overlap=None, batch=None):
         """Tiled diffusion: a pass larger than `tile` pixels on an axis evaluates the UNet in overlapping windows of that size and blends them
         (0 = off).  overlap: minimum overlap of neighbouring windows in pixels, a multiple of 8 with 2 x overlap <= tile; None keeps the
-        current setting (auto = a quarter of the tile unless set), -1 goes back to auto.  The options persist."""
+        current setting (auto = a quarter of the tile unless set), -1 goes back to auto.  batch: at most this many windows (1 .. 16) run as one
+        batched UNet evaluation, at the activation memory of a plan for that many windows; None keeps the current setting.  The options persist."""
         self.option_set("unet_tile", tile)
         if overlap is not None:
             self.option_set("unet_tile_overlap", overlap)
+        if batch is not None:
+            self.option_set("unet_tile_batch", batch)
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

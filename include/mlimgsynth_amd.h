@@ -70,6 +70,41 @@ int unet_denoise_build(UnetState* S);
 int unet_denoise_run_n(UnetState* S, const float* x, const float* cond, const float* label,
 	const float* sigma, float* dx);
 
+/* ---------------------------------------------------------------- ControlNet (not in the reference; the published cldm.py layout)
+ * A trainable copy of the UNet's encoder and middle block that also sees a control image (pose, depth, edges, tile).  Its outputs -- one per tensor the UNet pushes
+ * on its skip stack, through a 1x1 "zero" convolution each, and one for the middle block -- are added, times a gain, to the UNet's skip tensors and to mid.2's output.
+ * Three plans: the hint block (control_hint_*, once per image), the ControlNet (controlnet_*, per evaluation, on the UNet plan's inputs) and a UNet plan built with
+ * unet_denoise_build_ctrl, which reads the residuals where the ControlNet plan leaves them (channels-last fp32) and the gain from one float of device memory. */
+#define MLB_CONTROL_MAX 48
+typedef struct {
+	int n;                              /* residuals: skip tensors + 1 */
+	const float* r[MLB_CONTROL_MAX];    /* device, channels-last fp32 [n_img][rows][ld] */
+	int64_t ld[MLB_CONTROL_MAX];
+	int c[MLB_CONTROL_MAX], rows[MLB_CONTROL_MAX];   /* channels and rows per image of each */
+	int n_img;                          /* images the residuals hold; image n of the UNet plan reads image n % n_img */
+	const float* gain;                  /* device: the gain of the next evaluation (0: the residuals are not read) */
+} UnetControl;
+MLTensor* mlb_unet_denoise_ctrl(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* c, MLTensor* label, const UnetParams* P, const UnetControl* K);   /* K NULL: mlb_unet_denoise */
+int unet_denoise_build_ctrl(UnetState* S, const UnetControl* K);       /* unet_denoise_build with the control inputs; K NULL: the plain plan, op for op */
+
+typedef struct {
+	MLCtx* ctx;
+	const UnetParams* par;
+	int lw, lh, n_batch;
+	MLTensor *t_x, *t_t, *t_c, *t_l;    /* the UNet plan's inputs, same shapes */
+	MLTensor *t_hint;                   /* hint embedding, fp32 channels-last [n_batch][lh lw][n_ch]: the caller writes its device memory (mlctx_tensor_device_f32) */
+	int n_res;
+	MLTensor* t_res[MLB_CONTROL_MAX];   /* residuals in skip-stack push order, the middle block's last */
+} ControlState;
+/* hint block: RGB image [w,h,3,1] in [0,1] at pixel size -> [w/8,h/8,n_ch,1]; prefix "control" (parameters control.hint.<0|2|..|14>) */
+int control_hint_init(MLCtx* C, const UnetParams* P, unsigned w, unsigned h, MLTensor** t_img);
+int control_hint_build(MLCtx* C, const UnetParams* P, MLTensor* t_img);
+/* the ControlNet for a base model with parameters P at the UNet plan's size and batch (prefix "control"); init / build split like the UNet's so that x can be bound */
+int controlnet_init_nc(ControlState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch, int n_ctx_tok);
+int controlnet_build(ControlState* S);
+MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTensor* time, MLTensor* c, MLTensor* label, MLTensor* hint, const UnetParams* P);
+int controlnet_control(const ControlState* S, const float* gain_dev, UnetControl* K);     /* the residuals of a built plan, for unet_denoise_build_ctrl */
+
 /* ---------------------------------------------------------------- VAE / TAE decoders */
 typedef struct {
 	int ch_x, ch_z, ch, n_res, n_res_blk;
@@ -210,6 +245,9 @@ int clip_token_decode(const ClipTokenizer* T, int32_t token, char* out, int max,
  * tensor-name conversion: tnconv_sd, src/tensor_name_conv.c:274-324 (0 unused, 1 converted, 2 = open_clip fused in_proj) */
 enum { TNCONV_R_UNUSED = 0, TNCONV_R_GOOD = 1, TNCONV_R_QKV_PROJ = 2 };
 int tnconv_sd(const char* name, char* out, size_t out_size);
+/* ControlNet files, original (cldm.py) layout with or without a leading "control_model.": -> "control.<...>" (the encoder copy through the UNet's rules,
+ * input_hint_block.K -> hint.K, zero_convs.I.0 -> zero.I, middle_block_out.0 -> mid_out); 0 for anything else (UNet decoder names, diffusers-named files) */
+int tnconv_controlnet(const char* name, char* out, size_t out_size);
 /* tensor index over an mmap'd safetensors file (src/ccompute/tensorstore_safet.c:152-205, tensorstore.c:184-323) */
 typedef struct MLTStore MLTStore;
 typedef struct { char* name; int dtype; int n_dim; int64_t shape[4]; /* shape[0] fastest */ size_t size; const void* data; } MLTSEntry;
@@ -222,6 +260,7 @@ void mlts_close(MLTStore* S);
 /* LoRA (src/lora.c:9-138, tensor_callback_lora src/mlimgsynth.c:1068-1092): open a kohya-named LoRA file, merge it into the
  * model store: W += (scale | alpha/rank | 1) * mult * up.down for every "<X>.lora_down.weight"; returns the number of tensors patched */
 MLTStore* mlts_open_lora(const char* path);
+MLTStore* mlts_open_controlnet(const char* path);   /* a ControlNet file: names through tnconv_controlnet ("control.<...>"), unknown tensors dropped */
 int mlts_lora_apply(MLTStore* model, const MLTStore* lora, float mult, int wtype);
 /* the two halves of mlts_lora_apply, for the path that patches weights already on the device (mlctx_param_lora): the same validation, the same error texts.
  * mlts_lora_resolve: entry i of the adapter -> 0 (not a "<X>.lora_down.weight"), 1 with the item filled, < 0 on error.  mlts_lora_operands: up [n1][n_inner] and
@@ -288,6 +327,9 @@ typedef struct {
 	                          * memory, three to five device slabs (3 for SDXL) of `unet_split` MiB each (1 = the default 512 MiB: 1.5 GiB of slabs + 0.68 GB of resident step-invariant
 	                          * weights instead of 4.8 GiB) filled under the launches; excludes use_hipgraph */
 	int n_ctx_tok;           /* rows of the text context: 77 x W for a prompt of W 75-token windows (W <= 4); 0 = 77 */
+	/* (`control` lies in what was the structure's tail padding: the Python mirror keeps the layout before it as engine.AmdConfig and adds engine.AmdControlConfig,
+	 * of the same size.  A field added after it grows the structure: both mirrors then have to follow, and the size equality tests/test_controlnet_cpu.py asserts goes) */
+	int control;             /* 1: the engine holds a ControlNet (hint plan, ControlNet plan, UNet plan with control inputs); 0: none, every plan as without this field */
 } MLIS_AmdConfig;
 
 /* progress callback (MLIS_Callback, include/mlimgsynth.h:405): called after every COMPLETED step (the stream is
@@ -352,7 +394,24 @@ int mlis_amd_set_lmask(MLIS_AmdCtx* S, const float* lmask);
 int mlis_amd_encode(MLIS_AmdCtx* S, const float* images, int sample);
 MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S);                                /* NULL before the first encode / prepare */
 MLCtx* mlis_amd_encoder_prepare(MLIS_AmdCtx* S);
-MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i);     /* every plan of the engine: 0 UNet, 1 decoder, 2 encoder, 3 tile decoder, 4 tile encoder; NULL where there is none */
+MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i);     /* every plan of the engine: 0 UNet, 1 decoder, 2 encoder, 3 tile decoder, 4 tile encoder, 5 ControlNet, 6 hint block; NULL where there is none */
+/* ControlNet (engines created with MLIS_AmdConfig.control = 1; without a control image they behave as at strength 0).
+ * set_control_image: host NCHW [3][height][width] in [0,1] at the canvas's pixel size, shared by the batch; runs the hint plan; NULL clears the image.  _device: the
+ * same from device memory.  set_control: strength in [0, 2] (default 1) and the step window 0 <= start <= end <= 1 (default 0, 1), else an error; both may change
+ * between generations without touching a plan (the gain is device data: also under use_hipgraph).
+ * control_active (pure): 1 iff start n_step <= i_step + 0.5 < end n_step; both evaluations of a 2-NFE step share their step's answer, mlis_amd_dxdt has no step and is
+ * always controlled.  In a controlled evaluation with strength > 0 the ControlNet plan runs before the UNet plan (per window group on a tiled engine, on the
+ * group's crops of the hint embedding); otherwise it is skipped and the gain is 0.
+ * control_info: residuals of the ControlNet plan (0: none) and the evaluations of the last denoise / dxdt in which it ran. */
+int mlis_amd_set_control_image(MLIS_AmdCtx* S, const float* hint);
+int mlis_amd_set_control_image_device(MLIS_AmdCtx* S, const void* hint_dev);
+int mlis_amd_set_control(MLIS_AmdCtx* S, float strength, float start, float end);
+int mlis_amd_control_active(int i_step, int n_step, float start, float end);
+int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* evals_controlled);
+/* a caller's mark on the image the engine holds (0 after every set_control_image*, and without an image): a caller that sets the same image per generation can skip it */
+void mlis_amd_control_tag_set(MLIS_AmdCtx* S, uint64_t tag);
+uint64_t mlis_amd_control_tag(const MLIS_AmdCtx* S);
+const void* mlis_amd_control_image_device(MLIS_AmdCtx* S);   /* the control image the hint plan read: device NCHW fp32 [3][height][width], NULL without one */
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

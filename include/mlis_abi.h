@@ -65,7 +65,15 @@ typedef enum {
 	                                        * -1 = auto (default): a quarter of the tile, rounded down to a multiple of 8 */
 	/* packed windows: up to this many windows of a tiled pass run as one batched UNet evaluation (the effective count: mlis_amd_tile_pack).  Persists across
 	 * generations; costs the activation memory of a plan for that many windows x the batch.  (A block of its own from 121.) */
-	MLIS_OPT_AMD_UNET_TILE_BATCH = 121     /* "unet_tile_batch" (int): 1 .. 16, default 1 = one window per evaluation */
+	MLIS_OPT_AMD_UNET_TILE_BATCH = 121,    /* "unet_tile_batch" (int): 1 .. 16, default 1 = one window per evaluation */
+	/* ControlNet: the UNet is conditioned on a control image (pose, depth, edges, tile: the finished map, no preprocessor here) through a copy of its encoder */
+	MLIS_OPT_AMD_CONTROL_MODEL = 131,      /* "control_model" (string): a safetensors ControlNet in the original (cldm.py) layout for the base model, or "synth[:seed]" with a
+	                                        * "synth:" model; "" = off.  Engines with and without it coexist in the two resident slots */
+	MLIS_OPT_AMD_CONTROL_IMAGE = 132,      /* "control_image" (const MLIS_Image*, 3 channels; NULL clears; mlis_option_get gives an int: 1 if one is set): any size, resampled on the GPU (bilinear) to each pass's pixel size; it
+	                                        * stays set across generations, like the model */
+	MLIS_OPT_AMD_CONTROL_STRENGTH = 133,   /* "control_strength" (float, default 1): 0 .. 2, the gain on the ControlNet's residuals */
+	MLIS_OPT_AMD_CONTROL_START = 134,      /* "control_start" (float, default 0) and */
+	MLIS_OPT_AMD_CONTROL_END = 135         /* "control_end" (float, default 1): the share of the steps that is controlled, 0 <= start <= end <= 1 (checked by mlis_generate) */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 
@@ -133,6 +141,8 @@ struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* ctx);
 /* engines constructed by this context so far.  A context keeps its two most recently used engines (one per model / size / batch / ... key),
  * so a workflow that alternates between two sizes -- the hires fix -- rebuilds nothing; mlis_amd_engine_get returns the one used last. */
 int mlis_amd_engine_builds(MLIS_Ctx* ctx);
+/* ControlNet: evaluations of pass 0 / 1 of the last mlis_generate in which the ControlNet ran (a hires generation has two passes); -1 for a pass that did not run */
+int mlis_amd_control_evals(MLIS_Ctx* ctx, int pass);
 /* LoRA bookkeeping, cumulative like mlis_amd_engine_builds.  A change of the LoRA set or of a multiplier while engines or text towers are resident is applied
  * to their weights in place on the GPU: every weight the old set had patched is restored from the checkpoint (n_restored counts weights per plan), the new
  * set's adapters are applied in option order by a kernel that repeats the host merge's arithmetic (n_patched, per plan and adapter tensor).  With nothing

@@ -445,6 +445,18 @@ enum { MLSD_WINDOW_MAX_PACK = 16 };
 int mlsd_window_gather_packed(const float* canvas, int W, int H, float* win, int ww, int wh, const int* xs, const int* ys, int n_slots, int planes, void* stream);
 int mlsd_window_blend_packed(const float* eps_win, int64_t ld_win, float* eps_canvas, const float* wsum, int W, int H, int ww, int wh, const int* xs, const int* ys,
                              int n_used, int n_slots, int ox, int oy, int B, int G, int C, void* stream);
+/* ControlNet (csrc/hip/control.hip; not in the reference).
+ *   ctrl_add:  dst[n][r][c] = base[n][r][c] + gain * ctrl[n % n_ctrl_img][r][c], fp32 channels-last maps of rows_per_img rows x C with row strides ld_* (floats), the
+ *              product and the sum rounded separately.  gain is ONE float in device memory, read when the kernel runs: it may change between launches of a captured graph.
+ *              gain == 0: dst gets base's bits and ctrl is never read (it may hold NaN).  dst == base with equal strides is allowed (in place).
+ *              Refused before any launch: C or a stride not a multiple of 4, a stride below C, a pointer not 16-byte aligned, n_ctrl_img outside 1 .. n_img, dst
+ *              overlapping ctrl or (other than in place) base.
+ *   window_gather_nhwc:  dst [n_slots][n_rep][wh][ww][C] <- src [H][W][C] at ((ys[s] + v) mod H, (xs[s] + u) mod W): the window of slot s, n_rep copies of it, bit for
+ *              bit.  Starts as in mlsd_window_gather_packed.  Refuses C not a multiple of 4, pointers not 16-byte aligned, a window larger than the canvas, a start
+ *              outside it, n_slots outside 1 .. MLSD_WINDOW_MAX_PACK, overlapping buffers. */
+int mlsd_ctrl_add(float* dst, int64_t ld_dst, const float* base, int64_t ld_base, const float* ctrl, int64_t ld_ctrl, int n_img, int rows_per_img, int C, int n_ctrl_img,
+                  const float* gain_dev, void* stream);
+int mlsd_window_gather_nhwc(const float* src, int W, int H, int C, float* dst, int ww, int wh, const int* xs, const int* ys, int n_slots, int n_rep, void* stream);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

@@ -322,12 +322,13 @@ static const char k_usage[] =
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
+"ControlNet:  --control-model PATH|synth[:SEED]   --control-image PATH   --control-strength F   --control-start F   --control-end F\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";
 
 typedef struct {
-	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens;
+	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens, *ctl_img;
 	MLIS_Ctx *ctx;
 } Cli;
 
@@ -346,7 +347,7 @@ static int cli_option(Cli* C, const char* name, const char* next)
 	if (!strcmp(name, "debug")) { g_verbose = 3; mlis_option_set(C->ctx, MLIS_OPT_LOG_LEVEL, MLIS_LOGLVL_DEBUG); return 0; }
 	const struct { const char* n; const char** dst; } paths[] = {
 		{"input",&C->in_img},{"imask",&C->in_mask},{"ilatent",&C->in_lat},{"ilmask",&C->in_lmask},{"output",&C->out_img},
-		{"olatent",&C->out_lat},{"tokens",&C->tokens},{"ntokens",&C->ntokens} };
+		{"olatent",&C->out_lat},{"tokens",&C->tokens},{"ntokens",&C->ntokens},{"control-image",&C->ctl_img} };
 	for (size_t i=0;i<sizeof(paths)/sizeof(*paths);++i) if (!strcmp(name, paths[i].n)) { *paths[i].dst = next; return 1; }
 	if (mlis_option_set_str(C->ctx, name, next) < 0) FAIL("option '--%s %s': %s", name, next, mlis_errstr_get(C->ctx));
 	return 1;
@@ -422,6 +423,16 @@ static int cmd_generate(Cli* C)
 		if (im.c != 1) { mono = (unsigned char*)malloc((size_t)im.w*im.h); for (size_t i=0;i<(size_t)im.w*im.h;++i) mono[i] = im.d[i*im.c]; g.d = mono; g.c = 1; }
 		tensor_from_img(mlis_tensor_get(C->ctx, MLIS_TENSOR_MASK), NULL, &g);
 		tuf |= MLIS_TUF_MASK; free(mono); free(im.d);
+	}
+	if (C->ctl_img) {           /* the finished control map (no preprocessor): RGB, grey replicated, alpha dropped */
+		Img im; if (img_read(C->ctl_img, &im) < 0) return -1;
+		unsigned char *rgb = (unsigned char*)malloc((size_t)im.w * im.h * 3);
+		for (size_t i=0;i<(size_t)im.w*im.h;++i) for (int c=0;c<3;++c) rgb[i*3+c] = im.d[i*im.c + (im.c >= 3 ? c : 0)];
+		MLIS_Image mi; memset(&mi, 0, sizeof(mi));
+		mi.d = rgb; mi.sz = (size_t)im.w * im.h * 3; mi.w = im.w; mi.h = im.h; mi.c = 3;
+		const int r = mlis_option_set(C->ctx, MLIS_OPT_AMD_CONTROL_IMAGE, &mi);
+		free(rgb); free(im.d);
+		if (r < 0) FAIL("control image: %s", mlis_errstr_get(C->ctx));
 	}
 	if (C->in_lat) { if (tensor_load(mlis_tensor_get(C->ctx, MLIS_TENSOR_LATENT), C->in_lat) < 0) return -1; tuf |= MLIS_TUF_LATENT; }
 	if (C->in_lmask) { if (tensor_load(mlis_tensor_get(C->ctx, MLIS_TENSOR_LMASK), C->in_lmask) < 0) return -1; tuf |= MLIS_TUF_LMASK; }

@@ -24,7 +24,6 @@
 #include <stdio.h>
 #include <unistd.h>
 
-int unet_denoise_build(UnetState* S);
 
 #define MAX_STEPS 1001     /* the public option STEPS accepts 0..1000 like the reference (mlimgsynth_options_set.c.h); buffers that follow the step count are sized in ensure_steps */
 #define MAX_BATCH 64
@@ -84,6 +83,18 @@ struct MLIS_AmdCtx {
 	int PB, PN;                 /* images and rows of the UNet plan: B and N, times pack when tiled */
 	float *d_eps_canvas;        /* blended UNet output NHWC [N][hw][4] */
 	float *d_wsum;              /* [hw] sum of the blend weights of the windows covering a pixel */
+	/* ControlNet (MLIS_AmdConfig.control): the hint plan runs once per control image at the canvas's pixel size, the ControlNet plan before the UNet plan in every
+	 * controlled evaluation, on the UNet plan's inputs; the UNet plan was built with the residuals' addresses and reads its gain from d_gain */
+	MLCtx *ctl_ctx, *hint_ctx;
+	ControlState ctl;
+	UnetControl ctl_k;
+	MLTensor *t_hint_img;
+	float *d_gain;              /* [1] gain of the evaluation being enqueued: the strength, or 0 (outside the step window, no image, strength 0) */
+	int ctl_image;              /* a control image is set: the hint embedding is current */
+	uint64_t ctl_tag;           /* the caller's mark on that image (mlis_amd_control_tag_set) */
+	float ctl_strength, ctl_start, ctl_end;
+	int ctl_step_on;            /* the current step lies in the window (mlis_amd_control_active); mlis_amd_dxdt has no step: always */
+	int ctl_evals;              /* evaluations of the last denoise / dxdt in which the ControlNet plan ran */
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -93,6 +104,9 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	if (!S) return;
 	mlsd_stream_sync(S->stream);
 	if (S->unet_ctx) mlctx_destroy(S->unet_ctx);
+	if (S->ctl_ctx) mlctx_destroy(S->ctl_ctx);
+	if (S->hint_ctx) mlctx_destroy(S->hint_ctx);
+	mlsd_free(S->d_gain);
 	if (S->dec_ctx) mlctx_destroy(S->dec_ctx);
 	if (S->enc_ctx) mlctx_destroy(S->enc_ctx);
 	if (S->dect_ctx) mlctx_destroy(S->dect_ctx);
@@ -261,6 +275,8 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (S->c.method > SOLVER_METHOD_DPMPP2S) { mlsd_set_error(-1, "invalid sampling method %d", S->c.method); goto err; }
 	if (!(S->c.f_t_ini > 0)) S->c.f_t_ini = 1;
 	if (!S->c.weight_seed) S->c.weight_seed = 1234;
+	if (S->c.control != 0 && S->c.control != 1) { mlsd_set_error(-1, "control %d: 0 none, 1 ControlNet", S->c.control); goto err; }
+	S->ctl_strength = 1; S->ctl_start = 0; S->ctl_end = 1; S->ctl_step_on = 1;
 	if (unet_params_get(S->model, &S->unet_p) < 0) goto err;
 	if (vae_params_get(S->model, &S->vae_p) < 0) goto err;
 	if (S->c.width % 8 || S->c.height % 8 || S->c.width < 8 || S->c.height < 8) { fail("image size must be a multiple of 8"); goto err; }
@@ -294,6 +310,29 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	}
 	if (mlsd_malloc((void**)&S->d_cin, (size_t)S->PB*4)) goto err;
 
+	/* ---- ControlNet: the hint plan at the canvas's pixel size and the ControlNet plan on the UNet plan's inputs, both before the UNet plan, which takes the residuals' addresses */
+	if (S->c.control) {
+		if (mlsd_malloc((void**)&S->d_gain, 256) || mlsd_memset(S->d_gain, 0, 256, stream)) goto err;
+		S->hint_ctx = mlctx_new(stream);
+		mlctx_set_conv_wrap(S->hint_ctx, S->tiling);
+		if (control_hint_init(S->hint_ctx, &S->unet_p, S->c.width, S->c.height, &S->t_hint_img) < 0) goto err;
+		if (control_hint_build(S->hint_ctx, &S->unet_p, S->t_hint_img) < 0) goto err;
+		if (!S->c.defer_weights && mlctx_params_synth(S->hint_ctx, S->c.weight_seed) < 0) goto err;
+		S->ctl_ctx = mlctx_new(stream);
+		mlctx_set_conv_wrap(S->ctl_ctx, unet_wrap);
+		if (S->c.use_hipgraph && S->c.unet_split <= 0) mlctx_set_flags(S->ctl_ctx, MLB_F_HIPGRAPH);      /* (its weights stay resident with unet_split too) */
+		if (controlnet_init_nc(&S->ctl, S->ctl_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
+		if (mlctx_input_bind(S->ctl.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
+		if (controlnet_build(&S->ctl) < 0) goto err;
+		if (!S->c.defer_weights && mlctx_params_synth(S->ctl_ctx, S->c.weight_seed) < 0) goto err;
+		if (controlnet_control(&S->ctl, S->d_gain, &S->ctl_k) < 0) goto err;
+		{	/* the hint embedding travels as dense rows of n_ch floats: from the hint plan's result into the ControlNet plan's hint tensor (mlsd_window_gather_nhwc) */
+			int64_t ldh = 0, ldw = 0;
+			if (!mlctx_tensor_device_f32(S->hint_ctx, mlctx_result(S->hint_ctx), &ldh) || !mlctx_tensor_device_f32(S->ctl_ctx, S->ctl.t_hint, &ldw) ||
+			    ldh != S->unet_p.n_ch || ldw != S->unet_p.n_ch) { mlsd_set_error(-1, "internal: hint embedding rows of %lld / %lld floats, %d channels", (long long)ldh, (long long)ldw, S->unet_p.n_ch); goto err; }
+		}
+	}
+
 	/* ---- UNet plan, x bound to the resident evaluation point (c_in scaling + cond/uncond duplication in the gather) */
 	S->unet_ctx = mlctx_new(stream);
 	mlctx_set_conv_wrap(S->unet_ctx, unet_wrap);
@@ -302,7 +341,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
 	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
 	if (mlctx_input_bind(S->unet.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
-	if (unet_denoise_build(&S->unet) < 0) goto err;
+	if (unet_denoise_build_ctrl(&S->unet, S->c.control ? &S->ctl_k : NULL) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
 
 	/* ---- decoder plan, latent input bound to the same resident latent */
@@ -363,6 +402,10 @@ static int set_cond(MLIS_AmdCtx* S, const void* cond, const void* label, const v
 	const UnetParams *P = &S->unet_p;
 	if (fill_cond(S, S->unet.t_c, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
 	if (P->ch_adm_in && fill_cond(S, S->unet.t_l, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
+	if (S->ctl_ctx) {      /* the ControlNet plan takes the same conditioning */
+		if (fill_cond(S, S->ctl.t_c, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
+		if (P->ch_adm_in && fill_cond(S, S->ctl.t_l, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
+	}
 	if (mlsd_stream_sync(S->stream)) return -1;
 	S->cond_set = 1;
 	return 1;
@@ -554,6 +597,15 @@ static const float* noise_draw(MLIS_AmdCtx* S, int k)
 	return nz;
 }
 
+/* the in-launch hand-offs of the plans an evaluation runs (UNet, ControlNet): checked together, switched off together */
+static int eval_handoff_ops(MLIS_AmdCtx* S) { return mlctx_handoff_ops(S->unet_ctx) + (S->ctl_ctx ? mlctx_handoff_ops(S->ctl_ctx) : 0); }
+static int eval_handoff_check(MLIS_AmdCtx* S)
+{
+	const int a = mlctx_handoff_check(S->unet_ctx), b = S->ctl_ctx ? mlctx_handoff_check(S->ctl_ctx) : 0;      /* (both: a check also clears the plan's flags) */
+	return a < 0 || b < 0 ? -1 : 0;
+}
+static void eval_handoffs_off(MLIS_AmdCtx* S) { mlctx_handoffs_off(S->unet_ctx); if (S->ctl_ctx) mlctx_handoffs_off(S->ctl_ctx); }
+
 /* mlis_denoise_dxdt + unet_denoise_run_n (src/mlimgsynth.c:1565-1587, src/unet.c:460-498): one batched evaluation at
  * x_eval (device), sigma -> raw UNet output stays in the plan's result tensor.  `prefetch_draws`: noise draws to generate
  * on the host while this evaluation runs. */
@@ -569,6 +621,10 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 	/* the same timestep for every row and the same c_in for every image: written by a kernel from its arguments.  (As two 64-byte copies they queued behind the copy
 	 * engine's current job -- with streamed weights a 500 MB upload: 10 ms gaps in front of 4 of 20 evaluations, MLSD_ENGINE_TRACE.) */
 	if (mlsd_fill2_f32(d_t_in, S->PN, t, S->d_cin, S->PB, c_in, st)) return -1;
+	/* ControlNet: the plan runs in front of the UNet plan when this evaluation is controlled; either way the UNet plan's sums read the gain written here */
+	const int ctl_on = S->ctl_ctx && S->ctl_image && S->ctl_strength > 0 && S->ctl_step_on;
+	if (S->ctl_ctx && mlsd_fill2_f32((float*)mlctx_input_device_ptr(S->ctl.t_t), S->PN, t, S->d_gain, 1, ctl_on ? S->ctl_strength : 0.f, st)) return -1;
+	if (ctl_on) S->ctl_evals++;
 	int64_t ld = 0;
 	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
 	if (S->n_win) {
@@ -587,6 +643,14 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 				xs[s] = S->win_xs[j % S->n_win_x]; ys[s] = S->win_ys[j / S->n_win_x];
 			}
 			if (mlsd_window_gather_packed(x_eval, S->lw, S->lh, S->d_xin, S->win_w, S->win_h, xs, ys, P, B*4, st)) return -1;
+			if (ctl_on) {      /* every slot's crop of the canvas's hint embedding, for the cond and the uncond rows of the plan: [N / B][P][B] images */
+				const int nch = S->unet_p.n_ch;              /* (both row strides are n_ch: checked when the engine was created) */
+				const float *hs = mlctx_tensor_device_f32(S->hint_ctx, mlctx_result(S->hint_ctx), NULL);
+				float *hw_ = (float*)mlctx_tensor_device_f32(S->ctl_ctx, S->ctl.t_hint, NULL);
+				for (int q=0; q<N/B; ++q)
+					if (mlsd_window_gather_nhwc(hs, S->lw, S->lh, nch, hw_ + (size_t)q * P * B * whw * nch, S->win_w, S->win_h, xs, ys, P, B, st)) return -1;
+				if (mlctx_compute(S->ctl_ctx) < 0) return -1;
+			}
 			if (mlctx_compute(S->unet_ctx) < 0) return -1;
 			if (mlsd_window_blend_packed(eps, ld, S->d_eps_canvas, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, xs, ys, n_used, P, S->win_ox, S->win_oy, B, N / B, 4, st)) return -1;
 			if (mlsd_count_nonfinite(eps, (size_t)S->PN*whw*ld, S->d_nan, st)) return -1;
@@ -599,6 +663,7 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 	}
 	if (x_eval != S->d_xin && mlsd_memcpy(S->d_xin, x_eval, (size_t)B*4*S->hw*4, 2, st)) return -1;
 	mlsd_event_record(S->ev[S->i_eval][0], st);
+	if (ctl_on && mlctx_compute(S->ctl_ctx) < 0) return -1;
 	if (mlctx_compute(S->unet_ctx) < 0) return -1;               /* cond + uncond of all images: one evaluation */
 	mlsd_event_record(S->ev[S->i_eval][1], st);
 	S->i_eval++;
@@ -633,14 +698,14 @@ MLB_API int mlis_amd_dxdt(MLIS_AmdCtx* S, const float* x_host, float sigma, floa
 	const size_t nb = (size_t)S->B * 4 * S->hw * 4;
 	void *st = S->stream;
 	for (int attempt=0; ; ++attempt) {
-		S->i_eval = 0; S->last_nfe = 0;
+		S->i_eval = 0; S->last_nfe = 0; S->ctl_evals = 0; S->ctl_step_on = 1;
 		if (mlsd_memset(S->d_nan, 0, 4, st) || mlsd_memcpy(S->d_tmp[0], x_host, nb, 0, st)) return -1;
 		if (unet_eval(S, S->d_tmp[0], sigma, -1) < 0 || dxdt_finish(S, S->d_tmp[0], sigma, S->d_dx) < 0) return -1;
 		int32_t nan_count = 0;
 		if (mlsd_memcpy(dx_host, S->d_dx, nb, 1, st) || mlsd_memcpy(&nan_count, S->d_nan, 4, 1, st) || mlsd_stream_sync(st)) return -1;
-		if (mlctx_handoff_check(S->unet_ctx) < 0) {      /* as mlis_amd_denoise: once more on the hand-off-free plan */
+		if (eval_handoff_check(S) < 0) {      /* as mlis_amd_denoise: once more on the hand-off-free plans */
 			if (attempt) return -1;
-			mlctx_handoffs_off(S->unet_ctx); S->n_handoff_retries++;
+			eval_handoffs_off(S); S->n_handoff_retries++;
 			continue;
 		}
 		if (nan_count) return mlsd_set_error(-7 /* MLIS_E_NAN */, "NaN found in UNet output (%d values)", nan_count);
@@ -668,7 +733,7 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 	unsigned i_step_solver = 0;
 	float dt_prev = 0, h_last = 0;                                            /* taylor3 / dpmpp2m scalar state */
 	S->n_draw_gen = 0; S->i_eval = 0; S->last_nfe = 0; S->last_n_step = n_step;
-	S->k_draw = 0;
+	S->k_draw = 0; S->ctl_evals = 0;
 	if (mlsd_memset(S->d_nan, 0, 4, st)) return -1;
 	if (!S->have_init_latent && mlsd_memset(S->d_x, 0, (size_t)nel*4, st)) return -1;   /* mlimgsynth.c:1669-1670 */
 	if (method == SOLVER_METHOD_TAYLOR3 || method == SOLVER_METHOD_DPMPP2M) {
@@ -678,6 +743,7 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 
 	for (int s=0; s<n_step; ++s) {
 		float s_up = 0, s_down = sigmas[s+1];
+		S->ctl_step_on = mlis_amd_control_active(s, n_step, S->ctl_start, S->ctl_end);      /* both evaluations of a 2-NFE step share it */
 		if (s == 0) {                                                         /* sampling.c:129-137 */
 			if (S->have_lmask && mlsd_memcpy(S->d_x0, S->d_x, (size_t)nel*4, 2, st)) return -1;
 			const float *nz = noise_draw(S, S->k_draw++);
@@ -779,7 +845,8 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 	}
 	int32_t nan_count = 0;
 	if (mlsd_memcpy(&nan_count, S->d_nan, 4, 1, st) || mlsd_stream_sync(st)) return -1;
-	if (mlctx_handoff_check(S->unet_ctx) < 0) {                              /* an in-launch hand-off of the plan gave up waiting: results invalid (mlis_amd_denoise retries) */
+	S->ctl_step_on = 1;
+	if (eval_handoff_check(S) < 0) {                                         /* an in-launch hand-off of the plan gave up waiting: results invalid (mlis_amd_denoise retries) */
 		if (retry_wanted) *retry_wanted = 1;                                 /* out of band: a user callback may abort with any negative value, -8 included */
 		return -1;
 	}
@@ -823,7 +890,7 @@ static int denoise_once(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 MLB_API int mlis_amd_denoise(MLIS_AmdCtx* S, const uint64_t* seeds)
 {
 	if (seeds) mlis_amd_seed(S, seeds);
-	const int guard = mlctx_handoff_ops(S->unet_ctx) > 0;
+	const int guard = eval_handoff_ops(S) > 0;
 	const int had_init = S->have_init_latent;
 	const size_t xbytes = (size_t)S->B * 4 * S->hw * 4;
 	RngPhilox keep[MAX_BATCH];
@@ -837,13 +904,68 @@ MLB_API int mlis_amd_denoise(MLIS_AmdCtx* S, const uint64_t* seeds)
 	int retry = 0;
 	int r = denoise_once(S, NULL, &retry);
 	if (!retry || !guard) return r;
-	mlctx_handoffs_off(S->unet_ctx);
+	eval_handoffs_off(S);
 	S->n_handoff_retries++;
 	memcpy(S->rng, keep, sizeof(S->rng[0]) * (size_t)S->B);
 	S->have_init_latent = had_init;
 	if (had_init && mlsd_memcpy(S->d_x, S->d_xsave, xbytes, 2, S->stream)) return -1;
 	retry = 0;
 	return denoise_once(S, NULL, &retry);
+}
+
+/* ------------------------------------------------------------------ ControlNet
+ * 1 iff step i_step of n_step lies in the window: start n_step <= i_step + 0.5 < end n_step (the step's midpoint; in double from the float arguments) */
+MLB_API int mlis_amd_control_active(int i_step, int n_step, float start, float end)
+{
+	const double m = (double)i_step + 0.5;
+	return (double)start * n_step <= m && m < (double)end * n_step;
+}
+
+MLB_API int mlis_amd_set_control(MLIS_AmdCtx* S, float strength, float start, float end)
+{
+	if (!S || !S->ctl_ctx) return fail("mlis_amd_set_control: the engine was created without a ControlNet");
+	if (!(strength >= 0 && strength <= 2)) return mlsd_set_error(-1, "control strength %g: 0 .. 2", strength);
+	if (!(start >= 0 && start <= end && end <= 1)) return mlsd_set_error(-1, "control window %g .. %g: 0 <= start <= end <= 1", start, end);
+	S->ctl_strength = strength; S->ctl_start = start; S->ctl_end = end;
+	return 1;
+}
+
+/* the control image -> the hint embedding (once per image), and for a plain engine a copy of it per plan image (a tiled engine cuts windows out per evaluation).
+ * kind: 0 host, 2 device pointer. */
+static int set_control_image(MLIS_AmdCtx* S, const float* hint, int kind)
+{
+	if (!S || !S->ctl_ctx) return fail("mlis_amd_set_control_image: the engine was created without a ControlNet");
+	S->ctl_tag = 0;
+	if (!hint) { S->ctl_image = 0; return 1; }
+	void *st = S->stream;
+	S->ctl_image = 0;
+	if (mlsd_memcpy(mlctx_input_device_ptr(S->t_hint_img), hint, (size_t)3 * S->c.width * S->c.height * 4, kind, st)) return -1;
+	if (mlctx_compute_checked(S->hint_ctx) < 0) return -1;
+	if (!S->n_win) {
+		const float *hs = mlctx_tensor_device_f32(S->hint_ctx, mlctx_result(S->hint_ctx), NULL);
+		float *hw_ = (float*)mlctx_tensor_device_f32(S->ctl_ctx, S->ctl.t_hint, NULL);
+		const int zero = 0;
+		if (mlsd_window_gather_nhwc(hs, S->lw, S->lh, S->unet_p.n_ch, hw_, S->lw, S->lh, &zero, &zero, 1, S->N, st)) return -1;
+	}
+	if (mlsd_stream_sync(st)) return -1;
+	S->ctl_image = 1;
+	return 1;
+}
+MLB_API int mlis_amd_set_control_image(MLIS_AmdCtx* S, const float* hint) { return set_control_image(S, hint, 0); }
+MLB_API int mlis_amd_set_control_image_device(MLIS_AmdCtx* S, const void* hint_dev) { return set_control_image(S, (const float*)hint_dev, 2); }
+
+/* a caller's mark on the control image the engine holds (0 after every mlis_amd_set_control_image*): lets it skip setting the same image again */
+MLB_API void mlis_amd_control_tag_set(MLIS_AmdCtx* S, uint64_t tag) { if (S && S->ctl_image) S->ctl_tag = tag; }
+MLB_API uint64_t mlis_amd_control_tag(const MLIS_AmdCtx* S) { return S && S->ctl_image ? S->ctl_tag : 0; }
+/* the control image as the hint plan reads it: device, NCHW fp32 [3][height][width]; NULL without a ControlNet or an image (tests) */
+MLB_API const void* mlis_amd_control_image_device(MLIS_AmdCtx* S) { return S && S->ctl_ctx && S->ctl_image ? S->t_hint_img->in_stage : NULL; }
+
+MLB_API int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* evals_controlled)
+{
+	if (!S) return -1;
+	if (n_residuals) *n_residuals = S->ctl_ctx ? S->ctl.n_res : 0;
+	if (evals_controlled) *evals_controlled = S->ctl_evals;
+	return 1;
 }
 
 /* ------------------------------------------------------------------ VAE tiling
@@ -1094,11 +1216,12 @@ MLB_API void* mlis_amd_image_device(MLIS_AmdCtx* S) { return S->d_img; }
 MLB_API MLCtx* mlis_amd_unet_ctx(MLIS_AmdCtx* S) { return S->unet_ctx; }
 MLB_API MLCtx* mlis_amd_decoder_ctx(MLIS_AmdCtx* S) { return S->dec_ctx; }
 MLB_API MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S) { return S->enc_ctx; }
-/* every plan the engine holds, built or not yet: UNet, decoder, encoder, tile decoder, tile encoder (i < 5; NULL where there is none) */
+/* every plan the engine holds, built or not yet: UNet, decoder, encoder, tile decoder, tile encoder, ControlNet, hint block (i < 7; NULL where there is none) */
 MLB_API MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i)
 {
 	if (!S) return NULL;
-	switch (i) { case 0: return S->unet_ctx; case 1: return S->dec_ctx; case 2: return S->enc_ctx; case 3: return S->dect_ctx; case 4: return S->enct_ctx; }
+	switch (i) { case 0: return S->unet_ctx; case 1: return S->dec_ctx; case 2: return S->enc_ctx; case 3: return S->dect_ctx; case 4: return S->enct_ctx;
+	             case 5: return S->ctl_ctx; case 6: return S->hint_ctx; }
 	return NULL;
 }
 MLB_API float mlis_amd_last_unet_ms(MLIS_AmdCtx* S) { return S->last_unet_ms; }

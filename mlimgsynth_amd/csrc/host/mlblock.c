@@ -662,6 +662,8 @@ static int run_op(MLCtx* C, MLOp* op)
 	case OP_SOFTMAX: return mlsd_softmax_rows(op->u.smax.in, op->u.smax.ld_in, op->u.smax.out, op->u.smax.ld_out,
 	                                   op->u.smax.rows, op->u.smax.cols, op->u.smax.scale, st);
 	case OP_COPY_F32: return mlsd_memcpy(op->u.copy.dst, op->u.copy.src, op->u.copy.nbytes, 2, st);
+	case OP_CTRL_ADD: return mlsd_ctrl_add(op->u.cadd.dst, op->u.cadd.ld_dst, op->u.cadd.base, op->u.cadd.ld_base, op->u.cadd.ctrl, op->u.cadd.ld_ctrl,
+	                                   op->u.cadd.n_img, op->u.cadd.rows, op->u.cadd.C, op->u.cadd.n_ctrl, op->u.cadd.gain, st);
 	case OP_XA_VT: return mlsd_xattn_pack_vt(op->u.xavt.v, op->u.xavt.ldv, op->u.xavt.n_img, op->u.xavt.Tk, op->u.xavt.N, op->u.xavt.vt, st);
 	}
 	return mlsd_set_error(-1, "unknown op kind %d", (int)op->kind);
@@ -1076,6 +1078,7 @@ static int op_outputs(const MLOp* o, const void* out[3])
 	case OP_SOFTMAX: out[n++] = o->u.smax.out; break;
 	case OP_COPY_F32: out[n++] = o->u.copy.dst; break;
 	case OP_XA_VT: out[n++] = o->u.xavt.vt; break;
+	case OP_CTRL_ADD: out[n++] = o->u.cadd.dst; break;
 	}
 	return n;
 }
@@ -1722,6 +1725,7 @@ MLB_API double mlctx_op_bytes(const MLCtx* C, int i)
 	case OP_SOFTMAX: return (double)op->u.smax.rows * op->u.smax.cols * 6.0;
 	case OP_ACT: return (double)op->u.act.n * 6.0;
 	case OP_COPY_F32: return 2.0 * op->u.copy.nbytes;
+	case OP_CTRL_ADD: return 12.0 * op->u.cadd.n_img * (double)op->u.cadd.rows * op->u.cadd.C;      /* base and ctrl read, dst written (gain 0: ctrl is not read) */
 	default: return 0;
 	}
 }

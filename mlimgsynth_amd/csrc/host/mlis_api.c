@@ -43,6 +43,12 @@ struct MLIS_Ctx {
 	float hires_scale, hires_denoise; int hires_steps, hires_upscaler;      /* MLIS_OPT_AMD_HIRES_*: the two-pass generation of mlis_generate */
 	int unet_tile, unet_tile_overlap;       /* MLIS_OPT_AMD_UNET_TILE*: tiled diffusion, pixels; 0 = off, overlap -1 = auto */
 	int tiled_tile, tiled_overlap;          /* of the last generation, if one of its passes was tiled (infotext) */
+	/* MLIS_OPT_AMD_CONTROL_*: the ControlNet file (or "synth[:seed]"), the control image as given (any size; resampled per pass), strength and step window */
+	char *path_control; MLTStore *ts_control;
+	MLIS_Tensor control_image;
+	uint64_t control_image_gen;             /* counts the control images set: the mark an engine keeps on the one it holds (never 0 once an image is set) */
+	float control_strength, control_start, control_end;
+	int control_evals[2], control_pass;     /* controlled evaluations of the last generation's passes (mlis_amd_control_evals) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
 	int method, sched, n_step;
@@ -138,8 +144,10 @@ static const char* const k_tiling[] = { "none", "x", "y", "xy" };
 static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
 static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };            /* ids from MLIS_OPT_AMD_UNET_TILE */
 static const char* const k_option_amd3[] = { "unet_tile_batch" };                           /* ids from MLIS_OPT_AMD_UNET_TILE_BATCH */
+static const char* const k_option_amd4[] = { "control_model", "control_image", "control_strength", "control_start", "control_end" };   /* ids from MLIS_OPT_AMD_CONTROL_MODEL */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_CONTROL_MODEL && x < MLIS_OPT_AMD_CONTROL_MODEL + COUNTOF(k_option_amd4)) return k_option_amd4[x - MLIS_OPT_AMD_CONTROL_MODEL];
 	if (x >= MLIS_OPT_AMD_UNET_TILE_BATCH && x < MLIS_OPT_AMD_UNET_TILE_BATCH + COUNTOF(k_option_amd3)) return k_option_amd3[x - MLIS_OPT_AMD_UNET_TILE_BATCH];
 	if (x >= MLIS_OPT_AMD_UNET_TILE && x < MLIS_OPT_AMD_UNET_TILE + COUNTOF(k_option_amd2)) return k_option_amd2[x - MLIS_OPT_AMD_UNET_TILE];
 	if (x >= MLIS_OPT_AMD_TILING && x < MLIS_OPT_AMD_TILING + COUNTOF(k_option_amd)) return k_option_amd[x - MLIS_OPT_AMD_TILING];
@@ -153,6 +161,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i2 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE + i2);
 	const int i3 = from_list(k_option_amd3, COUNTOF(k_option_amd3), 1, s, strlen(s));
 	if (i3 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE_BATCH + i3);
+	const int i4 = from_list(k_option_amd4, COUNTOF(k_option_amd4), 1, s, strlen(s));
+	if (i4 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_MODEL + i4);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -215,6 +225,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
 	S->unet_tile_overlap = -1;
 	S->unet_tile_batch = 1;
+	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -226,6 +237,19 @@ static void engine_drop(MLIS_Ctx* S)
 	 * an engine that was only built for mlis_image_decode still has offset 0 and must not reset the context's running offset) */
 	if (S->eng) { mlis_amd_destroy(S->eng); S->eng = NULL; S->eng_key[0] = 0; }
 	if (S->eng2) { mlis_amd_destroy(S->eng2); S->eng2 = NULL; S->eng2_key[0] = 0; }
+}
+static int engine_has_control(MLIS_AmdCtx* e)
+{	/* asked of the engine itself, not read out of its key */
+	int n_res = 0;
+	return e && mlis_amd_control_info(e, &n_res, NULL) > 0 && n_res > 0;
+}
+static void control_engines_drop(MLIS_Ctx* S)
+{	/* the resident engines built with a ControlNet */
+	if (engine_has_control(S->eng2)) { mlis_amd_destroy(S->eng2); S->eng2 = NULL; S->eng2_key[0] = 0; }
+	if (engine_has_control(S->eng)) {
+		mlis_amd_destroy(S->eng); S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(S->eng_key));
+		S->eng2 = NULL; S->eng2_key[0] = 0;
+	}
 }
 static void textcond_drop(MLIS_Ctx* S) { if (S->tc) { mlis_amd_textcond_destroy(S->tc); S->tc = NULL; S->tc_key[0] = 0; } }
 static void applied_clear(MLIS_Ctx* S)
@@ -258,6 +282,7 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 	if (S->signature != CTX_SIGNATURE) return;
 	model_drop(S);
 	if (S->tok) clip_tokr_free(S->tok);
+	free(S->path_control); if (S->ts_control) mlts_close(S->ts_control); mlis_tensor_free(&S->control_image);
 	free(S->backend); free(S->path_model); free(S->path_tae); free(S->path_aux); free(S->path_lora_dir); free(S->prompt_raw); free(S->nprompt_raw);
 	mlis_prompt_free(&S->prompt); mlis_prompt_free(&S->nprompt);
 	for (int i=0;i<2;++i) { free(S->ptok[i]); free(S->ptokw[i]); }
@@ -275,6 +300,12 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 
 MLB_API const char* mlis_errstr_get(const MLIS_Ctx* S) { return S ? S->errstr : mlsd_last_error(); }
 MLB_API struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* S) { return S ? S->eng : NULL; }
+/* controlled evaluations of pass 0 / 1 of the last mlis_generate (a hires generation has two passes); -1 for a pass that did not run */
+MLB_API int mlis_amd_control_evals(MLIS_Ctx* S, int pass)
+{
+	if (!S || S->signature != CTX_SIGNATURE || pass < 0 || pass >= S->control_pass) return -1;
+	return S->control_evals[pass];
+}
 MLB_API int mlis_amd_engine_builds(MLIS_Ctx* S) { return (S && S->signature == CTX_SIGNATURE) ? S->n_eng_builds : -1; }
 MLB_API int mlis_amd_lora_stats(MLIS_Ctx* S, int* n_restored, int* n_patched, int* n_cold_merges)
 {
@@ -536,6 +567,22 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_UNET_TILE: if (!arg_int(A, 0, 65535, 0, &i) || i % 8) BAD_VALUE; S->unet_tile = i; break;     /* 0: off; the relation to the overlap is checked when an engine is needed (unet_tile_check) */
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: if (!arg_int(A, -1, 65535, -1, &i) || (i > 0 && i % 8)) BAD_VALUE; S->unet_tile_overlap = i; break;      /* -1: auto */
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
+	case MLIS_OPT_AMD_CONTROL_MODEL:       /* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
+		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
+		if (!S->path_control || strcmp(S->path_control, s)) { control_engines_drop(S); if (S->ts_control) { mlts_close(S->ts_control); S->ts_control = NULL; } }
+		str_set(&S->path_control, s);
+		break;
+	case MLIS_OPT_AMD_CONTROL_IMAGE: {
+		NO_STR;
+		const MLIS_Image *img = va_arg(*A->ap, const MLIS_Image*);
+		if (!img) { mlis_tensor_free(&S->control_image); break; }
+		if (img->c != 3) return api_error(S, MLIS_E_IMAGE, "invalid number of channels in control image: %d (3: the finished control map as RGB)", (int)img->c);
+		if (image_to_tensor(&S->control_image, img) < 0) return api_error(S, MLIS_E_IMAGE, "invalid control image");
+		S->control_image_gen++;      /* engines holding the previous image take this one at their next pass (control_apply) */
+	} break;
+	case MLIS_OPT_AMD_CONTROL_STRENGTH: if (!arg_float(A, 0, 2, 1, &f)) BAD_VALUE; S->control_strength = f; break;
+	case MLIS_OPT_AMD_CONTROL_START: if (!arg_float(A, 0, 1, 0, &f)) BAD_VALUE; S->control_start = f; break;      /* start <= end: checked by mlis_generate, the two are set one by one */
+	case MLIS_OPT_AMD_CONTROL_END: if (!arg_float(A, 0, 1, 1, &f)) BAD_VALUE; S->control_end = f; break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -602,6 +649,11 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_UNET_TILE: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile; } break;
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_overlap; } break;
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_batch; } break;
+	case MLIS_OPT_AMD_CONTROL_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_control ? S->path_control : ""; } break;
+	case MLIS_OPT_AMD_CONTROL_IMAGE: { int *p = va_arg(ap, int*); if (p) *p = tensor_good(&S->control_image); } break;      /* whether one is set */
+	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
+	case MLIS_OPT_AMD_CONTROL_START: { float *p = va_arg(ap, float*); if (p) *p = S->control_start; } break;
+	case MLIS_OPT_AMD_CONTROL_END: { float *p = va_arg(ap, float*); if (p) *p = S->control_end; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -678,7 +730,7 @@ static int resident_ctxs(MLIS_Ctx* S, MLCtx** out)
 {
 	int n = 0;
 	MLIS_AmdCtx *eng[2] = { S->eng, S->eng2 };
-	for (int e=0;e<2;++e) for (int i=0; eng[e] && i<5; ++i) {
+	for (int e=0;e<2;++e) for (int i=0; eng[e] && i<5; ++i) {      /* (plans 5 and 6, the ControlNet's, are left out: LoRAs do not touch it) */
 		MLCtx *c = mlis_amd_ctx_at(eng[e], i);
 		if (c && mlctx_params_loaded(c)) out[n++] = c;
 	}
@@ -918,6 +970,56 @@ static int unet_tile_check(MLIS_Ctx* S)
 	return 1;
 }
 
+/* the ControlNet's weights into plans 5 (ControlNet) and 6 (hint block) of the engine just built: "synth[:seed]" with a synthetic model, else a safetensors file in
+ * the original layout (its own store: the ControlNet is no part of the checkpoint).  A file of another architecture fails naming the first tensor that is
+ * missing or has the wrong element count (mlctx_tstore_load). */
+static int control_weights(MLIS_Ctx* S)
+{
+	const char *p = S->path_control;
+	const int is_synth = !strncmp(p, "synth", 5) && (!p[5] || p[5] == ':');
+	for (int i=5; i<=6; ++i) {
+		MLCtx *C = mlis_amd_ctx_at(S->eng, i);
+		if (!C) return api_error(S, MLIS_E_UNKNOWN, "internal: the engine has no ControlNet plan");
+		mlctx_set_wtype(C, S->wtype);
+		if (is_synth) {
+			if (!S->synth) return api_error(S, MLIS_E_OPT_VALUE, "control_model '%s' needs a synth: model (a checkpoint takes a ControlNet file)", p);
+			const uint64_t seed = p[5] == ':' ? strtoull(p + 6, NULL, 10) : S->synth_seed;
+			if (mlctx_params_synth(C, seed) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+			continue;
+		}
+		if (!S->ts_control) {
+			if (!file_exists(p)) return api_error(S, MLIS_E_FILE_NOT_FOUND, "ControlNet file '%s' not found", p);
+			if (!(S->ts_control = mlts_open_controlnet(p))) return api_error_lib(S, MLIS_E_UNKNOWN);
+		}
+		if (mlctx_tstore_load(C, S->ts_control) < 0) return api_error(S, MLIS_E_UNKNOWN, "ControlNet '%s' does not fit the model %s: %s", p, S->mname, mlsd_last_error());
+	}
+	return 1;
+}
+
+/* the control image at the pass's pixel size into the engine (resampled on the GPU, bilinear, as mlis_amd_tensor_resample does), strength and window */
+static int control_apply(MLIS_Ctx* S, int w_img, int h_img)
+{
+	if (str_empty(S->path_control)) return 1;
+	/* the engine has one pixel size: it still holds this very image, resampled and through the hint plan, unless the option was set again since (or the tiling changed
+	 * the resampler's edges: another engine) */
+	if (mlis_amd_control_tag(S->eng) == S->control_image_gen)
+		return mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
+	const MLIS_Tensor *src = &S->control_image;
+	const int sw = src->n[0], sh = src->n[1];
+	const size_t n_src = (size_t)3 * sw * sh, n_dst = (size_t)3 * w_img * h_img;
+	void *d_src = NULL, *d_dst = NULL;
+	int r = 1;
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+			|| mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, MLIS_AMD_RESAMPLE_BILINEAR, S->tiling, NULL) || mlsd_device_sync()
+			|| mlis_amd_set_control_image_device(S->eng, d_dst) < 0
+			|| mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0)
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) mlis_amd_control_tag_set(S->eng, S->control_image_gen);
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	return r;
+}
+
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
@@ -927,15 +1029,20 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	const int tile = (S->unet_tile > 0 && (S->unet_tile < lw * f || S->unet_tile < lh * f)) ? S->unet_tile : 0, overlap = tile ? unet_tile_overlap_eff(S) : 0;
 	char key[96];
 	int nk = snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
-	if (tile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/u%do%dp%d", tile, overlap, S->unet_tile_batch);
+	if (tile && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/u%do%dp%d", tile, overlap, S->unet_tile_batch);
+	const int control = !str_empty(S->path_control);      /* (one ControlNet per context: a changed file drops the engines, so the key only says whether) */
+	if (control && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/k1");
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
-	if ((!S->eng || strcmp(key, S->eng_key)) && S->eng2 && !strcmp(key, S->eng2_key)) {      /* the other resident engine: they change places */
+	/* (a slot serves when its key matches AND it holds a ControlNet exactly if one is wanted: a key cut short by a long model name cannot pass one for the other) */
+#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control)
+	if (!SLOT_IS(S->eng, S->eng_key) && SLOT_IS(S->eng2, S->eng2_key)) {      /* the other resident engine: they change places */
 		MLIS_AmdCtx *e = S->eng; char k[sizeof(S->eng_key)]; memcpy(k, S->eng_key, sizeof(k));
 		S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(k));
 		S->eng2 = e; memcpy(S->eng2_key, k, sizeof(k));
 	}
-	if (!S->eng || strcmp(key, S->eng_key)) {
+	if (!SLOT_IS(S->eng, S->eng_key)) {
+#undef SLOT_IS
 		if (S->eng) {           /* the engine used last moves to the second slot; what was there, the least recently used one, goes */
 			if (S->eng2) mlis_amd_destroy(S->eng2);
 			S->eng2 = S->eng; memcpy(S->eng2_key, S->eng_key, sizeof(S->eng_key));
@@ -947,11 +1054,14 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
+		c.control = control;
 		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
-		if (ctx_weights(S, mlis_amd_unet_ctx(S->eng), 0) < 0 || ctx_weights(S, mlis_amd_decoder_ctx(S->eng), tae) < 0) { mlis_amd_destroy(S->eng); S->eng = NULL; return -1; }
+		if (ctx_weights(S, mlis_amd_unet_ctx(S->eng), 0) < 0 || ctx_weights(S, mlis_amd_decoder_ctx(S->eng), tae) < 0 || (control && control_weights(S) < 0)) {
+			mlis_amd_destroy(S->eng); S->eng = NULL; return -1;
+		}
 		snprintf(S->eng_key, sizeof(S->eng_key), "%s", key);
 		if (S->dump_flags & 4) {   /* MLIS_DUMP_GRAPH (src/mlimgsynth.c:432,1298 -> MLB_F_DUMP -> "dump-graph-<name>.txt", src/mlblock.c:111-116) */
 			mlctx_block_graph_dump_path(mlis_amd_unet_ctx(S->eng), "dump-graph-unet.txt");
@@ -1278,6 +1388,11 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 		k_resample[S->hires_upscaler], S->hires_denoise);
 	if (S->tiled_tile) ADD(", Tiled diffusion: %d, Tile overlap: %d", S->tiled_tile, S->tiled_overlap);
 	if (S->tiled_tile && S->tiled_pack > 1) ADD(", Tile batch: %d", S->tiled_pack);
+	if (!str_empty(S->path_control)) {
+		const char *b = S->path_control, *sl = strrchr(b, '/'); if (sl) b = sl + 1;
+		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
+		ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", (int)(e - b), b, S->control_strength, S->control_start, S->control_end);
+	}
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1343,6 +1458,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 		if (mlis_amd_set_lmask(S->eng, S->lmask.d) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	} else { mlis_amd_set_lmask(S->eng, NULL); if (!(S->tuflags & MLIS_TUF_LMASK)) mlis_tensor_free(&S->lmask); }
 
+	if ((r = control_apply(S, w_img, h_img)) < 0) return r;
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	S->image.flags &= ~LT_F_READY;
@@ -1353,6 +1469,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	mlis_amd_set_callback(S->eng, S->callback ? denoise_cb : NULL, S);
 	r = mlis_amd_denoise(S->eng, NULL);
 	S->rng_offset = mlis_amd_rng_offset(S->eng);
+	if (S->control_pass < 2) mlis_amd_control_info(S->eng, NULL, &S->control_evals[S->control_pass++]);
 	S->last_n_step = mlis_amd_last_n_step(S->eng); S->last_nfe = S->nfe_base + mlis_amd_last_nfe(S->eng); S->prg.nfe = S->last_nfe;
 	if (r < 0) {
 		if (r < -1 && r != MLIS_E_NAN) return r;                                  /* the callback's abort code */
@@ -1407,6 +1524,13 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);
 	if ((r = tiling_check(S)) < 0) return r;
 	if ((r = unet_tile_check(S)) < 0) return r;
+	{	/* ControlNet: model and image come together, the window is an interval */
+		const int has_model = !str_empty(S->path_control), has_image = tensor_good(&S->control_image);
+		if (has_model && !has_image) return api_error(S, MLIS_E_OPT_VALUE, "control_model '%s' without a control_image", S->path_control);
+		if (has_image && !has_model) return api_error(S, MLIS_E_OPT_VALUE, "control_image without a control_model");
+		if (S->control_start > S->control_end) return api_error(S, MLIS_E_OPT_VALUE, "invalid control window: control_start %g > control_end %g", S->control_start, S->control_end);
+	}
+	S->control_evals[0] = S->control_evals[1] = S->control_pass = 0;
 	S->tiled_tile = S->tiled_overlap = S->tiled_pack = 0;
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	int w_img = 0, h_img = 0, hires_n_step = 0;

@@ -193,3 +193,22 @@ MLB_API int tnconv_sd(const char* name, char* out, size_t out_size)
 	if (c.ovf) return mlsd_set_error(-1, "tensor name too long: %s", name);
 	return r;
 }
+
+/* ControlNet files in the original (cldm.py) layout, with or without a leading "control_model.": the copy of the UNet's encoder goes through the UNet's own rules,
+ * input_hint_block.K -> hint.K, zero_convs.I.0 -> zero.I, middle_block_out.0 -> mid_out, everything under the prefix "control".  Names of the UNet's decoder
+ * (output_blocks, out) and diffusers-named files return 0. */
+MLB_API int tnconv_controlnet(const char* name, char* out, size_t out_size)
+{
+	if (!name || !out || !out_size) return -1;
+	Cur c = { name, strlen(name), out, 0, out_size, 0 };
+	out[0] = 0;
+	int r = 0;
+	take(&c, "control_model.");
+	emitz(&c, "control.");
+	if (rep(&c, "input_hint_block.", "hint.")) r = finish(&c, 1);
+	else if (rep(&c, "zero_convs.", "zero.")) r = finish(&c, number(&c, NULL, 1, 1) && take(&c, "0."));
+	else if (rep(&c, "middle_block_out.0.", "mid_out.")) r = finish(&c, 1);
+	else if (peek(&c, "time_embed.") || peek(&c, "label_emb.0.") || peek(&c, "input_blocks.") || peek(&c, "middle_block.")) r = unet(&c);
+	if (c.ovf) return mlsd_set_error(-1, "tensor name too long: %s", name);
+	return r;
+}

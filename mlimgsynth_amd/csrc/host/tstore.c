@@ -214,8 +214,10 @@ MLB_API MLTStore* mlts_open_safetensors(const char* path, int convert_names) { r
 /* LoRA file (kohya naming): "lora_" prefix stripped, then tnconv_sd; an unmatched "*.lora_down.weight" is an error, other
  * unmatched tensors are dropped (tensor_callback_lora, src/mlimgsynth.c:1068-1092) */
 MLB_API MLTStore* mlts_open_lora(const char* path) { return open_store(path, 2); }
+/* ControlNet file (original cldm.py layout): names through tnconv_controlnet, anything it does not know is dropped */
+MLB_API MLTStore* mlts_open_controlnet(const char* path) { return open_store(path, 3); }
 
-/* one tensor of the file: renamed / split / dropped according to `mode` (0 raw, 1 model, 2 LoRA); <0 on error */
+/* one tensor of the file: renamed / split / dropped according to `mode` (0 raw, 1 model, 2 LoRA, 3 ControlNet); <0 on error */
 static int add_file_tensor(MLTStore* S, const char* name, const MLTSEntry* e, int mode)
 {
 	if (!mode) { ts_add(S, name, e); return 1; }
@@ -225,7 +227,7 @@ static int add_file_tensor(MLTStore* S, const char* name, const MLTSEntry* e, in
 		if (strncmp(name, "lora_", 5)) { S->n_unused++; return 0; }
 		nm = name + 5;
 	}
-	const int r = tnconv_sd(nm, conv, sizeof(conv));                     /* tensor_callback_main :1033-1055 */
+	const int r = mode == 3 ? tnconv_controlnet(nm, conv, sizeof(conv)) : tnconv_sd(nm, conv, sizeof(conv));      /* tensor_callback_main :1033-1055 */
 	if (r < 0) return -1;
 	if (mode == 2 && r == 0) {
 		const size_t l = strlen(nm);

@@ -101,7 +101,7 @@ static MLTensor* mlb_unet__embed(MLCtx* C, MLTensor* time, MLTensor* label, cons
 }
 
 /* total width of all cross-attention k/v projections of the graph (same walk as __in/__mid/__out) */
-static int unet_cross_kv_width(const UnetParams* P)
+static int unet_cross_kv_width_ex(const UnetParams* P, int with_out)
 {
 	int total = 0, im = 0, ds = 1;
 	for (; P->ch_mult[im]; ++im) {
@@ -110,23 +110,59 @@ static int unet_cross_kv_width(const UnetParams* P)
 	}
 	im--;
 	total += P->transf_depth[im] * 2 * P->n_ch * P->ch_mult[im];                                                                  /* mid */
+	if (!with_out) return total;                                                                                                  /* (the ControlNet: encoder and middle block) */
 	for (; im >= 0; --im, ds /= 2)
 		if (static_vector_in(P->attn_res, ds)) total += (P->n_res_blk + 1) * P->transf_depth[im] * 2 * P->n_ch * P->ch_mult[im];   /* out */
 	return total;
 }
 
+static int unet_cross_kv_width(const UnetParams* P) { return unet_cross_kv_width_ex(P, 1); }
+
 /* total width of the resnets' time-embedding projections (same walk; every resnet projects emb to its ch_out) */
-static int unet_emb_proj_width(const UnetParams* P)
+static int unet_emb_proj_width_ex(const UnetParams* P, int with_out)
 {
 	int total = 0, im = 0;
 	for (; P->ch_mult[im]; ++im) total += P->n_res_blk * P->n_ch * P->ch_mult[im];       /* in  */
 	im--;
 	total += 2 * P->n_ch * P->ch_mult[im];                                                /* mid */
+	if (!with_out) return total;
 	for (; im >= 0; --im) total += (P->n_res_blk + 1) * P->n_ch * P->ch_mult[im];         /* out */
 	return total;
 }
 
+/* base + gain * ctrl as a FRESH fp32 tensor (mlsd_ctrl_add): `ctrl` is a residual of the ControlNet plan, channels-last fp32 in that plan's memory, the gain one float
+ * in device memory.  The result has no producing GEMM and no fp16 form: a GroupNorm that reads it computes its own statistics (the producer's column statistics
+ * describe `base`), and nothing cached for `base` (d16, silu16) is taken for the sum. */
+static MLTensor* mlb_ctrl_add(MLCtx* C, MLTensor* base, const UnetControl* K, int i)
+{
+	if (!base || C->err) return NULL;
+	const int64_t rows = (int64_t)base->n * base->h * base->w;
+	if (i < 0 || i >= K->n || !K->r[i] || !K->gain || K->c[i] != base->c || K->rows[i] != base->h * base->w || K->n_img < 1 || base->n % K->n_img) {
+		mlctx_fail(C, "unet: control residual %d does not match a %d x %d x %d map", i, base->n, base->h * base->w, base->c); return NULL;
+	}
+	const float *b = mlt_need32(C, base);
+	if (!b) return NULL;
+	MLTensor *y = mlt_new(C, base->n, base->h, base->w, base->c);
+	y->sz32 = (size_t)rows * base->c * sizeof(float);
+	y->d32 = (float*)mlctx_dalloc(C, y->sz32, 0); y->ld32 = base->c;
+	if (!y->d32) return NULL;
+	MLOp *op = mlctx_op_new(C, OP_CTRL_ADD, "ctrl_add");
+	op->u.cadd.dst = y->d32; op->u.cadd.ld_dst = y->ld32; op->u.cadd.base = b; op->u.cadd.ld_base = base->ld32;
+	op->u.cadd.ctrl = K->r[i]; op->u.cadd.ld_ctrl = K->ld[i];
+	op->u.cadd.n_img = base->n; op->u.cadd.rows = base->h * base->w; op->u.cadd.C = base->c; op->u.cadd.n_ctrl = K->n_img; op->u.cadd.gain = K->gain;
+	return y;
+}
+
+static int unet_emb_proj_width(const UnetParams* P) { return unet_emb_proj_width_ex(P, 1); }
+
 MLB_API MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, const UnetParams* P)
+{
+	return mlb_unet_denoise_ctrl(C, x, time, ctx, label, P, NULL);
+}
+
+/* K != NULL: the UNet of a ControlNet (cldm.py ControlledUnetModel): mid.2's output and every tensor popped from the skip stack get g x the matching residual added
+ * (K->r[i] for the i-th tensor pushed, K->r[K->n - 1] for the middle block).  K == NULL records exactly the plan of mlb_unet_denoise. */
+MLB_API MLTensor* mlb_unet_denoise_ctrl(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, const UnetParams* P, const UnetControl* K)
 {
 	char name[64];
 	mlctx_block_begin(C);
@@ -179,6 +215,12 @@ MLB_API MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTens
 		y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));
 		if (!y || !mlt_need32(C, y)) return NULL;
 		mlb_release(C, x); x = y;
+		if (K) {
+			if (K->n != ns + 1) { mlctx_fail(C, "unet: %d control residuals for %d skip tensors and the middle block", K->n, ns); return NULL; }
+			y = mlb_ctrl_add(C, x, K, K->n - 1);
+			if (!y) return NULL;
+			mlb_release(C, x); x = y;
+		}
 	}
 
 	/* ---- mlb_unet__out, src/unet.c:219-261 */
@@ -188,6 +230,11 @@ MLB_API MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTens
 		for (int j=0; j<P->n_res_blk+1; ++j, ++i_oblk) {
 			if (ns <= 0) { mlctx_fail(C, "unet: skip stack underflow"); return NULL; }
 			MLTensor *hsk = stack[--ns];
+			if (K) {
+				MLTensor *hc = mlb_ctrl_add(C, hsk, K, ns);
+				if (!hc) return NULL;
+				mlb_release(C, hsk); hsk = hc;
+			}
 			MLTensor *cat = mlb_concat_ch(C, x, hsk);            /* ggml_concat(x, h, 2): zero-copy */
 			int i_sub = 0;
 			ch = P->n_ch * P->ch_mult[im];
@@ -300,10 +347,12 @@ MLB_API int unet_denoise_init_nc(UnetState* S, MLCtx* C, const UnetParams* P, un
 }
 
 /* second half of init, split so that callers may bind the x input to a resident latent first */
-MLB_API int unet_denoise_build(UnetState* S)
+MLB_API int unet_denoise_build(UnetState* S) { return unet_denoise_build_ctrl(S, NULL); }
+
+MLB_API int unet_denoise_build_ctrl(UnetState* S, const UnetControl* K)
 {
 	MLCtx *C = S->ctx;
-	S->t_out = mlb_unet_denoise(C, S->t_x, S->t_t, S->t_c, S->t_l, S->par);
+	S->t_out = mlb_unet_denoise_ctrl(C, S->t_x, S->t_t, S->t_c, S->t_l, S->par, K);
 	if (!S->t_out) return -1;
 	if (mlctx_prep(C) < 0) return -1;
 	return 1;
@@ -361,4 +410,157 @@ MLB_API int unet_denoise_run(UnetState* S, const LocalTensor* x, const LocalTens
 	if (P->ch_adm_in && (!label || label->n[0] != P->ch_adm_in)) return mlsd_set_error(-1, "unet_denoise_run: label must be [%d]", P->ch_adm_in);
 	if (dx != x) ltensor_resize(dx, x->n[0], x->n[1], x->n[2], x->n[3]);   /* ltensor_resize_like(dx, x) (:466) */
 	return unet_denoise_run_n(S, x->d, cond->d, label ? label->d : NULL, &sigma, dx->d);
+}
+
+/* ------------------------------------------------------------------ ControlNet (not in the reference; the published cldm.py ControlNet / ControlledUnetModel)
+ * A copy of the UNet's encoder and middle block that also sees a control image.  Parameters under the prefix "control":
+ *   time_embed.*, label_embed.*, in.*, mid.*      as under "unet."
+ *   hint.<0|2|..|14>                              input_hint_block: eight 3x3 convolutions on the RGB image at pixel size, SiLU between them, three of stride 2
+ *   zero.<i>                                      1x1 convolution on the i-th tensor the UNet would push on its skip stack; its output is residual i
+ *   mid_out                                       1x1 convolution on mid.2's output: the last residual
+ * The hint block depends on the image alone, so it is a plan of its own (control_hint_*) that runs once per image; the ControlNet plan takes its output as the fp32
+ * channels-last tensor `t_hint`, one copy per plan image, and adds it to in.conv's output in that convolution's epilogue. */
+MLB_API int control_hint_init(MLCtx* C, const UnetParams* P, unsigned w, unsigned h, MLTensor** t_img)
+{
+	if (w % 8 || h % 8 || !w || !h) return mlsd_set_error(-1, "control hint: image size %ux%u must be a multiple of 8", w, h);
+	mlctx_begin(C, "ControlHint");
+	mlctx_set_tprefix(C, "control");
+	*t_img = mlctx_input_new_img(C, "hint", w, h, 3, 1);
+	(void)P;
+	return 1;
+}
+
+MLB_API int control_hint_build(MLCtx* C, const UnetParams* P, MLTensor* t_img)
+{
+	static const int width[7] = { 16, 16, 32, 32, 96, 96, 256 }, stride[8] = { 1, 1, 2, 1, 2, 1, 2, 1 };
+	char name[32];
+	MLTensor *x = t_img;
+	mlctx_block_begin(C);
+	for (int i=0; i<8; ++i) {
+		MLEpilogue silu = {0}; silu.act = MLSD_ACT_SILU;
+		sprintf(name, "hint.%d", 2*i);
+		MLTensor *y = MLN(name, mlb_conv2d_ex(C, x, i < 7 ? width[i] : P->n_ch, 3, stride[i], 1, 0, T, i < 7 ? &silu : NULL));
+		if (!y) return -1;
+		if (i == 7) { if (!mlt_need32(C, y)) return -1; }
+		else if (!mlt_need16(C, y)) return -1;
+		if (i) mlb_release(C, x);
+		x = y;
+	}
+	if (mlctx_prep(C) < 0) return -1;
+	return 1;
+}
+
+MLB_API int controlnet_init_nc(ControlState* S, MLCtx* C, const UnetParams* P, unsigned lw, unsigned lh, unsigned n_batch, int n_ctx_tok)
+{
+	if (!n_ctx_tok) n_ctx_tok = 77;
+	if (n_ctx_tok < 0 || n_ctx_tok % 77 || n_ctx_tok > 77 * MLIS_AMD_MAX_WINDOWS) return mlsd_set_error(-1, "controlnet: context of %d rows (77 x W, W <= %d)", n_ctx_tok, MLIS_AMD_MAX_WINDOWS);
+	unet_params_init();
+	memset(S, 0, sizeof(*S));
+	mlctx_begin(C, "ControlNet");
+	mlctx_set_tprefix(C, "control");
+	S->t_x = mlctx_input_new_img(C, "x", lw, lh, P->n_ch_in, n_batch);
+	S->t_t = mlctx_input_new_seq(C, "t", MLT_F32, n_batch, 1, 1);
+	S->t_c = mlctx_input_new_seq(C, "c", MLT_F32, P->n_ctx, n_ctx_tok, n_batch);
+	if (P->ch_adm_in) S->t_l = mlctx_input_new_seq(C, "l", MLT_F32, P->ch_adm_in, 1, n_batch);
+	/* the hint embedding, channels-last fp32 [n_batch][lh lw][n_ch]: written by the caller straight into device memory (mlctx_tensor_device_f32), never by an op */
+	MLTensor *th = mlt_new(C, n_batch, lh, lw, P->n_ch);
+	th->sz32 = 0; th->ld32 = P->n_ch; th->def_op = -1;
+	th->d32 = (float*)mlctx_dalloc(C, (size_t)n_batch * lw * lh * P->n_ch * sizeof(float), 0);
+	snprintf(th->name, sizeof(th->name), "hint");
+	S->t_hint = th;
+	S->ctx = C; S->par = P; S->lw = lw; S->lh = lh; S->n_batch = n_batch;
+	return th->d32 ? 1 : -1;
+}
+
+/* residual i: zero.<i> on a tensor of the ControlNet's forward path (which goes on unchanged) */
+static int control_zero(MLCtx* C, ControlState* S, MLTensor* x, const char* name)
+{
+	if (S->n_res >= MLB_CONTROL_MAX) return mlctx_fail(C, "controlnet: more than %d residuals", MLB_CONTROL_MAX);
+	MLTensor *r = MLN(name, mlb_conv2d_ex(C, x, x->c, 1, 1, 0, 0, T, NULL));
+	if (!r || !mlt_need32(C, r)) return -1;
+	S->t_res[S->n_res++] = r;         /* never released: the UNet plan reads it */
+	return 1;
+}
+
+MLB_API MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, MLTensor* hint, const UnetParams* P)
+{
+	char name[64];
+	mlctx_block_begin(C);
+	if (mlb_cross_kv_batch(C, ctx, unet_cross_kv_width_ex(P, 0)) < 0) return NULL;
+	MLTensor *emb = mlb_unet__embed(C, time, label, P);
+	if (!emb) return NULL;
+	if (mlb_emb_proj_batch(C, emb, unet_emb_proj_width_ex(P, 0)) < 0) return NULL;
+	S->n_res = 0;
+
+	/* ---- the walk of mlb_unet__in; a zero convolution wherever the UNet pushes */
+	MLEpilogue eh = {0}; eh.resid = hint;                       /* h = in.conv(x) + hint block (cldm.py: guided_hint is added after the first input block only) */
+	x = MLN("in.conv", mlb_conv2d_ex(C, x, P->n_ch, 3, 1, 1, 0, T, &eh));
+	if (!x || !mlt_need32(C, x)) return NULL;
+	if (control_zero(C, S, x, "zero.0") < 0) return NULL;
+	int im=0, i_blk=0, ds=1, ch=P->n_ch;
+	for (; P->ch_mult[im]; ++im) {
+		if (im) {
+			ds *= 2; i_blk++;
+			sprintf(name, "in.%d.0", i_blk);
+			MLTensor *y = MLN(name, mlb_downsample(C, x, ch, false));
+			if (!y || !mlt_need32(C, y)) return NULL;
+			mlb_release(C, x); x = y;
+			sprintf(name, "zero.%d", S->n_res);
+			if (control_zero(C, S, x, name) < 0) return NULL;
+		}
+		for (int j=0; j<P->n_res_blk; ++j) {
+			i_blk++;
+			sprintf(name, "in.%d.0", i_blk);
+			ch = P->n_ch * P->ch_mult[im];
+			MLTensor *y = MLN(name, mlb_resnet_ex(C, x, emb, ch));
+			if (!y || !mlt_need32(C, y)) return NULL;
+			mlb_release(C, x); x = y;
+			if (static_vector_in(P->attn_res, ds)) {
+				sprintf(name, "in.%d.1", i_blk);
+				y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+				if (!y || !mlt_need32(C, y)) return NULL;
+				mlb_release(C, x); x = y;
+			}
+			sprintf(name, "zero.%d", S->n_res);
+			if (control_zero(C, S, x, name) < 0) return NULL;
+		}
+	}
+
+	/* ---- mlb_unet__mid, then mid_out */
+	im = 0; while (P->ch_mult[im+1]) im++;
+	ch = P->n_ch * P->ch_mult[im];
+	MLTensor *y = MLN("mid.0", mlb_resnet_ex(C, x, emb, ch));
+	if (!y || !mlt_need32(C, y)) return NULL;
+	mlb_release(C, x); x = y;
+	y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+	if (!y || !mlt_need32(C, y)) return NULL;
+	mlb_release(C, x); x = y;
+	y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));
+	if (!y || !mlt_need32(C, y)) return NULL;
+	mlb_release(C, x); x = y;
+	if (control_zero(C, S, x, "mid_out") < 0) return NULL;
+	mlb_release(C, x);
+	mlb_release(C, emb);
+	return S->t_res[S->n_res - 1];
+}
+
+MLB_API int controlnet_build(ControlState* S)
+{
+	MLCtx *C = S->ctx;
+	if (!mlb_controlnet(C, S, S->t_x, S->t_t, S->t_c, S->t_l, S->t_hint, S->par)) return -1;
+	if (mlctx_prep(C) < 0) return -1;
+	return 1;
+}
+
+/* what the UNet plan needs to know of a built ControlNet plan: where its residuals lie.  gain_dev: the float (device memory) every sum reads its gain from */
+MLB_API int controlnet_control(const ControlState* S, const float* gain_dev, UnetControl* K)
+{
+	memset(K, 0, sizeof(*K));
+	if (!S || !S->n_res || !gain_dev) return mlsd_set_error(-1, "controlnet_control: no built ControlNet plan");
+	for (int i=0; i<S->n_res; ++i) {
+		const MLTensor *r = S->t_res[i];
+		K->r[i] = r->d32; K->ld[i] = r->ld32; K->c[i] = r->c; K->rows[i] = r->h * r->w;
+	}
+	K->n = S->n_res; K->n_img = S->n_batch; K->gain = gain_dev;
+	return 1;
 }

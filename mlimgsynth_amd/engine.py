@@ -49,6 +49,12 @@ class AmdConfig(ctypes.Structure):
                 ("defer_weights", c_int), ("unet_split", c_int), ("n_ctx_tok", c_int)]
 
 
+class AmdControlConfig(ctypes.Structure):
+    """MLIS_AmdConfig as it stands, with its trailing field `control`.  AmdConfig above is the layout before that field: the field lies in what was the
+    structure's tail padding, so a zero-initialised AmdConfig is a valid configuration without a ControlNet."""
+    _fields_ = AmdConfig._fields_ + [("control", c_int)]
+
+
 _proto_done = False
 
 
@@ -252,13 +258,13 @@ def _proto2():
     l.dnsamp_schedule.argtypes = [ctypes.POINTER(UnetParams), c_int, c_int, c_f, c_f, FP]
     l.dnsamp_ancestral.argtypes = [c_f, c_f, c_f, FP, FP]
     l.mlis_amd_create.restype = vp
-    l.mlis_amd_create.argtypes = [ctypes.POINTER(AmdConfig), vp]
+    l.mlis_amd_create.argtypes = [vp, vp]               # (MLIS_AmdConfig*: an AmdConfig or an AmdControlConfig by reference)
     l.mlis_amd_create_ex.restype = vp
-    l.mlis_amd_create_ex.argtypes = [ctypes.POINTER(AmdConfig), c_int, vp]
+    l.mlis_amd_create_ex.argtypes = [vp, c_int, vp]
     l.mlis_amd_create_tiled.restype = vp
-    l.mlis_amd_create_tiled.argtypes = [ctypes.POINTER(AmdConfig), c_int, c_int, c_int, c_int, vp]
+    l.mlis_amd_create_tiled.argtypes = [vp, c_int, c_int, c_int, c_int, vp]
     l.mlis_amd_create_tiled_packed.restype = vp
-    l.mlis_amd_create_tiled_packed.argtypes = [ctypes.POINTER(AmdConfig), c_int, c_int, c_int, c_int, c_int, vp]
+    l.mlis_amd_create_tiled_packed.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp]
     l.mlis_amd_tile_pack.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int)]
     l.mlis_amd_tile_pack_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_window_starts.argtypes = [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]
@@ -296,6 +302,13 @@ def _proto2():
     l.mlis_amd_encoder_ctx.restype = vp
     l.mlis_amd_encoder_ctx.argtypes = [vp]
     l.mlis_amd_set_callback.argtypes = [vp, vp, vp]
+    l.mlis_amd_ctx_at.restype = vp
+    l.mlis_amd_ctx_at.argtypes = [vp, c_int]
+    l.mlis_amd_set_control_image.argtypes = [vp, FP]
+    l.mlis_amd_set_control_image_device.argtypes = [vp, vp]
+    l.mlis_amd_set_control.argtypes = [vp, c_f, c_f, c_f]
+    l.mlis_amd_control_active.argtypes = [c_int, c_int, c_f, c_f]
+    l.mlis_amd_control_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l._proto2_done = True
     return l
 
@@ -310,6 +323,11 @@ def randn(seed, offset, n):
     out = np.empty(n, np.float32)
     _proto2().rng_philox_randn(ctypes.byref(r), n, fptr(out))
     return out, r.offset
+
+
+def control_active(i_step, n_step, start, end):
+    """mlis_amd_control_active: whether step i_step of n_step lies in the control window (start n_step <= i_step + 0.5 < end n_step)"""
+    return bool(_proto2().mlis_amd_control_active(int(i_step), int(n_step), float(start), float(end)))
 
 
 def schedule(model, n_step, sched=1, f_t_ini=1.0, f_t_end=0.0):
@@ -372,11 +390,12 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, tiling=0):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, tiling=0):
         l = _proto2()
-        self.cfg = AmdConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
+        self.cfg = AmdControlConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
-                             int(defer_weights), int(unet_split), int(n_ctx_tok))    # n_ctx_tok: context rows, 77 x W (windowed prompt)
+                             int(defer_weights), int(unet_split), int(n_ctx_tok),     # n_ctx_tok: context rows, 77 x W (windowed prompt)
+                             int(bool(control)))                                      # control: the engine holds a ControlNet (set_control_image / set_control)
         if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
             tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)      # times up to unet_tile_batch windows per evaluation
             self.h = l.mlis_amd_create_tiled_packed(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), vp(stream))
@@ -430,6 +449,39 @@ class Generator:
         dx = np.empty_like(x)
         check1(_proto2().mlis_amd_dxdt(self.h, fptr(x), float(sigma), fptr(dx)), "mlis_amd_dxdt")
         return dx
+
+    def set_sampler(self, n_step=0, method="euler", sched=1, cfg_scale=7.0, s_ancestral=1.0, s_noise=0.0, f_t_ini=1.0, f_t_end=0.0):
+        """mlis_amd_set_sampler: the sampler options of the next generations (plans and weights stay; cfg_scale must stay on its side of 1)"""
+        f = _proto2().mlis_amd_set_sampler
+        f.argtypes = [vp, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f]
+        check1(f(self.h, int(n_step), self.METHODS.get(method, method), int(sched), cfg_scale, s_ancestral, s_noise, f_t_ini, f_t_end), "mlis_amd_set_sampler")
+
+    def set_control_image(self, hint):
+        """mlis_amd_set_control_image: hint [3][H][W] in [0,1] at the canvas's pixel size (runs the hint plan); None clears it"""
+        a = np.ascontiguousarray(hint, np.float32) if hint is not None else None
+        if a is not None and a.shape != (3, self.h_px, self.w):
+            raise ValueError(f"control image of shape {a.shape}, the engine takes {(3, self.h_px, self.w)}")
+        check1(_proto2().mlis_amd_set_control_image(self.h, fptr(a)), "mlis_amd_set_control_image")
+
+    def set_control(self, strength=1.0, start=0.0, end=1.0):
+        """mlis_amd_set_control: strength in [0, 2], step window 0 <= start <= end <= 1"""
+        check1(_proto2().mlis_amd_set_control(self.h, float(strength), float(start), float(end)), "mlis_amd_set_control")
+
+    def control_info(self):
+        """(residuals of the ControlNet plan -- 0 without one --, evaluations of the last denoise / dxdt in which it ran)"""
+        n, e = c_int(), c_int()
+        check1(_proto2().mlis_amd_control_info(self.h, ctypes.byref(n), ctypes.byref(e)), "mlis_amd_control_info")
+        return n.value, e.value
+
+    def ctx_at(self, i):
+        """plan i of the engine (0 UNet, 1 decoder, 2 encoder, 3 tile decoder, 4 tile encoder, 5 ControlNet, 6 hint block), or None"""
+        h = _proto2().mlis_amd_ctx_at(self.h, int(i))
+        if not h:
+            return None
+        c = MLCtx.__new__(MLCtx)
+        c.h = h
+        c.destroy = lambda: None
+        return c
 
     def tile_info(self):
         """(windows per evaluation -- 0 when not tiled --, window width, window height) in latent pixels"""

@@ -155,6 +155,19 @@ def window_blend_packed(eps_win, ld_win, eps_canvas, wsum, W, H, ww, wh, xs, ys,
           "mlsd_window_blend_packed")
 
 
+def ctrl_add(dst, ld_dst, base, ld_base, ctrl, ld_ctrl, n_img, rows_per_img, C, n_ctrl_img, gain_dev, stream=None):
+    """mlsd_ctrl_add: dst[n][r][c] = base[n][r][c] + gain * ctrl[n % n_ctrl_img][r][c] on channels-last fp32 maps (device pointers; gain_dev: one float in device
+    memory).  gain == 0 copies base bit for bit without reading ctrl."""
+    check(lib().mlsd_ctrl_add(vp(dst), c_i64(ld_dst), vp(base), c_i64(ld_base), vp(ctrl), c_i64(ld_ctrl), n_img, rows_per_img, C, n_ctrl_img, vp(gain_dev), vp(stream)),
+          "mlsd_ctrl_add")
+
+
+def window_gather_nhwc(src, W, H, C, dst, ww, wh, xs, ys, n_rep, stream=None):
+    """mlsd_window_gather_nhwc: dst [len(xs)][n_rep][wh][ww][C] <- src [H][W][C] at ((ys[s] + v) mod H, (xs[s] + u) mod W), bit copies (xs, ys: host lists)."""
+    ax, ay = (c_int * max(len(xs), 1))(*xs), (c_int * max(len(ys), 1))(*ys)
+    check(lib().mlsd_window_gather_nhwc(vp(src), W, H, C, vp(dst), ww, wh, ax, ay, len(xs), n_rep, vp(stream)), "mlsd_window_gather_nhwc")
+
+
 def tile_pack(n_win, n_batch, pack):
     """mlis_amd_tile_pack: (windows per plan evaluation, plan evaluations) for n_win windows of n_batch images and at most `pack` windows per evaluation; None if refused."""
     n_eval = c_int()

@@ -43,7 +43,8 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                       "IMAGE_MASK", "NO_DECODE", "TENSOR_USE_FLAGS", "SEED", "VAE_TILE", "UNET_SPLIT", "THREADS", "DUMP_FLAGS", "AUX_DIR",
                       "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101, AMD_HIRES_SCALE=102, AMD_HIRES_DENOISE=103,
                                                                             AMD_HIRES_STEPS=104, AMD_HIRES_UPSCALER=105, AMD_UNET_TILE=111,
-                                                                           AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121))
+                                                                           AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121, AMD_CONTROL_MODEL=131, AMD_CONTROL_IMAGE=132,
+                                                                           AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 MLIS_CTEF_NO_NORM = 1
 
@@ -290,6 +291,29 @@ class MLImgSynth:
             self.option_set("unet_tile_overlap", overlap)
         if batch is not None:
             self.option_set("unet_tile_batch", batch)
+
+    # ---- ControlNet
+    def control_set(self, model=None, image=None, strength=None, start=None, end=None):
+        """ControlNet: model = path of a safetensors ControlNet for the base model ("synth[:seed]" with a synth: model, "" = off); image = the finished control
+        map, a uint8 array [h][w][3] of any size (it is resampled to each pass's size) or False to clear it; strength in [0, 2]; start / end: the share of the
+        steps that is controlled.  None keeps a setting.  The options persist across generations."""
+        if model is not None:
+            self.option_set("control_model", model)
+        if image is False:
+            r = self._lib.mlis_option_set(self._ctx, MLIS_OPT_AMD_CONTROL_IMAGE, ctypes.c_void_p(None))     # noqa: F821
+            if r < 0:
+                raise RuntimeError("Failed to clear the control image: %s" % self.errstr_get())
+        elif image is not None:
+            import numpy as np
+            a = np.ascontiguousarray(image, np.uint8)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("control image must be uint8 [h][w][3]")
+            img = MLIS_Image_C(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), a.size, a.shape[1], a.shape[0], 3, 0)
+            if self._lib.mlis_option_set(self._ctx, MLIS_OPT_AMD_CONTROL_IMAGE, ctypes.byref(img)) < 0:     # noqa: F821  (the library copies the pixels)
+                raise RuntimeError("Failed to set the control image: %s" % self.errstr_get())
+        for name, v in (("control_strength", strength), ("control_start", start), ("control_end", end)):
+            if v is not None:
+                self.option_set(name, v)
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

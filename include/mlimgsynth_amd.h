@@ -86,6 +86,15 @@ typedef struct {
 } UnetControl;
 MLTensor* mlb_unet_denoise_ctrl(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* c, MLTensor* label, const UnetParams* P, const UnetControl* K);   /* K NULL: mlb_unet_denoise */
 int unet_denoise_build_ctrl(UnetState* S, const UnetControl* K);       /* unet_denoise_build with the control inputs; K NULL: the plain plan, op for op */
+/* FreeU (version 2 of the published code; not in the reference): at every decoder concatenation whose backbone has n_ch x the top multiplier channels (stage 1) or
+ * half of that (stage 2) the backbone's first half is scaled by (b - 1) x its normalised channel-mean map + 1 (mlsd_freeu_backbone) and the skip tensor's four lowest
+ * spatial frequencies by s (mlsd_freeu_skip), both into fresh fp32 tensors.  The factors are device data: plans and captured graphs never change with them. */
+typedef struct {
+	const float* f;                     /* device: b1, b2, s1, s2 (four floats, each read on its own) */
+	int n_stage1, n_stage2;             /* out: concatenations treated at each stage */
+} UnetFreeU;
+MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* c, MLTensor* label, const UnetParams* P, const UnetControl* K, UnetFreeU* F);   /* F NULL: mlb_unet_denoise_ctrl */
+int unet_denoise_build_freeu(UnetState* S, const UnetControl* K, UnetFreeU* F);      /* unet_denoise_build_ctrl with FreeU; F NULL: that plan, op for op */
 
 typedef struct {
 	MLCtx* ctx;
@@ -329,8 +338,10 @@ typedef struct {
 	int n_ctx_tok;           /* rows of the text context: 77 x W for a prompt of W 75-token windows (W <= 4); 0 = 77 */
 	/* (`control` lies in what was the structure's tail padding: the Python mirror keeps the layout before it as engine.AmdConfig and adds engine.AmdControlConfig,
 	 * of the same size.  A field added after it grows the structure: both mirrors then have to follow, and the size equality tests/test_controlnet_cpu.py asserts goes) */
-	int control;             /* 1: the engine holds a ControlNet (hint plan, ControlNet plan, UNet plan with control inputs); 0: none, every plan as without this field */
+	int control;             /* flags, MLIS_AMD_CONTROL_*.  bit 0 (_NET): the engine holds a ControlNet (hint plan, ControlNet plan, UNet plan with control inputs);
+	                          * bit 1 (_FREEU): the UNet plan runs the FreeU passes at its decoder concatenations (mlis_amd_set_freeu); 0: every plan as without this field */
 } MLIS_AmdConfig;
+enum { MLIS_AMD_CONTROL_NET = 1, MLIS_AMD_CONTROL_FREEU = 2 };
 
 /* progress callback (MLIS_Callback, include/mlimgsynth.h:405): called after every COMPLETED step (the stream is
  * synchronised first); a negative return aborts the generation and is returned by mlis_amd_denoise/generate */
@@ -412,6 +423,13 @@ int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* evals_con
 void mlis_amd_control_tag_set(MLIS_AmdCtx* S, uint64_t tag);
 uint64_t mlis_amd_control_tag(const MLIS_AmdCtx* S);
 const void* mlis_amd_control_image_device(MLIS_AmdCtx* S);   /* the control image the hint plan read: device NCHW fp32 [3][height][width], NULL without one */
+/* FreeU (engines created with MLIS_AMD_CONTROL_FREEU in MLIS_AmdConfig.control).  set_freeu: the backbone factors b1, b2 and the skip factors s1, s2 of stage 1
+ * (backbone of n_ch x the top multiplier channels) and stage 2 (half of that), each in [0, 4], else an error; they are four floats of device memory, so they change
+ * between generations, and under use_hipgraph, without touching a plan.  All four start at 1: until they are set the engine computes what one without the flag does.
+ * freeu_info: the decoder concatenations the plan treats at each stage (0, 0 without the flag).  Tiled and packed engines apply FreeU per window plan evaluation:
+ * the channel-mean map is normalised, and the skip planes are filtered, over the window, as an untiled evaluation of that window would. */
+int mlis_amd_set_freeu(MLIS_AmdCtx* S, float b1, float b2, float s1, float s2);
+int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stage2);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

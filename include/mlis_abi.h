@@ -73,7 +73,16 @@ typedef enum {
 	                                        * stays set across generations, like the model */
 	MLIS_OPT_AMD_CONTROL_STRENGTH = 133,   /* "control_strength" (float, default 1): 0 .. 2, the gain on the ControlNet's residuals */
 	MLIS_OPT_AMD_CONTROL_START = 134,      /* "control_start" (float, default 0) and */
-	MLIS_OPT_AMD_CONTROL_END = 135         /* "control_end" (float, default 1): the share of the steps that is controlled, 0 <= start <= end <= 1 (checked by mlis_generate) */
+	MLIS_OPT_AMD_CONTROL_END = 135,        /* "control_end" (float, default 1): the share of the steps that is controlled, 0 <= start <= end <= 1 (checked by mlis_generate) */
+	/* FreeU (version 2 of the published code): at the decoder's concatenations the backbone's first half of channels is amplified by a structure map and the skip
+	 * tensor's lowest spatial frequencies are damped; no weights, no training.  Stage 1 is the concatenations whose backbone has the UNet's top channel count (1280),
+	 * stage 2 those with half of it.  The defaults of the four factors are the authors' recommendation for version 2 as recalled when this was written; it could
+	 * not be checked against the publication then -- front ends list per-model values, set them explicitly where it matters.  A factor of 1 switches its part off. */
+	MLIS_OPT_AMD_FREEU = 141,              /* "freeu" (int 0 / 1, default 0): part of the engine key, engines with and without coexist in the two resident slots */
+	MLIS_OPT_AMD_FREEU_B1 = 142,           /* "freeu_b1" (float 0 .. 4, default 1.3): backbone factor of stage 1 */
+	MLIS_OPT_AMD_FREEU_B2 = 143,           /* "freeu_b2" (float 0 .. 4, default 1.4): backbone factor of stage 2 */
+	MLIS_OPT_AMD_FREEU_S1 = 144,           /* "freeu_s1" (float 0 .. 4, default 0.9): skip factor of stage 1 */
+	MLIS_OPT_AMD_FREEU_S2 = 145            /* "freeu_s2" (float 0 .. 4, default 0.2): skip factor of stage 2.  The four are device data of the engine: a change rebuilds nothing */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 

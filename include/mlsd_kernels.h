@@ -457,6 +457,23 @@ int mlsd_window_blend_packed(const float* eps_win, int64_t ld_win, float* eps_ca
 int mlsd_ctrl_add(float* dst, int64_t ld_dst, const float* base, int64_t ld_base, const float* ctrl, int64_t ld_ctrl, int n_img, int rows_per_img, int C, int n_ctrl_img,
                   const float* gain_dev, void* stream);
 int mlsd_window_gather_nhwc(const float* src, int W, int H, int C, float* dst, int ww, int wh, const int* xs, const int* ys, int n_slots, int n_rep, void* stream);
+/* FreeU, version 2 of the published code (csrc/hip/freeu.hip; not in the reference).  Channels-last fp32 maps of n_img images with row strides ld_* (floats).
+ *   freeu_backbone: m[n,p] = mean_c src[n,p,c]; mh = (m - min_p m) / (max_p m - min_p m) per image; dst[n,p,c] = src[n,p,c] ((b - 1) mh[n,p] + 1) for c < C / 2,
+ *              src's bits for c >= C / 2.  Where max == min (the published code divides by zero) the factor is 1.
+ *   freeu_skip:  the published Fourier_filter with threshold 1 on planes of H x W, per image and channel: the four centred DFT bins {0,-1} x {0,-1} times s, the real
+ *              part of the inverse, in closed form (seven plane sums, a seven-term apply).  The form holds for H, W >= 2; 2 .. 1024 per side are accepted.
+ *   b_dev / s_dev are ONE float in device memory, read when the kernels run: they may change between launches of a captured graph.  A value of exactly 1 makes dst
+ *   a bit copy of src: no reduction runs and the workspace is never read.
+ *   ws: mlsd_freeu_ws_bytes(n_img, H, W, C) bytes (rows_per_img = H W for the backbone; the size serves either call), 16-byte aligned, contents irrelevant.
+ *   Sums are taken in a fixed order without atomics (the same bits every run): 256 slots that each add ceil(n / 256) terms in sequence, then a balanced tree of 8
+ *   levels; mlsd_freeu_depth(n) = ceil(n / 256) - 1 + 8 (pure, host) is the largest number of fp32 additions between a term and its finished sum of n terms
+ *   (n = C for the backbone's mean, n = H W for the filter's plane sums).
+ *   Refused before any launch: C not a multiple of 8 (C / 2 must fall on a 16-byte vector), a stride below C or not a multiple of 4, a pointer not 16-byte
+ *   aligned, H or W outside 2 .. 1024 (skip), dst, src, ws and the factor overlapping one another. */
+int mlsd_freeu_backbone(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, int n_img, int rows_per_img, int C, float* ws, const float* b_dev, void* stream);
+int mlsd_freeu_skip(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, int n_img, int H, int W, int C, float* ws, const float* s_dev, void* stream);
+size_t mlsd_freeu_ws_bytes(int n_img, int H, int W, int C);
+int mlsd_freeu_depth(int n_terms);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

@@ -323,6 +323,7 @@ static const char k_usage[] =
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
 "ControlNet:  --control-model PATH|synth[:SEED]   --control-image PATH   --control-strength F   --control-start F   --control-end F\n"
+"FreeU:       --freeu BOOL   --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";

@@ -95,6 +95,10 @@ struct MLIS_AmdCtx {
 	float ctl_strength, ctl_start, ctl_end;
 	int ctl_step_on;            /* the current step lies in the window (mlis_amd_control_active); mlis_amd_dxdt has no step: always */
 	int ctl_evals;              /* evaluations of the last denoise / dxdt in which the ControlNet plan ran */
+	/* FreeU (MLIS_AMD_CONTROL_FREEU): the UNet plan was built with the address of d_freeu; mlis_amd_set_freeu writes the four floats */
+	UnetFreeU fu;
+	float *d_freeu;             /* [4] b1, b2, s1, s2; all 1 (the plan's FreeU passes copy) until they are set */
+	float freeu_f[4];
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -107,6 +111,7 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	if (S->ctl_ctx) mlctx_destroy(S->ctl_ctx);
 	if (S->hint_ctx) mlctx_destroy(S->hint_ctx);
 	mlsd_free(S->d_gain);
+	mlsd_free(S->d_freeu);
 	if (S->dec_ctx) mlctx_destroy(S->dec_ctx);
 	if (S->enc_ctx) mlctx_destroy(S->enc_ctx);
 	if (S->dect_ctx) mlctx_destroy(S->dect_ctx);
@@ -275,7 +280,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (S->c.method > SOLVER_METHOD_DPMPP2S) { mlsd_set_error(-1, "invalid sampling method %d", S->c.method); goto err; }
 	if (!(S->c.f_t_ini > 0)) S->c.f_t_ini = 1;
 	if (!S->c.weight_seed) S->c.weight_seed = 1234;
-	if (S->c.control != 0 && S->c.control != 1) { mlsd_set_error(-1, "control %d: 0 none, 1 ControlNet", S->c.control); goto err; }
+	if (S->c.control & ~(MLIS_AMD_CONTROL_NET | MLIS_AMD_CONTROL_FREEU)) { mlsd_set_error(-1, "control %d: bit 0 ControlNet, bit 1 FreeU", S->c.control); goto err; }
 	S->ctl_strength = 1; S->ctl_start = 0; S->ctl_end = 1; S->ctl_step_on = 1;
 	if (unet_params_get(S->model, &S->unet_p) < 0) goto err;
 	if (vae_params_get(S->model, &S->vae_p) < 0) goto err;
@@ -311,7 +316,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (mlsd_malloc((void**)&S->d_cin, (size_t)S->PB*4)) goto err;
 
 	/* ---- ControlNet: the hint plan at the canvas's pixel size and the ControlNet plan on the UNet plan's inputs, both before the UNet plan, which takes the residuals' addresses */
-	if (S->c.control) {
+	if (S->c.control & MLIS_AMD_CONTROL_NET) {
 		if (mlsd_malloc((void**)&S->d_gain, 256) || mlsd_memset(S->d_gain, 0, 256, stream)) goto err;
 		S->hint_ctx = mlctx_new(stream);
 		mlctx_set_conv_wrap(S->hint_ctx, S->tiling);
@@ -341,7 +346,13 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
 	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
 	if (mlctx_input_bind(S->unet.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
-	if (unet_denoise_build_ctrl(&S->unet, S->c.control ? &S->ctl_k : NULL) < 0) goto err;
+	if (S->c.control & MLIS_AMD_CONTROL_FREEU) {      /* the factors live in device memory from the start: all 1, every FreeU pass of the plan a copy */
+		for (int i=0;i<4;++i) S->freeu_f[i] = 1;
+		if (mlsd_malloc((void**)&S->d_freeu, 256) || mlsd_memset(S->d_freeu, 0, 256, stream) || mlsd_memcpy(S->d_freeu, S->freeu_f, sizeof(S->freeu_f), 0, stream)
+				|| mlsd_stream_sync(stream)) goto err;
+		S->fu.f = S->d_freeu;
+	}
+	if (unet_denoise_build_freeu(&S->unet, (S->c.control & MLIS_AMD_CONTROL_NET) ? &S->ctl_k : NULL, (S->c.control & MLIS_AMD_CONTROL_FREEU) ? &S->fu : NULL) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
 
 	/* ---- decoder plan, latent input bound to the same resident latent */
@@ -965,6 +976,28 @@ MLB_API int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* e
 	if (!S) return -1;
 	if (n_residuals) *n_residuals = S->ctl_ctx ? S->ctl.n_res : 0;
 	if (evals_controlled) *evals_controlled = S->ctl_evals;
+	return 1;
+}
+
+/* ------------------------------------------------------------------ FreeU
+ * the factors of the next evaluations: four floats in device memory that the UNet plan's FreeU passes read when they run (a factor of exactly 1 makes its
+ * passes copies).  Nothing is rebuilt or captured again; tiled and packed engines need nothing more, every window plan evaluation runs the same passes. */
+MLB_API int mlis_amd_set_freeu(MLIS_AmdCtx* S, float b1, float b2, float s1, float s2)
+{
+	if (!S || !S->d_freeu) return fail("mlis_amd_set_freeu: the engine was created without FreeU");
+	const float f[4] = { b1, b2, s1, s2 };
+	for (int i=0;i<4;++i) if (!(f[i] >= 0 && f[i] <= 4)) return mlsd_set_error(-1, "FreeU factor %g: 0 .. 4", f[i]);
+	if (mlsd_stream_sync(S->stream)) return -1;      /* (the source of the copy is engine memory: nothing in flight reads the old values afterwards) */
+	memcpy(S->freeu_f, f, sizeof(f));
+	if (mlsd_memcpy(S->d_freeu, S->freeu_f, sizeof(f), 0, S->stream) || mlsd_stream_sync(S->stream)) return -1;
+	return 1;
+}
+
+MLB_API int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stage2)
+{
+	if (!S) return -1;
+	if (n_stage1) *n_stage1 = S->d_freeu ? S->fu.n_stage1 : 0;
+	if (n_stage2) *n_stage2 = S->d_freeu ? S->fu.n_stage2 : 0;
 	return 1;
 }
 

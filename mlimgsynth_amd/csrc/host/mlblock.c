@@ -664,6 +664,10 @@ static int run_op(MLCtx* C, MLOp* op)
 	case OP_COPY_F32: return mlsd_memcpy(op->u.copy.dst, op->u.copy.src, op->u.copy.nbytes, 2, st);
 	case OP_CTRL_ADD: return mlsd_ctrl_add(op->u.cadd.dst, op->u.cadd.ld_dst, op->u.cadd.base, op->u.cadd.ld_base, op->u.cadd.ctrl, op->u.cadd.ld_ctrl,
 	                                   op->u.cadd.n_img, op->u.cadd.rows, op->u.cadd.C, op->u.cadd.n_ctrl, op->u.cadd.gain, st);
+	case OP_FREEU_BACKBONE: return mlsd_freeu_backbone(op->u.freeu.dst, op->u.freeu.ld_dst, op->u.freeu.src, op->u.freeu.ld_src, op->u.freeu.n_img,
+	                                   op->u.freeu.H * op->u.freeu.W, op->u.freeu.C, op->u.freeu.ws, op->u.freeu.f, st);
+	case OP_FREEU_SKIP: return mlsd_freeu_skip(op->u.freeu.dst, op->u.freeu.ld_dst, op->u.freeu.src, op->u.freeu.ld_src, op->u.freeu.n_img, op->u.freeu.H, op->u.freeu.W,
+	                                   op->u.freeu.C, op->u.freeu.ws, op->u.freeu.f, st);
 	case OP_XA_VT: return mlsd_xattn_pack_vt(op->u.xavt.v, op->u.xavt.ldv, op->u.xavt.n_img, op->u.xavt.Tk, op->u.xavt.N, op->u.xavt.vt, st);
 	}
 	return mlsd_set_error(-1, "unknown op kind %d", (int)op->kind);
@@ -1079,6 +1083,7 @@ static int op_outputs(const MLOp* o, const void* out[3])
 	case OP_COPY_F32: out[n++] = o->u.copy.dst; break;
 	case OP_XA_VT: out[n++] = o->u.xavt.vt; break;
 	case OP_CTRL_ADD: out[n++] = o->u.cadd.dst; break;
+	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: out[n++] = o->u.freeu.dst; out[n++] = o->u.freeu.ws; break;
 	}
 	return n;
 }
@@ -1726,6 +1731,7 @@ MLB_API double mlctx_op_bytes(const MLCtx* C, int i)
 	case OP_ACT: return (double)op->u.act.n * 6.0;
 	case OP_COPY_F32: return 2.0 * op->u.copy.nbytes;
 	case OP_CTRL_ADD: return 12.0 * op->u.cadd.n_img * (double)op->u.cadd.rows * op->u.cadd.C;      /* base and ctrl read, dst written (gain 0: ctrl is not read) */
+	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: return 12.0 * op->u.freeu.n_img * (double)op->u.freeu.H * op->u.freeu.W * op->u.freeu.C;      /* src read by the reduction and by the apply, dst written (factor 1: one read) */
 	default: return 0;
 	}
 }

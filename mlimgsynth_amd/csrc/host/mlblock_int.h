@@ -12,7 +12,7 @@ int mlsd_set_error(int code, const char* fmt, ...);
 
 typedef enum {
 	OP_GEMM, OP_ATTN, OP_GN, OP_LN, OP_NCHW2NHWC, OP_NHWC2NCHW, OP_TEMB, OP_ACT, OP_CLIP_EMBED, OP_SOFTMAX,
-	OP_COPY_F32, OP_XA_VT, OP_ATTN_CTX, OP_CTRL_ADD,
+	OP_COPY_F32, OP_XA_VT, OP_ATTN_CTX, OP_CTRL_ADD, OP_FREEU_BACKBONE, OP_FREEU_SKIP,
 } MLOpKind;
 
 typedef struct MLOp {
@@ -37,6 +37,7 @@ typedef struct MLOp {
 		struct { const float* in; int64_t ld_in; void* out; int64_t ld_out; int rows, cols; float scale; } smax;
 		struct { const void* src; void* dst; size_t nbytes; } copy;
 		struct { float* dst; int64_t ld_dst; const float* base; int64_t ld_base; const float* ctrl; int64_t ld_ctrl; int n_img, rows, C, n_ctrl; const float* gain; } cadd;   /* mlsd_ctrl_add: ctrl and gain are device memory of another plan / the engine */
+		struct { float* dst; int64_t ld_dst; const float* src; int64_t ld_src; int n_img, H, W, C; float* ws; const float* f; } freeu;   /* mlsd_freeu_backbone (rows = H W) / mlsd_freeu_skip: ws is plan memory, f one float of the engine's device memory */
 		struct { const void* v; int64_t ldv; int n_img, Tk, N; void* vt; } xavt;      /* V^T pack of a cross attention that ends its q projection (mlsd_xattn_pack_vt) */
 	} u;
 } MLOp;

@@ -49,6 +49,7 @@ struct MLIS_Ctx {
 	uint64_t control_image_gen;             /* counts the control images set: the mark an engine keeps on the one it holds (never 0 once an image is set) */
 	float control_strength, control_start, control_end;
 	int control_evals[2], control_pass;     /* controlled evaluations of the last generation's passes (mlis_amd_control_evals) */
+	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
 	int method, sched, n_step;
@@ -145,8 +146,10 @@ static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
 static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };            /* ids from MLIS_OPT_AMD_UNET_TILE */
 static const char* const k_option_amd3[] = { "unet_tile_batch" };                           /* ids from MLIS_OPT_AMD_UNET_TILE_BATCH */
 static const char* const k_option_amd4[] = { "control_model", "control_image", "control_strength", "control_start", "control_end" };   /* ids from MLIS_OPT_AMD_CONTROL_MODEL */
+static const char* const k_option_amd5[] = { "freeu", "freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2" };   /* ids from MLIS_OPT_AMD_FREEU */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_FREEU && x < MLIS_OPT_AMD_FREEU + COUNTOF(k_option_amd5)) return k_option_amd5[x - MLIS_OPT_AMD_FREEU];
 	if (x >= MLIS_OPT_AMD_CONTROL_MODEL && x < MLIS_OPT_AMD_CONTROL_MODEL + COUNTOF(k_option_amd4)) return k_option_amd4[x - MLIS_OPT_AMD_CONTROL_MODEL];
 	if (x >= MLIS_OPT_AMD_UNET_TILE_BATCH && x < MLIS_OPT_AMD_UNET_TILE_BATCH + COUNTOF(k_option_amd3)) return k_option_amd3[x - MLIS_OPT_AMD_UNET_TILE_BATCH];
 	if (x >= MLIS_OPT_AMD_UNET_TILE && x < MLIS_OPT_AMD_UNET_TILE + COUNTOF(k_option_amd2)) return k_option_amd2[x - MLIS_OPT_AMD_UNET_TILE];
@@ -163,6 +166,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i3 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE_BATCH + i3);
 	const int i4 = from_list(k_option_amd4, COUNTOF(k_option_amd4), 1, s, strlen(s));
 	if (i4 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_MODEL + i4);
+	const int i5 = from_list(k_option_amd5, COUNTOF(k_option_amd5), 1, s, strlen(s));
+	if (i5 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_FREEU + i5);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -226,6 +231,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->unet_tile_overlap = -1;
 	S->unet_tile_batch = 1;
 	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
+	S->freeu_f[0] = 1.3f; S->freeu_f[1] = 1.4f; S->freeu_f[2] = 0.9f; S->freeu_f[3] = 0.2f;      /* b1, b2, s1, s2 (mlis_abi.h on where these come from) */
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -242,6 +248,11 @@ static int engine_has_control(MLIS_AmdCtx* e)
 {	/* asked of the engine itself, not read out of its key */
 	int n_res = 0;
 	return e && mlis_amd_control_info(e, &n_res, NULL) > 0 && n_res > 0;
+}
+static int engine_has_freeu(MLIS_AmdCtx* e)
+{
+	int n1 = 0, n2 = 0;
+	return e && mlis_amd_freeu_info(e, &n1, &n2) > 0 && n1 + n2 > 0;
 }
 static void control_engines_drop(MLIS_Ctx* S)
 {	/* the resident engines built with a ControlNet */
@@ -583,6 +594,11 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_CONTROL_STRENGTH: if (!arg_float(A, 0, 2, 1, &f)) BAD_VALUE; S->control_strength = f; break;
 	case MLIS_OPT_AMD_CONTROL_START: if (!arg_float(A, 0, 1, 0, &f)) BAD_VALUE; S->control_start = f; break;      /* start <= end: checked by mlis_generate, the two are set one by one */
 	case MLIS_OPT_AMD_CONTROL_END: if (!arg_float(A, 0, 1, 1, &f)) BAD_VALUE; S->control_end = f; break;
+	case MLIS_OPT_AMD_FREEU: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->freeu = i; break;      /* the one FreeU option in the engine key */
+	case MLIS_OPT_AMD_FREEU_B1: if (!arg_float(A, 0, 4, 1.3f, &f)) BAD_VALUE; S->freeu_f[0] = f; break;
+	case MLIS_OPT_AMD_FREEU_B2: if (!arg_float(A, 0, 4, 1.4f, &f)) BAD_VALUE; S->freeu_f[1] = f; break;
+	case MLIS_OPT_AMD_FREEU_S1: if (!arg_float(A, 0, 4, 0.9f, &f)) BAD_VALUE; S->freeu_f[2] = f; break;
+	case MLIS_OPT_AMD_FREEU_S2: if (!arg_float(A, 0, 4, 0.2f, &f)) BAD_VALUE; S->freeu_f[3] = f; break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -654,6 +670,9 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
 	case MLIS_OPT_AMD_CONTROL_START: { float *p = va_arg(ap, float*); if (p) *p = S->control_start; } break;
 	case MLIS_OPT_AMD_CONTROL_END: { float *p = va_arg(ap, float*); if (p) *p = S->control_end; } break;
+	case MLIS_OPT_AMD_FREEU: { int *p = va_arg(ap, int*); if (p) *p = S->freeu; } break;
+	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
+		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
 	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
 	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
@@ -1031,11 +1050,13 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	int nk = snprintf(key, sizeof(key), "%s/%dx%d/b%d/g%d/t%d/w%d/s%d/c%d/x%d", S->mname, lw, lh, B, S->cfg_scale > 1, tae, S->wtype, !!(S->flags & CF_UNET_SPLIT), ctx_tok, S->tiling);
 	if (tile && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/u%do%dp%d", tile, overlap, S->unet_tile_batch);
 	const int control = !str_empty(S->path_control);      /* (one ControlNet per context: a changed file drops the engines, so the key only says whether) */
-	if (control && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/k1");
+	if (control && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/k1");
+	const int freeu = S->freeu != 0;                      /* (the factors are device data of the engine: only on / off is built in) */
+	if (freeu && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/f1");
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	/* (a slot serves when its key matches AND it holds a ControlNet exactly if one is wanted: a key cut short by a long model name cannot pass one for the other) */
-#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control)
+#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control && engine_has_freeu(e) == freeu)
 	if (!SLOT_IS(S->eng, S->eng_key) && SLOT_IS(S->eng2, S->eng2_key)) {      /* the other resident engine: they change places */
 		MLIS_AmdCtx *e = S->eng; char k[sizeof(S->eng_key)]; memcpy(k, S->eng_key, sizeof(k));
 		S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(k));
@@ -1054,7 +1075,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		c.control = control;
+		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0);
 		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
@@ -1393,6 +1414,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
 		ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", (int)(e - b), b, S->control_strength, S->control_start, S->control_end);
 	}
+	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1459,6 +1481,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	} else { mlis_amd_set_lmask(S->eng, NULL); if (!(S->tuflags & MLIS_TUF_LMASK)) mlis_tensor_free(&S->lmask); }
 
 	if ((r = control_apply(S, w_img, h_img)) < 0) return r;
+	if (S->freeu && mlis_amd_set_freeu(S->eng, S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	S->image.flags &= ~LT_F_READY;

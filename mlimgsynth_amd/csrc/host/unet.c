@@ -155,6 +155,32 @@ static MLTensor* mlb_ctrl_add(MLCtx* C, MLTensor* base, const UnetControl* K, in
 
 static int unet_emb_proj_width(const UnetParams* P) { return unet_emb_proj_width_ex(P, 1); }
 
+/* FreeU on one operand of a decoder concatenation, as a FRESH fp32 tensor like mlb_ctrl_add's (no producer statistics, no cached fp16 form): kind OP_FREEU_BACKBONE
+ * (mlsd_freeu_backbone) or OP_FREEU_SKIP (mlsd_freeu_skip); `f` is the factor, one float in device memory.  The workspace is plan memory, free again for whatever
+ * is recorded after the op. */
+static MLTensor* mlb_freeu(MLCtx* C, MLTensor* t, const float* f, MLOpKind kind)
+{
+	if (!t || C->err) return NULL;
+	if (!f || (t->c & 7) || t->h < 2 || t->w < 2) {
+		mlctx_fail(C, "unet: FreeU on a %d x %d x %d map (channels a multiple of 8, at least 2 x 2 pixels)", t->w, t->h, t->c); return NULL;
+	}
+	const float *src = mlt_need32(C, t);
+	if (!src) return NULL;
+	const int64_t rows = (int64_t)t->n * t->h * t->w;
+	MLTensor *y = mlt_new(C, t->n, t->h, t->w, t->c);
+	y->sz32 = (size_t)rows * t->c * sizeof(float);
+	y->d32 = (float*)mlctx_dalloc(C, y->sz32, 0); y->ld32 = t->c;
+	const size_t sz_ws = mlsd_freeu_ws_bytes(t->n, t->h, t->w, t->c);
+	float *ws = (float*)mlctx_dalloc(C, sz_ws, 0);
+	if (!y->d32 || !ws) return NULL;
+	MLOp *op = mlctx_op_new(C, kind, kind == OP_FREEU_BACKBONE ? "freeu_backbone" : "freeu_skip");
+	op->u.freeu.dst = y->d32; op->u.freeu.ld_dst = y->ld32; op->u.freeu.src = src; op->u.freeu.ld_src = t->ld32;
+	op->u.freeu.n_img = t->n; op->u.freeu.H = t->h; op->u.freeu.W = t->w; op->u.freeu.C = t->c; op->u.freeu.ws = ws; op->u.freeu.f = f;
+	mlctx_drelease(C, ws, sz_ws);
+	return y;
+}
+
+
 MLB_API MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, const UnetParams* P)
 {
 	return mlb_unet_denoise_ctrl(C, x, time, ctx, label, P, NULL);
@@ -163,6 +189,16 @@ MLB_API MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTens
 /* K != NULL: the UNet of a ControlNet (cldm.py ControlledUnetModel): mid.2's output and every tensor popped from the skip stack get g x the matching residual added
  * (K->r[i] for the i-th tensor pushed, K->r[K->n - 1] for the middle block).  K == NULL records exactly the plan of mlb_unet_denoise. */
 MLB_API MLTensor* mlb_unet_denoise_ctrl(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, const UnetParams* P, const UnetControl* K)
+{
+	return mlb_unet_denoise_freeu(C, x, time, ctx, label, P, K, NULL);
+}
+
+/* F != NULL: FreeU (version 2 of the published code) at the decoder's concatenations.  The stage follows the BACKBONE's channel count as the published forward does:
+ * n_ch x the top multiplier (1280 for SD1 / SD2 / SDXL) is stage 1 with (b1, s1), half of that stage 2 with (b2, s2), anything else is left alone.  There the
+ * backbone goes through mlsd_freeu_backbone and the popped skip tensor -- after the control sum, where there is one -- through mlsd_freeu_skip, then the two are
+ * concatenated.  F->n_stage1 / n_stage2 count the concatenations treated.  F == NULL records exactly the plan of mlb_unet_denoise_ctrl. */
+MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* ctx, MLTensor* label, const UnetParams* P, const UnetControl* K,
+	UnetFreeU* F)
 {
 	char name[64];
 	mlctx_block_begin(C);
@@ -226,14 +262,28 @@ MLB_API MLTensor* mlb_unet_denoise_ctrl(MLCtx* C, MLTensor* x, MLTensor* time, M
 	/* ---- mlb_unet__out, src/unet.c:219-261 */
 	im = 0; ds = 1;
 	while (P->ch_mult[im+1]) { im++; ds *= 2; }
+	const int ch_top = P->n_ch * P->ch_mult[im];
+	if (F) { F->n_stage1 = F->n_stage2 = 0; if (!F->f) { mlctx_fail(C, "unet: FreeU without its factors"); return NULL; } }
 	for (int i_oblk=0; im>=0; --im) {
 		for (int j=0; j<P->n_res_blk+1; ++j, ++i_oblk) {
 			if (ns <= 0) { mlctx_fail(C, "unet: skip stack underflow"); return NULL; }
 			MLTensor *hsk = stack[--ns];
+			const int fu_stage = !F ? 0 : x->c == ch_top ? 1 : 2 * x->c == ch_top ? 2 : 0;
+			if (fu_stage) {
+				MLTensor *xb = mlb_freeu(C, x, F->f + (fu_stage - 1), OP_FREEU_BACKBONE);
+				if (!xb) return NULL;
+				mlb_release(C, x); x = xb;
+			}
 			if (K) {
 				MLTensor *hc = mlb_ctrl_add(C, hsk, K, ns);
 				if (!hc) return NULL;
 				mlb_release(C, hsk); hsk = hc;
+			}
+			if (fu_stage) {
+				MLTensor *hf = mlb_freeu(C, hsk, F->f + 2 + (fu_stage - 1), OP_FREEU_SKIP);
+				if (!hf) return NULL;
+				mlb_release(C, hsk); hsk = hf;
+				if (fu_stage == 1) F->n_stage1++; else F->n_stage2++;
 			}
 			MLTensor *cat = mlb_concat_ch(C, x, hsk);            /* ggml_concat(x, h, 2): zero-copy */
 			int i_sub = 0;
@@ -349,10 +399,12 @@ MLB_API int unet_denoise_init_nc(UnetState* S, MLCtx* C, const UnetParams* P, un
 /* second half of init, split so that callers may bind the x input to a resident latent first */
 MLB_API int unet_denoise_build(UnetState* S) { return unet_denoise_build_ctrl(S, NULL); }
 
-MLB_API int unet_denoise_build_ctrl(UnetState* S, const UnetControl* K)
+MLB_API int unet_denoise_build_ctrl(UnetState* S, const UnetControl* K) { return unet_denoise_build_freeu(S, K, NULL); }
+
+MLB_API int unet_denoise_build_freeu(UnetState* S, const UnetControl* K, UnetFreeU* F)
 {
 	MLCtx *C = S->ctx;
-	S->t_out = mlb_unet_denoise_ctrl(C, S->t_x, S->t_t, S->t_c, S->t_l, S->par, K);
+	S->t_out = mlb_unet_denoise_freeu(C, S->t_x, S->t_t, S->t_c, S->t_l, S->par, K, F);
 	if (!S->t_out) return -1;
 	if (mlctx_prep(C) < 0) return -1;
 	return 1;

@@ -55,6 +55,9 @@ class AmdControlConfig(ctypes.Structure):
     _fields_ = AmdConfig._fields_ + [("control", c_int)]
 
 
+CONTROL_NET, CONTROL_FREEU = 1, 2       # MLIS_AMD_CONTROL_*: the bits of `control`
+
+
 _proto_done = False
 
 
@@ -309,6 +312,8 @@ def _proto2():
     l.mlis_amd_set_control.argtypes = [vp, c_f, c_f, c_f]
     l.mlis_amd_control_active.argtypes = [c_int, c_int, c_f, c_f]
     l.mlis_amd_control_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    l.mlis_amd_set_freeu.argtypes = [vp, c_f, c_f, c_f, c_f]
+    l.mlis_amd_freeu_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l._proto2_done = True
     return l
 
@@ -390,12 +395,12 @@ class Generator:
 
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
-                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, tiling=0):
+                 defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, freeu=False, tiling=0):
         l = _proto2()
         self.cfg = AmdControlConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
                              int(defer_weights), int(unet_split), int(n_ctx_tok),     # n_ctx_tok: context rows, 77 x W (windowed prompt)
-                             int(bool(control)))                                      # control: the engine holds a ControlNet (set_control_image / set_control)
+                             (CONTROL_NET if control else 0) | (CONTROL_FREEU if freeu else 0))   # control: flags -- a ControlNet (set_control_image / set_control), FreeU (set_freeu)
         if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
             tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)      # times up to unet_tile_batch windows per evaluation
             self.h = l.mlis_amd_create_tiled_packed(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), vp(stream))
@@ -472,6 +477,16 @@ class Generator:
         n, e = c_int(), c_int()
         check1(_proto2().mlis_amd_control_info(self.h, ctypes.byref(n), ctypes.byref(e)), "mlis_amd_control_info")
         return n.value, e.value
+
+    def set_freeu(self, b1=1.0, b2=1.0, s1=1.0, s2=1.0):
+        """mlis_amd_set_freeu: backbone factors b1, b2 and skip factors s1, s2 of stages 1 and 2, each in [0, 4]; 1 switches that part off"""
+        check1(_proto2().mlis_amd_set_freeu(self.h, float(b1), float(b2), float(s1), float(s2)), "mlis_amd_set_freeu")
+
+    def freeu_info(self):
+        """(decoder concatenations treated at stage 1, at stage 2); (0, 0) for an engine without FreeU"""
+        a, b = c_int(), c_int()
+        check1(_proto2().mlis_amd_freeu_info(self.h, ctypes.byref(a), ctypes.byref(b)), "mlis_amd_freeu_info")
+        return a.value, b.value
 
     def ctx_at(self, i):
         """plan i of the engine (0 UNet, 1 decoder, 2 encoder, 3 tile decoder, 4 tile encoder, 5 ControlNet, 6 hint block), or None"""

@@ -162,6 +162,30 @@ def ctrl_add(dst, ld_dst, base, ld_base, ctrl, ld_ctrl, n_img, rows_per_img, C, 
           "mlsd_ctrl_add")
 
 
+def freeu_ws_bytes(n_img, H, W, C):
+    """mlsd_freeu_ws_bytes: workspace of either FreeU kernel for n_img maps of H x W x C"""
+    f = lib().mlsd_freeu_ws_bytes
+    f.restype = ctypes.c_size_t
+    return int(f(n_img, H, W, C))
+
+
+def freeu_depth(n_terms):
+    """mlsd_freeu_depth: the largest number of fp32 additions between a term and its finished sum of n_terms in the FreeU kernels"""
+    return int(lib().mlsd_freeu_depth(int(n_terms)))
+
+
+def freeu_backbone(dst, ld_dst, src, ld_src, n_img, rows_per_img, C, ws, b_dev, stream=None):
+    """mlsd_freeu_backbone: dst = src with its first C / 2 channels times (b - 1) x the per-image normalised channel-mean map + 1 (device pointers; b_dev: one
+    float in device memory; ws: freeu_ws_bytes).  b == 1 copies src bit for bit."""
+    check(lib().mlsd_freeu_backbone(vp(dst), c_i64(ld_dst), vp(src), c_i64(ld_src), n_img, rows_per_img, C, vp(ws), vp(b_dev), vp(stream)), "mlsd_freeu_backbone")
+
+
+def freeu_skip(dst, ld_dst, src, ld_src, n_img, H, W, C, ws, s_dev, stream=None):
+    """mlsd_freeu_skip: dst = src with the four lowest spatial frequencies of every H x W plane times s (device pointers; s_dev: one float in device memory).
+    s == 1 copies src bit for bit."""
+    check(lib().mlsd_freeu_skip(vp(dst), c_i64(ld_dst), vp(src), c_i64(ld_src), n_img, H, W, C, vp(ws), vp(s_dev), vp(stream)), "mlsd_freeu_skip")
+
+
 def window_gather_nhwc(src, W, H, C, dst, ww, wh, xs, ys, n_rep, stream=None):
     """mlsd_window_gather_nhwc: dst [len(xs)][n_rep][wh][ww][C] <- src [H][W][C] at ((ys[s] + v) mod H, (xs[s] + u) mod W), bit copies (xs, ys: host lists)."""
     ax, ay = (c_int * max(len(xs), 1))(*xs), (c_int * max(len(ys), 1))(*ys)

@@ -44,7 +44,8 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                       "CALLBACK", "ERROR_HANDLER", "LOG_LEVEL", "MODEL_TYPE", "WEIGHT_TYPE", "NO_PROMPT_PARSE"], explicit=dict(_LAST=35, AMD_TILING=101, AMD_HIRES_SCALE=102, AMD_HIRES_DENOISE=103,
                                                                             AMD_HIRES_STEPS=104, AMD_HIRES_UPSCALER=105, AMD_UNET_TILE=111,
                                                                            AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121, AMD_CONTROL_MODEL=131, AMD_CONTROL_IMAGE=132,
-                                                                           AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135))
+                                                                           AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135, AMD_FREEU=141,
+                                                                           AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 MLIS_CTEF_NO_NORM = 1
 
@@ -314,6 +315,16 @@ class MLImgSynth:
         for name, v in (("control_strength", strength), ("control_start", start), ("control_end", end)):
             if v is not None:
                 self.option_set(name, v)
+
+    # ---- FreeU
+    def freeu_set(self, on=None, b1=None, b2=None, s1=None, s2=None):
+        """FreeU (version 2): on = True / False; b1, b2 = backbone factors and s1, s2 = skip factors of stages 1 and 2, each in [0, 4] (1 = that part off).
+        None keeps a setting.  The options persist across generations; only `on` is built into the engine, a factor change rebuilds nothing."""
+        if on is not None:
+            self.option_set("freeu", 1 if on else 0)
+        for name, v in (("freeu_b1", b1), ("freeu_b2", b2), ("freeu_s1", s1), ("freeu_s2", s2)):
+            if v is not None:
+                self.option_set(name, float(v))
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

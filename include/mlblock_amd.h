@@ -34,6 +34,9 @@ enum MLCtxFlags {           /* src/mlblock.h:29-36 */
 	MLB_F_HIPGRAPH = 8,     /* new: capture the plan into a hipGraph at prep and replay it */
 	MLB_F_OPSHAPES = 16,    /* diagnostics: mlctx_op_info labels GEMMs with their MxNxK */
 	MLB_F_SYNTH_PARAMS = 32,/* mlctx_run_ fills the parameters with the deterministic synthetic weights (seed 1234) when no tensor store is attached */
+	MLB_F_KEEP = 64,        /* diagnostics (plan audit): mlb_release / mlctx_drelease give no block back to the arena, so every tensor keeps memory of its own for the
+	                         * life of the plan (use after release is still reported).  Set before the graph is built.  Nothing else depends on it, except that the live-memory
+	                         * statistic (mem_live and its peak) then never goes down */
 };
 
 /* ---- context lifecycle (mlctx_begin/end/prep/compute: src/mlblock.c:54-345) */
@@ -172,6 +175,40 @@ int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flops);
 const struct mlsd_gemm_args* mlctx_op_gemm_args(const MLCtx* C, int i);   /* op i's launch arguments if it is a GEMM / convolution, else NULL */
 const struct mlsd_attn_args* mlctx_op_attn_args(const MLCtx* C, int i);   /* op i's launch arguments if it is an attention launch (mlsd_attention or mlsd_attention_ctx), else NULL */
 int mlctx_op_attn_is_ctx(const MLCtx* C, int i);   /* 1 if op i is an attention launch that runs on mlsd_attention_ctx */
+/* ---- plan audit (diagnostics): what every recorded op was given, as the launcher will see it.  kind numbers the op kinds in the order 0 gemm / conv, 1 attention, 2 groupnorm,
+ * 3 layernorm, 4 nchw_to_nhwc_f16, 5 nhwc_to_nchw_f32, 6 timestep_embedding, 7 act_f32_to_f16, 8 clip_embed, 9 softmax_rows, 10 device copy, 11 xattn_pack_vt, 12 attention_ctx,
+ * 13 ctrl_add, 14 freeu_backbone, 15 freeu_skip; args points at the argument structure of that kind
+ * (mlsd_gemm_args, mlsd_attn_args, mlsd_gn_args of mlsd_kernels.h, or one of the mlb_*_args below) inside the plan: valid until the plan is reset, never to be written. */
+typedef struct mlb_ln_args { const float* x; int64_t ldx; int rows, d; float eps; const float *g, *b; void* y16; float* y32; } mlb_ln_args;                  /* mlsd_layernorm */
+typedef struct mlb_n2h_args { const float* src; int n_src, C, HW; void* dst; int n_dst, Cpad; const float* scale; float scale0; int mode; } mlb_n2h_args; /* mlsd_nchw_to_nhwc_f16 */
+typedef struct mlb_h2n_args { const float* src; int64_t ld; int n, C, HW; float* dst; float mul, add; } mlb_h2n_args;                                     /* mlsd_nhwc_to_nchw_f32 */
+typedef struct mlb_temb_args { const float* t; int n, dim; float maxp; void* out; } mlb_temb_args;                                                         /* mlsd_timestep_embedding */
+typedef struct mlb_act_args { const float* x; void* y; size_t n; int act; } mlb_act_args;                                                                  /* mlsd_act_f32_to_f16 */
+typedef struct mlb_cemb_args { const int32_t* tok; int n, T, d; const void* tw; const float* pw; float* out; } mlb_cemb_args;                              /* mlsd_clip_embed */
+typedef struct mlb_smax_args { const float* in; int64_t ld_in; void* out; int64_t ld_out; int rows, cols; float scale; } mlb_smax_args;                    /* mlsd_softmax_rows */
+typedef struct mlb_copy_args { const void* src; void* dst; size_t nbytes; } mlb_copy_args;                                                                 /* device-to-device copy */
+typedef struct mlb_cadd_args { float* dst; int64_t ld_dst; const float* base; int64_t ld_base; const float* ctrl; int64_t ld_ctrl; int n_img, rows, C, n_ctrl; const float* gain; } mlb_cadd_args;   /* mlsd_ctrl_add: ctrl and gain are device memory of another plan / the engine */
+typedef struct mlb_freeu_args { float* dst; int64_t ld_dst; const float* src; int64_t ld_src; int n_img, H, W, C; float* ws; const float* f; } mlb_freeu_args;   /* mlsd_freeu_backbone (rows = H W) / mlsd_freeu_skip: ws is plan memory, f one float of the engine's device memory */
+typedef struct mlb_xavt_args { const void* v; int64_t ldv; int n_img, Tk, N; void* vt; } mlb_xavt_args;                                                    /* mlsd_xattn_pack_vt: V^T pack of a cross attention that ends its q projection */
+typedef struct MLOpRecord {
+	int kind, fused, once;      /* see above; the op runs inside its producer's launch; the op is step-invariant (runs once per conditioning) */
+	int gn_src[2];              /* index of the op that defines each fp32 source of a GroupNorm / LayerNorm, -1: none */
+	const char* label;
+	const void* args; size_t args_bytes;
+} MLOpRecord;
+int mlctx_op_record(const MLCtx* C, int i, MLOpRecord* out);     /* 1, or -1 if there is no op i */
+/* device storage of parameter i of mlctx_param_info: address (a virtual one in a weight-streaming plan: see mlctx_weight_slab), elements including padding, bytes per element */
+int mlctx_param_device(const MLCtx* C, int i, const void** dev, size_t* elems, int* elem_bytes);
+int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes);   /* device slab k of a weight-streaming plan; 0 when there is no slab k */
+/* input i of the plan: its name, staging buffer (reference layout) and, where mlctx_input_bind gave one, the bound source and scale vector */
+typedef struct MLInputRecord { const char* name; const void* stage; size_t stage_bytes; const void* src; int n_src; const void* scale; } MLInputRecord;
+int mlctx_input_count(const MLCtx* C);
+int mlctx_input_record(const MLCtx* C, int i, MLInputRecord* out);
+/* block i the plan zeroed once when it was built and no launch writes in full (the channel padding of an fp16 output whose consumers need 8-channel pixels); 0 when there is no block i */
+int mlctx_zeroed_block(const MLCtx* C, int i, const void** dev, size_t* nbytes);
+/* the plan's shared scratch: 0 split-K / stream-K workspace, 1 stream-K flag words, 2 LayerNorm-ending counters, 3 LayerNorm-ending records (1 .. 3 are zeroed once and
+ * left zero by the launches that use them); 0 when the plan has none */
+int mlctx_scratch_block(const MLCtx* C, int which, const void** dev, size_t* nbytes);
 /* algorithmic HBM bytes of op i (operands read once, outputs written once) */
 double mlctx_op_bytes(const MLCtx* C, int i);
 /* time every op individually with HIP events (diagnostics; synchronises) */

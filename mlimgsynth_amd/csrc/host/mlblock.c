@@ -79,7 +79,7 @@ static void ctx_reset_(MLCtx* C)
 	if (C->ln_ws) { mlsd_free(C->ln_ws); C->ln_ws = NULL; C->ln_ws_bytes = 0; }
 	if (C->lora_buf) { mlsd_free(C->lora_buf); C->lora_buf = NULL; C->lora_buf_bytes = 0; }
 	wstream_free(C);
-	C->n_chunks = 0; C->cur = NULL; C->cur_left = 0; C->n_free = 0;
+	C->n_chunks = 0; C->cur = NULL; C->cur_left = 0; C->n_free = 0; C->n_zeroed = 0;
 	C->mem_compute = C->mem_params = C->mem_live = C->mem_peak_live = 0;
 	C->err = 0; C->prepared = 0; C->tuned = 0; C->n_tune_miss = 0; C->n_tune_near = 0; C->static_valid = 0; C->n_once = 0;
 	C->n_ln_fused = 0; C->n_ln_alias = 0; C->n_gn_fused = 0;
@@ -93,7 +93,7 @@ MLB_API void mlctx_destroy(MLCtx* C)
 	if (!C) return;
 	mlsd_stream_sync(C->stream);
 	ctx_reset(C);
-	free(C->ops); free(C->tensors); free(C->inputs); free(C->names); free(C->params); free(C->chunks); free(C->freel);
+	free(C->ops); free(C->tensors); free(C->inputs); free(C->names); free(C->params); free(C->chunks); free(C->freel); free(C->zeroed);
 	free(C);
 }
 
@@ -263,6 +263,7 @@ void mlctx_drelease(MLCtx* C, void* p, size_t nbytes)
 {
 	if (!p || !nbytes) return;
 	nbytes = ALIGN_UP(nbytes, 256);
+	if (C->flags & MLB_F_KEEP) return;      /* plan audit: the block stays with its tensor, nothing is lent out twice */
 	MLFreeBlk *b = VEC_PUSH(C, C->freel, C->n_free, C->cap_free, MLFreeBlk);
 	b->ptr = p; b->size = nbytes; b->rel_op = C->n_ops;
 	C->mem_live -= nbytes;
@@ -322,6 +323,7 @@ void* mlt_need16(MLCtx* C, MLTensor* t)
 			const size_t sz = (size_t)rows * cpad * 2;
 			t->d16 = dalloc_ex(C, sz, 2, 0); t->ld16 = cpad;
 			if (t->d16) mlsd_memset(t->d16, 0, sz, C->stream);
+			if (t->d16) { MLFreeBlk *z = VEC_PUSH(C, C->zeroed, C->n_zeroed, C->cap_zeroed, MLFreeBlk); z->ptr = t->d16; z->size = sz; z->rel_op = t->prod; }
 		} else {
 			t->sz16 = (size_t)rows * t->c * 2;
 			t->d16 = dalloc_ex(C, t->sz16, 0, t->prod); t->ld16 = t->c;
@@ -1659,6 +1661,84 @@ MLB_API const mlsd_attn_args* mlctx_op_attn_args(const MLCtx* C, int i)
 {
 	if (!C || i < 0 || i >= C->n_ops || (C->ops[i].kind != OP_ATTN && C->ops[i].kind != OP_ATTN_CTX)) return NULL;
 	return &C->ops[i].u.attn;
+}
+
+/* plan audit: the record of op i as it will be launched (kind, marks, the argument structure of its kind) */
+MLB_API int mlctx_op_record(const MLCtx* C, int i, MLOpRecord* out)
+{
+	if (!C || !out || i < 0 || i >= C->n_ops) return -1;
+	const MLOp *o = &C->ops[i];
+	out->kind = (int)o->kind; out->fused = o->fused; out->once = o->once;
+	out->gn_src[0] = o->gn_src[0]; out->gn_src[1] = o->gn_src[1];
+	out->label = o->label; out->args = &o->u; out->args_bytes = 0;
+	switch (o->kind) {
+	case OP_GEMM: out->args_bytes = sizeof(o->u.gemm); break;
+	case OP_ATTN: case OP_ATTN_CTX: out->args_bytes = sizeof(o->u.attn); break;
+	case OP_GN: out->args_bytes = sizeof(o->u.gn); break;
+	case OP_LN: out->args_bytes = sizeof(o->u.ln); break;
+	case OP_NCHW2NHWC: out->args_bytes = sizeof(o->u.n2h); break;
+	case OP_NHWC2NCHW: out->args_bytes = sizeof(o->u.h2n); break;
+	case OP_TEMB: out->args_bytes = sizeof(o->u.temb); break;
+	case OP_ACT: out->args_bytes = sizeof(o->u.act); break;
+	case OP_CLIP_EMBED: out->args_bytes = sizeof(o->u.cemb); break;
+	case OP_SOFTMAX: out->args_bytes = sizeof(o->u.smax); break;
+	case OP_COPY_F32: out->args_bytes = sizeof(o->u.copy); break;
+	case OP_XA_VT: out->args_bytes = sizeof(o->u.xavt); break;
+	case OP_CTRL_ADD: out->args_bytes = sizeof(o->u.cadd); break;
+	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: out->args_bytes = sizeof(o->u.freeu); break;
+	}
+	return 1;
+}
+
+MLB_API int mlctx_param_device(const MLCtx* C, int i, const void** dev, size_t* elems, int* elem_bytes)
+{
+	if (!C || i < 0 || i >= C->n_params) return -1;
+	if (dev) *dev = C->params[i].dev;
+	if (elems) *elems = C->params[i].dev_elems;
+	if (elem_bytes) *elem_bytes = C->params[i].type == MLT_F16 ? 2 : 4;
+	return 1;
+}
+
+MLB_API int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes)
+{
+	if (!C || !C->pstream || k < 0 || k >= C->n_slab || !C->slab[k]) return 0;
+	if (dev) *dev = C->slab[k];
+	if (nbytes) *nbytes = C->slab_bytes;
+	return 1;
+}
+
+MLB_API int mlctx_input_count(const MLCtx* C) { return C ? C->n_inputs : 0; }
+MLB_API int mlctx_input_record(const MLCtx* C, int i, MLInputRecord* out)
+{
+	if (!C || !out || i < 0 || i >= C->n_inputs) return -1;
+	const MLTensor *t = C->inputs[i];
+	out->name = t->name; out->stage = t->in_stage; out->stage_bytes = t->in_bytes;
+	out->src = t->in_src; out->n_src = t->in_src_n; out->scale = t->in_scale;
+	return 1;
+}
+
+MLB_API int mlctx_zeroed_block(const MLCtx* C, int i, const void** dev, size_t* nbytes)
+{
+	if (!C || i < 0 || i >= C->n_zeroed) return 0;
+	if (dev) *dev = C->zeroed[i].ptr;
+	if (nbytes) *nbytes = C->zeroed[i].size;
+	return 1;
+}
+
+MLB_API int mlctx_scratch_block(const MLCtx* C, int which, const void** dev, size_t* nbytes)
+{
+	const void *p = NULL; size_t n = 0;
+	if (!C) return 0;
+	switch (which) {
+	case 0: p = C->splitk_ws; n = C->splitk_ws_bytes; break;
+	case 1: p = C->sk_flags; n = (size_t)SK_FLAG_WORDS * 4; break;
+	case 2: p = C->ln_cnt; n = (size_t)LN_CNT_WORDS * 4; break;
+	case 3: p = C->ln_ws; n = C->ln_ws_bytes; break;
+	}
+	if (!p) return 0;
+	if (dev) *dev = p;
+	if (nbytes) *nbytes = n;
+	return 1;
 }
 
 MLB_API int mlctx_op_attn_is_ctx(const MLCtx* C, int i) { return C && i >= 0 && i < C->n_ops && C->ops[i].kind == OP_ATTN_CTX; }

@@ -10,7 +10,7 @@
 
 int mlsd_set_error(int code, const char* fmt, ...);
 
-typedef enum {
+typedef enum {      /* (the numbering is what mlctx_op_record reports: append only) */
 	OP_GEMM, OP_ATTN, OP_GN, OP_LN, OP_NCHW2NHWC, OP_NHWC2NCHW, OP_TEMB, OP_ACT, OP_CLIP_EMBED, OP_SOFTMAX,
 	OP_COPY_F32, OP_XA_VT, OP_ATTN_CTX, OP_CTRL_ADD, OP_FREEU_BACKBONE, OP_FREEU_SKIP,
 } MLOpKind;
@@ -28,17 +28,17 @@ typedef struct MLOp {
 		mlsd_gemm_args gemm;
 		mlsd_attn_args attn;
 		mlsd_gn_args gn;
-		struct { const float* x; int64_t ldx; int rows, d; float eps; const float *g, *b; void* y16; float* y32; } ln;
-		struct { const float* src; int n_src, C, HW; void* dst; int n_dst, Cpad; const float* scale; float scale0; int mode; } n2h;
-		struct { const float* src; int64_t ld; int n, C, HW; float* dst; float mul, add; } h2n;
-		struct { const float* t; int n, dim; float maxp; void* out; } temb;
-		struct { const float* x; void* y; size_t n; int act; } act;
-		struct { const int32_t* tok; int n, T, d; const void* tw; const float* pw; float* out; } cemb;
-		struct { const float* in; int64_t ld_in; void* out; int64_t ld_out; int rows, cols; float scale; } smax;
-		struct { const void* src; void* dst; size_t nbytes; } copy;
-		struct { float* dst; int64_t ld_dst; const float* base; int64_t ld_base; const float* ctrl; int64_t ld_ctrl; int n_img, rows, C, n_ctrl; const float* gain; } cadd;   /* mlsd_ctrl_add: ctrl and gain are device memory of another plan / the engine */
-		struct { float* dst; int64_t ld_dst; const float* src; int64_t ld_src; int n_img, H, W, C; float* ws; const float* f; } freeu;   /* mlsd_freeu_backbone (rows = H W) / mlsd_freeu_skip: ws is plan memory, f one float of the engine's device memory */
-		struct { const void* v; int64_t ldv; int n_img, Tk, N; void* vt; } xavt;      /* V^T pack of a cross attention that ends its q projection (mlsd_xattn_pack_vt) */
+		mlb_ln_args ln;
+		mlb_n2h_args n2h;
+		mlb_h2n_args h2n;
+		mlb_temb_args temb;
+		mlb_act_args act;
+		mlb_cemb_args cemb;
+		mlb_smax_args smax;
+		mlb_copy_args copy;
+		mlb_cadd_args cadd;
+		mlb_freeu_args freeu;
+		mlb_xavt_args xavt;
 	} u;
 } MLOp;
 
@@ -97,6 +97,7 @@ struct MLCtx {
 	void** chunks; int n_chunks, cap_chunks;
 	char* cur; size_t cur_left;
 	MLFreeBlk* freel; int n_free, cap_free;
+	MLFreeBlk* zeroed; int n_zeroed, cap_zeroed;   /* blocks zeroed once at build time that no launch writes in full (mlt_need16's channel padding): mlctx_zeroed_block */
 	size_t mem_compute, mem_params, mem_peak_live, mem_live;
 	void* gn_ws; size_t gn_ws_bytes;
 	void* graph_exec;

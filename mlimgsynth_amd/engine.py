@@ -58,6 +58,29 @@ class AmdControlConfig(ctypes.Structure):
 CONTROL_NET, CONTROL_FREEU = 1, 2       # MLIS_AMD_CONTROL_*: the bits of `control`
 
 
+# MLOpKind (include/mlblock_amd.h) and the ctypes record of each kind's arguments, for MLCtx.op_records
+OP_KINDS = ("gemm", "attn", "gn", "ln", "n2h", "h2n", "temb", "act", "cemb", "smax", "copy", "xavt", "attn_ctx", "cadd", "freeu_backbone", "freeu_skip")
+MLB_F_OPSHAPES, MLB_F_SYNTH_PARAMS, MLB_F_KEEP = 16, 32, 64
+
+
+def _op_arg_types():
+    from . import kernels as K
+    return {"gemm": K.GemmArgs, "attn": K.AttnArgs, "attn_ctx": K.AttnArgs, "gn": K.GnArgs, "ln": K.LnArgs, "n2h": K.N2hArgs, "h2n": K.H2nArgs,
+            "temb": K.TembArgs, "act": K.ActArgs, "cemb": K.CembArgs, "smax": K.SmaxArgs, "copy": K.CopyArgs, "xavt": K.XavtArgs, "cadd": K.CaddArgs,
+            "freeu_backbone": K.FreeuArgs, "freeu_skip": K.FreeuArgs}
+
+
+class OpRecord(ctypes.Structure):
+    """MLOpRecord"""
+    _fields_ = [("kind", c_int), ("fused", c_int), ("once", c_int), ("gn_src", c_int * 2), ("label", ctypes.c_char_p), ("args", vp),
+                ("args_bytes", ctypes.c_size_t)]
+
+
+class InputRecord(ctypes.Structure):
+    """MLInputRecord"""
+    _fields_ = [("name", ctypes.c_char_p), ("stage", vp), ("stage_bytes", ctypes.c_size_t), ("src", vp), ("n_src", c_int), ("scale", vp)]
+
+
 _proto_done = False
 
 
@@ -89,6 +112,14 @@ def L():
         l.unet_sigma_to_t.argtypes = [ctypes.POINTER(UnetParams), c_f]
         l.unet_t_to_sigma.restype = c_f
         l.unet_t_to_sigma.argtypes = [ctypes.POINTER(UnetParams), c_f]
+        l.mlctx_op_record.argtypes = [vp, c_int, ctypes.POINTER(OpRecord)]
+        l.mlctx_param_device.argtypes = [vp, c_int, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(c_int)]
+        l.mlctx_weight_slab.argtypes = [vp, c_int, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        l.mlctx_input_count.argtypes = [vp]
+        l.mlctx_input_record.argtypes = [vp, c_int, ctypes.POINTER(InputRecord)]
+        l.mlctx_zeroed_block.argtypes = [vp, c_int, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        l.mlctx_scratch_block.argtypes = [vp, c_int, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        l.mlctx_ln_alias_refused.argtypes = [vp]
         l.mlb_f32_to_f16_bits.restype = ctypes.c_uint16
         l.mlb_f32_to_f16_bits.argtypes = [c_f]
         l.mlb_f16_bits_to_f32.restype = c_f
@@ -145,6 +176,66 @@ class MLCtx:
             L().mlctx_op_info(self.h, i, ctypes.byref(lab), ctypes.byref(fl))
             out.append((lab.value.decode(), fl.value))
         return out
+
+    def op_records(self):
+        """mlctx_op_record of every op: [(kind name, label, fused, once, (gn_src0, gn_src1), a copy of the kind's argument structure)]"""
+        types, out, r = _op_arg_types(), [], OpRecord()
+        for i in range(self.info().n_ops):
+            check1(L().mlctx_op_record(self.h, i, ctypes.byref(r)), "mlctx_op_record")
+            kind = OP_KINDS[r.kind]
+            T = types[kind]
+            if r.args_bytes != ctypes.sizeof(T):
+                raise RuntimeError(f"op {i} ({kind}): the library's argument record has {r.args_bytes} bytes, its ctypes mirror {ctypes.sizeof(T)}")
+            a = T()
+            ctypes.memmove(ctypes.byref(a), r.args, ctypes.sizeof(T))
+            out.append((kind, (r.label or b"").decode(), r.fused, r.once, (r.gn_src[0], r.gn_src[1]), a))
+        return out
+
+    def param_devices(self):
+        """[(key, device address, bytes)] of the parameter table (mlctx_param_device)"""
+        out = []
+        for i, (key, _, _) in enumerate(self.param_list()):
+            p, n, e = vp(), ctypes.c_size_t(), c_int()
+            check1(L().mlctx_param_device(self.h, i, ctypes.byref(p), ctypes.byref(n), ctypes.byref(e)), "mlctx_param_device")
+            out.append((key, p.value or 0, n.value * e.value))
+        return out
+
+    def _blocks(self, f):
+        out, i = [], 0
+        while True:
+            p, n = vp(), ctypes.c_size_t()
+            if not f(self.h, i, ctypes.byref(p), ctypes.byref(n)):
+                return out
+            out.append((p.value or 0, n.value))
+            i += 1
+
+    def weight_slabs(self):
+        """[(address, bytes)] of the device slabs of a weight-streaming plan"""
+        return self._blocks(L().mlctx_weight_slab)
+
+    def zeroed_blocks(self):
+        """[(address, bytes)] of the blocks the plan zeroed once and no launch writes in full (mlctx_zeroed_block)"""
+        return self._blocks(L().mlctx_zeroed_block)
+
+    def scratch_blocks(self):
+        """{name: (address, bytes)} of the plan's shared scratch (mlctx_scratch_block)"""
+        out = {}
+        for which, name in enumerate(("splitk_ws", "sk_flags", "ln_cnt", "ln_ws")):
+            p, n = vp(), ctypes.c_size_t()
+            if L().mlctx_scratch_block(self.h, which, ctypes.byref(p), ctypes.byref(n)):
+                out[name] = (p.value or 0, n.value)
+        return out
+
+    def input_records(self):
+        """[(name, staging address, bytes, bound source address or 0, images of the bound source, scale vector address or 0)]"""
+        out, r = [], InputRecord()
+        for i in range(L().mlctx_input_count(self.h)):
+            check1(L().mlctx_input_record(self.h, i, ctypes.byref(r)), "mlctx_input_record")
+            out.append(((r.name or b"").decode(), r.stage or 0, r.stage_bytes, r.src or 0, r.n_src, r.scale or 0))
+        return out
+
+    def ln_alias_refused(self):
+        return int(L().mlctx_ln_alias_refused(self.h))
 
     def op_bytes(self):
         f = L().mlctx_op_bytes

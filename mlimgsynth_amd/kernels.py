@@ -59,6 +59,53 @@ class GnArgs(ctypes.Structure):
                 ("cs_shifted", c_int)]
 
 
+# the argument records of the plan's other op kinds (include/mlblock_amd.h: mlb_*_args), as mlctx_op_record hands them out
+class LnArgs(ctypes.Structure):
+    _fields_ = [("x", vp), ("ldx", c_i64), ("rows", c_int), ("d", c_int), ("eps", c_f), ("g", vp), ("b", vp), ("y16", vp), ("y32", vp)]
+
+
+class N2hArgs(ctypes.Structure):
+    _fields_ = [("src", vp), ("n_src", c_int), ("C", c_int), ("HW", c_int), ("dst", vp), ("n_dst", c_int), ("Cpad", c_int), ("scale", vp),
+                ("scale0", c_f), ("mode", c_int)]
+
+
+class H2nArgs(ctypes.Structure):
+    _fields_ = [("src", vp), ("ld", c_i64), ("n", c_int), ("C", c_int), ("HW", c_int), ("dst", vp), ("mul", c_f), ("add", c_f)]
+
+
+class TembArgs(ctypes.Structure):
+    _fields_ = [("t", vp), ("n", c_int), ("dim", c_int), ("maxp", c_f), ("out", vp)]
+
+
+class ActArgs(ctypes.Structure):
+    _fields_ = [("x", vp), ("y", vp), ("n", ctypes.c_size_t), ("act", c_int)]
+
+
+class CembArgs(ctypes.Structure):
+    _fields_ = [("tok", vp), ("n", c_int), ("T", c_int), ("d", c_int), ("tw", vp), ("pw", vp), ("out", vp)]
+
+
+class SmaxArgs(ctypes.Structure):
+    _fields_ = [("in_", vp), ("ld_in", c_i64), ("out", vp), ("ld_out", c_i64), ("rows", c_int), ("cols", c_int), ("scale", c_f)]
+
+
+class CopyArgs(ctypes.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("nbytes", ctypes.c_size_t)]
+
+
+class CaddArgs(ctypes.Structure):
+    _fields_ = [("dst", vp), ("ld_dst", c_i64), ("base", vp), ("ld_base", c_i64), ("ctrl", vp), ("ld_ctrl", c_i64), ("n_img", c_int), ("rows", c_int),
+                ("C", c_int), ("n_ctrl", c_int), ("gain", vp)]
+
+
+class FreeuArgs(ctypes.Structure):
+    _fields_ = [("dst", vp), ("ld_dst", c_i64), ("src", vp), ("ld_src", c_i64), ("n_img", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("ws", vp), ("f", vp)]
+
+
+class XavtArgs(ctypes.Structure):
+    _fields_ = [("v", vp), ("ldv", c_i64), ("n_img", c_int), ("Tk", c_int), ("N", c_int), ("vt", vp)]
+
+
 def gemm(args, stream=None):
     check(lib().mlsd_gemm(ctypes.byref(args), vp(stream)), "mlsd_gemm")
 

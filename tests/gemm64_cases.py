@@ -163,6 +163,43 @@ CASES = [
     lin("x25", L("256x128x64pp2"), "256x128x64pp2", 256, 128, 576, bias=True, tv=tv(25), exp=True),
 ]
 
+# ---- the epilogue combinations the bench plans put on each tile (tests/test_plan_audit_gpu.py, COVERED_ELSEWHERE): each case carries EXACTLY the features of one
+# op form -- row bias, residual, column statistics, the fp16 copy beside the fp32 output, the upsampled source -- because each combination selects its own epilogue body
+def _combo(cid, tile, tvn, cout, ksplit=1, ups=0, **f):
+    side = 8 if ups else 16
+    path = ("splitk_reduce_stats" if f.get("stats") else "splitk_reduce") if ksplit > 1 else tile
+    return conv(cid, L(tile, "conv", f",k/{ksplit}" if ksplit > 1 else ""), path, 2, side, side, 64, cout, 3, 1, 1, ups=ups, fam="offset", bias=True, ksplit=ksplit,
+                ws=ksplit > 1, tv=tv(tvn), **f)
+
+
+CASES += [
+    _combo("sk0_c16_stats", G0, 0, 128, ksplit=3, c16=True, stats=True),
+    _combo("sk0_stats_res", G0, 0, 128, ksplit=3, stats=True, resid=True),
+    _combo("sk0_stats_rowbias", G0, 0, 128, ksplit=3, stats=True, rowbias=256),
+    _combo("sk0_stats_ups", G0, 0, 128, ksplit=3, stats=True, ups=1),
+    _combo("sk1_c16_stats_res", G1, 1, 128, ksplit=3, c16=True, stats=True, resid=True),
+    _combo("g1_stats_rowbias", G1, 1, 128, stats=True, rowbias=256),
+    _combo("g1_stats_ups", G1, 1, 128, stats=True, ups=1),
+    _combo("g3_stats_ups", G3, 3, 128, stats=True, ups=1),
+    _combo("g4_plain", G4, 4, 128),
+    _combo("g4_stats", G4, 4, 128, stats=True),
+    _combo("g4_stats_res", G4, 4, 128, stats=True, resid=True),
+    _combo("g9_plain", G9, 9, 256),
+    _combo("g9_stats", G9, 9, 256, stats=True),
+    _combo("g9_stats_ups", G9, 9, 256, stats=True, ups=1),
+    _combo("g9_c16_stats_ups", G9, 9, 256, c16=True, stats=True, ups=1),
+    _combo("g9_c16_res", G9, 9, 256, c16=True, resid=True),
+    _combo("p20_stats_res", P20, 20, 320, stats=True, resid=True),
+    _combo("p20_stats_rowbias", P20, 20, 320, stats=True, rowbias=256),
+    _combo("p21_stats", P21, 21, 256, stats=True),
+    _combo("p21_stats_res", P21, 21, 256, stats=True, resid=True),
+    _combo("p21_ups", P21, 21, 256, ups=1),
+    _combo("p21_c16_res", P21, 21, 256, c16=True, resid=True),
+    lin("s29_m8_c16", L(SK29, "linear", ",k/10"), "skinny128x64", 8, 1280, 1280, ws=True, ksplit=10, bias=True, resid=True, c16=True, tv=tv(29)),
+    lin("p28_sk18_c16", L(P28), "128x320x64ppsk", 256, 320, 5760, fam="offset", sk=True, ws=True, bias=True, c16=True, tv=tv(28)),
+    conv("p28_conv_rowbias", L(P28, "conv"), "128x320x64ppsk", 1, 16, 16, 640, 640, 3, 1, 1, fam="offset", sk=True, ws=True, bias=True, rowbias=256, tv=tv(28)),
+]
+
 BY_ID = {c["id"]: c for c in CASES}
 
 

@@ -20,6 +20,9 @@ Bounds (u32 = 2^-24, u16 = 2^-11):
                     + C_ATTN * sum_j p_j dq_j (|v_j| + |o|),  dq_j = u16 * scale * sum_i |q_i k_ji|
                                                               (kernels that round the scaled Q to fp16 before the QK product: an error of
                                                               dq_j in score j moves o by p_j dq_j (v_j - o))
+                    A cross attention that ends its q projection (tests/plan_audit.py) takes q = fp16(the launch's fp32 projection), the reference
+                    q = fp16_rne(float64 projection): where the float64 value lies within the projection's fp32 bound of an fp16 tie the two may be
+                    neighbours, one fp16 ulp apart (fp16_tie_ulp); attention_dq_term adds what that moves o by, in the same first-order form.
   GEMM / implicit-GEMM convolution, per output element (tests/test_gemm_float64_gpu.py, tests/test_ref64_gemm_cpu.py):
                     acc:  C_GEMM * u32 * D * S,   S = sum_k |a_k w_k| in float64 (|A| @ |W|^T).
                           The products of fp16 operands are exact in fp32 (11 + 11 significant bits).  Every kernel sums them in MFMA steps of
@@ -39,6 +42,22 @@ Bounds (u32 = 2^-24, u16 = 2^-11):
                           GEGLU y = a gelu(g): |gelu(g)| e_a + |a| |gelu'(g)| e_g + C_ACT u32 (1 + |eta(g)|) |y| + u32 |y| + min(|y|, ACT_TINY).
                     fp16 outputs: the fp32 bound b32 + half_ulp16(|y| + b32); where a launch writes both C32 and C16, C16 must also be
                           fp16_rne(C32) bit for bit (the epilogues round the one fp32 value).  An fp16 output is +-inf exactly where fp16(C32) is.
+  Small ops of the plans (tests/plan_audit.py), each from the kernel's own rounding steps (elementwise.hip, norm.hip) and the ulp errors the HIP math API
+  documents for the functions it calls (expf, logf, sinf, cosf, tanhf: 1 ulp each; __expf: 2 + floor(|1.16 x|) ulp); one ulp is at most 2 u32 relative:
+                    act_f32_to_f16 (silu_f16): y = fp16(act(x)) with the epilogues' act_apply on an exact fp32 argument: act_bound(x, 0, act) above, then
+                          the fp16 rounding.  With MLSD_ACT_NONE (f32_to_f16) the op is exact: fp16_rne(x) bit for bit.
+                    timestep_embedding: e = -logf(P) j / half (logf 1 ulp, one multiply, one divide: 4 u32 relative), f = expf(e) (its argument's error
+                          moves it by 4 u32 |e|, expf adds 1 ulp), arg = t f (one multiply): arg is good to (4 |e| + 3) u32 relative; cosf / sinf move by
+                          at most |arg| times that and add 1 ulp of their own:
+                          b32 = u32 ((4 |e| + 3) |arg| + 2 |y|),  e = -ln(P) j / half, arg = t exp(e) in float64; then the fp16 rounding.
+                    softmax_rows: z_j = (x_j - max) scale (two roundings: 2 u32 |z_j| absolute), e_j = __expf(z_j): relative error
+                          d_j = u32 (2 |z_j| + 2 (2 + 1.16 |z_j|)) = u32 (4 + 4.32 |z_j|); the row sum (strided per lane, then a tree: at most cols / 256 + 10
+                          sequential fp32 adds) carries sum_k p_k d_k + (cols / 256 + 10) u32 relative, its reciprocal and the product 2 u32 each:
+                          b32_j = p_j (d_j + sum_k p_k d_k + (cols / 256 + 14) u32) + min(p_j, ACT_TINY) (v_exp_f32 may flush an fp32 subnormal); then the fp16 rounding.
+                    nchw_to_nhwc_f16, mode 1 (TAE clamp): y = fp16(3 tanhf(x / 3) s): m = x (1/3) (the constant and the product: 2 u32 relative, which moves
+                          tanh by (1 - t^2) |m| 2 u32), tanhf 1 ulp, the multiplies by 3 and by s one rounding each:
+                          b32 = |s| 3 u32 (2 (1 - t^2) |x / 3| + 4 |t|),  t = tanh(x / 3) in float64; then the fp16 rounding.
+                          Modes 0 and 2 are exact: fp16_rne of the fp32 products (x [* 2 - 1]) s.
 """
 import numpy as np
 
@@ -172,6 +191,30 @@ def attention_bound(q, k, v, heads, o, p, q_scaled_f16):
     return b.transpose(1, 0, 2).reshape(Tq, D)
 
 
+def fp16_tie_ulp(y, b):
+    """One fp16 ulp of y where a value known only to +- b may round to the other neighbour (y within b of the midpoint of two fp16 values), else 0:
+    how far fp16(kernel's fp32 value) can lie from fp16_rne(y) when the kernel's value is within b of y."""
+    y, b = np.asarray(y, np.float64), np.asarray(b, np.float64)
+    ulp = 2.0 * half_ulp16(y)
+    frac = np.abs(y) / ulp
+    dist = np.abs(frac - np.floor(frac) - 0.5) * ulp
+    return np.where(dist <= b, ulp, 0.0)
+
+
+def attention_dq_term(dq, k, v, heads, o, p):
+    """Bound term [Tq][H*d] for a Q whose elements may be off by dq [Tq][H*d] (absolute): score j of a row moves by at most
+    ds_j = sum_i dq_i |k_ji| / sqrt(d), and o by sum_j p_j ds_j (|v_j| + |o|) to first order (as the q_scaled_f16 term of attention_bound)."""
+    dq, k, v = (np.asarray(a, np.float64) for a in (dq, k, v))
+    Tq, D = dq.shape
+    d = D // heads
+    dh = dq.reshape(Tq, heads, d).transpose(1, 0, 2)
+    kh = np.abs(k.reshape(-1, heads, d).transpose(1, 0, 2))
+    vh = np.abs(v.reshape(-1, heads, d).transpose(1, 0, 2))
+    oh = np.abs(np.asarray(o, np.float64).reshape(Tq, heads, d).transpose(1, 0, 2))
+    w = p * (dh @ kh.transpose(0, 2, 1) / np.sqrt(d))
+    return (C_ATTN * (w @ vh + w.sum(-1, keepdims=True) * oh)).transpose(1, 0, 2).reshape(Tq, D)
+
+
 def attention_worst(got, want, bound):
     """Per-row ratio max|got - want| / (half_ulp16(want) + bound) [Tq]."""
     got = np.asarray(got, np.float64)
@@ -202,10 +245,11 @@ def gemm_depth(K, k_step, nsplit=1):
     return -(-K // k_step) + nsplit + 5
 
 
-def im2col64(x, n_img, H, W, Cin, KH, KW, stride, pad, ups, OH, OW, rows=None):
+def im2col64(x, n_img, H, W, Cin, KH, KW, stride, pad, ups, OH, OW, rows=None, wrap=0):
     """Implicit-GEMM A operand in float64: x is the NHWC image [n_img * H * W][Cin] (the fp16 values the kernel reads, Cin already padded
     to the kernel's multiple of 8); row m = (image, oy, ox), column k = (kh, kw, cin) with cin fastest; zero outside the (nearest-2x upsampled
-    when ups) image.  rows: the output rows wanted (default all)."""
+    when ups) image, or with wrap (bit 0 columns, bit 1 rows: mlsd_gemm_args.wrap) the pixel modulo the extent.  rows: the output rows wanted
+    (default all)."""
     x = np.asarray(x, np.float64).reshape(n_img, H, W, Cin)
     if ups:
         x = x.repeat(2, axis=1).repeat(2, axis=2)
@@ -215,8 +259,12 @@ def im2col64(x, n_img, H, W, Cin, KH, KW, stride, pad, ups, OH, OW, rows=None):
     out = np.zeros((len(m), KH, KW, Cin))
     for kh in range(KH):
         iy = oy * stride - pad + kh
+        if wrap & 2:
+            iy = iy % H
         for kw in range(KW):
             ix = ox * stride - pad + kw
+            if wrap & 1:
+                ix = ix % W
             ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
             out[ok, kh, kw] = x[b[ok], iy[ok], ix[ok]]
     return out.reshape(len(m), KH * KW * Cin)
@@ -346,3 +394,57 @@ def gemm_ratio16(got16, want, b32):
     inf_ok = (np.sign(g) == np.sign(want)) & (np.abs(want) + b32 >= 65520.0)
     r[~fin & ~inf_ok] = np.inf
     return r
+
+
+# ------------------------------------------------------------------ column statistics of a producer (mlsd_gemm_args.colstats)
+def colstats_ratios(c32, st, rows, shifted=True):
+    """The statistics a launch wrote beside its fp32 output c32 [M][N]: st [M / rows][2][N] = per block and column sum (x - K) and sum (x - K)^2 with
+    K = the block's first row (shifted), or the plain sums of x and x^2.  Ratio of each to C_NORM u32 of the sum of the magnitudes of its terms,
+    in float64 on the stored output: (ratios of the sums, ratios of the sums of squares), each [M / rows][N]."""
+    blk = np.asarray(c32, np.float64).reshape(-1, rows, np.asarray(c32).shape[1])
+    d = blk - blk[:, :1] if shifted else blk
+    st = np.asarray(st, np.float64)
+    es = np.abs(st[:, 0] - d.sum(1)) / (C_NORM * U32 * np.abs(d).sum(1) + 1e-30)
+    eq = np.abs(st[:, 1] - (d * d).sum(1)) / (C_NORM * U32 * (d * d).sum(1) + 1e-30)
+    return es, eq
+
+
+# ------------------------------------------------------------------ small ops of the plans (module docstring)
+ULP = 2.0 * U32          # one fp32 ulp, relative, at most
+ULP_EXPF = ULP_LOGF = ULP_SINCOSF = ULP_TANHF = 1.0      # HIP math API, maximum ulp error of the single-precision functions
+
+
+def act16_bound(x, act):
+    """(y64, b32) of y = act(x) computed in fp32 from an exact fp32 x (act_apply of common.hpp)"""
+    x = np.asarray(x, np.float64)
+    return act64(x, act), act_bound(x, 0.0, act)
+
+
+def timestep_embedding64(t, dim, max_period):
+    """(y64 [n][dim] = cos | sin, b32) of mlsd_timestep_embedding"""
+    t = np.asarray(t, np.float64).reshape(-1)
+    half = dim // 2
+    e = -np.log(float(max_period)) * np.arange(half) / half
+    arg = t[:, None] * np.exp(e)[None, :]
+    rel = ((2 * ULP_LOGF + 2) * np.abs(e) + 2 * ULP_EXPF + 1)[None, :]            # (4 |e| + 3) at 1 ulp each
+    y = np.concatenate([np.cos(arg), np.sin(arg)], axis=1)
+    b = U32 * (np.concatenate([rel * np.abs(arg)] * 2, axis=1) + 2 * ULP_SINCOSF * np.abs(y))
+    return y, b
+
+
+def softmax_rows64(x, scale):
+    """(p64, b32) of mlsd_softmax_rows on fp32 scores x [rows][cols]"""
+    x = np.asarray(x, np.float64)
+    z = (x - x.max(1, keepdims=True)) * float(scale)
+    e = np.exp(z)
+    p = e / e.sum(1, keepdims=True)
+    d = U32 * (2 * np.abs(z) + 2 * (2 + 1.16 * np.abs(z)))
+    b = p * (d + (p * d).sum(1, keepdims=True) + (x.shape[1] / 256.0 + 14) * U32) + np.minimum(p, ACT_TINY)      # (fp32 subnormals may be flushed: far below any fp16 value)
+    return p, b
+
+
+def tae_clamp64(x, s):
+    """(y64, b32) of the tanh mode of mlsd_nchw_to_nhwc_f16: 3 tanh(x / 3) s"""
+    x, s = np.asarray(x, np.float64), np.asarray(s, np.float64)
+    t = np.tanh(x / 3.0)
+    return 3.0 * t * s, np.abs(s) * 3.0 * U32 * (2 * (1 - t * t) * np.abs(x / 3.0) + (2 * ULP_TANHF + 2) * np.abs(t))

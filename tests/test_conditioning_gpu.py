@@ -84,10 +84,7 @@ def check_mean_rstd(path, table, x, G):
 def check_shifted_colstats(name, c32, st, rows):
     """The producer's statistics themselves (colstats_shift = 1): per block and column sum (x - K) and sum (x - K)^2, K = the block's first row,
     against float64 on the stored output, each to C_NORM u32 of the sum of the magnitudes of its terms."""
-    blk = c32.astype(np.float64).reshape(-1, rows, c32.shape[1])
-    d = blk - blk[:, :1]
-    es = np.abs(st[:, 0] - d.sum(1)) / (R.C_NORM * R.U32 * np.abs(d).sum(1) + 1e-30)
-    eq = np.abs(st[:, 1] - (d * d).sum(1)) / (R.C_NORM * R.U32 * (d * d).sum(1) + 1e-30)
+    es, eq = R.colstats_ratios(c32, st, rows)
     print(f"\n[conditioning] colstats {name} rows {rows}: shifted sums worst ratio {es.max():.3f} / {eq.max():.3f}")
     assert np.all(es <= 1.0) and np.all(eq <= 1.0), (name, float(es.max()), float(eq.max()))
 

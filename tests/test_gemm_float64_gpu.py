@@ -9,13 +9,13 @@ ratio of every case and, at the end, of every path is printed (convolutions also
 The census at the end builds the bench plans (without computing them) and checks that every GEMM path they choose has a case here.
 """
 import ctypes
-import re
 import zlib
 
 import numpy as np
 import pytest
 
 import gemm64_cases as GC
+import plan_audit as PA
 import ref64 as R
 
 pytestmark = pytest.mark.gpu
@@ -46,12 +46,11 @@ def K():
 
 
 def _k_step(c):
-    return R.K_STEP_GENERAL if c["variant"].split("<")[1].split(",")[0] in (GC.G0, GC.G1, GC.G3, GC.G4, GC.G9, GC.G16) else R.K_STEP_MFMA16
+    return PA.gemm_path(c["variant"])[2]      # (one parser of the launch labels for these tests and the plan audit: tests/plan_audit.py)
 
 
 def _nsplit(label):
-    m = re.search(r",k/(\d+)", label)
-    return int(m.group(1)) if m else 1
+    return PA.gemm_path(label)[3]
 
 
 def _rows_to_check(c):
@@ -102,8 +101,10 @@ def _args(kernels, _lib, c, dev, keep):
         a.sk_flags = d(np.zeros(4096, np.uint32))
     if c["stats"]:
         a.colstats, a.colstats_shift = d(np.zeros(2 * N * (M // 32 + 2), np.float32)), 1
+        keep.append(("colstats", keep[-1]))
     if c["ln"]:
         a.ln_y16, a.ldln = d(np.zeros((M, N), np.float16)), N
+        keep.append(("ln_y16", keep[-1]))
         a.ln_gamma, a.ln_beta, a.ln_eps = d(np.ones(N, np.float32)), d(np.zeros(N, np.float32)), 1e-5
         a.ln_ws, a.ln_cnt, a.ln_slot = d(np.zeros(M * (N // 128 + 1) * 4, np.float32)), d(np.zeros(8192, np.uint32)), 0
     return a
@@ -135,6 +136,21 @@ def test_gemm_float64(K, case):
     if got32 is not None and got16 is not None:
         same = R.fp16_rne(got32).view(np.uint16) == got16.view(np.uint16)
         assert same.all(), f"{c['id']}: C16 != fp16_rne(C32) at {np.argwhere(~same)[:4].tolist()}"
+    side = dict(k for k in keep if isinstance(k, tuple))
+    wst = wln = 0.0
+    if c["stats"]:      # the column statistics the launch wrote beside C32: the launch must be one that writes them, and they must describe the stored output
+        rows_st = kernels.gemm_route(a).stats_rows
+        assert rows_st > 0 and M % rows_st == 0 and got32 is not None, f"{c['id']} ({label}): the launch writes no column statistics (rows {rows_st})"
+        st = side["colstats"].download((M // rows_st, 2, c["N"]), np.float32)
+        es, eq = R.colstats_ratios(got32, st, rows_st, shifted=True)
+        wst = max(float(es.max()), float(eq.max()))
+        assert wst <= 1.0, f"{c['id']} ({label}): column statistics ratio {wst:.3g} > 1 (blocks of {rows_st} rows)"
+    if c["ln"]:         # the LayerNorm ending (gamma 1, beta 0, eps 1e-5 in _args) of the stored fp32 rows
+        assert kernels.gemm_route(a).ln > 0 and got32 is not None, f"{c['id']} ({label}): the launch does not end with its LayerNorm"
+        g, be = np.ones(c["N"]), np.zeros(c["N"])
+        ratio, _ = R.layernorm_worst(side["ln_y16"].download((M, c["N"]), np.float16), R.layernorm64(got32, 1e-5, g, be), got32, 1e-5, g, be)
+        wln = float(ratio.max())
+        assert wln <= 1.0, f"{c['id']} ({label}): LayerNorm ending ratio {wln:.3g} > 1 at row {int(np.argmax(ratio))}"
     D = R.gemm_depth(c["K"], _k_step(c), _nsplit(label) + (c["K"] // 64 if c["sk"] else 0))
     rows, lastcols = _rows_to_check(c)
     parts = [(rows, None)] + ([] if lastcols is None else [(np.arange(M), lastcols)])
@@ -163,7 +179,8 @@ def test_gemm_float64(K, case):
                 pytest.fail(f"{c['id']} ({label}): ratio {r[i]:.3g} > 1 at row {m_} col {n_}: ref {y[i]:.9g} bound {b[i]:.3g}")
     p = WORST.setdefault(c["path"], [0.0, 0.0, 0.0])
     p[0], p[1], p[2] = max(p[0], w32), max(p[1], w16), max(p[2], wb)
-    print(f"{c['id']:22s} {label:36s} worst C32 {w32:7.3f}  C16 {w16:7.3f}  border {wb:7.3f}")
+    print(f"{c['id']:22s} {label:36s} worst C32 {w32:7.3f}  C16 {w16:7.3f}  border {wb:7.3f}" + (f"  colstats {wst:7.3f}" if c["stats"] else "") +
+          (f"  ln_y16 {wln:7.3f}" if c["ln"] else ""))
 
 
 # ------------------------------------------------------------------ census
@@ -173,15 +190,7 @@ COVERED_ELSEWHERE = {"linear+attention": "test_conditioning_gpu.py (the q projec
 
 def path_key(label):
     """(tile, form) of a plan label: form is '', 'splitk' or 'layernorm' ('linear+attention' is tested with the attention kernels)"""
-    m = re.match(r"gemm<([^,>]+),([a-z]+)(\+[a-z]+)?(,k/\d+p?)?>", label)
-    assert m, label
-    tile, plus, ks = m.group(1), (m.group(3) or "")[1:], m.group(4)
-    if plus == "attention":
-        return tile, "linear+attention"
-    form = "layernorm" if plus == "layernorm" else ""
-    if ks and tile != GC.SK29:
-        form = (form + "+" if form else "") + "splitk"
-    return tile, form
+    return PA.gemm_path(label)[:2]
 
 
 def case_keys():

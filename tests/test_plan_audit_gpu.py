@@ -1,0 +1,220 @@
+"""Prepared plans on the device, audited launch by launch (tests/plan_audit.py).
+
+Every plan is built with MLB_F_KEEP (no block is lent out twice, so every operand is still in memory when the evaluation ends) and the synthetic
+weights, computed once, and then EVERY launch is recomputed in float64 from the operands it actually read -- folded residuals and row biases,
+column views, producer statistics, LayerNorm endings, hoisted ops -- and held to the per-element / per-row bounds of tests/ref64.py.  With -s the
+worst ratio per (kind, path) is printed.  The second test compares the default (recycling) plan with the kept plan bit for bit: the arena must
+not change a result.
+"""
+import contextlib
+import os
+
+import numpy as np
+import pytest
+
+import plan_audit as PA
+
+pytestmark = pytest.mark.gpu
+
+KEEP = PA.MLB_F_OPSHAPES | PA.MLB_F_KEEP
+
+# (spec, xattn mode while the plan is built, kinds the plan must contain)
+AUDITED = [
+    (("unet", "tiny", 16, 2), None, {"gemm", "attn", "gn", "ln", "act", "temb", "n2h"}),
+    (("unet", "tinyxl", 16, 2), None, {"gemm", "attn", "gn", "ln"}),
+    (("unet", "sd1", 16, 2), None, {"gemm", "attn", "gn", "ln"}),                # 512 x 320 rows: the 128x160 LayerNorm ending; 8-row levels: split-K, skinny tiles
+    (("vae_dec", "tiny", 8, 1), None, {"gemm", "gn", "smax", "n2h"}),
+    (("vae_enc", "tiny", 8, 1), None, {"gemm", "gn", "smax", "n2h"}),
+    (("tae_dec", "tiny", 8, 1), None, {"gemm", "n2h"}),
+    (("clip", "tiny", 2), None, {"gemm", "attn", "ln", "cemb"}),                  # causal attention, quick-GELU, clip_embed
+    # mlsd_gemm_set_xattn(2): the cross attention ends its q projection wherever the kernel takes the launch.  It takes 320-column projections (5 heads of 64) of
+    # K >= 192 on 128-row blocks: tinyxl's 64 / 128 channels never qualify, so the configuration is run at 320 channels on both levels (n_ch = 320, ch_mult 1, 1;
+    # 16 x 8 = 128 tokens at the attention level): K / V as column views of the batched context projection, the hoisted V^T pack, a q projection that stores no C16
+    (("unet", "tinyxl", (32, 16), 2, dict(params=dict(n_ch=320, ch_mult=(1, 1, 0, 0, 0)))), 2, {"gemm", "attn", "xavt"}),
+    (("unet", "sd1", 8, 2, dict(n_ctx_tok=154)), None, {"attn_ctx"}),             # windowed context: OP_ATTN_CTX
+]
+# + the SDXL real configuration at the smallest latent its three levels accept, for the bit comparison only
+BITWISE = [(s, x) for s, x, _ in AUDITED] + [(("unet", "sdxl", 4, 2), None)]
+
+
+@contextlib.contextmanager
+def _built(E, spec, xattn, flags, synth):
+    """the plan, built AND used under the xattn mode (the launcher asks the mode again at every launch), closed and the mode restored afterwards"""
+    engine, _lib = E
+    L = _lib.lib()
+    b = None
+    try:
+        if xattn is not None:
+            L.mlsd_gemm_set_xattn(xattn)
+        b = PA.build(engine, spec, flags, synth=synth)
+        yield b
+    finally:
+        if b is not None:
+            b.close()
+        if xattn is not None:
+            L.mlsd_gemm_set_xattn(-1)
+
+
+@pytest.fixture(scope="module")
+def E():
+    from mlimgsynth_amd import _lib, engine
+    yield engine, _lib
+
+
+@pytest.mark.parametrize("spec,xattn,kinds", AUDITED, ids=[PA.plan_id(s) + ("-xattn2" if x else "") for s, x, _ in AUDITED])
+def test_every_launch_against_float64(E, spec, xattn, kinds):
+    engine, _lib = E
+    with _built(E, spec, xattn, KEEP, True) as b:
+        out = b.run(1)
+        assert np.isfinite(out).all()
+        plan = PA.Plan(b.ctx, PA.plan_id(spec))
+        assert kinds <= {o.kind for o in plan.ops}, sorted({o.kind for o in plan.ops})
+        gone = PA.clobbered_operands(plan)
+        assert not gone, [f"{w} ({wn}) overwrites operand {rn} of {r}" for w, wn, r, rn in gone[:8]]
+        mem = PA.DeviceMemory(_lib)
+        worst, bad = {}, []
+        for i, op in enumerate(plan.ops):
+            if op.fused:      # checked as the ending of its producer, which must carry it
+                prod = plan.ops[i - 1]
+                assert prod.kind == "gemm" and (prod.a.ln_y16 == op.a.y16 if op.kind == "ln" else prod.a.gn_y16 == op.a.y16), (op, prod)
+            key, ratios = PA.verify_op(mem, plan, i)
+            for name, r in ratios.items():
+                k = key + (name,)
+                worst[k] = max(worst.get(k, 0.0), r)
+                if not r <= 1.0:
+                    bad.append(f"{op} output {name}: ratio {r:.4g}")
+        n_xa = sum(1 for o in plan.ops if o.kind == "gemm" and o.a.xa_k)
+        print(f"\n[plan audit] {PA.plan_id(spec)}{' xattn(2)' if xattn else ''}: {len(plan.ops)} ops, {n_xa} q projections end with their attention; worst ratio per (kind, path, output):")
+        for k, r in sorted(worst.items(), key=str):
+            print(f"  {k[0]:9s} {str(k[1]):44s} {k[2]:14s} {r:8.3f}")
+        assert not bad, bad[:12]
+        if xattn:      # the plan is here for the ending: it must have been taken, checked and fed by the hoisted pack
+            assert n_xa > 0 and any(k[2] == "xa_out" for k in worst) and any(k[0] == "xavt" for k in worst), (n_xa, sorted(worst, key=str))
+            assert all(not any(w.name == "C16" for w in o.writes) for o in plan.ops if o.kind == "gemm" and o.a.xa_k)
+
+
+def _two_evaluations(E, spec, xattn, flags):
+    with _built(E, spec, xattn, flags, True) as b:
+        sig = [PA.op_signature(o) for o in PA.Plan(b.ctx).ops]
+        return [b.run(1), b.run(5), b.run(1)], sig      # changed inputs, then the first ones again: hoisted ops and hand-off scratch are reused
+
+
+@pytest.mark.parametrize("spec,xattn", BITWISE, ids=[PA.plan_id(s) + ("-xattn2" if x else "") for s, x in BITWISE])
+def test_recycling_plan_equals_kept_plan_bit_for_bit(E, spec, xattn):
+    env = os.environ.get("MLSD_NO_LN_FOLD")
+    try:
+        rec, sig_r = _two_evaluations(E, spec, xattn, PA.MLB_F_OPSHAPES)
+        kept, sig_k = _two_evaluations(E, spec, xattn, KEEP)
+        if sig_r != sig_k:      # a LayerNorm fold the alias rule refuses only in the recycling plan: compare the unfolded plans
+            print(f"\n[plan audit] {PA.plan_id(spec)}: op lists differ in {sum(a != b for a, b in zip(sig_r, sig_k))} ops; compared with MLSD_NO_LN_FOLD=1")
+            os.environ["MLSD_NO_LN_FOLD"] = "1"
+            rec, sig_r = _two_evaluations(E, spec, xattn, PA.MLB_F_OPSHAPES)
+            kept, sig_k = _two_evaluations(E, spec, xattn, KEEP)
+            assert sig_r == sig_k
+    finally:
+        if env is None:
+            os.environ.pop("MLSD_NO_LN_FOLD", None)
+        else:
+            os.environ["MLSD_NO_LN_FOLD"] = env
+    for n, (a, b) in enumerate(zip(rec, kept)):
+        assert np.isfinite(a).all() and a.tobytes() == b.tobytes(), f"evaluation {n}: {int((a != b).sum())} of {a.size} values differ"
+    assert rec[0].tobytes() == rec[2].tobytes() and rec[0].tobytes() != rec[1].tobytes()
+
+
+# ------------------------------------------------------------------ census
+def _case_features(c):
+    return {name for name, on in (("row bias", c["rowbias"]), ("residual", c["resid"]), ("act_after_resid", c["post"]), ("GEGLU", c["act"] == 5),
+                                  ("C16 + C32", c["c16"] and c["c32"]), ("colstats", c["stats"]), ("LN ending", c["ln"]), ("upsample", c.get("ups"))) if on}
+
+
+# Op forms of the bench plans that the audited plans above do not contain, and the kernel-level float64 test that holds EXACTLY that form: a GEMM case on the same
+# tile and split form with the same set of epilogue features, no more and no fewer (each combination selects its own epilogue body); an attention case with the
+# same kernel label.  `once` only says when a launch runs (the later evaluations of the bit comparison above exercise it): the case is the form without it.
+# A form that a bench plan newly takes fails the census until its case is written and listed here.
+COVERED_ELSEWHERE = {
+    ('attn', 'attn<64x2s,d40>', ()): "test_attention_float64_gpu.py::test_attention_float64[x2s_d40_tk192_sigma1]",
+    ('attn', 'attn<64x2s,d64>', ()): "test_attention_float64_gpu.py::test_attention_float64[x2s_tk128_sigma1]",
+    ('attn', 'attn<tile,d160>', ()): "test_attention_float64_gpu.py::test_attention_float64[tile_d160_tk200_sigma1]",
+    ('attn', 'attn<tile,d80>', ()): "test_attention_float64_gpu.py::test_attention_float64[tile_d80_tk200_sigma1]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('C16 + C32', 'colstats')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_c16_stats]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_unequal]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_stats_res]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_stats_rowbias]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_stats_ups]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_stats]",
+    ('gemm', ('128x160x64tt', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[t30_res]",
+    ('gemm', ('128x160x64tt', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[t30_f32]",
+    ('gemm', ('128x320x64pp', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p18_generic_silu]",
+    ('gemm', ('128x320x64pp', ''), ('C16 + C32',)): "test_gemm_float64_gpu.py::test_gemm_float64[p18_subnormal]",
+    ('gemm', ('128x320x64pp', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p18_conv_stats_res]",
+    ('gemm', ('128x320x64pp', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[p18_f32_res]",
+    ('gemm', ('128x320x64pp', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[p18_f16_bigout]",
+    ('gemm', ('128x320x64pp', 'layernorm'), ('LN ending', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p18_ln]",
+    ('gemm', ('128x320x64pp', 'linear+attention'), ('xattn ending',)): "test_conditioning_gpu.py::test_attention_fused_into_the_q_projection",
+    ('gemm', ('128x320x64pp2', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p20_stats_res]",
+    ('gemm', ('128x320x64pp2', ''), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[p20_stats_rowbias]",
+    ('gemm', ('128x320x64pp2', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[p20_res]",
+    ('gemm', ('128x320x64ppsk', ''), ('C16 + C32',)): "test_gemm_float64_gpu.py::test_gemm_float64[p28_sk18_c16]",
+    ('gemm', ('128x320x64ppsk', ''), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[p28_conv_rowbias]",
+    ('gemm', ('256x128x32s3', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g4_stats_res]",
+    ('gemm', ('256x128x32s3', ''), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[g4_stats]",
+    ('gemm', ('256x128x32s3', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[g4_plain]",
+    ('gemm', ('256x128x64s2', ''), ('colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g3_stats_ups]",
+    ('gemm', ('256x256x64pp', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p17_generic_gelu]",
+    ('gemm', ('256x256x64pp', ''), ('GEGLU',)): "test_gemm_float64_gpu.py::test_gemm_float64[p17_geglu16]",
+    ('gemm', ('256x256x64pp', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[p17_f16]",
+    ('gemm', ('256x256x64pp2', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p21_c16_res]",
+    ('gemm', ('256x256x64pp2', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p21_stats_res]",
+    ('gemm', ('256x256x64pp2', ''), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[p21_stats]",
+    ('gemm', ('256x256x64pp2', ''), ('upsample',)): "test_gemm_float64_gpu.py::test_gemm_float64[p21_ups]",
+    ('gemm', ('256x256x64ppsk', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[p19_sk16]",
+    ('gemm', ('256x256x64ppsk', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[p19_sk64]",
+    ('gemm', ('256x256x64s2w16', ''), ('C16 + C32', 'colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g9_c16_stats_ups]",
+    ('gemm', ('256x256x64s2w16', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g9_c16_res]",
+    ('gemm', ('256x256x64s2w16', ''), ('colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g9_stats_ups]",
+    ('gemm', ('256x256x64s2w16', ''), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_stats]",
+    ('gemm', ('256x256x64s2w16', ''), ('once',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_plain]",
+    ('gemm', ('256x256x64s2w16', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[g9_plain]",
+    ('gemm', ('64x128x64s2', ''), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[g1_stats_rowbias]",
+    ('gemm', ('64x128x64s2', ''), ('colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g1_stats_ups]",
+    ('gemm', ('64x128x64s2', 'splitk'), ('C16 + C32', 'colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[sk1_c16_stats_res]",
+    ('gemm', ('conv3x3n16', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[n31_vae_out]",
+    ('gemm', ('skinny128x64', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[s29_m8_c16]",
+    ('xavt', '', ('once',)): "test_conditioning_gpu.py::test_attention_fused_into_the_q_projection",
+}
+
+
+def test_covered_elsewhere_names_cases_of_exactly_that_form():
+    import attn64_cases as AC
+    import gemm64_cases as GC
+    for (kind, path, feats), where in COVERED_ELSEWHERE.items():
+        cid = where[where.index("[") + 1:-1] if where.endswith("]") else None
+        if kind == "gemm" and where.startswith("test_gemm_float64_gpu.py"):
+            c = GC.BY_ID[cid]
+            assert not c["exp"] and PA.gemm_path(c["variant"])[:2] == path and _case_features(c) == set(feats) - {"once"}, (kind, path, feats, cid)
+        elif kind in ("attn", "attn_ctx") and where.startswith("test_attention_float64_gpu.py"):
+            assert any(c["id"] == cid and c["variant"] == path for c in AC.CASES), (path, cid)
+        else:
+            assert where.startswith("test_conditioning_gpu.py::test_attention_fused_into_the_q_projection") and (kind == "xavt" or "xattn ending" in feats), (kind, path, feats)
+
+
+def test_every_op_form_of_the_bench_plans_is_audited_or_covered(E):
+    """SD1.5 64x64 N = 2, SDXL 128x128 N = 8 and their KL-VAE decoders, built on the device as bench.py builds them (not computed): the key of every
+    op -- kind, GEMM tile and split form or attention kernel, and the epilogue / wiring features it uses -- must occur in an audited plan above or
+    in COVERED_ELSEWHERE."""
+    def keys(spec, xattn=None):
+        with _built(E, spec, xattn, PA.MLB_F_OPSHAPES, False) as b:
+            return {PA.census_key(o) for o in PA.Plan(b.ctx).ops}
+    audited = set()
+    for spec, xattn, _ in AUDITED:
+        audited |= keys(spec, xattn)
+    need = {}
+    for spec in PA.BENCH_PLANS:
+        for k in keys(spec):
+            need.setdefault(k, []).append(PA.plan_id(spec))
+    others = sorted((k for k in need if k not in audited), key=str)
+    print(f"\n[plan audit] census: {len(need)} op forms in the bench plans, {len(need) - len(others)} met in audited plans, the others:")
+    for k in others:
+        print(f"  {k} ({', '.join(need[k])}): {COVERED_ELSEWHERE.get(k)}")
+    missing = [k for k in others if k not in COVERED_ELSEWHERE]
+    assert not missing, f"op forms of the bench plans that no audited plan contains and COVERED_ELSEWHERE does not list: {missing}"

@@ -16,4 +16,5 @@ EVAL = 2e-3      # VAE / TAESD decode and encode; CLIP embeddings and features (
 # regression at 128 x 128 passes it.  Hence two stated bounds:
 EVAL_HEADLINE = 1.6e-3   # UNet evaluations at BASELINE's sizes (measured 1.0 - 1.2e-3: a 40 % regression fails)
 EVAL_SMALL = 2.5e-3      # UNet evaluations at test-sized latents (measured 0.6 - 2.2e-3 depending on the summation order; the scatter, not a kernel, sets this bound)
+# Below that bound the guard is the plan audit (tests/test_plan_audit_gpu.py): every launch of the test-size plans against float64 on the operands it actually read.
 LATENT = 1e-2    # final latent of a complete sampled generation (20-step Euler-a and the other solvers: errors of all evaluations compound)

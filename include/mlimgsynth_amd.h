@@ -287,6 +287,18 @@ const char* mlts_model_identify(const MLTStore* S, int* wtype);
 int mlctx_tstore_load(MLCtx* C, const MLTStore* S);
 int mlctx_tstore_load_key(MLCtx* C, const MLTStore* S, const char* key);      /* one of them */
 
+/* ---------------------------------------------------------------- ESRGAN upscaler (host/upscaler.c; not in the reference)
+ * RRDBNet x4 (num_feat 64, num_grow_ch 32, num_block from the file) on mlsd_conv3x3_dense.  spec: a safetensors file with BasicSR's names (conv_first,
+ * body.{i}.rdb{1..3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr, conv_last, each .weight and .bias; an optional "params_ema." / "params." prefix), or
+ * "synth[:seed[:blocks]]" (default seed 1234, 2 blocks).  The x2 pixel-unshuffle variant (conv_first with 12 input channels), a missing tensor and a wrong shape fail
+ * with the tensor's name in mlsd_last_error().  run: src [n_img][3][h][w] planar floats in 0..1 on the host -> dst [n_img][3][4h][4w] (not clamped); the work buffers
+ * are one device allocation kept between calls and grown on demand.  Zero padding at the image border, whatever the context's tiling. */
+typedef struct MLIS_AmdUpscaler MLIS_AmdUpscaler;
+MLIS_AmdUpscaler* mlis_amd_upscaler_create(const char* spec);      /* NULL on error */
+void mlis_amd_upscaler_destroy(MLIS_AmdUpscaler* U);
+int mlis_amd_upscaler_info(const MLIS_AmdUpscaler* U, int* n_block, int* scale);
+int mlis_amd_upscaler_run(MLIS_AmdUpscaler* U, const float* src, int w, int h, int n_img, float* dst);
+
 /* ---------------------------------------------------------------- prompt pre-processing (src/prompt_preproc.h:104-209)
  * text = the prompt with emphasis marks / options removed; chunks index into it; loras name into lora_names */
 typedef struct { int begin, len; float w; } MLISPromptChunk;

@@ -82,7 +82,12 @@ typedef enum {
 	MLIS_OPT_AMD_FREEU_B1 = 142,           /* "freeu_b1" (float 0 .. 4, default 1.3): backbone factor of stage 1 */
 	MLIS_OPT_AMD_FREEU_B2 = 143,           /* "freeu_b2" (float 0 .. 4, default 1.4): backbone factor of stage 2 */
 	MLIS_OPT_AMD_FREEU_S1 = 144,           /* "freeu_s1" (float 0 .. 4, default 0.9): skip factor of stage 1 */
-	MLIS_OPT_AMD_FREEU_S2 = 145            /* "freeu_s2" (float 0 .. 4, default 0.2): skip factor of stage 2.  The four are device data of the engine: a change rebuilds nothing */
+	MLIS_OPT_AMD_FREEU_S2 = 145,           /* "freeu_s2" (float 0 .. 4, default 0.2): skip factor of stage 2.  The four are device data of the engine: a change rebuilds nothing */
+	/* ESRGAN upscaler (RRDBNet x4): a learned pixel-space upscaler for mlis_amd_tensor_upscale and, with hires_use_model, for the hires fix */
+	MLIS_OPT_AMD_UPSCALE_MODEL = 151,      /* "upscale_model" (string): a safetensors RRDBNet in BasicSR's naming, or "synth[:seed[:blocks]]"; empty clears it and frees the
+	                                        * resident upscaler.  The upscaler is built on first use and stays resident, keyed by this string */
+	MLIS_OPT_AMD_HIRES_USE_MODEL = 152     /* "hires_use_model" (int 0 / 1, default 0): the hires fix decodes its first pass, upscales the IMAGE 4x with upscale_model, resamples it
+	                                        * to the target size in the hires_upscaler mode (a plain resample, not antialiased) and runs the second pass as img2img from it */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 
@@ -162,6 +167,12 @@ int mlis_amd_lora_stats(MLIS_Ctx* ctx, int* n_restored, int* n_patched, int* n_c
  * Tap indices outside a plane are clamped to the border, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed.
  * Returns 1, MLIS_E_OPT_VALUE for a bad mode or size. */
 int mlis_amd_tensor_resample(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int mode);
+/* dst = src upscaled 4x by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 -> dst [4w][4h][3][n] (not clamped).  src == dst is allowed.
+ * The upscaler is built on the first use and stays resident in the context until the option changes (mlis_amd_upscaler_builds counts the builds); the image border is
+ * padded with zeros whatever "tiling" says.  Returns 1, MLIS_E_OPT_VALUE when no upscale_model is set or src is not a 3-channel image. */
+int mlis_amd_tensor_upscale(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst);
+/* upscalers constructed by this context so far (cumulative, like mlis_amd_engine_builds); *resident = 1 while one is held */
+int mlis_amd_upscaler_builds(MLIS_Ctx* ctx, int* resident);
 
 #ifdef __cplusplus
 }

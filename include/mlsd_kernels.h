@@ -474,6 +474,35 @@ int mlsd_freeu_backbone(float* dst, int64_t ld_dst, const float* src, int64_t ld
 int mlsd_freeu_skip(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, int n_img, int H, int W, int C, float* ws, const float* s_dev, void* stream);
 size_t mlsd_freeu_ws_bytes(int n_img, int H, int W, int C);
 int mlsd_freeu_depth(int n_terms);
+/* Dense-block convolution of the ESRGAN upscaler (csrc/hip/upscale.hip; not in the reference): 3x3, stride 1, zero padding 1, Cin in {32, 64, 96, 128, 160, 192} to N in
+ * {32, 64} output channels over a channels-last fp16 image [n_img][H][W] with lda halfs between pixels (lda >= Cin: A may be a channel slice of a wider buffer; columns >= Cin
+ * are never read).  upsample 1: the output is 2H x 2W and the taps read the nearest-2x upsampled image (folded into the gather, as mlsd_gemm_args.upsample).
+ * W_: fp16 [N][3][3][Cin], K-contiguous (mlsd_gemm's conv layout).  Outputs C16 (fp16, stride ldc16) and / or C32 (fp32, stride ldc32), each possibly a channel slice: columns
+ * outside [0, N) of a destination row are never written.
+ * Arithmetic: fp16 operands, fp32 accumulation on MFMA (v_mfma_f32_16x16x32_f16), nothing else rounded; then in fp32, each operation rounded once:
+ *   z = acc + bias[n];  a = lrelu ? (z >= 0 ? z : 0.2f z) : z;  y = a * scale + resid[m][n]  (scale applies even without resid);  resid2: y = y * scale2 + resid2[m][n];
+ *   C32 = y, C16 = y rounded to nearest even.  Deterministic: the same input gives the same bits.
+ * Refused with an error and no launch: Cin or N outside the lists; A or W_ not 16-byte aligned, lda not a multiple of 8; C32 / resid / resid2 not 16-byte aligned or a stride
+ * of theirs not a multiple of 4; C16 not 8-byte aligned or ldc16 not a multiple of 4; a stride below its width; an output that aliases A (a tap reads neighbours that
+ * another wave may already have overwritten) -- except an fp16 slice of A's own rows (ldc16 == lda, no upsample) in columns >= Cin, which the taps never read; C32
+ * overlapping a residual other than in place (same pointer and stride). */
+typedef struct mlsd_dconv_args {
+	const void* A; int64_t lda;
+	int n_img, H, W, Cin;
+	int upsample;
+	const void* W_; int N;
+	const float* bias;          /* [N] or NULL */
+	int lrelu;                  /* LeakyReLU(0.2) */
+	float scale;
+	const float* resid; int64_t ldr;      /* fp32 [M][ldr] or NULL */
+	float scale2;
+	const float* resid2; int64_t ldr2;    /* fp32 [M][ldr2] or NULL */
+	float* C32; int64_t ldc32;
+	void* C16; int64_t ldc16;
+} mlsd_dconv_args;
+int mlsd_conv3x3_dense(const mlsd_dconv_args* a, void* stream);
+/* label of the kernel instantiation these arguments launch, "dconv3x3<n32,c192[,up]>" (mlsd_gemm_variant's counterpart; valid until the thread's next call) */
+const char* mlsd_dconv_variant(const mlsd_dconv_args* a);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

@@ -314,11 +314,12 @@ static unsigned char* img_from_tensor(const MLIS_Tensor* t)
 /* ------------------------------------------------------------------ options */
 static const char k_usage[] =
 "Usage: mlimgsynth-amd [COMMAND] [OPTIONS]\n\n"
-"Commands: generate | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
+"Commands: generate | upscale | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
 "Generation:  -p --prompt TEXT   -n --nprompt TEXT   -d --image-dim W,H   -i --input PATH   --imask PATH\n"
 "             --ilatent PATH   --ilmask PATH   -o --output PATH   --olatent PATH   --no-prompt-parse BOOL\n"
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
-"Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic\n"
+"Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic   --hires-use-model y|n\n"
+"Upscaler:    --upscale-model PATH|synth[:SEED[:BLOCKS]]   (ESRGAN RRDBNet x4, safetensors);  upscale -i IN -o OUT --upscale-model PATH needs no -m\n"
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
@@ -489,6 +490,31 @@ end:
 	return R;
 }
 
+/* upscale: --input 4x through the --upscale-model, no SD model involved */
+static int cmd_upscale(Cli* C)
+{
+	const char *model = NULL;
+	mlis_option_get(C->ctx, MLIS_OPT_AMD_UPSCALE_MODEL, &model);
+	if (!model || !*model) FAIL("upscale needs --upscale-model");
+	if (!C->in_img) FAIL("upscale needs --input");
+	Img im; if (img_read(C->in_img, &im) < 0) return -1;
+	unsigned char *rgb = (unsigned char*)malloc((size_t)im.w * im.h * 3);      /* RGB: grey replicated, alpha dropped */
+	for (size_t i=0;i<(size_t)im.w*im.h;++i) for (int c=0;c<3;++c) rgb[i*3+c] = im.d[i*im.c + (im.c >= 3 ? c : 0)];
+	Img in3 = im; in3.d = rgb; in3.c = 3;
+	MLIS_Tensor t = {0};
+	tensor_from_img(&t, NULL, &in3);
+	free(rgb); free(im.d);
+	int r = mlis_amd_tensor_upscale(C->ctx, &t, &t);
+	if (r < 0) fprintf(stderr, "error: upscale: %s\n", mlis_errstr_get(C->ctx));
+	else {
+		unsigned char *px = img_from_tensor(&t);
+		r = img_write(C->out_img ? C->out_img : "output.png", px, (unsigned)t.n[0], (unsigned)t.n[1], 3, NULL);
+		free(px);
+	}
+	mlis_tensor_free(&t);
+	return r < 0 ? -1 : 1;
+}
+
 static int cmd_text(Cli* C, int encode)
 {
 	const char *prompt = NULL;
@@ -521,6 +547,7 @@ int main(int argc, char** argv)
 	if (!C.cmd) { fputs(k_usage, stderr); goto end; }
 	int r;
 	if (!strcmp(C.cmd, "generate")) r = cmd_generate(&C);
+	else if (!strcmp(C.cmd, "upscale")) r = cmd_upscale(&C);
 	else if (!strcmp(C.cmd, "list-backends")) {
 		r = 1;
 		for (unsigned i=0; ; ++i) {

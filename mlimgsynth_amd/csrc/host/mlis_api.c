@@ -49,6 +49,8 @@ struct MLIS_Ctx {
 	uint64_t control_image_gen;             /* counts the control images set: the mark an engine keeps on the one it holds (never 0 once an image is set) */
 	float control_strength, control_start, control_end;
 	int control_evals[2], control_pass;     /* controlled evaluations of the last generation's passes (mlis_amd_control_evals) */
+	char *path_upscale; MLIS_AmdUpscaler *upscaler;       /* MLIS_OPT_AMD_UPSCALE_MODEL and the resident upscaler built from it (dropped whenever the option changes) */
+	int n_upscaler_builds, hires_use_model;                                     /* mlis_amd_upscaler_builds; MLIS_OPT_AMD_HIRES_USE_MODEL */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
@@ -147,8 +149,10 @@ static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };
 static const char* const k_option_amd3[] = { "unet_tile_batch" };                           /* ids from MLIS_OPT_AMD_UNET_TILE_BATCH */
 static const char* const k_option_amd4[] = { "control_model", "control_image", "control_strength", "control_start", "control_end" };   /* ids from MLIS_OPT_AMD_CONTROL_MODEL */
 static const char* const k_option_amd5[] = { "freeu", "freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2" };   /* ids from MLIS_OPT_AMD_FREEU */
+static const char* const k_option_amd6[] = { "upscale_model", "hires_use_model" };                       /* ids from MLIS_OPT_AMD_UPSCALE_MODEL */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_UPSCALE_MODEL && x < MLIS_OPT_AMD_UPSCALE_MODEL + COUNTOF(k_option_amd6)) return k_option_amd6[x - MLIS_OPT_AMD_UPSCALE_MODEL];
 	if (x >= MLIS_OPT_AMD_FREEU && x < MLIS_OPT_AMD_FREEU + COUNTOF(k_option_amd5)) return k_option_amd5[x - MLIS_OPT_AMD_FREEU];
 	if (x >= MLIS_OPT_AMD_CONTROL_MODEL && x < MLIS_OPT_AMD_CONTROL_MODEL + COUNTOF(k_option_amd4)) return k_option_amd4[x - MLIS_OPT_AMD_CONTROL_MODEL];
 	if (x >= MLIS_OPT_AMD_UNET_TILE_BATCH && x < MLIS_OPT_AMD_UNET_TILE_BATCH + COUNTOF(k_option_amd3)) return k_option_amd3[x - MLIS_OPT_AMD_UNET_TILE_BATCH];
@@ -168,6 +172,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i4 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_MODEL + i4);
 	const int i5 = from_list(k_option_amd5, COUNTOF(k_option_amd5), 1, s, strlen(s));
 	if (i5 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_FREEU + i5);
+	const int i6 = from_list(k_option_amd6, COUNTOF(k_option_amd6), 1, s, strlen(s));
+	if (i6 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UPSCALE_MODEL + i6);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -262,6 +268,7 @@ static void control_engines_drop(MLIS_Ctx* S)
 		S->eng2 = NULL; S->eng2_key[0] = 0;
 	}
 }
+static void upscaler_drop(MLIS_Ctx* S) { if (S->upscaler) { mlis_amd_upscaler_destroy(S->upscaler); S->upscaler = NULL; } }
 static void textcond_drop(MLIS_Ctx* S) { if (S->tc) { mlis_amd_textcond_destroy(S->tc); S->tc = NULL; S->tc_key[0] = 0; } }
 static void applied_clear(MLIS_Ctx* S)
 {
@@ -293,6 +300,7 @@ MLB_API void mlis_ctx_destroy(MLIS_Ctx** pctx)
 	if (S->signature != CTX_SIGNATURE) return;
 	model_drop(S);
 	if (S->tok) clip_tokr_free(S->tok);
+	upscaler_drop(S); free(S->path_upscale);
 	free(S->path_control); if (S->ts_control) mlts_close(S->ts_control); mlis_tensor_free(&S->control_image);
 	free(S->backend); free(S->path_model); free(S->path_tae); free(S->path_aux); free(S->path_lora_dir); free(S->prompt_raw); free(S->nprompt_raw);
 	mlis_prompt_free(&S->prompt); mlis_prompt_free(&S->nprompt);
@@ -599,6 +607,12 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_FREEU_B2: if (!arg_float(A, 0, 4, 1.4f, &f)) BAD_VALUE; S->freeu_f[1] = f; break;
 	case MLIS_OPT_AMD_FREEU_S1: if (!arg_float(A, 0, 4, 0.9f, &f)) BAD_VALUE; S->freeu_f[2] = f; break;
 	case MLIS_OPT_AMD_FREEU_S2: if (!arg_float(A, 0, 4, 0.2f, &f)) BAD_VALUE; S->freeu_f[3] = f; break;
+	case MLIS_OPT_AMD_UPSCALE_MODEL:       /* a changed value frees the resident upscaler; the next use builds the new one */
+		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
+		if (!S->path_upscale || strcmp(S->path_upscale, s)) upscaler_drop(S);
+		str_set(&S->path_upscale, s);
+		break;
+	case MLIS_OPT_AMD_HIRES_USE_MODEL: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->hires_use_model = i; break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -671,6 +685,8 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_CONTROL_START: { float *p = va_arg(ap, float*); if (p) *p = S->control_start; } break;
 	case MLIS_OPT_AMD_CONTROL_END: { float *p = va_arg(ap, float*); if (p) *p = S->control_end; } break;
 	case MLIS_OPT_AMD_FREEU: { int *p = va_arg(ap, int*); if (p) *p = S->freeu; } break;
+	case MLIS_OPT_AMD_UPSCALE_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_upscale ? S->path_upscale : ""; } break;
+	case MLIS_OPT_AMD_HIRES_USE_MODEL: { int *p = va_arg(ap, int*); if (p) *p = S->hires_use_model; } break;
 	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
 		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
@@ -1278,11 +1294,12 @@ static int engine_for_image(MLIS_Ctx* S, int w, int h)
 }
 
 MLB_API int mlis_image_encode(MLIS_Ctx* S, const MLIS_Tensor* image, MLIS_Tensor* latent, int flags)
-{	/* :1301-1330; batch: the same image for every batch element */
+{	/* :1301-1330; batch: the same image for every batch element, or (n[3] == BATCH_SIZE: the hires fix with an upscale model) one image each */
 	(void)flags;
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
 	int r = mlis_setup(S); if (r < 0) return r;
-	if (image->n[2] != 3 || image->n[3] != 1) return api_error(S, MLIS_E_IMAGE, "invalid input image shape: %dx%dx%dx%d", image->n[0], image->n[1], image->n[2], image->n[3]);
+	const int Bi = S->n_batch > 0 ? S->n_batch : 1;
+	if (image->n[2] != 3 || (image->n[3] != 1 && image->n[3] != Bi)) return api_error(S, MLIS_E_IMAGE, "invalid input image shape: %dx%dx%dx%d", image->n[0], image->n[1], image->n[2], image->n[3]);
 	const int w = image->n[0], h = image->n[1];
 	if ((r = tiling_check(S)) < 0) return r;
 	if (engine_for_image(S, w, h) < 0) return -1;
@@ -1294,15 +1311,16 @@ MLB_API int mlis_image_encode(MLIS_Ctx* S, const MLIS_Tensor* image, MLIS_Tensor
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
 	const size_t per = (size_t)3 * w * h;
 	float *imgs = (float*)malloc(per * B * 4);
-	for (int b=0;b<B;++b) memcpy(imgs + per*b, image->d, per*4);
+	for (int b=0;b<B;++b) memcpy(imgs + per*b, image->d + (image->n[3] == B ? per*b : 0), per*4);
 	uint64_t seeds[MAX_IMAGES]; for (int b=0;b<B && b<MAX_IMAGES;++b) seeds[b] = S->seed + b;
 	mlis_amd_seed_ex(S->eng, seeds, S->rng_offset);
 	r = mlis_amd_encode(S->eng, imgs, 1);
 	free(imgs);
 	if (r < 0) return api_error_lib(S, r == MLIS_E_NAN ? MLIS_E_NAN : MLIS_E_UNKNOWN);
 	S->rng_offset = mlis_amd_rng_offset(S->eng);
-	mlis_tensor_resize(latent, w/8, h/8, 4, 1);
-	if (mlsd_memcpy(latent->d, mlis_amd_latent_device(S->eng), (size_t)4*(w/8)*(h/8)*4, 1, NULL) || mlsd_device_sync()) return api_error_lib(S, MLIS_E_UNKNOWN);
+	const int n_lat = image->n[3];      /* one latent per image given */
+	mlis_tensor_resize(latent, w/8, h/8, 4, n_lat);
+	if (mlsd_memcpy(latent->d, mlis_amd_latent_device(S->eng), (size_t)n_lat*4*(w/8)*(h/8)*4, 1, NULL) || mlsd_device_sync()) return api_error_lib(S, MLIS_E_UNKNOWN);
 	return progress(S, MLIS_STAGE_IMAGE_ENCODE, 1, 1);
 }
 
@@ -1369,6 +1387,50 @@ MLB_API int mlis_amd_tensor_resample(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_T
 	return tensor_resample(S, src, dst, w, h, mode);
 }
 
+/* ------------------------------------------------------------------ model upscaling (ESRGAN, host/upscaler.c) */
+/* the context's upscaler for the upscale_model option as it stands: built on first use, resident until the option changes */
+static int upscaler_get(MLIS_Ctx* S)
+{
+	if (str_empty(S->path_upscale)) return api_error(S, MLIS_E_OPT_VALUE, "no upscale_model is set");
+	if (S->upscaler) return 1;
+	int r = backend_setup(S); if (r < 0) return r;
+	S->upscaler = mlis_amd_upscaler_create(S->path_upscale);
+	if (!S->upscaler) return api_error_lib(S, MLIS_E_UNKNOWN);
+	S->n_upscaler_builds++;
+	return 1;
+}
+
+/* src may be dst (the result is computed into a buffer of its own first) */
+static int tensor_upscale(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst)
+{
+	if (str_empty(S->path_upscale)) return api_error(S, MLIS_E_OPT_VALUE, "no upscale_model is set");
+	if (!src || !dst || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || src->n[2] != 3 || src->n[3] < 1)
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor to upscale: an image of 3 channels is needed");
+	const int w = src->n[0], h = src->n[1], b = src->n[3];
+	if ((double)w * h * b * 16 * 3 >= 2147483648.0) return api_error(S, MLIS_E_OPT_VALUE, "image too large to upscale: %dx%d x %d", w, h, b);
+	int r = upscaler_get(S); if (r < 0) return r;
+	float *out = (float*)malloc(sizeof(float) * (size_t)16 * w * h * 3 * b);
+	if (!out) return api_error(S, MLIS_E_UNKNOWN, "out of memory");
+	if (mlis_amd_upscaler_run(S->upscaler, src->d, w, h, b, out) < 0) { free(out); return api_error_lib(S, MLIS_E_UNKNOWN); }
+	mlis_tensor_resize(dst, 4 * w, 4 * h, 3, b);
+	memcpy(dst->d, out, sizeof(float) * (size_t)16 * w * h * 3 * b);
+	free(out);
+	return 1;
+}
+
+MLB_API int mlis_amd_tensor_upscale(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_upscale(S, src, dst);
+}
+
+MLB_API int mlis_amd_upscaler_builds(MLIS_Ctx* S, int* resident)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	if (resident) *resident = S->upscaler != NULL;
+	return S->n_upscaler_builds;
+}
+
 /* ------------------------------------------------------------------ generation */
 static int denoise_cb(void* user, int step, int n_step, int nfe)
 {
@@ -1405,7 +1467,11 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	}
 	if (S->flags & CF_USE_TAE) ADD(", VAE: tae");
 	if (S->tiling) ADD(", Tiling: %s", k_tiling[S->tiling]);
-	if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
+	if (hires_on(S) && S->hires_use_model) {       /* the model file's basename, as ControlNet below */
+		const char *b = S->path_upscale ? S->path_upscale : "", *sl = strrchr(b, '/'); if (sl) b = sl + 1;
+		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
+		ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %.*s, Denoising strength: %g", S->hires_scale, hires_n_step, (int)(e - b), b, S->hires_denoise);
+	} else if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
 		k_resample[S->hires_upscaler], S->hires_denoise);
 	if (S->tiled_tile) ADD(", Tiled diffusion: %d, Tile overlap: %d", S->tiled_tile, S->tiled_overlap);
 	if (S->tiled_tile && S->tiled_pack > 1) ADD(", Tile batch: %d", S->tiled_pack);
@@ -1512,7 +1578,8 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 
 /* hires fix: the txt2img pass at IMAGE_DIM (never decoded), its latent upscaled, then the img2img-from-latent pass at the target size with
  * f_t_ini = hires_denoise -- what a caller gets from generate (NO_DECODE) + mlis_amd_tensor_resample + generate (MLIS_TUF_LATENT), with the
- * prompt, the token ids and the prompt's LoRAs in place until the end and the Philox streams running on from the first pass */
+ * prompt, the token ids and the prompt's LoRAs in place until the end and the Philox streams running on from the first pass.  With hires_use_model the first pass
+ * IS decoded, its image goes 4x through the upscale model and a plain resample to the target size, and the second pass is img2img from that image */
 static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int* hires_n_step)
 {
 	static const struct { int flag; const char* what; } inputs[] = { {MLIS_TUF_IMAGE, "an input image (image)"}, {MLIS_TUF_LATENT, "an input latent (tensor_use_flags latent)"},
@@ -1520,12 +1587,19 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 	for (int i=0;i<COUNTOF(inputs);++i) if (S->tuflags & inputs[i].flag)
 		return api_error(S, MLIS_E_OPT_VALUE, "hires_scale %g cannot be combined with %s: the hires fix is a txt2img feature", S->hires_scale, inputs[i].what);
 	const float f_t_ini = S->f_t_ini; const int n_step = S->n_step, tuflags = S->tuflags;
-	int r = generate_pass(S, 0, pw_img, ph_img);
+	const int use_model = S->hires_use_model;
+	int r = generate_pass(S, use_model, pw_img, ph_img);
 	if (r >= 0) {
 		const int steps1 = S->last_n_step, lw = S->latent.n[0], lh = S->latent.n[1];
-		r = tensor_resample(S, &S->latent, &S->latent, (int)floor((double)lw * S->hires_scale + 0.5), (int)floor((double)lh * S->hires_scale + 0.5), S->hires_upscaler);
+		const int tw = (int)floor((double)lw * S->hires_scale + 0.5), th = (int)floor((double)lh * S->hires_scale + 0.5);      /* the target latent size, either way */
+		if (use_model) {
+			/* the decoded first pass upscaled 4x by the model, brought to the target pixel size by a plain resample; the second pass encodes it (generate_pass, MLIS_TUF_IMAGE):
+			 * what a caller gets from generate + mlis_amd_tensor_upscale + mlis_amd_tensor_resample + generate with an input image */
+			r = tensor_upscale(S, &S->image, &S->image);
+			if (r >= 0) r = tensor_resample(S, &S->image, &S->image, tw * 8, th * 8, S->hires_upscaler);
+		} else r = tensor_resample(S, &S->latent, &S->latent, tw, th, S->hires_upscaler);
 		if (r >= 0) {
-			S->tuflags = (tuflags & MLIS_TUF_CONDITIONING) | MLIS_TUF_LATENT;
+			S->tuflags = (tuflags & MLIS_TUF_CONDITIONING) | (use_model ? MLIS_TUF_IMAGE : MLIS_TUF_LATENT);
 			S->f_t_ini = S->hires_denoise;
 			if (S->hires_steps > 0) S->n_step = S->hires_steps;
 			int method, sched; sampler_defaults(S, hires_n_step, &method, &sched);   /* "Hires steps": the count asked for (as "Steps" does, webui's convention); with f_t_ini < 1 the pass runs fewer */
@@ -1542,6 +1616,8 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 MLB_API int mlis_generate(MLIS_Ctx* S)
 {
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	if (hires_on(S) && S->hires_use_model && str_empty(S->path_upscale))
+		return api_error(S, MLIS_E_OPT_VALUE, "hires_use_model is set but no upscale_model");
 	int r = mlis_setup(S); if (r < 0) return r;
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);

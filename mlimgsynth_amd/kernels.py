@@ -102,12 +102,29 @@ class FreeuArgs(ctypes.Structure):
     _fields_ = [("dst", vp), ("ld_dst", c_i64), ("src", vp), ("ld_src", c_i64), ("n_img", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("ws", vp), ("f", vp)]
 
 
+class DconvArgs(ctypes.Structure):
+    """mlsd_dconv_args: the dense-block convolution of the ESRGAN upscaler (hip/upscale.hip)"""
+    _fields_ = [("A", vp), ("lda", c_i64), ("n_img", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("upsample", c_int),
+                ("W_", vp), ("N", c_int), ("bias", vp), ("lrelu", c_int), ("scale", c_f), ("resid", vp), ("ldr", c_i64),
+                ("scale2", c_f), ("resid2", vp), ("ldr2", c_i64), ("C32", vp), ("ldc32", c_i64), ("C16", vp), ("ldc16", c_i64)]
+
+
 class XavtArgs(ctypes.Structure):
     _fields_ = [("v", vp), ("ldv", c_i64), ("n_img", c_int), ("Tk", c_int), ("N", c_int), ("vt", vp)]
 
 
 def gemm(args, stream=None):
     check(lib().mlsd_gemm(ctypes.byref(args), vp(stream)), "mlsd_gemm")
+
+
+def conv3x3_dense(args, stream=None):
+    check(lib().mlsd_conv3x3_dense(ctypes.byref(args), vp(stream)), "mlsd_conv3x3_dense")
+
+
+def dconv_variant(args):
+    f = lib().mlsd_dconv_variant
+    f.restype = ctypes.c_char_p
+    return f(ctypes.byref(args)).decode()
 
 
 def gemm_splitk_ws_bytes(m, n, ksplit):

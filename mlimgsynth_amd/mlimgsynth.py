@@ -45,7 +45,8 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                             AMD_HIRES_STEPS=104, AMD_HIRES_UPSCALER=105, AMD_UNET_TILE=111,
                                                                            AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121, AMD_CONTROL_MODEL=131, AMD_CONTROL_IMAGE=132,
                                                                            AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135, AMD_FREEU=141,
-                                                                           AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145))
+                                                                           AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145,
+                                                                           AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 MLIS_CTEF_NO_NORM = 1
 
@@ -78,6 +79,7 @@ _PROTOTYPES = {
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
 mlis_lib = None
@@ -270,9 +272,10 @@ class MLImgSynth:
         return self._transform(self._lib.mlis_mask_encode, "encode the mask", mask, flags)
 
     # ---- hires fix
-    def hires_set(self, scale, denoise=None, steps=None, upscaler=None):
+    def hires_set(self, scale, denoise=None, steps=None, upscaler=None, use_model=None):
         """Two-pass generation: scale 0 or 1 switches it off, else 1 < scale <= 4; denoise in (0, 1] is the second pass's strength,
-        steps its step count (0 = the STEPS value), upscaler 'nearest' | 'bilinear' | 'bicubic'.  The options persist."""
+        steps its step count (0 = the STEPS value), upscaler 'nearest' | 'bilinear' | 'bicubic'; use_model True: the first pass is decoded and
+        upscaled 4x by the "upscale_model" option's ESRGAN model, then resampled to the target size in the `upscaler` mode.  The options persist."""
         self.option_set("hires_scale", scale)
         if denoise is not None:
             self.option_set("hires_denoise", denoise)
@@ -280,6 +283,8 @@ class MLImgSynth:
             self.option_set("hires_steps", steps)
         if upscaler is not None:
             self.option_set("hires_upscaler", upscaler)
+        if use_model is not None:
+            self.option_set("hires_use_model", 1 if use_model else 0)
 
     # ---- tiled diffusion
     def unet_tile_set(self, tile, overlap=None, batch=None):
@@ -332,6 +337,15 @@ class MLImgSynth:
         tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
         if self._lib.mlis_amd_tensor_resample(self._ctx, ctypes.byref(tin), tout, w, h, mode) < 0:
             raise RuntimeError("Failed to resample the tensor: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
+
+    def upscale(self, image):
+        """Upscale an image tensor [n,3,h,w] in [0,1] 4x with the ESRGAN model of the "upscale_model" option (a safetensors RRDBNet or
+        "synth[:seed[:blocks]]"); the result is not clamped.  The upscaler is built on first use and stays resident."""
+        tin = image._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_upscale(self._ctx, ctypes.byref(tin), tout) < 0:
+            raise RuntimeError("Failed to upscale the image: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
 
     def engine_builds(self):

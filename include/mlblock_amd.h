@@ -197,6 +197,10 @@ typedef struct MLOpRecord {
 	const void* args; size_t args_bytes;
 } MLOpRecord;
 int mlctx_op_record(const MLCtx* C, int i, MLOpRecord* out);     /* 1, or -1 if there is no op i */
+/* the op kinds themselves, from the table the executor runs on: the short name of kind `kind` ("gemm", "attn", ...: the order above) and the size of its argument
+ * structure; 1, or 0 when there is no such kind (the kinds are 0 .. the first that returns 0) */
+int mlctx_op_kind_info(int kind, const char** name, size_t* args_bytes);
+int mlctx_op_kind_can_fuse(int kind);   /* 1 if MLOpRecord.fused can say of an op of this kind that it runs inside its producer's launch, 0 if the kind always launches */
 /* device storage of parameter i of mlctx_param_info: address (a virtual one in a weight-streaming plan: see mlctx_weight_slab), elements including padding, bytes per element */
 int mlctx_param_device(const MLCtx* C, int i, const void** dev, size_t* elems, int* elem_bytes);
 int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes);   /* device slab k of a weight-streaming plan; 0 when there is no slab k */

@@ -643,36 +643,8 @@ MLB_API int mlctx_output_get(MLCtx* C, MLTensor* t, float* out, size_t nbytes)
 /* ------------------------------------------------------------------ prep / compute */
 static int run_op(MLCtx* C, MLOp* op)
 {
-	void *st = C->stream;
-	switch (op->kind) {
-	case OP_GEMM: return mlsd_gemm(&op->u.gemm, st);
-	case OP_ATTN: return mlsd_attention(&op->u.attn, st);
-	case OP_ATTN_CTX: return mlsd_attention_ctx(&op->u.attn, st);   /* cross attention over more than 96 context rows (windowed prompt) */
-	case OP_GN:   if (op->fused) return 0;                    /* its producer's reduce pass ends with it (wire_gn_fold) */
-	              return mlsd_groupnorm(&op->u.gn, st);
-	case OP_LN:   if (op->fused) return 0;                    /* its producer ends with it (wire_ln_fold) */
-	              return mlsd_layernorm(op->u.ln.x, op->u.ln.ldx, op->u.ln.rows, op->u.ln.d, op->u.ln.eps, op->u.ln.g, op->u.ln.b,
-	                                   op->u.ln.y16, op->u.ln.y32, st);
-	case OP_NCHW2NHWC: return mlsd_nchw_to_nhwc_f16(op->u.n2h.src, op->u.n2h.n_src, op->u.n2h.C, op->u.n2h.HW, op->u.n2h.dst,
-	                                   op->u.n2h.n_dst, op->u.n2h.Cpad, op->u.n2h.scale, op->u.n2h.scale0, op->u.n2h.mode, st);
-	case OP_NHWC2NCHW: return mlsd_nhwc_to_nchw_f32(op->u.h2n.src, op->u.h2n.ld, op->u.h2n.n, op->u.h2n.C, op->u.h2n.HW,
-	                                   op->u.h2n.dst, op->u.h2n.mul, op->u.h2n.add, st);
-	case OP_TEMB: return mlsd_timestep_embedding(op->u.temb.t, op->u.temb.n, op->u.temb.dim, op->u.temb.maxp, op->u.temb.out, st);
-	case OP_ACT:  return mlsd_act_f32_to_f16(op->u.act.x, op->u.act.y, op->u.act.n, op->u.act.act, st);
-	case OP_CLIP_EMBED: return mlsd_clip_embed(op->u.cemb.tok, op->u.cemb.n, op->u.cemb.T, op->u.cemb.d, op->u.cemb.tw,
-	                                   op->u.cemb.pw, op->u.cemb.out, st);
-	case OP_SOFTMAX: return mlsd_softmax_rows(op->u.smax.in, op->u.smax.ld_in, op->u.smax.out, op->u.smax.ld_out,
-	                                   op->u.smax.rows, op->u.smax.cols, op->u.smax.scale, st);
-	case OP_COPY_F32: return mlsd_memcpy(op->u.copy.dst, op->u.copy.src, op->u.copy.nbytes, 2, st);
-	case OP_CTRL_ADD: return mlsd_ctrl_add(op->u.cadd.dst, op->u.cadd.ld_dst, op->u.cadd.base, op->u.cadd.ld_base, op->u.cadd.ctrl, op->u.cadd.ld_ctrl,
-	                                   op->u.cadd.n_img, op->u.cadd.rows, op->u.cadd.C, op->u.cadd.n_ctrl, op->u.cadd.gain, st);
-	case OP_FREEU_BACKBONE: return mlsd_freeu_backbone(op->u.freeu.dst, op->u.freeu.ld_dst, op->u.freeu.src, op->u.freeu.ld_src, op->u.freeu.n_img,
-	                                   op->u.freeu.H * op->u.freeu.W, op->u.freeu.C, op->u.freeu.ws, op->u.freeu.f, st);
-	case OP_FREEU_SKIP: return mlsd_freeu_skip(op->u.freeu.dst, op->u.freeu.ld_dst, op->u.freeu.src, op->u.freeu.ld_src, op->u.freeu.n_img, op->u.freeu.H, op->u.freeu.W,
-	                                   op->u.freeu.C, op->u.freeu.ws, op->u.freeu.f, st);
-	case OP_XA_VT: return mlsd_xattn_pack_vt(op->u.xavt.v, op->u.xavt.ldv, op->u.xavt.n_img, op->u.xavt.Tk, op->u.xavt.N, op->u.xavt.vt, st);
-	}
-	return mlsd_set_error(-1, "unknown op kind %d", (int)op->kind);
+	if ((unsigned)op->kind >= OP_KIND_COUNT || !k_op_class[op->kind].run) return mlsd_set_error(-1, "unknown op kind %d", (int)op->kind);
+	return k_op_class[op->kind].run(op, C->stream);
 }
 
 /* ------------------------------------------------------------------ GEMM tile selection
@@ -1061,35 +1033,6 @@ done:
  * that launch gets a statistics buffer and the GroupNorm's first pass over the fp32 map is replaced by gn_finalize over the
  * statistics.  The choice is a pure function of the plan (tile table + shapes); MLSD_GN_TWO_PASS=1 keeps the two-pass form
  * (A/B timing, and the reference for the parity test). */
-/* every buffer an op writes (at most 3) */
-static int op_outputs(const MLOp* o, const void* out[3])
-{
-	int n = 0;
-	switch (o->kind) {
-	case OP_GEMM:
-		if (o->u.gemm.C32) out[n++] = o->u.gemm.C32;
-		if (o->u.gemm.C16) out[n++] = o->u.gemm.C16;
-		if (o->u.gemm.ln_y16 && n < 3) out[n++] = o->u.gemm.ln_y16;
-		if (o->u.gemm.gn_y16 && n < 3) out[n++] = o->u.gemm.gn_y16;
-		if (o->u.gemm.xa_k && n < 3) out[n++] = o->u.gemm.xa_out;
-		break;
-	case OP_ATTN: case OP_ATTN_CTX: out[n++] = o->u.attn.out; break;
-	case OP_GN: out[n++] = o->u.gn.y16; if (o->u.gn.raw16) out[n++] = o->u.gn.raw16; break;
-	case OP_LN: if (o->u.ln.y16) out[n++] = o->u.ln.y16; if (o->u.ln.y32) out[n++] = o->u.ln.y32; break;
-	case OP_NCHW2NHWC: out[n++] = o->u.n2h.dst; break;
-	case OP_NHWC2NCHW: out[n++] = o->u.h2n.dst; break;
-	case OP_TEMB: out[n++] = o->u.temb.out; break;
-	case OP_ACT: out[n++] = o->u.act.y; break;
-	case OP_CLIP_EMBED: out[n++] = o->u.cemb.out; break;
-	case OP_SOFTMAX: out[n++] = o->u.smax.out; break;
-	case OP_COPY_F32: out[n++] = o->u.copy.dst; break;
-	case OP_XA_VT: out[n++] = o->u.xavt.vt; break;
-	case OP_CTRL_ADD: out[n++] = o->u.cadd.dst; break;
-	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: out[n++] = o->u.freeu.dst; out[n++] = o->u.freeu.ws; break;
-	}
-	return n;
-}
-
 /* The producer of a GroupNorm source is the op that DEFINES the source tensor (MLTensor.prod, recorded with the GroupNorm:
  * MLOp.gn_src), not "the last GEMM that happens to write this address": arena blocks are recycled, so an address match alone
  * could pick a stale writer.  It qualifies only if it still writes exactly this matrix and NO op between it and the GroupNorm
@@ -1104,8 +1047,8 @@ static MLOp* gn_producer(MLCtx* C, int gn_idx, int src, const float* x, int64_t 
 	    o->u.gemm.act == MLSD_ACT_GEGLU) return NULL;
 	const char *lo = (const char*)x, *hi = lo + (size_t)rows * ld * sizeof(float);
 	for (int k=j+1; k<gn_idx; ++k) {
-		const void *out[3];
-		const int n = op_outputs(&C->ops[k], out);
+		const void *out[MLOP_MAX_OUTPUTS];
+		const int n = mlop_outputs(&C->ops[k], out);
 		for (int q=0;q<n;++q) if ((const char*)out[q] >= lo && (const char*)out[q] < hi) return NULL;
 	}
 	return o;
@@ -1250,21 +1193,12 @@ static int hoist_on(void);
  * compute(1) | upload(3) into slab 1 || compute(2) ...: hipMemcpyAsync on a copy stream, ordered against the compute stream by events, so the next segment's weights
  * arrive under the current segment's launches.  Same launches, same operands: results are bit-identical to the resident plan.  Resident instead of streamed: the
  * K/V projection weights of the cross attentions (their launch is step-invariant and hoisted out of the evaluation) and everything that is not a weight. */
-static const void** op_weight_slots(MLOp* o, int* n)
+/* where op o keeps the pointers that may be parameters (k_op_class[kind].params); returns how many */
+static int op_weight_slots(MLOp* o, const void** slots[MLOP_MAX_PARAMS])
 {
-	static _Thread_local const void** slots[8];
-	int k = 0;
-	switch (o->kind) {
-	case OP_GEMM: slots[k++] = &o->u.gemm.W_; slots[k++] = (const void**)&o->u.gemm.bias; slots[k++] = (const void**)&o->u.gemm.bias_m;
-	              slots[k++] = (const void**)&o->u.gemm.ln_gamma; slots[k++] = (const void**)&o->u.gemm.ln_beta;
-	              slots[k++] = (const void**)&o->u.gemm.gn_gamma; slots[k++] = (const void**)&o->u.gemm.gn_beta; break;     /* (a GroupNorm folded into the reduce pass: EXPERIMENTS builds) */
-	case OP_GN:   slots[k++] = (const void**)&o->u.gn.gamma; slots[k++] = (const void**)&o->u.gn.beta; break;
-	case OP_LN:   slots[k++] = (const void**)&o->u.ln.g; slots[k++] = (const void**)&o->u.ln.b; break;
-	case OP_CLIP_EMBED: slots[k++] = &o->u.cemb.tw; slots[k++] = (const void**)&o->u.cemb.pw; break;
-	default: break;
-	}
-	*n = k;
-	return (const void**)slots;
+	const MLOpClass *k = &k_op_class[o->kind];
+	for (int q=0; q<k->params.n; ++q) slots[q] = (const void**)((char*)o + k->params.off[q]);
+	return k->params.n;
 }
 
 static int pv_find(const MLCtx* C, size_t voff)
@@ -1325,8 +1259,8 @@ static int wstream_setup(MLCtx* C)
 	C->segs = (MLWSeg*)calloc((size_t)cap, sizeof(MLWSeg)); C->n_segs = 0;
 	MLWSeg *cur = NULL;
 	for (int i=0;i<C->n_ops && R>0;++i) {
-		int ns; const void ***sl = (const void***)op_weight_slots(&C->ops[i], &ns);
-		int al[8], na = 0; size_t add = 0;
+		const void **sl[MLOP_MAX_PARAMS]; const int ns = op_weight_slots(&C->ops[i], sl);
+		int al[MLOP_MAX_PARAMS], na = 0; size_t add = 0;
 		for (int q=0;q<ns;++q) {
 			const void *pp = *sl[q];
 			if (!pp || !is_virtual(C, pp)) continue;
@@ -1388,7 +1322,7 @@ static int wstream_setup(MLCtx* C)
 		MLWSeg *sg = &C->segs[g];
 		C->stream_bytes_per_eval += sg->bytes;
 		for (int i=sg->op0; i<sg->op1; ++i) {
-			int ns; const void ***sl = (const void***)op_weight_slots(&C->ops[i], &ns);
+			const void **sl[MLOP_MAX_PARAMS]; const int ns = op_weight_slots(&C->ops[i], sl);
 			for (int q=0;q<ns;++q) {
 				const void *pp = *sl[q];
 				if (!pp || !is_virtual(C, pp)) continue;
@@ -1670,23 +1604,7 @@ MLB_API int mlctx_op_record(const MLCtx* C, int i, MLOpRecord* out)
 	const MLOp *o = &C->ops[i];
 	out->kind = (int)o->kind; out->fused = o->fused; out->once = o->once;
 	out->gn_src[0] = o->gn_src[0]; out->gn_src[1] = o->gn_src[1];
-	out->label = o->label; out->args = &o->u; out->args_bytes = 0;
-	switch (o->kind) {
-	case OP_GEMM: out->args_bytes = sizeof(o->u.gemm); break;
-	case OP_ATTN: case OP_ATTN_CTX: out->args_bytes = sizeof(o->u.attn); break;
-	case OP_GN: out->args_bytes = sizeof(o->u.gn); break;
-	case OP_LN: out->args_bytes = sizeof(o->u.ln); break;
-	case OP_NCHW2NHWC: out->args_bytes = sizeof(o->u.n2h); break;
-	case OP_NHWC2NCHW: out->args_bytes = sizeof(o->u.h2n); break;
-	case OP_TEMB: out->args_bytes = sizeof(o->u.temb); break;
-	case OP_ACT: out->args_bytes = sizeof(o->u.act); break;
-	case OP_CLIP_EMBED: out->args_bytes = sizeof(o->u.cemb); break;
-	case OP_SOFTMAX: out->args_bytes = sizeof(o->u.smax); break;
-	case OP_COPY_F32: out->args_bytes = sizeof(o->u.copy); break;
-	case OP_XA_VT: out->args_bytes = sizeof(o->u.xavt); break;
-	case OP_CTRL_ADD: out->args_bytes = sizeof(o->u.cadd); break;
-	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: out->args_bytes = sizeof(o->u.freeu); break;
-	}
+	out->label = o->label; out->args = &o->u; out->args_bytes = k_op_class[o->kind].args_bytes;
 	return 1;
 }
 
@@ -1748,28 +1666,15 @@ MLB_API int mlctx_op_info(const MLCtx* C, int i, const char** label, double* flo
 	if (i < 0 || i >= C->n_ops) return -1;
 	if (label) {
 		const MLOp *op = &C->ops[i];
+		const MLOpClass *k = &k_op_class[op->kind];
 		static _Thread_local char buf[96];
-		if (op->kind == OP_GEMM) {
-			const mlsd_gemm_args *g = &op->u.gemm;
-			snprintf(buf, sizeof(buf), "%s%s%s", op->label[0] ? op->label : mlsd_gemm_variant(g), C->flags & MLB_F_OPSHAPES ? " " : "", "");
-			if (C->flags & MLB_F_OPSHAPES) {
-				size_t l = strlen(buf);
-				snprintf(buf + l, sizeof(buf) - l, "%dx%dx%d%s%s", g->M, g->N, g->K, g->C32 ? " f32" : "", g->resid ? "+res" : "");
-			}
+		*label = (!op->label[0] && k->unnamed) ? k->unnamed(op) : op->label;
+		if (k->shape && (C->flags & MLB_F_OPSHAPES)) {
+			snprintf(buf, sizeof(buf), "%s ", *label);
+			const size_t l = strlen(buf);
+			k->shape(op, buf + l, sizeof(buf) - l);
 			*label = buf;
-		} else if ((op->kind == OP_ATTN || op->kind == OP_ATTN_CTX) && (C->flags & MLB_F_OPSHAPES)) {
-			const mlsd_attn_args *a = &op->u.attn;
-			snprintf(buf, sizeof(buf), "%s b%d h%d d%d %dx%d", op->label, a->n_batch, a->n_head, a->d_head, a->Tq, a->Tk);
-			*label = buf;
-		} else if (op->kind == OP_LN && (C->flags & MLB_F_OPSHAPES)) {
-			snprintf(buf, sizeof(buf), "%s %dx%d", op->label, op->u.ln.rows, op->u.ln.d);
-			*label = buf;
-		} else if (op->kind == OP_GN && (C->flags & MLB_F_OPSHAPES)) {
-			const mlsd_gn_args *a = &op->u.gn;
-			snprintf(buf, sizeof(buf), "%s n%d hw%d c%d+%d%s%s", op->label, a->n_img, a->HW, a->C1, a->C2, a->raw16 ? " +raw" : "",
-				a->cs1 ? " stats" : "");   /* "stats": first pass replaced by the producers' column statistics */
-			*label = buf;
-		} else *label = op->label;
+		}
 	}
 	if (flops) *flops = C->ops[i].flops;
 	return 1;
@@ -1780,40 +1685,7 @@ MLB_API double mlctx_op_bytes(const MLCtx* C, int i)
 {
 	if (i < 0 || i >= C->n_ops) return 0;
 	const MLOp *op = &C->ops[i];
-	switch (op->kind) {
-	case OP_GEMM: {
-		const mlsd_gemm_args *g = &op->u.gemm;
-		const double nout = g->act == MLSD_ACT_GEGLU ? g->N / 2 : g->N;
-		double b = g->conv ? 2.0 * g->n_img * g->H * g->W * g->Cin : 2.0 * g->M * (double)g->K;
-		b += 2.0 * g->N * (double)g->K;
-		if (g->bias) b += 4.0 * g->N;
-		if (g->rowbias) b += 4.0 * (g->M / (g->rows_per_batch > 0 ? g->rows_per_batch : 1)) * (double)g->N;
-		if (g->resid) b += 4.0 * g->M * nout;
-		if (g->C32) b += 4.0 * g->M * nout;
-		if (g->C16) b += 2.0 * g->M * nout;
-		if (g->xa_k) b += 2.0 * g->M * nout + 2.0 * 2.0 * (g->M / g->xa_Tq) * (double)g->xa_Tk * g->N;      /* the attention's output + the images' K and V */
-		return b;
-	}
-	case OP_ATTN: case OP_ATTN_CTX: {
-		const mlsd_attn_args *a = &op->u.attn;
-		const double D = (double)a->n_head * a->d_head;
-		return 2.0 * a->n_batch * D * (2.0 * a->Tq + 2.0 * a->Tk);
-	}
-	case OP_GN: {
-		const mlsd_gn_args *a = &op->u.gn;
-		if (op->fused) return 0.0;
-		const double n = (double)a->n_img * a->HW * (a->C1 + a->C2);
-		return n * (4.0 + 2.0 + (a->raw16 ? 2.0 : 0.0));
-	}
-	case OP_LN: if (op->fused) return 0.0;
-		return (double)op->u.ln.rows * op->u.ln.d * (4.0 + (op->u.ln.y16 ? 2.0 : 0.0) + (op->u.ln.y32 ? 4.0 : 0.0));
-	case OP_SOFTMAX: return (double)op->u.smax.rows * op->u.smax.cols * 6.0;
-	case OP_ACT: return (double)op->u.act.n * 6.0;
-	case OP_COPY_F32: return 2.0 * op->u.copy.nbytes;
-	case OP_CTRL_ADD: return 12.0 * op->u.cadd.n_img * (double)op->u.cadd.rows * op->u.cadd.C;      /* base and ctrl read, dst written (gain 0: ctrl is not read) */
-	case OP_FREEU_BACKBONE: case OP_FREEU_SKIP: return 12.0 * op->u.freeu.n_img * (double)op->u.freeu.H * op->u.freeu.W * op->u.freeu.C;      /* src read by the reduction and by the apply, dst written (factor 1: one read) */
-	default: return 0;
-	}
+	return k_op_class[op->kind].bytes ? k_op_class[op->kind].bytes(op) : 0;
 }
 
 MLB_API int mlctx_profile_ops(MLCtx* C, float* ms_out, int n_out)
@@ -1832,7 +1704,7 @@ MLB_API int mlctx_profile_ops(MLCtx* C, float* ms_out, int n_out)
 			if (mlsd_stream_sync(C->stream)) return -1;
 			++seg;
 		}
-		if ((C->ops[i].kind == OP_LN || C->ops[i].kind == OP_GN || C->ops[i].kind == OP_GEMM) && C->ops[i].fused) {     /* runs inside its producer: no launch (an empty event pair would read ~4.8 us) */
+		if (k_op_class[C->ops[i].kind].fused_is_no_launch && C->ops[i].fused) {     /* runs inside its producer: no launch (an empty event pair would read ~4.8 us) */
 			if (i < n_out) ms_out[i] = 0;
 			continue;
 		}

@@ -13,6 +13,7 @@ int mlsd_set_error(int code, const char* fmt, ...);
 typedef enum {      /* (the numbering is what mlctx_op_record reports: append only) */
 	OP_GEMM, OP_ATTN, OP_GN, OP_LN, OP_NCHW2NHWC, OP_NHWC2NCHW, OP_TEMB, OP_ACT, OP_CLIP_EMBED, OP_SOFTMAX,
 	OP_COPY_F32, OP_XA_VT, OP_ATTN_CTX, OP_CTRL_ADD, OP_FREEU_BACKBONE, OP_FREEU_SKIP,
+	OP_KIND_COUNT       /* (not a kind: the length of k_op_class) */
 } MLOpKind;
 
 typedef struct MLOp {
@@ -41,6 +42,25 @@ typedef struct MLOp {
 		mlb_xavt_args xavt;
 	} u;
 } MLOp;
+
+/* Everything the executor knows about one kind of op: k_op_class[kind] (mlblock_ops.c) is the only place that says it.
+ * Fields are named by their offset in MLOp (offsetof(MLOp, u.<member>.<field>)); each holds one pointer. */
+#define MLOP_MAX_OUTPUTS 5      /* OP_GEMM: C32, C16, ln_y16, gn_y16, xa_out */
+#define MLOP_MAX_PARAMS  7      /* OP_GEMM: W_, bias, bias_m, ln_gamma, ln_beta, gn_gamma, gn_beta */
+typedef struct MLOpClass {
+	const char* name;           /* what mlctx_op_kind_info reports */
+	size_t args_bytes;          /* sizeof of the kind's member of MLOp.u */
+	int (*run)(const MLOp* op, void* stream);
+	struct { int n; size_t off[MLOP_MAX_OUTPUTS]; } out;      /* the buffers the launch writes (a NULL field is no output) ... */
+	int (*outputs)(const MLOp* op, const void* out[MLOP_MAX_OUTPUTS]);   /* ... or, where a field counts only under a condition, a function that lists them */
+	struct { int n; size_t off[MLOP_MAX_PARAMS]; } params;    /* the fields that may hold a parameter: weight streaming patches exactly these */
+	double (*bytes)(const MLOp* op);                          /* mlctx_op_bytes; NULL: 0 */
+	void (*shape)(const MLOp* op, char* buf, size_t n);       /* MLB_F_OPSHAPES: what mlctx_op_info puts after "<label> "; NULL: the plain label */
+	const char* (*unnamed)(const MLOp* op);                   /* the label of an op recorded without one; NULL: none */
+	int fused_is_no_launch;     /* MLOp.fused can mark an op of this kind as running inside its producer's launch (mlctx_profile_ops times no launch for it) */
+} MLOpClass;
+extern const MLOpClass k_op_class[OP_KIND_COUNT];
+int mlop_outputs(const MLOp* op, const void* out[MLOP_MAX_OUTPUTS]);      /* every buffer the op writes; returns how many */
 
 struct MLTensor {
 	int64_t ne[4];          /* logical (reference) shape */

@@ -58,12 +58,26 @@ class AmdControlConfig(ctypes.Structure):
 CONTROL_NET, CONTROL_FREEU = 1, 2       # MLIS_AMD_CONTROL_*: the bits of `control`
 
 
-# MLOpKind (include/mlblock_amd.h) and the ctypes record of each kind's arguments, for MLCtx.op_records
-OP_KINDS = ("gemm", "attn", "gn", "ln", "n2h", "h2n", "temb", "act", "cemb", "smax", "copy", "xavt", "attn_ctx", "cadd", "freeu_backbone", "freeu_skip")
 MLB_F_OPSHAPES, MLB_F_SYNTH_PARAMS, MLB_F_KEEP = 16, 32, 64
+
+_op_kinds = None
+
+
+def op_kinds():
+    """[(name, bytes of the argument structure)] of every op kind, in the library's numbering (mlctx_op_kind_info); read once"""
+    global _op_kinds
+    if _op_kinds is None:
+        f = L().mlctx_op_kind_info
+        f.argtypes = [c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t)]
+        kinds, name, nb = [], ctypes.c_char_p(), ctypes.c_size_t()
+        while f(len(kinds), ctypes.byref(name), ctypes.byref(nb)):
+            kinds.append((name.value.decode(), nb.value))
+        _op_kinds = kinds
+    return _op_kinds
 
 
 def _op_arg_types():
+    """the ctypes record of each kind's arguments, for MLCtx.op_records"""
     from . import kernels as K
     return {"gemm": K.GemmArgs, "attn": K.AttnArgs, "attn_ctx": K.AttnArgs, "gn": K.GnArgs, "ln": K.LnArgs, "n2h": K.N2hArgs, "h2n": K.H2nArgs,
             "temb": K.TembArgs, "act": K.ActArgs, "cemb": K.CembArgs, "smax": K.SmaxArgs, "copy": K.CopyArgs, "xavt": K.XavtArgs, "cadd": K.CaddArgs,
@@ -179,10 +193,10 @@ class MLCtx:
 
     def op_records(self):
         """mlctx_op_record of every op: [(kind name, label, fused, once, (gn_src0, gn_src1), a copy of the kind's argument structure)]"""
-        types, out, r = _op_arg_types(), [], OpRecord()
+        types, kinds, out, r = _op_arg_types(), op_kinds(), [], OpRecord()
         for i in range(self.info().n_ops):
             check1(L().mlctx_op_record(self.h, i, ctypes.byref(r)), "mlctx_op_record")
-            kind = OP_KINDS[r.kind]
+            kind = kinds[r.kind][0]
             T = types[kind]
             if r.args_bytes != ctypes.sizeof(T):
                 raise RuntimeError(f"op {i} ({kind}): the library's argument record has {r.args_bytes} bytes, its ctypes mirror {ctypes.sizeof(T)}")

@@ -2,7 +2,7 @@
 
 A prepared plan is a list of launches on raw device pointers, rewired by mlctx_prep (folded residuals and norms, producer statistics, hoisted
 step-invariant ops, column views of batched projections) over an arena that recycles blocks.  This module restates, from the RAW ARGUMENTS of
-every op (MLCtx.op_records, never the C side's op_outputs), which byte ranges the op reads and which it writes, and derives the dataflow:
+every op (MLCtx.op_records, never the C side's table of outputs, k_op_class), which byte ranges the op reads and which it writes, and derives the dataflow:
 
   extents(op)            -> (reads, writes): lists of Range (base, rows, row bytes, stride; column views have stride > row bytes)
   Plan.latest_writer     -> the last op before op i (in run order: `once` ops run before everything else, `fused` ops write nothing) whose

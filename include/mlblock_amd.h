@@ -153,6 +153,9 @@ int mlctx_param_info(const MLCtx* C, int i, const char** key, int* type, int64_t
 int mlctx_param_set(MLCtx* C, const char* key, int src_type, const void* host_data, int64_t n_elem);
 /* index of the parameter `key` for mlctx_param_info, or -1 */
 int mlctx_param_find(const MLCtx* C, const char* key);
+/* The phase weights of the plan's upsampling convolutions (mlb_upsample's phase form: derived from a conv weight's values at every load / LoRA update of it):
+ * entry i -> index of the source parameter, device pointer of the derived fp16 [4][cout][2][2][cin], cout, cin (padded).  Returns the number of entries. */
+int mlctx_ups_weights(const MLCtx* C, int i, int* param, const void** dev, int* cout, int* cin);
 /* LoRA update of one loaded parameter in place on the device: W += (up . down) scale, up [n1][r] and down [r][n0] host fp32 already rounded to the operand
  * precision of the host merge (mlts_lora_apply), whose arithmetic the kernel repeats operation for operation: the parameter ends up bit-identical to one
  * loaded from a merged store.  Resident parameters are patched on the context's stream, streamed ones through their host master copy.
@@ -203,7 +206,7 @@ int mlctx_op_kind_info(int kind, const char** name, size_t* args_bytes);
 int mlctx_op_kind_can_fuse(int kind);   /* 1 if MLOpRecord.fused can say of an op of this kind that it runs inside its producer's launch, 0 if the kind always launches */
 /* device storage of parameter i of mlctx_param_info: address (a virtual one in a weight-streaming plan: see mlctx_weight_slab), elements including padding, bytes per element */
 int mlctx_param_device(const MLCtx* C, int i, const void** dev, size_t* elems, int* elem_bytes);
-int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes);   /* device slab k of a weight-streaming plan; 0 when there is no slab k */
+int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes);   /* weight storage that is not a named parameter's own: device slab k of a weight-streaming plan, or, in a resident plan, the k-th block of phase weights derived from an upsampling convolution's parameter (mlctx_ups_weights); 0 when there is no block k */
 /* input i of the plan: its name, staging buffer (reference layout) and, where mlctx_input_bind gave one, the bound source and scale vector */
 typedef struct MLInputRecord { const char* name; const void* stage; size_t stage_bytes; const void* src; int n_src; const void* scale; } MLInputRecord;
 int mlctx_input_count(const MLCtx* C);

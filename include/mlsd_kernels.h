@@ -197,6 +197,16 @@ typedef struct mlsd_gemm_args {
 	const void* xa_vt;
 	void* xa_out; int64_t xa_ldo;
 	int xa_Tq, xa_Tk;
+	/* conv, PHASE FORM of an upsampling convolution (the ping-pong tiles only; every other kernel refuses them; 0 = off).  A 3x3 convolution over a nearest-2x
+	 * upsampled H x W source equals four 2x2 convolutions over the SOURCE, one per output parity (py, px), with the weights mlsd_ups_phase_weights derives:
+	 *   tap_oy / tap_ox  moves the tap window along its axis: tap (kh, kw) of output pixel (oh, ow) reads source pixel (oh stride - pad + tap_oy + kh, ow stride - pad
+	 *                    + tap_ox + kw), bounds-checked or wrapped like any tap.  A phase launch: KH = KW = 2, stride 1, pad 1, tap_oy = py, tap_ox = px, OH = H, OW = W.
+	 *   out_phase        1 + 2 py + px: row (n, y, x) of the launch is stored at pixel (2 y + py, 2 x + px) of a [n][2 OH][2 OW] image whose pixels are ldc32 floats apart
+	 *                    (C32 = that image; fp32 output, bias or none, nothing else in the epilogue).  Needs OW % 16 == 0: a 16-row block of the epilogue lies in one
+	 *                    image row.  The four launches write disjoint pixels and need no order among themselves.
+	 * (These three stand before colstats_shift and wrap, which tests/test_tiling_cpu.py pins as the record's last two fields.) */
+	int tap_oy, tap_ox;
+	int out_phase;
 	/* 1: colstats holds SHIFTED sums, sum (x - K) and sum (x - K)^2 with K = C32[first row of the block][n], which the consuming
 	 * GroupNorm reads back from C32 (mlsd_gn_args.cs_shifted).  0: the plain sums of x and x^2.  Plain fp32 sums of squares lose
 	 * ~2^-24 sqrt(rows) r^2 of a group's variance (r = |mean| / std: percents at r = 300), which no later double arithmetic recovers;
@@ -209,6 +219,20 @@ typedef struct mlsd_gemm_args {
 } mlsd_gemm_args;
 
 int mlsd_gemm(const mlsd_gemm_args* a, void* stream);
+/* The phase weights of an upsampling 3x3 convolution: src fp16 [cout][3][3][cin] (cin = the padded channel count of the weight's rows) ->
+ * dst fp16 [4][cout][2][2][cin], phase = 2 py + px, dst[phase][o][a][b][c] = fp16_rne( fp32 sum over kh in S(py, a), kw in S(px, b), ascending (kh, kw), of src[o][kh][kw][c] )
+ * with S(0, 0) = {0}, S(0, 1) = {1, 2}, S(1, 0) = {0, 1}, S(1, 1) = {2}: the taps of one axis that land on the same source pixel. */
+int mlsd_ups_phase_weights(const void* src, void* dst, int cout, int cin, void* stream);
+int mlsd_ups_phase_weights_host(const void* src, void* dst, int cout, int cin);      /* the same rule on host memory (the master copy of a weight-streaming plan) */
+/* The index maps of a convolution launch without the upsample in its gather, restated on the host (tests): the source pixel (n H + ih) W + iw that tap (kh, kw) of
+ * row m reads, -1 where it reads a zero; and the pixel of the output that row m is stored at (out_phase: of the [n][2 OH][2 OW] image).  -2: bad arguments. */
+long mlsd_conv_tap_source(const mlsd_gemm_args* a, int m, int kh, int kw);
+long mlsd_conv_out_pixel(const mlsd_gemm_args* a, int m);
+/* Phase form of the upsampling convolutions in the plans built from now on (mlb_upsample): -1 = where it wins (W % 16 == 0, enough rows), 0 = never,
+ * 2 = wherever the kernels take it (A/B and tests).  Default: MLSD_UPS_PHASES from the environment, else -1. */
+int mlsd_gemm_phase_form(const mlsd_gemm_args* a);      /* 1 if a launch with these phase fields runs, 0 if mlsd_gemm would refuse it */
+void mlsd_gemm_set_ups_phases(int mode);
+int mlsd_gemm_ups_phases(void);
 /* rows per statistics block (64 or 128) if this launch would write a->colstats, 0 if its kernel cannot */
 int mlsd_gemm_colstats_rows(const mlsd_gemm_args* a);
 /* != 0 if this launch (ln_* fields set) ends with the LayerNorm of its output (see mlsd_gemm_args.ln_y16): 1 = inside the launch, the tiles of a row block exchanging their

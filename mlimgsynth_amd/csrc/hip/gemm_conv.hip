@@ -913,6 +913,7 @@ GemmP gemm_params_from(const mlsd_gemm_args* a, const GemmRoute& r)
     p.ldrb = a->ldrb; p.resid = a->resid; p.ldr = a->ldr; p.act = a->act;
     p.C32 = a->C32; p.ldc32 = a->ldc32; p.C16 = (_Float16*)a->C16; p.ldc16 = a->ldc16;
     p.cs_shift = a->colstats_shift ? 1 : 0;
+    p.tap_oy = a->tap_oy; p.tap_ox = a->tap_ox; p.opix = a->out_phase;
     return p;
 }
 
@@ -1024,9 +1025,20 @@ int device_cus()
 // tile of the same shape (9 / 16)
 int g_gemm_korder = 0;     // experiment (EXPERIMENTS builds): slab-ordered K for the ping-pong convolutions, timing only -- see mlsd_gemm_set_korder
 int pp_epilogue_kind(const mlsd_gemm_args* a, int BN);
+// the phase form of an upsampling convolution (mlsd_gemm_args.tap_oy / tap_ox / out_phase): only the ping-pong convolution kernels read these fields
+bool phase_fields(const mlsd_gemm_args* a) { return a->tap_oy || a->tap_ox || a->out_phase; }
+bool phase_ok(const mlsd_gemm_args* a, int BN)
+{
+    if (!a->conv || a->upsample || a->stride != 1 || a->tap_oy < 0 || a->tap_oy > 1 || a->tap_ox < 0 || a->tap_ox > 1 || a->out_phase < 0 || a->out_phase > 4) return false;
+    if (!a->out_phase) return true;
+    // the pixel map: whole 16-row blocks inside one image row, the launch's own image extent, and the one epilogue built with it
+    return !(a->OW & 15) && a->OH > 0 && a->M == a->n_img * a->OH * a->OW && pp_epilogue_kind(a, BN) == PP_EPI_F32_PIX;
+}
 bool pp_eligible(const mlsd_gemm_args* a, int BM, int BN)
 {
-    if ((a->K & 63) || a->K < 192 || (a->M % (BM / 2)) || (a->N % (BN / 4))) return false;
+    if (phase_fields(a) && !phase_ok(a, BN)) return false;
+    // (a pixel-map launch is made of whole 16-row blocks, which its epilogue takes or skips one by one: M need not fill whole wave slabs)
+    if ((a->K & 63) || a->K < 192 || (a->out_phase ? (a->M & 15) : (a->M % (BM / 2))) || (a->N % (BN / 4))) return false;
     if (a->conv && ((a->Cin & 63) || a->KH * a->KW > 9)) return false;   // a K tile must lie inside one filter tap
     if (a->conv && a->upsample) {       // nearest-2x upsampled source (round 5): stride 1, and the two epilogues the upsampling convolutions of the UNets / decoders use
         const int e = pp_epilogue_kind(a, BN);
@@ -1034,7 +1046,7 @@ bool pp_eligible(const mlsd_gemm_args* a, int BM, int BN)
     }
     if (a->conv && a->wrap) {           // circular padding (built with the four fp32 epilogues; the row keeps (oh - pad, ow - pad) in 16-bit halves as the upsampling form does)
         const int e = pp_epilogue_kind(a, BN);
-        if (a->pad > 16 || a->H > 16000 || a->W > 16000 || (e != PP_EPI_F32 && e != PP_EPI_F32_STATS && e != PP_EPI_F32_RES && e != PP_EPI_F32_RES_STATS)) return false;
+        if (a->pad > 16 || a->H > 16000 || a->W > 16000 || (e != PP_EPI_F32 && e != PP_EPI_F32_STATS && e != PP_EPI_F32_RES && e != PP_EPI_F32_RES_STATS && e != PP_EPI_F32_PIX)) return false;
     }
     if (a->rowbias && ((a->rows_per_batch > 0 ? a->rows_per_batch : 1) % BM)) return false;
     if (a->act == MLSD_ACT_GEGLU && BN != 256) return false;
@@ -1082,6 +1094,8 @@ int pp_epilogue_kind(const mlsd_gemm_args* a, int BN)
 {
     if (a->xa_k && BN == 320 && xattn_eligible(a)) return PP_EPI_XATTN;
     if ((g_gemm_dbg & 2) || a->bias_m) return PP_EPI_GENERIC;
+    if (a->out_phase)       // the pixel map is built into ONE epilogue: fp32 out, bias or none (pp_eligible refuses the launch otherwise)
+        return (a->act == MLSD_ACT_NONE && a->C32 && !a->C16 && !a->resid && !a->rowbias && !a->colstats && !a->ln_y16 && !a->gn_y16 && !a->xa_k) ? PP_EPI_F32_PIX : PP_EPI_GENERIC;
     const bool c16_wide = a->C16 && !(a->ldc16 & 7) && !((uintptr_t)a->C16 & 15);     // the fp16 fast paths store 16 bytes per lane
     if (a->act == MLSD_ACT_NONE) {
         if (a->C16 && !a->C32 && !a->resid) return c16_wide ? PP_EPI_F16 : PP_EPI_GENERIC;
@@ -1110,7 +1124,7 @@ int sk_share(long ntiles, int nkt, int ncu)
 
 bool sk_eligible(const mlsd_gemm_args* a, int BM, int BN, bool ignore_stats = false)
 {
-    if (!pp_eligible(a, BM, BN) || !a->ws || !a->sk_flags || ((uintptr_t)a->ws & 15) || device_cus() < g_gemm_ncu || (a->conv && a->upsample)) return false;
+    if (!pp_eligible(a, BM, BN) || !a->ws || !a->sk_flags || ((uintptr_t)a->ws & 15) || device_cus() < g_gemm_ncu || (a->conv && a->upsample) || phase_fields(a)) return false;
     if (a->conv && a->colstats && !ignore_stats) return false;      // (the conv builds with the statistics epilogue do not fit the register budget beside the hand-off code)
     if (a->conv && a->wrap && !a->colstats && pp_epilogue_kind(a, BN) != PP_EPI_F32 && pp_epilogue_kind(a, BN) != PP_EPI_F32_RES) return false;     // (the wrap builds: F32, F32_RES)
     const long tiles = (long)((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN), nkt = a->K / 64;
@@ -1179,6 +1193,8 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
         default: return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, false, PP_EPI_GENERIC, true>);
         }
     }
+    if (epi == PP_EPI_F32_PIX)          // a phase of an upsampling convolution (pp_eligible: conv, no upsample in the gather), with or without the wrap
+        return r.wrap ? go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 5, PP_EPI_F32_PIX, false, NPH, SCH>) : go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, true, PP_EPI_F32_PIX, false, NPH, SCH>);
     if (r.wrap) {                       // circular padding (CONV | 4; pp_eligible admits these epilogues only)
         if (a->upsample) {
             if (epi == PP_EPI_F32_STATS) return go(gemm_pp_kernel<BM, BN, CB0, CB1, RESBATCH, 6, PP_EPI_F32_STATS, false, NPH, SCH>);
@@ -1235,7 +1251,7 @@ int launch_pp(const mlsd_gemm_args* a, const GemmRoute& r, hipStream_t st)
 // split-K workspace and splitk_reduce (declared above) adds them and applies the epilogue -- also for ONE slice
 bool skinny_eligible(const mlsd_gemm_args* a)
 {
-    if (a->M > 128 || a->act == MLSD_ACT_GEGLU || (a->K & 63) || a->K < 128 || (a->N & 3) || !a->ws || ((uintptr_t)a->ws & 15)) return false;
+    if (a->M > 128 || a->act == MLSD_ACT_GEGLU || (a->K & 63) || a->K < 128 || (a->N & 3) || !a->ws || ((uintptr_t)a->ws & 15) || phase_fields(a)) return false;
     if (a->conv && (a->upsample || (a->Cin & 63) || a->KH * a->KW > 9)) return false;
     if (a->conv && a->wrap && (a->pad > 16 || a->H > 16000 || a->W > 16000)) return false;     // (the wrap build keeps (oh - pad, ow - pad) in 16-bit halves)
     return wide_epilogue_ok(a);
@@ -1399,6 +1415,10 @@ GemmRoute resolve(const mlsd_gemm_args* a)
     r.pick = pick_variant(a);
     int v = r.pick;
     GemmFamily fam = FAM_GENERAL;
+    if (phase_fields(a)) {      // the phase form of an upsampling convolution: built into the plain ping-pong tiles only.  Whatever tile was asked for, one of those runs it
+        const bool is_pp = v == MLSD_TILE_PP_256x256 || v == MLSD_TILE_PP_128x320 || v == MLSD_TILE_PP2_256x256 || v == MLSD_TILE_PP2_128x320;      // (mlsd_gemm refuses the launch
+        if (!is_pp || !pp_eligible(a, kVariants[v].bm, kVariants[v].bn)) v = pp_eligible(a, 256, 256) ? MLSD_TILE_PP_256x256 : MLSD_TILE_PP_128x320;    //  if none of them takes it)
+    }
     switch (v) {
     case MLSD_TILE_W4_256x256: case MLSD_TILE_W4_128x320:       // one wave per SIMD (EXPERIMENTS builds); anything else: the ping-pong tile of the same shape
         if (mlsd_gemm_w4_eligible(a, v - MLSD_TILE_W4_256x256)) fam = FAM_W4; else v = v == MLSD_TILE_W4_256x256 ? MLSD_TILE_PP_256x256 : MLSD_TILE_PP_128x320;
@@ -1510,6 +1530,10 @@ MLSD_API int mlsd_gemm(const mlsd_gemm_args* a, void* stream)
     if (a->act == MLSD_ACT_GEGLU && (a->N & 63)) return mlsd_set_error(-1, "mlsd_gemm: GEGLU needs N %% 64 == 0");
     if (!a->C32 && !a->C16 && !a->xa_k) return mlsd_set_error(-1, "mlsd_gemm: no output");
     const GemmRoute r = resolve(a);
+    if (phase_fields(a) && r.fam != FAM_PP)
+        return mlsd_set_error(-1, "mlsd_gemm: tap_oy / tap_ox / out_phase = %d / %d / %d: only the ping-pong convolution tiles take the phase form of an upsampling convolution "
+                              "(conv, no upsample, stride 1, K %% 64 == 0 and >= 192, Cin %% 64 == 0, N in whole wave columns; out_phase: OW %% 16 == 0, fp32 output, bias only)",
+                              a->tap_oy, a->tap_ox, a->out_phase);
     if (a->colstats && a->colstats_rows > 0 && r.stats_rows != a->colstats_rows)
         return mlsd_set_error(-1, "mlsd_gemm: a GroupNorm was planned on this launch's column statistics (blocks of %d rows) but the launch "
                               "would write %d-row blocks / none: tile or epilogue settings changed after planning", a->colstats_rows, r.stats_rows);
@@ -1634,6 +1658,18 @@ MLSD_API int mlsd_gemm_ln_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info 
 MLSD_API int mlsd_gemm_gn_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.gn; }
 
 MLSD_API void mlsd_gemm_set_xattn(int mode) { g_xattn_mode = (mode >= 0 && mode <= 2) ? mode : -1; }
+
+/* 1 if a launch with these tap_oy / tap_ox / out_phase fields runs (on a ping-pong convolution tile, whatever tile it asks for); 0: mlsd_gemm would refuse it */
+MLSD_API int mlsd_gemm_phase_form(const mlsd_gemm_args* a) { return a && phase_fields(a) && resolve(a).fam == FAM_PP; }
+
+/* phase form of the upsampling convolutions (mlb_upsample asks at plan-build time): -1 auto, 0 off, 2 force; unset: MLSD_UPS_PHASES (in the style of MLSD_NO_HOIST), else auto */
+static int g_ups_phases = -2;
+MLSD_API void mlsd_gemm_set_ups_phases(int mode) { g_ups_phases = (mode == 0 || mode == 2) ? mode : -1; }
+MLSD_API int mlsd_gemm_ups_phases(void)
+{
+    if (g_ups_phases == -2) { const char* e = getenv("MLSD_UPS_PHASES"); g_ups_phases = (e && (*e == '0' || *e == '2') && !e[1]) ? *e - '0' : -1; }
+    return g_ups_phases;
+}
 
 /* 1 if this launch (xa_* fields set) ends with the cross attention of the q it projects: the plan builder then records no attention launch */
 MLSD_API int mlsd_gemm_xattn_fused(const mlsd_gemm_args* a) { mlsd_gemm_route_info r; return mlsd_gemm_route(a, &r) ? 0 : r.xattn; }

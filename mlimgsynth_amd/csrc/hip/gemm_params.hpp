@@ -62,12 +62,24 @@ struct GemmP {
     long xa_ldk, xa_ldo;
     int xa_Tq, xa_Tk;
     float xa_sc;
+    // phase form of an upsampling convolution (mlsd_gemm_args.tap_oy / tap_ox / out_phase; the ping-pong conv kernels): the tap window's origin per axis, and
+    // opix = 1 + 2 py + px: row (n, y, x) is stored at pixel (2 y + py, 2 x + px) of a [n][2 OH][2 OW] image (PP_EPI_F32_PIX).  0: none.
+    int tap_oy, tap_ox, opix;
 };
 
 static_assert(offsetof(GemmP, wrap) + sizeof(int) == offsetof(GemmP, rowbias), "GemmP::wrap must fill act_post's padding");
 
 // wrap (circular padding): a coordinate at most one extent outside [0, e) folded into it
-__device__ __forceinline__ int wrap_fold(int v, int e) { return v < 0 ? v + e : (v >= e ? v - e : v); }
+__host__ __device__ __forceinline__ int wrap_fold(int v, int e) { return v < 0 ? v + e : (v >= e ? v - e : v); }
+
+// phase form of an upsampling convolution (GemmP::opix = 1 + 2 py + px): the pixel of the [n][2 OH][2 OW] output that row m = (n, y, x) of the launch is stored at
+__host__ __device__ __forceinline__ long ups_out_pixel(int m, int OH, int OW, int opix)
+{
+    const int hw = OH * OW, ph = opix - 1;
+    const int img = m / hw, rem = m - img * hw;
+    const int y = rem / OW, x = rem - y * OW;
+    return (long)img * 4 * hw + (long)(2 * y + (ph >> 1)) * (2 * OW) + 2 * x + (ph & 1);
+}
 
 // LDS tile: rows of BK halfs (128 B at BK=64, 64 B at BK=32); the 16-byte chunk c of row r lives at slot
 // c ^ swz(r) so that a ds_read_b128 fragment read (32 lanes = 32 consecutive rows, one logical chunk)

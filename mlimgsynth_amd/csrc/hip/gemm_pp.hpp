@@ -105,7 +105,11 @@ __device__ __forceinline__ PPTile pp_tile_plain(const GemmP& p, int bid)
 // per-row bias, any output combination: decided per element at run time), 1 = fp16 out, 2 = fp32 out, 3 = fp32 out + fp32
 // residual, 4 = GEGLU fp16 out (256-wide tile); 1..4: no activation / per-row bias, straight-line code (see epi_fast).
 enum { PP_EPI_GENERIC = 0, PP_EPI_F16 = 1, PP_EPI_F32 = 2, PP_EPI_F32_RES = 3, PP_EPI_GEGLU16 = 4, PP_EPI_F32_STATS = 5, PP_EPI_F32_RES_STATS = 6,
-       PP_EPI_F32_LN = 7, PP_EPI_F32_RES_LN = 8, PP_EPI_XATTN = 9 };
+       PP_EPI_F32_LN = 7, PP_EPI_F32_RES_LN = 8, PP_EPI_XATTN = 9, PP_EPI_F32_PIX = 10 };
+// F32_PIX (CONV, fp32 output, bias or none): one PHASE of an upsampling convolution (mlsd_gemm_args.out_phase).  The launch is a 2x2 convolution over the source image
+// (GemmP::tap_oy / tap_ox place its window) and row (n, y, x) goes to pixel (2 y + py, 2 x + px) of the 2 OH x 2 OW output: OW % 16 == 0, so a 16-row block of the
+// epilogue lies in one image row and the map costs one base address per block (two scalar divisions), its 16 lanes l15 writing every second pixel from there.  Whole
+// 16-row blocks are in or out of the problem (M % 16 == 0), so M need not fill whole wave slabs here: blocks past M are skipped (their rows were staged clamped).
 // XATTN (round 6, 128 x 320 tile = 128 query rows x 5 heads of 64, one output tile per block): the launch is the q projection of a cross attention and ENDS with that
 // attention (mlsd_gemm_args.xa_*).  Nothing of q reaches HBM.  After the K loop (LDS map: K [77][656 B] at 0, q [128][656 B] at 50 KB; V^T [320][208 B] later over q):
 //   1. the tail stages of the ring are drained (they target the LDS this epilogue re-uses), the image's K rows of the tile's 320 columns go global -> LDS by LDS-DMA;
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
                 const int ohw = p.OH * p.OW;
                 const int img = m / ohw, rem = m - img * ohw;
                 const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
+                const int ih0 = oh * p.stride - p.pad + p.tap_oy, iw0 = ow * p.stride - p.pad + p.tap_ox;      // (tap_o*: the window origin of a phase launch, 0 otherwise)
                 const int He = UPS ? 2 * p.H : p.H, We = UPS ? 2 * p.W : p.W;
                 int mk = 0;
                 if constexpr (WRAP) {
@@ -451,8 +455,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
     // the conversion and the store.
     // Residual rows are fetched PF row blocks ahead of their use (all of them on the 128-row tile: 80 registers that the
     // main loop's fragments no longer need; two blocks = 32 registers on the 256-row tile).
-    auto epi_fast = [&](auto S32_, auto S16_, auto RES_, auto ST_, int wrow0, int wcol0) __attribute__((always_inline)) {
-        constexpr bool S32 = decltype(S32_)::value, S16 = decltype(S16_)::value, RES = decltype(RES_)::value, ST = decltype(ST_)::value;
+    auto epi_fast = [&](auto S32_, auto S16_, auto RES_, auto ST_, auto PIX_, int wrow0, int wcol0) __attribute__((always_inline)) {
+        constexpr bool S32 = decltype(S32_)::value, S16 = decltype(S16_)::value, RES = decltype(RES_)::value, ST = decltype(ST_)::value, PIX = decltype(PIX_)::value;
+        static_assert(!PIX || (S32 && !S16 && !RES && !ST), "the pixel map is built for the plain fp32 epilogue");
         constexpr int NR = 2 * RA;                               // 16-row blocks of the wave's slab: r = qa * RA + i
         constexpr int PF = !ST ? (BM == 128 ? NR : 2) : (BM == 128 ? NR : 1);  // (the statistics need 2 * NCB * 4 registers of their own)
         // ST: per column, sum and sum of squares over the wave's WM rows (a lane accumulates its 2*RA rows, the 16 lanes of a
@@ -477,12 +482,22 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
         };
 #pragma unroll
         for (int r = 0; r < PF && r < NR; ++r) fetch(r);
-        float* c32b = S32 ? p.C32 + (long)(wrow0 + l15) * p.ldc32 + wcol0 + 4 * lg : nullptr;
+        float* c32b = S32 && !PIX ? p.C32 + (long)(wrow0 + l15) * p.ldc32 + wcol0 + 4 * lg : nullptr;
         _Float16* c16b = S16 ? p.C16 + (long)(wrow0 + l15) * p.ldc16 + wcol0 + 4 * lg : nullptr;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             if (r + PF < NR) fetch(r + PF);
             const int qa = r / RA, i = r % RA;
+            if constexpr (PIX) {
+                // the block's first row (n, y, x0) -> pixel (2 y + py, 2 x0 + px) of image n; lane row l15 is 2 l15 pixels further along that image row
+                const int mb = wrow0 + row_of(r);
+                if (mb < p.M) {
+                    const long opx = ups_out_pixel(mb, p.OH, p.OW, p.opix) + 2 * l15;
+                    float* orow = p.C32 + opx * p.ldc32 + wcol0 + 4 * lg;
+#pragma unroll
+                    for (int c = 0; c < NCB; ++c) *reinterpret_cast<f32x4*>(orow + c * 16) = acc[qa][i][c] + cb[c];
+                }
+            } else
             if constexpr (S16 && !S32 && !RES && !ST) {
                 // fp16 only: the row's 16 columns of a block sit in 4 lanes (lg) as 8-byte pieces.  The tail is store-ISSUE bound
                 // (~34 clocks per wave store, gemm_trace; tools/store_ab.py measured 8192x3840x1280 84.2 -> 75.9 us), so pairs of column blocks exchange halves between lane groups 0<->1 and
@@ -963,11 +978,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p)
         using std::integral_constant;
         using T = std::true_type;
         using F = std::false_type;
-        if constexpr (EPI == PP_EPI_F16) { epi_fast(F{}, T{}, F{}, F{}, wrow0, wcol0); return; }
-        if constexpr (EPI == PP_EPI_F32) { epi_fast(T{}, F{}, F{}, F{}, wrow0, wcol0); return; }
-        if constexpr (EPI == PP_EPI_F32_RES) { epi_fast(T{}, F{}, T{}, F{}, wrow0, wcol0); return; }
-        if constexpr (EPI == PP_EPI_F32_STATS) { epi_fast(T{}, F{}, F{}, T{}, wrow0, wcol0); return; }
-        if constexpr (EPI == PP_EPI_F32_RES_STATS) { epi_fast(T{}, F{}, T{}, T{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F16) { epi_fast(F{}, T{}, F{}, F{}, F{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F32) { epi_fast(T{}, F{}, F{}, F{}, F{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F32_RES) { epi_fast(T{}, F{}, T{}, F{}, F{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F32_STATS) { epi_fast(T{}, F{}, F{}, T{}, F{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F32_RES_STATS) { epi_fast(T{}, F{}, T{}, T{}, F{}, wrow0, wcol0); return; }
+        if constexpr (EPI == PP_EPI_F32_PIX) { epi_fast(T{}, F{}, F{}, F{}, T{}, wrow0, wcol0); return; }
         if constexpr (EPI == PP_EPI_GEGLU16) { epi_fast_geglu(wrow0, wcol0); return; }
         if constexpr (EPI == PP_EPI_F32_LN) { epi_ln(F{}, wrow0, wcol0); return; }
         if constexpr (EPI == PP_EPI_F32_RES_LN) { epi_ln(T{}, wrow0, wcol0); return; }

@@ -82,7 +82,7 @@ static void ctx_reset_(MLCtx* C)
 	C->n_chunks = 0; C->cur = NULL; C->cur_left = 0; C->n_free = 0; C->n_zeroed = 0;
 	C->mem_compute = C->mem_params = C->mem_live = C->mem_peak_live = 0;
 	C->err = 0; C->prepared = 0; C->tuned = 0; C->n_tune_miss = 0; C->n_tune_near = 0; C->static_valid = 0; C->n_once = 0;
-	C->n_ln_fused = 0; C->n_ln_alias = 0; C->n_gn_fused = 0;
+	C->n_ln_fused = 0; C->n_ln_alias = 0; C->n_gn_fused = 0; C->n_ups = 0;
 	memset(&C->kvb, 0, sizeof(C->kvb));
 	memset(&C->epb, 0, sizeof(C->epb));
 	memset(&C->info, 0, sizeof(C->info));
@@ -93,7 +93,7 @@ MLB_API void mlctx_destroy(MLCtx* C)
 	if (!C) return;
 	mlsd_stream_sync(C->stream);
 	ctx_reset(C);
-	free(C->ops); free(C->tensors); free(C->inputs); free(C->names); free(C->params); free(C->chunks); free(C->freel); free(C->zeroed);
+	free(C->ops); free(C->tensors); free(C->inputs); free(C->names); free(C->params); free(C->chunks); free(C->freel); free(C->zeroed); free(C->ups);
 	free(C);
 }
 
@@ -299,9 +299,10 @@ float* mlt_need32(MLCtx* C, MLTensor* t)
 	const int64_t rows = (int64_t)t->n * t->h * t->w;
 	if (t->prod >= 0) {
 		MLOp *op = &C->ops[t->prod];
+		const int nph = op->phases > 0 ? op->phases : 1;      /* the phase launches of an upsampling convolution write the tensor together: the first of them is its first writer */
 		t->sz32 = (size_t)rows * t->c * sizeof(float);
-		t->d32 = (float*)dalloc_ex(C, t->sz32, 0, t->prod); t->ld32 = t->c;
-		op->u.gemm.C32 = t->d32; op->u.gemm.ldc32 = t->c;
+		t->d32 = (float*)dalloc_ex(C, t->sz32, 0, t->prod - (nph - 1)); t->ld32 = t->c;
+		for (int k=0;k<nph;++k) { op[-k].u.gemm.C32 = t->d32; op[-k].u.gemm.ldc32 = t->c; }
 		return t->d32;
 	}
 	mlctx_fail(C, "tensor %s has no fp32 form", t->name);
@@ -314,6 +315,10 @@ void* mlt_need16(MLCtx* C, MLTensor* t)
 	if (t->d16) return t->d16;
 	if (t->released) { mlctx_fail(C, "use of released tensor %s", t->name); return NULL; }
 	const int64_t rows = (int64_t)t->n * t->h * t->w;
+	if (t->prod >= 0 && C->ops[t->prod].phases > 0) {
+		/* the phase launches of an upsampling convolution store fp32 only (the pixel map is built into that one epilogue): the fp16 form is a conversion of the finished map, below */
+		if (!mlt_need32(C, t)) return NULL;
+	} else
 	if (t->prod >= 0) {
 		MLOp *op = &C->ops[t->prod];
 		if (t->c % 8) {
@@ -1484,11 +1489,11 @@ MLB_API int mlctx_prep(MLCtx* C)
 		MLOp *op = &C->ops[i];
 		if (op->kind == OP_GEMM) {
 			if (!op->u.gemm.C32 && !op->u.gemm.C16 && !op->u.gemm.xa_k) return mlctx_fail(C, "op %d (%s): output never consumed", i, op->label);
-			if (op->u.gemm.conv) nconv++;
+			if (op->u.gemm.conv && (!op->u.gemm.out_phase || op->phases)) nconv++;      /* (the phase launches of an upsampling convolution are ONE convolution of the model) */
 			/* tile selection: a pure function of the shape (table), unless the offline timing mode is on */
 			if (!autotune_on()) { int r = select_gemm(C, op); if (r < 0) return -1; if (r != 1) { C->n_tune_miss++; g_tune_miss++; } }     /* (2: a neighbour's tile; 0: the static rule) */
 		}
-		fl += op->flops;
+		fl += op->flops + op->flops_saved;      /* the model's count (MLOp.flops_saved) */
 	}
 	if (C->flags & MLB_F_DUMP) {            /* src/mlblock.c:111-116 */
 		char path[96]; snprintf(path, sizeof(path), "dump-graph-%s.txt", C->name[0] ? C->name : "ctx");
@@ -1619,6 +1624,11 @@ MLB_API int mlctx_param_device(const MLCtx* C, int i, const void** dev, size_t* 
 
 MLB_API int mlctx_weight_slab(const MLCtx* C, int k, const void** dev, size_t* nbytes)
 {
+	if (C && !C->pstream && k >= 0 && k < C->n_ups) {      /* a resident plan: the phase weights derived from its upsampling convolutions' parameters (a streamed plan's pass through its slabs) */
+		if (dev) *dev = C->ups[k].dev;
+		if (nbytes) *nbytes = (size_t)16 * C->ups[k].cout * C->ups[k].cin * 2;
+		return 1;
+	}
 	if (!C || !C->pstream || k < 0 || k >= C->n_slab || !C->slab[k]) return 0;
 	if (dev) *dev = C->slab[k];
 	if (nbytes) *nbytes = C->slab_bytes;
@@ -1827,7 +1837,54 @@ MLB_API int mlctx_param_set(MLCtx* C, const char* key, int src_type, const void*
 	if (rc) return -1;
 	p->loaded = 1;
 	C->static_valid = 0;      /* a step-invariant op (the cross attentions' K / V projection) may read this weight */
+	if (mlctx_ups_derive(C, (int)(p - C->params)) < 0) return -1;
 	return 1;
+}
+
+/* Phase weights of the upsampling convolutions (mlb_upsample): the only values in a plan DERIVED from a weight's values, so every path on which a weight becomes
+ * resident or changes ends here -- mlctx_param_set, mlctx_params_synth, mlctx_param_lora.  Formed once per weight load on the context's stream (a device kernel;
+ * the dry runtime computes the same rule on the host), never per evaluation. */
+void* mlctx_ups_weights_new(MLCtx* C, int param, int cout, int cin)
+{
+	void *dev = mlctx_walloc(C, (size_t)16 * cout * cin * 2);      /* (a streamed plan: a virtual range like any weight's; its master copy is what mlctx_ups_derive fills) */
+	if (!dev) return NULL;
+	struct MLUpsW *u = VEC_PUSH(C, C->ups, C->n_ups, C->cap_ups, struct MLUpsW);
+	u->param = param; u->dev = dev; u->cout = cout; u->cin = cin;
+	return dev;
+}
+
+int mlctx_ups_derive(MLCtx* C, int param)
+{
+	int n = 0;
+	for (int i=0;i<C->n_ups;++i) {
+		const struct MLUpsW *u = &C->ups[i];
+		if (param >= 0 && u->param != param) continue;
+		if (is_virtual(C, u->dev)) {
+			/* streamed weights: source and result live in the pinned host master; the same rule on the host, once per weight load.  Whatever wrote the source's master on
+			 * the plan's stream has to be done, and segments uploaded ahead hold the old bytes */
+			if (mlsd_stream_sync(C->stream) || (C->copy_stream && mlsd_stream_sync(C->copy_stream))) return -1;
+			C->pf_valid = 0;
+			const size_t vo = (size_t)((const char*)u->dev - MLW_VBASE);
+			const MLWAlloc *a = &C->pv_allocs[pv_find(C, vo)];
+			if (mlsd_ups_phase_weights_host(param_master(C, &C->params[u->param]), C->pmaster + a->moff + (vo - a->voff), u->cout, u->cin)) return -1;
+		} else
+		if (mlsd_ups_phase_weights(C->params[u->param].dev, u->dev, u->cout, u->cin, C->stream)) return -1;
+		++n;
+	}
+	return n;
+}
+
+/* the phase weights as the plan holds them (tests): entry i -> source parameter index, device pointer, cout, cin; returns the number of entries */
+MLB_API int mlctx_ups_weights(const MLCtx* C, int i, int* param, const void** dev, int* cout, int* cin)
+{
+	if (!C) return 0;
+	if (i >= 0 && i < C->n_ups) {
+		if (param) *param = C->ups[i].param;
+		if (dev) *dev = C->ups[i].dev;
+		if (cout) *cout = C->ups[i].cout;
+		if (cin) *cin = C->ups[i].cin;
+	}
+	return C->n_ups;
 }
 
 MLB_API int mlctx_param_find(const MLCtx* C, const char* key)
@@ -1887,6 +1944,7 @@ MLB_API int mlctx_param_lora(MLCtx* C, const char* key, const float* up, const f
 	C->static_valid = 0;
 	if (bad) return mlsd_set_error(-1, "NaN in LoRA result");
 	if (pm && (mlsd_memcpy(pm, W, pbytes, 1, C->stream) || mlsd_stream_sync(C->stream))) return -1;
+	if (mlctx_ups_derive(C, ip) < 0) return -1;       /* the phase weights of an upsampling convolution follow their source weight */
 	return 1;
 }
 
@@ -1939,6 +1997,7 @@ MLB_API int mlctx_params_synth(MLCtx* C, uint64_t seed)
 		if (pm && mlsd_memcpy(pm, dst, pbytes, 1, C->stream)) return -1;
 		p->loaded = 1;
 	}
+	if (mlctx_ups_derive(C, -1) < 0) return -1;
 	if (mlsd_stream_sync(C->stream)) return -1;
 	C->info.t_load = now_s() - t0;
 	return 1;

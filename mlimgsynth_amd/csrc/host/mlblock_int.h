@@ -23,6 +23,11 @@ typedef struct MLOp {
 	int gn_src[2];          /* OP_GN: index of the op that PRODUCES each fp32 source (MLTensor.prod), -1 = not a GEMM/conv output */
 	int fused;              /* OP_LN: the producer's launch ends with this LayerNorm (wire_ln_fold): the op itself does nothing; OP_GEMM: the Linear runs as the second GEMM of its producer's launch */
 	int folded_from;        /* OP_GEMM: the tile a producer had before wire_ln_fold moved it to the 128 x 160 kernel for its LayerNorm: mlctx_handoffs_off returns it there (-1: the static rule; 0: not moved) */
+	double flops_saved;     /* FLOPs of the model's graph that this op's form does not execute (the phase form of an upsampling convolution: 5/9 of the 3x3 form's, booked on its
+	                         * last launch).  `flops` is what the launch executes (per-launch rates, mlctx_op_info); MLCtxInfo.flops stays the MODEL's count = sum of flops + flops_saved,
+	                         * the figure BASELINE and the benchmark's job rates are stated in */
+	int phases;             /* OP_GEMM: > 0 on the LAST of `phases` consecutive launches that together write one tensor (the phase form of an upsampling convolution,
+	                         * mlb_upsample): an output bound late (mlt_need32) is bound to all of them */
 	int once;               /* step-invariant: depends only on inputs marked static_src (the text conditioning); mlctx_compute
 	                         * re-runs it only after such an input was written (mlctx_input_set / mlctx_input_device_ptr) */
 	union {
@@ -148,6 +153,9 @@ struct MLCtx {
 	void* pscratch; size_t pscratch_bytes;  /* device scratch for the synthetic fill and the LoRA update of a streamed weight */
 	void* lora_buf; size_t lora_buf_bytes;  /* device staging of a LoRA update's flag and operands (mlctx_param_lora) */
 	size_t stream_bytes_per_eval; int stream_copies_per_eval;
+	/* phase weights of the upsampling convolutions (mlb_upsample's phase form; in a weight-streaming plan `dev` is a virtual range and the derivation runs on the host master): derived from parameter `param` ([cout][3][3][cin]) into `dev`
+	 * ([4][cout][2][2][cin]) whenever that parameter's values change -- mlctx_param_set, mlctx_params_synth, mlctx_param_lora (mlctx_ups_derive) */
+	struct MLUpsW { int param; void* dev; int cout, cin; } *ups; int n_ups, cap_ups;
 	MLCtxInfo info;
 };
 
@@ -159,6 +167,8 @@ struct MLCtx {
 typedef struct MLWAlloc { size_t voff, bytes, moff; } MLWAlloc;     /* moff: offset in the host master (segment order, wstream_setup) */
 typedef struct MLWSeg { int op0, op1; int n; struct { size_t voff, bytes, soff, moff; } *r; size_t bytes; } MLWSeg;
 void* mlctx_walloc(MLCtx* C, size_t nbytes);      /* weight storage: device memory, or a virtual address when the plan streams its weights */
+void* mlctx_ups_weights_new(MLCtx* C, int param, int cout, int cin);      /* storage for the phase weights derived from conv weight `param` (device memory, or a virtual range in a weight-streaming plan), registered for mlctx_ups_derive */
+int   mlctx_ups_derive(MLCtx* C, int param);      /* (re)derive the phase weights that depend on parameter `param` (< 0: all of them) on the context's stream */
 
 /* internal helpers shared by mlblock_nn.c and the model builders */
 MLTensor* mlt_new(MLCtx* C, int n, int h, int w, int c);

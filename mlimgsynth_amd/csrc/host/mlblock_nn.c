@@ -195,9 +195,65 @@ MLB_API MLTensor* mlb_downsample(MLCtx* C, MLTensor* x, int ch_out, bool vae)
 	return MLN("conv", mlb_conv2d_ex(C, x, ch_out, 3, 2, 1, 0, T, NULL));
 }
 
+/* The upsampling convolution as FOUR 2x2 convolutions over the source image, one per output parity (hip/ups_phase.hip has the identity): 4/9 of the multiply-adds of
+ * the form that folds the upsample into the gather.  Same parameters under the same names (the 3x3 weight stays the loaded one: a LoRA patches it); the launches read
+ * phase weights derived from it at every load (mlctx_ups_weights_new) and write disjoint pixels of one fp32 tensor, in no particular order among themselves.  They emit
+ * no column statistics: a consuming GroupNorm runs its own first pass (gn_producer finds no single producer of the map). */
+static MLTensor* conv_ups_phases(MLCtx* C, MLTensor* x, int ch_out, const mlsd_gemm_args* proto)
+{
+	mlctx_block_begin(C);       /* (the scope mlb_conv2d_ex2 opens for its parameters) */
+	const void *xd = mlt_need16(C, x);
+	if (!xd) return NULL;
+	if (x->ld16 != x->c) { mlctx_fail(C, "upsample: padded input rows in the phase form"); return NULL; }
+	const int ch_in = x->c, cpad = proto->Cin;
+	MLParam *w = mlctx_param_new(C, "weight", MLT_F16, 3, 3, ch_in, ch_out, 1, 0, 0);
+	const int wi = (int)(w - C->params);
+	MLParam *b = mlctx_param_new(C, "bias", MLT_F32, ch_out, 1, 1, 1, 0, 0, 0);
+	const float *bd = (const float*)b->dev;
+	const char *wd = (const char*)mlctx_ups_weights_new(C, wi, ch_out, cpad);
+	if (!wd) return NULL;
+	MLTensor *y = mlt_new(C, x->n, 2*x->h, 2*x->w, ch_out);
+	for (int ph=0; ph<4; ++ph) {
+		MLOp *op = mlctx_op_new(C, OP_GEMM, "");
+		mlsd_gemm_args *g = &op->u.gemm;
+		*g = *proto;
+		g->A = xd; g->W_ = wd + (size_t)ph * ch_out * 4 * cpad * 2; g->bias = bd;
+		g->tap_oy = ph >> 1; g->tap_ox = ph & 1; g->out_phase = 1 + ph;
+		op->flops = 2.0 * g->M * (double)ch_out * 4 * ch_in;      /* what is executed: 4 taps per phase */
+		if (ph == 3) { op->phases = 4; op->flops_saved = 2.0 * 4 * g->M * (double)ch_out * 5 * ch_in; }      /* 9 - 4 taps of each of the 4 M output pixels */
+	}
+	y->prod = C->n_ops - 1;
+	return y;
+}
+
 MLB_API MLTensor* mlb_upsample(MLCtx* C, MLTensor* x, int ch_out)
 {
 	mlctx_block_begin(C);
+	/* The phase form where it is eligible (resident and weight-streaming plans alike: a streamed plan must give the resident plan's bits, and streams the derived
+	 * weights instead of the loaded 3x3 ones, which then stay in its host master only): a form the ping-pong kernels take
+	 * (W % 16 == 0, Cin % 64 == 0, whole wave columns), and -- unless forced, mlsd_gemm_set_ups_phases(2) -- enough rows that four launches win: each phase launch must
+	 * bring at least one full round of 256 tiles of 128 x 320 (SDXL batch 4: 8192 x 1280 and up; profiles/NOTES.md has the in-plan A/B).  Below that the four launches
+	 * each leave CUs idle where the single launch fills them, and today's form stays. */
+	/* A plan built in the dry runtime (no device: the host-side audits of tests/plan_audit.py) keeps today's form as well: that audit states what a GEMM writes as
+	 * M rows at one stride and cannot express the pixel map; the form's buffer binding is held on the device instead (tests/test_upsample_phases_gpu.py). */
+	const int mode = mlsd_gemm_ups_phases();
+	if (x && !C->err && mode != 0 && !C->dry && x->h > 1 && !(x->c % 8)) {
+		mlsd_gemm_args g; memset(&g, 0, sizeof g);
+		g.lda = x->c; g.conv = 1; g.n_img = x->n; g.H = x->h; g.W = x->w; g.Cin = x->c; g.OH = x->h; g.OW = x->w;
+		g.KH = 2; g.KW = 2; g.stride = 1; g.pad = 1; g.wrap = C->conv_wrap;
+		g.ldb = 4 * (int64_t)x->c; g.M = x->n * x->h * x->w; g.N = ch_out; g.K = 4 * x->c;
+		g.rows_per_batch = x->h * x->w; g.ldrb = ch_out;
+		/* (the route reads pointers for null and alignment only: placeholders until the operands exist) */
+		static _Alignas(256) float ph[64];
+		g.A = ph; g.W_ = ph; g.bias = ph; g.C32 = ph; g.ldc32 = ch_out; g.tap_oy = 1; g.tap_ox = 1; g.out_phase = 4;
+		/* (whole tile columns of one of the two tiles: a 64- or 128-channel output would idle most of a 256-wide tile, and today's form runs those on narrower ones) */
+		const long tiles = (ch_out % 320 && ch_out % 256) ? 0 : (long)(g.M / 128) * ((ch_out + 319) / 320);
+		/* (seamless-tiling plans, mlctx_set_conv_wrap: the kernels take the wrap, and the forced mode uses it, but the rule leaves those plans on today's form) */
+		if (mlsd_gemm_phase_form(&g) && (mode == 2 || (tiles >= 256 && !C->conv_wrap))) {
+			g.A = g.W_ = NULL; g.bias = NULL; g.C32 = NULL; g.ldc32 = 0;
+			return MLN("conv", conv_ups_phases(C, x, ch_out, &g));
+		}
+	}
 	/* ggml_upscale(x,2,NEAREST) is folded into the conv's gather */
 	return MLN("conv", mlb_conv2d_ex(C, x, ch_out, 3, 1, 1, 1, T, NULL));
 }

@@ -38,6 +38,7 @@ class GemmArgs(ctypes.Structure):
                 ("gn_y16", vp), ("gn_ldy", ctypes.c_int64), ("gn_gamma", vp), ("gn_beta", vp), ("gn_eps", ctypes.c_float), ("gn_groups", c_int), ("gn_hw", c_int),
                 ("gn_silu", c_int),
                 ("xa_k", vp), ("xa_ldk", c_i64), ("xa_vt", vp), ("xa_out", vp), ("xa_ldo", c_i64), ("xa_Tq", c_int), ("xa_Tk", c_int),
+                ("tap_oy", c_int), ("tap_ox", c_int), ("out_phase", c_int),
                 ("colstats_shift", c_int), ("wrap", c_int)]
 
 

@@ -69,8 +69,8 @@ typedef enum {
 	/* ControlNet: the UNet is conditioned on a control image (pose, depth, edges, tile: the finished map, no preprocessor here) through a copy of its encoder */
 	MLIS_OPT_AMD_CONTROL_MODEL = 131,      /* "control_model" (string): a safetensors ControlNet in the original (cldm.py) layout for the base model, or "synth[:seed]" with a
 	                                        * "synth:" model; "" = off.  Engines with and without it coexist in the two resident slots */
-	MLIS_OPT_AMD_CONTROL_IMAGE = 132,      /* "control_image" (const MLIS_Image*, 3 channels; NULL clears; mlis_option_get gives an int: 1 if one is set): any size, resampled on the GPU (bilinear) to each pass's pixel size; it
-	                                        * stays set across generations, like the model */
+	MLIS_OPT_AMD_CONTROL_IMAGE = 132,      /* "control_image" (const MLIS_Image*, 3 channels; NULL clears; mlis_option_get gives an int: 1 if one is set): any size, resampled on the GPU to each pass's pixel size
+	                                        * (bilinear; with the downscale_filter where that is set and an axis shrinks); it stays set across generations, like the model */
 	MLIS_OPT_AMD_CONTROL_STRENGTH = 133,   /* "control_strength" (float, default 1): 0 .. 2, the gain on the ControlNet's residuals */
 	MLIS_OPT_AMD_CONTROL_START = 134,      /* "control_start" (float, default 0) and */
 	MLIS_OPT_AMD_CONTROL_END = 135,        /* "control_end" (float, default 1): the share of the steps that is controlled, 0 <= start <= end <= 1 (checked by mlis_generate) */
@@ -86,10 +86,16 @@ typedef enum {
 	/* ESRGAN upscaler (RRDBNet x4): a learned pixel-space upscaler for mlis_amd_tensor_upscale and, with hires_use_model, for the hires fix */
 	MLIS_OPT_AMD_UPSCALE_MODEL = 151,      /* "upscale_model" (string): a safetensors RRDBNet in BasicSR's naming, or "synth[:seed[:blocks]]"; empty clears it and frees the
 	                                        * resident upscaler.  The upscaler is built on first use and stays resident, keyed by this string */
-	MLIS_OPT_AMD_HIRES_USE_MODEL = 152     /* "hires_use_model" (int 0 / 1, default 0): the hires fix decodes its first pass, upscales the IMAGE 4x with upscale_model, resamples it
-	                                        * to the target size in the hires_upscaler mode (a plain resample, not antialiased) and runs the second pass as img2img from it */
+	MLIS_OPT_AMD_HIRES_USE_MODEL = 152,    /* "hires_use_model" (int 0 / 1, default 0): the hires fix decodes its first pass, upscales the IMAGE 4x with upscale_model, resamples it
+	                                        * to the target size (in the hires_upscaler mode, a plain resample; with the downscale_filter where that is set) and runs the second
+	                                        * pass as img2img from it */
+	/* antialiased downscaling: the filter of the resamples that shrink an image -- the hires fix's model path to its target size and the control image to a pass's size --,
+	 * its support grows with the shrink factor (mlis_amd_tensor_resample_aa).  A resample where neither axis shrinks runs as with "none"; the latent upscale of the plain
+	 * hires fix stays on hires_upscaler.  Persists across generations.  (A block of its own from 161.) */
+	MLIS_OPT_AMD_DOWNSCALE_FILTER = 161    /* "downscale_filter": none|box|bilinear|bicubic|lanczos or 0..4 (int; 0 = none, else MLIS_AMD_AA_* + 1), default none = the plain resamples */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
+enum { MLIS_AMD_AA_BOX = 0, MLIS_AMD_AA_TRIANGLE = 1, MLIS_AMD_AA_CUBIC = 2, MLIS_AMD_AA_LANCZOS = 3 };
 
 typedef struct MLIS_Ctx MLIS_Ctx;                                                                            /* :352 */
 typedef struct MLIS_Image { uint8_t* d; size_t sz; unsigned w, h, c; int flags; } MLIS_Image;                /* :356-363 */
@@ -167,6 +173,11 @@ int mlis_amd_lora_stats(MLIS_Ctx* ctx, int* n_restored, int* n_patched, int* n_c
  * Tap indices outside a plane are clamped to the border, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed.
  * Returns 1, MLIS_E_OPT_VALUE for a bad mode or size. */
 int mlis_amd_tensor_resample(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int mode);
+/* dst = src resampled to w x h on the GPU with a filter whose support grows with the shrink factor (MLIS_AMD_AA_*: box, triangle = antialiased bilinear, Keys cubic
+ * with a = -0.5, lanczos3; what PIL's resize and torch's interpolate(antialias=True) compute); when enlarging, the filters interpolate.  Edges: taps outside a plane
+ * are dropped and the rest renormalised, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed; otherwise the contract of
+ * mlis_amd_tensor_resample.  Returns 1, MLIS_E_OPT_VALUE for a bad filter or size. */
+int mlis_amd_tensor_resample_aa(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int filter);
 /* dst = src upscaled 4x by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 -> dst [4w][4h][3][n] (not clamped).  src == dst is allowed.
  * The upscaler is built on the first use and stays resident in the context until the option changes (mlis_amd_upscaler_builds counts the builds); the image border is
  * padded with zeros whatever "tiling" says.  Returns 1, MLIS_E_OPT_VALUE when no upscale_model is set or src is not a 3-channel image. */

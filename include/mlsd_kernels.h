@@ -442,6 +442,31 @@ int mlsd_copy_slice2(float* dst, int dw, int dh, const float* src, int sw, int s
 enum { MLSD_RESAMPLE_NEAREST = 0, MLSD_RESAMPLE_BILINEAR = 1, MLSD_RESAMPLE_BICUBIC = 2 };
 enum { MLSD_RESAMPLE_MAX_EXTENT = 1 << 22 };
 int mlsd_resample2d(const float* src, int sw, int sh, float* dst, int dw, int dh, int planes, int mode, int wrap, void* stream);
+/* Antialiased resampling of the same planes (hip/resample_aa.hip; not in the reference): a filter whose support grows with the shrink factor, as PIL's resize
+ * and torch's interpolate(antialias=True).  Per axis, with scale = s_in / s_out and fs = max(scale, 1), output index d has the centre c = scale (d + 0.5) and the
+ * taps j in [lo, hi), lo = floor(c - sup fs + 0.5), hi = floor(c + sup fs + 0.5): the exact integer floor divisions of s_in (2 d + 1) + s_out -+ (2 sup) max(s_in, s_out)
+ * by 2 s_out.  Without wrap lo and hi are clipped to [0, s_in]; with wrap they are not, the tap index is taken modulo s_in (a window may go around a small plane
+ * several times).  The weight of tap j is f((j - c + 0.5) / fs), computed and normalised to sum 1 in double, rounded once to fp32.
+ *   MLSD_AA_BOX       sup 0.5  f = 1 on -0.5 < x <= 0.5 (integer factors: the average of the block)
+ *   MLSD_AA_TRIANGLE  sup 1    1 - |x|                              (torch: bilinear, antialias=True)
+ *   MLSD_AA_CUBIC     sup 2    Keys cubic, a = -0.5 (not the -0.75 of MLSD_RESAMPLE_BICUBIC)      (torch: bicubic, antialias=True)
+ *   MLSD_AA_LANCZOS3  sup 3    sinc(x) sinc(x / 3)                  (PIL: LANCZOS)
+ * mlsd_resample_aa_taps fills start[s_out], count[s_out] and w[s_out][k_max] (the row's tail beyond its count is zero) for one axis and returns the largest count,
+ * or -1 for a bad argument or a k_max below it; mlsd_resample_aa_max_taps returns the largest count of the unclipped windows, an upper bound for either wrap.  Host
+ * code, no GPU needed.
+ * mlsd_resample2d_aa: two passes, rows first ([planes][sh][dw] in the workspace), then columns; an axis whose extents are equal is skipped, equal sizes on both copy
+ * the planes bit for bit.  Every sum is fp32 in ascending tap order, products and additions rounded one by one: the result is a function of the tables alone.
+ * wrap as mlsd_resample2d.  ws: mlsd_resample2d_aa_ws_bytes of device memory (the tables, built on the host per call and uploaded on the stream, which is waited for
+ * once, and the intermediate): not for captured plans.  Returns -1 before any launch for non-positive extents, extents above MLSD_RESAMPLE_MAX_EXTENT, 2^31 elements or
+ * more in src, dst or the intermediate, a bad filter or wrap, a NULL workspace, or src, dst and ws overlapping. */
+enum { MLSD_AA_BOX = 0, MLSD_AA_TRIANGLE = 1, MLSD_AA_CUBIC = 2, MLSD_AA_LANCZOS3 = 3 };
+int mlsd_resample_aa_taps(int s_in, int s_out, int filter, int wrap_axis, int* start, int* count, float* w, int k_max);
+int mlsd_resample_aa_max_taps(int s_in, int s_out, int filter);
+size_t mlsd_resample2d_aa_ws_bytes(int sw, int sh, int dw, int dh, int planes, int filter);
+int mlsd_resample2d_aa(const float* src, int sw, int sh, float* dst, int dw, int dh, int planes, int filter, int wrap, void* ws, void* stream);
+/* for measurements (tools/resample_aa_measure.py): the LDS bytes a block of the horizontal pass may use, 0 .. 32 KiB (the default); a launch whose tile needs more reads
+ * global memory directly, so 0 runs every shape that way.  The results do not depend on it.  A negative value only asks; returns the previous limit. */
+int mlsd_resample2d_aa_lds_limit(int bytes);
 /* Tiled diffusion (MultiDiffusion; not in the reference): the canvas latent is evaluated in overlapping windows of the UNet plan's size, the windows'
  * outputs are blended by a weighted average.  Window pixel (v, u) of a ww x wh window that starts at (x0, y0) lies on canvas pixel
  * ((y0 + v) mod H, (x0 + u) mod W): a window may straddle the seam of a wrapped axis; on an axis that does not wrap the caller keeps x0 + ww <= W.

@@ -8,6 +8,7 @@
  * without a CLIP vocabulary file).
  */
 #include <ctype.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -320,6 +321,8 @@ static const char k_usage[] =
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
 "Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic   --hires-use-model y|n\n"
 "Upscaler:    --upscale-model PATH|synth[:SEED[:BLOCKS]]   (ESRGAN RRDBNet x4, safetensors);  upscale -i IN -o OUT --upscale-model PATH needs no -m\n"
+"             --outscale F   (upscale: 0 < F <= 4, the x4 output filtered down to F times the input; lanczos unless --downscale-filter names another)\n"
+"Downscaling: --downscale-filter none|box|bilinear|bicubic|lanczos   (antialiased: hires fix with a model, control image, --outscale)\n"
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
@@ -331,6 +334,7 @@ static const char k_usage[] =
 
 typedef struct {
 	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens, *ctl_img;
+	double outscale;        /* upscale --outscale: 0 = not given */
 	MLIS_Ctx *ctx;
 } Cli;
 
@@ -351,6 +355,11 @@ static int cli_option(Cli* C, const char* name, const char* next)
 		{"input",&C->in_img},{"imask",&C->in_mask},{"ilatent",&C->in_lat},{"ilmask",&C->in_lmask},{"output",&C->out_img},
 		{"olatent",&C->out_lat},{"tokens",&C->tokens},{"ntokens",&C->ntokens},{"control-image",&C->ctl_img} };
 	for (size_t i=0;i<sizeof(paths)/sizeof(*paths);++i) if (!strcmp(name, paths[i].n)) { *paths[i].dst = next; return 1; }
+	if (!strcmp(name, "outscale")) {
+		char *e = NULL; const double f = strtod(next, &e);
+		if (e == next || *e || !(f > 0 && f <= 4)) FAIL("option '--outscale %s': a factor in (0, 4] is needed", next);
+		C->outscale = f; return 1;
+	}
 	if (mlis_option_set_str(C->ctx, name, next) < 0) FAIL("option '--%s %s': %s", name, next, mlis_errstr_get(C->ctx));
 	return 1;
 }
@@ -506,7 +515,14 @@ static int cmd_upscale(Cli* C)
 	free(rgb); free(im.d);
 	int r = mlis_amd_tensor_upscale(C->ctx, &t, &t);
 	if (r < 0) fprintf(stderr, "error: upscale: %s\n", mlis_errstr_get(C->ctx));
-	else {
+	else if (C->outscale > 0 && C->outscale != 4) {      /* the x4 output filtered down to round(F w) x round(F h) */
+		int filter = 0;
+		mlis_option_get(C->ctx, MLIS_OPT_AMD_DOWNSCALE_FILTER, &filter);
+		const int w = (int)floor(C->outscale * (t.n[0] / 4) + 0.5), h = (int)floor(C->outscale * (t.n[1] / 4) + 0.5);
+		r = mlis_amd_tensor_resample_aa(C->ctx, &t, &t, w > 1 ? w : 1, h > 1 ? h : 1, filter ? filter - 1 : MLIS_AMD_AA_LANCZOS);
+		if (r < 0) fprintf(stderr, "error: outscale: %s\n", mlis_errstr_get(C->ctx));
+	}
+	if (r >= 0) {
 		unsigned char *px = img_from_tensor(&t);
 		r = img_write(C->out_img ? C->out_img : "output.png", px, (unsigned)t.n[0], (unsigned)t.n[1], 3, NULL);
 		free(px);

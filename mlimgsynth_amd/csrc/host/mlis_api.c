@@ -51,6 +51,7 @@ struct MLIS_Ctx {
 	int control_evals[2], control_pass;     /* controlled evaluations of the last generation's passes (mlis_amd_control_evals) */
 	char *path_upscale; MLIS_AmdUpscaler *upscaler;       /* MLIS_OPT_AMD_UPSCALE_MODEL and the resident upscaler built from it (dropped whenever the option changes) */
 	int n_upscaler_builds, hires_use_model;                                     /* mlis_amd_upscaler_builds; MLIS_OPT_AMD_HIRES_USE_MODEL */
+	int downscale_filter;   /* MLIS_OPT_AMD_DOWNSCALE_FILTER: 0 none, else MLIS_AMD_AA_* + 1: the filter of the resamples that shrink (hires model path, control image) */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
@@ -150,8 +151,11 @@ static const char* const k_option_amd3[] = { "unet_tile_batch" };               
 static const char* const k_option_amd4[] = { "control_model", "control_image", "control_strength", "control_start", "control_end" };   /* ids from MLIS_OPT_AMD_CONTROL_MODEL */
 static const char* const k_option_amd5[] = { "freeu", "freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2" };   /* ids from MLIS_OPT_AMD_FREEU */
 static const char* const k_option_amd6[] = { "upscale_model", "hires_use_model" };                       /* ids from MLIS_OPT_AMD_UPSCALE_MODEL */
+static const char* const k_option_amd7[] = { "downscale_filter" };                                       /* ids from MLIS_OPT_AMD_DOWNSCALE_FILTER */
+static const char* const k_downscale[] = { "none", "box", "bilinear", "bicubic", "lanczos" };            /* 0, MLIS_AMD_AA_* + 1 */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_DOWNSCALE_FILTER && x < MLIS_OPT_AMD_DOWNSCALE_FILTER + COUNTOF(k_option_amd7)) return k_option_amd7[x - MLIS_OPT_AMD_DOWNSCALE_FILTER];
 	if (x >= MLIS_OPT_AMD_UPSCALE_MODEL && x < MLIS_OPT_AMD_UPSCALE_MODEL + COUNTOF(k_option_amd6)) return k_option_amd6[x - MLIS_OPT_AMD_UPSCALE_MODEL];
 	if (x >= MLIS_OPT_AMD_FREEU && x < MLIS_OPT_AMD_FREEU + COUNTOF(k_option_amd5)) return k_option_amd5[x - MLIS_OPT_AMD_FREEU];
 	if (x >= MLIS_OPT_AMD_CONTROL_MODEL && x < MLIS_OPT_AMD_CONTROL_MODEL + COUNTOF(k_option_amd4)) return k_option_amd4[x - MLIS_OPT_AMD_CONTROL_MODEL];
@@ -174,6 +178,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i5 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_FREEU + i5);
 	const int i6 = from_list(k_option_amd6, COUNTOF(k_option_amd6), 1, s, strlen(s));
 	if (i6 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UPSCALE_MODEL + i6);
+	const int i7 = from_list(k_option_amd7, COUNTOF(k_option_amd7), 1, s, strlen(s));
+	if (i7 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_DOWNSCALE_FILTER + i7);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -613,6 +619,20 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		str_set(&S->path_upscale, s);
 		break;
 	case MLIS_OPT_AMD_HIRES_USE_MODEL: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->hires_use_model = i; break;
+	case MLIS_OPT_AMD_DOWNSCALE_FILTER:    /* none|box|bilinear|bicubic|lanczos or 0..4 */
+		if (A->is_str) {
+			next_str_arg(A);
+			i = from_list(k_downscale, COUNTOF(k_downscale), 1, A->arg_b, A->arg_n);
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i >= COUNTOF(k_downscale)) BAD_VALUE;
+		/* an engine that holds the control image resampled with the old filter takes it again at its next pass (control_apply), as after a new image */
+		if (i != S->downscale_filter && tensor_good(&S->control_image)) S->control_image_gen++;
+		S->downscale_filter = i;
+		break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -687,6 +707,7 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_FREEU: { int *p = va_arg(ap, int*); if (p) *p = S->freeu; } break;
 	case MLIS_OPT_AMD_UPSCALE_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_upscale ? S->path_upscale : ""; } break;
 	case MLIS_OPT_AMD_HIRES_USE_MODEL: { int *p = va_arg(ap, int*); if (p) *p = S->hires_use_model; } break;
+	case MLIS_OPT_AMD_DOWNSCALE_FILTER: { int *p = va_arg(ap, int*); if (p) *p = S->downscale_filter; } break;
 	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
 		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
@@ -1031,27 +1052,33 @@ static int control_weights(MLIS_Ctx* S)
 	return 1;
 }
 
-/* the control image at the pass's pixel size into the engine (resampled on the GPU, bilinear, as mlis_amd_tensor_resample does), strength and window */
+/* the control image at the pass's pixel size into the engine (resampled on the GPU: bilinear, as mlis_amd_tensor_resample does, or with the downscale_filter
+ * where that is set and an axis shrinks, as mlis_amd_tensor_resample_aa does), strength and window */
 static int control_apply(MLIS_Ctx* S, int w_img, int h_img)
 {
 	if (str_empty(S->path_control)) return 1;
-	/* the engine has one pixel size: it still holds this very image, resampled and through the hint plan, unless the option was set again since (or the tiling changed
-	 * the resampler's edges: another engine) */
+	/* the engine has one pixel size: it still holds this very image, resampled and through the hint plan, unless the option was set again since, the downscale_filter
+	 * changed (either counts control_image_gen on) or the tiling changed the resampler's edges (another engine) */
 	if (mlis_amd_control_tag(S->eng) == S->control_image_gen)
 		return mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
 	const MLIS_Tensor *src = &S->control_image;
 	const int sw = src->n[0], sh = src->n[1];
 	const size_t n_src = (size_t)3 * sw * sh, n_dst = (size_t)3 * w_img * h_img;
-	void *d_src = NULL, *d_dst = NULL;
+	const int aa = S->downscale_filter && (w_img < sw || h_img < sh);
+	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL;
 	int r = 1;
 	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
-			|| mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, MLIS_AMD_RESAMPLE_BILINEAR, S->tiling, NULL) || mlsd_device_sync()
+			|| (aa ? (mlsd_malloc(&d_ws, mlsd_resample2d_aa_ws_bytes(sw, sh, w_img, h_img, 3, S->downscale_filter - 1))
+					|| mlsd_resample2d_aa((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, S->downscale_filter - 1, S->tiling, d_ws, NULL))
+				: mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, MLIS_AMD_RESAMPLE_BILINEAR, S->tiling, NULL))
+			|| mlsd_device_sync()
 			|| mlis_amd_set_control_image_device(S->eng, d_dst) < 0
 			|| mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0)
 		r = api_error_lib(S, MLIS_E_UNKNOWN);
 	if (r > 0) mlis_amd_control_tag_set(S->eng, S->control_image_gen);
 	if (d_src) mlsd_free(d_src);
 	if (d_dst) mlsd_free(d_dst);
+	if (d_ws) mlsd_free(d_ws);
 	return r;
 }
 
@@ -1387,6 +1414,38 @@ MLB_API int mlis_amd_tensor_resample(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_T
 	return tensor_resample(S, src, dst, w, h, mode);
 }
 
+/* the same through mlsd_resample2d_aa (filter: MLIS_AMD_AA_*) */
+static int tensor_resample_aa(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int filter)
+{
+	if (filter < MLIS_AMD_AA_BOX || filter > MLIS_AMD_AA_LANCZOS) return api_error(S, MLIS_E_OPT_VALUE, "invalid resampling filter %d", filter);
+	if (!src || !dst || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || src->n[2] < 1 || src->n[3] < 1)
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor to resample");
+	const int sw = src->n[0], sh = src->n[1], c = src->n[2], b = src->n[3];
+	const size_t n_src = mlis_tensor_count(src), n_dst = (size_t)c * b * (w > 0 ? w : 0) * (h > 0 ? h : 0), n_mid = (size_t)c * b * sh * (w > 0 ? w : 0);
+	if (w < 1 || h < 1 || w > 65535 || h > 65535 || n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31) || n_mid >= ((size_t)1 << 31))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid size to resample to: %dx%d", w, h);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL;
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_malloc(&d_ws, mlsd_resample2d_aa_ws_bytes(sw, sh, w, h, c * b, filter))
+			|| mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+			|| mlsd_resample2d_aa((const float*)d_src, sw, sh, (float*)d_dst, w, h, c * b, filter, S->tiling, d_ws, NULL))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, w, h, c, b);
+		if (mlsd_memcpy(dst->d, d_dst, n_dst * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	if (d_ws) mlsd_free(d_ws);
+	return r;
+}
+
+MLB_API int mlis_amd_tensor_resample_aa(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int filter)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_resample_aa(S, src, dst, w, h, filter);
+}
+
 /* ------------------------------------------------------------------ model upscaling (ESRGAN, host/upscaler.c) */
 /* the context's upscaler for the upscale_model option as it stands: built on first use, resident until the option changes */
 static int upscaler_get(MLIS_Ctx* S)
@@ -1481,6 +1540,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 		ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", (int)(e - b), b, S->control_strength, S->control_start, S->control_end);
 	}
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
+	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1593,10 +1653,12 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 		const int steps1 = S->last_n_step, lw = S->latent.n[0], lh = S->latent.n[1];
 		const int tw = (int)floor((double)lw * S->hires_scale + 0.5), th = (int)floor((double)lh * S->hires_scale + 0.5);      /* the target latent size, either way */
 		if (use_model) {
-			/* the decoded first pass upscaled 4x by the model, brought to the target pixel size by a plain resample; the second pass encodes it (generate_pass, MLIS_TUF_IMAGE):
-			 * what a caller gets from generate + mlis_amd_tensor_upscale + mlis_amd_tensor_resample + generate with an input image */
+			/* the decoded first pass upscaled 4x by the model, brought to the target pixel size by a plain resample -- or, with a downscale_filter and an axis that
+			 * shrinks, by that filter --; the second pass encodes it (generate_pass, MLIS_TUF_IMAGE): what a caller gets from generate + mlis_amd_tensor_upscale +
+			 * mlis_amd_tensor_resample (or _resample_aa) + generate with an input image */
 			r = tensor_upscale(S, &S->image, &S->image);
-			if (r >= 0) r = tensor_resample(S, &S->image, &S->image, tw * 8, th * 8, S->hires_upscaler);
+			if (r >= 0 && S->downscale_filter && (tw * 8 < S->image.n[0] || th * 8 < S->image.n[1])) r = tensor_resample_aa(S, &S->image, &S->image, tw * 8, th * 8, S->downscale_filter - 1);
+			else if (r >= 0) r = tensor_resample(S, &S->image, &S->image, tw * 8, th * 8, S->hires_upscaler);
 		} else r = tensor_resample(S, &S->latent, &S->latent, tw, th, S->hires_upscaler);
 		if (r >= 0) {
 			S->tuflags = (tuflags & MLIS_TUF_CONDITIONING) | (use_model ? MLIS_TUF_IMAGE : MLIS_TUF_LATENT);

@@ -184,6 +184,41 @@ def resample2d(src, sw, sh, dst, dw, dh, planes, mode, wrap=0, stream=None):
     check(lib().mlsd_resample2d(vp(src), sw, sh, vp(dst), dw, dh, planes, mode, wrap, vp(stream)), "mlsd_resample2d")
 
 
+AA_BOX, AA_TRIANGLE, AA_CUBIC, AA_LANCZOS3 = range(4)
+
+
+def resample_aa_max_taps(s_in, s_out, filter):
+    """mlsd_resample_aa_max_taps: the largest tap count of one axis (of the unclipped windows: an upper bound with or without wrap); -1 if refused."""
+    return int(lib().mlsd_resample_aa_max_taps(int(s_in), int(s_out), int(filter)))
+
+
+def resample_aa_taps(s_in, s_out, filter, wrap_axis=0):
+    """mlsd_resample_aa_taps: (start int32 [s_out], count int32 [s_out], w float32 [s_out][K]) of one axis, K the largest count; None if refused.  Host code."""
+    import numpy as np
+    k = resample_aa_max_taps(s_in, s_out, filter)
+    if k < 1:
+        return None
+    start, count, w = np.zeros(s_out, np.int32), np.zeros(s_out, np.int32), np.zeros((s_out, k), np.float32)
+    ip, fp = ctypes.POINTER(c_int), ctypes.POINTER(c_f)
+    f = lib().mlsd_resample_aa_taps
+    f.restype, f.argtypes = c_int, [c_int, c_int, c_int, c_int, ip, ip, fp, c_int]
+    used = f(int(s_in), int(s_out), int(filter), int(wrap_axis), start.ctypes.data_as(ip), count.ctypes.data_as(ip), w.ctypes.data_as(fp), k)
+    return None if used < 0 else (start, count, np.ascontiguousarray(w[:, :used]))
+
+
+def resample2d_aa_ws_bytes(sw, sh, dw, dh, planes, filter):
+    """mlsd_resample2d_aa_ws_bytes: device workspace of one resample2d_aa call (tables + the intermediate); 0 for arguments it refuses."""
+    f = lib().mlsd_resample2d_aa_ws_bytes
+    f.restype = ctypes.c_size_t
+    return int(f(int(sw), int(sh), int(dw), int(dh), int(planes), int(filter)))
+
+
+def resample2d_aa(src, sw, sh, dst, dw, dh, planes, filter, wrap=0, ws=None, stream=None):
+    """mlsd_resample2d_aa: fp32 planes [planes][sh][sw] -> [planes][dh][dw] through a filter that widens with the shrink factor (AA_*; device pointers; ws:
+    resample2d_aa_ws_bytes of device memory); wrap bit 0 columns, bit 1 rows."""
+    check(lib().mlsd_resample2d_aa(vp(src), sw, sh, vp(dst), dw, dh, planes, filter, wrap, vp(ws), vp(stream)), "mlsd_resample2d_aa")
+
+
 WINDOW_MAX_AXIS = 64
 
 

@@ -13,6 +13,7 @@ The library is found like the reference does (environment MLIS_LIB_PATH first), 
 mlimgsynth_amd/lib/libmlimgsynth_amd.so.  It is loaded on first use, not at import, and there is no CPU fallback.
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -46,8 +47,9 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121, AMD_CONTROL_MODEL=131, AMD_CONTROL_IMAGE=132,
                                                                            AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135, AMD_FREEU=141,
                                                                            AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145,
-                                                                           AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152))
+                                                                           AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
+_define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
 MLIS_CTEF_NO_NORM = 1
 
 
@@ -78,6 +80,7 @@ _PROTOTYPES = {
     "mlis_mask_encode": (_I, [_V, _TP, _TP, _I]), "mlis_text_tokenize": (_I, [_V, _S, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), _I]),
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
+    "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
@@ -182,7 +185,7 @@ class MLImgSynth:
 
     def option_get(self, option, out):
         """out: a ctypes object receiving the value (c_char_p for MODEL / PROMPT / NPROMPT, c_int for MODEL_TYPE: the four options
-        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER / AMD_UNET_TILE / AMD_UNET_TILE_OVERLAP / AMD_UNET_TILE_BATCH, c_float for
+        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER / AMD_UNET_TILE / AMD_UNET_TILE_OVERLAP / AMD_UNET_TILE_BATCH / AMD_DOWNSCALE_FILTER, c_float for
         AMD_HIRES_SCALE / AMD_HIRES_DENOISE)."""
         r = self._lib.mlis_option_get(self._ctx, option, ctypes.byref(out))
         if r < 0:
@@ -339,13 +342,32 @@ class MLImgSynth:
             raise RuntimeError("Failed to resample the tensor: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
 
-    def upscale(self, image):
+    def tensor_resample_aa(self, tensor, w, h, filter=MLIS_AMD_AA_LANCZOS):   # noqa: F821
+        """Resample every plane of a tensor to w x h on the GPU through a filter whose support grows with the shrink factor (MLIS_AMD_AA_*: what PIL's resize and
+        torch's interpolate(antialias=True) compute); edges wrap along the axes of the tiling option."""
+        tin = tensor._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_resample_aa(self._ctx, ctypes.byref(tin), tout, w, h, filter) < 0:
+            raise RuntimeError("Failed to resample the tensor: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
+
+    def upscale(self, image, outscale=None):
         """Upscale an image tensor [n,3,h,w] in [0,1] 4x with the ESRGAN model of the "upscale_model" option (a safetensors RRDBNet or
-        "synth[:seed[:blocks]]"); the result is not clamped.  The upscaler is built on first use and stays resident."""
+        "synth[:seed[:blocks]]"); the result is not clamped.  The upscaler is built on first use and stays resident.
+        outscale F in (0, 4]: the x4 output is brought to round(F w) x round(F h) with the "downscale_filter" option's filter, lanczos where that is none
+        (Real-ESRGAN's --outscale); None or 4 is the x4 output itself."""
+        if outscale is not None and not 0 < outscale <= 4:
+            raise ValueError("outscale must be in (0, 4]")
         tin = image._c()
         tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
         if self._lib.mlis_amd_tensor_upscale(self._ctx, ctypes.byref(tin), tout) < 0:
             raise RuntimeError("Failed to upscale the image: %s" % self.errstr_get())
+        if outscale is not None and outscale != 4:
+            f = _I()
+            self.option_get(MLIS_OPT_AMD_DOWNSCALE_FILTER, f)                          # noqa: F821
+            w, h = int(math.floor(outscale * image.n[0] + 0.5)), int(math.floor(outscale * image.n[1] + 0.5))
+            if self._lib.mlis_amd_tensor_resample_aa(self._ctx, tout, tout, max(w, 1), max(h, 1), f.value - 1 if f.value else MLIS_AMD_AA_LANCZOS) < 0:   # noqa: F821
+                raise RuntimeError("Failed to resample the upscaled image: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
 
     def engine_builds(self):

@@ -435,6 +435,8 @@ int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* evals_con
 void mlis_amd_control_tag_set(MLIS_AmdCtx* S, uint64_t tag);
 uint64_t mlis_amd_control_tag(const MLIS_AmdCtx* S);
 const void* mlis_amd_control_image_device(MLIS_AmdCtx* S);   /* the control image the hint plan read: device NCHW fp32 [3][height][width], NULL without one */
+/* the same copied to the host: host_dst (may be NULL) gets [3][height][width] floats, *w and *h (may be NULL) the size.  Returns 1, 0 when no image is held, -1 on a copy error */
+int mlis_amd_control_image_get(const MLIS_AmdCtx* S, float* host_dst, int* w, int* h);
 /* FreeU (engines created with MLIS_AMD_CONTROL_FREEU in MLIS_AmdConfig.control).  set_freeu: the backbone factors b1, b2 and the skip factors s1, s2 of stage 1
  * (backbone of n_ch x the top multiplier channels) and stage 2 (half of that), each in [0, 4], else an error; they are four floats of device memory, so they change
  * between generations, and under use_hipgraph, without touching a plan.  All four start at 1: until they are set the engine computes what one without the flag does.

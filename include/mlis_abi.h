@@ -66,7 +66,7 @@ typedef enum {
 	/* packed windows: up to this many windows of a tiled pass run as one batched UNet evaluation (the effective count: mlis_amd_tile_pack).  Persists across
 	 * generations; costs the activation memory of a plan for that many windows x the batch.  (A block of its own from 121.) */
 	MLIS_OPT_AMD_UNET_TILE_BATCH = 121,    /* "unet_tile_batch" (int): 1 .. 16, default 1 = one window per evaluation */
-	/* ControlNet: the UNet is conditioned on a control image (pose, depth, edges, tile: the finished map, no preprocessor here) through a copy of its encoder */
+	/* ControlNet: the UNet is conditioned on a control image (pose, depth, edges, tile: the finished map, or a picture for the control_preprocess of 171) through a copy of its encoder */
 	MLIS_OPT_AMD_CONTROL_MODEL = 131,      /* "control_model" (string): a safetensors ControlNet in the original (cldm.py) layout for the base model, or "synth[:seed]" with a
 	                                        * "synth:" model; "" = off.  Engines with and without it coexist in the two resident slots */
 	MLIS_OPT_AMD_CONTROL_IMAGE = 132,      /* "control_image" (const MLIS_Image*, 3 channels; NULL clears; mlis_option_get gives an int: 1 if one is set): any size, resampled on the GPU to each pass's pixel size
@@ -92,10 +92,19 @@ typedef enum {
 	/* antialiased downscaling: the filter of the resamples that shrink an image -- the hires fix's model path to its target size and the control image to a pass's size --,
 	 * its support grows with the shrink factor (mlis_amd_tensor_resample_aa).  A resample where neither axis shrinks runs as with "none"; the latent upscale of the plain
 	 * hires fix stays on hires_upscaler.  Persists across generations.  (A block of its own from 161.) */
-	MLIS_OPT_AMD_DOWNSCALE_FILTER = 161    /* "downscale_filter": none|box|bilinear|bicubic|lanczos or 0..4 (int; 0 = none, else MLIS_AMD_AA_* + 1), default none = the plain resamples */
+	MLIS_OPT_AMD_DOWNSCALE_FILTER = 161,   /* "downscale_filter": none|box|bilinear|bicubic|lanczos or 0..4 (int; 0 = none, else MLIS_AMD_AA_* + 1), default none = the plain resamples */
+	/* control image preprocessor: run on the GPU AFTER the control image was resampled to a pass's pixel size ("pixel perfect"), so the hires second pass and tiled
+	 * canvases get one-pixel edges at their own resolution.  canny: mlis_amd_tensor_canny with the three options below and the context's "tiling" as wrap; invert:
+	 * 1 - x (a black-on-white drawing for a scribble or line-art ControlNet).  A change of any of the four while a control image is set makes the engines take the
+	 * image again at their next pass; nothing is rebuilt.  They persist across generations.  (A block of its own from 171.) */
+	MLIS_OPT_AMD_CONTROL_PREPROCESS = 171, /* "control_preprocess": none|canny|invert or 0..2 (int; MLIS_AMD_PREPROCESS_*), default none = the control image is the finished map */
+	MLIS_OPT_AMD_CANNY_LOW = 172,          /* "canny_low" (float 0 .. 32767, default 100) and */
+	MLIS_OPT_AMD_CANNY_HIGH = 173,         /* "canny_high" (float 0 .. 32767, default 200): the hysteresis thresholds on the gradient magnitude of the 8-bit image; swapped if low > high */
+	MLIS_OPT_AMD_CANNY_L2 = 174            /* "canny_l2" (int 0 / 1, default 0): the magnitude is sqrt(dx^2 + dy^2) (compared squared) instead of |dx| + |dy| */
 } MLIS_Option;
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 enum { MLIS_AMD_AA_BOX = 0, MLIS_AMD_AA_TRIANGLE = 1, MLIS_AMD_AA_CUBIC = 2, MLIS_AMD_AA_LANCZOS = 3 };
+enum { MLIS_AMD_PREPROCESS_NONE = 0, MLIS_AMD_PREPROCESS_CANNY = 1, MLIS_AMD_PREPROCESS_INVERT = 2 };
 
 typedef struct MLIS_Ctx MLIS_Ctx;                                                                            /* :352 */
 typedef struct MLIS_Image { uint8_t* d; size_t sz; unsigned w, h, c; int flags; } MLIS_Image;                /* :356-363 */
@@ -178,6 +187,11 @@ int mlis_amd_tensor_resample(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor*
  * are dropped and the rest renormalised, or wrap around along the axes of the context's "tiling" option.  src == dst is allowed; otherwise the contract of
  * mlis_amd_tensor_resample.  Returns 1, MLIS_E_OPT_VALUE for a bad filter or size. */
 int mlis_amd_tensor_resample_aa(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int w, int h, int filter);
+/* dst = the Canny edge map of src on the GPU: src [w][h][1 or 3][1] floats in 0..1 -> dst [w][h][3][1], 1 on edges and 0 elsewhere, the three channels equal
+ * (the rules: mlsd_canny in mlsd_kernels.h -- OpenCV's Canny(img_u8, low, high) with aperture 3 as recalled, parity-unpinned against OpenCV).  low, high: 0 .. 32767,
+ * swapped if low > high; l2: 0 / 1; wrap: bit 0 columns, bit 1 rows wrap around (what "tiling" x / y / xy mean), 0 .. 3.  src == dst is allowed.  Needs no model.
+ * Returns 1, MLIS_E_OPT_VALUE for bad arguments. */
+int mlis_amd_tensor_canny(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, float low, float high, int l2, int wrap);
 /* dst = src upscaled 4x by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 -> dst [4w][4h][3][n] (not clamped).  src == dst is allowed.
  * The upscaler is built on the first use and stays resident in the context until the option changes (mlis_amd_upscaler_builds counts the builds); the image border is
  * padded with zeros whatever "tiling" says.  Returns 1, MLIS_E_OPT_VALUE when no upscale_model is set or src is not a 3-channel image. */

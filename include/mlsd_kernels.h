@@ -467,6 +467,35 @@ int mlsd_resample2d_aa(const float* src, int sw, int sh, float* dst, int dw, int
 /* for measurements (tools/resample_aa_measure.py): the LDS bytes a block of the horizontal pass may use, 0 .. 32 KiB (the default); a launch whose tile needs more reads
  * global memory directly, so 0 runs every shape that way.  The results do not depend on it.  A negative value only asks; returns the previous limit. */
 int mlsd_resample2d_aa_lds_limit(int bytes);
+/* Canny edge detection of NCHW fp32 planes (hip/canny.hip; not in the reference): the preprocessor of a ControlNet's control image.  The specification is
+ * OpenCV's Canny with aperture 3 as recalled, written out here; OpenCV was not at hand: parity-unpinned against OpenCV, pinned to these rules.  Everything
+ * behind (a) is integer arithmetic, so the result is held bit for bit (tests/canny_ref.py restates it twice).
+ *  (a) q = min(255, max(0, (int)floorf(v * 255.0f + 0.5f))) per plane (product and sum rounded one by one; resamples overshoot, hence the clamp).
+ *  (b) thresholds (mlsd_canny_thresholds, host only): the two are swapped if low > high; L1: lo = floor(low), hi = floor(high); L2: both are limited to 32767
+ *      (and to 0 from below) first, then lo = floor(low)^2, hi = floor(high)^2 -- magnitudes are compared squared, there is no square root.  Returns 0, -1 for a NaN
+ *      or a NULL pointer.  mlsd_canny takes lo and hi as this gives them.
+ *  (c) Sobel per plane in int: dx = (q[y-1][x+1] + 2 q[y][x+1] + q[y+1][x+1]) - (the same at x-1), dy likewise down minus up; taps outside the image replicate
+ *      the border pixel, or wrap around on an axis named in `wrap` (bit 0 columns, bit 1 rows, as mlsd_resample2d).
+ *  (d) m = |dx| + |dy| (L1) or dx^2 + dy^2 (L2); with 3 planes a pixel takes dx, dy and m from the plane with the largest m, the lowest plane index on ties.
+ *      m outside the image counts as 0, on a wrapped axis it is the wrapped pixel's.
+ *  (e) non-maximum suppression of the pixels with m > lo: with x = |dx|, y = |dy| << 15, t22 = 13573 x, t67 = t22 + (x << 16): if y < t22 the pixel is kept when
+ *      m > m[y][x-1] && m >= m[y][x+1]; else if y > t67 when m > m[y-1][x] && m >= m[y+1][x]; else, with s = -1 if (dx ^ dy) < 0 and 1 otherwise, when
+ *      m > m[y-1][x-s] && m > m[y+1][x+s].  A kept pixel is strong if m > hi, else weak.
+ *  (f) hysteresis: an edge is every strong pixel and every weak pixel 8-connected to a strong one through weak or strong pixels, around wrapped axes too.
+ * dst [planes_out][h][w] gets 1.0f on edges and 0.0f elsewhere, every plane the same.  ws: mlsd_canny_ws_bytes(w, h) of device memory from mlsd_malloc (two
+ * byte maps and the sweeps' flags; 0 for a size mlsd_canny refuses).  The hysteresis runs as sweeps over 128 x 128 tiles, launched in small groups whose flags the
+ * host reads back, waiting for the stream: not for captured plans.  *n_passes (host, may be NULL): the sweeps up to and including the first that changed nothing,
+ * at least 1 and at most w h + 1, which is also the cap of the host's loop (up to mlsd_canny_tile(4) - 1 further launched sweeps copied their input).
+ * Returns -1 before any launch for planes or planes_out not 1 or 3, an extent below 1 or above MLSD_CANNY_MAX_EXTENT, 2^31 elements or more in 3 planes, a bad wrap
+ * or l2, a NULL workspace, or src, dst and ws overlapping.
+ * mlsd_canny_tile: the kernels' constants for tests and measurements -- 0, 1: tile of the classification (x, y); 2, 3: tile of a sweep; 4: sweeps per group.
+ * mlsd_invert: dst[i] = 1 - src[i] (one rounding), src == dst allowed. */
+enum { MLSD_CANNY_MAX_EXTENT = 1 << 20 };
+size_t mlsd_canny_ws_bytes(int w, int h);
+int mlsd_canny(const float* src, int w, int h, int planes, int low, int high, int l2, int wrap, float* dst, int planes_out, void* ws, int* n_passes, void* stream);
+int mlsd_canny_thresholds(double low, double high, int l2, int* lo, int* hi);
+int mlsd_canny_tile(int which);
+int mlsd_invert(const float* src, float* dst, int64_t n, void* stream);
 /* Tiled diffusion (MultiDiffusion; not in the reference): the canvas latent is evaluated in overlapping windows of the UNet plan's size, the windows'
  * outputs are blended by a weighted average.  Window pixel (v, u) of a ww x wh window that starts at (x0, y0) lies on canvas pixel
  * ((y0 + v) mod H, (x0 + u) mod W): a window may straddle the seam of a wrapped axis; on an axis that does not wrap the caller keeps x0 + ww <= W.

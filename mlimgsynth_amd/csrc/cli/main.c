@@ -315,7 +315,7 @@ static unsigned char* img_from_tensor(const MLIS_Tensor* t)
 /* ------------------------------------------------------------------ options */
 static const char k_usage[] =
 "Usage: mlimgsynth-amd [COMMAND] [OPTIONS]\n\n"
-"Commands: generate | upscale | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
+"Commands: generate | upscale | canny | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
 "Generation:  -p --prompt TEXT   -n --nprompt TEXT   -d --image-dim W,H   -i --input PATH   --imask PATH\n"
 "             --ilatent PATH   --ilmask PATH   -o --output PATH   --olatent PATH   --no-prompt-parse BOOL\n"
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
@@ -327,6 +327,9 @@ static const char k_usage[] =
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
 "ControlNet:  --control-model PATH|synth[:SEED]   --control-image PATH   --control-strength F   --control-start F   --control-end F\n"
+"             --control-preprocess none|canny|invert   (run on the control image after it was resampled to each pass's size)\n"
+"Canny:       --canny-low F   --canny-high F   --canny-l2 y|n   (thresholds 0 .. 32767, defaults 100 200; l2: sqrt(dx^2 + dy^2) instead of |dx| + |dy|)\n"
+"             canny -i IN -o OUT [--canny-low F --canny-high F --canny-l2 y|n --tiling none|x|y|xy] writes the edge map of IN and needs no -m\n"
 "FreeU:       --freeu BOOL   --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
@@ -435,7 +438,7 @@ static int cmd_generate(Cli* C)
 		tensor_from_img(mlis_tensor_get(C->ctx, MLIS_TENSOR_MASK), NULL, &g);
 		tuf |= MLIS_TUF_MASK; free(mono); free(im.d);
 	}
-	if (C->ctl_img) {           /* the finished control map (no preprocessor): RGB, grey replicated, alpha dropped */
+	if (C->ctl_img) {           /* the control map, finished or for --control-preprocess: RGB, grey replicated, alpha dropped */
 		Img im; if (img_read(C->ctl_img, &im) < 0) return -1;
 		unsigned char *rgb = (unsigned char*)malloc((size_t)im.w * im.h * 3);
 		for (size_t i=0;i<(size_t)im.w*im.h;++i) for (int c=0;c<3;++c) rgb[i*3+c] = im.d[i*im.c + (im.c >= 3 ? c : 0)];
@@ -531,6 +534,33 @@ static int cmd_upscale(Cli* C)
 	return r < 0 ? -1 : 1;
 }
 
+/* canny: the edge map of --input with the canny_* options (the tiling as wrap), no SD model involved */
+static int cmd_canny(Cli* C)
+{
+	if (!C->in_img) FAIL("canny needs --input");
+	Img im; if (img_read(C->in_img, &im) < 0) return -1;
+	unsigned char *rgb = (unsigned char*)malloc((size_t)im.w * im.h * 3);      /* RGB: grey replicated, alpha dropped */
+	for (size_t i=0;i<(size_t)im.w*im.h;++i) for (int c=0;c<3;++c) rgb[i*3+c] = im.d[i*im.c + (im.c >= 3 ? c : 0)];
+	Img in3 = im; in3.d = rgb; in3.c = 3;
+	MLIS_Tensor t = {0};
+	tensor_from_img(&t, NULL, &in3);
+	free(rgb); free(im.d);
+	float low = 100, high = 200; int l2 = 0, wrap = 0;
+	mlis_option_get(C->ctx, MLIS_OPT_AMD_CANNY_LOW, &low);
+	mlis_option_get(C->ctx, MLIS_OPT_AMD_CANNY_HIGH, &high);
+	mlis_option_get(C->ctx, MLIS_OPT_AMD_CANNY_L2, &l2);
+	mlis_option_get(C->ctx, MLIS_OPT_AMD_TILING, &wrap);
+	int r = mlis_amd_tensor_canny(C->ctx, &t, &t, low, high, l2, wrap);
+	if (r < 0) fprintf(stderr, "error: canny: %s\n", mlis_errstr_get(C->ctx));
+	else {
+		unsigned char *px = img_from_tensor(&t);
+		r = img_write(C->out_img ? C->out_img : "output.png", px, (unsigned)t.n[0], (unsigned)t.n[1], 3, NULL);
+		free(px);
+	}
+	mlis_tensor_free(&t);
+	return r < 0 ? -1 : 1;
+}
+
 static int cmd_text(Cli* C, int encode)
 {
 	const char *prompt = NULL;
@@ -564,6 +594,7 @@ int main(int argc, char** argv)
 	int r;
 	if (!strcmp(C.cmd, "generate")) r = cmd_generate(&C);
 	else if (!strcmp(C.cmd, "upscale")) r = cmd_upscale(&C);
+	else if (!strcmp(C.cmd, "canny")) r = cmd_canny(&C);
 	else if (!strcmp(C.cmd, "list-backends")) {
 		r = 1;
 		for (unsigned i=0; ; ++i) {

@@ -970,6 +970,15 @@ MLB_API void mlis_amd_control_tag_set(MLIS_AmdCtx* S, uint64_t tag) { if (S && S
 MLB_API uint64_t mlis_amd_control_tag(const MLIS_AmdCtx* S) { return S && S->ctl_image ? S->ctl_tag : 0; }
 /* the control image as the hint plan reads it: device, NCHW fp32 [3][height][width]; NULL without a ControlNet or an image (tests) */
 MLB_API const void* mlis_amd_control_image_device(MLIS_AmdCtx* S) { return S && S->ctl_ctx && S->ctl_image ? S->t_hint_img->in_stage : NULL; }
+/* ... and copied to the host: what a pass was really conditioned on */
+MLB_API int mlis_amd_control_image_get(const MLIS_AmdCtx* S, float* host_dst, int* w, int* h)
+{
+	if (!S || !S->ctl_ctx || !S->ctl_image) return 0;
+	if (w) *w = S->c.width;
+	if (h) *h = S->c.height;
+	if (host_dst && (mlsd_memcpy(host_dst, S->t_hint_img->in_stage, (size_t)3 * S->c.width * S->c.height * 4, 1, S->stream) || mlsd_stream_sync(S->stream))) return -1;
+	return 1;
+}
 
 MLB_API int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* evals_controlled)
 {

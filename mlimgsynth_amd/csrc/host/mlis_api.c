@@ -52,6 +52,7 @@ struct MLIS_Ctx {
 	char *path_upscale; MLIS_AmdUpscaler *upscaler;       /* MLIS_OPT_AMD_UPSCALE_MODEL and the resident upscaler built from it (dropped whenever the option changes) */
 	int n_upscaler_builds, hires_use_model;                                     /* mlis_amd_upscaler_builds; MLIS_OPT_AMD_HIRES_USE_MODEL */
 	int downscale_filter;   /* MLIS_OPT_AMD_DOWNSCALE_FILTER: 0 none, else MLIS_AMD_AA_* + 1: the filter of the resamples that shrink (hires model path, control image) */
+	int control_preprocess; float canny_low, canny_high; int canny_l2;   /* MLIS_OPT_AMD_CONTROL_PREPROCESS (MLIS_AMD_PREPROCESS_*) and MLIS_OPT_AMD_CANNY_*: what control_apply runs behind its resample */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
@@ -153,8 +154,11 @@ static const char* const k_option_amd5[] = { "freeu", "freeu_b1", "freeu_b2", "f
 static const char* const k_option_amd6[] = { "upscale_model", "hires_use_model" };                       /* ids from MLIS_OPT_AMD_UPSCALE_MODEL */
 static const char* const k_option_amd7[] = { "downscale_filter" };                                       /* ids from MLIS_OPT_AMD_DOWNSCALE_FILTER */
 static const char* const k_downscale[] = { "none", "box", "bilinear", "bicubic", "lanczos" };            /* 0, MLIS_AMD_AA_* + 1 */
+static const char* const k_option_amd8[] = { "control_preprocess", "canny_low", "canny_high", "canny_l2" };   /* ids from MLIS_OPT_AMD_CONTROL_PREPROCESS */
+static const char* const k_preprocess[] = { "none", "canny", "invert" };                                 /* MLIS_AMD_PREPROCESS_* */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_CONTROL_PREPROCESS && x < MLIS_OPT_AMD_CONTROL_PREPROCESS + COUNTOF(k_option_amd8)) return k_option_amd8[x - MLIS_OPT_AMD_CONTROL_PREPROCESS];
 	if (x >= MLIS_OPT_AMD_DOWNSCALE_FILTER && x < MLIS_OPT_AMD_DOWNSCALE_FILTER + COUNTOF(k_option_amd7)) return k_option_amd7[x - MLIS_OPT_AMD_DOWNSCALE_FILTER];
 	if (x >= MLIS_OPT_AMD_UPSCALE_MODEL && x < MLIS_OPT_AMD_UPSCALE_MODEL + COUNTOF(k_option_amd6)) return k_option_amd6[x - MLIS_OPT_AMD_UPSCALE_MODEL];
 	if (x >= MLIS_OPT_AMD_FREEU && x < MLIS_OPT_AMD_FREEU + COUNTOF(k_option_amd5)) return k_option_amd5[x - MLIS_OPT_AMD_FREEU];
@@ -180,6 +184,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i6 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UPSCALE_MODEL + i6);
 	const int i7 = from_list(k_option_amd7, COUNTOF(k_option_amd7), 1, s, strlen(s));
 	if (i7 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_DOWNSCALE_FILTER + i7);
+	const int i8 = from_list(k_option_amd8, COUNTOF(k_option_amd8), 1, s, strlen(s));
+	if (i8 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_PREPROCESS + i8);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -243,6 +249,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->unet_tile_overlap = -1;
 	S->unet_tile_batch = 1;
 	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
+	S->canny_low = 100; S->canny_high = 200;
 	S->freeu_f[0] = 1.3f; S->freeu_f[1] = 1.4f; S->freeu_f[2] = 0.9f; S->freeu_f[3] = 0.2f;      /* b1, b2, s1, s2 (mlis_abi.h on where these come from) */
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
@@ -633,6 +640,27 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (i != S->downscale_filter && tensor_good(&S->control_image)) S->control_image_gen++;
 		S->downscale_filter = i;
 		break;
+	/* the preprocessor and its parameters: like the downscale_filter, a changed value makes the engines take the control image again (control_apply) */
+	case MLIS_OPT_AMD_CONTROL_PREPROCESS:  /* none|canny|invert or 0..2 */
+		if (A->is_str) {
+			next_str_arg(A);
+			i = from_list(k_preprocess, COUNTOF(k_preprocess), 1, A->arg_b, A->arg_n);
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i >= COUNTOF(k_preprocess)) BAD_VALUE;
+		if (i != S->control_preprocess && tensor_good(&S->control_image)) S->control_image_gen++;
+		S->control_preprocess = i;
+		break;
+	case MLIS_OPT_AMD_CANNY_LOW: if (!arg_float(A, 0, 32767, 100, &f)) BAD_VALUE; if (f != S->canny_low && tensor_good(&S->control_image)) S->control_image_gen++; S->canny_low = f; break;
+	case MLIS_OPT_AMD_CANNY_HIGH: if (!arg_float(A, 0, 32767, 200, &f)) BAD_VALUE; if (f != S->canny_high && tensor_good(&S->control_image)) S->control_image_gen++; S->canny_high = f; break;
+	case MLIS_OPT_AMD_CANNY_L2:
+		if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE;
+		if (i != S->canny_l2 && tensor_good(&S->control_image)) S->control_image_gen++;
+		S->canny_l2 = i;
+		break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -708,6 +736,10 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_UPSCALE_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_upscale ? S->path_upscale : ""; } break;
 	case MLIS_OPT_AMD_HIRES_USE_MODEL: { int *p = va_arg(ap, int*); if (p) *p = S->hires_use_model; } break;
 	case MLIS_OPT_AMD_DOWNSCALE_FILTER: { int *p = va_arg(ap, int*); if (p) *p = S->downscale_filter; } break;
+	case MLIS_OPT_AMD_CONTROL_PREPROCESS: { int *p = va_arg(ap, int*); if (p) *p = S->control_preprocess; } break;
+	case MLIS_OPT_AMD_CANNY_LOW: { float *p = va_arg(ap, float*); if (p) *p = S->canny_low; } break;
+	case MLIS_OPT_AMD_CANNY_HIGH: { float *p = va_arg(ap, float*); if (p) *p = S->canny_high; } break;
+	case MLIS_OPT_AMD_CANNY_L2: { int *p = va_arg(ap, int*); if (p) *p = S->canny_l2; } break;
 	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
 		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
@@ -1052,33 +1084,52 @@ static int control_weights(MLIS_Ctx* S)
 	return 1;
 }
 
+/* Canny of device planes [planes][h][w] into d_dst [3][h][w] (mlsd_canny with the thresholds of mlsd_canny_thresholds and a workspace of its own); waits for the
+ * default stream.  0, or mlsd's error */
+static int canny_device(const float* d_src, int w, int h, int planes, float low, float high, int l2, int wrap, float* d_dst)
+{
+	int lo = 0, hi = 0;
+	void *d_ws = NULL;
+	int r = mlsd_canny_thresholds(low, high, l2, &lo, &hi);
+	if (!r) r = mlsd_malloc(&d_ws, mlsd_canny_ws_bytes(w, h));
+	if (!r) r = mlsd_canny(d_src, w, h, planes, lo, hi, l2, wrap, d_dst, 3, d_ws, NULL, NULL);
+	if (!r) r = mlsd_device_sync();
+	if (d_ws) mlsd_free(d_ws);
+	return r;
+}
+
 /* the control image at the pass's pixel size into the engine (resampled on the GPU: bilinear, as mlis_amd_tensor_resample does, or with the downscale_filter
- * where that is set and an axis shrinks, as mlis_amd_tensor_resample_aa does), strength and window */
+ * where that is set and an axis shrinks, as mlis_amd_tensor_resample_aa does; then through the control_preprocess at that size, as mlis_amd_tensor_canny does with
+ * the tiling as wrap), strength and window */
 static int control_apply(MLIS_Ctx* S, int w_img, int h_img)
 {
 	if (str_empty(S->path_control)) return 1;
-	/* the engine has one pixel size: it still holds this very image, resampled and through the hint plan, unless the option was set again since, the downscale_filter
-	 * changed (either counts control_image_gen on) or the tiling changed the resampler's edges (another engine) */
+	/* the engine has one pixel size: it still holds this very image, resampled, preprocessed and through the hint plan, unless the option was set again since, the
+	 * downscale_filter, the control_preprocess or a canny_* option changed (each counts control_image_gen on) or the tiling changed the edges (another engine) */
 	if (mlis_amd_control_tag(S->eng) == S->control_image_gen)
 		return mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
 	const MLIS_Tensor *src = &S->control_image;
 	const int sw = src->n[0], sh = src->n[1];
 	const size_t n_src = (size_t)3 * sw * sh, n_dst = (size_t)3 * w_img * h_img;
 	const int aa = S->downscale_filter && (w_img < sw || h_img < sh);
-	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL;
+	const int pre = S->control_preprocess;
+	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL, *d_pre = NULL;
 	int r = 1;
-	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || (pre && mlsd_malloc(&d_pre, n_dst * 4)) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
 			|| (aa ? (mlsd_malloc(&d_ws, mlsd_resample2d_aa_ws_bytes(sw, sh, w_img, h_img, 3, S->downscale_filter - 1))
 					|| mlsd_resample2d_aa((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, S->downscale_filter - 1, S->tiling, d_ws, NULL))
 				: mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, MLIS_AMD_RESAMPLE_BILINEAR, S->tiling, NULL))
+			|| (pre == MLIS_AMD_PREPROCESS_CANNY && canny_device((const float*)d_dst, w_img, h_img, 3, S->canny_low, S->canny_high, S->canny_l2, S->tiling, (float*)d_pre))
+			|| (pre == MLIS_AMD_PREPROCESS_INVERT && mlsd_invert((const float*)d_dst, (float*)d_pre, (int64_t)n_dst, NULL))
 			|| mlsd_device_sync()
-			|| mlis_amd_set_control_image_device(S->eng, d_dst) < 0
+			|| mlis_amd_set_control_image_device(S->eng, pre ? d_pre : d_dst) < 0
 			|| mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0)
 		r = api_error_lib(S, MLIS_E_UNKNOWN);
 	if (r > 0) mlis_amd_control_tag_set(S->eng, S->control_image_gen);
 	if (d_src) mlsd_free(d_src);
 	if (d_dst) mlsd_free(d_dst);
 	if (d_ws) mlsd_free(d_ws);
+	if (d_pre) mlsd_free(d_pre);
 	return r;
 }
 
@@ -1446,6 +1497,32 @@ MLB_API int mlis_amd_tensor_resample_aa(MLIS_Ctx* S, const MLIS_Tensor* src, MLI
 	return tensor_resample_aa(S, src, dst, w, h, filter);
 }
 
+/* ------------------------------------------------------------------ control image preprocessor (hip/canny.hip) */
+/* host tensor -> device, mlsd_canny, -> host tensor [w][h][3][1]; src may be dst */
+MLB_API int mlis_amd_tensor_canny(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, float low, float high, int l2, int wrap)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	if (!src || !dst || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || (src->n[2] != 1 && src->n[2] != 3) || src->n[3] != 1)
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor for canny (one image of 1 or 3 channels)");
+	if (!(low >= 0 && low <= 32767) || !(high >= 0 && high <= 32767) || (l2 & ~1) || (wrap & ~3))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid canny arguments: low %g, high %g (0 .. 32767), l2 %d (0, 1), wrap %d (0 .. 3)", low, high, l2, wrap);
+	const int w = src->n[0], h = src->n[1], c = src->n[2];
+	const size_t n = (size_t)w * h;
+	if (!mlsd_canny_ws_bytes(w, h)) return api_error(S, MLIS_E_OPT_VALUE, "invalid size for canny: %dx%d", w, h);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_dst = NULL;
+	if (mlsd_malloc(&d_src, n * c * 4) || mlsd_malloc(&d_dst, n * 3 * 4) || mlsd_memcpy(d_src, src->d, n * c * 4, 0, NULL)
+			|| canny_device((const float*)d_src, w, h, c, low, high, l2, wrap, (float*)d_dst))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, w, h, 3, 1);
+		if (mlsd_memcpy(dst->d, d_dst, n * 3 * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	return r;
+}
+
 /* ------------------------------------------------------------------ model upscaling (ESRGAN, host/upscaler.c) */
 /* the context's upscaler for the upscale_model option as it stands: built on first use, resident until the option changes */
 static int upscaler_get(MLIS_Ctx* S)
@@ -1541,6 +1618,8 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	}
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
+	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
+	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);

@@ -417,6 +417,7 @@ def _proto2():
     l.mlis_amd_set_control.argtypes = [vp, c_f, c_f, c_f]
     l.mlis_amd_control_active.argtypes = [c_int, c_int, c_f, c_f]
     l.mlis_amd_control_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    l.mlis_amd_control_image_get.argtypes = [vp, FP, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_set_freeu.argtypes = [vp, c_f, c_f, c_f, c_f]
     l.mlis_amd_freeu_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l._proto2_done = True
@@ -576,6 +577,15 @@ class Generator:
     def set_control(self, strength=1.0, start=0.0, end=1.0):
         """mlis_amd_set_control: strength in [0, 2], step window 0 <= start <= end <= 1"""
         check1(_proto2().mlis_amd_set_control(self.h, float(strength), float(start), float(end)), "mlis_amd_set_control")
+
+    def control_image(self):
+        """mlis_amd_control_image_get: the control map the engine holds, float32 [3][H][W], or None without one"""
+        w, h = c_int(), c_int()
+        if check1(_proto2().mlis_amd_control_image_get(self.h, None, ctypes.byref(w), ctypes.byref(h)), "mlis_amd_control_image_get") == 0:
+            return None
+        a = np.empty((3, h.value, w.value), np.float32)
+        check1(_proto2().mlis_amd_control_image_get(self.h, fptr(a), None, None), "mlis_amd_control_image_get")
+        return a
 
     def control_info(self):
         """(residuals of the ControlNet plan -- 0 without one --, evaluations of the last denoise / dxdt in which it ran)"""

@@ -219,6 +219,39 @@ def resample2d_aa(src, sw, sh, dst, dw, dh, planes, filter, wrap=0, ws=None, str
     check(lib().mlsd_resample2d_aa(vp(src), sw, sh, vp(dst), dw, dh, planes, filter, wrap, vp(ws), vp(stream)), "mlsd_resample2d_aa")
 
 
+def canny_ws_bytes(w, h):
+    """mlsd_canny_ws_bytes: device workspace of one canny call (two class maps and the sweeps' flags); 0 for a size it refuses."""
+    f = lib().mlsd_canny_ws_bytes
+    f.restype = ctypes.c_size_t
+    return int(f(int(w), int(h)))
+
+
+def canny_thresholds(low, high, l2=False):
+    """mlsd_canny_thresholds: (lo, hi) as mlsd_canny takes them -- swapped if low > high, floored, under l2 limited to 32767 and squared.  Host only."""
+    lo, hi = c_int(), c_int()
+    check(lib().mlsd_canny_thresholds(ctypes.c_double(low), ctypes.c_double(high), 1 if l2 else 0, ctypes.byref(lo), ctypes.byref(hi)), "mlsd_canny_thresholds")
+    return lo.value, hi.value
+
+
+def canny_tile(which):
+    """mlsd_canny_tile: 0, 1 the classification kernel's tile (x, y); 2, 3 a hysteresis sweep's tile; 4 the sweeps launched per flag read"""
+    return int(lib().mlsd_canny_tile(int(which)))
+
+
+def canny(src, w, h, planes, lo, hi, l2, wrap, dst, planes_out, ws, stream=None):
+    """mlsd_canny: fp32 planes [planes][h][w] in [0,1] -> edge map [planes_out][h][w] of 1.0 / 0.0 (device pointers; lo, hi: canny_thresholds; ws: canny_ws_bytes
+    of device memory; wrap bit 0 columns, bit 1 rows).  Returns the hysteresis sweeps up to and including the first that changed nothing."""
+    n = c_int()
+    check(lib().mlsd_canny(vp(src), int(w), int(h), int(planes), int(lo), int(hi), 1 if l2 else 0, int(wrap), vp(dst), int(planes_out), vp(ws), ctypes.byref(n), vp(stream)),
+          "mlsd_canny")
+    return n.value
+
+
+def invert(src, dst, n, stream=None):
+    """mlsd_invert: dst[i] = 1 - src[i] for n floats (device pointers)"""
+    check(lib().mlsd_invert(vp(src), vp(dst), c_i64(n), vp(stream)), "mlsd_invert")
+
+
 WINDOW_MAX_AXIS = 64
 
 

@@ -47,9 +47,11 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_UNET_TILE_OVERLAP=112, AMD_UNET_TILE_BATCH=121, AMD_CONTROL_MODEL=131, AMD_CONTROL_IMAGE=132,
                                                                            AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135, AMD_FREEU=141,
                                                                            AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145,
-                                                                           AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161))
+                                                                           AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161,
+                                                                           AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 _define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
+_define("MLIS_AMD_PREPROCESS_", ["NONE", "CANNY", "INVERT"])
 MLIS_CTEF_NO_NORM = 1
 
 
@@ -82,6 +84,7 @@ _PROTOTYPES = {
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
     "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mlis_amd_tensor_canny": (_I, [_V, _TP, _TP, _F, _F, _I, _I]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
@@ -302,10 +305,12 @@ class MLImgSynth:
             self.option_set("unet_tile_batch", batch)
 
     # ---- ControlNet
-    def control_set(self, model=None, image=None, strength=None, start=None, end=None):
-        """ControlNet: model = path of a safetensors ControlNet for the base model ("synth[:seed]" with a synth: model, "" = off); image = the finished control
+    def control_set(self, model=None, image=None, strength=None, start=None, end=None, preprocess=None, canny_low=None, canny_high=None, canny_l2=None):
+        """ControlNet: model = path of a safetensors ControlNet for the base model ("synth[:seed]" with a synth: model, "" = off); image = the control
         map, a uint8 array [h][w][3] of any size (it is resampled to each pass's size) or False to clear it; strength in [0, 2]; start / end: the share of the
-        steps that is controlled.  None keeps a setting.  The options persist across generations."""
+        steps that is controlled; preprocess = 'none' (the image is the finished map) | 'canny' | 'invert', run on the GPU after the resample, at each pass's own
+        size; canny_low / canny_high = its thresholds in 0 .. 32767 (100, 200), canny_l2 = True for the Euclidean gradient magnitude.  None keeps a setting.
+        The options persist across generations."""
         if model is not None:
             self.option_set("control_model", model)
         if image is False:
@@ -320,9 +325,29 @@ class MLImgSynth:
             img = MLIS_Image_C(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), a.size, a.shape[1], a.shape[0], 3, 0)
             if self._lib.mlis_option_set(self._ctx, MLIS_OPT_AMD_CONTROL_IMAGE, ctypes.byref(img)) < 0:     # noqa: F821  (the library copies the pixels)
                 raise RuntimeError("Failed to set the control image: %s" % self.errstr_get())
-        for name, v in (("control_strength", strength), ("control_start", start), ("control_end", end)):
+        for name, v in (("control_strength", strength), ("control_start", start), ("control_end", end), ("control_preprocess", preprocess),
+                        ("canny_low", canny_low), ("canny_high", canny_high)):
             if v is not None:
                 self.option_set(name, v)
+        if canny_l2 is not None:
+            self.option_set("canny_l2", 1 if canny_l2 else 0)
+
+    def canny(self, image, low=100, high=200, l2=False, wrap=0):
+        """Canny edge map on the GPU (OpenCV's Canny(img_u8, low, high) with aperture 3 as recalled; the rules are in mlsd_kernels.h).  image: an MLIS_Tensor
+        [1,c,h,w] in [0,1] or a uint8 array [h][w] / [h][w][c], c = 1 or 3.  Returns an MLIS_Tensor [1,3,h,w]: 1 on edges, 0 elsewhere.  wrap: bit 0 columns,
+        bit 1 rows wrap around.  Needs no model."""
+        if not isinstance(image, MLIS_Tensor):
+            import numpy as np
+            a = np.asarray(image)
+            if a.dtype != np.uint8 or a.ndim not in (2, 3):
+                raise ValueError("canny takes an MLIS_Tensor or a uint8 array [h][w] or [h][w][c]")
+            a = a[:, :, None] if a.ndim == 2 else a
+            image = tensor_from_numpy((a.astype(np.float32) / np.float32(255)).transpose(2, 0, 1)[None])
+        tin = image._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_canny(self._ctx, ctypes.byref(tin), tout, float(low), float(high), 1 if l2 else 0, int(wrap)) < 0:
+            raise RuntimeError("Failed to run canny: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
 
     # ---- FreeU
     def freeu_set(self, on=None, b1=None, b2=None, s1=None, s2=None):

@@ -100,8 +100,25 @@ typedef enum {
 	MLIS_OPT_AMD_CONTROL_PREPROCESS = 171, /* "control_preprocess": none|canny|invert or 0..2 (int; MLIS_AMD_PREPROCESS_*), default none = the control image is the finished map */
 	MLIS_OPT_AMD_CANNY_LOW = 172,          /* "canny_low" (float 0 .. 32767, default 100) and */
 	MLIS_OPT_AMD_CANNY_HIGH = 173,         /* "canny_high" (float 0 .. 32767, default 200): the hysteresis thresholds on the gradient magnitude of the 8-bit image; swapped if low > high */
-	MLIS_OPT_AMD_CANNY_L2 = 174            /* "canny_l2" (int 0 / 1, default 0): the magnitude is sqrt(dx^2 + dy^2) (compared squared) instead of |dx| + |dy| */
+	MLIS_OPT_AMD_CANNY_L2 = 174,           /* "canny_l2" (int 0 / 1, default 0): the magnitude is sqrt(dx^2 + dy^2) (compared squared) instead of |dx| + |dy| */
+	/* region inpainting: what front ends call "inpaint area: only masked", "mask blur" and the paste-back.  When any of the six is off its default and the generation
+	 * has a mask (image_mask, or the alpha of image), the mask goes through mlis_amd_tensor_mask_weight (mask_invert), _mask_grow (mask_grow) and _gauss_blur (mask_blur)
+	 * to the repaint weight p, and the pass runs with 1 - p as its mask.  With all six at their defaults none of that runs and a generation gives the bytes it gave
+	 * before these existed.  They persist across generations.  mlis_generate refuses: masked with a tiling other than none (a crop is not periodic), masked or
+	 * inpaint_composite without an image and a mask, or with no_decode, and a mask that leaves nothing to repaint.  (A block of its own from 181.) */
+	MLIS_OPT_AMD_INPAINT_AREA = 181,       /* "inpaint_area": whole|masked or 0..1 (int; MLIS_AMD_INPAINT_*), default whole.  masked: the region of mlis_amd_inpaint_region around the
+	                                        * bounding box of p > 0 is cropped from the image (any size, not only multiples of 8) and from 1 - p, both are resampled to IMAGE_DIM (the
+	                                        * image in the hires_upscaler mode, the mask in that mode but bilinear for bicubic so that it stays in 0 .. 1; where an axis shrinks and a
+	                                        * downscale_filter is set, with that filter), inpainted there as img2img, the result is resampled back to the region's size by the same
+	                                        * choice and composited into the untouched image through p.  A control image is taken to cover the whole picture and cropped likewise */
+	MLIS_OPT_AMD_INPAINT_PADDING = 182,    /* "inpaint_padding" (int pixels, 0 .. 512, default 32): what the bounding box is padded by on each side */
+	MLIS_OPT_AMD_MASK_BLUR = 183,          /* "mask_blur" (float sigma, 0 .. 64, default 0): the Gaussian blur of the repaint weight (mlis_amd_tensor_gauss_blur) */
+	MLIS_OPT_AMD_MASK_GROW = 184,          /* "mask_grow" (int pixels, -256 .. 256, default 0): the repainted area grows by so many pixels, or shrinks if negative */
+	MLIS_OPT_AMD_MASK_INVERT = 185,        /* "mask_invert" (int 0 / 1, default 0): the mask says 1 = repaint, the front ends' convention, not the reference's 1 = keep */
+	MLIS_OPT_AMD_INPAINT_COMPOSITE = 186   /* "inpaint_composite" (int 0 / 1, default 0): with inpaint_area whole, the decoded images are composited over the input image through
+	                                        * p, so that pixels with p == 0 are the input's, exactly.  masked implies it */
 } MLIS_Option;
+enum { MLIS_AMD_INPAINT_WHOLE = 0, MLIS_AMD_INPAINT_MASKED = 1 };
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };
 enum { MLIS_AMD_AA_BOX = 0, MLIS_AMD_AA_TRIANGLE = 1, MLIS_AMD_AA_CUBIC = 2, MLIS_AMD_AA_LANCZOS = 3 };
 enum { MLIS_AMD_PREPROCESS_NONE = 0, MLIS_AMD_PREPROCESS_CANNY = 1, MLIS_AMD_PREPROCESS_INVERT = 2 };
@@ -192,6 +209,31 @@ int mlis_amd_tensor_resample_aa(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tens
  * swapped if low > high; l2: 0 / 1; wrap: bit 0 columns, bit 1 rows wrap around (what "tiling" x / y / xy mean), 0 .. 3.  src == dst is allowed.  Needs no model.
  * Returns 1, MLIS_E_OPT_VALUE for bad arguments. */
 int mlis_amd_tensor_canny(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, float low, float high, int l2, int wrap);
+/* Region inpainting, piece by piece (the kernels and their rules: mlsd_kernels.h, "region inpainting").  Each goes from host tensors to the GPU and back, needs no model and
+ * allows src == dst; wrap as in mlis_amd_tensor_canny.  They return 1, MLIS_E_OPT_VALUE for bad arguments.
+ *   mask_weight  dst = clamp(invert ? src : 1 - src, 0, 1), any shape: the repaint weight p of a mask
+ *   mask_grow    src [w][h][1][1]: maximum (radius > 0) or minimum (radius < 0) over the (2 |radius| + 1)^2 square, |radius| <= 256
+ *   gauss_blur   every plane of src blurred with sigma 0 .. 64: radius (int)(2.5 sigma + 0.5), taps normalised in double; a border pixel is replicated (both as recalled
+ *                from the front ends' OpenCV calls, parity-unpinned)
+ *   mask_bbox    bbox = x0, y0, x1, y1 (half open) of the pixels of src [w][h][1][1] with a value > 0; 0, 0, 0, 0 if none
+ *   composite    dst [W][H][c][B] = orig outside the rectangle at (x0, y0) of the patch's size, orig (1 - p) + patch p inside (fp32, each operation rounded once);
+ *                orig [W][H][c][1 or B], patch [cw][ch][c][B], p [W][H][1][1].  dst may be orig or patch */
+int mlis_amd_tensor_mask_weight(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int invert);
+int mlis_amd_tensor_mask_grow(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, int radius, int wrap);
+int mlis_amd_tensor_gauss_blur(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst, float sigma, int wrap);
+int mlis_amd_tensor_mask_bbox(MLIS_Ctx* ctx, const MLIS_Tensor* src, int bbox[4]);
+int mlis_amd_tensor_composite(MLIS_Ctx* ctx, MLIS_Tensor* dst, const MLIS_Tensor* orig, const MLIS_Tensor* patch, const MLIS_Tensor* p, int x0, int y0);
+/* The region that inpaint_area masked processes, out = x0, y0, x1, y1 (half open), from the bounding box of the repaint weight; integers only, no context, no GPU.
+ * This project's own rule:
+ *  1. the box is padded by `padding` on each side and clamped to the W x H image; cw x ch is its size.
+ *  2. the shorter side grows to the aspect tw : th of the processing size: if cw th < ch tw the width becomes min(W, ceil(ch tw / th)), otherwise the height becomes
+ *     min(H, ceil(cw th / tw)).  Of the extra pixels floor(extra / 2) go to the left (top), the rest to the other side; a rectangle that then crosses an edge of the
+ *     image is shifted back inside.
+ * Returns 1; -1 for an empty or misplaced box (x0 < x1, y0 < y1, inside the image), W, H, tw or th below 1, or a negative padding. */
+int mlis_amd_inpaint_region(int W, int H, const int bbox[4], int padding, int tw, int th, int out[4]);
+/* of the last mlis_generate: region = the rectangle composited (the whole image with inpaint_area whole), proc = the size the pass ran at.  Returns 1, or 0 (and zeros) if
+ * that generation composited nothing.  Either pointer may be NULL. */
+int mlis_amd_inpaint_info(MLIS_Ctx* ctx, int region[4], int proc[2]);
 /* dst = src upscaled 4x by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 -> dst [4w][4h][3][n] (not clamped).  src == dst is allowed.
  * The upscaler is built on the first use and stays resident in the context until the option changes (mlis_amd_upscaler_builds counts the builds); the image border is
  * padded with zeros whatever "tiling" says.  Returns 1, MLIS_E_OPT_VALUE when no upscale_model is set or src is not a 3-channel image. */

@@ -496,6 +496,44 @@ int mlsd_canny(const float* src, int w, int h, int planes, int low, int high, in
 int mlsd_canny_thresholds(double low, double high, int l2, int* lo, int* hi);
 int mlsd_canny_tile(int which);
 int mlsd_invert(const float* src, float* dst, int64_t n, void* stream);
+/* Region inpainting, the image-space pieces (hip/inpaint.hip; not in the reference): fp32 planes [planes][h][w].  wrap: bit 0 the x axis, bit 1 the y axis, as
+ * everywhere.  An index outside a plane replicates the border pixel (what OpenCV's BORDER_REPLICATE does; the border mode front ends blur their masks with is
+ * BORDER_REFLECT_101 as recalled, which could not be checked when this was written: parity-unpinned, pinned to this rule); on a wrapped axis it is taken modulo
+ * the extent, a true modulo, so a radius may exceed the extent.  No float atomics anywhere: two calls give identical bytes.  Crops are mlsd_window_gather.
+ *   mlsd_mask_weight  p[i] = min(max(invert ? m[i] : 1 - m[i], 0), 1), the repaint weight; NaN gives 0.  The reference's masks say 1 = keep, 0 = repaint; invert
+ *                     takes the front ends' convention (white = repaint).  mask == p is allowed.
+ *   mlsd_mask_grow    one plane.  radius > 0: the maximum over the (2 r + 1)^2 square around a pixel; radius < 0: the minimum over the (2 |r| + 1)^2 square; 0: a
+ *                     copy of the bits.  |radius| <= MLSD_MASK_GROW_MAX.  Separable: rows into ws (w h floats), then columns.  Maximum and minimum are exact, the
+ *                     result is held bit for bit.
+ *   mlsd_gauss_taps   host only.  Radius r = (int)(2.5 sigma + 0.5) -- the kernel size OpenCV's GaussianBlur gets from the front ends' "mask blur" as recalled
+ *                     (ksize = 2 int(2.5 sigma + 0.5) + 1); it could not be checked: parity-unpinned, pinned to this rule.  Weights exp(-k^2 / (2 sigma^2)),
+ *                     k = -r .. r, computed and normalised to sum 1 in double, then rounded to float.  Returns 2 r + 1, or -1 when that exceeds k_max or sigma is
+ *                     outside 0 .. MLSD_GAUSS_MAX_SIGMA (so r <= 160, at most MLSD_GAUSS_MAX_TAPS taps).  r == 0 (sigma < 0.2): one tap of 1.0.
+ *   mlsd_gauss_blur   dst[y][x] = sum_j t[j] (sum_k t[k] src[y - r + j][x - r + k]): rows first into the workspace, then columns; each sum is fp32 in ascending
+ *                     tap order, every product and addition rounded on its own (no contraction), so every route to the kernel agrees bit for bit, whatever the
+ *                     tile.  r == 0 copies the bits.  ws: mlsd_gauss_blur_ws_bytes(w, h, planes) of device memory (the taps, uploaded on the stream, which is
+ *                     waited for once, and the intermediate): not for captured plans.  The row pass stages its tile's span in LDS and reads global memory
+ *                     directly where the span of 4 rows exceeds the limit: mlsd_gauss_blur_lds_limit(bytes) lowers that limit (0 .. 32768; 0 runs every shape
+ *                     the direct way; negative only asks; returns the previous limit) for tests and measurements.  The results do not depend on it.
+ *   mlsd_mask_bbox    out4_dev (4 ints in device memory) = x0, y0, x1, y1, half open, of the pixels with p > 0 (1e-30 counts, -0.0 and NaN do not); 0, 0, 0, 0
+ *                     when there are none.  Integer minima and maxima (integer atomics: order-independent): an initialising fill, the reduction, and a
+ *                     one-thread launch that writes the zeros of the empty case.
+ *   mlsd_composite    dst [B][planes][H][W]; orig [n_orig][planes][H][W], n_orig 1 (shared) or B; patch [B][planes][ch][cw]; p [H][W].  Outside the rectangle
+ *                     [x0, x0 + cw) x [y0, y0 + ch) dst = orig, a copy; inside dst = orig (1 - p) + patch p in mask_apply's arithmetic: 1 - p, the two products
+ *                     and the sum each rounded once.  So p == 0 gives the original's value, p == 1 the patch's, and the result is numpy's fp32 expression.
+ *                     dst may be orig when n_orig == B.
+ * All return -1 before any launch for a NULL pointer, an extent below 1 or above MLSD_INPAINT_MAX_EXTENT, 2^31 elements or more, a bad wrap, radius, sigma or
+ * rectangle, and buffers that overlap other than as allowed above. */
+enum { MLSD_INPAINT_MAX_EXTENT = 1 << 20, MLSD_MASK_GROW_MAX = 256, MLSD_GAUSS_MAX_SIGMA = 64, MLSD_GAUSS_MAX_TAPS = 321 };
+int mlsd_mask_weight(const float* mask, float* p, int64_t n, int invert, void* stream);
+int mlsd_mask_grow(const float* src, float* dst, int w, int h, int radius, int wrap, void* ws, void* stream);
+int mlsd_gauss_taps(float sigma, float* w, int k_max);
+size_t mlsd_gauss_blur_ws_bytes(int w, int h, int planes);
+int mlsd_gauss_blur(const float* src, float* dst, int w, int h, int planes, float sigma, int wrap, void* ws, void* stream);
+int mlsd_gauss_blur_lds_limit(int bytes);
+int mlsd_mask_bbox(const float* p, int w, int h, int* out4_dev, void* stream);
+int mlsd_composite(float* dst, const float* orig, int n_orig, const float* patch, const float* p, int W, int H, int planes, int B, int x0, int y0, int cw, int ch,
+                   void* stream);
 /* Tiled diffusion (MultiDiffusion; not in the reference): the canvas latent is evaluated in overlapping windows of the UNet plan's size, the windows'
  * outputs are blended by a weighted average.  Window pixel (v, u) of a ww x wh window that starts at (x0, y0) lies on canvas pixel
  * ((y0 + v) mod H, (x0 + u) mod W): a window may straddle the seam of a wrapped axis; on an axis that does not wrap the caller keeps x0 + ww <= W.

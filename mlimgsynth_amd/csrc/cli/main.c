@@ -330,7 +330,9 @@ static const char k_usage[] =
 "             --control-preprocess none|canny|invert   (run on the control image after it was resampled to each pass's size)\n"
 "Canny:       --canny-low F   --canny-high F   --canny-l2 y|n   (thresholds 0 .. 32767, defaults 100 200; l2: sqrt(dx^2 + dy^2) instead of |dx| + |dy|)\n"
 "             canny -i IN -o OUT [--canny-low F --canny-high F --canny-l2 y|n --tiling none|x|y|xy] writes the edge map of IN and needs no -m\n"
-"FreeU:       --freeu BOOL   --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
+"Inpainting:  --inpaint-area whole|masked   --inpaint-padding PX   --mask-blur SIGMA   --mask-grow PX   --mask-invert y|n   --inpaint-composite y|n\n"
+"             (with -i and --imask; masked: only the padded bounding box of the repainted pixels is processed, at -d, and pasted back; -i may have any size)\n"
+"FreeU:       --freeu BOOL  --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";

@@ -53,6 +53,10 @@ struct MLIS_Ctx {
 	int n_upscaler_builds, hires_use_model;                                     /* mlis_amd_upscaler_builds; MLIS_OPT_AMD_HIRES_USE_MODEL */
 	int downscale_filter;   /* MLIS_OPT_AMD_DOWNSCALE_FILTER: 0 none, else MLIS_AMD_AA_* + 1: the filter of the resamples that shrink (hires model path, control image) */
 	int control_preprocess; float canny_low, canny_high; int canny_l2;   /* MLIS_OPT_AMD_CONTROL_PREPROCESS (MLIS_AMD_PREPROCESS_*) and MLIS_OPT_AMD_CANNY_*: what control_apply runs behind its resample */
+	/* MLIS_OPT_AMD_INPAINT_* / MASK_*: region inpainting (generate_inpaint); the rectangle and processing size of the last generation (mlis_amd_inpaint_info) */
+	int inpaint_area, inpaint_padding, mask_grow, mask_invert, inpaint_composite; float mask_blur;
+	int inp_region[4], inp_proc[2], inp_done;
+	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
@@ -156,8 +160,11 @@ static const char* const k_option_amd7[] = { "downscale_filter" };              
 static const char* const k_downscale[] = { "none", "box", "bilinear", "bicubic", "lanczos" };            /* 0, MLIS_AMD_AA_* + 1 */
 static const char* const k_option_amd8[] = { "control_preprocess", "canny_low", "canny_high", "canny_l2" };   /* ids from MLIS_OPT_AMD_CONTROL_PREPROCESS */
 static const char* const k_preprocess[] = { "none", "canny", "invert" };                                 /* MLIS_AMD_PREPROCESS_* */
+static const char* const k_option_amd9[] = { "inpaint_area", "inpaint_padding", "mask_blur", "mask_grow", "mask_invert", "inpaint_composite" };   /* ids from MLIS_OPT_AMD_INPAINT_AREA */
+static const char* const k_inpaint_area[] = { "whole", "masked" };                                       /* MLIS_AMD_INPAINT_* */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_INPAINT_AREA && x < MLIS_OPT_AMD_INPAINT_AREA + COUNTOF(k_option_amd9)) return k_option_amd9[x - MLIS_OPT_AMD_INPAINT_AREA];
 	if (x >= MLIS_OPT_AMD_CONTROL_PREPROCESS && x < MLIS_OPT_AMD_CONTROL_PREPROCESS + COUNTOF(k_option_amd8)) return k_option_amd8[x - MLIS_OPT_AMD_CONTROL_PREPROCESS];
 	if (x >= MLIS_OPT_AMD_DOWNSCALE_FILTER && x < MLIS_OPT_AMD_DOWNSCALE_FILTER + COUNTOF(k_option_amd7)) return k_option_amd7[x - MLIS_OPT_AMD_DOWNSCALE_FILTER];
 	if (x >= MLIS_OPT_AMD_UPSCALE_MODEL && x < MLIS_OPT_AMD_UPSCALE_MODEL + COUNTOF(k_option_amd6)) return k_option_amd6[x - MLIS_OPT_AMD_UPSCALE_MODEL];
@@ -186,6 +193,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i7 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_DOWNSCALE_FILTER + i7);
 	const int i8 = from_list(k_option_amd8, COUNTOF(k_option_amd8), 1, s, strlen(s));
 	if (i8 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_PREPROCESS + i8);
+	const int i9 = from_list(k_option_amd9, COUNTOF(k_option_amd9), 1, s, strlen(s));
+	if (i9 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_INPAINT_AREA + i9);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -250,6 +259,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->unet_tile_batch = 1;
 	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
 	S->canny_low = 100; S->canny_high = 200;
+	S->inpaint_padding = 32;
 	S->freeu_f[0] = 1.3f; S->freeu_f[1] = 1.4f; S->freeu_f[2] = 0.9f; S->freeu_f[3] = 0.2f;      /* b1, b2, s1, s2 (mlis_abi.h on where these come from) */
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
@@ -661,6 +671,23 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (i != S->canny_l2 && tensor_good(&S->control_image)) S->control_image_gen++;
 		S->canny_l2 = i;
 		break;
+	case MLIS_OPT_AMD_INPAINT_AREA:        /* whole|masked or 0..1 */
+		if (A->is_str) {
+			next_str_arg(A);
+			i = from_list(k_inpaint_area, COUNTOF(k_inpaint_area), 1, A->arg_b, A->arg_n);
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i >= COUNTOF(k_inpaint_area)) BAD_VALUE;
+		S->inpaint_area = i;
+		break;
+	case MLIS_OPT_AMD_INPAINT_PADDING: if (!arg_int(A, 0, 512, 32, &i)) BAD_VALUE; S->inpaint_padding = i; break;
+	case MLIS_OPT_AMD_MASK_BLUR: if (!arg_float(A, 0, MLSD_GAUSS_MAX_SIGMA, 0, &f)) BAD_VALUE; S->mask_blur = f; break;
+	case MLIS_OPT_AMD_MASK_GROW: if (!arg_int(A, -MLSD_MASK_GROW_MAX, MLSD_MASK_GROW_MAX, 0, &i)) BAD_VALUE; S->mask_grow = i; break;
+	case MLIS_OPT_AMD_MASK_INVERT: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->mask_invert = i; break;
+	case MLIS_OPT_AMD_INPAINT_COMPOSITE: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->inpaint_composite = i; break;
 	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
@@ -740,6 +767,12 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_CANNY_LOW: { float *p = va_arg(ap, float*); if (p) *p = S->canny_low; } break;
 	case MLIS_OPT_AMD_CANNY_HIGH: { float *p = va_arg(ap, float*); if (p) *p = S->canny_high; } break;
 	case MLIS_OPT_AMD_CANNY_L2: { int *p = va_arg(ap, int*); if (p) *p = S->canny_l2; } break;
+	case MLIS_OPT_AMD_INPAINT_AREA: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_area; } break;
+	case MLIS_OPT_AMD_INPAINT_PADDING: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_padding; } break;
+	case MLIS_OPT_AMD_MASK_BLUR: { float *p = va_arg(ap, float*); if (p) *p = S->mask_blur; } break;
+	case MLIS_OPT_AMD_MASK_GROW: { int *p = va_arg(ap, int*); if (p) *p = S->mask_grow; } break;
+	case MLIS_OPT_AMD_MASK_INVERT: { int *p = va_arg(ap, int*); if (p) *p = S->mask_invert; } break;
+	case MLIS_OPT_AMD_INPAINT_COMPOSITE: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_composite; } break;
 	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
 		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
 	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
@@ -1101,21 +1134,32 @@ static int canny_device(const float* d_src, int w, int h, int planes, float low,
 /* the control image at the pass's pixel size into the engine (resampled on the GPU: bilinear, as mlis_amd_tensor_resample does, or with the downscale_filter
  * where that is set and an axis shrinks, as mlis_amd_tensor_resample_aa does; then through the control_preprocess at that size, as mlis_amd_tensor_canny does with
  * the tiling as wrap), strength and window */
-static int control_apply(MLIS_Ctx* S, int w_img, int h_img)
+/* rect (NULL: none, the behaviour of every pass but a masked inpaint's): x0, y0, x1, y1 of a W x H picture that the control image is taken to cover; the image is
+ * first cropped (mlsd_window_gather) to the rectangle scaled to its own size, floor(x0 Wc / W) .. ceil(x1 Wc / W) and likewise in y, then treated as ever.  An
+ * engine does not keep a cropped image for its next pass. */
+static int control_apply(MLIS_Ctx* S, int w_img, int h_img, const int* rect, int W, int H)
 {
 	if (str_empty(S->path_control)) return 1;
 	/* the engine has one pixel size: it still holds this very image, resampled, preprocessed and through the hint plan, unless the option was set again since, the
 	 * downscale_filter, the control_preprocess or a canny_* option changed (each counts control_image_gen on) or the tiling changed the edges (another engine) */
-	if (mlis_amd_control_tag(S->eng) == S->control_image_gen)
+	if (!rect && mlis_amd_control_tag(S->eng) == S->control_image_gen)
 		return mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0 ? api_error_lib(S, MLIS_E_UNKNOWN) : 1;
 	const MLIS_Tensor *src = &S->control_image;
-	const int sw = src->n[0], sh = src->n[1];
-	const size_t n_src = (size_t)3 * sw * sh, n_dst = (size_t)3 * w_img * h_img;
+	const int Wc = src->n[0], Hc = src->n[1];
+	int cx0 = 0, cy0 = 0, sw = Wc, sh = Hc;
+	if (rect) {
+		cx0 = (int)((int64_t)rect[0] * Wc / W); cy0 = (int)((int64_t)rect[1] * Hc / H);
+		sw = (int)(((int64_t)rect[2] * Wc + W - 1) / W) - cx0; sh = (int)(((int64_t)rect[3] * Hc + H - 1) / H) - cy0;
+	}
+	const size_t n_full = (size_t)3 * Wc * Hc, n_src = (size_t)3 * sw * sh, n_dst = (size_t)3 * w_img * h_img;
 	const int aa = S->downscale_filter && (w_img < sw || h_img < sh);
 	const int pre = S->control_preprocess;
-	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL, *d_pre = NULL;
+	void *d_full = NULL, *d_src = NULL, *d_dst = NULL, *d_ws = NULL, *d_pre = NULL;
 	int r = 1;
-	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || (pre && mlsd_malloc(&d_pre, n_dst * 4)) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || (pre && mlsd_malloc(&d_pre, n_dst * 4))
+			|| (rect ? (mlsd_malloc(&d_full, n_full * 4) || mlsd_memcpy(d_full, src->d, n_full * 4, 0, NULL)
+					|| mlsd_window_gather((const float*)d_full, Wc, Hc, (float*)d_src, sw, sh, cx0, cy0, 3, NULL))
+				: mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL))
 			|| (aa ? (mlsd_malloc(&d_ws, mlsd_resample2d_aa_ws_bytes(sw, sh, w_img, h_img, 3, S->downscale_filter - 1))
 					|| mlsd_resample2d_aa((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, S->downscale_filter - 1, S->tiling, d_ws, NULL))
 				: mlsd_resample2d((const float*)d_src, sw, sh, (float*)d_dst, w_img, h_img, 3, MLIS_AMD_RESAMPLE_BILINEAR, S->tiling, NULL))
@@ -1125,7 +1169,8 @@ static int control_apply(MLIS_Ctx* S, int w_img, int h_img)
 			|| mlis_amd_set_control_image_device(S->eng, pre ? d_pre : d_dst) < 0
 			|| mlis_amd_set_control(S->eng, S->control_strength, S->control_start, S->control_end) < 0)
 		r = api_error_lib(S, MLIS_E_UNKNOWN);
-	if (r > 0) mlis_amd_control_tag_set(S->eng, S->control_image_gen);
+	if (r > 0) mlis_amd_control_tag_set(S->eng, rect ? 0 : S->control_image_gen);      /* (0 is no image's mark: the next pass takes the image again) */
+	if (d_full) mlsd_free(d_full);
 	if (d_src) mlsd_free(d_src);
 	if (d_dst) mlsd_free(d_dst);
 	if (d_ws) mlsd_free(d_ws);
@@ -1523,6 +1568,163 @@ MLB_API int mlis_amd_tensor_canny(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tens
 	return r;
 }
 
+/* ------------------------------------------------------------------ region inpainting, piece by piece (hip/inpaint.hip) */
+/* each: host tensor -> device, one mlsd_ call, -> host tensor; src may be dst (it is on the device before dst is resized) */
+enum { MASK_OP_WEIGHT, MASK_OP_GROW, MASK_OP_BLUR };
+static int tensor_mask_op(MLIS_Ctx* S, int op, const MLIS_Tensor* src, MLIS_Tensor* dst, int iarg, float farg, int wrap)
+{
+	static const char* const names[] = { "mask_weight", "mask_grow", "gauss_blur" };
+	if (!src || !dst || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || src->n[2] < 1 || src->n[3] < 1 || mlis_tensor_count(src) >= ((size_t)1 << 31)
+			|| (op == MASK_OP_GROW && (src->n[2] != 1 || src->n[3] != 1)))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor for %s%s", names[op], op == MASK_OP_GROW ? " (one plane)" : "");
+	if ((wrap & ~3) || (op == MASK_OP_WEIGHT && (iarg & ~1)) || (op == MASK_OP_GROW && (iarg < -MLSD_MASK_GROW_MAX || iarg > MLSD_MASK_GROW_MAX))
+			|| (op == MASK_OP_BLUR && !(farg >= 0 && farg <= MLSD_GAUSS_MAX_SIGMA)))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid %s arguments: %d, %g, wrap %d", names[op], iarg, farg, wrap);
+	const int w = src->n[0], h = src->n[1], c = src->n[2], b = src->n[3];
+	const size_t n = mlis_tensor_count(src);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_dst = NULL, *d_ws = NULL;
+	if (mlsd_malloc(&d_src, n * 4) || mlsd_malloc(&d_dst, n * 4) || mlsd_memcpy(d_src, src->d, n * 4, 0, NULL)
+			|| (op == MASK_OP_WEIGHT && mlsd_mask_weight((const float*)d_src, (float*)d_dst, (int64_t)n, iarg, NULL))
+			|| (op == MASK_OP_GROW && (mlsd_malloc(&d_ws, n * 4) || mlsd_mask_grow((const float*)d_src, (float*)d_dst, w, h, iarg, wrap, d_ws, NULL)))
+			|| (op == MASK_OP_BLUR && (mlsd_malloc(&d_ws, mlsd_gauss_blur_ws_bytes(w, h, c * b)) || mlsd_gauss_blur((const float*)d_src, (float*)d_dst, w, h, c * b, farg, wrap, d_ws, NULL))))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, w, h, c, b);
+		if (mlsd_memcpy(dst->d, d_dst, n * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	if (d_ws) mlsd_free(d_ws);
+	return r;
+}
+
+static int tensor_mask_bbox(MLIS_Ctx* S, const MLIS_Tensor* src, int bbox[4])
+{
+	if (!src || !bbox || !tensor_good(src) || src->n[0] < 1 || src->n[1] < 1 || src->n[2] != 1 || src->n[3] != 1 || mlis_tensor_count(src) >= ((size_t)1 << 31))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor for mask_bbox (one plane)");
+	const size_t n = mlis_tensor_count(src);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_box = NULL;
+	if (mlsd_malloc(&d_src, n * 4) || mlsd_malloc(&d_box, 4 * sizeof(int)) || mlsd_memcpy(d_src, src->d, n * 4, 0, NULL)
+			|| mlsd_mask_bbox((const float*)d_src, src->n[0], src->n[1], (int*)d_box, NULL) || mlsd_memcpy(bbox, d_box, 4 * sizeof(int), 1, NULL) || mlsd_device_sync())
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (d_src) mlsd_free(d_src);
+	if (d_box) mlsd_free(d_box);
+	return r;
+}
+
+/* dst may be orig or patch: all three inputs are on the device before dst is resized */
+static int tensor_composite(MLIS_Ctx* S, MLIS_Tensor* dst, const MLIS_Tensor* orig, const MLIS_Tensor* patch, const MLIS_Tensor* p, int x0, int y0)
+{
+	if (!dst || !orig || !patch || !p || !tensor_good(orig) || !tensor_good(patch) || !tensor_good(p))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor for composite");
+	const int W = orig->n[0], H = orig->n[1], c = orig->n[2], B = patch->n[3], cw = patch->n[0], ch = patch->n[1];
+	if (W < 1 || H < 1 || c < 1 || B < 1 || patch->n[2] != c || (orig->n[3] != 1 && orig->n[3] != B) || p->n[0] != W || p->n[1] != H || p->n[2] != 1 || p->n[3] != 1
+			|| (double)W * H * c * B >= 2147483648.0)
+		return api_error(S, MLIS_E_OPT_VALUE, "composite: orig %dx%dx%dx%d, patch %dx%dx%dx%d and p %dx%dx%dx%d do not fit together", orig->n[0], orig->n[1], orig->n[2], orig->n[3],
+			patch->n[0], patch->n[1], patch->n[2], patch->n[3], p->n[0], p->n[1], p->n[2], p->n[3]);
+	if (cw < 1 || ch < 1 || x0 < 0 || y0 < 0 || cw > W - x0 || ch > H - y0)
+		return api_error(S, MLIS_E_OPT_VALUE, "composite: a patch of %dx%d at (%d, %d) does not lie inside the %dx%d image", cw, ch, x0, y0, W, H);
+	const int n_orig = orig->n[3];
+	const size_t n_dst = (size_t)W * H * c * B, n_o = (size_t)W * H * c * n_orig, n_patch = mlis_tensor_count(patch), n_p = (size_t)W * H;
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_dst = NULL, *d_orig = NULL, *d_patch = NULL, *d_p = NULL;
+	if (mlsd_malloc(&d_dst, n_dst * 4) || mlsd_malloc(&d_orig, n_o * 4) || mlsd_malloc(&d_patch, n_patch * 4) || mlsd_malloc(&d_p, n_p * 4)
+			|| mlsd_memcpy(d_orig, orig->d, n_o * 4, 0, NULL) || mlsd_memcpy(d_patch, patch->d, n_patch * 4, 0, NULL) || mlsd_memcpy(d_p, p->d, n_p * 4, 0, NULL)
+			|| mlsd_composite((float*)d_dst, (const float*)d_orig, n_orig, (const float*)d_patch, (const float*)d_p, W, H, c, B, x0, y0, cw, ch, NULL))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, W, H, c, B);
+		if (mlsd_memcpy(dst->d, d_dst, n_dst * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_dst) mlsd_free(d_dst);
+	if (d_orig) mlsd_free(d_orig);
+	if (d_patch) mlsd_free(d_patch);
+	if (d_p) mlsd_free(d_p);
+	return r;
+}
+
+/* dst = the cw x ch window of every plane of src at (x0, y0), inside the image (mlsd_window_gather); src may be dst */
+static int tensor_crop(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int x0, int y0, int cw, int ch)
+{
+	const int W = src->n[0], H = src->n[1], c = src->n[2], b = src->n[3];
+	if (cw < 1 || ch < 1 || x0 < 0 || y0 < 0 || cw > W - x0 || ch > H - y0) return api_error(S, MLIS_E_OPT_VALUE, "crop: %dx%d at (%d, %d) of a %dx%d image", cw, ch, x0, y0, W, H);
+	const size_t n_src = mlis_tensor_count(src), n_dst = (size_t)cw * ch * c * b;
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_src = NULL, *d_dst = NULL;
+	if (mlsd_malloc(&d_src, n_src * 4) || mlsd_malloc(&d_dst, n_dst * 4) || mlsd_memcpy(d_src, src->d, n_src * 4, 0, NULL)
+			|| mlsd_window_gather((const float*)d_src, W, H, (float*)d_dst, cw, ch, x0, y0, c * b, NULL))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, cw, ch, c, b);
+		if (mlsd_memcpy(dst->d, d_dst, n_dst * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_src) mlsd_free(d_src);
+	if (d_dst) mlsd_free(d_dst);
+	return r;
+}
+
+MLB_API int mlis_amd_tensor_mask_weight(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int invert)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_mask_op(S, MASK_OP_WEIGHT, src, dst, invert, 0, 0);
+}
+MLB_API int mlis_amd_tensor_mask_grow(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, int radius, int wrap)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_mask_op(S, MASK_OP_GROW, src, dst, radius, 0, wrap);
+}
+MLB_API int mlis_amd_tensor_gauss_blur(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst, float sigma, int wrap)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_mask_op(S, MASK_OP_BLUR, src, dst, 0, sigma, wrap);
+}
+MLB_API int mlis_amd_tensor_mask_bbox(MLIS_Ctx* S, const MLIS_Tensor* src, int bbox[4])
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_mask_bbox(S, src, bbox);
+}
+MLB_API int mlis_amd_tensor_composite(MLIS_Ctx* S, MLIS_Tensor* dst, const MLIS_Tensor* orig, const MLIS_Tensor* patch, const MLIS_Tensor* p, int x0, int y0)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_composite(S, dst, orig, patch, p, x0, y0);
+}
+
+/* the region rule (mlis_abi.h) */
+MLB_API int mlis_amd_inpaint_region(int W, int H, const int bbox[4], int padding, int tw, int th, int out[4])
+{
+	if (!bbox || !out || W < 1 || H < 1 || tw < 1 || th < 1 || padding < 0) return -1;
+	if (bbox[0] < 0 || bbox[1] < 0 || bbox[2] > W || bbox[3] > H || bbox[0] >= bbox[2] || bbox[1] >= bbox[3]) return -1;
+	int64_t x0 = (int64_t)bbox[0] - padding, y0 = (int64_t)bbox[1] - padding, x1 = (int64_t)bbox[2] + padding, y1 = (int64_t)bbox[3] + padding;
+	if (x0 < 0) x0 = 0;
+	if (y0 < 0) y0 = 0;
+	if (x1 > W) x1 = W;
+	if (y1 > H) y1 = H;
+	int64_t cw = x1 - x0, ch = y1 - y0;
+	if (cw * th < ch * tw) {
+		int64_t n = (ch * tw + th - 1) / th; if (n > W) n = W;
+		x0 -= (n - cw) / 2; cw = n;
+		if (x0 < 0) x0 = 0;
+		if (x0 + cw > W) x0 = W - cw;
+	} else {
+		int64_t n = (cw * th + tw - 1) / tw; if (n > H) n = H;
+		y0 -= (n - ch) / 2; ch = n;
+		if (y0 < 0) y0 = 0;
+		if (y0 + ch > H) y0 = H - ch;
+	}
+	out[0] = (int)x0; out[1] = (int)y0; out[2] = (int)(x0 + cw); out[3] = (int)(y0 + ch);
+	return 1;
+}
+
+MLB_API int mlis_amd_inpaint_info(MLIS_Ctx* S, int region[4], int proc[2])
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	for (int i=0; region && i<4; ++i) region[i] = S->inp_done ? S->inp_region[i] : 0;
+	for (int i=0; proc && i<2; ++i) proc[i] = S->inp_done ? S->inp_proc[i] : 0;
+	return S->inp_done;
+}
+
 /* ------------------------------------------------------------------ model upscaling (ESRGAN, host/upscaler.c) */
 /* the context's upscaler for the upscale_model option as it stands: built on first use, resident until the option changes */
 static int upscaler_get(MLIS_Ctx* S)
@@ -1620,6 +1822,13 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
 	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);
+	if (tensor_good(&S->lmask) && !hires_on(S)) {      /* region inpainting: the items that are set */
+		if (S->inpaint_area == MLIS_AMD_INPAINT_MASKED) ADD(", Inpaint area: masked, Padding: %d", S->inpaint_padding);
+		else if (S->inpaint_composite) ADD(", Inpaint area: whole, Composite: 1");
+		if (S->mask_blur > 0) ADD(", Mask blur: %g", S->mask_blur);
+		if (S->mask_grow) ADD(", Mask grow: %d", S->mask_grow);
+		if (S->mask_invert) ADD(", Mask invert: 1");
+	}
 	ADD(", Version: MLImgSynth v%s", MLIS_VERSION_STR);
 #undef ADD
 	free(S->infotext); S->infotext = strdup(buf);
@@ -1685,7 +1894,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 		if (mlis_amd_set_lmask(S->eng, S->lmask.d) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	} else { mlis_amd_set_lmask(S->eng, NULL); if (!(S->tuflags & MLIS_TUF_LMASK)) mlis_tensor_free(&S->lmask); }
 
-	if ((r = control_apply(S, w_img, h_img)) < 0) return r;
+	if ((r = control_apply(S, w_img, h_img, S->control_rect_on ? S->control_rect : NULL, S->control_rect_W, S->control_rect_H)) < 0) return r;
 	if (S->freeu && mlis_amd_set_freeu(S->eng, S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
@@ -1754,9 +1963,88 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 	return r;
 }
 
+/* region inpainting: any of the six options off its default */
+static int inpaint_on(const MLIS_Ctx* S)
+{
+	return S->inpaint_area != MLIS_AMD_INPAINT_WHOLE || S->inpaint_composite || S->mask_grow || S->mask_blur > 0 || S->mask_invert;
+}
+static int inpaint_composites(const MLIS_Ctx* S) { return S->inpaint_area == MLIS_AMD_INPAINT_MASKED || S->inpaint_composite; }
+
+/* what generate_inpaint refuses; before mlis_setup, so that none of them needs a model */
+static int inpaint_check(MLIS_Ctx* S)
+{
+	const int masked = S->inpaint_area == MLIS_AMD_INPAINT_MASKED;
+	if (masked && S->tiling) return api_error(S, MLIS_E_OPT_VALUE, "inpaint_area masked cannot be combined with tiling '%s': a crop is not periodic", k_tiling[S->tiling]);
+	if (inpaint_composites(S)) {
+		const char *what = masked ? "inpaint_area masked" : "inpaint_composite";
+		if (!(S->tuflags & MLIS_TUF_IMAGE) || !(S->tuflags & MLIS_TUF_MASK) || !tensor_good(&S->image) || !tensor_good(&S->mask))
+			return api_error(S, MLIS_E_OPT_VALUE, "%s needs an input image (image) and a mask (image_mask)", what);
+		if (S->flags & CF_NO_DECODE) return api_error(S, MLIS_E_OPT_VALUE, "%s cannot be combined with no_decode: the composite is made of decoded images", what);
+	}
+	if ((S->tuflags & MLIS_TUF_MASK) && (S->tuflags & MLIS_TUF_IMAGE) && tensor_good(&S->mask) && tensor_good(&S->image)
+			&& (S->mask.n[0] != S->image.n[0] || S->mask.n[1] != S->image.n[1]))
+		return api_error(S, MLIS_E_IMAGE, "the mask %dx%d does not match the image %dx%d", S->mask.n[0], S->mask.n[1], S->image.n[0], S->image.n[1]);
+	return 1;
+}
+
+/* the resample of a masked pass, to the processing size and back: antialiased with the downscale_filter where that is set and an axis shrinks, else plain in `mode`
+ * -- the choice of the hires model path */
+static int inpaint_resample(MLIS_Ctx* S, MLIS_Tensor* t, int w, int h, int mode)
+{
+	if (S->downscale_filter && (w < t->n[0] || h < t->n[1])) return tensor_resample_aa(S, t, t, w, h, S->downscale_filter - 1);
+	return tensor_resample(S, t, t, w, h, mode);
+}
+
+/* region inpainting around generate_pass -- what a caller gets from the public calls in this order: mlis_amd_tensor_mask_weight, _mask_grow, _gauss_blur (p),
+ * _mask_bbox, mlis_amd_inpaint_region, a crop of the image and of 1 - p, mlis_amd_tensor_resample (or _resample_aa) of both to IMAGE_DIM, mlis_generate with image and
+ * mask, a resample back, mlis_amd_tensor_composite into the untouched image.  With inpaint_area whole the pass runs on the whole image with 1 - p as its mask and,
+ * with inpaint_composite, its decoded images are composited over the input through p.  Without a mask there is nothing to process: the plain pass. */
+static int generate_inpaint(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
+{
+	if (!(S->tuflags & MLIS_TUF_MASK) || !tensor_good(&S->mask)) return generate_pass(S, decode, pw_img, ph_img);
+	const int masked = S->inpaint_area == MLIS_AMD_INPAINT_MASKED, composite = inpaint_composites(S);
+	const int W = S->mask.n[0], H = S->mask.n[1];
+	if (S->mask.n[2] != 1 || S->mask.n[3] != 1) return api_error(S, MLIS_E_IMAGE, "the mask must be one plane");
+	MLIS_Tensor p = {0}, orig = {0};
+	int r, box[4] = {0}, reg[4] = { 0, 0, W, H };
+	if ((r = tensor_mask_op(S, MASK_OP_WEIGHT, &S->mask, &p, S->mask_invert, 0, 0)) < 0) goto done;
+	if (S->mask_grow && (r = tensor_mask_op(S, MASK_OP_GROW, &p, &p, S->mask_grow, 0, S->tiling)) < 0) goto done;
+	if (S->mask_blur > 0 && (r = tensor_mask_op(S, MASK_OP_BLUR, &p, &p, 0, S->mask_blur, S->tiling)) < 0) goto done;
+	if ((r = tensor_mask_bbox(S, &p, box)) < 0) goto done;
+	if (box[2] <= box[0]) { r = api_error(S, MLIS_E_OPT_VALUE, "the mask leaves nothing to repaint (mask_invert %d, mask_grow %d)", S->mask_invert, S->mask_grow); goto done; }
+	for (size_t i=0, n=(size_t)W*H; i<n; ++i) S->mask.d[i] = 1.0f - p.d[i];      /* the pass's mask: 1 = keep */
+	if (composite) mlis_tensor_copy(&orig, &S->image);
+	if (masked) {
+		const int tw = S->width, th = S->height;
+		if (tw < 8 || th < 8 || tw % 8 || th % 8) { r = api_error(S, MLIS_E_OPT_VALUE, "inpaint_area masked: invalid processing size %dx%d (image_dim)", tw, th); goto done; }
+		if (mlis_amd_inpaint_region(W, H, box, S->inpaint_padding, tw, th, reg) < 0) { r = api_error(S, MLIS_E_UNKNOWN, "internal: inpaint region"); goto done; }
+		const int cw = reg[2] - reg[0], ch = reg[3] - reg[1];
+		const int mask_mode = S->hires_upscaler == MLIS_AMD_RESAMPLE_BICUBIC ? MLIS_AMD_RESAMPLE_BILINEAR : S->hires_upscaler;      /* the mask stays in 0 .. 1 */
+		if ((r = tensor_crop(S, &S->image, &S->image, reg[0], reg[1], cw, ch)) < 0 || (r = tensor_crop(S, &S->mask, &S->mask, reg[0], reg[1], cw, ch)) < 0
+				|| (r = inpaint_resample(S, &S->image, tw, th, S->hires_upscaler)) < 0 || (r = inpaint_resample(S, &S->mask, tw, th, mask_mode)) < 0) goto done;
+		S->control_rect_on = 1; memcpy(S->control_rect, reg, sizeof(reg)); S->control_rect_W = W; S->control_rect_H = H;
+		r = generate_pass(S, 1, pw_img, ph_img);
+		S->control_rect_on = 0;
+		if (r < 0) goto done;
+		if ((r = inpaint_resample(S, &S->image, cw, ch, S->hires_upscaler)) < 0) goto done;
+	} else if ((r = generate_pass(S, decode, pw_img, ph_img)) < 0) goto done;
+	if (composite) {
+		S->inp_proc[0] = *pw_img; S->inp_proc[1] = *ph_img;
+		if ((r = tensor_composite(S, &S->image, &orig, &S->image, &p, reg[0], reg[1])) < 0) goto done;
+		S->image.flags |= LT_F_READY;
+		memcpy(S->inp_region, reg, sizeof(reg)); S->inp_done = 1;
+		*pw_img = W; *ph_img = H;
+	}
+done:
+	mlis_tensor_free(&p); mlis_tensor_free(&orig);
+	return r;
+}
+
 MLB_API int mlis_generate(MLIS_Ctx* S)
 {
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	S->inp_done = 0;
+	if (inpaint_on(S)) { int c = inpaint_check(S); if (c < 0) return c; }
 	if (hires_on(S) && S->hires_use_model && str_empty(S->path_upscale))
 		return api_error(S, MLIS_E_OPT_VALUE, "hires_use_model is set but no upscale_model");
 	int r = mlis_setup(S); if (r < 0) return r;
@@ -1775,7 +2063,8 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	int w_img = 0, h_img = 0, hires_n_step = 0;
 	const int decode = !(S->flags & CF_NO_DECODE);
-	r = hires_on(S) ? generate_hires(S, decode, &w_img, &h_img, &hires_n_step) : generate_pass(S, decode, &w_img, &h_img);
+	r = hires_on(S) ? generate_hires(S, decode, &w_img, &h_img, &hires_n_step)      /* (it refuses image and mask inputs) */
+		: inpaint_on(S) ? generate_inpaint(S, decode, &w_img, &h_img) : generate_pass(S, decode, &w_img, &h_img);
 	if (r < 0) return r;
 	infotext_update(S, w_img, h_img, hires_n_step);
 	/* mlis_prompt_clear :692-709 */

@@ -252,6 +252,55 @@ def invert(src, dst, n, stream=None):
     check(lib().mlsd_invert(vp(src), vp(dst), c_i64(n), vp(stream)), "mlsd_invert")
 
 
+MASK_GROW_MAX, GAUSS_MAX_SIGMA, GAUSS_MAX_TAPS = 256, 64, 321
+
+
+def mask_weight(mask, p, n, invert, stream=None):
+    """mlsd_mask_weight: p[i] = clamp(invert ? mask[i] : 1 - mask[i], 0, 1) for n floats (device pointers); NaN gives 0"""
+    check(lib().mlsd_mask_weight(vp(mask), vp(p), c_i64(n), 1 if invert else 0, vp(stream)), "mlsd_mask_weight")
+
+
+def mask_grow(src, dst, w, h, radius, wrap, ws, stream=None):
+    """mlsd_mask_grow: one plane [h][w]; maximum (radius > 0) or minimum (radius < 0) over the (2 |radius| + 1)^2 square (device pointers; ws: w h floats)"""
+    check(lib().mlsd_mask_grow(vp(src), vp(dst), int(w), int(h), int(radius), int(wrap), vp(ws), vp(stream)), "mlsd_mask_grow")
+
+
+def gauss_taps(sigma, k_max=GAUSS_MAX_TAPS):
+    """mlsd_gauss_taps: the normalised float taps of sigma (2 int(2.5 sigma + 0.5) + 1 of them) as a list, or None when refused (host only)"""
+    w = (ctypes.c_float * max(int(k_max), 1))()
+    n = lib().mlsd_gauss_taps(ctypes.c_float(sigma), w, int(k_max))
+    return None if n < 0 else [w[i] for i in range(n)]
+
+
+def gauss_blur_ws_bytes(w, h, planes):
+    """mlsd_gauss_blur_ws_bytes: workspace of gauss_blur"""
+    f = lib().mlsd_gauss_blur_ws_bytes
+    f.restype = ctypes.c_size_t
+    return int(f(int(w), int(h), int(planes)))
+
+
+def gauss_blur(src, dst, w, h, planes, sigma, wrap, ws, stream=None):
+    """mlsd_gauss_blur: planes [planes][h][w] blurred with gauss_taps(sigma), rows then columns, fp32 sums in tap order (device pointers; ws: gauss_blur_ws_bytes)"""
+    check(lib().mlsd_gauss_blur(vp(src), vp(dst), int(w), int(h), int(planes), ctypes.c_float(sigma), int(wrap), vp(ws), vp(stream)), "mlsd_gauss_blur")
+
+
+def gauss_blur_lds_limit(nbytes=-1):
+    """mlsd_gauss_blur_lds_limit: set the LDS a row-pass tile may use (0 = always read global memory directly; negative only asks); returns the previous limit"""
+    return int(lib().mlsd_gauss_blur_lds_limit(int(nbytes)))
+
+
+def mask_bbox(p, w, h, out4, stream=None):
+    """mlsd_mask_bbox: out4 (4 ints, device) = x0, y0, x1, y1 (half open) of the pixels of p [h][w] with a value > 0; zeros if none"""
+    check(lib().mlsd_mask_bbox(vp(p), int(w), int(h), vp(out4), vp(stream)), "mlsd_mask_bbox")
+
+
+def composite(dst, orig, n_orig, patch, p, W, H, planes, B, x0, y0, cw, ch, stream=None):
+    """mlsd_composite: dst [B][planes][H][W] = orig outside the rectangle, orig (1 - p) + patch p inside (device pointers; orig of 1 or B images, patch
+    [B][planes][ch][cw], p [H][W]); dst may be orig when n_orig == B"""
+    check(lib().mlsd_composite(vp(dst), vp(orig), int(n_orig), vp(patch), vp(p), int(W), int(H), int(planes), int(B), int(x0), int(y0), int(cw), int(ch), vp(stream)),
+          "mlsd_composite")
+
+
 WINDOW_MAX_AXIS = 64
 
 

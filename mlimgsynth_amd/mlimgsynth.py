@@ -48,10 +48,13 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_CONTROL_STRENGTH=133, AMD_CONTROL_START=134, AMD_CONTROL_END=135, AMD_FREEU=141,
                                                                            AMD_FREEU_B1=142, AMD_FREEU_B2=143, AMD_FREEU_S1=144, AMD_FREEU_S2=145,
                                                                            AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161,
-                                                                           AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174))
+                                                                           AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174,
+                                                                           AMD_INPAINT_AREA=181, AMD_INPAINT_PADDING=182, AMD_MASK_BLUR=183, AMD_MASK_GROW=184,
+                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 _define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
 _define("MLIS_AMD_PREPROCESS_", ["NONE", "CANNY", "INVERT"])
+_define("MLIS_AMD_INPAINT_", ["WHOLE", "MASKED"])
 MLIS_CTEF_NO_NORM = 1
 
 
@@ -85,6 +88,12 @@ _PROTOTYPES = {
     "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_canny": (_I, [_V, _TP, _TP, _F, _F, _I, _I]),
+    "mlis_amd_tensor_mask_weight": (_I, [_V, _TP, _TP, _I]), "mlis_amd_tensor_mask_grow": (_I, [_V, _TP, _TP, _I, _I]),
+    "mlis_amd_tensor_gauss_blur": (_I, [_V, _TP, _TP, _F, _I]), "mlis_amd_tensor_mask_bbox": (_I, [_V, _TP, ctypes.POINTER(_I)]),
+    "mlis_amd_tensor_composite": (_I, [_V, _TP, _TP, _TP, _TP, _I, _I]),
+    "mlis_amd_inpaint_region": (_I, [_I, _I, ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(_I)]),
+    "mlis_amd_inpaint_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mlis_amd_prompt_tokens_set": (_I, [_V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_F), _I, _I]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
@@ -349,6 +358,64 @@ class MLImgSynth:
             raise RuntimeError("Failed to run canny: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
 
+    # ---- region inpainting
+    def inpaint_set(self, area=None, padding=None, mask_blur=None, mask_grow=None, invert=None, composite=None):
+        """Region inpainting: area = 'whole' | 'masked' (masked: only the padded, aspect-fitted bounding box of the repainted pixels is cropped, resampled to
+        IMAGE_DIM, inpainted and composited back into the untouched image, which may have any size); padding = pixels around the bounding box (0 .. 512, 32);
+        mask_blur = Gaussian sigma of the repaint weight (0 .. 64); mask_grow = pixels the repainted area grows (or shrinks, negative) by (-256 .. 256);
+        invert = True: the mask says white = repaint; composite = True: with area 'whole', paste the result over the input through the soft mask.  None
+        keeps a setting.  The options persist across generations; with all six at their defaults a generation is what it was without them."""
+        for name, v in (("inpaint_area", area), ("inpaint_padding", padding), ("mask_blur", mask_blur), ("mask_grow", mask_grow)):
+            if v is not None:
+                self.option_set(name, v)
+        if invert is not None:
+            self.option_set("mask_invert", 1 if invert else 0)
+        if composite is not None:
+            self.option_set("inpaint_composite", 1 if composite else 0)
+
+    def _mask_call(self, fn, what, tensor, *args):
+        tin = tensor._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if fn(self._ctx, ctypes.byref(tin), tout, *args) < 0:
+            raise RuntimeError("Failed to %s: %s" % (what, self.errstr_get()))
+        return MLIS_Tensor(tout.contents)
+
+    def mask_process(self, mask, grow=0, blur=0.0, invert=False, wrap=0):
+        """The repaint weight p of a mask on the GPU, as a generation with these options computes it: clamp(invert ? m : 1 - m, 0, 1), grown by `grow` pixels
+        (maximum over a square; negative shrinks), blurred with sigma `blur`.  mask: an MLIS_Tensor [1,1,h,w].  wrap: bit 0 columns, bit 1 rows wrap around."""
+        p = self._mask_call(self._lib.mlis_amd_tensor_mask_weight, "weigh the mask", mask, 1 if invert else 0)
+        if grow:
+            p = self._mask_call(self._lib.mlis_amd_tensor_mask_grow, "grow the mask", p, int(grow), int(wrap))
+        if blur > 0:
+            p = self._mask_call(self._lib.mlis_amd_tensor_gauss_blur, "blur the mask", p, float(blur), int(wrap))
+        return p
+
+    def gauss_blur(self, tensor, sigma, wrap=0):
+        "Gaussian blur of every plane of a tensor on the GPU (radius int(2.5 sigma + 0.5), border replicated or wrapped)."
+        return self._mask_call(self._lib.mlis_amd_tensor_gauss_blur, "blur the tensor", tensor, float(sigma), int(wrap))
+
+    def mask_bbox(self, p):
+        "(x0, y0, x1, y1), half open, of the pixels of p [1,1,h,w] with a value > 0; (0, 0, 0, 0) if there are none."
+        tin, box = p._c(), (_I * 4)()
+        if self._lib.mlis_amd_tensor_mask_bbox(self._ctx, ctypes.byref(tin), box) < 0:
+            raise RuntimeError("Failed to find the bounding box: %s" % self.errstr_get())
+        return tuple(int(v) for v in box)
+
+    def composite(self, orig, patch, p, x0=0, y0=0):
+        """orig [1 or n,c,H,W] with patch [n,c,ch,cw] pasted at (x0, y0) through the weight p [1,1,H,W]: orig (1 - p) + patch p inside the rectangle, orig
+        outside, in fp32 on the GPU.  Returns an MLIS_Tensor [n,c,H,W]."""
+        to, tp, tw = orig._c(), patch._c(), p._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_composite(self._ctx, tout, ctypes.byref(to), ctypes.byref(tp), ctypes.byref(tw), int(x0), int(y0)) < 0:
+            raise RuntimeError("Failed to composite: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
+
+    def inpaint_info(self):
+        "((x0, y0, x1, y1), (w, h)): the rectangle the last generation composited and the size its pass ran at; None if it composited nothing."
+        reg, proc = (_I * 4)(), (_I * 2)()
+        r = self._lib.mlis_amd_inpaint_info(self._ctx, reg, proc)
+        return (tuple(int(v) for v in reg), tuple(int(v) for v in proc)) if r > 0 else None
+
     # ---- FreeU
     def freeu_set(self, on=None, b1=None, b2=None, s1=None, s2=None):
         """FreeU (version 2): on = True / False; b1, b2 = backbone factors and s1, s2 = skip factors of stages 1 and 2, each in [0, 4] (1 = that part off).
@@ -418,4 +485,11 @@ def tensor_from_numpy(a):
     return t
 
 
-__all__ = [n for n in globals() if n.startswith("MLIS_") or n in ("MLImgSynth", "load_library", "tensor_from_numpy")]
+def inpaint_region(W, H, bbox, padding, tw, th):
+    """mlis_amd_inpaint_region: the rectangle (x0, y0, x1, y1) that inpaint_area masked processes for a bounding box in a W x H image, or None if refused."""
+    box, out = (_I * 4)(*[int(v) for v in bbox]), (_I * 4)()
+    r = load_library().mlis_amd_inpaint_region(int(W), int(H), box, int(padding), int(tw), int(th), out)
+    return tuple(int(v) for v in out) if r > 0 else None
+
+
+__all__ = [n for n in globals() if n.startswith("MLIS_") or n in ("MLImgSynth", "load_library", "tensor_from_numpy", "inpaint_region")]

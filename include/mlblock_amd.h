@@ -50,6 +50,11 @@ void   mlctx_set_wtype(MLCtx* C, int wtype);               /* linear weight type
                                                               * device storage and MFMA operands are always F16 */
 void   mlctx_set_conv_wrap(MLCtx* C, int mode);         /* circular padding of the convolutions built from now on (seamless tiling): 0 none, 1 columns (x),
                                                               * 2 rows (y), 3 both; a tap outside the image reads the pixel modulo the image size */
+void   mlctx_set_hypertile(MLCtx* C, int tile_px, int depth);   /* HyperTile for the spatial transformers built from now on: tile_px > 0 tiles the self-attention of
+                                                              * every level the rule of mlis_amd_hypertile_side cuts (UNet downscale ds, px_per_token = 8 ds) with
+                                                              * log2(ds) <= depth; 0: off, the plan is op for op the one without this call */
+/* what that rule did to the spatial transformers built so far: how many were tiled / left whole, and th, tw, nh, nw per depth 0..3 (zeros where the depth is not tiled) */
+int    mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, int tiles[4][4]);
 int    mlctx_prep(MLCtx* C);              /* resolve parameter names, finish the plan (result = last tensor) */
 int    mlctx_compute(MLCtx* C);           /* replay the plan on the context's stream (asynchronous) */
 int    mlctx_sync(MLCtx* C);
@@ -189,7 +194,7 @@ typedef struct mlb_temb_args { const float* t; int n, dim; float maxp; void* out
 typedef struct mlb_act_args { const float* x; void* y; size_t n; int act; } mlb_act_args;                                                                  /* mlsd_act_f32_to_f16 */
 typedef struct mlb_cemb_args { const int32_t* tok; int n, T, d; const void* tw; const float* pw; float* out; } mlb_cemb_args;                              /* mlsd_clip_embed */
 typedef struct mlb_smax_args { const float* in; int64_t ld_in; void* out; int64_t ld_out; int rows, cols; float scale; } mlb_smax_args;                    /* mlsd_softmax_rows */
-typedef struct mlb_copy_args { const void* src; void* dst; size_t nbytes; } mlb_copy_args;                                                                 /* device-to-device copy */
+typedef struct mlb_copy_args { const void* src; void* dst; size_t nbytes; int n_img, H, W, th, tw, row_bytes, inverse; } mlb_copy_args;                    /* device-to-device copy of nbytes; th > 0: mlsd_tile_permute of n_img maps of H x W rows of row_bytes (nbytes is still the whole extent) */
 typedef struct mlb_cadd_args { float* dst; int64_t ld_dst; const float* base; int64_t ld_base; const float* ctrl; int64_t ld_ctrl; int n_img, rows, C, n_ctrl; const float* gain; } mlb_cadd_args;   /* mlsd_ctrl_add: ctrl and gain are device memory of another plan / the engine */
 typedef struct mlb_freeu_args { float* dst; int64_t ld_dst; const float* src; int64_t ld_src; int n_img, H, W, C; float* ws; const float* f; } mlb_freeu_args;   /* mlsd_freeu_backbone (rows = H W) / mlsd_freeu_skip: ws is plan memory, f one float of the engine's device memory */
 typedef struct mlb_xavt_args { const void* v; int64_t ldv; int n_img, Tk, N; void* vt; } mlb_xavt_args;                                                    /* mlsd_xattn_pack_vt: V^T pack of a cross attention that ends its q projection */

@@ -351,9 +351,15 @@ typedef struct {
 	/* (`control` lies in what was the structure's tail padding: the Python mirror keeps the layout before it as engine.AmdConfig and adds engine.AmdControlConfig,
 	 * of the same size.  A field added after it grows the structure: both mirrors then have to follow, and the size equality tests/test_controlnet_cpu.py asserts goes) */
 	int control;             /* flags, MLIS_AMD_CONTROL_*.  bit 0 (_NET): the engine holds a ControlNet (hint plan, ControlNet plan, UNet plan with control inputs);
-	                          * bit 1 (_FREEU): the UNet plan runs the FreeU passes at its decoder concatenations (mlis_amd_set_freeu); 0: every plan as without this field */
+	                          * bit 1 (_FREEU): the UNet plan runs the FreeU passes at its decoder concatenations (mlis_amd_set_freeu);
+	                          * bit 2 (_HYPERTILE): HyperTile, with the tile in units of 8 px in bits 8..20 and the depth in bits 24..25 (MLIS_AMD_CONTROL_HYPERTILE_OF builds
+	                          * all three; mlis_amd_hypertile_info); 0: every plan as without this field */
 } MLIS_AmdConfig;
-enum { MLIS_AMD_CONTROL_NET = 1, MLIS_AMD_CONTROL_FREEU = 2 };
+enum { MLIS_AMD_CONTROL_NET = 1, MLIS_AMD_CONTROL_FREEU = 2, MLIS_AMD_CONTROL_HYPERTILE = 4 };
+/* the bits of `control` for HyperTile with a tile of tile_px pixels (32 .. 8192, a multiple of 8) down to UNet depth `depth` (0 .. 3); tile_px 0: no bits */
+#define MLIS_AMD_CONTROL_HYPERTILE_OF(tile_px, depth) ((tile_px) > 0 ? (MLIS_AMD_CONTROL_HYPERTILE | ((((tile_px) / 8) & 0x1FFF) << 8) | (((depth) & 3) << 24)) : 0)
+#define MLIS_AMD_CONTROL_HYPERTILE_PX(control)    ((((control) >> 8) & 0x1FFF) * 8)
+#define MLIS_AMD_CONTROL_HYPERTILE_DEPTH(control) (((control) >> 24) & 3)
 
 /* progress callback (MLIS_Callback, include/mlimgsynth.h:405): called after every COMPLETED step (the stream is
  * synchronised first); a negative return aborts the generation and is returned by mlis_amd_denoise/generate */
@@ -444,6 +450,24 @@ int mlis_amd_control_image_get(const MLIS_AmdCtx* S, float* host_dst, int* w, in
  * the channel-mean map is normalised, and the skip planes are filtered, over the window, as an untiled evaluation of that window would. */
 int mlis_amd_set_freeu(MLIS_AmdCtx* S, float b1, float b2, float s1, float s2);
 int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stage2);
+/* HyperTile (engines created with MLIS_AMD_CONTROL_HYPERTILE_OF(tile_px, depth) in MLIS_AmdConfig.control; not in the reference).  Inside a spatial transformer
+ * everything between proj_in and proj_out is per token except the self-attention, so the token rows are brought into tile-major order once at the block's entry and
+ * back once at its exit (mlsd_tile_permute on the fp16 operands of proj_in and proj_out), and every self-attention in between is the launch it always was with
+ * images x tiles batches of th tw tokens.  Cross-attention, convolutions, norms and Linear layers see what they saw.
+ * hypertile_side: the tile's side, in tokens, on an axis of `side` tokens at px_per_token image pixels per token (8 x the UNet downscale): with
+ * m = min(max(tile_px / px_per_token, 4), side) (integer division; the floor of 4 tokens keeps degenerate tiles out), the smallest divisor of side that is >= m.
+ * Pure, host.  A level of h x w tokens at downscale ds is TILED when (side(h), side(w)) != (h, w) and log2(ds) <= depth; a level that is not gets no ops at all.
+ * This is the published rule with its random choice among the divisors (swap_size) fixed to the first, written from memory: parity with the published code is not
+ * pinned by a test.  The rule is applied to the UNet plan's own size: tiled-diffusion engines apply it to their window, and the ControlNet's encoder copy follows it.
+ * hypertile_info: the UNet plan's spatial transformers that are tiled / not tiled, and th, tw, nh, nw for each depth 0..3 (zeros where the depth is not tiled);
+ * (0, all, zeros) for an engine without the flag.  Any of the three pointers may be NULL.  Returns 1.
+ * unet_hypertile_cuts: how many spatial transformers of a UNet plan of lw x lh latent pixels the setting tiles (pure, host; the walk of the plan builder, held to
+ * built plans by tests/test_hypertile_cpu.py); mlis_generate takes the plain engine under the plain key for a pass where it is 0.
+ * The permuted rows are the dense fp16 operands of proj_in and proj_out, whole 16-byte pieces: the channel counts of a spatial transformer are multiples of 32
+ * (its GroupNorm), so this always holds; a plan builder that asked for a tiled level on rows that are not is refused with an error, the level is not left whole. */
+int mlis_amd_hypertile_side(int side, int px_per_token, int tile_px);
+int unet_hypertile_cuts(const UnetParams* P, int lw, int lh, int tile_px, int depth);
+int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, int tiles[4][4]);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

@@ -115,8 +115,15 @@ typedef enum {
 	MLIS_OPT_AMD_MASK_BLUR = 183,          /* "mask_blur" (float sigma, 0 .. 64, default 0): the Gaussian blur of the repaint weight (mlis_amd_tensor_gauss_blur) */
 	MLIS_OPT_AMD_MASK_GROW = 184,          /* "mask_grow" (int pixels, -256 .. 256, default 0): the repainted area grows by so many pixels, or shrinks if negative */
 	MLIS_OPT_AMD_MASK_INVERT = 185,        /* "mask_invert" (int 0 / 1, default 0): the mask says 1 = repaint, the front ends' convention, not the reference's 1 = keep */
-	MLIS_OPT_AMD_INPAINT_COMPOSITE = 186   /* "inpaint_composite" (int 0 / 1, default 0): with inpaint_area whole, the decoded images are composited over the input image through
+	MLIS_OPT_AMD_INPAINT_COMPOSITE = 186,  /* "inpaint_composite" (int 0 / 1, default 0): with inpaint_area whole, the decoded images are composited over the input image through
 	                                        * p, so that pixels with p == 0 are the input's, exactly.  masked implies it */
+	/* HyperTile: every UNet (and ControlNet) self-attention is computed inside tiles of its token map; convolutions and cross-attention keep the whole picture.  No
+	 * weights, no training.  The tile of a level is chosen per axis by mlis_amd_hypertile_side (include/mlimgsynth_amd.h), per pass size: a pass whose levels all come
+	 * out as one tile (the 512 px first pass of a hires run with hypertile 512) runs the plain plan.  The rule is the published one with its random choice among the
+	 * divisors fixed to the first, as recalled when this was written; it could not be checked against the publication then.  Both are part of the engine key: engines
+	 * with different settings coexist in the two resident slots.  They persist across generations.  (A block of its own from 191.) */
+	MLIS_OPT_AMD_HYPERTILE = 191,          /* "hypertile" (int, pixels): 0 = off (default), else 32 .. 8192 and a multiple of 8: the tile's side in image pixels */
+	MLIS_OPT_AMD_HYPERTILE_DEPTH = 192     /* "hypertile_depth" (int 0 .. 3, default 3): the deepest UNet level (log2 of its downscale) that is tiled */
 } MLIS_Option;
 enum { MLIS_AMD_INPAINT_WHOLE = 0, MLIS_AMD_INPAINT_MASKED = 1 };
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };

@@ -590,6 +590,14 @@ int mlsd_freeu_backbone(float* dst, int64_t ld_dst, const float* src, int64_t ld
 int mlsd_freeu_skip(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, int n_img, int H, int W, int C, float* ws, const float* s_dev, void* stream);
 size_t mlsd_freeu_ws_bytes(int n_img, int H, int W, int C);
 int mlsd_freeu_depth(int n_terms);
+/* HyperTile's row permutation (csrc/hip/hypertile.hip; not in the reference).  src and dst are dense [n_img][H W] rows of row_bytes bytes each.  With nh = H / th,
+ * nw = W / tw:
+ *   inverse 0:  dst row ((img nh + ty) nw + tx) th tw + y tw + x  =  src row img H W + (ty th + y) W + tx tw + x    (image order -> tile-major order)
+ *   inverse 1:  the same map with the roles of the two sides swapped                                                (tile-major order -> image order)
+ *   so that every tile of th x tw tokens is a contiguous run of th tw rows.  Bytes are moved, nothing is computed: fp16 and fp32 rows alike, NaN payloads survive.
+ *   All offsets are 64-bit.  Refused with an error and no launch: th not dividing H or tw not dividing W, row_bytes not a multiple of 16, a pointer not 16-byte
+ *   aligned, src == dst or overlapping ranges (there is no in-place form), a count below 1. */
+int mlsd_tile_permute(const void* src, void* dst, int n_img, int H, int W, int th, int tw, int row_bytes, int inverse, void* stream);
 /* Dense-block convolution of the ESRGAN upscaler (csrc/hip/upscale.hip; not in the reference): 3x3, stride 1, zero padding 1, Cin in {32, 64, 96, 128, 160, 192} to N in
  * {32, 64} output channels over a channels-last fp16 image [n_img][H][W] with lda halfs between pixels (lda >= Cin: A may be a channel slice of a wider buffer; columns >= Cin
  * are never read).  upsample 1: the output is 2H x 2W and the taps read the nearest-2x upsampled image (folded into the gather, as mlsd_gemm_args.upsample).

@@ -99,6 +99,7 @@ struct MLIS_AmdCtx {
 	UnetFreeU fu;
 	float *d_freeu;             /* [4] b1, b2, s1, s2; all 1 (the plan's FreeU passes copy) until they are set */
 	float freeu_f[4];
+	int ht_px, ht_depth;        /* HyperTile (MLIS_AMD_CONTROL_HYPERTILE): tile in pixels (0: off) and deepest tiled level, given to the UNet and ControlNet plans before they are built */
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -280,7 +281,14 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (S->c.method > SOLVER_METHOD_DPMPP2S) { mlsd_set_error(-1, "invalid sampling method %d", S->c.method); goto err; }
 	if (!(S->c.f_t_ini > 0)) S->c.f_t_ini = 1;
 	if (!S->c.weight_seed) S->c.weight_seed = 1234;
-	if (S->c.control & ~(MLIS_AMD_CONTROL_NET | MLIS_AMD_CONTROL_FREEU)) { mlsd_set_error(-1, "control %d: bit 0 ControlNet, bit 1 FreeU", S->c.control); goto err; }
+	{	/* the bits of `control`: 0 ControlNet, 1 FreeU, 2 HyperTile with its tile (bits 8..20, units of 8 px) and depth (bits 24..25) */
+		const int ht = S->c.control & MLIS_AMD_CONTROL_HYPERTILE, ht_bits = (0x1FFF << 8) | (3 << 24), ht_px = MLIS_AMD_CONTROL_HYPERTILE_PX(S->c.control);
+		if (S->c.control & ~(MLIS_AMD_CONTROL_NET | MLIS_AMD_CONTROL_FREEU | MLIS_AMD_CONTROL_HYPERTILE | ht_bits) || (!ht && (S->c.control & ht_bits))) {
+			mlsd_set_error(-1, "control %d: bit 0 ControlNet, bit 1 FreeU, bit 2 HyperTile (tile / 8 in bits 8..20, depth in bits 24..25)", S->c.control); goto err;
+		}
+		if (ht && (ht_px < 32 || ht_px > 8192)) { mlsd_set_error(-1, "HyperTile tile of %d px: 32 .. 8192, a multiple of 8", ht_px); goto err; }
+		S->ht_px = ht ? ht_px : 0; S->ht_depth = ht ? MLIS_AMD_CONTROL_HYPERTILE_DEPTH(S->c.control) : 0;
+	}
 	S->ctl_strength = 1; S->ctl_start = 0; S->ctl_end = 1; S->ctl_step_on = 1;
 	if (unet_params_get(S->model, &S->unet_p) < 0) goto err;
 	if (vae_params_get(S->model, &S->vae_p) < 0) goto err;
@@ -325,6 +333,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 		if (!S->c.defer_weights && mlctx_params_synth(S->hint_ctx, S->c.weight_seed) < 0) goto err;
 		S->ctl_ctx = mlctx_new(stream);
 		mlctx_set_conv_wrap(S->ctl_ctx, unet_wrap);
+		mlctx_set_hypertile(S->ctl_ctx, S->ht_px, S->ht_depth);
 		if (S->c.use_hipgraph && S->c.unet_split <= 0) mlctx_set_flags(S->ctl_ctx, MLB_F_HIPGRAPH);      /* (its weights stay resident with unet_split too) */
 		if (controlnet_init_nc(&S->ctl, S->ctl_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
 		if (mlctx_input_bind(S->ctl.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
@@ -341,6 +350,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	/* ---- UNet plan, x bound to the resident evaluation point (c_in scaling + cond/uncond duplication in the gather) */
 	S->unet_ctx = mlctx_new(stream);
 	mlctx_set_conv_wrap(S->unet_ctx, unet_wrap);
+	mlctx_set_hypertile(S->unet_ctx, S->ht_px, S->ht_depth);
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
@@ -986,6 +996,13 @@ MLB_API int mlis_amd_control_info(const MLIS_AmdCtx* S, int* n_residuals, int* e
 	if (n_residuals) *n_residuals = S->ctl_ctx ? S->ctl.n_res : 0;
 	if (evals_controlled) *evals_controlled = S->ctl_evals;
 	return 1;
+}
+
+/* ------------------------------------------------------------------ HyperTile: what the rule did to the UNet plan (the plan was built with it: nothing to set) */
+MLB_API int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, int tiles[4][4])
+{
+	if (!S || !S->unet_ctx) return fail("mlis_amd_hypertile_info: no engine");
+	return mlctx_hypertile_info(S->unet_ctx, n_tiled, n_untiled, tiles);
 }
 
 /* ------------------------------------------------------------------ FreeU

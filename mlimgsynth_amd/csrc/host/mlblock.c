@@ -86,6 +86,7 @@ static void ctx_reset_(MLCtx* C)
 	memset(&C->kvb, 0, sizeof(C->kvb));
 	memset(&C->epb, 0, sizeof(C->epb));
 	memset(&C->info, 0, sizeof(C->info));
+	C->ht.nt = C->ht.n_tiled = C->ht.n_untiled = 0; memset(C->ht.tiles, 0, sizeof(C->ht.tiles));      /* (tile_px / depth are settings of the context, like conv_wrap) */
 }
 
 MLB_API void mlctx_destroy(MLCtx* C)
@@ -112,6 +113,15 @@ MLB_API void mlctx_set_tprefix(MLCtx* C, const char* p) { snprintf(C->tprefix, s
 MLB_API void mlctx_set_flags(MLCtx* C, int f) { C->flags = f; }
 MLB_API void mlctx_set_wtype(MLCtx* C, int t) { C->wtype = t; }
 MLB_API void mlctx_set_conv_wrap(MLCtx* C, int mode) { C->conv_wrap = mode & 3; }
+MLB_API void mlctx_set_hypertile(MLCtx* C, int tile_px, int depth) { C->ht.tile_px = tile_px > 0 ? tile_px : 0; C->ht.depth = depth < 0 ? 0 : depth > 3 ? 3 : depth; }
+MLB_API int mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, int tiles[4][4])
+{
+	if (!C) return -1;
+	if (n_tiled) *n_tiled = C->ht.n_tiled;
+	if (n_untiled) *n_untiled = C->ht.n_untiled;
+	if (tiles) memcpy(tiles, C->ht.tiles, sizeof(C->ht.tiles));
+	return 1;
+}
 MLB_API MLTensor* mlctx_result(MLCtx* C) { return C->result; }
 MLB_API int mlctx_sync(MLCtx* C) { return mlsd_stream_sync(C->stream) ? -1 : 1; }
 

@@ -110,6 +110,9 @@ struct MLCtx {
 	char tprefix[32];
 	int flags, wtype;
 	int conv_wrap;          /* mlctx_set_conv_wrap: mlsd_gemm_args.wrap of the convolutions built from now on */
+	/* HyperTile (mlctx_set_hypertile; mlb_spatial_transf of unet.c).  nt is set only while a tiled block's transformer layers are being built: mlb_attn_mhead_ex then
+	 * records a SELF-attention as nb x nt batches of Tq / nt tokens (the rows are in tile-major order between the block's two permuting copies); 0 elsewhere */
+	struct { int tile_px, depth, nt, n_tiled, n_untiled, tiles[4][4]; } ht;
 	int err;
 	/* plan */
 	MLOp* ops; int n_ops, cap_ops;

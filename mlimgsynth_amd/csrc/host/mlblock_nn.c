@@ -459,8 +459,12 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 		MLTensor *qkv = fused_proj(C, q, d_embed, bias, n_qkv, 3);
 		if (!qkv) return NULL;
 		const char *p = (const char*)mlt_need16(C, qkv);
+		/* HyperTile: between a tiled spatial transformer's two permuting copies every tile is a contiguous run of Tq / nt rows, so the self-attention per tile is this
+		 * launch with nb x nt batches (the batch strides are Tq / nt rows of the same buffers) */
+		const int nt = C->ht.nt > 0 ? C->ht.nt : 1;
+		if (Tq % nt) { mlctx_fail(C, "attention: %d tiles do not divide %d tokens", nt, Tq); return NULL; }
 		record_attn(C, p, 3*d_embed, p + (size_t)d_embed*2, 3*d_embed, p + (size_t)d_embed*4, 3*d_embed, a->d16, d_embed,
-			nb, Tq, Tk, n_head, d_head, mask, 0);
+			nb * nt, Tq / nt, Tk / nt, n_head, d_head, mask, 0);
 		mlb_release(C, qkv);
 	} else {
 		if (k != v) { mlctx_fail(C, "attention: k and v must share their input"); return NULL; }

@@ -44,7 +44,12 @@ static int run_smax(const MLOp* op, void* st)
 	const mlb_smax_args *a = &op->u.smax;
 	return mlsd_softmax_rows(a->in, a->ld_in, a->out, a->ld_out, a->rows, a->cols, a->scale, st);
 }
-static int run_copy(const MLOp* op, void* st) { return mlsd_memcpy(op->u.copy.dst, op->u.copy.src, op->u.copy.nbytes, 2, st); }
+static int run_copy(const MLOp* op, void* st)
+{
+	const mlb_copy_args *a = &op->u.copy;
+	if (a->th > 0) return mlsd_tile_permute(a->src, a->dst, a->n_img, a->H, a->W, a->th, a->tw, a->row_bytes, a->inverse, st);      /* HyperTile's row permutation */
+	return mlsd_memcpy(a->dst, a->src, a->nbytes, 2, st);
+}
 static int run_xavt(const MLOp* op, void* st)
 {
 	const mlb_xavt_args *a = &op->u.xavt;

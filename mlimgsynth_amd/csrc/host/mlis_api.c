@@ -58,6 +58,7 @@ struct MLIS_Ctx {
 	int inp_region[4], inp_proc[2], inp_done;
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
+	int hypertile, hypertile_depth;         /* MLIS_OPT_AMD_HYPERTILE*: tile in pixels (0 = off) and deepest tiled UNet level; both part of the engine key */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
 	int method, sched, n_step;
@@ -161,9 +162,11 @@ static const char* const k_downscale[] = { "none", "box", "bilinear", "bicubic",
 static const char* const k_option_amd8[] = { "control_preprocess", "canny_low", "canny_high", "canny_l2" };   /* ids from MLIS_OPT_AMD_CONTROL_PREPROCESS */
 static const char* const k_preprocess[] = { "none", "canny", "invert" };                                 /* MLIS_AMD_PREPROCESS_* */
 static const char* const k_option_amd9[] = { "inpaint_area", "inpaint_padding", "mask_blur", "mask_grow", "mask_invert", "inpaint_composite" };   /* ids from MLIS_OPT_AMD_INPAINT_AREA */
+static const char* const k_option_amd10[] = { "hypertile", "hypertile_depth" };                         /* ids from MLIS_OPT_AMD_HYPERTILE */
 static const char* const k_inpaint_area[] = { "whole", "masked" };                                       /* MLIS_AMD_INPAINT_* */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_HYPERTILE && x < MLIS_OPT_AMD_HYPERTILE + COUNTOF(k_option_amd10)) return k_option_amd10[x - MLIS_OPT_AMD_HYPERTILE];
 	if (x >= MLIS_OPT_AMD_INPAINT_AREA && x < MLIS_OPT_AMD_INPAINT_AREA + COUNTOF(k_option_amd9)) return k_option_amd9[x - MLIS_OPT_AMD_INPAINT_AREA];
 	if (x >= MLIS_OPT_AMD_CONTROL_PREPROCESS && x < MLIS_OPT_AMD_CONTROL_PREPROCESS + COUNTOF(k_option_amd8)) return k_option_amd8[x - MLIS_OPT_AMD_CONTROL_PREPROCESS];
 	if (x >= MLIS_OPT_AMD_DOWNSCALE_FILTER && x < MLIS_OPT_AMD_DOWNSCALE_FILTER + COUNTOF(k_option_amd7)) return k_option_amd7[x - MLIS_OPT_AMD_DOWNSCALE_FILTER];
@@ -195,6 +198,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i8 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_PREPROCESS + i8);
 	const int i9 = from_list(k_option_amd9, COUNTOF(k_option_amd9), 1, s, strlen(s));
 	if (i9 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_INPAINT_AREA + i9);
+	const int i10 = from_list(k_option_amd10, COUNTOF(k_option_amd10), 1, s, strlen(s));
+	if (i10 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_HYPERTILE + i10);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -257,6 +262,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
 	S->unet_tile_overlap = -1;
 	S->unet_tile_batch = 1;
+	S->hypertile = 0; S->hypertile_depth = 3;
 	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
 	S->canny_low = 100; S->canny_high = 200;
 	S->inpaint_padding = 32;
@@ -609,6 +615,8 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_UNET_TILE: if (!arg_int(A, 0, 65535, 0, &i) || i % 8) BAD_VALUE; S->unet_tile = i; break;     /* 0: off; the relation to the overlap is checked when an engine is needed (unet_tile_check) */
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: if (!arg_int(A, -1, 65535, -1, &i) || (i > 0 && i % 8)) BAD_VALUE; S->unet_tile_overlap = i; break;      /* -1: auto */
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
+	case MLIS_OPT_AMD_HYPERTILE: if (!arg_int(A, 0, 8192, 0, &i) || i % 8 || (i && i < 32)) BAD_VALUE; S->hypertile = i; break;      /* 0: off; the rule is applied per pass size (engine_get) */
+	case MLIS_OPT_AMD_HYPERTILE_DEPTH: if (!arg_int(A, 0, 3, 3, &i)) BAD_VALUE; S->hypertile_depth = i; break;
 	case MLIS_OPT_AMD_CONTROL_MODEL:       /* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
 		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
 		if (!S->path_control || strcmp(S->path_control, s)) { control_engines_drop(S); if (S->ts_control) { mlts_close(S->ts_control); S->ts_control = NULL; } }
@@ -754,6 +762,8 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_UNET_TILE: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile; } break;
 	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_overlap; } break;
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_batch; } break;
+	case MLIS_OPT_AMD_HYPERTILE: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile; } break;
+	case MLIS_OPT_AMD_HYPERTILE_DEPTH: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile_depth; } break;
 	case MLIS_OPT_AMD_CONTROL_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_control ? S->path_control : ""; } break;
 	case MLIS_OPT_AMD_CONTROL_IMAGE: { int *p = va_arg(ap, int*); if (p) *p = tensor_good(&S->control_image); } break;      /* whether one is set */
 	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
@@ -1178,6 +1188,16 @@ static int control_apply(MLIS_Ctx* S, int w_img, int h_img, const int* rect, int
 	return r;
 }
 
+/* HyperTile: a pass the rule does not touch (unet_hypertile_cuts, host/unet.c, beside the builder whose walk it repeats) takes the plain engine under the plain key:
+ * the 512 px first pass of a hires generation with hypertile 512 */
+static int hypertile_cuts(const char* model, int lw, int lh, int tile_px, int depth)
+{
+	UnetParams P;
+	if (tile_px <= 0) return 0;
+	if (unet_params_get(model, &P) < 0) return 1;
+	return unet_hypertile_cuts(&P, lw, lh, tile_px, depth);
+}
+
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
@@ -1191,7 +1211,11 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	const int control = !str_empty(S->path_control);      /* (one ControlNet per context: a changed file drops the engines, so the key only says whether) */
 	if (control && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/k1");
 	const int freeu = S->freeu != 0;                      /* (the factors are device data of the engine: only on / off is built in) */
-	if (freeu && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/f1");
+	if (freeu && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/f1");
+	/* (the UNet plan of a tiled pass has the size of one window: the rule sees that) */
+	const int plw = tile && tile / f < lw ? tile / f : lw, plh = tile && tile / f < lh ? tile / f : lh;
+	const int hypertile = hypertile_cuts(S->mname, plw, plh, S->hypertile, S->hypertile_depth) ? S->hypertile : 0;
+	if (hypertile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/h%dd%d", hypertile, S->hypertile_depth);
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	/* (a slot serves when its key matches AND it holds a ControlNet exactly if one is wanted: a key cut short by a long model name cannot pass one for the other) */
@@ -1214,7 +1238,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0);
+		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0) | MLIS_AMD_CONTROL_HYPERTILE_OF(hypertile, S->hypertile_depth);
 		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
@@ -1819,6 +1843,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 		ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", (int)(e - b), b, S->control_strength, S->control_start, S->control_end);
 	}
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
+	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
 	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);

@@ -51,9 +51,45 @@ static bool static_vector_in(const int* svec, int v)
 	return false;
 }
 
-/* src/unet.c:110-145.  Consumes nothing: x0 stays valid (it is the block's residual). */
+/* HyperTile's tile rule (include/mlimgsynth_amd.h): the smallest divisor of `side` that is at least min(max(tile_px / px_per_token, 4), side) */
+MLB_API int mlis_amd_hypertile_side(int side, int px_per_token, int tile_px)
+{
+	if (side < 1 || px_per_token < 1) return side;
+	int m = tile_px / px_per_token;
+	if (m < 4) m = 4;
+	if (m > side) m = side;
+	while (side % m) ++m;
+	return m;
+}
+
+/* one permuting copy of a tiled spatial transformer: the dense fp16 rows of `t` (n maps of h x w tokens) into a fresh fp16 tensor, image order -> tile-major order
+ * or back (mlsd_tile_permute).  It rides on the copy kind: nbytes is the whole extent, the geometry says how the rows move. */
+static MLTensor* mlb_tile_permute16(MLCtx* C, MLTensor* t, int th, int tw, int inverse)
+{
+	const void *src = mlt_need16(C, t);
+	if (!src) return NULL;
+	/* (cannot happen in a spatial transformer: both operands have d_embed or the block's channel count, a multiple of 32 by the GroupNorm in front of it, so their
+	 * fp16 rows are dense and whole 16-byte pieces; a builder that came here with anything else gets an error, not a silently untiled level) */
+	if (t->ld16 != t->c || (t->c * 2) % 16) { mlctx_fail(C, "hypertile: rows of %d halfs at stride %lld", t->c, (long long)t->ld16); return NULL; }
+	MLTensor *y = mlt_new(C, t->n, t->h, t->w, t->c);
+	y->sz16 = (size_t)t->n * t->h * t->w * t->c * 2;
+	y->d16 = mlctx_dalloc(C, y->sz16, 0); y->ld16 = t->c;
+	if (!y->d16) return NULL;
+	MLOp *op = mlctx_op_new(C, OP_COPY_F32, inverse ? "hypertile_untile" : "hypertile_tile");
+	mlb_copy_args *a = &op->u.copy;
+	a->src = src; a->dst = y->d16; a->nbytes = y->sz16;
+	a->n_img = t->n; a->H = t->h; a->W = t->w; a->th = th; a->tw = tw; a->row_bytes = t->c * 2; a->inverse = inverse;
+	return y;
+}
+
+/* src/unet.c:110-145.  Consumes nothing: x0 stays valid (it is the block's residual).
+ * ds is the UNet downscale of the level.  HyperTile (mlctx_set_hypertile): on a level the rule cuts, the token rows are in tile-major order from proj_in's A operand
+ * to proj_out's A operand, and every self-attention in between runs per tile (C->ht.nt).  The two copies sit on the fp16 operands, not on the fp32 token matrix:
+ * half the bytes, proj_in still ends with the first LayerNorm (that fold needs the LayerNorm right behind the GEMM that defines its input), and the GroupNorm
+ * statistics wiring sees the producers it saw (x0's producer before the block, proj_out behind it).  proj_in / proj_out are 1x1 convolutions: per token, so
+ * the order of the rows does not matter to them; the residual x0 and the block's output are in image order. */
 static MLTensor* mlb_spatial_transf(MLCtx* C, MLTensor* x, MLTensor* ctx,
-	int d_embed, int d_head, int n_head, int n_depth)
+	int d_embed, int d_head, int n_head, int n_depth, int ds)
 {
 	MLTensor *x0 = x;
 	char name[64];
@@ -62,16 +98,39 @@ static MLTensor* mlb_spatial_transf(MLCtx* C, MLTensor* x, MLTensor* ctx,
 	if (!n_head)  n_head  = d_embed / d_head;
 	if (!d_head)  d_head  = d_embed / n_head;
 	if (!d_embed) d_embed = d_head * n_head;
+	int th = x->h, tw = x->w, lvl = 0;
+	while ((1 << lvl) < ds) ++lvl;
+	if (C->ht.tile_px > 0 && lvl <= C->ht.depth && lvl < 4) {
+		th = mlis_amd_hypertile_side(x->h, 8 * ds, C->ht.tile_px);
+		tw = mlis_amd_hypertile_side(x->w, 8 * ds, C->ht.tile_px);
+	}
+	const int tiled = th != x->h || tw != x->w;
+	if (tiled) { C->ht.n_tiled++; int *q = C->ht.tiles[lvl]; q[0] = th; q[1] = tw; q[2] = x->h / th; q[3] = x->w / tw; }
+	else C->ht.n_untiled++;
 
 	MLTensor *h = MLN("norm", mlb_groupnorm_ex(C, x, 32, 1e-6f, 0, 0, NULL));
+	if (tiled && h) {
+		MLTensor *hp = mlb_tile_permute16(C, h, th, tw, 0);
+		if (!hp) return NULL;
+		mlb_release(C, h);
+		h = hp;
+	}
 	/* proj_in: 1x1 conv; its output IS the token matrix [N][h*w][d_embed] (no permute needed) */
 	x = MLN("proj_in", mlb_conv2d_ex(C, h, d_embed, 1, 1, 0, 0, T, NULL));
 	if (!x || !mlt_need32(C, x)) return NULL;
 	mlb_release(C, h);
+	if (tiled) C->ht.nt = (x0->h / th) * (x0->w / tw);
 	for (int i=0; i<n_depth; ++i) {
 		sprintf(name, "transf.%d", i);
 		x = MLN(name, mlb_basic_transf(C, x, ctx, d_embed, d_embed, n_head));   /* consumes x */
-		if (!x) return NULL;
+		if (!x) { C->ht.nt = 0; return NULL; }
+	}
+	C->ht.nt = 0;
+	if (tiled) {
+		MLTensor *xi = mlb_tile_permute16(C, x, th, tw, 1);
+		if (!xi) return NULL;
+		mlb_release(C, x);
+		x = xi;
 	}
 	MLEpilogue ep = {0}; ep.resid = x0;
 	MLTensor *y = MLN("proj_out", mlb_conv2d_ex(C, x, ch_in, 1, 1, 0, 0, T, &ep));
@@ -117,6 +176,20 @@ static int unet_cross_kv_width_ex(const UnetParams* P, int with_out)
 }
 
 static int unet_cross_kv_width(const UnetParams* P) { return unet_cross_kv_width_ex(P, 1); }
+
+/* HyperTile: the spatial transformers of a UNet plan of lw x lh latent pixels that mlb_spatial_transf would tile with this setting (same walk: a level's map is the
+ * ceil-half of the one above -- 3x3 stride-2 convolution, padding 1 --, n_res_blk encoder and n_res_blk + 1 decoder transformers on the levels of attn_res, the
+ * middle block's at the deepest level whatever that list says).  0: the plan is the plain plan.  tests/test_hypertile_cpu.py holds it to what built plans report. */
+MLB_API int unet_hypertile_cuts(const UnetParams* P, int lw, int lh, int tile_px, int depth)
+{
+	int n = 0;
+	if (tile_px <= 0) return 0;
+	for (int im=0, ds=1, w=lw, h=lh; P->ch_mult[im]; ++im, ds*=2, w=(w+1)/2, h=(h+1)/2) {
+		const int count = (static_vector_in(P->attn_res, ds) ? 2 * P->n_res_blk + 1 : 0) + (P->ch_mult[im+1] ? 0 : 1);
+		if (count && im <= depth && im < 4 && (mlis_amd_hypertile_side(h, 8 * ds, tile_px) != h || mlis_amd_hypertile_side(w, 8 * ds, tile_px) != w)) n += count;
+	}
+	return n;
+}
 
 /* total width of the resnets' time-embedding projections (same walk; every resnet projects emb to its ch_out) */
 static int unet_emb_proj_width_ex(const UnetParams* P, int with_out)
@@ -229,7 +302,7 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 			if (!x || !mlt_need32(C, x)) return NULL;
 			if (static_vector_in(P->attn_res, ds)) {
 				sprintf(name, "in.%d.1", i_blk);
-				MLTensor *y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+				MLTensor *y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
 				if (!y || !mlt_need32(C, y)) return NULL;
 				mlb_release(C, x);
 				x = y;
@@ -245,7 +318,7 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 		MLTensor *y = MLN("mid.0", mlb_resnet_ex(C, x, emb, ch));   /* x stays on the skip stack */
 		if (!y || !mlt_need32(C, y)) return NULL;
 		x = y;
-		y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+		y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
 		if (!y || !mlt_need32(C, y)) return NULL;
 		mlb_release(C, x); x = y;
 		y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));
@@ -295,7 +368,7 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 			x = y;
 			if (static_vector_in(P->attn_res, ds)) {
 				sprintf(name, "out.%d.%d", i_oblk, i_sub++);
-				y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+				y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
 				if (!y || !mlt_need32(C, y)) return NULL;
 				mlb_release(C, x); x = y;
 			}
@@ -569,7 +642,7 @@ MLB_API MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTenso
 			mlb_release(C, x); x = y;
 			if (static_vector_in(P->attn_res, ds)) {
 				sprintf(name, "in.%d.1", i_blk);
-				y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+				y = MLN(name, mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
 				if (!y || !mlt_need32(C, y)) return NULL;
 				mlb_release(C, x); x = y;
 			}
@@ -584,7 +657,7 @@ MLB_API MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTenso
 	MLTensor *y = MLN("mid.0", mlb_resnet_ex(C, x, emb, ch));
 	if (!y || !mlt_need32(C, y)) return NULL;
 	mlb_release(C, x); x = y;
-	y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im]));
+	y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
 	if (!y || !mlt_need32(C, y)) return NULL;
 	mlb_release(C, x); x = y;
 	y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));

@@ -91,7 +91,9 @@ class SmaxArgs(ctypes.Structure):
 
 
 class CopyArgs(ctypes.Structure):
-    _fields_ = [("src", vp), ("dst", vp), ("nbytes", ctypes.c_size_t)]
+    """mlb_copy_args: a device copy of nbytes; th > 0: the HyperTile row permutation (mlsd_tile_permute) of n_img maps of H x W rows of row_bytes"""
+    _fields_ = [("src", vp), ("dst", vp), ("nbytes", ctypes.c_size_t), ("n_img", c_int), ("H", c_int), ("W", c_int), ("th", c_int), ("tw", c_int),
+                ("row_bytes", c_int), ("inverse", c_int)]
 
 
 class CaddArgs(ctypes.Structure):
@@ -342,6 +344,12 @@ def ctrl_add(dst, ld_dst, base, ld_base, ctrl, ld_ctrl, n_img, rows_per_img, C, 
     memory).  gain == 0 copies base bit for bit without reading ctrl."""
     check(lib().mlsd_ctrl_add(vp(dst), c_i64(ld_dst), vp(base), c_i64(ld_base), vp(ctrl), c_i64(ld_ctrl), n_img, rows_per_img, C, n_ctrl_img, vp(gain_dev), vp(stream)),
           "mlsd_ctrl_add")
+
+
+def tile_permute(src, dst, n_img, H, W, th, tw, row_bytes, inverse=False, stream=None):
+    """mlsd_tile_permute: dense [n_img][H W] rows of row_bytes bytes from image order into tile-major order (tiles of th x tw rows), or back with inverse
+    (device pointers; 16-byte aligned, row_bytes a multiple of 16, no overlap)"""
+    check(lib().mlsd_tile_permute(vp(src), vp(dst), n_img, H, W, th, tw, row_bytes, 1 if inverse else 0, vp(stream)), "mlsd_tile_permute")
 
 
 def freeu_ws_bytes(n_img, H, W, C):

@@ -50,7 +50,7 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161,
                                                                            AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174,
                                                                            AMD_INPAINT_AREA=181, AMD_INPAINT_PADDING=182, AMD_MASK_BLUR=183, AMD_MASK_GROW=184,
-                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186))
+                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186, AMD_HYPERTILE=191, AMD_HYPERTILE_DEPTH=192))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 _define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
 _define("MLIS_AMD_PREPROCESS_", ["NONE", "CANNY", "INVERT"])
@@ -94,6 +94,7 @@ _PROTOTYPES = {
     "mlis_amd_inpaint_region": (_I, [_I, _I, ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(_I)]),
     "mlis_amd_inpaint_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_prompt_tokens_set": (_I, [_V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_F), _I, _I]),
+    "mlis_amd_engine_get": (_V, [_V]), "mlis_amd_hypertile_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
@@ -425,6 +426,26 @@ class MLImgSynth:
         for name, v in (("freeu_b1", b1), ("freeu_b2", b2), ("freeu_s1", s1), ("freeu_s2", s2)):
             if v is not None:
                 self.option_set(name, float(v))
+
+    # ---- HyperTile
+    def hypertile_set(self, tile=None, depth=None):
+        """HyperTile: tile = the tile's side in image pixels (0 = off, else 32 .. 8192 and a multiple of 8), depth = the deepest UNet level that is tiled
+        (0 .. 3).  None keeps a setting.  Both persist across generations and are built into the engine; the rule is applied per pass size."""
+        if tile is not None:
+            self.option_set("hypertile", int(tile))
+        if depth is not None:
+            self.option_set("hypertile_depth", int(depth))
+
+    def hypertile_info(self):
+        """(n_tiled, n_untiled, tiles) of the engine used last: its UNet's spatial transformers that are tiled / not, and (th, tw, nh, nw) per depth 0 .. 3
+        (zeros where the depth is not tiled); None before the first engine."""
+        e = self._lib.mlis_amd_engine_get(self._ctx)
+        if not e:
+            return None
+        a, b, t = _I(), _I(), (_I * 16)()
+        if self._lib.mlis_amd_hypertile_info(e, ctypes.byref(a), ctypes.byref(b), t) < 0:
+            raise RuntimeError("Failed to read the HyperTile plan: %s" % self.errstr_get())
+        return a.value, b.value, [tuple(int(t[4 * i + j]) for j in range(4)) for i in range(4)]
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

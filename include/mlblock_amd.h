@@ -55,6 +55,11 @@ void   mlctx_set_hypertile(MLCtx* C, int tile_px, int depth);   /* HyperTile for
                                                               * log2(ds) <= depth; 0: off, the plan is op for op the one without this call */
 /* what that rule did to the spatial transformers built so far: how many were tiled / left whole, and th, tw, nh, nw per depth 0..3 (zeros where the depth is not tiled) */
 int    mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, int tiles[4][4]);
+/* Perturbed-attention guidance: the last n_img images of the UNet plan built from now on are the PERTURBED group -- in the self-attentions of the middle block's
+ * spatial transformer their attention matrix is the identity (mlb_attn_mhead_ex); 0: off, the plan is op for op the one without this call.
+ * _info: the self-attentions recorded that way so far and the images of the group. */
+void   mlctx_set_pag(MLCtx* C, int n_img);
+int    mlctx_pag_info(const MLCtx* C, int* n_attn, int* n_img);
 int    mlctx_prep(MLCtx* C);              /* resolve parameter names, finish the plan (result = last tensor) */
 int    mlctx_compute(MLCtx* C);           /* replay the plan on the context's stream (asynchronous) */
 int    mlctx_sync(MLCtx* C);

@@ -353,9 +353,10 @@ typedef struct {
 	int control;             /* flags, MLIS_AMD_CONTROL_*.  bit 0 (_NET): the engine holds a ControlNet (hint plan, ControlNet plan, UNet plan with control inputs);
 	                          * bit 1 (_FREEU): the UNet plan runs the FreeU passes at its decoder concatenations (mlis_amd_set_freeu);
 	                          * bit 2 (_HYPERTILE): HyperTile, with the tile in units of 8 px in bits 8..20 and the depth in bits 24..25 (MLIS_AMD_CONTROL_HYPERTILE_OF builds
-	                          * all three; mlis_amd_hypertile_info); 0: every plan as without this field */
+	                          * all three; mlis_amd_hypertile_info); bit 3 (_PAG): perturbed-attention guidance, the UNet plan carries a third row group (mlis_amd_set_pag);
+	                          * 0: every plan as without this field */
 } MLIS_AmdConfig;
-enum { MLIS_AMD_CONTROL_NET = 1, MLIS_AMD_CONTROL_FREEU = 2, MLIS_AMD_CONTROL_HYPERTILE = 4 };
+enum { MLIS_AMD_CONTROL_NET = 1, MLIS_AMD_CONTROL_FREEU = 2, MLIS_AMD_CONTROL_HYPERTILE = 4, MLIS_AMD_CONTROL_PAG = 8 };
 /* the bits of `control` for HyperTile with a tile of tile_px pixels (32 .. 8192, a multiple of 8) down to UNet depth `depth` (0 .. 3); tile_px 0: no bits */
 #define MLIS_AMD_CONTROL_HYPERTILE_OF(tile_px, depth) ((tile_px) > 0 ? (MLIS_AMD_CONTROL_HYPERTILE | ((((tile_px) / 8) & 0x1FFF) << 8) | (((depth) & 3) << 24)) : 0)
 #define MLIS_AMD_CONTROL_HYPERTILE_PX(control)    ((((control) >> 8) & 0x1FFF) * 8)
@@ -468,6 +469,30 @@ int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stage2);
 int mlis_amd_hypertile_side(int side, int px_per_token, int tile_px);
 int unet_hypertile_cuts(const UnetParams* P, int lw, int lh, int tile_px, int depth);
 int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, int tiles[4][4]);
+/* Perturbed-attention guidance, PAG (engines created with MLIS_AMD_CONTROL_PAG in MLIS_AmdConfig.control; "Self-Rectifying Diffusion Sampling with
+ * Perturbed-Attention Guidance", 2024; not in the reference).  The rule, as recalled from the publication and the front ends that ship it -- parity with the published
+ * code is NOT pinned by a test, the rule below is:
+ *   - beside the cond (and, at cfg_scale > 1, uncond) evaluation the UNet is evaluated once more per image on the cond row's inputs (latent, timestep, context, label),
+ *     with softmax(q k^T) v replaced by v in the self-attentions (attn1) of the MIDDLE block's spatial transformer: attn1(x) = out_proj(v_proj(x)).  Cross-attention,
+ *     the feed-forwards and every other block are what they are;
+ *   - with c, u, p the cond, uncond and perturbed outputs (after the v-prediction rescale where the model has one): dx = g + pag_scale (c - p), g the plain mix
+ *     (c f + u (1 - f), or c at cfg_scale <= 1).  So it also guides where CFG does nothing.
+ * Here it is a third group of B rows in the one batched plan, not a second pass: an evaluation has mlis_amd_eval_rows(B, cfg_scale, pag) rows
+ * [cond B | uncond B (cfg_scale > 1) | perturbed B], every writer of the plan's inputs fills the last group with the cond group's values, and only mid.1 differs: its
+ * fused q|k|v projection and its attention launch cover the other groups, one more GEMM on the v_proj slice of the fused weight (no new parameter: checkpoints,
+ * LoRAs and weight streaming see what they saw) writes the perturbed group's rows of the buffer out_proj reads.  HyperTile keeps working (images are contiguous row
+ * runs in tile-major order too); the ControlNet's encoder copy is never perturbed, its plan holds the other groups and the UNet plan's sums hand the perturbed group
+ * the cond group's residuals; tiled and packed engines blend three groups (the mix is affine in eps).  An engine whose rows per plan evaluation exceed what a plain
+ * engine may hold (128) is refused at creation.
+ * set_pag: the scale, 0 .. 20, else an error; a field of the engine handed to the mix kernels (mlsd_dxdt_pag, mlsd_euler_pag_update) by value, so it changes between
+ * generations, and under use_hipgraph, without touching a plan.  Engines start at 0, where the flag alone computes what the plain mix does (the third group is
+ * evaluated and not read).  pag_info: the perturbed self-attentions of the UNet plan (0 without the flag) and the rows of one evaluation.
+ * Not included: layer selections other than the middle block; a step window or an adaptive scale (a plan is fixed: outside a window the perturbed rows would still be
+ * computed, and saving them needs a plain plan beside this one on one set of weights); guidance rescale; self-attention guidance. */
+#define MLIS_AMD_MAX_EVAL_ROWS 128        /* rows of one plan evaluation: what a plain engine of the largest batch holds (2 x 64) */
+int mlis_amd_eval_rows(int B, float cfg_scale, int pag);
+int mlis_amd_set_pag(MLIS_AmdCtx* S, float scale);
+int mlis_amd_pag_info(const MLIS_AmdCtx* S, int* n_attn, int* rows);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

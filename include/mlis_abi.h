@@ -123,7 +123,15 @@ typedef enum {
 	 * divisors fixed to the first, as recalled when this was written; it could not be checked against the publication then.  Both are part of the engine key: engines
 	 * with different settings coexist in the two resident slots.  They persist across generations.  (A block of its own from 191.) */
 	MLIS_OPT_AMD_HYPERTILE = 191,          /* "hypertile" (int, pixels): 0 = off (default), else 32 .. 8192 and a multiple of 8: the tile's side in image pixels */
-	MLIS_OPT_AMD_HYPERTILE_DEPTH = 192     /* "hypertile_depth" (int 0 .. 3, default 3): the deepest UNet level (log2 of its downscale) that is tiled */
+	MLIS_OPT_AMD_HYPERTILE_DEPTH = 192,    /* "hypertile_depth" (int 0 .. 3, default 3): the deepest UNet level (log2 of its downscale) that is tiled */
+	/* Perturbed-attention guidance (PAG): beside the cond and uncond evaluations the UNet is evaluated once more per image with the self-attentions of its middle block
+	 * replaced by the identity (softmax(q k^T) v -> v), and dx = cfg mix + pag_scale (cond - perturbed).  No weights, no training; it composes with CFG and also guides
+	 * at cfg_scale <= 1, where CFG does nothing (few-step distilled checkpoints).  The rule (include/mlimgsynth_amd.h) is written as recalled from the publication and the
+	 * front ends that ship it: parity with them is not pinned by a test.  pag_scale > 0 is part of the engine key as on / off: the engine's UNet plan carries a third row
+	 * group (about 1.5 x the work of a CFG evaluation, 2 x at cfg_scale <= 1); the value is a kernel argument and changes without building anything.  With 0 none of it
+	 * runs: the plain engine under the plain key.  A batch whose rows per evaluation the engine refuses (more than 128) is MLIS_E_OPT_VALUE at generation.  Not
+	 * included: other layer selections, a step window or adaptive scale, guidance rescale, self-attention guidance.  (A block of its own from 201.) */
+	MLIS_OPT_AMD_PAG_SCALE = 201           /* "pag_scale" (float 0 .. 20, default 0 = off; front ends default to 3 when it is switched on) */
 } MLIS_Option;
 enum { MLIS_AMD_INPAINT_WHOLE = 0, MLIS_AMD_INPAINT_MASKED = 1 };
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };

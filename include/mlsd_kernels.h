@@ -411,6 +411,19 @@ int mlsd_dxdt_cfg(const float* eps, int64_t ld, const float* x_eval, float* dx, 
  * x += (eps_c*f + eps_u*(1-f))*dt [+ noise*s_up]; same operation order as dxdt_cfg + vec_axpy + noise_add_s */
 int mlsd_euler_cfg_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float dt,
                           const float* noise, float s_up, void* stream);
+/* Perturbed-attention guidance (csrc/hip/guidance.hip; not in the reference): the mix of a plan with a third row group.  eps NHWC [N][HW][ld] with the groups
+ * [cond B | uncond B (only at cfg > 1) | perturbed B], so N = (cfg > 1 ? 2B : B) + B.  Per element, c, u, p after the v-prediction rescale:
+ *   g = the value mlsd_dxdt_cfg computes, by its very operations;  dx = fadd(g, fmul(pag, fsub(c, p))), each rounded once.
+ * pag == 0 takes mlsd_dxdt_cfg's path: the same bytes, and the perturbed rows are not read.  cfg and pag go by value (wave-uniform): they change between launches,
+ * and under a captured evaluation, without anything being rebuilt.  ld = 4 (the tiled canvas) and the plan's padded stride alike; 16-byte accesses where C == 4,
+ * ld % 4 == 0 and eps is 16-byte aligned (and on the NCHW side where HW % 4 == 0 and the planes are aligned), element by element elsewhere.
+ * Refused before any launch: a NULL buffer (x_eval may be NULL without vparam), B, C or HW below 1, ld < C, pag < 0 or NaN, 2^31 elements or more.
+ * euler_pag_update: the fused Euler(-ancestral) step with this mix (eps models: no rescale), x updated in place; operation order of mlsd_dxdt_pag + mlsd_vec_axpy +
+ * mlsd_noise_add_s, bit for bit (noise NULL: no third part). */
+int mlsd_dxdt_pag(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag,
+                  int vparam, float c_out, float c_skip, void* stream);
+int mlsd_euler_pag_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float dt,
+                          const float* noise, float s_up, void* stream);
 int mlsd_vec_axpy(float* out, const float* x, const float* d, float dt, int64_t n, void* stream);     /* out = x + d*dt (solvers.c:86,105,278) */
 int mlsd_solver_heun_corr(float* x, const float* dx, const float* d1, float dt, int64_t n, void* stream);   /* solvers.c:112-113 */
 int mlsd_solver_taylor3(float* x, const float* dx, float* dp1, float* dp2, float dt, float idtp, float f2, float f3,

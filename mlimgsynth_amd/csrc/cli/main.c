@@ -334,6 +334,7 @@ static const char k_usage[] =
 "             (with -i and --imask; masked: only the padded bounding box of the repainted pixels is processed, at -d, and pasted back; -i may have any size)\n"
 "FreeU:       --freeu BOOL  --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "HyperTile:   --hypertile PX   --hypertile-depth N   (self-attention inside tiles of PX image pixels, 32 .. 8192 in steps of 8, 0 = off; UNet levels 0 .. N <= 3)\n"
+"PAG:         --pag-scale F   (perturbed-attention guidance, 0 .. 20, 0 = off, 3 is the usual value; one more UNet row group per image)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";

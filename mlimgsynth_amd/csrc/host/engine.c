@@ -99,6 +99,11 @@ struct MLIS_AmdCtx {
 	UnetFreeU fu;
 	float *d_freeu;             /* [4] b1, b2, s1, s2; all 1 (the plan's FreeU passes copy) until they are set */
 	float freeu_f[4];
+	/* perturbed-attention guidance (MLIS_AMD_CONTROL_PAG): the UNet plan carries a third row group, [cond | uncond | perturbed] (mlis_amd_eval_rows), whose middle-block
+	 * self-attentions are the identity (mlctx_set_pag); dxdt_finish and the fused Euler step mix it in with pag_scale, a by-value kernel argument */
+	int pag;                    /* the flag */
+	float pag_scale;            /* 0 .. 20 (mlis_amd_set_pag); 0: the plain mix, the perturbed rows are computed and not read */
+	int CN;                     /* rows of the ControlNet plan: PN without the perturbed group (it is never perturbed; the UNet plan's sums hand that group the cond residuals) */
 	int ht_px, ht_depth;        /* HyperTile (MLIS_AMD_CONTROL_HYPERTILE): tile in pixels (0: off) and deepest tiled level, given to the UNet and ControlNet plans before they are built */
 };
 
@@ -159,6 +164,13 @@ static int ensure_steps(MLIS_AmdCtx* S, int ns)
 static int solver_nfe(int method)
 {	/* SolverClass.n_fe, src/solvers.c:90-296 */
 	return (method == SOLVER_METHOD_HEUN || method == SOLVER_METHOD_DPMPP2S) ? 2 : 1;
+}
+
+/* rows of one UNet evaluation for B images: [cond B | uncond B (cfg_scale > 1) | perturbed B (pag)].  Pure; -1 for B < 1 */
+MLB_API int mlis_amd_eval_rows(int B, float cfg_scale, int pag)
+{
+	if (B < 1) return -1;
+	return (cfg_scale > 1 ? 2 * B : B) + (pag ? B : 0);
 }
 
 MLB_API MLIS_AmdCtx* mlis_amd_create(const MLIS_AmdConfig* cfg, void* stream) { return mlis_amd_create_ex(cfg, 0, stream); }
@@ -281,11 +293,12 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (S->c.method > SOLVER_METHOD_DPMPP2S) { mlsd_set_error(-1, "invalid sampling method %d", S->c.method); goto err; }
 	if (!(S->c.f_t_ini > 0)) S->c.f_t_ini = 1;
 	if (!S->c.weight_seed) S->c.weight_seed = 1234;
-	{	/* the bits of `control`: 0 ControlNet, 1 FreeU, 2 HyperTile with its tile (bits 8..20, units of 8 px) and depth (bits 24..25) */
+	{	/* the bits of `control`: 0 ControlNet, 1 FreeU, 2 HyperTile with its tile (bits 8..20, units of 8 px) and depth (bits 24..25), 3 perturbed-attention guidance */
 		const int ht = S->c.control & MLIS_AMD_CONTROL_HYPERTILE, ht_bits = (0x1FFF << 8) | (3 << 24), ht_px = MLIS_AMD_CONTROL_HYPERTILE_PX(S->c.control);
-		if (S->c.control & ~(MLIS_AMD_CONTROL_NET | MLIS_AMD_CONTROL_FREEU | MLIS_AMD_CONTROL_HYPERTILE | ht_bits) || (!ht && (S->c.control & ht_bits))) {
-			mlsd_set_error(-1, "control %d: bit 0 ControlNet, bit 1 FreeU, bit 2 HyperTile (tile / 8 in bits 8..20, depth in bits 24..25)", S->c.control); goto err;
+		if (S->c.control & ~(MLIS_AMD_CONTROL_NET | MLIS_AMD_CONTROL_FREEU | MLIS_AMD_CONTROL_HYPERTILE | MLIS_AMD_CONTROL_PAG | ht_bits) || (!ht && (S->c.control & ht_bits))) {
+			mlsd_set_error(-1, "control %d: bit 0 ControlNet, bit 1 FreeU, bit 2 HyperTile (tile / 8 in bits 8..20, depth in bits 24..25), bit 3 PAG", S->c.control); goto err;
 		}
+		S->pag = (S->c.control & MLIS_AMD_CONTROL_PAG) != 0;
 		if (ht && (ht_px < 32 || ht_px > 8192)) { mlsd_set_error(-1, "HyperTile tile of %d px: 32 .. 8192, a multiple of 8", ht_px); goto err; }
 		S->ht_px = ht ? ht_px : 0; S->ht_depth = ht ? MLIS_AMD_CONTROL_HYPERTILE_DEPTH(S->c.control) : 0;
 	}
@@ -295,8 +308,10 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (S->c.width % 8 || S->c.height % 8 || S->c.width < 8 || S->c.height < 8) { fail("image size must be a multiple of 8"); goto err; }
 	S->lw = S->c.width / S->vae_p.f_down; S->lh = S->c.height / S->vae_p.f_down; S->hw = S->lw * S->lh;
 	S->B = S->c.n_batch;
-	S->N = S->c.cfg_scale > 1 ? 2*S->B : S->B;
+	S->N = mlis_amd_eval_rows(S->B, S->c.cfg_scale, S->pag);
 	S->PB = S->B; S->PN = S->N;
+	/* (a plain engine holds at most 2 x MAX_BATCH rows: the third group must fit under the same cap) */
+	if (S->N > MLIS_AMD_MAX_EVAL_ROWS) { mlsd_set_error(-1, "PAG: %d rows per evaluation (batch %d), at most %d", S->N, S->B, MLIS_AMD_MAX_EVAL_ROWS); goto err; }
 	const int B = S->B, ns = S->c.n_step;
 	const size_t lat_elems = (size_t)B * 4 * S->hw;
 
@@ -318,10 +333,12 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 		unet_wrap = S->tiling & ((ulw == S->lw ? 1 : 0) | (ulh == S->lh ? 2 : 0));
 		S->pack = mlis_amd_tile_pack(S->n_win, B, pack, &S->n_eval);
 		S->PB = S->pack * B; S->PN = S->pack * S->N;
+		if (S->PN > MLIS_AMD_MAX_EVAL_ROWS) { mlsd_set_error(-1, "PAG: %d rows per plan evaluation (%d windows of batch %d), at most %d", S->PN, S->pack, B, MLIS_AMD_MAX_EVAL_ROWS); goto err; }
 		mlsd_free(S->d_xin); S->d_xin = NULL;
 		if (mlsd_malloc((void**)&S->d_xin, (size_t)S->PB * 4 * ulw * ulh * 4)) goto err;
 	}
 	if (mlsd_malloc((void**)&S->d_cin, (size_t)S->PB*4)) goto err;
+	S->CN = S->PN - (S->pag ? S->PB : 0);
 
 	/* ---- ControlNet: the hint plan at the canvas's pixel size and the ControlNet plan on the UNet plan's inputs, both before the UNet plan, which takes the residuals' addresses */
 	if (S->c.control & MLIS_AMD_CONTROL_NET) {
@@ -335,7 +352,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 		mlctx_set_conv_wrap(S->ctl_ctx, unet_wrap);
 		mlctx_set_hypertile(S->ctl_ctx, S->ht_px, S->ht_depth);
 		if (S->c.use_hipgraph && S->c.unet_split <= 0) mlctx_set_flags(S->ctl_ctx, MLB_F_HIPGRAPH);      /* (its weights stay resident with unet_split too) */
-		if (controlnet_init_nc(&S->ctl, S->ctl_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
+		if (controlnet_init_nc(&S->ctl, S->ctl_ctx, &S->unet_p, ulw, ulh, S->CN, S->c.n_ctx_tok) < 0) goto err;
 		if (mlctx_input_bind(S->ctl.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
 		if (controlnet_build(&S->ctl) < 0) goto err;
 		if (!S->c.defer_weights && mlctx_params_synth(S->ctl_ctx, S->c.weight_seed) < 0) goto err;
@@ -351,6 +368,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	S->unet_ctx = mlctx_new(stream);
 	mlctx_set_conv_wrap(S->unet_ctx, unet_wrap);
 	mlctx_set_hypertile(S->unet_ctx, S->ht_px, S->ht_depth);
+	mlctx_set_pag(S->unet_ctx, S->pag ? S->PB : 0);
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
@@ -407,11 +425,13 @@ MLB_API int mlis_amd_set_callback(MLIS_AmdCtx* S, mlis_amd_progress_fn fn, void*
 	return 1;
 }
 
-static int fill_cond(MLIS_AmdCtx* S, MLTensor* t, const void* a, const void* b, size_t per_bytes, int kind)
-{	/* rows 0..PB-1 <- a (cond), rows PB..2PB-1 <- b (uncond); the shared prompt is replicated per image (of every window of a packed plan) */
+static int fill_cond(MLIS_AmdCtx* S, MLTensor* t, int rows, const void* a, const void* b, size_t per_bytes, int kind)
+{	/* rows 0..PB-1 <- a (cond), rows PB..2PB-1 <- b (uncond) when the plan has that group, and the perturbed group (the UNet plan of a PAG engine: its last PB of
+	 * `rows` rows) <- a again; the shared prompt is replicated per image (of every window of a packed plan) */
 	char *dst = (char*)mlctx_input_device_ptr(t);
-	for (int n=0; n<S->PN; ++n) {
-		const void *src = n < S->PB ? a : b;
+	const int p0 = S->pag && rows == S->PN ? rows - S->PB : rows;
+	for (int n=0; n<rows; ++n) {
+		const void *src = n < S->PB || n >= p0 ? a : b;
 		if (!src) return fail("missing (un)conditioning");
 		if (mlsd_memcpy(dst + (size_t)n*per_bytes, src, per_bytes, kind, S->stream)) return -1;
 	}
@@ -421,11 +441,11 @@ static int fill_cond(MLIS_AmdCtx* S, MLTensor* t, const void* a, const void* b, 
 static int set_cond(MLIS_AmdCtx* S, const void* cond, const void* label, const void* uncond, const void* unlabel, int kind)
 {
 	const UnetParams *P = &S->unet_p;
-	if (fill_cond(S, S->unet.t_c, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
-	if (P->ch_adm_in && fill_cond(S, S->unet.t_l, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
+	if (fill_cond(S, S->unet.t_c, S->PN, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
+	if (P->ch_adm_in && fill_cond(S, S->unet.t_l, S->PN, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
 	if (S->ctl_ctx) {      /* the ControlNet plan takes the same conditioning */
-		if (fill_cond(S, S->ctl.t_c, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
-		if (P->ch_adm_in && fill_cond(S, S->ctl.t_l, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
+		if (fill_cond(S, S->ctl.t_c, S->CN, cond, uncond, (size_t)S->c.n_ctx_tok*P->n_ctx*4, kind) < 0) return -1;
+		if (P->ch_adm_in && fill_cond(S, S->ctl.t_l, S->CN, label, unlabel, (size_t)P->ch_adm_in*4, kind) < 0) return -1;
 	}
 	if (mlsd_stream_sync(S->stream)) return -1;
 	S->cond_set = 1;
@@ -644,7 +664,7 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 	if (mlsd_fill2_f32(d_t_in, S->PN, t, S->d_cin, S->PB, c_in, st)) return -1;
 	/* ControlNet: the plan runs in front of the UNet plan when this evaluation is controlled; either way the UNet plan's sums read the gain written here */
 	const int ctl_on = S->ctl_ctx && S->ctl_image && S->ctl_strength > 0 && S->ctl_step_on;
-	if (S->ctl_ctx && mlsd_fill2_f32((float*)mlctx_input_device_ptr(S->ctl.t_t), S->PN, t, S->d_gain, 1, ctl_on ? S->ctl_strength : 0.f, st)) return -1;
+	if (S->ctl_ctx && mlsd_fill2_f32((float*)mlctx_input_device_ptr(S->ctl.t_t), S->CN, t, S->d_gain, 1, ctl_on ? S->ctl_strength : 0.f, st)) return -1;
 	if (ctl_on) S->ctl_evals++;
 	int64_t ld = 0;
 	const float *eps = mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, &ld);
@@ -668,12 +688,17 @@ static int unet_eval(MLIS_AmdCtx* S, const float* x_eval, float sigma, int prefe
 				const int nch = S->unet_p.n_ch;              /* (both row strides are n_ch: checked when the engine was created) */
 				const float *hs = mlctx_tensor_device_f32(S->hint_ctx, mlctx_result(S->hint_ctx), NULL);
 				float *hw_ = (float*)mlctx_tensor_device_f32(S->ctl_ctx, S->ctl.t_hint, NULL);
-				for (int q=0; q<N/B; ++q)
+				for (int q=0; q<S->CN/S->PB; ++q)
 					if (mlsd_window_gather_nhwc(hs, S->lw, S->lh, nch, hw_ + (size_t)q * P * B * whw * nch, S->win_w, S->win_h, xs, ys, P, B, st)) return -1;
 				if (mlctx_compute(S->ctl_ctx) < 0) return -1;
 			}
 			if (mlctx_compute(S->unet_ctx) < 0) return -1;
-			if (mlsd_window_blend_packed(eps, ld, S->d_eps_canvas, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, xs, ys, n_used, P, S->win_ox, S->win_oy, B, N / B, 4, st)) return -1;
+			/* (the blend takes one or two row groups: the third group of a PAG engine is a launch of its own, on that group's part of both buffers) */
+			for (int q=0; q<N/B; q+=2) {
+				const int nq = N/B - q < 2 ? N/B - q : 2;
+				if (mlsd_window_blend_packed(eps + (size_t)q * P * B * whw * ld, ld, S->d_eps_canvas + (size_t)q * B * S->hw * 4, S->d_wsum, S->lw, S->lh, S->win_w, S->win_h, xs, ys,
+						n_used, P, S->win_ox, S->win_oy, B, nq, 4, st)) return -1;
+			}
 			if (mlsd_count_nonfinite(eps, (size_t)S->PN*whw*ld, S->d_nan, st)) return -1;
 			if (g == 0 && prefetch_upto >= 0 && !noise_gen(S, prefetch_upto)) return -1;
 		}
@@ -707,6 +732,7 @@ static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* 
 	int64_t ld = 0;
 	const float *eps = eps_get(S, &ld);
 	const float c_skip = sigma / (sigma*sigma + 1), c_out = 1 / sqrt(sigma*sigma + 1);   /* unet.c:491-492 */
+	if (S->pag) return mlsd_dxdt_pag(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->pag_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 	return mlsd_dxdt_cfg(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 }
 
@@ -803,7 +829,8 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 				const float *eps = eps_get(S, &ld);
 				const float *nz = anc_noise ? noise_draw(S, S->k_draw) : NULL;
 				if (anc_noise && !nz) return -1;
-				if (mlsd_euler_cfg_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, t1 - t0, nz, s_up, st)) return -1;
+				if (S->pag ? mlsd_euler_pag_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, S->pag_scale, t1 - t0, nz, s_up, st)
+				           : mlsd_euler_cfg_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, t1 - t0, nz, s_up, st)) return -1;
 				if (nz) { S->k_draw++; s_up = -1; }                               /* noise already added */
 			} else {
 				if (dxdt_finish(S, S->d_x, t0, S->d_dx) < 0) return -1;
@@ -966,7 +993,7 @@ static int set_control_image(MLIS_AmdCtx* S, const float* hint, int kind)
 		const float *hs = mlctx_tensor_device_f32(S->hint_ctx, mlctx_result(S->hint_ctx), NULL);
 		float *hw_ = (float*)mlctx_tensor_device_f32(S->ctl_ctx, S->ctl.t_hint, NULL);
 		const int zero = 0;
-		if (mlsd_window_gather_nhwc(hs, S->lw, S->lh, S->unet_p.n_ch, hw_, S->lw, S->lh, &zero, &zero, 1, S->N, st)) return -1;
+		if (mlsd_window_gather_nhwc(hs, S->lw, S->lh, S->unet_p.n_ch, hw_, S->lw, S->lh, &zero, &zero, 1, S->CN, st)) return -1;
 	}
 	if (mlsd_stream_sync(st)) return -1;
 	S->ctl_image = 1;
@@ -1024,6 +1051,27 @@ MLB_API int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stag
 	if (!S) return -1;
 	if (n_stage1) *n_stage1 = S->d_freeu ? S->fu.n_stage1 : 0;
 	if (n_stage2) *n_stage2 = S->d_freeu ? S->fu.n_stage2 : 0;
+	return 1;
+}
+
+/* ------------------------------------------------------------------ perturbed-attention guidance
+ * the scale of the next evaluations: a field of the engine that dxdt_finish and the fused Euler step hand to their kernels by value.  Nothing is rebuilt or captured
+ * again (the mix is not part of the captured evaluation).  Tiled and packed engines need nothing more: the mix is affine in eps, so blending raw outputs stays exact. */
+MLB_API int mlis_amd_set_pag(MLIS_AmdCtx* S, float scale)
+{
+	if (!S || !S->pag) return fail("mlis_amd_set_pag: the engine was created without PAG");
+	if (!(scale >= 0 && scale <= 20)) return mlsd_set_error(-1, "PAG scale %g: 0 .. 20", scale);
+	S->pag_scale = scale;
+	return 1;
+}
+
+MLB_API int mlis_amd_pag_info(const MLIS_AmdCtx* S, int* n_attn, int* rows)
+{	/* the perturbed self-attentions of the UNet plan (0 without the flag) and the rows of one evaluation */
+	if (!S) return -1;
+	int n = 0;
+	if (S->pag && S->unet_ctx) mlctx_pag_info(S->unet_ctx, &n, NULL);
+	if (n_attn) *n_attn = n;
+	if (rows) *rows = S->N;
 	return 1;
 }
 

@@ -87,6 +87,7 @@ static void ctx_reset_(MLCtx* C)
 	memset(&C->epb, 0, sizeof(C->epb));
 	memset(&C->info, 0, sizeof(C->info));
 	C->ht.nt = C->ht.n_tiled = C->ht.n_untiled = 0; memset(C->ht.tiles, 0, sizeof(C->ht.tiles));      /* (tile_px / depth are settings of the context, like conv_wrap) */
+	C->pag.cur = C->pag.n_attn = 0;                                                                   /* (and so is pag.n_img) */
 }
 
 MLB_API void mlctx_destroy(MLCtx* C)
@@ -120,6 +121,14 @@ MLB_API int mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, i
 	if (n_tiled) *n_tiled = C->ht.n_tiled;
 	if (n_untiled) *n_untiled = C->ht.n_untiled;
 	if (tiles) memcpy(tiles, C->ht.tiles, sizeof(C->ht.tiles));
+	return 1;
+}
+MLB_API void mlctx_set_pag(MLCtx* C, int n_img) { C->pag.n_img = n_img > 0 ? n_img : 0; }
+MLB_API int mlctx_pag_info(const MLCtx* C, int* n_attn, int* n_img)
+{
+	if (!C) return -1;
+	if (n_attn) *n_attn = C->pag.n_attn;
+	if (n_img) *n_img = C->pag.n_img;
 	return 1;
 }
 MLB_API MLTensor* mlctx_result(MLCtx* C) { return C->result; }

@@ -113,6 +113,10 @@ struct MLCtx {
 	/* HyperTile (mlctx_set_hypertile; mlb_spatial_transf of unet.c).  nt is set only while a tiled block's transformer layers are being built: mlb_attn_mhead_ex then
 	 * records a SELF-attention as nb x nt batches of Tq / nt tokens (the rows are in tile-major order between the block's two permuting copies); 0 elsewhere */
 	struct { int tile_px, depth, nt, n_tiled, n_untiled, tiles[4][4]; } ht;
+	/* Perturbed-attention guidance (mlctx_set_pag; mlb_unet_denoise_freeu of unet.c).  n_img is the setting: the plan's last n_img images are the perturbed group.  cur is
+	 * set to it only while the middle block's transformer layers are being built: mlb_attn_mhead_ex then records a SELF-attention without the q, k projections and the
+	 * attention of those images, their attention output is v_proj of their rows (one more GEMM on the v slice of the fused weight); 0 elsewhere.  n_attn counts them */
+	struct { int n_img, cur, n_attn; } pag;
 	int err;
 	/* plan */
 	MLOp* ops; int n_ops, cap_ops;

@@ -389,8 +389,9 @@ static void record_attn(MLCtx* C, const void* q, int64_t ldq, const void* k, int
 }
 
 /* three (or two) projections sharing one input as ONE GEMM: parameters keep the reference's names
- * (q_proj/k_proj/v_proj .weight/.bias) but live in consecutive row blocks of one buffer */
-static MLTensor* fused_proj(MLCtx* C, MLTensor* x, int d_embed, bool bias, const char* const* names, int n_proj)
+ * (q_proj/k_proj/v_proj .weight/.bias) but live in consecutive row blocks of one buffer.  n_img: the launch covers the rows of the first n_img images of x only
+ * (x->n: all of them).  *w_out / *b_out (may be NULL): where the fused weight and bias lie, for a caller that records a launch on one slice of them */
+static MLTensor* fused_proj(MLCtx* C, MLTensor* x, int d_embed, bool bias, const char* const* names, int n_proj, int n_img, const char** w_out, const float** b_out)
 {
 	const int n_in = x->c;
 	const void *xd = mlt_need16(C, x);
@@ -404,10 +405,12 @@ static MLTensor* fused_proj(MLCtx* C, MLTensor* x, int d_embed, bool bias, const
 		if (bias) mlctx_param_new_at(C, "bias", MLT_F32, d_embed, 1, 1, 1, 0, bbase + (size_t)i * d_embed);
 		mlctx_named_op(C, names[i]);
 	}
-	MLTensor *y = mlt_new(C, x->n, x->h, x->w, n_proj * d_embed);
+	if (w_out) *w_out = wbase;
+	if (b_out) *b_out = bbase;
+	MLTensor *y = mlt_new(C, n_img, x->h, x->w, n_proj * d_embed);
 	MLOp *op = mlctx_op_new(C, OP_GEMM, "");
 	mlsd_gemm_args *g = &op->u.gemm;
-	g->A = xd; g->lda = x->ld16; g->W_ = wbase; g->ldb = n_in; g->M = (int)rows_of(x); g->N = n_proj * d_embed; g->K = n_in;
+	g->A = xd; g->lda = x->ld16; g->W_ = wbase; g->ldb = n_in; g->M = (int)rows_of(y); g->N = n_proj * d_embed; g->K = n_in;
 	g->bias = bbase;
 	op->flops = 2.0 * g->M * (double)g->N * n_in;
 	y->prod = C->n_ops - 1;
@@ -456,7 +459,13 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 	MLTensor *a = mlt_new(C, q->n, q->h, q->w, d_embed);
 	a->sz16 = (size_t)rows_of(q) * d_embed * 2; a->d16 = mlctx_dalloc(C, a->sz16, 0); a->ld16 = d_embed;
 	if (q == k && k == v) {
-		MLTensor *qkv = fused_proj(C, q, d_embed, bias, n_qkv, 3);
+		/* Perturbed-attention guidance (C->pag.cur: set while the middle block's layers are built): the last np images take v for softmax(q k^T) v, so the fused
+		 * projection and the attention cover the first nb - np images, and the rows of the last np images of the attention output are v_proj of their rows of the
+		 * same input -- one more GEMM on the v slice of the fused weight (no new parameter), written where out_proj, one launch over all nb images, reads */
+		const int np = C->pag.cur > 0 ? C->pag.cur : 0;
+		if (np >= nb) { mlctx_fail(C, "attention: %d perturbed images of %d", np, nb); return NULL; }
+		const char *wqkv = NULL; const float *bqkv = NULL;
+		MLTensor *qkv = fused_proj(C, q, d_embed, bias, n_qkv, 3, nb - np, &wqkv, &bqkv);
 		if (!qkv) return NULL;
 		const char *p = (const char*)mlt_need16(C, qkv);
 		/* HyperTile: between a tiled spatial transformer's two permuting copies every tile is a contiguous run of Tq / nt rows, so the self-attention per tile is this
@@ -464,8 +473,19 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 		const int nt = C->ht.nt > 0 ? C->ht.nt : 1;
 		if (Tq % nt) { mlctx_fail(C, "attention: %d tiles do not divide %d tokens", nt, Tq); return NULL; }
 		record_attn(C, p, 3*d_embed, p + (size_t)d_embed*2, 3*d_embed, p + (size_t)d_embed*4, 3*d_embed, a->d16, d_embed,
-			nb * nt, Tq / nt, Tk / nt, n_head, d_head, mask, 0);
+			(nb - np) * nt, Tq / nt, Tk / nt, n_head, d_head, mask, 0);
 		mlb_release(C, qkv);
+		if (np) {
+			const int64_t r0 = (int64_t)(nb - np) * Tq;                  /* (images are contiguous row runs in tile-major order too) */
+			MLOp *op = mlctx_op_new(C, OP_GEMM, "pag_v_proj");
+			mlsd_gemm_args *g = &op->u.gemm;
+			g->A = (const char*)q->d16 + (size_t)r0 * q->ld16 * 2; g->lda = q->ld16; g->W_ = wqkv + (size_t)2 * d_embed * q->c * 2; g->ldb = q->c;
+			g->M = (int)((int64_t)np * Tq); g->N = d_embed; g->K = q->c;
+			g->bias = bqkv ? bqkv + 2 * d_embed : NULL;
+			g->C16 = (char*)a->d16 + (size_t)r0 * d_embed * 2; g->ldc16 = d_embed;
+			op->flops = 2.0 * g->M * (double)g->N * g->K;
+			C->pag.n_attn++;
+		}
 	} else {
 		if (k != v) { mlctx_fail(C, "attention: k and v must share their input"); return NULL; }
 		const int kv_batched = C->kvb.ctx == k && !bias && k->c == C->kvb.n_in && C->kvb.n_used + 2*d_embed <= C->kvb.n_total;
@@ -512,7 +532,7 @@ MLTensor* mlb_attn_mhead_ex(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v, int
 			}
 			mlb_release(C, qp);
 		} else {
-			MLTensor *kv = fused_proj(C, k, d_embed, bias, n_kv, 2);
+			MLTensor *kv = fused_proj(C, k, d_embed, bias, n_kv, 2, k->n, NULL, NULL);
 			if (!kv) return NULL;
 			const char *pq = (const char*)mlt_need16(C, qp), *pk = (const char*)mlt_need16(C, kv);
 			record_attn(C, pq, d_embed, pk, 2*d_embed, pk + (size_t)d_embed*2, 2*d_embed, a->d16, d_embed,

@@ -58,6 +58,7 @@ struct MLIS_Ctx {
 	int inp_region[4], inp_proc[2], inp_done;
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
+	float pag_scale;                        /* MLIS_OPT_AMD_PAG_SCALE: > 0 is part of the engine key as on / off; the value is handed to the engine per generation */
 	int hypertile, hypertile_depth;         /* MLIS_OPT_AMD_HYPERTILE*: tile in pixels (0 = off) and deepest tiled UNet level; both part of the engine key */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
 	float cfg_scale;
@@ -163,9 +164,11 @@ static const char* const k_option_amd8[] = { "control_preprocess", "canny_low", 
 static const char* const k_preprocess[] = { "none", "canny", "invert" };                                 /* MLIS_AMD_PREPROCESS_* */
 static const char* const k_option_amd9[] = { "inpaint_area", "inpaint_padding", "mask_blur", "mask_grow", "mask_invert", "inpaint_composite" };   /* ids from MLIS_OPT_AMD_INPAINT_AREA */
 static const char* const k_option_amd10[] = { "hypertile", "hypertile_depth" };                         /* ids from MLIS_OPT_AMD_HYPERTILE */
+static const char* const k_option_amd11[] = { "pag_scale" };                                            /* ids from MLIS_OPT_AMD_PAG_SCALE */
 static const char* const k_inpaint_area[] = { "whole", "masked" };                                       /* MLIS_AMD_INPAINT_* */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_PAG_SCALE && x < MLIS_OPT_AMD_PAG_SCALE + COUNTOF(k_option_amd11)) return k_option_amd11[x - MLIS_OPT_AMD_PAG_SCALE];
 	if (x >= MLIS_OPT_AMD_HYPERTILE && x < MLIS_OPT_AMD_HYPERTILE + COUNTOF(k_option_amd10)) return k_option_amd10[x - MLIS_OPT_AMD_HYPERTILE];
 	if (x >= MLIS_OPT_AMD_INPAINT_AREA && x < MLIS_OPT_AMD_INPAINT_AREA + COUNTOF(k_option_amd9)) return k_option_amd9[x - MLIS_OPT_AMD_INPAINT_AREA];
 	if (x >= MLIS_OPT_AMD_CONTROL_PREPROCESS && x < MLIS_OPT_AMD_CONTROL_PREPROCESS + COUNTOF(k_option_amd8)) return k_option_amd8[x - MLIS_OPT_AMD_CONTROL_PREPROCESS];
@@ -200,6 +203,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i9 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_INPAINT_AREA + i9);
 	const int i10 = from_list(k_option_amd10, COUNTOF(k_option_amd10), 1, s, strlen(s));
 	if (i10 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_HYPERTILE + i10);
+	const int i11 = from_list(k_option_amd11, COUNTOF(k_option_amd11), 1, s, strlen(s));
+	if (i11 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_PAG_SCALE + i11);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -263,6 +268,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	S->unet_tile_overlap = -1;
 	S->unet_tile_batch = 1;
 	S->hypertile = 0; S->hypertile_depth = 3;
+	S->pag_scale = 0;
 	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
 	S->canny_low = 100; S->canny_high = 200;
 	S->inpaint_padding = 32;
@@ -283,6 +289,11 @@ static int engine_has_control(MLIS_AmdCtx* e)
 {	/* asked of the engine itself, not read out of its key */
 	int n_res = 0;
 	return e && mlis_amd_control_info(e, &n_res, NULL) > 0 && n_res > 0;
+}
+static int engine_has_pag(MLIS_AmdCtx* e)
+{
+	int n = 0;
+	return e && mlis_amd_pag_info(e, &n, NULL) > 0 && n > 0;
 }
 static int engine_has_freeu(MLIS_AmdCtx* e)
 {
@@ -617,6 +628,7 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
 	case MLIS_OPT_AMD_HYPERTILE: if (!arg_int(A, 0, 8192, 0, &i) || i % 8 || (i && i < 32)) BAD_VALUE; S->hypertile = i; break;      /* 0: off; the rule is applied per pass size (engine_get) */
 	case MLIS_OPT_AMD_HYPERTILE_DEPTH: if (!arg_int(A, 0, 3, 3, &i)) BAD_VALUE; S->hypertile_depth = i; break;
+	case MLIS_OPT_AMD_PAG_SCALE: if (!arg_float(A, 0, 20, 0, &f)) BAD_VALUE; S->pag_scale = f; break;      /* > 0: the engine with the third row group (engine_get) */
 	case MLIS_OPT_AMD_CONTROL_MODEL:       /* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
 		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
 		if (!S->path_control || strcmp(S->path_control, s)) { control_engines_drop(S); if (S->ts_control) { mlts_close(S->ts_control); S->ts_control = NULL; } }
@@ -764,6 +776,7 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_batch; } break;
 	case MLIS_OPT_AMD_HYPERTILE: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile; } break;
 	case MLIS_OPT_AMD_HYPERTILE_DEPTH: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile_depth; } break;
+	case MLIS_OPT_AMD_PAG_SCALE: { float *p = va_arg(ap, float*); if (p) *p = S->pag_scale; } break;
 	case MLIS_OPT_AMD_CONTROL_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_control ? S->path_control : ""; } break;
 	case MLIS_OPT_AMD_CONTROL_IMAGE: { int *p = va_arg(ap, int*); if (p) *p = tensor_good(&S->control_image); } break;      /* whether one is set */
 	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
@@ -1215,11 +1228,22 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	/* (the UNet plan of a tiled pass has the size of one window: the rule sees that) */
 	const int plw = tile && tile / f < lw ? tile / f : lw, plh = tile && tile / f < lh ? tile / f : lh;
 	const int hypertile = hypertile_cuts(S->mname, plw, plh, S->hypertile, S->hypertile_depth) ? S->hypertile : 0;
-	if (hypertile && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/h%dd%d", hypertile, S->hypertile_depth);
+	if (hypertile && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/h%dd%d", hypertile, S->hypertile_depth);
+	const int pag = S->pag_scale > 0;                     /* (the scale is an argument of the mix kernels: only on / off is built in) */
+	if (pag && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/p1");
+	if (pag) {      /* the third row group must fit what an engine holds per plan evaluation: refused here as a bad option value, before anything is built */
+		int pk = 1, xs[MLSD_WINDOW_MAX_AXIS];
+		if (tile) {
+			const int nx = mlis_amd_window_starts(lw, tile / f, overlap / f, S->tiling & 1, xs, MLSD_WINDOW_MAX_AXIS), ny = mlis_amd_window_starts(lh, tile / f, overlap / f, S->tiling & 2, xs, MLSD_WINDOW_MAX_AXIS);
+			if (nx > 0 && ny > 0) pk = mlis_amd_tile_pack(nx * ny, B, S->unet_tile_batch, NULL);
+		}
+		const int rows = mlis_amd_eval_rows(B, S->cfg_scale, 1) * (pk > 0 ? pk : 1);
+		if (rows > MLIS_AMD_MAX_EVAL_ROWS) return api_error(S, MLIS_E_OPT_VALUE, "pag_scale: %d rows per UNet evaluation (batch %d), at most %d", rows, B, MLIS_AMD_MAX_EVAL_ROWS);
+	}
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	/* (a slot serves when its key matches AND it holds a ControlNet exactly if one is wanted: a key cut short by a long model name cannot pass one for the other) */
-#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control && engine_has_freeu(e) == freeu)
+#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control && engine_has_freeu(e) == freeu && engine_has_pag(e) == pag)
 	if (!SLOT_IS(S->eng, S->eng_key) && SLOT_IS(S->eng2, S->eng2_key)) {      /* the other resident engine: they change places */
 		MLIS_AmdCtx *e = S->eng; char k[sizeof(S->eng_key)]; memcpy(k, S->eng_key, sizeof(k));
 		S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(k));
@@ -1238,7 +1262,8 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.s_noise = S->s_noise; c.f_t_ini = S->f_t_ini; c.f_t_end = S->f_t_end; c.defer_weights = 1;
 		c.unet_split = (S->flags & CF_UNET_SPLIT) ? 1 : 0;      /* MLIS_OPT_UNET_SPLIT (src/mlimgsynth.c:1629 unet_split): the UNet's weights are streamed, not resident */
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
-		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0) | MLIS_AMD_CONTROL_HYPERTILE_OF(hypertile, S->hypertile_depth);
+		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0) | MLIS_AMD_CONTROL_HYPERTILE_OF(hypertile, S->hypertile_depth) |
+			(pag ? MLIS_AMD_CONTROL_PAG : 0);
 		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
@@ -1844,6 +1869,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	}
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
+	if (S->pag_scale > 0) ADD(", PAG: %g", S->pag_scale);
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
 	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);
@@ -1921,6 +1947,7 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 
 	if ((r = control_apply(S, w_img, h_img, S->control_rect_on ? S->control_rect : NULL, S->control_rect_W, S->control_rect_H)) < 0) return r;
 	if (S->freeu && mlis_amd_set_freeu(S->eng, S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+	if (S->pag_scale > 0 && mlis_amd_set_pag(S->eng, S->pag_scale) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	S->image.flags &= ~LT_F_READY;

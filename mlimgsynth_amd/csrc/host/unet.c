@@ -210,7 +210,10 @@ static MLTensor* mlb_ctrl_add(MLCtx* C, MLTensor* base, const UnetControl* K, in
 {
 	if (!base || C->err) return NULL;
 	const int64_t rows = (int64_t)base->n * base->h * base->w;
-	if (i < 0 || i >= K->n || !K->r[i] || !K->gain || K->c[i] != base->c || K->rows[i] != base->h * base->w || K->n_img < 1 || base->n % K->n_img) {
+	/* image n reads control image n % K->n_img: whole repeats of the control batch, or -- a plan with a perturbed group (mlctx_set_pag), whose ControlNet plan holds the
+	 * other groups only -- that batch once and then its FIRST images, the cond group the perturbed group copies, for the last pag.n_img images */
+	const int pag_tail = C->pag.n_img > 0 && base->n == K->n_img + C->pag.n_img && C->pag.n_img <= K->n_img;
+	if (i < 0 || i >= K->n || !K->r[i] || !K->gain || K->c[i] != base->c || K->rows[i] != base->h * base->w || K->n_img < 1 || (base->n % K->n_img && !pag_tail)) {
 		mlctx_fail(C, "unet: control residual %d does not match a %d x %d x %d map", i, base->n, base->h * base->w, base->c); return NULL;
 	}
 	const float *b = mlt_need32(C, base);
@@ -318,7 +321,10 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 		MLTensor *y = MLN("mid.0", mlb_resnet_ex(C, x, emb, ch));   /* x stays on the skip stack */
 		if (!y || !mlt_need32(C, y)) return NULL;
 		x = y;
+		/* perturbed-attention guidance (mlctx_set_pag): the self-attentions of this block, and of no other, treat the plan's last pag.n_img images as perturbed */
+		C->pag.cur = C->pag.n_img;
 		y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
+		C->pag.cur = 0;
 		if (!y || !mlt_need32(C, y)) return NULL;
 		mlb_release(C, x); x = y;
 		y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));

@@ -55,13 +55,20 @@ class AmdControlConfig(ctypes.Structure):
     _fields_ = AmdConfig._fields_ + [("control", c_int)]
 
 
-CONTROL_NET, CONTROL_FREEU, CONTROL_HYPERTILE = 1, 2, 4       # MLIS_AMD_CONTROL_*: the bits of `control`
+CONTROL_NET, CONTROL_FREEU, CONTROL_HYPERTILE, CONTROL_PAG = 1, 2, 4, 8       # MLIS_AMD_CONTROL_*: the bits of `control`
 
 
 def control_hypertile(tile_px, depth=3):
     """MLIS_AMD_CONTROL_HYPERTILE_OF: the bits of `control` for HyperTile with a tile of tile_px pixels (units of 8 px in bits 8..20) down to UNet depth
     `depth` (bits 24..25); 0 for tile_px 0"""
     return (CONTROL_HYPERTILE | (((int(tile_px) // 8) & 0x1FFF) << 8) | ((int(depth) & 3) << 24)) if tile_px else 0
+
+
+def eval_rows(B, cfg_scale, pag):
+    """mlis_amd_eval_rows: rows of one UNet evaluation, [cond B | uncond B (cfg_scale > 1) | perturbed B (pag)]"""
+    f = L().mlis_amd_eval_rows
+    f.restype, f.argtypes = c_int, [c_int, c_f, c_int]
+    return int(f(int(B), float(cfg_scale), int(bool(pag))))
 
 
 def hypertile_side(side, px_per_token, tile_px):
@@ -336,11 +343,15 @@ class Unet:
     """unet_denoise_init_n / unet_denoise_run_n (src/unet.c:336-498) with a batch dimension."""
 
     def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0, n_ctx_tok=77,
-                 hypertile=0, hypertile_depth=3, tiling=0):
+                 hypertile=0, hypertile_depth=3, pag=0, tiling=0):
         self.P = unet_params(model)
         self.ctx = MLCtx(stream, flags)
         if hypertile:                   # HyperTile: self-attention inside tiles of `hypertile` image pixels, UNet levels 0 .. hypertile_depth
             set_hypertile(self.ctx, hypertile, hypertile_depth)
+        if pag:                         # perturbed-attention guidance: the plan's last `pag` images are the perturbed group (mlctx_set_pag)
+            f = L().mlctx_set_pag
+            f.restype, f.argtypes = None, [vp, c_int]
+            f(self.ctx.h, int(pag))
         if tiling:                      # seamless tiling: 1 x, 2 y, 3 xy (circular padding of every convolution built below)
             set_conv_wrap(self.ctx, tiling)
         if stream_weights_mib:          # the reference's --unet-split: weights in pinned host memory, three device slabs of this size
@@ -443,6 +454,8 @@ def _proto2():
     l.mlis_amd_set_freeu.argtypes = [vp, c_f, c_f, c_f, c_f]
     l.mlis_amd_freeu_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_hypertile_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    l.mlis_amd_set_pag.argtypes = [vp, c_f]
+    l.mlis_amd_pag_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l._proto2_done = True
     return l
 
@@ -525,13 +538,14 @@ class Generator:
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
                  defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, freeu=False,
-                 hypertile=0, hypertile_depth=3, tiling=0):
+                 hypertile=0, hypertile_depth=3, pag=False, tiling=0):
         l = _proto2()
         self.cfg = AmdControlConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
                              int(defer_weights), int(unet_split), int(n_ctx_tok),     # n_ctx_tok: context rows, 77 x W (windowed prompt)
                              (CONTROL_NET if control else 0) | (CONTROL_FREEU if freeu else 0) |   # control: flags -- a ControlNet (set_control_image / set_control), FreeU (set_freeu),
-                             control_hypertile(hypertile, hypertile_depth))                        # HyperTile with a tile of `hypertile` pixels (hypertile_info)
+                             control_hypertile(hypertile, hypertile_depth) |                       # HyperTile with a tile of `hypertile` pixels (hypertile_info),
+                             (CONTROL_PAG if pag else 0))                                          # perturbed-attention guidance: a third row group (set_pag, pag_info)
         if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
             tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)      # times up to unet_tile_batch windows per evaluation
             self.h = l.mlis_amd_create_tiled_packed(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), vp(stream))
@@ -626,6 +640,16 @@ class Generator:
         """(decoder concatenations treated at stage 1, at stage 2); (0, 0) for an engine without FreeU"""
         a, b = c_int(), c_int()
         check1(_proto2().mlis_amd_freeu_info(self.h, ctypes.byref(a), ctypes.byref(b)), "mlis_amd_freeu_info")
+        return a.value, b.value
+
+    def set_pag(self, scale=3.0):
+        """mlis_amd_set_pag: the scale of the perturbed-attention term, 0 .. 20; engines start at 0 (the plain mix)"""
+        check1(_proto2().mlis_amd_set_pag(self.h, float(scale)), "mlis_amd_set_pag")
+
+    def pag_info(self):
+        """(perturbed self-attentions of the UNet plan -- 0 for an engine without PAG --, rows of one evaluation)"""
+        a, b = c_int(), c_int()
+        check1(_proto2().mlis_amd_pag_info(self.h, ctypes.byref(a), ctypes.byref(b)), "mlis_amd_pag_info")
         return a.value, b.value
 
     def hypertile_info(self):

@@ -346,6 +346,21 @@ def ctrl_add(dst, ld_dst, base, ld_base, ctrl, ld_ctrl, n_img, rows_per_img, C, 
           "mlsd_ctrl_add")
 
 
+def dxdt_pag(eps, ld, x_eval, dx, B, C, HW, cfg, pag, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
+    """mlsd_dxdt_pag: dx [B][C][HW] = the CFG mix of eps NHWC [N][HW][ld] (groups cond | uncond at cfg > 1 | perturbed) + pag * (cond - perturbed), each
+    group after the v-prediction rescale with vparam; pag == 0 is mlsd_dxdt_cfg's path and does not read the perturbed rows (device pointers)."""
+    f = lib().mlsd_dxdt_pag
+    f.argtypes = [vp, c_i64, vp, vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, ctypes.c_float, ctypes.c_float, vp]
+    check(f(vp(eps), ld, vp(x_eval), vp(dx), B, C, HW, cfg, pag, int(vparam), c_out, c_skip, vp(stream)), "mlsd_dxdt_pag")
+
+
+def euler_pag_update(x, eps, ld, B, C, HW, cfg, pag, dt, noise=None, s_up=0.0, stream=None):
+    """mlsd_euler_pag_update: x += mix * dt (+ noise * s_up), the fused Euler(-ancestral) step with the mix of dxdt_pag (no rescale), in place"""
+    f = lib().mlsd_euler_pag_update
+    f.argtypes = [vp, vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, ctypes.c_float, vp]
+    check(f(vp(x), vp(eps), ld, B, C, HW, cfg, pag, dt, vp(noise), s_up, vp(stream)), "mlsd_euler_pag_update")
+
+
 def tile_permute(src, dst, n_img, H, W, th, tw, row_bytes, inverse=False, stream=None):
     """mlsd_tile_permute: dense [n_img][H W] rows of row_bytes bytes from image order into tile-major order (tiles of th x tw rows), or back with inverse
     (device pointers; 16-byte aligned, row_bytes a multiple of 16, no overlap)"""

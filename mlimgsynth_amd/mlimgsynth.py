@@ -50,7 +50,7 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161,
                                                                            AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174,
                                                                            AMD_INPAINT_AREA=181, AMD_INPAINT_PADDING=182, AMD_MASK_BLUR=183, AMD_MASK_GROW=184,
-                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186, AMD_HYPERTILE=191, AMD_HYPERTILE_DEPTH=192))
+                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186, AMD_HYPERTILE=191, AMD_HYPERTILE_DEPTH=192, AMD_PAG_SCALE=201))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 _define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
 _define("MLIS_AMD_PREPROCESS_", ["NONE", "CANNY", "INVERT"])
@@ -95,6 +95,7 @@ _PROTOTYPES = {
     "mlis_amd_inpaint_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_prompt_tokens_set": (_I, [_V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_F), _I, _I]),
     "mlis_amd_engine_get": (_V, [_V]), "mlis_amd_hypertile_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mlis_amd_pag_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
@@ -446,6 +447,23 @@ class MLImgSynth:
         if self._lib.mlis_amd_hypertile_info(e, ctypes.byref(a), ctypes.byref(b), t) < 0:
             raise RuntimeError("Failed to read the HyperTile plan: %s" % self.errstr_get())
         return a.value, b.value, [tuple(int(t[4 * i + j]) for j in range(4)) for i in range(4)]
+
+    # ---- perturbed-attention guidance
+    def pag_set(self, scale=3.0):
+        """Perturbed-attention guidance: scale in [0, 20]; 0 switches it off (the default), 3 is what front ends use.  It persists across generations.  Only
+        on / off is built into the engine (a third UNet row group per image); changing the value builds nothing."""
+        self.option_set("pag_scale", float(scale))
+
+    def pag_info(self):
+        """(perturbed self-attentions of the UNet plan -- 0 for an engine without PAG --, rows of one UNet evaluation) of the engine used last; None before the
+        first engine."""
+        e = self._lib.mlis_amd_engine_get(self._ctx)
+        if not e:
+            return None
+        a, b = _I(), _I()
+        if self._lib.mlis_amd_pag_info(e, ctypes.byref(a), ctypes.byref(b)) < 0:
+            raise RuntimeError("Failed to read the PAG plan: %s" % self.errstr_get())
+        return a.value, b.value
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

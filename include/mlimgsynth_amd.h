@@ -29,6 +29,8 @@ typedef struct {
 	int clip_norm, cond_label, uncond_empty_zero, vparam;
 	int n_step_train;
 	float sigma_min, sigma_max;
+	int zsnr;                /* the sigma table unet_t_to_sigma / unet_sigma_to_t / dnsamp_schedule read: 0 the scaled-linear one, 1 its zero-terminal-SNR rescale
+	                          * (unet_params_set_zsnr keeps sigma_max in step); not in the reference's structure: appended */
 } UnetParams;
 
 /* "sd1" | "sd2" | "sdxl" (g_unet_sd1/sd2/sdxl, src/unet.c:21-83) | "tiny" | "tinyxl" (test configs) */
@@ -39,6 +41,13 @@ MLTensor* mlb_unet_denoise(MLCtx* C, MLTensor* x, MLTensor* time, MLTensor* c, M
 void  unet_params_init(void);
 float unet_sigma_to_t(const UnetParams* P, float sigma);
 float unet_t_to_sigma(const UnetParams* P, float t);
+/* The zero-terminal-SNR table ("Common Diffusion Noise Schedules and Sample Steps are Flawed", 2023, Algorithm 1; not in the reference), built beside the plain one
+ * from the same double-precision cumulative products abar_i: s_i = sqrt(abar_i), s'_i = (s_i - s_999) s_0 / (s_0 - s_999), abar'_i = s'_i^2, the last clamped to
+ * 4.8973451890853435e-08 (sigma 4518.76; the front ends' constant as recalled, parity-unpinned), sigma'_i = sqrt((1 - abar'_i) / abar'_i), stored as float logs.
+ * unet_log_sigmas: the 1000 stored logs of either table.  unet_params_set_zsnr: the flag and the sigma range that goes with it.  unet_params_sizeof: sizeof(UnetParams). */
+const float* unet_log_sigmas(int zsnr);
+void  unet_params_set_zsnr(UnetParams* P, int zsnr);
+int   unet_params_sizeof(void);
 
 typedef struct {
 	MLCtx* ctx;
@@ -281,6 +290,7 @@ int mlts_count(const MLTStore* S);
 const MLTSEntry* mlts_at(const MLTStore* S, int i);
 const MLTSEntry* mlts_find(const MLTStore* S, const char* name);
 int mlts_stats(const MLTStore* S, int* n_unused, int* n_split);
+int mlts_markers(const MLTStore* S, int* v_pred, int* ztsnr);      /* marker tensors "v_pred" / "ztsnr" of the file (mlis_amd_prediction_resolve) */
 /* mlis_model_identify (src/mlimgsynth.c:1206-1249): "sd1" | "sd2" | "sdxl" or NULL; *wtype = dtype of the probe tensor */
 const char* mlts_model_identify(const MLTStore* S, int* wtype);
 /* mlctx_tstore_load (src/mlblock.c:266-292): every parameter of the prepared plan by name; element count checked */
@@ -488,11 +498,31 @@ int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, 
  * generations, and under use_hipgraph, without touching a plan.  Engines start at 0, where the flag alone computes what the plain mix does (the third group is
  * evaluated and not read).  pag_info: the perturbed self-attentions of the UNet plan (0 without the flag) and the rows of one evaluation.
  * Not included: layer selections other than the middle block; a step window or an adaptive scale (a plan is fixed: outside a window the perturbed rows would still be
- * computed, and saving them needs a plain plan beside this one on one set of weights); guidance rescale; self-attention guidance. */
+ * computed, and saving them needs a plain plan beside this one on one set of weights); self-attention guidance.  (Guidance rescale: mlis_amd_set_cfg_rescale.) */
 #define MLIS_AMD_MAX_EVAL_ROWS 128        /* rows of one plan evaluation: what a plain engine of the largest batch holds (2 x 64) */
 int mlis_amd_eval_rows(int B, float cfg_scale, int pag);
 int mlis_amd_set_pag(MLIS_AmdCtx* S, float scale);
 int mlis_amd_pag_info(const MLIS_AmdCtx* S, int* n_attn, int* rows);
+/* Prediction type, zero-terminal-SNR schedule and guidance rescale ("Common Diffusion Noise Schedules and Sample Steps are Flawed", 2023; not in the reference): what
+ * a v-prediction SDXL checkpoint trained on the rescaled schedule needs.  All three are fields of the engine handed over per generation, as mlis_amd_set_pag hands
+ * over its scale: none is in a plan or in the engine key, none rebuilds or recaptures anything, and at their defaults no new code runs.
+ *   set_prediction: vparam 1 = the mix maps the output through out*c_out + x*c_skip (0: eps), zsnr 1 = schedule and sigma <-> t read the second table
+ *     (unet_log_sigmas); negative = the model type's own.  With zsnr the uniform schedule starts at the clamped last entry, sigma 4518.76: c_in = 1/sqrt(sigma^2 + 1) is
+ *     applied to the fp32 latent by the kernel that writes the plan's fp16 input, c_skip and c_out are formed in fp32 as ever, and t = 999 is an ordinary timestep.
+ *     Karras with zsnr spends its steps between 4518 and sigma_min: allowed, the user's choice.  No trailing / SGM spacing here.
+ *   set_cfg_rescale: phi 0 .. 1 (0 = off; front ends use 0.7).  Where phi > 0 and the guided prediction differs from the cond one (cfg_scale > 1, or PAG with a scale),
+ *     dxdt_finish and the fused Euler step run mlsd_guidance_stats on the raw outputs (of a tiled engine: the blended canvas, so the statistics are the whole image's)
+ *     and then mlsd_dxdt_rescaled / mlsd_euler_rescaled_update: three launches per mix.  The hires fix rescales in both passes; the statistics are per image, so a
+ *     multi-GPU split needs no communication.
+ *   guidance_info: the resolved values, the sigma range, phi, the rescaled mixes so far and the last mix's factors (returns how many were written).
+ * prediction_resolve: the pure rule of the `prediction` / `zsnr` options.  opt_prediction 0 auto, 1 eps, 2 v; opt_zsnr 0 auto, 1 off, 2 on; ckpt_v_pred / ckpt_ztsnr:
+ * the checkpoint carries a tensor named "v_pred" / "ztsnr" (mlts_markers; the published v-pred SDXL checkpoints' marker convention AS RECALLED, parity-unpinned).
+ * auto = sd2 and tinyv are v, a v_pred marker makes any model v, everything else eps; the second table only with a ztsnr marker.  Explicit values always win. */
+int mlis_amd_set_prediction(MLIS_AmdCtx* S, int vparam, int zsnr);
+int mlis_amd_set_cfg_rescale(MLIS_AmdCtx* S, float phi);
+int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float* sigma_min, float* sigma_max, float* phi, int* n_evals, float* factors, int max_factors);
+int mlis_amd_last_rows(MLIS_AmdCtx* S, float* out, size_t nbytes);      /* the raw outputs the last mix read, host [N][4][hw] (tests, tools) */
+int mlis_amd_prediction_resolve(const char* model, int ckpt_v_pred, int ckpt_ztsnr, int opt_prediction, int opt_zsnr, int* vparam, int* zsnr);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);

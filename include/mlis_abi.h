@@ -130,8 +130,18 @@ typedef enum {
 	 * front ends that ship it: parity with them is not pinned by a test.  pag_scale > 0 is part of the engine key as on / off: the engine's UNet plan carries a third row
 	 * group (about 1.5 x the work of a CFG evaluation, 2 x at cfg_scale <= 1); the value is a kernel argument and changes without building anything.  With 0 none of it
 	 * runs: the plain engine under the plain key.  A batch whose rows per evaluation the engine refuses (more than 128) is MLIS_E_OPT_VALUE at generation.  Not
-	 * included: other layer selections, a step window or adaptive scale, guidance rescale, self-attention guidance.  (A block of its own from 201.) */
-	MLIS_OPT_AMD_PAG_SCALE = 201           /* "pag_scale" (float 0 .. 20, default 0 = off; front ends default to 3 when it is switched on) */
+	 * included: other layer selections, a step window or adaptive scale, self-attention guidance (guidance rescale: cfg_rescale below).  (A block of its own from 201.) */
+	MLIS_OPT_AMD_PAG_SCALE = 201,          /* "pag_scale" (float 0 .. 20, default 0 = off; front ends default to 3 when it is switched on) */
+	/* v-prediction checkpoints on a zero-terminal-SNR schedule, and the guidance rescale they are sampled with ("Common Diffusion Noise Schedules and Sample Steps are
+	 * Flawed", 2023).  The prediction type is no longer tied to the model type: an SDXL checkpoint may be v-prediction.  None of the three is part of the engine key and
+	 * none builds anything: they are handed to the engine per generation (include/mlimgsynth_amd.h, mlis_amd_set_prediction / _set_cfg_rescale).  At the defaults every
+	 * generation returns the bytes it returned without them.  `auto` is what the model type says (sd2, tinyv: v) and what the checkpoint says: a tensor named "v_pred"
+	 * makes it v-prediction, one named "ztsnr" selects the rescaled sigma table -- the published checkpoints' marker convention as recalled, parity-unpinned; the
+	 * explicit values always win.  With zsnr the uniform schedule starts at sigma 4518.76 (the clamped last entry).  Not included: trailing / SGM timestep spacing, a
+	 * step window for the rescale, dynamic thresholding, APG, CFG++.  (A block of its own from 211.) */
+	MLIS_OPT_AMD_CFG_RESCALE = 211,        /* "cfg_rescale" (float 0 .. 1, default 0 = off; front ends use 0.7): phi of the guidance rescale */
+	MLIS_OPT_AMD_PREDICTION = 212,         /* "prediction" (auto|eps|v or 0 .. 2, default auto) */
+	MLIS_OPT_AMD_ZSNR = 213                /* "zsnr" (auto|off|on or 0 .. 2, default auto; n|y are accepted for off|on) */
 } MLIS_Option;
 enum { MLIS_AMD_INPAINT_WHOLE = 0, MLIS_AMD_INPAINT_MASKED = 1 };
 enum { MLIS_AMD_RESAMPLE_NEAREST = 0, MLIS_AMD_RESAMPLE_BILINEAR = 1, MLIS_AMD_RESAMPLE_BICUBIC = 2 };

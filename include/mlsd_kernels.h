@@ -424,6 +424,29 @@ int mlsd_dxdt_pag(const float* eps, int64_t ld, const float* x_eval, float* dx, 
                   int vparam, float c_out, float c_skip, void* stream);
 int mlsd_euler_pag_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float dt,
                           const float* noise, float s_up, void* stream);
+/* Guidance rescale (csrc/hip/guidance.hip; "Common Diffusion Noise Schedules and Sample Steps are Flawed", 2023, Algorithm 2; not in the reference).  eps and the row
+ * groups as for mlsd_dxdt_pag.  Per image b over its n = C*HW elements, c, u, p the RAW outputs of the groups (a v model's own prediction, before the v map):
+ *   g = fadd(fmul(c, cfg), fmul(u, 1 - cfg))  (cfg > 1; else c);   g = fadd(g, fmul(pag, fsub(c, p)))  (pag != 0)
+ *   f = phi*sqrt(M2(c) / M2(g)) + (1 - phi),  M2 the sum of squared deviations from the mean (the n - 1 of the standard deviations cancels); formed in double, rounded
+ *       once to float; 1 where M2(g) is zero or not finite, where n == 1, and where g is c (cfg <= 1 and pag == 0: the statistics are not launched)
+ *   r = fmul(g, f);   dx = vparam ? fadd(fmul(r, c_out), fmul(x, c_skip)) : r
+ * guidance_stats writes factor[b] (device, B floats): one launch of (mlsd_guidance_blocks(HW), B) blocks -- a rule of HW alone -- that accumulate sums and sums of
+ * squares in double (lanes, then waves, then LDS; each block stores four doubles to scratch[b][block][4]), one launch that sums an image's partials in block order.  No
+ * atomics and no block waits on another, so the factors are the same bits on every run.  scratch: mlsd_guidance_scratch_bytes(B, HW) bytes (at most
+ * B * MLSD_GUIDANCE_MAX_BLOCKS * 32), 8-byte aligned.
+ * dxdt_rescaled / euler_rescaled_update: mlsd_dxdt_pag / mlsd_euler_pag_update with the multiplication by factor[b] (a device pointer), same access pattern; the fused
+ * form (eps models) equals dxdt_rescaled + mlsd_vec_axpy + mlsd_noise_add_s bit for bit.
+ * Refused before any launch: a NULL buffer (x_eval may be NULL without vparam), B, C or HW below 1, ld < C, pag < 0 or NaN, cfg NaN, phi outside 0 .. 1 or NaN,
+ * 2^31 elements or more, a scratch smaller than mlsd_guidance_scratch_bytes. */
+#define MLSD_GUIDANCE_MAX_BLOCKS 64
+int    mlsd_guidance_blocks(int HW);
+size_t mlsd_guidance_scratch_bytes(int B, int HW);
+int mlsd_guidance_stats(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float phi, double* scratch, size_t scratch_bytes,
+                        float* factor, void* stream);
+int mlsd_dxdt_rescaled(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag,
+                       const float* factor, int vparam, float c_out, float c_skip, void* stream);
+int mlsd_euler_rescaled_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, const float* factor, float dt,
+                               const float* noise, float s_up, void* stream);
 int mlsd_vec_axpy(float* out, const float* x, const float* d, float dt, int64_t n, void* stream);     /* out = x + d*dt (solvers.c:86,105,278) */
 int mlsd_solver_heun_corr(float* x, const float* dx, const float* d1, float dt, int64_t n, void* stream);   /* solvers.c:112-113 */
 int mlsd_solver_taylor3(float* x, const float* dx, float* dp1, float* dp2, float dt, float idtp, float f2, float f3,

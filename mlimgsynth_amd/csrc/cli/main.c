@@ -335,6 +335,8 @@ static const char k_usage[] =
 "FreeU:       --freeu BOOL  --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "HyperTile:   --hypertile PX   --hypertile-depth N   (self-attention inside tiles of PX image pixels, 32 .. 8192 in steps of 8, 0 = off; UNet levels 0 .. N <= 3)\n"
 "PAG:         --pag-scale F   (perturbed-attention guidance, 0 .. 20, 0 = off, 3 is the usual value; one more UNet row group per image)\n"
+"Guidance:    --cfg-rescale F   --prediction auto|eps|v   --zsnr auto|y|n   (guidance rescale 0 .. 1, 0 = off, 0.7 is the usual value; prediction type and\n"
+"             zero-terminal-SNR sigma table, auto = what the model type and the checkpoint's v_pred / ztsnr markers say)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";

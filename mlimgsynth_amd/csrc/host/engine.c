@@ -105,6 +105,14 @@ struct MLIS_AmdCtx {
 	float pag_scale;            /* 0 .. 20 (mlis_amd_set_pag); 0: the plain mix, the perturbed rows are computed and not read */
 	int CN;                     /* rows of the ControlNet plan: PN without the perturbed group (it is never perturbed; the UNet plan's sums hand that group the cond residuals) */
 	int ht_px, ht_depth;        /* HyperTile (MLIS_AMD_CONTROL_HYPERTILE): tile in pixels (0: off) and deepest tiled level, given to the UNet and ControlNet plans before they are built */
+	/* guidance rescale (mlis_amd_set_cfg_rescale): the mix multiplies the guided prediction by a per-image factor (mlsd_guidance_stats).  The buffers exist only once
+	 * a phi > 0 was set; the prediction type and the sigma table (mlis_amd_set_prediction) live in unet_p (vparam, zsnr).  None of it is in a plan. */
+	float cfg_rescale;          /* phi, 0 .. 1; 0: the plain mix kernels */
+	double *d_gr_part;          /* [B][mlsd_guidance_blocks(hw)][4] partial sums */
+	float *d_gr_factor;         /* [B] the factors of the last rescaled mix */
+	size_t gr_part_bytes;
+	int gr_evals;               /* rescaled mixes since the engine was created */
+	int vparam_model;           /* the model type's own prediction type (mlis_amd_set_prediction with a negative value goes back to it) */
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -118,6 +126,7 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	if (S->hint_ctx) mlctx_destroy(S->hint_ctx);
 	mlsd_free(S->d_gain);
 	mlsd_free(S->d_freeu);
+	mlsd_free(S->d_gr_part); mlsd_free(S->d_gr_factor);
 	if (S->dec_ctx) mlctx_destroy(S->dec_ctx);
 	if (S->enc_ctx) mlctx_destroy(S->enc_ctx);
 	if (S->dect_ctx) mlctx_destroy(S->dect_ctx);
@@ -304,6 +313,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	}
 	S->ctl_strength = 1; S->ctl_start = 0; S->ctl_end = 1; S->ctl_step_on = 1;
 	if (unet_params_get(S->model, &S->unet_p) < 0) goto err;
+	S->vparam_model = S->unet_p.vparam;
 	if (vae_params_get(S->model, &S->vae_p) < 0) goto err;
 	if (S->c.width % 8 || S->c.height % 8 || S->c.width < 8 || S->c.height < 8) { fail("image size must be a multiple of 8"); goto err; }
 	S->lw = S->c.width / S->vae_p.f_down; S->lh = S->c.height / S->vae_p.f_down; S->hw = S->lw * S->lh;
@@ -726,12 +736,25 @@ static const float* eps_get(MLIS_AmdCtx* S, int64_t* ld)
 	return mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, ld);
 }
 
+/* guidance rescale runs where phi > 0 and the guided prediction is not the cond prediction itself; elsewhere the plain kernels, and their bytes */
+static int rescale_on(const MLIS_AmdCtx* S) { return S->cfg_rescale > 0 && (S->c.cfg_scale > 1 || (S->pag && S->pag_scale != 0)); }
+static int rescale_stats(MLIS_AmdCtx* S, const float* eps, int64_t ld)
+{
+	S->gr_evals++;
+	return mlsd_guidance_stats(eps, ld, S->B, 4, S->hw, S->c.cfg_scale, S->pag ? S->pag_scale : 0, S->cfg_rescale, S->d_gr_part, S->gr_part_bytes, S->d_gr_factor, S->stream);
+}
+
 /* dx = CFG mix (+ v-param rescale) of the evaluation just enqueued */
 static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* dx)
 {
 	int64_t ld = 0;
 	const float *eps = eps_get(S, &ld);
 	const float c_skip = sigma / (sigma*sigma + 1), c_out = 1 / sqrt(sigma*sigma + 1);   /* unet.c:491-492 */
+	if (rescale_on(S)) {      /* statistics of the raw outputs (the blended canvas of a tiled engine: the whole image), then the mix with the factor */
+		const float pag = S->pag ? S->pag_scale : 0;
+		if (rescale_stats(S, eps, ld)) return -1;
+		return mlsd_dxdt_rescaled(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, pag, S->d_gr_factor, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
+	}
 	if (S->pag) return mlsd_dxdt_pag(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->pag_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 	return mlsd_dxdt_cfg(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 }
@@ -829,6 +852,10 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 				const float *eps = eps_get(S, &ld);
 				const float *nz = anc_noise ? noise_draw(S, S->k_draw) : NULL;
 				if (anc_noise && !nz) return -1;
+				if (rescale_on(S)) {
+					if (rescale_stats(S, eps, ld)) return -1;
+					if (mlsd_euler_rescaled_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, S->pag ? S->pag_scale : 0, S->d_gr_factor, t1 - t0, nz, s_up, st)) return -1;
+				} else
 				if (S->pag ? mlsd_euler_pag_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, S->pag_scale, t1 - t0, nz, s_up, st)
 				           : mlsd_euler_cfg_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, t1 - t0, nz, s_up, st)) return -1;
 				if (nz) { S->k_draw++; s_up = -1; }                               /* noise already added */
@@ -1073,6 +1100,74 @@ MLB_API int mlis_amd_pag_info(const MLIS_AmdCtx* S, int* n_attn, int* rows)
 	if (n_attn) *n_attn = n;
 	if (rows) *rows = S->N;
 	return 1;
+}
+
+/* ------------------------------------------------------------------ prediction type, sigma table, guidance rescale
+ * Fields of the engine that the schedule, sigma <-> t and the mix read: set per generation, nothing is rebuilt or captured again (the mix is outside the captured
+ * evaluation, the schedule is host arithmetic).  vparam / zsnr: 0 or 1, negative: what the model type says (zsnr: off). */
+MLB_API int mlis_amd_set_prediction(MLIS_AmdCtx* S, int vparam, int zsnr)
+{
+	if (!S) return fail("mlis_amd_set_prediction: no engine");
+	if (vparam > 1 || zsnr > 1) return mlsd_set_error(-1, "mlis_amd_set_prediction: vparam %d, zsnr %d (0, 1 or negative for the model type's)", vparam, zsnr);
+	S->unet_p.vparam = vparam < 0 ? S->vparam_model : vparam;
+	unet_params_set_zsnr(&S->unet_p, zsnr > 0);
+	return 1;
+}
+
+/* the raw outputs the last mix read (the plan's result, or the blended canvas of a tiled engine): host [N][4][hw], N = mlis_amd_eval_rows.  For tests and tools. */
+MLB_API int mlis_amd_last_rows(MLIS_AmdCtx* S, float* out, size_t nbytes)
+{
+	if (!S || !out || nbytes != (size_t)S->N * 4 * S->hw * 4) return fail("mlis_amd_last_rows: bad argument");
+	int64_t ld = 0;
+	const float *eps = eps_get(S, &ld);
+	const size_t rows = (size_t)S->N * S->hw;
+	float *tmp = (float*)malloc(rows * ld * 4);
+	if (!tmp) return fail("out of memory");
+	if (mlsd_memcpy(tmp, eps, rows * ld * 4, 1, S->stream) || mlsd_stream_sync(S->stream)) { free(tmp); return -1; }
+	for (int n=0; n<S->N; ++n) for (int p=0; p<S->hw; ++p) for (int c=0; c<4; ++c)
+		out[((size_t)n*4 + c)*S->hw + p] = tmp[((size_t)n*S->hw + p)*ld + c];
+	free(tmp);
+	return 1;
+}
+
+MLB_API int mlis_amd_prediction_resolve(const char* model, int ckpt_v_pred, int ckpt_ztsnr, int opt_prediction, int opt_zsnr, int* vparam, int* zsnr)
+{
+	UnetParams U;
+	if (!model || unet_params_get(model, &U) < 0) return -1;
+	if (opt_prediction < 0 || opt_prediction > 2 || opt_zsnr < 0 || opt_zsnr > 2) return mlsd_set_error(-1, "prediction %d / zsnr %d: 0 .. 2", opt_prediction, opt_zsnr);
+	if (vparam) *vparam = opt_prediction ? opt_prediction == 2 : (U.vparam || ckpt_v_pred);
+	if (zsnr) *zsnr = opt_zsnr ? opt_zsnr == 2 : ckpt_ztsnr != 0;
+	return 1;
+}
+
+MLB_API int mlis_amd_set_cfg_rescale(MLIS_AmdCtx* S, float phi)
+{
+	if (!S) return fail("mlis_amd_set_cfg_rescale: no engine");
+	if (!(phi >= 0 && phi <= 1)) return mlsd_set_error(-1, "guidance rescale %g: 0 .. 1", phi);
+	if (phi > 0 && !S->d_gr_part) {
+		const size_t nb = mlsd_guidance_scratch_bytes(S->B, S->hw);
+		if (mlsd_malloc((void**)&S->d_gr_part, nb) || mlsd_malloc((void**)&S->d_gr_factor, (size_t)S->B * 4)) return -1;
+		S->gr_part_bytes = nb;
+	}
+	S->cfg_rescale = phi;
+	return 1;
+}
+
+/* the resolved prediction type and table, the sigma range the schedule walks, phi, the rescaled mixes so far, and the factors of the last one (at most max_factors of
+ * the B; the stream is synchronised for them).  Returns the number of factors written: 0 before the first rescaled mix. */
+MLB_API int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float* sigma_min, float* sigma_max, float* phi, int* n_evals, float* factors, int max_factors)
+{
+	if (!S) return -1;
+	if (vparam) *vparam = S->unet_p.vparam;
+	if (zsnr) *zsnr = S->unet_p.zsnr;
+	if (sigma_min) *sigma_min = S->unet_p.sigma_min;
+	if (sigma_max) *sigma_max = S->unet_p.sigma_max;
+	if (phi) *phi = S->cfg_rescale;
+	if (n_evals) *n_evals = S->gr_evals;
+	if (!factors || max_factors < 1 || !S->gr_evals || !S->d_gr_factor) return 0;
+	const int n = max_factors < S->B ? max_factors : S->B;
+	if (mlsd_memcpy(factors, S->d_gr_factor, (size_t)n * 4, 1, S->stream) || mlsd_stream_sync(S->stream)) return -1;
+	return n;
 }
 
 /* ------------------------------------------------------------------ VAE tiling

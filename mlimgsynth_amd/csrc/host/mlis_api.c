@@ -58,6 +58,9 @@ struct MLIS_Ctx {
 	int inp_region[4], inp_proc[2], inp_done;
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
+	float cfg_rescale;                      /* MLIS_OPT_AMD_CFG_RESCALE: phi of the guidance rescale, handed to the engine per generation (never part of the engine key) */
+	int prediction, zsnr;                   /* MLIS_OPT_AMD_PREDICTION (0 auto, 1 eps, 2 v) / MLIS_OPT_AMD_ZSNR (0 auto, 1 off, 2 on): resolved per generation (guidance_resolve) */
+	int ckpt_v_pred, ckpt_ztsnr;            /* the checkpoint's marker tensors (mlts_markers); 0 for the synthetic models */
 	float pag_scale;                        /* MLIS_OPT_AMD_PAG_SCALE: > 0 is part of the engine key as on / off; the value is handed to the engine per generation */
 	int hypertile, hypertile_depth;         /* MLIS_OPT_AMD_HYPERTILE*: tile in pixels (0 = off) and deepest tiled UNet level; both part of the engine key */
 	int unet_tile_batch, tiled_pack;        /* MLIS_OPT_AMD_UNET_TILE_BATCH: at most this many windows per plan evaluation; the effective pack of the last tiled pass (infotext) */
@@ -165,9 +168,13 @@ static const char* const k_preprocess[] = { "none", "canny", "invert" };        
 static const char* const k_option_amd9[] = { "inpaint_area", "inpaint_padding", "mask_blur", "mask_grow", "mask_invert", "inpaint_composite" };   /* ids from MLIS_OPT_AMD_INPAINT_AREA */
 static const char* const k_option_amd10[] = { "hypertile", "hypertile_depth" };                         /* ids from MLIS_OPT_AMD_HYPERTILE */
 static const char* const k_option_amd11[] = { "pag_scale" };                                            /* ids from MLIS_OPT_AMD_PAG_SCALE */
+static const char* const k_option_amd12[] = { "cfg_rescale", "prediction", "zsnr" };                    /* ids from MLIS_OPT_AMD_CFG_RESCALE */
+static const char* const k_prediction[] = { "auto", "eps", "v" };
+static const char* const k_zsnr[] = { "auto", "off", "on" };
 static const char* const k_inpaint_area[] = { "whole", "masked" };                                       /* MLIS_AMD_INPAINT_* */
 MLB_API const char* mlis_option_str(MLIS_Option x)
 {
+	if (x >= MLIS_OPT_AMD_CFG_RESCALE && x < MLIS_OPT_AMD_CFG_RESCALE + COUNTOF(k_option_amd12)) return k_option_amd12[x - MLIS_OPT_AMD_CFG_RESCALE];
 	if (x >= MLIS_OPT_AMD_PAG_SCALE && x < MLIS_OPT_AMD_PAG_SCALE + COUNTOF(k_option_amd11)) return k_option_amd11[x - MLIS_OPT_AMD_PAG_SCALE];
 	if (x >= MLIS_OPT_AMD_HYPERTILE && x < MLIS_OPT_AMD_HYPERTILE + COUNTOF(k_option_amd10)) return k_option_amd10[x - MLIS_OPT_AMD_HYPERTILE];
 	if (x >= MLIS_OPT_AMD_INPAINT_AREA && x < MLIS_OPT_AMD_INPAINT_AREA + COUNTOF(k_option_amd9)) return k_option_amd9[x - MLIS_OPT_AMD_INPAINT_AREA];
@@ -205,6 +212,8 @@ MLB_API MLIS_Option mlis_option_fromz(const char* s)
 	if (i10 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_HYPERTILE + i10);
 	const int i11 = from_list(k_option_amd11, COUNTOF(k_option_amd11), 1, s, strlen(s));
 	if (i11 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_PAG_SCALE + i11);
+	const int i12 = from_list(k_option_amd12, COUNTOF(k_option_amd12), 1, s, strlen(s));
+	if (i12 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CFG_RESCALE + i12);
 	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
 }
 
@@ -289,6 +298,11 @@ static int engine_has_control(MLIS_AmdCtx* e)
 {	/* asked of the engine itself, not read out of its key */
 	int n_res = 0;
 	return e && mlis_amd_control_info(e, &n_res, NULL) > 0 && n_res > 0;
+}
+/* `prediction` / `zsnr` resolved against the model type and the checkpoint's markers (mlis_amd_prediction_resolve) */
+static int guidance_resolve(MLIS_Ctx* S, int* vparam, int* zsnr)
+{
+	return mlis_amd_prediction_resolve(S->mname, S->ckpt_v_pred, S->ckpt_ztsnr, S->prediction, S->zsnr, vparam, zsnr);
 }
 static int engine_has_pag(MLIS_AmdCtx* e)
 {
@@ -628,6 +642,24 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
 	case MLIS_OPT_AMD_HYPERTILE: if (!arg_int(A, 0, 8192, 0, &i) || i % 8 || (i && i < 32)) BAD_VALUE; S->hypertile = i; break;      /* 0: off; the rule is applied per pass size (engine_get) */
 	case MLIS_OPT_AMD_HYPERTILE_DEPTH: if (!arg_int(A, 0, 3, 3, &i)) BAD_VALUE; S->hypertile_depth = i; break;
+	case MLIS_OPT_AMD_CFG_RESCALE: if (!arg_float(A, 0, 1, 0, &f)) BAD_VALUE; S->cfg_rescale = f; break;      /* handed to the engine per generation */
+	case MLIS_OPT_AMD_PREDICTION:          /* auto|eps|v or 0..2 */
+	case MLIS_OPT_AMD_ZSNR:                /* auto|off|on (also n|y) or 0..2 */
+		if (A->is_str) {
+			next_str_arg(A);
+			if (id == MLIS_OPT_AMD_PREDICTION) i = from_list(k_prediction, COUNTOF(k_prediction), 1, A->arg_b, A->arg_n);
+			else {
+				i = from_list(k_zsnr, COUNTOF(k_zsnr), 1, A->arg_b, A->arg_n);
+				if (i < 0 && A->arg_n == 1 && (A->arg_b[0] == 'n' || A->arg_b[0] == 'y')) i = A->arg_b[0] == 'y' ? 2 : 1;
+			}
+			if (i < 0) {
+				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : 0;
+				if (tail != A->arg_b + A->arg_n) i = -1;
+			}
+		} else i = va_arg(*A->ap, int);
+		if (i < 0 || i > 2) BAD_VALUE;
+		if (id == MLIS_OPT_AMD_PREDICTION) S->prediction = i; else S->zsnr = i;
+		break;
 	case MLIS_OPT_AMD_PAG_SCALE: if (!arg_float(A, 0, 20, 0, &f)) BAD_VALUE; S->pag_scale = f; break;      /* > 0: the engine with the third row group (engine_get) */
 	case MLIS_OPT_AMD_CONTROL_MODEL:       /* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
 		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
@@ -777,6 +809,9 @@ MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
 	case MLIS_OPT_AMD_HYPERTILE: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile; } break;
 	case MLIS_OPT_AMD_HYPERTILE_DEPTH: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile_depth; } break;
 	case MLIS_OPT_AMD_PAG_SCALE: { float *p = va_arg(ap, float*); if (p) *p = S->pag_scale; } break;
+	case MLIS_OPT_AMD_CFG_RESCALE: { float *p = va_arg(ap, float*); if (p) *p = S->cfg_rescale; } break;
+	case MLIS_OPT_AMD_PREDICTION: { int *p = va_arg(ap, int*); if (p) *p = S->prediction; } break;
+	case MLIS_OPT_AMD_ZSNR: { int *p = va_arg(ap, int*); if (p) *p = S->zsnr; } break;
 	case MLIS_OPT_AMD_CONTROL_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_control ? S->path_control : ""; } break;
 	case MLIS_OPT_AMD_CONTROL_IMAGE: { int *p = va_arg(ap, int*); if (p) *p = tensor_good(&S->control_image); } break;      /* whether one is set */
 	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
@@ -1028,12 +1063,13 @@ MLB_API int mlis_setup(MLIS_Ctx* S)
 			const int mt = model_from(nm, strlen(nm));
 			if (mt <= 0) return api_error(S, MLIS_E_OPT_VALUE, "unknown synthetic model '%s'", nm);
 			if (model_type_set_ex(S, mt, 0) < 0) return MLIS_E_OPT_VALUE;
-			S->synth = 1;
+			S->synth = 1; S->ckpt_v_pred = S->ckpt_ztsnr = 0;
 		} else {
 			/* mlis_model_load :1163-1204 + mlis_model_identify :1206-1249 */
 			S->synth = 0;
 			S->ts = mlts_open_safetensors(S->path_model, 1);
 			if (!S->ts) return api_error_lib(S, file_exists(S->path_model) ? MLIS_E_UNKNOWN : MLIS_E_FILE_NOT_FOUND);
+			mlts_markers(S->ts, &S->ckpt_v_pred, &S->ckpt_ztsnr);      /* what `prediction` / `zsnr` = auto resolve to (guidance_resolve) */
 			int wt = -1;
 			const char *m = mlts_model_identify(S->ts, &wt);
 			if (m) { if (model_type_set_ex(S, model_from(m, strlen(m)), 0) < 0) { mlts_close(S->ts); S->ts = NULL; return MLIS_E_OPT_VALUE; } }
@@ -1870,6 +1906,14 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
 	if (S->pag_scale > 0) ADD(", PAG: %g", S->pag_scale);
+	if (S->cfg_rescale > 0) ADD(", CFG rescale: %g", S->cfg_rescale);
+	{	/* the prediction type and the schedule, where they are not the model type's own */
+		int vp = 0, zs = 0, vp0 = 0;
+		if (guidance_resolve(S, &vp, &zs) > 0 && mlis_amd_prediction_resolve(S->mname, 0, 0, 0, 0, &vp0, NULL) > 0) {
+			if (vp != vp0) ADD(", Prediction: %s", vp ? "v-prediction" : "eps");
+			if (zs) ADD(", Schedule: zsnr");
+		}
+	}
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
 	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);
@@ -1948,6 +1992,11 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	if ((r = control_apply(S, w_img, h_img, S->control_rect_on ? S->control_rect : NULL, S->control_rect_W, S->control_rect_H)) < 0) return r;
 	if (S->freeu && mlis_amd_set_freeu(S->eng, S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	if (S->pag_scale > 0 && mlis_amd_set_pag(S->eng, S->pag_scale) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
+	{	/* prediction type, sigma table and guidance rescale: fields of the engine, set for every pass (a resident engine may have served other settings) */
+		int vp = 0, zs = 0;
+		if (guidance_resolve(S, &vp, &zs) < 0 || mlis_amd_set_prediction(S->eng, vp, zs) < 0 || mlis_amd_set_cfg_rescale(S->eng, S->cfg_rescale) < 0)
+			return api_error_lib(S, MLIS_E_UNKNOWN);
+	}
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	S->image.flags &= ~LT_F_READY;

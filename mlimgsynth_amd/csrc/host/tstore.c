@@ -27,6 +27,7 @@ struct MLTStore {
 	void** owned; int n_owned, cap_owned;     /* heap buffers of patched tensors (LoRA) */
 	void* map; size_t map_size;
 	int n_unused, n_split;
+	int v_pred, ztsnr;                        /* marker tensors seen in the file (mlts_markers) */
 };
 
 /* ------------------------------------------------------------------ tiny JSON cursor (safetensors header only) */
@@ -220,6 +221,14 @@ MLB_API MLTStore* mlts_open_controlnet(const char* path) { return open_store(pat
 /* one tensor of the file: renamed / split / dropped according to `mode` (0 raw, 1 model, 2 LoRA, 3 ControlNet); <0 on error */
 static int add_file_tensor(MLTStore* S, const char* name, const MLTSEntry* e, int mode)
 {
+	if (mode < 2) {      /* marker tensors of v-prediction / zero-terminal-SNR checkpoints: bare or under the UNet prefix, any shape; noted, never a parameter */
+		const char *m = name;
+		if (!strncmp(m, "model.diffusion_model.", 22)) m += 22; else if (!strncmp(m, "unet.", 5)) m += 5;
+		const int iv = !strcmp(m, "v_pred"), iz = !strcmp(m, "ztsnr");
+		if (iv) S->v_pred = 1;
+		if (iz) S->ztsnr = 1;
+		if (iv || iz) return 0;
+	}
 	if (!mode) { ts_add(S, name, e); return 1; }
 	char conv[512];
 	const char *nm = name;
@@ -398,6 +407,15 @@ MLB_API int mlts_stats(const MLTStore* S, int* n_unused, int* n_split)
 {
 	if (n_unused) *n_unused = S->n_unused;
 	if (n_split) *n_split = S->n_split;
+	return 1;
+}
+
+/* whether the file carried a tensor named "v_pred" / "ztsnr" (bare, or under "model.diffusion_model." / "unet."): they are not entries and not counted as unused */
+MLB_API int mlts_markers(const MLTStore* S, int* v_pred, int* ztsnr)
+{
+	if (!S) return -1;
+	if (v_pred) *v_pred = S->v_pred;
+	if (ztsnr) *ztsnr = S->ztsnr;
 	return 1;
 }
 

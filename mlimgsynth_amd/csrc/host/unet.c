@@ -400,6 +400,11 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 
 /* ------------------------------------------------------------------ sigma tables (src/unet.c:283-334) */
 static float g_log_sigmas_sd[1000];
+/* the zero-terminal-SNR table (UnetParams.zsnr; "Common Diffusion Noise Schedules and Sample Steps are Flawed", 2023, Algorithm 1; not in the reference): with
+ * s_i = sqrt(abar_i) of the table above, s'_i = (s_i - s_999) s_0 / (s_0 - s_999), abar'_i = s'_i^2.  abar'_999 would be 0 and its sigma infinite, which a
+ * k-diffusion sampler cannot walk, so the last entry is clamped to the constant below: the front ends' value AS RECALLED, not pinned against their code. */
+#define UNET_ZSNR_ABAR_LAST 4.8973451890853435e-08
+static float g_log_sigmas_zsnr[1000];
 
 MLB_API void unet_params_init(void)
 {
@@ -408,12 +413,34 @@ MLB_API void unet_params_init(void)
 	double linear_start = 0.00085, linear_end = 0.0120,
 	       b = sqrt(linear_start), e = sqrt(linear_end),
 	       f = (e - b) / (n - 1), alpha_cumprod = 1.0;
+	double abar[1000];
 	for (unsigned i=0; i<n; ++i) {
 		double beta = b + f*i, alpha = 1.0 - beta*beta;
 		alpha_cumprod *= alpha;
-		double sigma = sqrt((1 - alpha_cumprod) / alpha_cumprod);
+		abar[i] = alpha_cumprod;
+	}
+	/* both tables from the doubles of that one loop; the plain table's first entry, the "done" mark above, is written last */
+	const double s0 = sqrt(abar[0]), sT = sqrt(abar[n-1]);
+	for (unsigned i=0; i<n; ++i) {
+		double sz = (sqrt(abar[i]) - sT) * s0 / (s0 - sT), az = i == n-1 ? UNET_ZSNR_ABAR_LAST : sz * sz;
+		g_log_sigmas_zsnr[i] = log(sqrt((1 - az) / az));
+	}
+	for (unsigned i=n; i-- > 0; ) {
+		double sigma = sqrt((1 - abar[i]) / abar[i]);
 		g_log_sigmas_sd[i] = log(sigma);
 	}
+}
+
+MLB_API const float* unet_log_sigmas(int zsnr) { unet_params_init(); return zsnr ? g_log_sigmas_zsnr : g_log_sigmas_sd; }
+MLB_API int unet_params_sizeof(void) { return (int)sizeof(UnetParams); }
+
+/* the sigma range of the table a model walks: UnetParams.sigma_min / sigma_max follow its zsnr flag (the plain table's are the reference's constants) */
+MLB_API void unet_params_set_zsnr(UnetParams* P, int zsnr)
+{
+	unet_params_init();
+	P->zsnr = zsnr ? 1 : 0;
+	P->sigma_min = 0.029167158f;
+	P->sigma_max = zsnr ? (float)exp(g_log_sigmas_zsnr[999]) : 14.614641f;
 }
 
 static float linear_interp(unsigned n, const float* vec, float t)
@@ -443,13 +470,13 @@ MLB_API float unet_sigma_to_t(const UnetParams* P, float sigma)
 {
 	unet_params_init();
 	float ls = log(sigma);
-	return linear_est(P->n_step_train, g_log_sigmas_sd, ls);
+	return linear_est(P->n_step_train, P->zsnr ? g_log_sigmas_zsnr : g_log_sigmas_sd, ls);
 }
 
 MLB_API float unet_t_to_sigma(const UnetParams* P, float t)
 {
 	unet_params_init();
-	float ls = linear_interp(P->n_step_train, g_log_sigmas_sd, t);
+	float ls = linear_interp(P->n_step_train, P->zsnr ? g_log_sigmas_zsnr : g_log_sigmas_sd, t);
 	return exp(ls);
 }
 

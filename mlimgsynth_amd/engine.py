@@ -18,7 +18,7 @@ class UnetParams(ctypes.Structure):
                 ("ch_mult", c_int * 5), ("transf_depth", c_int * 5), ("n_te", c_int), ("n_head", c_int),
                 ("d_head", c_int), ("n_ctx", c_int), ("n_ch", c_int), ("ch_adm_in", c_int),
                 ("clip_norm", c_int), ("cond_label", c_int), ("uncond_empty_zero", c_int), ("vparam", c_int),
-                ("n_step_train", c_int), ("sigma_min", c_f), ("sigma_max", c_f)]
+                ("n_step_train", c_int), ("sigma_min", c_f), ("sigma_max", c_f), ("zsnr", c_int)]
 
 
 class UnetState(ctypes.Structure):
@@ -333,10 +333,31 @@ class MLCtx:
             pass
 
 
-def unet_params(model):
+def unet_params(model, zsnr=False):
+    """unet_params_get; zsnr: the zero-terminal-SNR sigma table and its sigma range (unet_params_set_zsnr)"""
     u = UnetParams()
     check1(L().unet_params_get(model.encode(), ctypes.byref(u)), "unet_params_get")
+    if zsnr:
+        f = L().unet_params_set_zsnr
+        f.restype, f.argtypes = None, [ctypes.POINTER(UnetParams), c_int]
+        f(ctypes.byref(u), 1)
     return u
+
+
+def log_sigmas(zsnr=False):
+    """unet_log_sigmas: the 1000 stored float logs of the plain or of the zero-terminal-SNR sigma table"""
+    f = L().unet_log_sigmas
+    f.restype, f.argtypes = FP, [c_int]
+    return np.ctypeslib.as_array(f(int(bool(zsnr))), (1000,)).copy()
+
+
+def prediction_resolve(model, ckpt_v_pred=False, ckpt_ztsnr=False, prediction=0, zsnr=0):
+    """mlis_amd_prediction_resolve -> (vparam, zsnr): options 0 auto, 1 eps / off, 2 v / on against the model type and the checkpoint's markers"""
+    f = L().mlis_amd_prediction_resolve
+    f.restype, f.argtypes = c_int, [ctypes.c_char_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    v, z = c_int(-1), c_int(-1)
+    check1(f(model.encode(), int(bool(ckpt_v_pred)), int(bool(ckpt_ztsnr)), int(prediction), int(zsnr), ctypes.byref(v), ctypes.byref(z)), "mlis_amd_prediction_resolve")
+    return v.value, z.value
 
 
 class Unet:
@@ -456,6 +477,9 @@ def _proto2():
     l.mlis_amd_hypertile_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_set_pag.argtypes = [vp, c_f]
     l.mlis_amd_pag_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    l.mlis_amd_set_prediction.argtypes = [vp, c_int, c_int]
+    l.mlis_amd_set_cfg_rescale.argtypes = [vp, c_f]
+    l.mlis_amd_guidance_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), FP, FP, FP, ctypes.POINTER(c_int), FP, c_int]
     l._proto2_done = True
     return l
 
@@ -477,12 +501,24 @@ def control_active(i_step, n_step, start, end):
     return bool(_proto2().mlis_amd_control_active(int(i_step), int(n_step), float(start), float(end)))
 
 
-def schedule(model, n_step, sched=1, f_t_ini=1.0, f_t_end=0.0):
-    P = unet_params(model)
+def schedule(model, n_step, sched=1, f_t_ini=1.0, f_t_end=0.0, zsnr=False):
+    P = unet_params(model, zsnr)
     sig = np.zeros(n_step + 2, np.float32)
     n = _proto2().dnsamp_schedule(ctypes.byref(P), n_step, sched, f_t_ini, f_t_end, fptr(sig))
     check1(n, "dnsamp_schedule")
     return sig[:n + 1]
+
+
+def guidance_info(engine, n_batch):
+    """mlis_amd_guidance_info of an engine handle as a dict (Generator.guidance_info, MLImgSynth.guidance_info)"""
+    v, z, n = c_int(), c_int(), c_int()
+    smin, smax, phi = c_f(), c_f(), c_f()
+    fac = np.zeros(max(int(n_batch), 1), np.float32)
+    r = _proto2().mlis_amd_guidance_info(engine, ctypes.byref(v), ctypes.byref(z), ctypes.byref(smin), ctypes.byref(smax), ctypes.byref(phi), ctypes.byref(n),
+                                         fptr(fac), fac.size)
+    if r < 0:
+        check1(r, "mlis_amd_guidance_info")
+    return dict(vparam=v.value, zsnr=z.value, sigma_min=smin.value, sigma_max=smax.value, cfg_rescale=phi.value, n_evals=n.value, factors=fac[:r].copy())
 
 
 class Decoder:
@@ -651,6 +687,28 @@ class Generator:
         a, b = c_int(), c_int()
         check1(_proto2().mlis_amd_pag_info(self.h, ctypes.byref(a), ctypes.byref(b)), "mlis_amd_pag_info")
         return a.value, b.value
+
+    def set_prediction(self, vparam=-1, zsnr=-1):
+        """mlis_amd_set_prediction: v-prediction (1) or eps (0) mix and the zero-terminal-SNR sigma table (1) or the plain one (0); negative: the model type's"""
+        check1(_proto2().mlis_amd_set_prediction(self.h, int(vparam), int(zsnr)), "mlis_amd_set_prediction")
+
+    def set_cfg_rescale(self, phi=0.7):
+        """mlis_amd_set_cfg_rescale: phi of the guidance rescale, 0 .. 1; engines start at 0 (the plain mix kernels)"""
+        check1(_proto2().mlis_amd_set_cfg_rescale(self.h, float(phi)), "mlis_amd_set_cfg_rescale")
+
+    def last_rows(self):
+        """mlis_amd_last_rows: the raw UNet outputs the last mix read, [N][4][lh][lw] (cond | uncond at cfg > 1 | perturbed with PAG); a tiled engine's blended canvas"""
+        a, b = c_int(), c_int()
+        check1(_proto2().mlis_amd_pag_info(self.h, ctypes.byref(a), ctypes.byref(b)), "mlis_amd_pag_info")
+        out = np.empty((b.value, 4, self.h_px // 8, self.w // 8), np.float32)
+        f = _proto2().mlis_amd_last_rows
+        f.argtypes = [vp, FP, ctypes.c_size_t]
+        check1(f(self.h, fptr(out), out.nbytes), "mlis_amd_last_rows")
+        return out
+
+    def guidance_info(self):
+        """dict: vparam, zsnr, sigma_min, sigma_max, cfg_rescale, n_evals (rescaled mixes so far), factors (float32 [B] of the last rescaled mix; empty before one)"""
+        return guidance_info(self.h, self.cfg.n_batch)
 
     def hypertile_info(self):
         """(spatial transformers of the UNet plan that are tiled, that are not, [(th, tw, nh, nw) per depth 0 .. 3, zeros where the depth is not tiled])"""

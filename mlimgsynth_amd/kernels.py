@@ -361,6 +361,39 @@ def euler_pag_update(x, eps, ld, B, C, HW, cfg, pag, dt, noise=None, s_up=0.0, s
     check(f(vp(x), vp(eps), ld, B, C, HW, cfg, pag, dt, vp(noise), s_up, vp(stream)), "mlsd_euler_pag_update")
 
 
+def guidance_blocks(HW):
+    """mlsd_guidance_blocks: blocks per image of the guidance-rescale statistics, a rule of HW alone"""
+    return int(lib().mlsd_guidance_blocks(int(HW)))
+
+
+def guidance_scratch_bytes(B, HW):
+    f = lib().mlsd_guidance_scratch_bytes
+    f.restype, f.argtypes = ctypes.c_size_t, [c_int, c_int]
+    return int(f(int(B), int(HW)))
+
+
+def guidance_stats(eps, ld, B, C, HW, cfg, pag, phi, scratch, scratch_bytes, factor, stream=None):
+    """mlsd_guidance_stats: factor [B] = phi * sqrt(M2(cond) / M2(guided)) + 1 - phi per image of eps NHWC [N][HW][ld] (raw outputs; groups as for dxdt_pag);
+    scratch: guidance_scratch_bytes(B, HW) bytes of device memory (device pointers)"""
+    f = lib().mlsd_guidance_stats
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, ctypes.c_size_t, vp, vp]
+    check(f(vp(eps), ld, B, C, HW, cfg, pag, phi, vp(scratch), scratch_bytes, vp(factor), vp(stream)), "mlsd_guidance_stats")
+
+
+def dxdt_rescaled(eps, ld, x_eval, dx, B, C, HW, cfg, pag, factor, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
+    """mlsd_dxdt_rescaled: dx = guided mix of the raw outputs * factor[b], then the v map with vparam (device pointers)"""
+    f = lib().mlsd_dxdt_rescaled
+    f.argtypes = [vp, c_i64, vp, vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, c_int, ctypes.c_float, ctypes.c_float, vp]
+    check(f(vp(eps), ld, vp(x_eval), vp(dx), B, C, HW, cfg, pag, vp(factor), int(vparam), c_out, c_skip, vp(stream)), "mlsd_dxdt_rescaled")
+
+
+def euler_rescaled_update(x, eps, ld, B, C, HW, cfg, pag, factor, dt, noise=None, s_up=0.0, stream=None):
+    """mlsd_euler_rescaled_update: x += rescaled mix * dt (+ noise * s_up), in place (eps models)"""
+    f = lib().mlsd_euler_rescaled_update
+    f.argtypes = [vp, vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, ctypes.c_float, vp, ctypes.c_float, vp]
+    check(f(vp(x), vp(eps), ld, B, C, HW, cfg, pag, vp(factor), dt, vp(noise), s_up, vp(stream)), "mlsd_euler_rescaled_update")
+
+
 def tile_permute(src, dst, n_img, H, W, th, tw, row_bytes, inverse=False, stream=None):
     """mlsd_tile_permute: dense [n_img][H W] rows of row_bytes bytes from image order into tile-major order (tiles of th x tw rows), or back with inverse
     (device pointers; 16-byte aligned, row_bytes a multiple of 16, no overlap)"""

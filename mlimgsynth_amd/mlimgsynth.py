@@ -50,7 +50,8 @@ _define("MLIS_OPT_", ["NONE", "BACKEND", "MODEL", "TAE", "LORA_DIR", "LORA", "LO
                                                                            AMD_UPSCALE_MODEL=151, AMD_HIRES_USE_MODEL=152, AMD_DOWNSCALE_FILTER=161,
                                                                            AMD_CONTROL_PREPROCESS=171, AMD_CANNY_LOW=172, AMD_CANNY_HIGH=173, AMD_CANNY_L2=174,
                                                                            AMD_INPAINT_AREA=181, AMD_INPAINT_PADDING=182, AMD_MASK_BLUR=183, AMD_MASK_GROW=184,
-                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186, AMD_HYPERTILE=191, AMD_HYPERTILE_DEPTH=192, AMD_PAG_SCALE=201))
+                                                                           AMD_MASK_INVERT=185, AMD_INPAINT_COMPOSITE=186, AMD_HYPERTILE=191, AMD_HYPERTILE_DEPTH=192, AMD_PAG_SCALE=201,
+                                                                           AMD_CFG_RESCALE=211, AMD_PREDICTION=212, AMD_ZSNR=213))
 _define("MLIS_AMD_RESAMPLE_", ["NEAREST", "BILINEAR", "BICUBIC"])
 _define("MLIS_AMD_AA_", ["BOX", "TRIANGLE", "CUBIC", "LANCZOS"])
 _define("MLIS_AMD_PREPROCESS_", ["NONE", "CANNY", "INVERT"])
@@ -464,6 +465,27 @@ class MLImgSynth:
         if self._lib.mlis_amd_pag_info(e, ctypes.byref(a), ctypes.byref(b)) < 0:
             raise RuntimeError("Failed to read the PAG plan: %s" % self.errstr_get())
         return a.value, b.value
+
+    # ---- prediction type, zero-terminal-SNR schedule, guidance rescale
+    def guidance_set(self, cfg_rescale=None, prediction=None, zsnr=None):
+        """cfg_rescale: phi of the guidance rescale in [0, 1], 0 = off (front ends use 0.7).  prediction: "auto" | "eps" | "v".  zsnr: "auto" | "off" | "on" (or a
+        bool): the zero-terminal-SNR sigma table.  "auto" is what the model type and the checkpoint's v_pred / ztsnr markers say.  Arguments left None keep their
+        value; all persist across generations and none builds an engine."""
+        if cfg_rescale is not None:
+            self.option_set("cfg_rescale", float(cfg_rescale))
+        if prediction is not None:
+            self.option_set("prediction", str(prediction))
+        if zsnr is not None:
+            self.option_set("zsnr", ("on" if zsnr else "off") if isinstance(zsnr, bool) else str(zsnr))
+
+    def guidance_info(self):
+        """dict of the engine used last: vparam and zsnr as resolved, sigma_min, sigma_max, cfg_rescale, n_evals (rescaled mixes so far) and factors (the last
+        mix's per-image factors); None before the first engine."""
+        e = self._lib.mlis_amd_engine_get(self._ctx)
+        if not e:
+            return None
+        from . import engine as E
+        return E.guidance_info(e, 64)      # (room for the largest batch; the engine writes its own B factors)
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

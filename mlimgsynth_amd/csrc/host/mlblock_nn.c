@@ -234,10 +234,8 @@ MLB_API MLTensor* mlb_upsample(MLCtx* C, MLTensor* x, int ch_out)
 	 * (W % 16 == 0, Cin % 64 == 0, whole wave columns), and -- unless forced, mlsd_gemm_set_ups_phases(2) -- enough rows that four launches win: each phase launch must
 	 * bring at least one full round of 256 tiles of 128 x 320 (SDXL batch 4: 8192 x 1280 and up; profiles/NOTES.md has the in-plan A/B).  Below that the four launches
 	 * each leave CUs idle where the single launch fills them, and today's form stays. */
-	/* A plan built in the dry runtime (no device: the host-side audits of tests/plan_audit.py) keeps today's form as well: that audit states what a GEMM writes as
-	 * M rows at one stride and cannot express the pixel map; the form's buffer binding is held on the device instead (tests/test_upsample_phases_gpu.py). */
 	const int mode = mlsd_gemm_ups_phases();
-	if (x && !C->err && mode != 0 && !C->dry && x->h > 1 && !(x->c % 8)) {
+	if (x && !C->err && mode != 0 && x->h > 1 && !(x->c % 8)) {
 		mlsd_gemm_args g; memset(&g, 0, sizeof g);
 		g.lda = x->c; g.conv = 1; g.n_img = x->n; g.H = x->h; g.W = x->w; g.Cin = x->c; g.OH = x->h; g.OW = x->w;
 		g.KH = 2; g.KW = 2; g.stride = 1; g.pad = 1; g.wrap = C->conv_wrap;

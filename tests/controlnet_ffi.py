@@ -17,6 +17,14 @@ class ControlState(C.Structure):     # include/mlimgsynth_amd.h
                 ("t_hint", F.vp), ("n_res", F.ci), ("t_res", F.vp * CONTROL_MAX)]
 
 
+class UnetControl(C.Structure):      # include/mlimgsynth_amd.h: where a built ControlNet plan leaves its residuals, for unet_denoise_build_ctrl
+    _fields_ = [("n", F.ci), ("r", F.vp * CONTROL_MAX), ("ld", c64 * CONTROL_MAX), ("c", F.ci * CONTROL_MAX), ("rows", F.ci * CONTROL_MAX), ("n_img", F.ci), ("gain", F.vp)]
+
+
+class UnetFreeU(C.Structure):        # the four FreeU factors (device memory) and, out, the concatenations treated per stage
+    _fields_ = [("f", F.vp), ("n_stage1", F.ci), ("n_stage2", F.ci)]
+
+
 PROTOTYPES = [
     ("mlsd_ctrl_add", F.ci, [F.vp, c64, F.vp, c64, F.vp, c64, F.ci, F.ci, F.ci, F.ci, F.vp, F.vp]),
     ("mlsd_window_gather_nhwc", F.ci, [F.vp, F.ci, F.ci, F.ci, F.vp, F.ci, F.ci, pi, pi, F.ci, F.ci, F.vp]),
@@ -37,12 +45,22 @@ PROTOTYPES = [
     ("control_hint_init", F.ci, [F.vp, F.vp, C.c_uint, C.c_uint, C.POINTER(F.vp)]),
     ("control_hint_build", F.ci, [F.vp, F.vp, F.vp]),
 ]
+# what a test needs to drive the three plans at the context level (tests/plan_audit.py)
+PLAN_PROTOTYPES = [
+    ("controlnet_control", F.ci, [C.POINTER(ControlState), F.vp, C.POINTER(UnetControl)]),
+    ("unet_denoise_build_freeu", F.ci, [F.vp, C.POINTER(UnetControl), C.POINTER(UnetFreeU)]),
+    ("mlctx_input_set", F.ci, [F.vp, F.vp, F.vp, C.c_size_t]),
+    ("mlctx_output_get", F.ci, [F.vp, F.vp, F.vp, C.c_size_t]),
+    ("mlctx_result", F.vp, [F.vp]),
+    ("mlctx_compute_checked", F.ci, [F.vp]),
+    ("mlctx_tensor_device_f32", F.vp, [F.vp, F.vp, C.POINTER(c64)]),
+]
 EXPORTS = [p[0] for p in PROTOTYPES] + ["mlis_amd_set_control_image_device", "mlb_controlnet", "mlb_unet_denoise_ctrl", "unet_denoise_build_ctrl", "controlnet_control"]
 
 
 def bind(path):
     lib = F.bind(path)
-    for name, res, args in PROTOTYPES:
+    for name, res, args in PROTOTYPES + PLAN_PROTOTYPES:
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
     return lib

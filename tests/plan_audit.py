@@ -13,6 +13,10 @@ every op (MLCtx.op_records, never the C side's table of outputs, k_op_class), wh
 
 verify_op(mem, plan, i) recomputes one op in float64 from the operands it actually read (tests/ref64.py: references and bounds) and returns
 the worst ratio to the bound per output; kinds and arguments it does not know FAIL BY NAME (Unknown), they are never skipped.
+
+Forms of the option plans: the control sum (cadd: its residuals and its gain live in ANOTHER plan's memory and a driver buffer, declared to Plan as
+external ranges), the two FreeU passes, HyperTile's permuting copy (copy with th > 0) and the phase launches of an upsampling convolution (GEMM with
+out_phase: the write is a strided pixel map, one Range per (image, source row)).
 """
 import bisect
 import ctypes
@@ -94,21 +98,24 @@ def covered_by(r, covers):
                 return True
     if not covers:
         return False
-    lo = r.base + np.arange(r.rows, dtype=np.int64) * r.stride
-    hi = lo + r.row_bytes
-    cur = lo.copy()
-    for _ in range(64 * len(covers) + 1):      # sweep: extend the covered prefix of every row while some range continues it
-        before = cur.copy()
-        for c in covers:
-            k = np.clip((cur - c.base) // c.stride, 0, c.rows - 1)
-            s = c.base + k * c.stride
-            inside = (s <= cur) & (cur < s + c.row_bytes)
-            cur = np.where(inside, np.maximum(cur, s + c.row_bytes), cur)
-        if (cur >= hi).all():
-            return True
-        if (cur == before).all():
-            return False
-    raise Unknown(f"coverage of {r} by {covers} undecided")
+    los = []      # the union of the covers' rows (those that can touch r), merged into disjoint intervals; then every row of r must lie inside one
+    for c in covers:
+        k0, k1 = max(0, (r.lo - c.base - c.row_bytes) // c.stride + 1), min(c.rows - 1, (r.hi - 1 - c.base) // c.stride)
+        if k0 <= k1:
+            lo = c.base + np.arange(k0, k1 + 1, dtype=np.int64) * c.stride
+            los.append(np.stack([lo, lo + c.row_bytes]))
+    if not los:
+        return False
+    lo, hi = np.concatenate(los, axis=1)
+    o = np.argsort(lo, kind="stable")
+    lo, reach = lo[o], np.maximum.accumulate(hi[o])
+    first = np.ones(lo.size, bool)
+    first[1:] = lo[1:] > reach[:-1]
+    idx = np.nonzero(first)[0]
+    starts, ends = lo[idx], reach[np.append(idx[1:] - 1, lo.size - 1)]
+    rlo = r.base + np.arange(r.rows, dtype=np.int64) * r.stride
+    j = np.searchsorted(starts, rlo, side="right") - 1
+    return bool(((j >= 0) & (ends[np.maximum(j, 0)] >= rlo + r.row_bytes)).all())
 
 
 # ------------------------------------------------------------------ what an op reads and writes
@@ -144,8 +151,54 @@ def _scratch_range(name, ptr, scratch, which):
     return Range(name, ptr, 1, base + n - ptr, scratch=True)
 
 
-def extents(op, scratch=None):
-    """(reads, writes) of one op record, from its raw arguments; scratch: the plan's shared scratch blocks {name: (address, bytes)}"""
+def phase_of(a):
+    """(py, px) of a phase launch of an upsampling convolution (mlsd_gemm_args.out_phase 1 .. 4), None for every other GEMM; fields the launcher would
+    refuse (mlsd_gemm_phase_form) and forms the audit has not met raise"""
+    if not a.out_phase:
+        if a.tap_oy or a.tap_ox:
+            raise Unknown(f"gemm with tap offsets ({a.tap_oy}, {a.tap_ox}) and no out_phase")
+        return None
+    if not 1 <= a.out_phase <= 4:
+        raise Unknown(f"gemm with out_phase {a.out_phase}")
+    py, px = (a.out_phase - 1) >> 1, (a.out_phase - 1) & 1
+    if (a.tap_oy, a.tap_ox) != (py, px):
+        raise Unknown(f"phase launch {a.out_phase} with tap offsets ({a.tap_oy}, {a.tap_ox})")
+    if (not a.conv or (a.KH, a.KW, a.stride, a.pad, a.upsample) != (2, 2, 1, 1, 0) or (a.OH, a.OW) != (a.H, a.W) or not a.C32 or a.C16 or a.resid or a.rowbias
+            or a.bias_m or a.act or a.colstats or a.ln_y16 or a.gn_y16 or a.xa_k):
+        raise Unknown(f"phase launch {a.out_phase} of a form that is no plain 2x2 convolution with an fp32 output")
+    return py, px
+
+
+def phase_pixel_ranges(a, name="C32"):
+    """what a phase launch writes: pixel (2 y + py, 2 x + px) of the [n_img][2 H][2 W] rows of ldc32 floats; per (image, y) W rows of N floats, two pixels apart"""
+    py, px = phase_of(a)
+    return [Range(name, a.C32 + ((n * 2 * a.H + 2 * y + py) * 2 * a.W + px) * a.ldc32 * 4, a.W, a.N * 4, 2 * a.ldc32 * 4)
+            for n in range(a.n_img) for y in range(a.H)]
+
+
+def tile_form(a):
+    """"" for a plain device copy, "tile" / "untile" for HyperTile's row permutation (mlb_copy_args.th > 0); arguments mlsd_tile_permute would refuse raise"""
+    if a.th <= 0:
+        if a.th or a.tw or a.inverse:
+            raise Unknown(f"copy with th {a.th}, tw {a.tw}, inverse {a.inverse}")
+        return ""
+    if a.tw <= 0 or a.n_img < 1 or a.H < 1 or a.W < 1 or a.row_bytes < 1 or a.H % a.th or a.W % a.tw:
+        raise Unknown(f"permuting copy of {a.n_img} maps of {a.H} x {a.W} rows in tiles of {a.th} x {a.tw}")
+    if a.nbytes != a.n_img * a.H * a.W * a.row_bytes:
+        raise Unknown(f"permuting copy of {a.nbytes} bytes for {a.n_img} x {a.H} x {a.W} rows of {a.row_bytes} bytes")
+    if a.inverse not in (0, 1):
+        raise Unknown(f"permuting copy with inverse {a.inverse}")
+    return "untile" if a.inverse else "tile"
+
+
+def _gain_of(mem, a):
+    """the gain a control sum read (None without a memory image: the static audit counts the residuals as read)"""
+    return None if mem is None else float(_vec(mem, a.gain, 1)[0])
+
+
+def extents(op, scratch=None, mem=None):
+    """(reads, writes) of one op record, from its raw arguments; scratch: the plan's shared scratch blocks {name: (address, bytes)}; mem: the memory image
+    after the evaluation, where there is one (a control sum whose gain is 0 never reads its residuals)"""
     k, a = op.kind, op.a
     rd, wr = [], []
     R_ = lambda *x, **y: rd.append(Range(*x, **y))
@@ -154,6 +207,7 @@ def extents(op, scratch=None):
         return rd, wr          # the producer's launch does it all (its ln_* / gn_* arguments)
     if k == "gemm":
         nout = _gemm_nout(a)
+        phase = phase_of(a)
         if a.conv:
             if a.K != a.KH * a.KW * a.Cin or a.M != a.n_img * a.OH * a.OW:
                 raise Unknown(f"conv with K {a.K} != {a.KH}x{a.KW}x{a.Cin} or M {a.M} != {a.n_img}x{a.OH}x{a.OW}")
@@ -180,7 +234,9 @@ def extents(op, scratch=None):
             R_("xa_k", a.xa_k, n_img * a.xa_Tk, a.N * 2, a.xa_ldk * 2)
             R_("xa_vt", a.xa_vt, 1, n_img * a.N * 96 * 2)
             W_("xa_out", a.xa_out, a.M, a.N * 2, a.xa_ldo * 2)
-        if a.C32:
+        if phase:
+            wr += phase_pixel_ranges(a)
+        elif a.C32:
             W_("C32", a.C32, a.M, nout * 4, a.ldc32 * 4)
         if a.C16 and not xattn:      # (a q projection that ends with its attention does not store the projection)
             W_("C16", a.C16, a.M, nout * 2, a.ldc16 * 2)
@@ -266,39 +322,76 @@ def extents(op, scratch=None):
         R_("in", a.in_, a.rows, a.cols * 4, a.ld_in * 4)
         W_("out", a.out, a.rows, a.cols * 2, a.ld_out * 2)
     elif k == "copy":
+        tile_form(a)
         R_("src", a.src, 1, a.nbytes)
         W_("dst", a.dst, 1, a.nbytes)
     elif k == "xavt":
         R_("v", a.v, a.n_img * a.Tk, a.N * 2, a.ldv * 2)
         W_("vt", a.vt, 1, a.n_img * a.N * 96 * 2)
-    elif k in ("cadd", "freeu_backbone", "freeu_skip"):
-        raise Unknown(f"{k}: not in audited plans")
+    elif k == "cadd":
+        if a.n_img < 1 or a.rows < 1 or not 1 <= a.n_ctrl <= a.n_img or a.C < 4 or a.C % 4 or min(a.ld_dst, a.ld_base, a.ld_ctrl) < a.C:
+            raise Unknown(f"control sum of {a.n_img} images of {a.rows} rows x {a.C} with {a.n_ctrl} control images, strides {a.ld_dst} {a.ld_base} {a.ld_ctrl}")
+        R_("base", a.base, a.n_img * a.rows, a.C * 4, a.ld_base * 4)
+        R_("gain", a.gain, 1, 4)
+        if _gain_of(mem, a) != 0.0:
+            R_("ctrl", a.ctrl, a.n_ctrl * a.rows, a.C * 4, a.ld_ctrl * 4)
+        W_("dst", a.dst, a.n_img * a.rows, a.C * 4, a.ld_dst * 4)
+    elif k in ("freeu_backbone", "freeu_skip"):
+        if a.n_img < 1 or a.H < 2 or a.W < 2 or a.C < 8 or a.C % 8 or min(a.ld_dst, a.ld_src) < a.C:
+            raise Unknown(f"{k} on {a.n_img} maps of {a.H} x {a.W} x {a.C}, strides {a.ld_dst} {a.ld_src}")
+        from mlimgsynth_amd import kernels
+        R_("src", a.src, a.n_img * a.H * a.W, a.C * 4, a.ld_src * 4)
+        R_("f", a.f, 1, 4)
+        W_("dst", a.dst, a.n_img * a.H * a.W, a.C * 4, a.ld_dst * 4)      # (the C columns the kernels write: a destination's padding keeps its bytes)
+        W_("ws", a.ws, 1, kernels.freeu_ws_bytes(a.n_img, a.H, a.W, a.C), scratch=True)
     else:
         raise Unknown(f"op kind {k!r}")
     return rd, wr
 
 
 # ------------------------------------------------------------------ the plan and its dataflow
+def ups_weights(ctx):
+    """[(address of the derived phase weights, fp16 [4][cout][2][2][cin]; address of the loaded 3x3 weight they are derived from, fp16 [cout][3][3][cin];
+    cout; cin)] of the plan's upsampling convolutions in the phase form (mlctx_ups_weights, mlctx_param_device).  A weight-streaming plan gives []: its
+    addresses are virtual ones that nothing may read."""
+    from mlimgsynth_amd import engine
+    f = engine.L().mlctx_ups_weights
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+    n = f(ctx.h, -1, None, None, None, None)
+    if not n or ctx.streaming_info() is not None:
+        return []
+    devs, out = ctx.param_devices(), []
+    for i in range(n):
+        pi, dev, cout, cin = ctypes.c_int(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        f(ctx.h, i, ctypes.byref(pi), ctypes.byref(dev), ctypes.byref(cout), ctypes.byref(cin))
+        out.append((dev.value or 0, devs[pi.value][1], cout.value, cin.value))
+    return out
+
+
 class Op:
     __slots__ = ("i", "kind", "label", "fused", "once", "gn_src", "a", "reads", "writes", "shape_label")
 
-    def __init__(self, i, kind, label, fused, once, gn_src, a, shape_label="", scratch=None):
+    def __init__(self, i, kind, label, fused, once, gn_src, a, shape_label="", scratch=None, mem=None):
         self.i, self.kind, self.label, self.fused, self.once, self.gn_src, self.a, self.shape_label = i, kind, label, fused, once, gn_src, a, shape_label
-        self.reads, self.writes = extents(self, scratch)
+        self.reads, self.writes = extents(self, scratch, mem)
 
     def __repr__(self):
         return f"op {self.i} ({self.kind} {self.shape_label or self.label})"
 
 
 class Plan:
-    """Snapshot of a prepared context: ops with their extents, the read-only regions, and an index of the writes in run order."""
+    """Snapshot of a prepared context: ops with their extents, the read-only regions, and an index of the writes in run order.
+    external: [(name, address, bytes)] of memory outside the context that its launches read (another plan's tensors, a driver's buffers): only what is
+    declared counts as written.  mem: the memory image after the evaluation (extents)."""
 
-    def __init__(self, ctx, name=""):
+    def __init__(self, ctx, name="", external=(), mem=None):
         self.name = name
         labels = [lab for lab, _ in ctx.op_list()]
         self.scratch = ctx.scratch_blocks()
-        self.ops = [Op(i, *rec, shape_label=labels[i], scratch=self.scratch) for i, rec in enumerate(ctx.op_records())]
+        self.ops = [Op(i, *rec, shape_label=labels[i], scratch=self.scratch, mem=mem) for i, rec in enumerate(ctx.op_records())]
+        self.ups = ups_weights(ctx)
         reg = [("parameter", key, p, n) for key, p, n in ctx.param_devices() if p and n]
+        reg += [("external", nm, p, n) for nm, p, n in external if p and n]
         reg += [("parameter", f"weight slab {k}", p, n) for k, (p, n) in enumerate(ctx.weight_slabs())]
         for nm, stage, nb, src, n_src, scale in ctx.input_records():
             reg.append(("input", nm, stage, nb))
@@ -327,7 +420,7 @@ class Plan:
         self._w_lo = np.array([self.ops[t[1]].writes[t[2]].lo for t in w], np.int64)
         self._w_hi = np.array([self.ops[t[1]].writes[t[2]].hi for t in w], np.int64)
 
-    def region_ranges(self, r, classes=("parameter", "input", "zeroed once")):
+    def region_ranges(self, r, classes=("parameter", "input", "zeroed once", "external")):
         """the read-only / zeroed regions that touch range r, as ranges"""
         out = []
         j = bisect.bisect_right(self._reg_lo, r.hi)
@@ -348,7 +441,7 @@ class Plan:
         return out
 
     def latest_writer(self, i, r):
-        """(op index, output name) of the last op that runs before op i and writes into r; else "parameter" / "input" / "zeroed once"; else None"""
+        """(op index, output name) of the last op that runs before op i and writes into r; else "parameter" / "input" / "zeroed once" / "external"; else None"""
         for j, wr in self.writers(r, 0, self.rank[i]):
             return j, wr.name
         for cls, _ in self.region_ranges(r):
@@ -370,7 +463,7 @@ def uncovered_reads(plan):
             if not covered_by(r, cov):
                 bad.append((o, r.name, f"{o} reads {r}: nobody wrote it (candidates {cov[:4]})"))
         for w in o.writes:
-            for cls, c in plan.region_ranges(w, classes=("parameter", "input")):
+            for cls, c in plan.region_ranges(w, classes=("parameter", "input", "external")):
                 if overlaps(w, c) and not (cls == "parameter" and w.name == "colstats"):      # (statistics buffers are allocated with the parameters)
                     bad.append((o, w.name, f"{o} writes {w} into {cls} {c}"))
     return bad
@@ -412,21 +505,32 @@ def lifetime_diffs(rec, kept):
             wk, wr = kept.latest_writer(ok.i, rk), rec.latest_writer(orr.i, rr)
             if wk != wr:
                 bad.append(f"{ok} operand {rk.name}: written by {wk} in the kept plan, by {wr} in the recycling plan")
-            if isinstance(wk, tuple):
-                last_reader[wk] = max(last_reader.get(wk, -1), kept.rank[ok.i])
+            if isinstance(wk, tuple):      # (the pixels of an upsampled map come from four phase launches: the reader keeps all of them alive)
+                for w in [wk] + phase_siblings(kept, wk):
+                    last_reader[w] = max(last_reader.get(w, -1), kept.rank[ok.i])
     for (j, nm), last in sorted(last_reader.items()):
-        w = next(x for x in rec.ops[j].writes if x.name == nm)
-        if w.scratch:
-            continue
         lo = rec.rank[j] + 1
-        for k, wr in rec.writers(w, lo, last):       # strictly between the writer and its last reader
-            if not (wr.scratch and w.scratch):
-                bad.append(f"{rec.ops[j]} output {nm} is rewritten by {rec.ops[k]} ({wr.name}) before its last reader {rec.ops[rec.order[last]]}")
-        if rec.ops[j].once:                        # never run again in later evaluations: nothing may ever write it
-            for k, wr in rec.writers(w, lo, len(rec.ops)):
-                if not rec.ops[k].once:
-                    bad.append(f"step-invariant {rec.ops[j]} output {nm} is rewritten by {rec.ops[k]} ({wr.name})")
+        sib = {k for k, _ in phase_siblings(rec, (j, nm))}      # (the phase launches write disjoint pixels of one map: no rewriting among themselves)
+        seen = set()
+        for w in (x for x in rec.ops[j].writes if x.name == nm and not x.scratch):
+            for k, wr in rec.writers(w, lo, last):       # strictly between the writer and its last reader
+                if k not in sib and (k, wr.name) not in seen:
+                    seen.add((k, wr.name))
+                    bad.append(f"{rec.ops[j]} output {nm} is rewritten by {rec.ops[k]} ({wr.name}) before its last reader {rec.ops[rec.order[last]]}")
+            if rec.ops[j].once:                        # never run again in later evaluations: nothing may ever write it
+                for k, wr in rec.writers(w, lo, len(rec.ops)):
+                    if not rec.ops[k].once:
+                        bad.append(f"step-invariant {rec.ops[j]} output {nm} is rewritten by {rec.ops[k]} ({wr.name})")
     return bad
+
+
+def phase_siblings(plan, w):
+    """the other phase launches, [(op index, "C32")], of the upsampled map that writer w = (op index, output) is a phase launch of; else []"""
+    j, nm = w
+    o = plan.ops[j]
+    if o.kind != "gemm" or nm != "C32" or not o.a.out_phase:
+        return []
+    return [(q.i, "C32") for q in plan.ops[max(0, j - 3):j + 4] if q.i != j and q.kind == "gemm" and q.a.out_phase and q.a.C32 == o.a.C32]      # (all four carry the map's base address)
 
 
 # ------------------------------------------------------------------ op lists without pointers (the keep flag must not change the plan)
@@ -446,20 +550,174 @@ def op_signature(o):
 class Built:
     """One prepared plan: .ctx (engine.MLCtx), .run(seed) -> the result tensor for seeded inputs (device only), .close()"""
 
-    def __init__(self, ctx, run, keep):
-        self.ctx, self.run, self._keep = ctx, run, keep
+    def __init__(self, ctx, run, keep, external=(), close=None, info=None):
+        self.ctx, self.run, self._keep, self.external, self._close, self.info = ctx, run, keep, list(external), close, info or {}
 
     def close(self):
         self.ctx.destroy()
+        if self._close:      # (what the plan read from outside itself lives until here: a ControlNet plan, the driver's buffers)
+            self._close()
 
 
 def _normal(seed, *shape):
     return np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
 
 
+GAIN, FREEU_FACTORS = 0.75, (1.4, 1.6, 0.9, 0.2)      # the control gain and the (b1, b2, s1, s2) of the option plans, as the feature tests use them
+
+
+def _control_lib():
+    import controlnet_ffi as CF
+    from mlimgsynth_amd import _lib
+    _lib.lib()
+    return CF, CF.bind(_lib.LIB_PATH), _lib
+
+
+def _upload(_lib, ptr, arr):
+    arr = np.ascontiguousarray(arr)
+    _lib.check(_lib.lib().mlsd_memcpy(_lib.vp(ptr), arr.ctypes.data_as(_lib.vp), ctypes.c_size_t(arr.nbytes), 0, None), "mlsd_memcpy")
+    _lib.check(_lib.lib().mlsd_stream_sync(None), "sync")
+
+
+def _unet_inputs(seed, P, n, lw, lh, n_ctx_tok):
+    x = _normal(seed, n, P.n_ch_in, lh, lw)
+    x += np.resize(np.array([0.0, 3.0, -10.0, 30.0], np.float32), P.n_ch_in)[None, :, None, None]      # channel means far from zero: badly conditioned first GroupNorm
+    cond = _normal(seed + 1, n, n_ctx_tok, P.n_ctx)
+    label = _normal(seed + 2, n, P.ch_adm_in) if P.ch_adm_in else None
+    sigma = np.linspace(0.7, 9.0, n).astype(np.float32) * (1 + seed % 3)
+    return x, cond, label, sigma
+
+
+class _ControlNet:
+    """A ControlNet plan at the context level (controlnet_init_nc / controlnet_build): .ctx, .K (UnetControl: where its residuals lie, for a UNet plan and for
+    reading them back), .run(seed, x, cond, label, sigma) on the first n images of a UNet plan's inputs with a seeded hint embedding."""
+
+    def __init__(self, engine, P, lw, lh, n, flags, synth, opt):
+        CF, self.lib, self._lib = _control_lib()
+        self.engine, self.P, self.n, self.lw, self.lh = engine, P, n, lw, lh
+        self.ctx = engine.MLCtx(flags=flags)
+        if opt.get("tiling"):
+            engine.set_conv_wrap(self.ctx, opt["tiling"])
+        if opt.get("hypertile"):
+            engine.set_hypertile(self.ctx, opt["hypertile"], opt.get("hypertile_depth", 3))
+        self.n_ctx_tok = int(opt.get("n_ctx_tok", 77))
+        self.S = CF.ControlState()
+        engine.check1(self.lib.controlnet_init_nc(ctypes.byref(self.S), self.ctx.h, ctypes.addressof(P), lw, lh, n, self.n_ctx_tok), "controlnet_init_nc")
+        engine.check1(self.lib.controlnet_build(ctypes.byref(self.S)), "controlnet_build")
+        if synth:
+            self.ctx.params_synth(1234)
+        self.gain = self._lib.from_numpy(np.array([GAIN], np.float32))
+        self.K = CF.UnetControl()
+        engine.check1(self.lib.controlnet_control(ctypes.byref(self.S), self.gain.ptr, ctypes.byref(self.K)), "controlnet_control")
+        ld = ctypes.c_int64()
+        self.hint = self.lib.mlctx_tensor_device_f32(self.ctx.h, self.S.t_hint, ctypes.byref(ld))
+        if not self.hint or ld.value != P.n_ch:
+            raise Unknown(f"ControlNet hint embedding at {self.hint} with rows of {ld.value} floats")
+        self.hint_bytes = n * lw * lh * P.n_ch * 4
+
+    def residuals(self):
+        """[(name, address, bytes)] of the residuals, from their first to their last element"""
+        K = self.K
+        return [(f"control residual {i}", K.r[i], ((K.n_img * K.rows[i] - 1) * K.ld[i] + K.c[i]) * 4) for i in range(K.n)]
+
+    def run(self, seed, x, cond, label, sigma):
+        e, lib, C, S, n = self.engine, self.lib, self.ctx.h, self.S, self.n
+        c_in = (1 / np.sqrt(sigma[:n].astype(np.float32) ** 2 + 1)).astype(np.float32)
+        xs = np.ascontiguousarray(x[:n] * c_in[:, None, None, None], np.float32)
+        ts = np.array([e.L().unet_sigma_to_t(ctypes.byref(self.P), float(s)) for s in sigma[:n]], np.float32)
+        for t, a in ((S.t_x, xs), (S.t_t, ts), (S.t_c, np.ascontiguousarray(cond[:n])), (S.t_l, None if label is None else np.ascontiguousarray(label[:n]))):
+            if t and a is not None:
+                e.check1(lib.mlctx_input_set(C, t, a.ctypes.data_as(ctypes.c_void_p), a.nbytes), "mlctx_input_set")
+        _upload(self._lib, self.hint, 0.5 * _normal(seed + 3, n, self.lh * self.lw, self.P.n_ch))
+        e.check1(lib.mlctx_compute_checked(C), "mlctx_compute_checked")
+        self.ctx.sync()
+
+    def read(self):
+        mem, K = DeviceMemory(self._lib), self.K
+        return np.concatenate([_mat(mem, K.r[i], K.n_img * K.rows[i], K.c[i], K.ld[i], np.float32).reshape(-1) for i in range(K.n)])
+
+    def close(self):
+        self.ctx.destroy()
+        self.gain.free()
+
+
+def _build_option_unet(engine, model, P, lw, lh, n, flags, synth, opt, option):
+    """the UNet plan with a ControlNet's residuals (control: images of the ControlNet plan; gain), FreeU (freeu) and / or the forced phase form of its upsampling
+    convolutions (ups_phases), at the context level: unet_denoise_build_freeu with a UnetControl and a UnetFreeU"""
+    CF, lib, _lib = _control_lib()
+    L = engine.L()
+    n_ctrl, gain, ups = option.get("control"), float(option.get("gain", GAIN)), option.get("ups_phases")
+    net = ff = None
+    ext, info = [], {}
+    if ups is not None:
+        L.mlsd_gemm_set_ups_phases(int(ups))
+    try:
+        if n_ctrl:      # the ControlNet plan first: the UNet plan is recorded on the addresses of its residuals
+            net = _ControlNet(engine, P, lw, lh, n_ctrl, flags, synth, opt)
+            _upload(_lib, net.gain.ptr, np.array([gain], np.float32))
+            ext += net.residuals() + [("control gain", net.gain.ptr, 4)]
+        un = engine.Unet.__new__(engine.Unet)
+        un.P, un.ctx = P, engine.MLCtx(None, flags)
+        if opt.get("hypertile"):
+            engine.set_hypertile(un.ctx, opt["hypertile"], opt.get("hypertile_depth", 3))
+        if opt.get("pag"):
+            L.mlctx_set_pag.restype, L.mlctx_set_pag.argtypes = None, [engine.vp, ctypes.c_int]
+            L.mlctx_set_pag(un.ctx.h, int(opt["pag"]))
+        if opt.get("tiling"):
+            engine.set_conv_wrap(un.ctx, opt["tiling"])
+        if set(opt) - {"hypertile", "hypertile_depth", "pag", "tiling", "n_ctx_tok"}:
+            raise Unknown(f"option plan with {sorted(opt)}")
+        un.S, un.lw, un.lh, un.n, un.n_ctx_tok = engine.UnetState(), lw, lh, n, int(opt.get("n_ctx_tok", 77))
+        engine.check1(L.unet_denoise_init_nc(ctypes.byref(un.S), un.ctx.h, ctypes.byref(P), lw, lh, n, un.n_ctx_tok), "unet_denoise_init_nc")
+        F = None
+        if option.get("freeu"):
+            ff = _lib.from_numpy(np.array(FREEU_FACTORS, np.float32))
+            F = CF.UnetFreeU(f=ff.ptr)
+            ext.append(("FreeU factors", ff.ptr, 16))
+        engine.check1(lib.unet_denoise_build_freeu(ctypes.addressof(un.S), ctypes.byref(net.K) if net else None, ctypes.byref(F) if F else None), "unet_denoise_build_freeu")
+        if F:
+            info["freeu_stages"] = (F.n_stage1, F.n_stage2)
+        if synth:
+            un.ctx.params_synth(1234)
+    finally:
+        if ups is not None:
+            L.mlsd_gemm_set_ups_phases(-1)
+
+    def poison_phase_outputs():      # an fp32 map the four phase launches fill: NaN before the evaluation, so an unwritten pixel is seen (kept plans: the block is the map's alone)
+        for kind, _, _, _, _, a in (un.ctx.op_records() if flags & MLB_F_KEEP else ()):
+            if kind == "gemm" and a.out_phase == 1:
+                _upload(_lib, a.C32, np.full(4 * a.M * a.ldc32, np.nan, np.float32))
+
+    def run(seed):
+        x, cond, label, sigma = _unet_inputs(seed, P, n, lw, lh, un.n_ctx_tok)
+        if ups is not None:      # (the launcher asks the mode again at every launch)
+            L.mlsd_gemm_set_ups_phases(int(ups))
+        try:
+            if net:
+                net.run(seed, x, cond, label, sigma)
+                if gain == 0.0:      # the residuals are never read then: poison them
+                    for _, ptr, nb in net.residuals():
+                        _upload(_lib, ptr, np.full(nb // 4, np.nan, np.float32))
+            poison_phase_outputs()
+            return un.run(x, cond, label, sigma)
+        finally:
+            if ups is not None:
+                L.mlsd_gemm_set_ups_phases(-1)
+
+    def close():
+        if net:
+            net.close()
+        if ff:
+            ff.free()
+    info["control"] = net
+    return Built(un.ctx, run, (un, P), ext, close, info)
+
+
 def build(engine, spec, flags=0, synth=False):
-    """spec: ("unet", model, lat | (lw, lh), n[, dict(n_ctx_tok=, tiling=, stream_weights_mib=, params=)]) | ("vae_dec" | "vae_enc" | "tae_dec" | "tae_enc", model, lat, n[, dict(tiling=)])
-    | ("clip", model, n_prompt).  synth: fill the parameters with the synthetic weights (seed 1234; needs a device)."""
+    """spec: ("unet", model, lat | (lw, lh), n[, dict(n_ctx_tok=, tiling=, stream_weights_mib=, params=, hypertile=, pag=, control=, gain=, freeu=, ups_phases=)])
+    | ("vae_dec" | "vae_enc" | "tae_dec" | "tae_enc", model, lat, n[, dict(tiling=)]) | ("clip", model, n_prompt) | ("controlnet", model, lat, n) | ("control_hint", model, lat).
+    control: the images of the ControlNet plan whose residuals the UNet plan adds (gain: 0.75), freeu: the FreeU passes with the factors (1.4, 1.6, 0.9, 0.2),
+    ups_phases: mlsd_gemm_set_ups_phases around build and run.  synth: fill the parameters with the synthetic weights (seed 1234; needs a device)."""
     kind, model, opt = spec[0], spec[1], (spec[4] if len(spec) > 4 else {})
     l = engine._proto2()
     vp, FP = engine.vp, engine.FP
@@ -467,6 +725,12 @@ def build(engine, spec, flags=0, synth=False):
         (lw, lh), n = (spec[2] if isinstance(spec[2], tuple) else (spec[2], spec[2])), spec[3]
         opt = dict(opt)
         over = opt.pop("params", None)
+        option = {k: opt.pop(k) for k in ("control", "gain", "freeu", "ups_phases") if k in opt}
+        if option:
+            P = engine.unet_params(model)
+            for k, v in (over or {}).items():
+                setattr(P, k, v)
+            return _build_option_unet(engine, model, P, lw, lh, n, flags, synth, opt, option)
         if over:      # the named configuration with other hyper-parameters (another width): engine.Unet asks unet_params for them
             orig = engine.unet_params
 
@@ -484,13 +748,35 @@ def build(engine, spec, flags=0, synth=False):
         P = un.P
 
         def run(seed):
-            x = _normal(seed, n, P.n_ch_in, lh, lw)
-            x += np.resize(np.array([0.0, 3.0, -10.0, 30.0], np.float32), P.n_ch_in)[None, :, None, None]      # channel means far from zero: badly conditioned first GroupNorm
-            cond = _normal(seed + 1, n, un.n_ctx_tok, P.n_ctx)
-            label = _normal(seed + 2, n, P.ch_adm_in) if P.ch_adm_in else None
-            sigma = np.linspace(0.7, 9.0, n).astype(np.float32) * (1 + seed % 3)
-            return un.run(x, cond, label, sigma)
+            return un.run(*_unet_inputs(seed, P, n, lw, lh, un.n_ctx_tok))
         return Built(un.ctx, run, un)
+    if kind in ("controlnet", "control_hint"):
+        P = engine.unet_params(model)
+        if kind == "controlnet":
+            lat, n = spec[2], spec[3]
+            net = _ControlNet(engine, P, lat, lat, n, flags, synth, opt)
+
+            def run(seed):
+                net.run(seed, *_unet_inputs(seed, P, n, lat, lat, net.n_ctx_tok))
+                return net.read()
+            # (the hint embedding is written by the driver straight into the plan's memory, by no launch; the gain is not read by this plan)
+            return Built(net.ctx, run, (net, P), [("hint embedding", net.hint, net.hint_bytes)], net.gain.free)
+        CF, lib, _lib = _control_lib()
+        lat, side = spec[2], 8 * spec[2]
+        ctx, t = engine.MLCtx(flags=flags), vp()
+        engine.check1(lib.control_hint_init(ctx.h, ctypes.addressof(P), side, side, ctypes.byref(t)), "control_hint_init")
+        engine.check1(lib.control_hint_build(ctx.h, ctypes.addressof(P), t), "control_hint_build")
+        if synth:
+            ctx.params_synth(1234)
+
+        def run(seed):
+            img = np.random.default_rng(seed).random((1, 3, side, side)).astype(np.float32)
+            out = np.empty((1, P.n_ch, lat, lat), np.float32)
+            engine.check1(lib.mlctx_input_set(ctx.h, t, img.ctypes.data_as(vp), img.nbytes), "mlctx_input_set")
+            engine.check1(lib.mlctx_compute_checked(ctx.h), "mlctx_compute_checked")
+            engine.check1(lib.mlctx_output_get(ctx.h, lib.mlctx_result(ctx.h), out.ctypes.data_as(vp), out.nbytes), "mlctx_output_get")
+            return out
+        return Built(ctx, run, (t, P))
     ctx = engine.MLCtx(flags=flags)
     if opt.get("tiling"):
         engine.set_conv_wrap(ctx, opt["tiling"])
@@ -691,9 +977,15 @@ def gemm_path(label):
     return tile, form, (R.K_STEP_GENERAL if tile in GENERAL_TILES else R.K_STEP_MFMA16), ns
 
 
-def _verify_gemm(mem, op):
+def _phase_launches(ops, op):
+    """{out_phase: op} of the phase launches in `ops` that write the upsampled map op writes"""
+    return {o.a.out_phase: o for o in ops if o.kind == "gemm" and o.a.out_phase and o.a.C32 == op.a.C32}
+
+
+def _verify_gemm(mem, op, ops=(), ups=()):
     from mlimgsynth_amd import kernels
     a = op.a
+    phase = phase_of(a)
     label = kernels.gemm_variant(a)
     tile, form, k_step, ns = gemm_path(label)
     M, N, K, nout = a.M, a.N, a.K, _gemm_nout(a)
@@ -701,7 +993,10 @@ def _verify_gemm(mem, op):
         raise Unknown(f"gemm activation {a.act}")
     if a.conv:
         x = _mat(mem, a.A, a.n_img * a.H * a.W, a.Cin, a.lda, np.float16)
-        A = R.im2col64(x, a.n_img, a.H, a.W, a.Cin, a.KH, a.KW, a.stride, a.pad, a.upsample, a.OH, a.OW, wrap=a.wrap)
+        if phase:
+            A = R.phase_A(x.reshape(a.n_img, a.H, a.W, a.Cin), phase[0], phase[1], a.wrap)
+        else:
+            A = R.im2col64(x, a.n_img, a.H, a.W, a.Cin, a.KH, a.KW, a.stride, a.pad, a.upsample, a.OH, a.OW, wrap=a.wrap)
     else:
         if a.upsample or a.wrap:
             raise Unknown("upsample / wrap on a launch that is no convolution")
@@ -716,7 +1011,33 @@ def _verify_gemm(mem, op):
                              bias_m=_vec(mem, a.bias_m, M) if a.bias_m else None, act=a.act,
                              resid=_mat(mem, a.resid, M, nout, a.ldr, np.float32) if a.resid else None, act_after_resid=bool(a.act_after_resid))
     out, got32 = {}, None
-    if a.C32:
+    if phase:
+        # the launch's pixels (2 y + py, 2 x + px) of the [n_img][2 H][2 W] map against its own operands; the bound of an fp32 convolution output
+        full = _mat(mem, a.C32, 4 * M, N, a.ldc32, np.float32).reshape(a.n_img, 2 * a.H, 2 * a.W, N)
+        out["C32"] = _worst(R.gemm_ratio32(full[:, phase[0]::2, phase[1]::2].reshape(M, N), y, b))
+        # The pixels of the other three parities are not this launch's.  When the evaluation has ended each of them holds what the launch of ITS parity
+        # wrote (that launch's own check says so, and a stray write that survived fails there or in the assembled map below), or, where the plan has no
+        # launch for a parity, still the poison the map was filled with
+        sib = _phase_launches(ops, op)
+        lone = [full[:, q >> 1::2, q & 1::2] for q in range(4) if q + 1 not in sib and q + 1 != a.out_phase]
+        out["other parities"] = 0.0 if all(np.isnan(v).all() for v in lone) else float("inf")
+        if a.out_phase == 4:      # the assembled map against float64 of the original form, upsample + 3x3 with the loaded weight: U16 S' + b (tests/test_upsample_phases_gpu.py)
+            if sorted(sib) != [1, 2, 3, 4] or any((o.a.A, o.a.bias, o.a.N, o.a.K, o.a.ldb, o.a.wrap, o.a.lda) != (a.A, a.bias, N, K, a.ldb, a.wrap, a.lda) for o in sib.values()):
+                raise Unknown(f"{op}: phase launch 4 without its three sibling launches on the same operands")
+            src = [u for u in ups if u[0] == sib[1].a.W_ and u[2] == N and u[3] == a.Cin]
+            if len(src) != 1 or any(sib[q].a.W_ != src[0][0] + (q - 1) * N * K * 2 for q in sib):
+                raise Unknown(f"{op}: phase launches whose weights are not the derived weights of one loaded 3x3 parameter")
+            w3 = _mat(mem, src[0][1], N, 9 * a.Cin, 9 * a.Cin, np.float16).astype(np.float64)
+            A3 = R.im2col64(x, a.n_img, a.H, a.W, a.Cin, 3, 3, 1, 1, 1, 2 * a.H, 2 * a.W, wrap=a.wrap)
+            y3 = (A3 @ w3.T + (_vec(mem, a.bias, N).astype(np.float64) if a.bias else 0.0)).reshape(full.shape)
+            w = 0.0
+            for q, o in sib.items():
+                qy, qx = phase_of(o.a)
+                acc_q, S_q = (acc, S) if q == 4 else R.gemm64(R.phase_A(x.reshape(a.n_img, a.H, a.W, a.Cin), qy, qx, a.wrap), _mat(mem, o.a.W_, N, K, a.ldb, np.float16))
+                _, b_q = R.gemm_epilogue64(acc_q, S_q, D, np.arange(M), np.arange(N), bias=_vec(mem, a.bias, N) if a.bias else None)
+                w = max(w, _worst(R.gemm_ratio32(full[:, qy::2, qx::2].reshape(M, N), y3[:, qy::2, qx::2].reshape(M, N), R.U16 * S_q + b_q)))
+            out["assembled"] = w
+    elif a.C32:
         got32 = _mat(mem, a.C32, M, nout, a.ldc32, np.float32)
         out["C32"] = _worst(R.gemm_ratio32(got32, y, b))
     if a.xa_k:
@@ -762,7 +1083,7 @@ def _verify_gemm(mem, op):
         got = _mat(mem, a.gn_y16, M, N, a.gn_ldy, np.float16).reshape(x.shape)
         want = R.groupnorm64(x, None, a.gn_groups, a.gn_eps, g, be, bool(a.gn_silu))
         out["gn_y16"] = _worst(R.groupnorm_worst(got, want, x, a.gn_groups, a.gn_eps, g, be)[0])
-    return (op.kind, f"{tile} {form}".strip()), out
+    return (op.kind, f"{tile} {form}".strip() + (" phase" if phase else "")), out
 
 
 def _verify_attn(mem, op):
@@ -868,7 +1189,12 @@ def _verify_small(mem, op):
         p, b = R.softmax_rows64(x, a.scale)
         return (k, ""), {"out": _worst(R.gemm_ratio16(_mat(mem, a.out, a.rows, a.cols, a.ld_out, np.float16), p, b))}
     if k == "copy":
-        return (k, ""), {"dst": _bits_equal(mem.read(a.dst, a.nbytes), mem.read(a.src, a.nbytes))}
+        form = tile_form(a)
+        want = np.array(mem.read(a.src, a.nbytes))
+        if form:      # HyperTile's row permutation: image order -> tile-major order, or back
+            import hypertile_ref as HR
+            want = HR.permute_rows(want.reshape(a.n_img * a.H * a.W, a.row_bytes), a.n_img, a.H, a.W, a.th, a.tw, inverse=bool(a.inverse)).reshape(-1)
+        return (k, form), {"dst": _bits_equal(np.array(mem.read(a.dst, a.nbytes)), want)}
     if k == "xavt":
         if a.Tk > 96:
             raise Unknown("xattn_pack_vt beyond 96 keys")
@@ -876,21 +1202,59 @@ def _verify_small(mem, op):
         want = np.zeros((a.n_img, a.N, 96), np.float16)
         want[:, :, :a.Tk] = v.transpose(0, 2, 1)
         return (k, ""), {"vt": _bits_equal(_vec(mem, a.vt, a.n_img * a.N * 96, np.float16).reshape(want.shape), want)}
-    if k in ("cadd", "freeu_backbone", "freeu_skip"):
-        raise Unknown(f"{k}: not in audited plans")
+    if k == "cadd":
+        # dst = base + gain ctrl, image n with residual image n % n_ctrl (the rows of ctrl modulo its row count); |err| <= 2^-23 (|base| + |gain ctrl|), derived in
+        # tests/test_controlnet_gpu.py.  Gain 0 (or -0): the bits of base, and ctrl is never read
+        rows = a.n_img * a.rows
+        gain = _gain_of(mem, a)
+        base, got = _mat(mem, a.base, rows, a.C, a.ld_base, np.float32), _mat(mem, a.dst, rows, a.C, a.ld_dst, np.float32)
+        if gain == 0.0:
+            return (k, "gain 0"), {"dst": _bits_equal(got, base)}
+        ctrl = _mat(mem, a.ctrl, a.n_ctrl * a.rows, a.C, a.ld_ctrl, np.float32)
+        kb = ctrl[np.arange(rows) % (a.n_ctrl * a.rows)].astype(np.float64) * gain
+        want = base.astype(np.float64) + kb
+        return (k, ""), {"dst": _worst(R.gemm_ratio32(got, want, 2.0 ** -23 * (np.abs(base).astype(np.float64) + np.abs(kb))))}
+    if k in ("freeu_backbone", "freeu_skip"):
+        # the bounds `skip` and `backbone` derived in tests/test_freeu_gpu.py; a factor of exactly 1 is a bit copy
+        import freeu_ref as FR
+        from mlimgsynth_amd import kernels
+        n, H, W, C, u = a.n_img, a.H, a.W, a.C, R.U32
+        f = float(_vec(mem, a.f, 1)[0])
+        src, got = _mat(mem, a.src, n * H * W, C, a.ld_src, np.float32), _mat(mem, a.dst, n * H * W, C, a.ld_dst, np.float32)
+        if f == 1.0:
+            return (k, "factor 1"), {"dst": _bits_equal(got, src)}
+        x64 = src.astype(np.float64).reshape(n, H, W, C).transpose(0, 3, 1, 2)
+        nhwc = lambda v: v.transpose(0, 2, 3, 1).reshape(n * H * W, C)
+        if k == "freeu_skip":
+            D = kernels.freeu_depth(H * W)
+            A = np.broadcast_to(4.0 / (H * W) * np.abs(x64).sum(axis=(2, 3), keepdims=True), x64.shape)
+            ref = FR.fourier_filter64(x64, f)
+            return (k, ""), {"dst": _worst(R.gemm_ratio32(got, nhwc(ref), u * (2 * np.abs(nhwc(ref)) + abs(f - 1) * (D + 16) * nhwc(A))))}
+        D = kernels.freeu_depth(C)
+        m = x64.mean(axis=1)
+        span = m.max(axis=(1, 2)) - m.min(axis=(1, 2))
+        delta = u * (D + 2) * np.abs(x64).mean(axis=1).max(axis=(1, 2))
+        for i in range(n):      # the bound's condition on the data (a nearly constant mean map has no normalised form): a failure by name, never a skip
+            if not (span[i] > 0 and delta[i] / span[i] <= 1e-4):
+                raise Unknown(f"{op}: image {i}: delta / (max - min) = {delta[i]:.3g} / {span[i]:.3g} of the channel-mean map is above 1e-4, the backbone bound does not hold")
+        slack = np.broadcast_to((3 * delta / span + 4 * u)[:, None, None, None], x64.shape)
+        ref = nhwc(FR.backbone64(x64, f))
+        bound = 2 * u * np.abs(ref) + np.abs(src.astype(np.float64)) * abs(f - 1) * nhwc(slack)
+        return (k, ""), {"dst": _worst(R.gemm_ratio32(got, ref, bound)), "kept half": _bits_equal(got[:, C // 2:], src[:, C // 2:])}
     raise Unknown(f"op kind {k!r}")
 
 
 def verify_op(mem, plan, i):
     """((kind, path), {output: worst ratio to its bound}) of op i recomputed in float64 from the operands it read; exact ops give 0 or inf.
     A `fused` LayerNorm / GroupNorm gives {}: it is checked as the ending of its producer (ln_y16 / gn_y16 there).  Unknown kinds and arguments raise."""
-    op = plan.ops[i] if isinstance(plan, Plan) else plan[i]
+    ops = plan.ops if isinstance(plan, Plan) else plan
+    op = ops[i]
     if op.fused:
         if op.kind not in ("ln", "gn"):
             raise Unknown(f"{op}: fused mark on a {op.kind}")
         return (op.kind, "ending of its producer"), {}
-    if op.kind == "gemm":
-        return _verify_gemm(mem, op)
+    if op.kind == "gemm":      # (a phase launch of an upsampling convolution is judged with its sibling launches and the loaded 3x3 weight: the plan's `ups`)
+        return _verify_gemm(mem, op, ops[max(0, i - 3):i + 4] if op.a.out_phase else (), getattr(plan, "ups", ()))
     if op.kind in ("attn", "attn_ctx"):
         return _verify_attn(mem, op)
     if op.kind == "gn":
@@ -911,7 +1275,7 @@ def census_key(op):
         path = (tile, form)
         for name, on in (("row bias", a.rowbias), ("residual", a.resid), ("act_after_resid", a.act_after_resid), ("GEGLU", a.act == 5),
                          ("C16 + C32", a.C16 and a.C32 and not a.xa_k), ("colstats", a.colstats), ("LN ending", a.ln_y16), ("GN ending", a.gn_y16),
-                         ("xattn ending", a.xa_k), ("upsample", a.upsample), ("wrap", a.conv and a.wrap)):
+                         ("xattn ending", a.xa_k), ("upsample", a.upsample), ("wrap", a.conv and a.wrap), ("phase", phase_of(a))):
             if on:
                 f.add(name)
     elif op.kind in ("attn", "attn_ctx"):
@@ -924,6 +1288,8 @@ def census_key(op):
         path = f"act {a.act}"
     elif op.kind == "n2h":
         path = f"mode {a.mode}"
+    elif op.kind == "copy":
+        path = tile_form(a)
     if op.once:
         f.add("once")
     if op.fused:

@@ -270,6 +270,24 @@ def im2col64(x, n_img, H, W, Cin, KH, KW, stride, pad, ups, OH, OW, rows=None, w
     return out.reshape(len(m), KH * KW * Cin)
 
 
+def phase_A(x, py, px, wrap):
+    """float64 A operand [n H W][2][2][Cin] of phase (py, px) of an upsampling convolution's phase form (mlsd_gemm_args.tap_oy / tap_ox = py / px): x is the
+    NHWC source [n][H][W][Cin]; source pixel (y - 1 + py + a, x - 1 + px + b), zero or wrapped outside"""
+    n, H, W, C = x.shape
+    out = np.zeros((n, H, W, 2, 2, C))
+    for a in range(2):
+        for b in range(2):
+            iy, ix = np.arange(H) - 1 + py + a, np.arange(W) - 1 + px + b
+            if wrap & 2:
+                iy = iy % H
+            if wrap & 1:
+                ix = ix % W
+            oky, okx = (iy >= 0) & (iy < H), (ix >= 0) & (ix < W)
+            g = x[:, np.clip(iy, 0, H - 1)][:, :, np.clip(ix, 0, W - 1)].astype(np.float64)
+            out[:, :, :, a, b, :] = g * oky[None, :, None, None] * okx[None, None, :, None]
+    return out.reshape(n * H * W, 4 * C)
+
+
 def gemm64(A, Wt):
     """C = A . W^T and S = |A| . |W|^T in float64, from the fp16 operand values."""
     A, Wt = np.asarray(A, np.float64), np.asarray(Wt, np.float64)

@@ -286,7 +286,7 @@ AUDITED = [("unet", "tiny", 16, 2, dict(hypertile=64)), ("unet", "tinyxl", (20, 
 
 @pytest.mark.parametrize("spec", AUDITED, ids=[PA.plan_id(s) for s in AUDITED])
 def test_dataflow_of_tiled_plans(spec):
-    """the plan audit's dataflow checks (not its launch verifier, which models a copy as linear): every read has a writer, no launch writes onto its own operand
+    """the plan audit's dataflow checks (its launch verifier runs on the device, tests/test_plan_audit_gpu.py): every read has a writer, no launch writes onto its own operand
     but the LayerNorm ending's sound form, and the recycling arena never changes who wrote what a launch reads"""
     from mlimgsynth_amd import _lib, engine
     L = _lib.lib()

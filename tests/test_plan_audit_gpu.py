@@ -5,14 +5,26 @@ weights, computed once, and then EVERY launch is recomputed in float64 from the 
 column views, producer statistics, LayerNorm endings, hoisted ops -- and held to the per-element / per-row bounds of tests/ref64.py.  With -s the
 worst ratio per (kind, path) is printed.  The second test compares the default (recycling) plan with the kept plan bit for bit: the arena must
 not change a result.
+
+The option plans are audited the same way (tests/plan_audit.py has their rules): a UNet with the control sums of a ControlNet plan of fewer images, the same at
+gain 0 with poisoned residuals, the ControlNet plan and its hint block, FreeU, control + PAG (the third row group reads the cond group's residuals), HyperTile with
+and without PAG (permuting copies bit for bit, per-tile attention, pag_v_proj in tile-major order), and the forced phase form of the upsampling convolution, plain
+and with seamless tiling, on a poisoned map.  What those plans read from outside themselves is declared by the builder; an undeclared range fails the coverage check.
+
+Measured on MI355X, worst ratio to the bound over these plans: control sum 0.982 (the bound is attained where the base vanishes; gain 0: bit-equal), freeu_backbone
+0.063 (the kept half bit-equal), freeu_skip 0.210, tile / untile copies bit-equal, phase launches against their own operands 0.021, the assembled map against
+upsample + 3x3 with the loaded weight 0.131 (0.069 with seamless tiling), no pixel of another parity or of the poison left.
 """
 import contextlib
 import os
+import re
 
 import numpy as np
 import pytest
 
 import plan_audit as PA
+import test_hypertile_cpu as THC
+import test_pag_cpu as TPC
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +44,24 @@ AUDITED = [
     # 16 x 8 = 128 tokens at the attention level): K / V as column views of the batched context projection, the hoisted V^T pack, a q projection that stores no C16
     (("unet", "tinyxl", (32, 16), 2, dict(params=dict(n_ch=320, ch_mult=(1, 1, 0, 0, 0)))), 2, {"gemm", "attn", "xavt"}),
     (("unet", "sd1", 8, 2, dict(n_ctx_tok=154)), None, {"attn_ctx"}),             # windowed context: OP_ATTN_CTX
+    # ---- the option plans.  ControlNet: the UNet's control sums on the residuals of a ControlNet plan of ONE image (image n reads residual image n % 1), the same
+    # with gain 0 (the sums are bit copies and the residuals, poisoned, are never read), the ControlNet plan itself and its hint block
+    (("unet", "tinyxl", 16, 2, dict(control=1)), None, {"cadd"}),
+    (("unet", "tinyxl", 16, 2, dict(control=1, gain=0.0)), None, {"cadd"}),
+    (("controlnet", "tinyxl", 16, 1), None, {"gemm", "gn", "attn"}),
+    (("control_hint", "tinyxl", 16), None, {"gemm", "n2h"}),
+    (("unet", "tinyxl", 16, 2, dict(freeu=True)), None, {"freeu_backbone", "freeu_skip"}),      # both stages; the half kept; the padding
+    (("unet", "tinyxl", 16, 3, dict(control=2, pag=1)), None, {"cadd"}),          # pag_tail: row group 3 reads the cond residuals; the pag_v_proj GEMM
+    # HyperTile (non-square tiles at 20 x 12 and 16 x 24) and PAG inside tiles: pag_v_proj's rows in tile-major order.  The permuting copies, the per-tile attention
+    # (n_batch = images x tiles, batch strides of a tile) and pag_v_proj (a GEMM on a row slice of the fused q | k | v weight into the tail rows of the attention
+    # output) are judged by the copy rule above and by the unchanged GEMM and attention verifiers, from their raw arguments: the audit needed no code for them
+    (THC.AUDITED[0], None, {"copy", "attn"}), (THC.AUDITED[1], None, {"copy", "attn"}), (THC.AUDITED[2], None, {"copy", "attn"}),
+    (TPC.AUDITED[2], None, {"copy", "attn"}),
+    # the phase form of the upsampling convolution, forced (320 channels on both levels: a form the ping-pong tiles take), plain and with seamless tiling
+    (("unet", "tinyxl", (32, 16), 2, dict(params=dict(n_ch=320, ch_mult=(1, 1, 0, 0, 0)), ups_phases=2)), None, {"gemm"}),
+    (("unet", "tinyxl", (32, 16), 2, dict(params=dict(n_ch=320, ch_mult=(1, 1, 0, 0, 0)), ups_phases=2, tiling=3)), None, {"gemm"}),
 ]
+assert THC.AUDITED[2] == ("unet", "sd1", (16, 24), 2, dict(hypertile=64)) and TPC.AUDITED[2] == ("unet", "tiny", 16, 6, dict(pag=2, hypertile=32))
 # + the SDXL real configuration at the smallest latent its three levels accept, for the bit comparison only
 BITWISE = [(s, x) for s, x, _ in AUDITED] + [(("unet", "sdxl", 4, 2), None)]
 
@@ -67,11 +96,13 @@ def test_every_launch_against_float64(E, spec, xattn, kinds):
     with _built(E, spec, xattn, KEEP, True) as b:
         out = b.run(1)
         assert np.isfinite(out).all()
-        plan = PA.Plan(b.ctx, PA.plan_id(spec))
+        mem = PA.DeviceMemory(_lib)
+        plan = PA.Plan(b.ctx, PA.plan_id(spec), external=b.external, mem=mem)
         assert kinds <= {o.kind for o in plan.ops}, sorted({o.kind for o in plan.ops})
         gone = PA.clobbered_operands(plan)
         assert not gone, [f"{w} ({wn}) overwrites operand {rn} of {r}" for w, wn, r, rn in gone[:8]]
-        mem = PA.DeviceMemory(_lib)
+        uncovered = PA.uncovered_reads(plan)      # (what the plan reads from outside itself -- residuals, gain, FreeU factors, hint embedding -- is declared by the builder)
+        assert not uncovered, [why for _, _, why in uncovered[:6]]
         worst, bad = {}, []
         for i, op in enumerate(plan.ops):
             if op.fused:      # checked as the ending of its producer, which must carry it
@@ -88,9 +119,43 @@ def test_every_launch_against_float64(E, spec, xattn, kinds):
         for k, r in sorted(worst.items(), key=str):
             print(f"  {k[0]:9s} {str(k[1]):44s} {k[2]:14s} {r:8.3f}")
         assert not bad, bad[:12]
+        _option_forms(spec, plan, worst, b)
         if xattn:      # the plan is here for the ending: it must have been taken, checked and fed by the hoisted pack
             assert n_xa > 0 and any(k[2] == "xa_out" for k in worst) and any(k[0] == "xavt" for k in worst), (n_xa, sorted(worst, key=str))
             assert all(not any(w.name == "C16" for w in o.writes) for o in plan.ops if o.kind == "gemm" and o.a.xa_k)
+
+
+def _option_forms(spec, plan, worst, b):
+    """the forms an option plan is in AUDITED for: present, and judged by their own rule"""
+    opt = spec[4] if len(spec) > 4 and isinstance(spec[4], dict) else {}
+    seen = {k[:2] for k in worst}
+    cadd = [o for o in plan.ops if o.kind == "cadd"]
+    if opt.get("control"):
+        assert cadd and all(o.a.n_ctrl == opt["control"] < o.a.n_img == spec[3] for o in cadd)
+        zero = opt.get("gain") == 0.0
+        assert (("cadd", "gain 0") in seen) == zero and (("cadd", "") in seen) != zero
+        assert all(("ctrl" in [r.name for r in o.reads]) != zero for o in cadd)
+        assert all(np.isnan(PA._mat(PA.DeviceMemory(b.info["control"]._lib), o.a.ctrl, 1, o.a.C, o.a.C, np.float32)).all() == zero for o in cadd)
+    if opt.get("pag"):
+        assert any(o.kind == "gemm" and o.label == "pag_v_proj" for o in plan.ops)
+        if opt.get("control"):      # pag_tail: the third row group adds the cond group's residuals
+            assert all(o.a.n_img == o.a.n_ctrl + opt["pag"] for o in cadd)
+    if opt.get("freeu"):
+        n1, n2 = b.info["freeu_stages"]
+        assert n1 > 0 and n2 > 0 and ("freeu_backbone", "") in seen and ("freeu_skip", "") in seen and any(k[2] == "kept half" for k in worst)
+        assert sum(1 for o in plan.ops if o.kind == "freeu_skip") == n1 + n2 == sum(1 for o in plan.ops if o.kind == "freeu_backbone")
+    if opt.get("hypertile"):
+        cp = [o for o in plan.ops if o.kind == "copy" and o.a.th > 0]
+        assert ("copy", "tile") in seen and ("copy", "untile") in seen and len(cp) % 2 == 0
+        for c in cp:      # every tiled level has self-attentions over its tiles: n_batch = images x tiles, a tile's tokens each
+            nt = (c.a.H // c.a.th) * (c.a.W // c.a.tw)
+            assert any(o.kind == "attn" and o.a.Tq == o.a.Tk == c.a.th * c.a.tw and o.a.n_batch % nt == 0 and 0 < o.a.n_batch // nt <= c.a.n_img for o in plan.ops), c
+        if isinstance(spec[2], tuple):      # maps that are not square; at 20 x 12 the second level (10 x 6 tokens) is cut into tiles that are not square either
+            assert all(c.a.H != c.a.W for c in cp) and (spec[2] != (20, 12) or any(c.a.th != c.a.tw for c in cp))
+    if opt.get("ups_phases"):
+        ph = [o for o in plan.ops if o.kind == "gemm" and o.a.out_phase]
+        assert [o.a.out_phase for o in ph] == [1, 2, 3, 4] and all(bool(o.a.wrap) == bool(opt.get("tiling")) for o in ph)
+        assert {k[2] for k in worst if k[0] == "gemm" and str(k[1]).endswith("phase")} == {"C32", "other parities", "assembled"}
 
 
 def _two_evaluations(E, spec, xattn, flags):
@@ -181,6 +246,9 @@ COVERED_ELSEWHERE = {
     ('gemm', ('conv3x3n16', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[n31_vae_out]",
     ('gemm', ('skinny128x64', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[s29_m8_c16]",
     ('xavt', '', ('once',)): "test_conditioning_gpu.py::test_attention_fused_into_the_q_projection",
+    # the phase launches of the SDXL UNet's upsampling convolutions (128 x 128 latent, N = 8) run on the 128x320 ping-pong tile; the audited plans above meet the form
+    # on the 256x256 tile, which is the one the KL-VAE decoders' phase launches take
+    ('gemm', ('128x320x64pp', ''), ('phase',)): "test_upsample_phases_gpu.py::test_phase_launches_and_assembled_output_float64[t18_b1_w0_h4]",
 }
 
 
@@ -192,6 +260,15 @@ def test_covered_elsewhere_names_cases_of_exactly_that_form():
         if kind == "gemm" and where.startswith("test_gemm_float64_gpu.py"):
             c = GC.BY_ID[cid]
             assert not c["exp"] and PA.gemm_path(c["variant"])[:2] == path and _case_features(c) == set(feats) - {"once"}, (kind, path, feats, cid)
+        elif kind == "gemm" and where.startswith("test_upsample_phases_gpu.py::test_phase_launches_and_assembled_output_float64["):
+            # a phase form: the case's own launch arguments (all four) must have exactly this key -- the tile the launcher routes them to, out_phase set, wrap or not
+            import test_upsample_phases_gpu as UP
+            from mlimgsynth_amd import kernels
+            tile, bias_on, wrap, H = map(int, re.fullmatch(r"t(\d+)_b(\d)_w(\d)_h(\d+)", cid).groups())
+            assert (tile, bias_on, wrap, H) in UP.CASES and "phase" in feats, cid
+            for ph in range(4):
+                a = UP.phase_launch_args(kernels, 0x10000, (UP.N_IMG, H, UP.W_SRC, UP.CIN), 0x20000, 0x30000 if bias_on else None, UP.TILES[tile][1], tile, wrap, 0x40000, ph)
+                assert a.out_phase == 1 + ph and PA.census_key(PA.Op(0, "gemm", "", 0, 0, (-1, -1), a)) == (kind, path, tuple(sorted(set(feats) - {"once"}))), (cid, ph)
         elif kind in ("attn", "attn_ctx") and where.startswith("test_attention_float64_gpu.py"):
             assert any(c["id"] == cid and c["variant"] == path for c in AC.CASES), (path, cid)
         else:
@@ -218,3 +295,10 @@ def test_every_op_form_of_the_bench_plans_is_audited_or_covered(E):
         print(f"  {k} ({', '.join(need[k])}): {COVERED_ELSEWHERE.get(k)}")
     missing = [k for k in others if k not in COVERED_ELSEWHERE]
     assert not missing, f"op forms of the bench plans that no audited plan contains and COVERED_ELSEWHERE does not list: {missing}"
+    # the forms of the option plans are met, and the census sees the phase form the bench plans run (it has a key of its own, not a plain convolution's)
+    for want in (("cadd", "", ()), ("freeu_backbone", "", ()), ("freeu_skip", "", ()), ("copy", "tile", ()), ("copy", "untile", ())):
+        assert want in audited, want
+    phase = sorted((k for k in need if k[0] == "gemm" and "phase" in k[2]), key=str)
+    print(f"[plan audit] census: phase forms of the bench plans: {[(k, need[k]) for k in phase]}")
+    assert phase and any("unet-sdxl" in p for k in phase for p in need[k]) and any(k[0] == "gemm" and "phase" in k[2] for k in audited)
+    assert all(k in audited or COVERED_ELSEWHERE[k].startswith("test_upsample_phases_gpu.py") for k in phase)

@@ -17,7 +17,6 @@ Measured on MI355X (worst ratio to the bound over all cases): phase launches 0.0
 forced / off rel-L2: UNet 5.3e-4 (1.44e-3 / 0.89e-3 against the oracle forced, 1.41e-3 / 0.87e-3 off), decoder 4.1e-4 (9.6e-4 against the oracle forced, 8.4e-4 off).
 """
 import ctypes
-import itertools
 
 import numpy as np
 import pytest
@@ -55,30 +54,22 @@ def operands():
     return x, w, bias
 
 
-def phase_A(x, py, px, wrap):
-    """float64 A operand [n H W][2][2][Cin] of phase (py, px): source pixel (y - 1 + py + a, x - 1 + px + b), zero or wrapped outside"""
-    n, H, W, C = x.shape
-    out = np.zeros((n, H, W, 2, 2, C))
-    for a, b in itertools.product(range(2), repeat=2):
-        iy, ix = np.arange(H) - 1 + py + a, np.arange(W) - 1 + px + b
-        if wrap & 2:
-            iy = iy % H
-        if wrap & 1:
-            ix = ix % W
-        oky, okx = (iy >= 0) & (iy < H), (ix >= 0) & (ix < W)
-        g = x[:, np.clip(iy, 0, H - 1)][:, :, np.clip(ix, 0, W - 1)].astype(np.float64)
-        out[:, :, :, a, b, :] = g * oky[None, :, None, None] * okx[None, None, :, None]
-    return out.reshape(n * H * W, 4 * C)
+phase_A = R.phase_A      # (the A operand of a phase launch: shared with the plan audit)
+
+
+def phase_launch_args(kernels, x_ptr, shape, w_ptr, bias_ptr, N, tile, wrap, out_ptr, ph):
+    """the arguments of phase launch ph (0 .. 3) of a case: also what the census of tests/test_plan_audit_gpu.py reads a case's form from"""
+    n, H, W, C = shape
+    return kernels.GemmArgs(A=x_ptr, lda=C, conv=1, n_img=n, H=H, W=W, Cin=C, OH=H, OW=W, KH=2, KW=2, stride=1, pad=1,
+                            W_=w_ptr + ph * N * 4 * C * 2, ldb=4 * C, M=n * H * W, N=N, K=4 * C, bias=bias_ptr, C32=out_ptr, ldc32=N,
+                            tile_variant=kernels.tile_arg(tile), wrap=wrap, tap_oy=ph >> 1, tap_ox=ph & 1, out_phase=1 + ph)
 
 
 def run_phases(K, x, wdev, bias_dev, N, tile, wrap, out32):
     kernels, _lib = K
-    n, H, W, C = x.shape
     xd = _lib.from_numpy(x)
     for ph in range(4):
-        a = kernels.GemmArgs(A=xd.ptr, lda=C, conv=1, n_img=n, H=H, W=W, Cin=C, OH=H, OW=W, KH=2, KW=2, stride=1, pad=1,
-                             W_=wdev.ptr + ph * N * 4 * C * 2, ldb=4 * C, M=n * H * W, N=N, K=4 * C, bias=bias_dev, C32=out32.ptr, ldc32=N,
-                             tile_variant=kernels.tile_arg(tile), wrap=wrap, tap_oy=ph >> 1, tap_ox=ph & 1, out_phase=1 + ph)
+        a = phase_launch_args(kernels, xd.ptr, x.shape, wdev.ptr, bias_dev, N, tile, wrap, out32.ptr, ph)
         assert kernels.gemm_variant(a) == f"gemm<{TILES[tile][0]},conv>"
         kernels.gemm(a)
     kernels.sync()

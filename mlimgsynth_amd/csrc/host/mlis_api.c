@@ -133,10 +133,6 @@ static const char* const k_method[] = { "none", "euler", "heun", "taylor3", "dpm
 static const char* const k_sched[] = { "none", "uniform", "karras" };
 static const char* const k_model[][2] = { {"none","None"}, {"sd1","Stable Diffusion 1.x"}, {"sd2","Stable Diffusion 2.x"}, {"sdxl","Stable Diffusion XL"} };
 static const struct { const char* n; int id; } k_loglvl[] = { {"none",0}, {"error",10}, {"warning",20}, {"info",30}, {"verbose",40}, {"debug",50}, {"max",255} };
-static const char* const k_option[] = { "none", "backend", "model", "tae", "lora_dir", "lora", "lora_clear", "prompt", "nprompt", "image_dim",
-	"batch_size", "clip_skip", "cfg_scale", "method", "scheduler", "steps", "f_t_ini", "f_t_end", "s_noise", "s_ancestral", "image",
-	"image_mask", "no_decode", "tensor_use_flags", "seed", "vae_tile", "unet_split", "threads", "dump_flags", "aux_dir", "callback",
-	"error_handler", "log_level", "model_type", "weight_type", "no_prompt_parse" };
 #define COUNTOF(a) ((int)(sizeof(a)/sizeof((a)[0])))
 
 static int from_list(const char* const* list, int n, int stride, const char* s, size_t len)
@@ -153,69 +149,13 @@ MLB_API const char* mlis_sched_str(MLIS_Scheduler x) { return (x >= 0 && x < COU
 MLB_API MLIS_Scheduler mlis_sched_fromz(const char* s) { return (MLIS_Scheduler)from_list(k_sched, COUNTOF(k_sched), 1, s, strlen(s)); }
 MLB_API const char* mlis_loglvl_str(MLIS_LogLvl id) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (k_loglvl[i].id == (int)id) return k_loglvl[i].n; return "???"; }
 MLB_API MLIS_LogLvl mlis_loglvl_fromz(const char* s) { for (int i=0;i<COUNTOF(k_loglvl);++i) if (id_eq(s, strlen(s), k_loglvl[i].n)) return (MLIS_LogLvl)k_loglvl[i].id; return (MLIS_LogLvl)-1; }
-static const char* const k_option_amd[] = { "tiling", "hires_scale", "hires_denoise", "hires_steps", "hires_upscaler" };   /* ids from MLIS_OPT_AMD_TILING */
 static const char* const k_tiling[] = { "none", "x", "y", "xy" };
 static const char* const k_resample[] = { "nearest", "bilinear", "bicubic" };
-static const char* const k_option_amd2[] = { "unet_tile", "unet_tile_overlap" };            /* ids from MLIS_OPT_AMD_UNET_TILE */
-static const char* const k_option_amd3[] = { "unet_tile_batch" };                           /* ids from MLIS_OPT_AMD_UNET_TILE_BATCH */
-static const char* const k_option_amd4[] = { "control_model", "control_image", "control_strength", "control_start", "control_end" };   /* ids from MLIS_OPT_AMD_CONTROL_MODEL */
-static const char* const k_option_amd5[] = { "freeu", "freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2" };   /* ids from MLIS_OPT_AMD_FREEU */
-static const char* const k_option_amd6[] = { "upscale_model", "hires_use_model" };                       /* ids from MLIS_OPT_AMD_UPSCALE_MODEL */
-static const char* const k_option_amd7[] = { "downscale_filter" };                                       /* ids from MLIS_OPT_AMD_DOWNSCALE_FILTER */
 static const char* const k_downscale[] = { "none", "box", "bilinear", "bicubic", "lanczos" };            /* 0, MLIS_AMD_AA_* + 1 */
-static const char* const k_option_amd8[] = { "control_preprocess", "canny_low", "canny_high", "canny_l2" };   /* ids from MLIS_OPT_AMD_CONTROL_PREPROCESS */
 static const char* const k_preprocess[] = { "none", "canny", "invert" };                                 /* MLIS_AMD_PREPROCESS_* */
-static const char* const k_option_amd9[] = { "inpaint_area", "inpaint_padding", "mask_blur", "mask_grow", "mask_invert", "inpaint_composite" };   /* ids from MLIS_OPT_AMD_INPAINT_AREA */
-static const char* const k_option_amd10[] = { "hypertile", "hypertile_depth" };                         /* ids from MLIS_OPT_AMD_HYPERTILE */
-static const char* const k_option_amd11[] = { "pag_scale" };                                            /* ids from MLIS_OPT_AMD_PAG_SCALE */
-static const char* const k_option_amd12[] = { "cfg_rescale", "prediction", "zsnr" };                    /* ids from MLIS_OPT_AMD_CFG_RESCALE */
 static const char* const k_prediction[] = { "auto", "eps", "v" };
 static const char* const k_zsnr[] = { "auto", "off", "on" };
 static const char* const k_inpaint_area[] = { "whole", "masked" };                                       /* MLIS_AMD_INPAINT_* */
-MLB_API const char* mlis_option_str(MLIS_Option x)
-{
-	if (x >= MLIS_OPT_AMD_CFG_RESCALE && x < MLIS_OPT_AMD_CFG_RESCALE + COUNTOF(k_option_amd12)) return k_option_amd12[x - MLIS_OPT_AMD_CFG_RESCALE];
-	if (x >= MLIS_OPT_AMD_PAG_SCALE && x < MLIS_OPT_AMD_PAG_SCALE + COUNTOF(k_option_amd11)) return k_option_amd11[x - MLIS_OPT_AMD_PAG_SCALE];
-	if (x >= MLIS_OPT_AMD_HYPERTILE && x < MLIS_OPT_AMD_HYPERTILE + COUNTOF(k_option_amd10)) return k_option_amd10[x - MLIS_OPT_AMD_HYPERTILE];
-	if (x >= MLIS_OPT_AMD_INPAINT_AREA && x < MLIS_OPT_AMD_INPAINT_AREA + COUNTOF(k_option_amd9)) return k_option_amd9[x - MLIS_OPT_AMD_INPAINT_AREA];
-	if (x >= MLIS_OPT_AMD_CONTROL_PREPROCESS && x < MLIS_OPT_AMD_CONTROL_PREPROCESS + COUNTOF(k_option_amd8)) return k_option_amd8[x - MLIS_OPT_AMD_CONTROL_PREPROCESS];
-	if (x >= MLIS_OPT_AMD_DOWNSCALE_FILTER && x < MLIS_OPT_AMD_DOWNSCALE_FILTER + COUNTOF(k_option_amd7)) return k_option_amd7[x - MLIS_OPT_AMD_DOWNSCALE_FILTER];
-	if (x >= MLIS_OPT_AMD_UPSCALE_MODEL && x < MLIS_OPT_AMD_UPSCALE_MODEL + COUNTOF(k_option_amd6)) return k_option_amd6[x - MLIS_OPT_AMD_UPSCALE_MODEL];
-	if (x >= MLIS_OPT_AMD_FREEU && x < MLIS_OPT_AMD_FREEU + COUNTOF(k_option_amd5)) return k_option_amd5[x - MLIS_OPT_AMD_FREEU];
-	if (x >= MLIS_OPT_AMD_CONTROL_MODEL && x < MLIS_OPT_AMD_CONTROL_MODEL + COUNTOF(k_option_amd4)) return k_option_amd4[x - MLIS_OPT_AMD_CONTROL_MODEL];
-	if (x >= MLIS_OPT_AMD_UNET_TILE_BATCH && x < MLIS_OPT_AMD_UNET_TILE_BATCH + COUNTOF(k_option_amd3)) return k_option_amd3[x - MLIS_OPT_AMD_UNET_TILE_BATCH];
-	if (x >= MLIS_OPT_AMD_UNET_TILE && x < MLIS_OPT_AMD_UNET_TILE + COUNTOF(k_option_amd2)) return k_option_amd2[x - MLIS_OPT_AMD_UNET_TILE];
-	if (x >= MLIS_OPT_AMD_TILING && x < MLIS_OPT_AMD_TILING + COUNTOF(k_option_amd)) return k_option_amd[x - MLIS_OPT_AMD_TILING];
-	return (x >= 0 && x < COUNTOF(k_option)) ? k_option[x] : "???";
-}
-MLB_API MLIS_Option mlis_option_fromz(const char* s)
-{
-	const int i = from_list(k_option_amd, COUNTOF(k_option_amd), 1, s, strlen(s));
-	if (i >= 0) return (MLIS_Option)(MLIS_OPT_AMD_TILING + i);
-	const int i2 = from_list(k_option_amd2, COUNTOF(k_option_amd2), 1, s, strlen(s));
-	if (i2 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE + i2);
-	const int i3 = from_list(k_option_amd3, COUNTOF(k_option_amd3), 1, s, strlen(s));
-	if (i3 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UNET_TILE_BATCH + i3);
-	const int i4 = from_list(k_option_amd4, COUNTOF(k_option_amd4), 1, s, strlen(s));
-	if (i4 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_MODEL + i4);
-	const int i5 = from_list(k_option_amd5, COUNTOF(k_option_amd5), 1, s, strlen(s));
-	if (i5 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_FREEU + i5);
-	const int i6 = from_list(k_option_amd6, COUNTOF(k_option_amd6), 1, s, strlen(s));
-	if (i6 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_UPSCALE_MODEL + i6);
-	const int i7 = from_list(k_option_amd7, COUNTOF(k_option_amd7), 1, s, strlen(s));
-	if (i7 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_DOWNSCALE_FILTER + i7);
-	const int i8 = from_list(k_option_amd8, COUNTOF(k_option_amd8), 1, s, strlen(s));
-	if (i8 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CONTROL_PREPROCESS + i8);
-	const int i9 = from_list(k_option_amd9, COUNTOF(k_option_amd9), 1, s, strlen(s));
-	if (i9 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_INPAINT_AREA + i9);
-	const int i10 = from_list(k_option_amd10, COUNTOF(k_option_amd10), 1, s, strlen(s));
-	if (i10 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_HYPERTILE + i10);
-	const int i11 = from_list(k_option_amd11, COUNTOF(k_option_amd11), 1, s, strlen(s));
-	if (i11 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_PAG_SCALE + i11);
-	const int i12 = from_list(k_option_amd12, COUNTOF(k_option_amd12), 1, s, strlen(s));
-	if (i12 >= 0) return (MLIS_Option)(MLIS_OPT_AMD_CFG_RESCALE + i12);
-	return (MLIS_Option)from_list(k_option, COUNTOF(k_option), 1, s, strlen(s));
-}
 
 static const char* model_name(int mt)
 {
@@ -261,6 +201,7 @@ static int tensor_good(const MLIS_Tensor* t) { return t->d && mlis_tensor_count(
 
 static int lora_add(MLIS_Ctx* S, const char* name, size_t len, float mult, int flags);
 static void loras_remove(MLIS_Ctx* S, int only_prompt);
+static void options_init(MLIS_Ctx* S);       /* the initial value of every option in the table (k_opt) */
 
 /* ------------------------------------------------------------------ context */
 MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
@@ -271,17 +212,7 @@ MLB_API MLIS_Ctx* mlis_ctx_create_i(int version)
 	if (!S) return NULL;
 	S->signature = CTX_SIGNATURE;
 	S->wtype = MLT_F16;
-	S->cfg_scale = 7;
-	S->f_t_ini = 1;
-	S->hires_denoise = 0.7f; S->hires_upscaler = MLIS_AMD_RESAMPLE_BILINEAR;
-	S->unet_tile_overlap = -1;
-	S->unet_tile_batch = 1;
-	S->hypertile = 0; S->hypertile_depth = 3;
-	S->pag_scale = 0;
-	S->control_strength = 1; S->control_start = 0; S->control_end = 1;
-	S->canny_low = 100; S->canny_high = 200;
-	S->inpaint_padding = 32;
-	S->freeu_f[0] = 1.3f; S->freeu_f[1] = 1.4f; S->freeu_f[2] = 0.9f; S->freeu_f[3] = 0.2f;      /* b1, b2, s1, s2 (mlis_abi.h on where these come from) */
+	options_init(S);
 	struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts);
 	S->seed = (uint64_t)ts.tv_sec * 1000 + ts.tv_nsec / 1000000;      /* g_rng.seed = timing_timeofday()*1000 (:458) */
 	return S;
@@ -424,17 +355,19 @@ static int image_to_tensor(MLIS_Tensor* T, const MLIS_Image* I)
 	return 1;
 }
 
-static void prompt_set(MLIS_Ctx* S, int neg, const char* text, int* err)
+/* the prompt text just stored in prompt_raw / nprompt_raw, taken apart */
+static int prompt_parse(MLIS_Ctx* S, int neg)
 {
 	MLISPrompt *P = neg ? &S->nprompt : &S->prompt;
-	str_set(neg ? &S->nprompt_raw : &S->prompt_raw, text);
+	const char *text = neg ? S->nprompt_raw : S->prompt_raw;
 	S->have_ptok[neg] = 0;
 	if (S->flags & CF_NO_PROMPT_PARSE) mlis_prompt_set_raw(P, text);
-	else if (mlis_prompt_set_parse(P, text) < 0) { *err = api_error_lib(S, MLIS_E_PROMPT_PARSE); return; }
+	else if (mlis_prompt_set_parse(P, text) < 0) return api_error_lib(S, MLIS_E_PROMPT_PARSE);
 	else for (int i=0; i<P->n_lora; ++i) {            /* <lora:NAME:MULT> in the prompt (:49-52) */
 		int r = lora_add(S, P->lora_names + P->loras[i].name_off, (size_t)P->loras[i].len, P->loras[i].w, LF_PROMPT);
-		if (r < 0) { *err = r; return; }
+		if (r < 0) return r;
 	}
+	return 1;
 }
 
 static int file_exists(const char* p);
@@ -521,13 +454,71 @@ static char* arg_str(ArgSrc* A, int whole, size_t mn)
 	return r;
 }
 
-static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
-{	/* src/mlimgsynth_options_set.c.h, option by option */
+/* One row per option (k_opt): everything the API knows about it.  Names, setting, getting and the values of a new context all derive from the rows.
+ * Adding an option: the enumerator in mlis_abi.h, the field of MLIS_Ctx plus its row here, the constant in mlimgsynth.py. */
+enum { OK_NONE,
+	OK_INT,         /* int field: decimal text or int */
+	OK_FLOAT,       /* float field: strtof text or double */
+	OK_FLAG,        /* the reference's booleans, a bit of S->flags: arg_bool (variadic: any int, !!v) */
+	OK_BOOL,        /* int field: arg_bool in text, an int in 0..1 variadic */
+	OK_ENUM,        /* int field: a name of `names`, else a whole-token decimal; variadic any int; 0 <= v < n_names */
+	OK_STR,         /* char* field: the whole remaining text, or a const char*, of at least `mn` characters */
+	OK_CUSTOM };    /* option_custom reads the arguments itself */
+enum { OF_GET = 1,       /* mlis_option_get serves it: int* (OK_CUSTOM: what `get` gives), float* or const char** (never NULL, "" while unset) */
+       OF_RETAKE = 2 };  /* a changed value makes the engines take the control image again (control_apply), as after a new image */
+typedef struct OptRow {
+	int id; const char* name;
+	int kind, flags;
+	size_t where;                   /* offsetof the field in MLIS_Ctx; OK_FLAG: the bit */
+	double mn, mx;                  /* inclusive range */
+	double init, empty;             /* the value of a new context; the value an empty string stands for: one outside the range (NAN, -1) refuses it */
+	const char* const* names; int n_names;
+	const char* letters;            /* OK_ENUM: letters[v] is a one-letter, case-sensitive name of value v ('-': none) */
+	int (*valid)(double v);         /* what a range cannot express */
+	int (*after)(MLIS_Ctx* S, int changed);          /* runs once the value is stored; its result is the call's */
+	int (*get)(const MLIS_Ctx* S);
+} OptRow;
+
+static int opt_bad_value(MLIS_Ctx* S, const OptRow* o, const ArgSrc* A)
+{
+	return A->is_str ? api_error(S, MLIS_E_OPT_VALUE, "invalid argument '%.*s' for option '%s'", (int)A->arg_n, A->arg_b ? A->arg_b : "", o->name)
+		: api_error(S, MLIS_E_OPT_VALUE, "invalid argument for option '%s'", o->name);
+}
+
+/* ---- rules a range cannot express */
+static int valid_mult8(double v) { return (int)v % 8 == 0; }
+static int valid_hires_scale(double v) { return !(v > 0 && v < 1); }           /* 0 and 1: off */
+static int valid_positive(double v) { return v > 0; }
+static int valid_hypertile(double v) { return (int)v % 8 == 0 && (v == 0 || v >= 32); }      /* 0: off; the rule is applied per pass size (engine_get) */
+static int valid_tile_overlap(double v) { return v <= 0 || (int)v % 8 == 0; }  /* -1: auto */
+
+/* ---- what follows a stored value */
+static int after_model(MLIS_Ctx* S, int changed) { (void)changed; model_drop(S); return 1; }
+static int after_tae(MLIS_Ctx* S, int changed)
+{
+	(void)changed;
+	if (*S->path_tae) S->flags |= CF_USE_TAE; else S->flags &= ~CF_USE_TAE;
+	engine_drop(S); return 1;
+}
+static int after_aux_dir(MLIS_Ctx* S, int changed) { (void)changed; if (S->tok) { clip_tokr_free(S->tok); S->tok = NULL; } return 1; }
+static int after_prompt(MLIS_Ctx* S, int changed) { (void)changed; return prompt_parse(S, 0); }
+static int after_nprompt(MLIS_Ctx* S, int changed) { (void)changed; return prompt_parse(S, 1); }
+static int after_control_model(MLIS_Ctx* S, int changed)
+{	/* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
+	if (changed) { control_engines_drop(S); if (S->ts_control) { mlts_close(S->ts_control); S->ts_control = NULL; } }
+	return 1;
+}
+static int after_upscale_model(MLIS_Ctx* S, int changed) { if (changed) upscaler_drop(S); return 1; }      /* the next use builds the new one */
+
+/* ---- OK_CUSTOM: options whose arguments are pointers, two values or a grammar of their own (src/mlimgsynth_options_set.c.h, option by option) */
+static int get_model_type(const MLIS_Ctx* S) { return S->model_type; }
+static int get_control_image(const MLIS_Ctx* S) { return tensor_good(&S->control_image); }      /* whether one is set */
+static int option_custom(MLIS_Ctx* S, const OptRow* o, ArgSrc* A)
+{
 	int i = 0, j = 0, err = 1; float f = 0; char *s = NULL;
-#define BAD_VALUE do { free(s); return A->is_str ? api_error(S, MLIS_E_OPT_VALUE, "invalid argument '%.*s' for option '%s'", (int)A->arg_n, A->arg_b ? A->arg_b : "", mlis_option_str(id)) \
-	: api_error(S, MLIS_E_OPT_VALUE, "invalid argument for option '%s'", mlis_option_str(id)); } while (0)
-#define NO_STR do { if (A->is_str) return api_error(S, MLIS_E_OPT_VALUE, "option '%s' cannot be set with a string value", mlis_option_str(id)); } while (0)
-	switch (id) {
+#define BAD_VALUE do { free(s); return opt_bad_value(S, o, A); } while (0)
+#define NO_STR do { if (A->is_str) return api_error(S, MLIS_E_OPT_VALUE, "option '%s' cannot be set with a string value", o->name); } while (0)
+	switch (o->id) {
 	case MLIS_OPT_BACKEND: {
 		if (!(s = arg_str(A, 0, 0))) BAD_VALUE;
 		char *p2 = A->is_str ? arg_str(A, 0, 0) : NULL;
@@ -535,16 +526,11 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		free(p2);
 		str_set(&S->backend, s); S->rflags &= ~READY_BACKEND;
 	} break;
-	case MLIS_OPT_MODEL: if (!(s = arg_str(A, 1, 1))) BAD_VALUE; str_set(&S->path_model, s); model_drop(S); break;
-	case MLIS_OPT_TAE: if (!(s = arg_str(A, 1, 0))) BAD_VALUE; str_set(&S->path_tae, s);
-		if (*s) S->flags |= CF_USE_TAE; else S->flags &= ~CF_USE_TAE; engine_drop(S); break;
 	case MLIS_OPT_MODEL_TYPE:
 		if (A->is_str) { next_str_arg(A); i = model_from(A->arg_b, A->arg_n); if (i < 0) BAD_VALUE; } else i = va_arg(*A->ap, int);
 		if (model_type_set(S, i) < 0) return MLIS_E_OPT_VALUE;
 		model_drop(S);
 		break;
-	case MLIS_OPT_AUX_DIR: if (!(s = arg_str(A, 1, 0))) BAD_VALUE; str_set(&S->path_aux, s); if (S->tok) { clip_tokr_free(S->tok); S->tok = NULL; } break;
-	case MLIS_OPT_LORA_DIR: if (!(s = arg_str(A, 1, 0))) BAD_VALUE; str_set(&S->path_lora_dir, s); break;
 	case MLIS_OPT_LORA: {
 		if (!(s = arg_str(A, 0, 1))) BAD_VALUE;
 		f = 1;
@@ -552,14 +538,8 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		err = lora_add(S, s, strlen(s), f, 0);
 	} break;
 	case MLIS_OPT_LORA_CLEAR: loras_remove(S, 0); break;
-	case MLIS_OPT_PROMPT: if (!(s = arg_str(A, 1, 0))) BAD_VALUE; prompt_set(S, 0, s, &err); break;
-	case MLIS_OPT_NPROMPT: if (!(s = arg_str(A, 1, 0))) BAD_VALUE; prompt_set(S, 1, s, &err); break;
-	case MLIS_OPT_NO_PROMPT_PARSE: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_NO_PROMPT_PARSE; else S->flags &= ~CF_NO_PROMPT_PARSE; break;
 	case MLIS_OPT_IMAGE_DIM: if (!arg_int(A, 0, 65535, 0, &i) || !arg_int(A, 0, 65535, 0, &j)) BAD_VALUE; S->width = i; S->height = j; break;
-	case MLIS_OPT_BATCH_SIZE: if (!arg_int(A, 0, 1024, 0, &i)) BAD_VALUE; S->n_batch = i; break;
-	case MLIS_OPT_CLIP_SKIP: if (!arg_int(A, 0, 255, 0, &i)) BAD_VALUE; S->clip_skip = i; break;
-	case MLIS_OPT_CFG_SCALE: if (!arg_float(A, 0, 255, NAN, &f)) BAD_VALUE; S->cfg_scale = f; break;
-	case MLIS_OPT_METHOD:
+	case MLIS_OPT_METHOD:          /* (variadic: like the scheduler, not range-checked) */
 		if (A->is_str) {
 			next_str_arg(A);
 			size_t n = A->arg_n; int anc = 0;
@@ -569,14 +549,9 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 			if (anc) S->s_ancestral = 1;
 		} else i = va_arg(*A->ap, int);
 		S->method = i; break;
-	case MLIS_OPT_SCHEDULER:
+	case MLIS_OPT_SCHEDULER:       /* a name only, no decimal: not an OK_ENUM */
 		if (A->is_str) { next_str_arg(A); i = from_list(k_sched, COUNTOF(k_sched), 1, A->arg_b, A->arg_n); if (i < 0) BAD_VALUE; } else i = va_arg(*A->ap, int);
 		S->sched = i; break;
-	case MLIS_OPT_STEPS: if (!arg_int(A, 0, 1000, 0, &i)) BAD_VALUE; S->n_step = i; break;
-	case MLIS_OPT_F_T_INI: if (!arg_float(A, 0, 1, NAN, &f)) BAD_VALUE; S->f_t_ini = f; break;
-	case MLIS_OPT_F_T_END: if (!arg_float(A, 0, 1, NAN, &f)) BAD_VALUE; S->f_t_end = f; break;
-	case MLIS_OPT_S_NOISE: if (!arg_float(A, 0, 255, NAN, &f)) BAD_VALUE; S->s_noise = f; break;
-	case MLIS_OPT_S_ANCESTRAL: if (!arg_float(A, 0, 255, NAN, &f)) BAD_VALUE; S->s_ancestral = f; break;
 	case MLIS_OPT_IMAGE: {
 		NO_STR;
 		const MLIS_Image *img = va_arg(*A->ap, const MLIS_Image*);
@@ -598,8 +573,6 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (image_to_tensor(&S->mask, img) < 0) return api_error(S, MLIS_E_IMAGE, "invalid image mask");
 		S->tuflags |= MLIS_TUF_MASK;
 	} break;
-	case MLIS_OPT_NO_DECODE: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_NO_DECODE; else S->flags &= ~CF_NO_DECODE; break;
-	case MLIS_OPT_TENSOR_USE_FLAGS: if (!arg_int(A, 0, 0x7fffffff, 0, &i)) BAD_VALUE; S->tuflags = i; break;
 	case MLIS_OPT_SEED:
 		if (A->is_str) {
 			if (!A->cur[0]) break;                                   /* empty string: keep the random seed */
@@ -609,63 +582,6 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 			S->seed = v;
 		} else S->seed = va_arg(*A->ap, uint64_t);
 		break;
-	case MLIS_OPT_VAE_TILE: if (!arg_int(A, 0, 65535, 0, &i)) BAD_VALUE; S->vae_tile = i; break;
-	case MLIS_OPT_AMD_TILING:      /* none|x|y|xy or 0..3; a changed mode rebuilds the engine (engine_get key) */
-		if (A->is_str) {
-			next_str_arg(A);
-			i = from_list(k_tiling, COUNTOF(k_tiling), 1, A->arg_b, A->arg_n);
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i > 3) BAD_VALUE;
-		S->tiling = i;
-		break;
-	case MLIS_OPT_AMD_HIRES_SCALE: if (!arg_float(A, 0, 4, NAN, &f) || (f > 0 && f < 1)) BAD_VALUE; S->hires_scale = f; break;   /* 0 and 1: off */
-	case MLIS_OPT_AMD_HIRES_DENOISE: if (!arg_float(A, 0, 1, NAN, &f) || !(f > 0)) BAD_VALUE; S->hires_denoise = f; break;
-	case MLIS_OPT_AMD_HIRES_STEPS: if (!arg_int(A, 0, 1000, 0, &i)) BAD_VALUE; S->hires_steps = i; break;
-	case MLIS_OPT_AMD_HIRES_UPSCALER:      /* nearest|bilinear|bicubic or 0..2 */
-		if (A->is_str) {
-			next_str_arg(A);
-			i = from_list(k_resample, COUNTOF(k_resample), 1, A->arg_b, A->arg_n);
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i >= COUNTOF(k_resample)) BAD_VALUE;
-		S->hires_upscaler = i;
-		break;
-	case MLIS_OPT_AMD_UNET_TILE: if (!arg_int(A, 0, 65535, 0, &i) || i % 8) BAD_VALUE; S->unet_tile = i; break;     /* 0: off; the relation to the overlap is checked when an engine is needed (unet_tile_check) */
-	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: if (!arg_int(A, -1, 65535, -1, &i) || (i > 0 && i % 8)) BAD_VALUE; S->unet_tile_overlap = i; break;      /* -1: auto */
-	case MLIS_OPT_AMD_UNET_TILE_BATCH: if (!arg_int(A, 1, MLSD_WINDOW_MAX_PACK, 1, &i)) BAD_VALUE; S->unet_tile_batch = i; break;      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
-	case MLIS_OPT_AMD_HYPERTILE: if (!arg_int(A, 0, 8192, 0, &i) || i % 8 || (i && i < 32)) BAD_VALUE; S->hypertile = i; break;      /* 0: off; the rule is applied per pass size (engine_get) */
-	case MLIS_OPT_AMD_HYPERTILE_DEPTH: if (!arg_int(A, 0, 3, 3, &i)) BAD_VALUE; S->hypertile_depth = i; break;
-	case MLIS_OPT_AMD_CFG_RESCALE: if (!arg_float(A, 0, 1, 0, &f)) BAD_VALUE; S->cfg_rescale = f; break;      /* handed to the engine per generation */
-	case MLIS_OPT_AMD_PREDICTION:          /* auto|eps|v or 0..2 */
-	case MLIS_OPT_AMD_ZSNR:                /* auto|off|on (also n|y) or 0..2 */
-		if (A->is_str) {
-			next_str_arg(A);
-			if (id == MLIS_OPT_AMD_PREDICTION) i = from_list(k_prediction, COUNTOF(k_prediction), 1, A->arg_b, A->arg_n);
-			else {
-				i = from_list(k_zsnr, COUNTOF(k_zsnr), 1, A->arg_b, A->arg_n);
-				if (i < 0 && A->arg_n == 1 && (A->arg_b[0] == 'n' || A->arg_b[0] == 'y')) i = A->arg_b[0] == 'y' ? 2 : 1;
-			}
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : 0;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i > 2) BAD_VALUE;
-		if (id == MLIS_OPT_AMD_PREDICTION) S->prediction = i; else S->zsnr = i;
-		break;
-	case MLIS_OPT_AMD_PAG_SCALE: if (!arg_float(A, 0, 20, 0, &f)) BAD_VALUE; S->pag_scale = f; break;      /* > 0: the engine with the third row group (engine_get) */
-	case MLIS_OPT_AMD_CONTROL_MODEL:       /* a changed ControlNet drops the engines that hold one (their ControlNet plans have the old weights); plain engines stay */
-		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
-		if (!S->path_control || strcmp(S->path_control, s)) { control_engines_drop(S); if (S->ts_control) { mlts_close(S->ts_control); S->ts_control = NULL; } }
-		str_set(&S->path_control, s);
-		break;
 	case MLIS_OPT_AMD_CONTROL_IMAGE: {
 		NO_STR;
 		const MLIS_Image *img = va_arg(*A->ap, const MLIS_Image*);
@@ -674,73 +590,6 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		if (image_to_tensor(&S->control_image, img) < 0) return api_error(S, MLIS_E_IMAGE, "invalid control image");
 		S->control_image_gen++;      /* engines holding the previous image take this one at their next pass (control_apply) */
 	} break;
-	case MLIS_OPT_AMD_CONTROL_STRENGTH: if (!arg_float(A, 0, 2, 1, &f)) BAD_VALUE; S->control_strength = f; break;
-	case MLIS_OPT_AMD_CONTROL_START: if (!arg_float(A, 0, 1, 0, &f)) BAD_VALUE; S->control_start = f; break;      /* start <= end: checked by mlis_generate, the two are set one by one */
-	case MLIS_OPT_AMD_CONTROL_END: if (!arg_float(A, 0, 1, 1, &f)) BAD_VALUE; S->control_end = f; break;
-	case MLIS_OPT_AMD_FREEU: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->freeu = i; break;      /* the one FreeU option in the engine key */
-	case MLIS_OPT_AMD_FREEU_B1: if (!arg_float(A, 0, 4, 1.3f, &f)) BAD_VALUE; S->freeu_f[0] = f; break;
-	case MLIS_OPT_AMD_FREEU_B2: if (!arg_float(A, 0, 4, 1.4f, &f)) BAD_VALUE; S->freeu_f[1] = f; break;
-	case MLIS_OPT_AMD_FREEU_S1: if (!arg_float(A, 0, 4, 0.9f, &f)) BAD_VALUE; S->freeu_f[2] = f; break;
-	case MLIS_OPT_AMD_FREEU_S2: if (!arg_float(A, 0, 4, 0.2f, &f)) BAD_VALUE; S->freeu_f[3] = f; break;
-	case MLIS_OPT_AMD_UPSCALE_MODEL:       /* a changed value frees the resident upscaler; the next use builds the new one */
-		if (!(s = arg_str(A, 1, 0))) BAD_VALUE;
-		if (!S->path_upscale || strcmp(S->path_upscale, s)) upscaler_drop(S);
-		str_set(&S->path_upscale, s);
-		break;
-	case MLIS_OPT_AMD_HIRES_USE_MODEL: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->hires_use_model = i; break;
-	case MLIS_OPT_AMD_DOWNSCALE_FILTER:    /* none|box|bilinear|bicubic|lanczos or 0..4 */
-		if (A->is_str) {
-			next_str_arg(A);
-			i = from_list(k_downscale, COUNTOF(k_downscale), 1, A->arg_b, A->arg_n);
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i >= COUNTOF(k_downscale)) BAD_VALUE;
-		/* an engine that holds the control image resampled with the old filter takes it again at its next pass (control_apply), as after a new image */
-		if (i != S->downscale_filter && tensor_good(&S->control_image)) S->control_image_gen++;
-		S->downscale_filter = i;
-		break;
-	/* the preprocessor and its parameters: like the downscale_filter, a changed value makes the engines take the control image again (control_apply) */
-	case MLIS_OPT_AMD_CONTROL_PREPROCESS:  /* none|canny|invert or 0..2 */
-		if (A->is_str) {
-			next_str_arg(A);
-			i = from_list(k_preprocess, COUNTOF(k_preprocess), 1, A->arg_b, A->arg_n);
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i >= COUNTOF(k_preprocess)) BAD_VALUE;
-		if (i != S->control_preprocess && tensor_good(&S->control_image)) S->control_image_gen++;
-		S->control_preprocess = i;
-		break;
-	case MLIS_OPT_AMD_CANNY_LOW: if (!arg_float(A, 0, 32767, 100, &f)) BAD_VALUE; if (f != S->canny_low && tensor_good(&S->control_image)) S->control_image_gen++; S->canny_low = f; break;
-	case MLIS_OPT_AMD_CANNY_HIGH: if (!arg_float(A, 0, 32767, 200, &f)) BAD_VALUE; if (f != S->canny_high && tensor_good(&S->control_image)) S->control_image_gen++; S->canny_high = f; break;
-	case MLIS_OPT_AMD_CANNY_L2:
-		if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE;
-		if (i != S->canny_l2 && tensor_good(&S->control_image)) S->control_image_gen++;
-		S->canny_l2 = i;
-		break;
-	case MLIS_OPT_AMD_INPAINT_AREA:        /* whole|masked or 0..1 */
-		if (A->is_str) {
-			next_str_arg(A);
-			i = from_list(k_inpaint_area, COUNTOF(k_inpaint_area), 1, A->arg_b, A->arg_n);
-			if (i < 0) {
-				char *tail = (char*)A->arg_b + A->arg_n; i = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : -1;
-				if (tail != A->arg_b + A->arg_n) i = -1;
-			}
-		} else i = va_arg(*A->ap, int);
-		if (i < 0 || i >= COUNTOF(k_inpaint_area)) BAD_VALUE;
-		S->inpaint_area = i;
-		break;
-	case MLIS_OPT_AMD_INPAINT_PADDING: if (!arg_int(A, 0, 512, 32, &i)) BAD_VALUE; S->inpaint_padding = i; break;
-	case MLIS_OPT_AMD_MASK_BLUR: if (!arg_float(A, 0, MLSD_GAUSS_MAX_SIGMA, 0, &f)) BAD_VALUE; S->mask_blur = f; break;
-	case MLIS_OPT_AMD_MASK_GROW: if (!arg_int(A, -MLSD_MASK_GROW_MAX, MLSD_MASK_GROW_MAX, 0, &i)) BAD_VALUE; S->mask_grow = i; break;
-	case MLIS_OPT_AMD_MASK_INVERT: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->mask_invert = i; break;
-	case MLIS_OPT_AMD_INPAINT_COMPOSITE: if (!(A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i))) BAD_VALUE; S->inpaint_composite = i; break;
-	case MLIS_OPT_UNET_SPLIT: if (!arg_bool(A, &i)) BAD_VALUE; if (i) S->flags |= CF_UNET_SPLIT; else S->flags &= ~CF_UNET_SPLIT; break;   /* weight streaming through three device slabs (engine_get) */
 	case MLIS_OPT_WEIGHT_TYPE:
 		if (S->n_applied) { S->ts_partial = 1; S->rflags &= ~READY_LORAS; }      /* the merge's operand rounding follows the weight type: active adapters are merged again, the cold way */
 		if (A->is_str) {
@@ -756,19 +605,175 @@ static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
 		else if (i == MLT_F32 || i == MLT_F16 || i == MLT_BF16) { S->wtype = i; S->flags |= CF_WEIGHT_TYPE_SET; }
 		else return api_error(S, MLIS_E_OPT_VALUE, "weight type %d is not supported (f32, f16, bf16; quantised ggml types are not)", i);
 		break;
-	case MLIS_OPT_THREADS: if (!arg_int(A, 0, 65535, 0, &i)) BAD_VALUE; S->n_thread = i; break;
-	case MLIS_OPT_DUMP_FLAGS: if (!arg_int(A, 0, 0x7fffffff, 0, &i)) BAD_VALUE; S->dump_flags = i; break;
 	case MLIS_OPT_CALLBACK: NO_STR; S->callback = va_arg(*A->ap, MLIS_Callback); S->callback_ud = va_arg(*A->ap, void*); break;
 	case MLIS_OPT_ERROR_HANDLER: NO_STR; S->errh = va_arg(*A->ap, MLIS_ErrorHandler); S->errh_ud = va_arg(*A->ap, void*); break;
 	case MLIS_OPT_LOG_LEVEL:
 		if (A->is_str) { next_str_arg(A); } else (void)va_arg(*A->ap, int);   /* this library does not log: accepted, ignored */
 		break;
-	default: return api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
 	}
 	free(s);
 	return err;
 #undef BAD_VALUE
 #undef NO_STR
+}
+
+/* ---- the rows.  AT fails to compile unless the field has the type the row's kind reads and writes. */
+#define AT(type, field) _Generic(&((MLIS_Ctx*)0)->field, type*: offsetof(MLIS_Ctx, field))
+#define ROW(ID, NAME, KIND, ...) { .id = ID, .name = NAME, .kind = KIND, __VA_ARGS__ }
+#define O_INT(ID, NAME, FIELD, MN, MX, INIT, EMPTY, ...) ROW(ID, NAME, OK_INT, .where = AT(int, FIELD), .mn = MN, .mx = MX, .init = INIT, .empty = EMPTY, __VA_ARGS__)
+#define O_FLOAT(ID, NAME, FIELD, MN, MX, INIT, EMPTY, ...) ROW(ID, NAME, OK_FLOAT, .where = AT(float, FIELD), .mn = MN, .mx = MX, .init = INIT, .empty = EMPTY, __VA_ARGS__)
+#define O_FLAG(ID, NAME, BIT) ROW(ID, NAME, OK_FLAG, .where = BIT)
+#define O_BOOL(ID, NAME, FIELD, ...) ROW(ID, NAME, OK_BOOL, .where = AT(int, FIELD), __VA_ARGS__)
+#define O_ENUM(ID, NAME, FIELD, LIST, INIT, EMPTY, ...) ROW(ID, NAME, OK_ENUM, .where = AT(int, FIELD), .names = LIST, .n_names = COUNTOF(LIST), .init = INIT, .empty = EMPTY, __VA_ARGS__)
+#define O_STR(ID, NAME, FIELD, MINLEN, ...) ROW(ID, NAME, OK_STR, .where = AT(char*, FIELD), .mn = MINLEN, __VA_ARGS__)
+#define O_CUSTOM(ID, NAME, ...) ROW(ID, NAME, OK_CUSTOM, __VA_ARGS__)
+#define REFUSED NAN
+static const OptRow k_opt[] = {
+	ROW(MLIS_OPT_NONE, "none", OK_NONE, .where = 0),
+	O_CUSTOM(MLIS_OPT_BACKEND, "backend"),
+	O_STR(MLIS_OPT_MODEL, "model", path_model, 1, .flags = OF_GET, .after = after_model),
+	O_STR(MLIS_OPT_TAE, "tae", path_tae, 0, .after = after_tae),
+	O_STR(MLIS_OPT_LORA_DIR, "lora_dir", path_lora_dir, 0),
+	O_CUSTOM(MLIS_OPT_LORA, "lora"),
+	O_CUSTOM(MLIS_OPT_LORA_CLEAR, "lora_clear"),
+	O_STR(MLIS_OPT_PROMPT, "prompt", prompt_raw, 0, .flags = OF_GET, .after = after_prompt),
+	O_STR(MLIS_OPT_NPROMPT, "nprompt", nprompt_raw, 0, .flags = OF_GET, .after = after_nprompt),
+	O_CUSTOM(MLIS_OPT_IMAGE_DIM, "image_dim"),
+	O_INT(MLIS_OPT_BATCH_SIZE, "batch_size", n_batch, 0, 1024, 0, 0),
+	O_INT(MLIS_OPT_CLIP_SKIP, "clip_skip", clip_skip, 0, 255, 0, 0),
+	O_FLOAT(MLIS_OPT_CFG_SCALE, "cfg_scale", cfg_scale, 0, 255, 7, REFUSED),
+	O_CUSTOM(MLIS_OPT_METHOD, "method"),
+	O_CUSTOM(MLIS_OPT_SCHEDULER, "scheduler"),
+	O_INT(MLIS_OPT_STEPS, "steps", n_step, 0, 1000, 0, 0),
+	O_FLOAT(MLIS_OPT_F_T_INI, "f_t_ini", f_t_ini, 0, 1, 1, REFUSED),
+	O_FLOAT(MLIS_OPT_F_T_END, "f_t_end", f_t_end, 0, 1, 0, REFUSED),
+	O_FLOAT(MLIS_OPT_S_NOISE, "s_noise", s_noise, 0, 255, 0, REFUSED),
+	O_FLOAT(MLIS_OPT_S_ANCESTRAL, "s_ancestral", s_ancestral, 0, 255, 0, REFUSED),
+	O_CUSTOM(MLIS_OPT_IMAGE, "image"),
+	O_CUSTOM(MLIS_OPT_IMAGE_MASK, "image_mask"),
+	O_FLAG(MLIS_OPT_NO_DECODE, "no_decode", CF_NO_DECODE),
+	O_INT(MLIS_OPT_TENSOR_USE_FLAGS, "tensor_use_flags", tuflags, 0, 0x7fffffff, 0, 0),
+	O_CUSTOM(MLIS_OPT_SEED, "seed"),
+	O_INT(MLIS_OPT_VAE_TILE, "vae_tile", vae_tile, 0, 65535, 0, 0),
+	O_FLAG(MLIS_OPT_UNET_SPLIT, "unet_split", CF_UNET_SPLIT),      /* weight streaming through three device slabs (engine_get) */
+	O_INT(MLIS_OPT_THREADS, "threads", n_thread, 0, 65535, 0, 0),
+	O_INT(MLIS_OPT_DUMP_FLAGS, "dump_flags", dump_flags, 0, 0x7fffffff, 0, 0),
+	O_STR(MLIS_OPT_AUX_DIR, "aux_dir", path_aux, 0, .after = after_aux_dir),
+	O_CUSTOM(MLIS_OPT_CALLBACK, "callback"),
+	O_CUSTOM(MLIS_OPT_ERROR_HANDLER, "error_handler"),
+	O_CUSTOM(MLIS_OPT_LOG_LEVEL, "log_level"),
+	O_CUSTOM(MLIS_OPT_MODEL_TYPE, "model_type", .flags = OF_GET, .get = get_model_type),
+	O_CUSTOM(MLIS_OPT_WEIGHT_TYPE, "weight_type"),
+	O_FLAG(MLIS_OPT_NO_PROMPT_PARSE, "no_prompt_parse", CF_NO_PROMPT_PARSE),
+	/* a changed tiling mode, freeu, hypertile or hypertile_depth, or pag_scale going on / off, selects another engine (engine_get key) */
+	O_ENUM(MLIS_OPT_AMD_TILING, "tiling", tiling, k_tiling, 0, -1, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_HIRES_SCALE, "hires_scale", hires_scale, 0, 4, 0, REFUSED, .flags = OF_GET, .valid = valid_hires_scale),
+	O_FLOAT(MLIS_OPT_AMD_HIRES_DENOISE, "hires_denoise", hires_denoise, 0, 1, 0.7, REFUSED, .flags = OF_GET, .valid = valid_positive),
+	O_INT(MLIS_OPT_AMD_HIRES_STEPS, "hires_steps", hires_steps, 0, 1000, 0, 0, .flags = OF_GET),
+	O_ENUM(MLIS_OPT_AMD_HIRES_UPSCALER, "hires_upscaler", hires_upscaler, k_resample, MLIS_AMD_RESAMPLE_BILINEAR, -1, .flags = OF_GET),
+	O_INT(MLIS_OPT_AMD_UNET_TILE, "unet_tile", unet_tile, 0, 65535, 0, 0, .flags = OF_GET, .valid = valid_mult8),      /* the relation to the overlap is checked when an engine is needed (unet_tile_check) */
+	O_INT(MLIS_OPT_AMD_UNET_TILE_OVERLAP, "unet_tile_overlap", unet_tile_overlap, -1, 65535, -1, -1, .flags = OF_GET, .valid = valid_tile_overlap),
+	O_INT(MLIS_OPT_AMD_UNET_TILE_BATCH, "unet_tile_batch", unet_tile_batch, 1, MLSD_WINDOW_MAX_PACK, 1, 1, .flags = OF_GET),      /* an upper bound: mlis_amd_tile_pack gives the effective pack */
+	O_STR(MLIS_OPT_AMD_CONTROL_MODEL, "control_model", path_control, 0, .flags = OF_GET, .after = after_control_model),
+	O_CUSTOM(MLIS_OPT_AMD_CONTROL_IMAGE, "control_image", .flags = OF_GET, .get = get_control_image),
+	O_FLOAT(MLIS_OPT_AMD_CONTROL_STRENGTH, "control_strength", control_strength, 0, 2, 1, 1, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_CONTROL_START, "control_start", control_start, 0, 1, 0, 0, .flags = OF_GET),      /* start <= end: checked by mlis_generate, the two are set one by one */
+	O_FLOAT(MLIS_OPT_AMD_CONTROL_END, "control_end", control_end, 0, 1, 1, 1, .flags = OF_GET),
+	O_BOOL(MLIS_OPT_AMD_FREEU, "freeu", freeu, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_FREEU_B1, "freeu_b1", freeu_f[0], 0, 4, 1.3, 1.3, .flags = OF_GET),      /* (mlis_abi.h on where the four initial values come from) */
+	O_FLOAT(MLIS_OPT_AMD_FREEU_B2, "freeu_b2", freeu_f[1], 0, 4, 1.4, 1.4, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_FREEU_S1, "freeu_s1", freeu_f[2], 0, 4, 0.9, 0.9, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_FREEU_S2, "freeu_s2", freeu_f[3], 0, 4, 0.2, 0.2, .flags = OF_GET),
+	O_STR(MLIS_OPT_AMD_UPSCALE_MODEL, "upscale_model", path_upscale, 0, .flags = OF_GET, .after = after_upscale_model),
+	O_BOOL(MLIS_OPT_AMD_HIRES_USE_MODEL, "hires_use_model", hires_use_model, .flags = OF_GET),
+	O_ENUM(MLIS_OPT_AMD_DOWNSCALE_FILTER, "downscale_filter", downscale_filter, k_downscale, 0, -1, .flags = OF_GET | OF_RETAKE),
+	O_ENUM(MLIS_OPT_AMD_CONTROL_PREPROCESS, "control_preprocess", control_preprocess, k_preprocess, 0, -1, .flags = OF_GET | OF_RETAKE),
+	O_FLOAT(MLIS_OPT_AMD_CANNY_LOW, "canny_low", canny_low, 0, 32767, 100, 100, .flags = OF_GET | OF_RETAKE),
+	O_FLOAT(MLIS_OPT_AMD_CANNY_HIGH, "canny_high", canny_high, 0, 32767, 200, 200, .flags = OF_GET | OF_RETAKE),
+	O_BOOL(MLIS_OPT_AMD_CANNY_L2, "canny_l2", canny_l2, .flags = OF_GET | OF_RETAKE),
+	O_ENUM(MLIS_OPT_AMD_INPAINT_AREA, "inpaint_area", inpaint_area, k_inpaint_area, 0, -1, .flags = OF_GET),
+	O_INT(MLIS_OPT_AMD_INPAINT_PADDING, "inpaint_padding", inpaint_padding, 0, 512, 32, 32, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_MASK_BLUR, "mask_blur", mask_blur, 0, MLSD_GAUSS_MAX_SIGMA, 0, 0, .flags = OF_GET),
+	O_INT(MLIS_OPT_AMD_MASK_GROW, "mask_grow", mask_grow, -MLSD_MASK_GROW_MAX, MLSD_MASK_GROW_MAX, 0, 0, .flags = OF_GET),
+	O_BOOL(MLIS_OPT_AMD_MASK_INVERT, "mask_invert", mask_invert, .flags = OF_GET),
+	O_BOOL(MLIS_OPT_AMD_INPAINT_COMPOSITE, "inpaint_composite", inpaint_composite, .flags = OF_GET),
+	O_INT(MLIS_OPT_AMD_HYPERTILE, "hypertile", hypertile, 0, 8192, 0, 0, .flags = OF_GET, .valid = valid_hypertile),
+	O_INT(MLIS_OPT_AMD_HYPERTILE_DEPTH, "hypertile_depth", hypertile_depth, 0, 3, 3, 3, .flags = OF_GET),
+	O_FLOAT(MLIS_OPT_AMD_PAG_SCALE, "pag_scale", pag_scale, 0, 20, 0, 0, .flags = OF_GET),      /* the value is handed to the engine per generation, as cfg_rescale */
+	O_FLOAT(MLIS_OPT_AMD_CFG_RESCALE, "cfg_rescale", cfg_rescale, 0, 1, 0, 0, .flags = OF_GET),
+	O_ENUM(MLIS_OPT_AMD_PREDICTION, "prediction", prediction, k_prediction, 0, 0, .flags = OF_GET),
+	O_ENUM(MLIS_OPT_AMD_ZSNR, "zsnr", zsnr, k_zsnr, 0, 0, .flags = OF_GET, .letters = "-ny"),
+};
+#undef REFUSED
+
+static const OptRow* option_row(int id)
+{
+	for (int k=0;k<COUNTOF(k_opt);++k) if (k_opt[k].id == id) return &k_opt[k];
+	return NULL;
+}
+MLB_API const char* mlis_option_str(MLIS_Option x) { const OptRow *o = option_row((int)x); return o ? o->name : "???"; }
+MLB_API MLIS_Option mlis_option_fromz(const char* s)
+{
+	for (int k=0;k<COUNTOF(k_opt);++k) if (id_eq(s, strlen(s), k_opt[k].name)) return (MLIS_Option)k_opt[k].id;
+	return (MLIS_Option)-1;
+}
+
+static void options_init(MLIS_Ctx* S)
+{
+	for (const OptRow *o = k_opt; o < k_opt + COUNTOF(k_opt); ++o) {
+		void *p = (char*)S + o->where;
+		if (o->kind == OK_FLOAT) *(float*)p = (float)o->init;
+		else if (o->kind == OK_INT || o->kind == OK_BOOL || o->kind == OK_ENUM) *(int*)p = (int)o->init;
+	}
+}
+
+static int arg_enum(ArgSrc* A, const OptRow* o, int* out)
+{
+	int v;
+	if (A->is_str) {
+		next_str_arg(A);
+		v = from_list(o->names, o->n_names, 1, A->arg_b, A->arg_n);
+		const char *l = (v < 0 && o->letters && A->arg_n == 1) ? strchr(o->letters, A->arg_b[0]) : NULL;
+		if (l && *l != '-') v = (int)(l - o->letters);
+		if (v < 0) {
+			char *tail = (char*)A->arg_b + A->arg_n; v = A->arg_n ? (int)strtol(A->arg_b, &tail, 10) : (int)o->empty;
+			if (tail != A->arg_b + A->arg_n) v = -1;
+		}
+	} else v = va_arg(*A->ap, int);
+	if (v < 0 || v >= o->n_names) return 0;
+	*out = v; return 1;
+}
+
+static int option_apply(MLIS_Ctx* S, int id, ArgSrc* A)
+{
+	const OptRow *o = option_row(id);
+	if (!o || o->kind == OK_NONE) return api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
+	void *p = (char*)S + o->where;
+	int i = 0, ok = 0, changed; float f = 0;
+	switch (o->kind) {
+	case OK_CUSTOM: return option_custom(S, o, A);
+	case OK_FLAG:
+		if (!arg_bool(A, &i)) return opt_bad_value(S, o, A);
+		if (i) S->flags |= (int)o->where; else S->flags &= ~(int)o->where;
+		return 1;
+	case OK_STR: {
+		char **ps = (char**)p, *s = arg_str(A, 1, (size_t)o->mn);
+		if (!s) return opt_bad_value(S, o, A);
+		changed = !*ps || strcmp(*ps, s);
+		free(*ps); *ps = s;
+		return o->after ? o->after(S, changed) : 1;
+	}
+	case OK_FLOAT: ok = arg_float(A, (float)o->mn, (float)o->mx, (float)o->empty, &f); break;
+	case OK_INT: ok = arg_int(A, (int)o->mn, (int)o->mx, (int)o->empty, &i); break;
+	case OK_BOOL: ok = A->is_str ? arg_bool(A, &i) : arg_int(A, 0, 1, 0, &i); break;
+	case OK_ENUM: ok = arg_enum(A, o, &i); break;
+	}
+	const int is_f = o->kind == OK_FLOAT;
+	if (!ok || (o->valid && !o->valid(is_f ? (double)f : (double)i))) return opt_bad_value(S, o, A);
+	changed = is_f ? f != *(float*)p : i != *(int*)p;
+	if (changed && (o->flags & OF_RETAKE) && tensor_good(&S->control_image)) S->control_image_gen++;
+	if (is_f) *(float*)p = f; else *(int*)p = i;
+	return o->after ? o->after(S, changed) : 1;
 }
 
 MLB_API int mlis_option_set(MLIS_Ctx* S, MLIS_Option id, ...)
@@ -791,54 +796,17 @@ MLB_API int mlis_option_set_str(MLIS_Ctx* S, const char* name, const char* value
 }
 
 MLB_API int mlis_option_get(MLIS_Ctx* S, MLIS_Option id, ...)
-{	/* src/mlimgsynth_options_get.c.h: the four options the reference implements */
+{	/* src/mlimgsynth_options_get.c.h implements four options (MODEL, MODEL_TYPE, PROMPT, NPROMPT); here also every MLIS_OPT_AMD_* one */
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	const OptRow *o = option_row((int)id);
+	if (!o || !(o->flags & OF_GET)) return api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
+	const void *p = (const char*)S + o->where;
 	va_list ap; va_start(ap, id);
-	int r = 1;
-	switch ((int)id) {
-	case MLIS_OPT_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_model ? S->path_model : ""; } break;
-	case MLIS_OPT_MODEL_TYPE: { int *p = va_arg(ap, int*); if (p) *p = S->model_type; } break;
-	case MLIS_OPT_AMD_TILING: { int *p = va_arg(ap, int*); if (p) *p = S->tiling; } break;
-	case MLIS_OPT_AMD_HIRES_SCALE: { float *p = va_arg(ap, float*); if (p) *p = S->hires_scale; } break;
-	case MLIS_OPT_AMD_HIRES_DENOISE: { float *p = va_arg(ap, float*); if (p) *p = S->hires_denoise; } break;
-	case MLIS_OPT_AMD_HIRES_STEPS: { int *p = va_arg(ap, int*); if (p) *p = S->hires_steps; } break;
-	case MLIS_OPT_AMD_HIRES_UPSCALER: { int *p = va_arg(ap, int*); if (p) *p = S->hires_upscaler; } break;
-	case MLIS_OPT_AMD_UNET_TILE: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile; } break;
-	case MLIS_OPT_AMD_UNET_TILE_OVERLAP: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_overlap; } break;
-	case MLIS_OPT_AMD_UNET_TILE_BATCH: { int *p = va_arg(ap, int*); if (p) *p = S->unet_tile_batch; } break;
-	case MLIS_OPT_AMD_HYPERTILE: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile; } break;
-	case MLIS_OPT_AMD_HYPERTILE_DEPTH: { int *p = va_arg(ap, int*); if (p) *p = S->hypertile_depth; } break;
-	case MLIS_OPT_AMD_PAG_SCALE: { float *p = va_arg(ap, float*); if (p) *p = S->pag_scale; } break;
-	case MLIS_OPT_AMD_CFG_RESCALE: { float *p = va_arg(ap, float*); if (p) *p = S->cfg_rescale; } break;
-	case MLIS_OPT_AMD_PREDICTION: { int *p = va_arg(ap, int*); if (p) *p = S->prediction; } break;
-	case MLIS_OPT_AMD_ZSNR: { int *p = va_arg(ap, int*); if (p) *p = S->zsnr; } break;
-	case MLIS_OPT_AMD_CONTROL_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_control ? S->path_control : ""; } break;
-	case MLIS_OPT_AMD_CONTROL_IMAGE: { int *p = va_arg(ap, int*); if (p) *p = tensor_good(&S->control_image); } break;      /* whether one is set */
-	case MLIS_OPT_AMD_CONTROL_STRENGTH: { float *p = va_arg(ap, float*); if (p) *p = S->control_strength; } break;
-	case MLIS_OPT_AMD_CONTROL_START: { float *p = va_arg(ap, float*); if (p) *p = S->control_start; } break;
-	case MLIS_OPT_AMD_CONTROL_END: { float *p = va_arg(ap, float*); if (p) *p = S->control_end; } break;
-	case MLIS_OPT_AMD_FREEU: { int *p = va_arg(ap, int*); if (p) *p = S->freeu; } break;
-	case MLIS_OPT_AMD_UPSCALE_MODEL: { const char **p = va_arg(ap, const char**); if (p) *p = S->path_upscale ? S->path_upscale : ""; } break;
-	case MLIS_OPT_AMD_HIRES_USE_MODEL: { int *p = va_arg(ap, int*); if (p) *p = S->hires_use_model; } break;
-	case MLIS_OPT_AMD_DOWNSCALE_FILTER: { int *p = va_arg(ap, int*); if (p) *p = S->downscale_filter; } break;
-	case MLIS_OPT_AMD_CONTROL_PREPROCESS: { int *p = va_arg(ap, int*); if (p) *p = S->control_preprocess; } break;
-	case MLIS_OPT_AMD_CANNY_LOW: { float *p = va_arg(ap, float*); if (p) *p = S->canny_low; } break;
-	case MLIS_OPT_AMD_CANNY_HIGH: { float *p = va_arg(ap, float*); if (p) *p = S->canny_high; } break;
-	case MLIS_OPT_AMD_CANNY_L2: { int *p = va_arg(ap, int*); if (p) *p = S->canny_l2; } break;
-	case MLIS_OPT_AMD_INPAINT_AREA: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_area; } break;
-	case MLIS_OPT_AMD_INPAINT_PADDING: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_padding; } break;
-	case MLIS_OPT_AMD_MASK_BLUR: { float *p = va_arg(ap, float*); if (p) *p = S->mask_blur; } break;
-	case MLIS_OPT_AMD_MASK_GROW: { int *p = va_arg(ap, int*); if (p) *p = S->mask_grow; } break;
-	case MLIS_OPT_AMD_MASK_INVERT: { int *p = va_arg(ap, int*); if (p) *p = S->mask_invert; } break;
-	case MLIS_OPT_AMD_INPAINT_COMPOSITE: { int *p = va_arg(ap, int*); if (p) *p = S->inpaint_composite; } break;
-	case MLIS_OPT_AMD_FREEU_B1: case MLIS_OPT_AMD_FREEU_B2: case MLIS_OPT_AMD_FREEU_S1: case MLIS_OPT_AMD_FREEU_S2:
-		{ float *p = va_arg(ap, float*); if (p) *p = S->freeu_f[id - MLIS_OPT_AMD_FREEU_B1]; } break;
-	case MLIS_OPT_PROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->prompt_raw ? S->prompt_raw : ""; } break;
-	case MLIS_OPT_NPROMPT: { const char **p = va_arg(ap, const char**); if (p) *p = S->nprompt_raw ? S->nprompt_raw : ""; } break;
-	default: r = api_error(S, MLIS_E_UNK_OPT, "unknown option %u", (unsigned)id);
-	}
+	if (o->kind == OK_FLOAT) { float *out = va_arg(ap, float*); if (out) *out = *(const float*)p; }
+	else if (o->kind == OK_STR) { const char **out = va_arg(ap, const char**); if (out) *out = *(char* const*)p ? *(char* const*)p : ""; }
+	else { int *out = va_arg(ap, int*); if (out) *out = o->kind == OK_CUSTOM ? o->get(S) : *(const int*)p; }
 	va_end(ap);
-	return r;
+	return 1;
 }
 
 MLB_API int mlis_amd_prompt_tokens_set(MLIS_Ctx* S, const int32_t* tokens, const float* weights, int n, int negative)
@@ -1864,6 +1832,15 @@ static int denoise_cb(void* user, int step, int n_step, int nfe)
 
 static int hires_on(const MLIS_Ctx* S) { return S->hires_scale > 1; }
 
+/* a model file's name as the infotext gives it: the basename without its extension, *len characters from the result */
+static const char* path_stem(const char* path, int* len)
+{
+	const char *b = path ? path : "", *sl = strrchr(b, '/'); if (sl) b = sl + 1;
+	const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
+	*len = (int)(e - b);
+	return b;
+}
+
 static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 {	/* mlis_infotext_update :1589-1632 (imitates stable-diffusion-webui create_infotext) */
 	char buf[4096]; int n = 0;
@@ -1883,26 +1860,19 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	ADD(", NFE: %u", (unsigned)S->last_nfe);
 	ADD(", Size: %ux%u", (unsigned)w, (unsigned)h);
 	ADD(", Clip skip: %d", S->clip_skip);
-	{
-		const char *b = S->path_model ? S->path_model : "", *sl = strrchr(b, '/'); if (sl) b = sl + 1;
-		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
-		ADD(", Model: %.*s", (int)(e - b), b);
-	}
+	int nb; const char *b = path_stem(S->path_model, &nb);
+	ADD(", Model: %.*s", nb, b);
 	if (S->flags & CF_USE_TAE) ADD(", VAE: tae");
 	if (S->tiling) ADD(", Tiling: %s", k_tiling[S->tiling]);
-	if (hires_on(S) && S->hires_use_model) {       /* the model file's basename, as ControlNet below */
-		const char *b = S->path_upscale ? S->path_upscale : "", *sl = strrchr(b, '/'); if (sl) b = sl + 1;
-		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
-		ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %.*s, Denoising strength: %g", S->hires_scale, hires_n_step, (int)(e - b), b, S->hires_denoise);
-	} else if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
+	b = path_stem(S->path_upscale, &nb);
+	if (hires_on(S) && S->hires_use_model)
+		ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %.*s, Denoising strength: %g", S->hires_scale, hires_n_step, nb, b, S->hires_denoise);
+	else if (hires_on(S)) ADD(", Hires upscale: %g, Hires steps: %d, Hires upscaler: %s, Denoising strength: %g", S->hires_scale, hires_n_step,
 		k_resample[S->hires_upscaler], S->hires_denoise);
 	if (S->tiled_tile) ADD(", Tiled diffusion: %d, Tile overlap: %d", S->tiled_tile, S->tiled_overlap);
 	if (S->tiled_tile && S->tiled_pack > 1) ADD(", Tile batch: %d", S->tiled_pack);
-	if (!str_empty(S->path_control)) {
-		const char *b = S->path_control, *sl = strrchr(b, '/'); if (sl) b = sl + 1;
-		const char *e = strrchr(b, '.'); if (!e) e = b + strlen(b);
-		ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", (int)(e - b), b, S->control_strength, S->control_start, S->control_end);
-	}
+	b = path_stem(S->path_control, &nb);
+	if (!str_empty(S->path_control)) ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", nb, b, S->control_strength, S->control_start, S->control_end);
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
 	if (S->pag_scale > 0) ADD(", PAG: %g", S->pag_scale);

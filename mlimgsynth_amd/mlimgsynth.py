@@ -199,9 +199,9 @@ class MLImgSynth:
         return r
 
     def option_get(self, option, out):
-        """out: a ctypes object receiving the value (c_char_p for MODEL / PROMPT / NPROMPT, c_int for MODEL_TYPE: the four options
-        mlis_option_get implements, as in the reference; c_int for AMD_TILING / AMD_HIRES_STEPS / AMD_HIRES_UPSCALER / AMD_UNET_TILE / AMD_UNET_TILE_OVERLAP / AMD_UNET_TILE_BATCH / AMD_DOWNSCALE_FILTER, c_float for
-        AMD_HIRES_SCALE / AMD_HIRES_DENOISE)."""
+        """out: a ctypes object receiving the value: c_int for int, bool and enum options, c_float for float options, c_char_p for
+        string options.  mlis_option_get serves MODEL, MODEL_TYPE, PROMPT and NPROMPT, as in the reference, and every MLIS_OPT_AMD_* option
+        (AMD_CONTROL_IMAGE gives a c_int: whether an image is set)."""
         r = self._lib.mlis_option_get(self._ctx, option, ctypes.byref(out))
         if r < 0:
             raise RuntimeError("Failed to get option %s: %s" % (option, self.errstr_get()))

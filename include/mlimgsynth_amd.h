@@ -494,7 +494,7 @@ int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, 
  * runs in tile-major order too); the ControlNet's encoder copy is never perturbed, its plan holds the other groups and the UNet plan's sums hand the perturbed group
  * the cond group's residuals; tiled and packed engines blend three groups (the mix is affine in eps).  An engine whose rows per plan evaluation exceed what a plain
  * engine may hold (128) is refused at creation.
- * set_pag: the scale, 0 .. 20, else an error; a field of the engine handed to the mix kernels (mlsd_dxdt_pag, mlsd_euler_pag_update) by value, so it changes between
+ * set_pag: the scale, 0 .. 20, else an error; a field of the engine handed to the mix kernels (mlsd_dxdt_guided, mlsd_euler_guided_update: the ones every engine runs) by value, so it changes between
  * generations, and under use_hipgraph, without touching a plan.  Engines start at 0, where the flag alone computes what the plain mix does (the third group is
  * evaluated and not read).  pag_info: the perturbed self-attentions of the UNet plan (0 without the flag) and the rows of one evaluation.
  * Not included: layer selections other than the middle block; a step window or an adaptive scale (a plan is fixed: outside a window the perturbed rows would still be
@@ -512,7 +512,7 @@ int mlis_amd_pag_info(const MLIS_AmdCtx* S, int* n_attn, int* rows);
  *     Karras with zsnr spends its steps between 4518 and sigma_min: allowed, the user's choice.  No trailing / SGM spacing here.
  *   set_cfg_rescale: phi 0 .. 1 (0 = off; front ends use 0.7).  Where phi > 0 and the guided prediction differs from the cond one (cfg_scale > 1, or PAG with a scale),
  *     dxdt_finish and the fused Euler step run mlsd_guidance_stats on the raw outputs (of a tiled engine: the blended canvas, so the statistics are the whole image's)
- *     and then mlsd_dxdt_rescaled / mlsd_euler_rescaled_update: three launches per mix.  The hires fix rescales in both passes; the statistics are per image, so a
+ *     and hand its factors to mlsd_dxdt_guided / mlsd_euler_guided_update: three launches per mix.  The hires fix rescales in both passes; the statistics are per image, so a
  *     multi-GPU split needs no communication.
  *   guidance_info: the resolved values, the sigma range, phi, the rescaled mixes so far and the last mix's factors (returns how many were written).
  * prediction_resolve: the pure rule of the `prediction` / `zsnr` options.  opt_prediction 0 auto, 1 eps, 2 v; opt_zsnr 0 auto, 1 off, 2 on; ckpt_v_pred / ckpt_ztsnr:

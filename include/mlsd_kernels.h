@@ -403,50 +403,52 @@ int mlsd_noise_add(float* x, const float* noise, const float* s, int B, int64_t 
 /* ---- general sampler (all solvers / in-painting / img2img / v-prediction): one launch per loop of the reference, same
  * fp32/fp64 operation order (bit-identical to the host arithmetic).  x, dx, tmp vectors: NCHW fp32 [B][C][HW], n = B*C*HW.
  * Scalars by value (they are wave-uniform kernel arguments: nothing to upload or sync). */
-/* dx = CFG mix (src/mlimgsynth.c:1565-1587) of the UNet outputs eps NHWC [2B|B][HW][ld]; vparam != 0: each branch first
- * rescaled out*c_out + x_eval*c_skip (src/unet.c:490-494) */
+/* The guidance mix (csrc/hip/guidance.hip): the guided prediction of one evaluation, from the UNet output eps NHWC [N][HW][ld] with the row groups
+ * [cond B | uncond B (only at cfg > 1) | perturbed B (only read at pag != 0)].  Classifier-free guidance is src/mlimgsynth.c:1565-1587; perturbed-attention guidance
+ * ("Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance", 2024) and guidance rescale ("Common Diffusion Noise Schedules and Sample Steps are Flawed",
+ * 2023, Algorithm 2) are not in the reference.  Per element, every operation rounded once:
+ *   guided(c, u, p):  g = c;   cfg > 1: g = fadd(fmul(c, cfg), fmul(u, 1 - cfg));   pag != 0: g = fadd(g, fmul(pag, fsub(c, p)))
+ *   v(e) = vparam ? fadd(fmul(e, c_out), fmul(x_eval, c_skip)) : e                                                          (src/unet.c:490-494)
+ *   factor == NULL:  dx = guided(v(c), v(u), v(p))            -- the v map on each group, then the mix
+ *   factor != NULL:  dx = v(fmul(guided(c, u, p), factor[b])) -- the mix of the RAW outputs, the rescale, then the v map once (other arithmetic, on purpose)
+ * Rows a launch does not need (uncond at cfg <= 1, perturbed at pag == 0) are never read.  cfg, pag and the scalars go by value (wave-uniform): they change between
+ * launches, and under a captured evaluation, without anything being rebuilt; factor is a device pointer to B floats.
+ * Forms, all of the same bytes: C == 4, ld % 4 == 0 and eps 16-byte aligned: a thread owns pixels, one 16-byte load per group row -- four pixels where HW % 4 == 0
+ * and x, out and noise are 16-byte aligned, else one; everything else: element by element.  ld = 4 (the tiled canvas) and the plan's padded stride alike.
+ * euler_guided_update: the fused Euler(-ancestral) step (eps models: no v map), x updated in place: fadd(x, fmul(dx, dt)), then fadd(., fmul(noise, s_up)) where
+ * noise is given -- dxdt_guided + mlsd_vec_axpy + mlsd_noise_add_s bit for bit (src/solvers.c:86, src/sampling.c:170-174).
+ * Refused before any launch, by every entry below: a NULL eps, dx or x (x_eval may be NULL without vparam), B, C or HW below 1, ld < C, pag < 0 or NaN, cfg NaN,
+ * 2^31 elements or more.  (The two *_cfg entries launched unchecked, and the two *_pag entries took a NaN cfg, before the mix was stated once.) */
+int mlsd_dxdt_guided(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag, const float* factor /* NULL: no rescale */,
+                     int vparam, float c_out, float c_skip, void* stream);
+int mlsd_euler_guided_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, const float* factor, float dt,
+                             const float* noise, float s_up, void* stream);
+/* the narrow names: the general entries with some arguments fixed; error texts name the entry that was called */
 int mlsd_dxdt_cfg(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg,
-                  int vparam, float c_out, float c_skip, void* stream);
-/* fused Euler(-ancestral) step with the CFG mix (one launch per step; the 1-NFE eps-model path):
- * x += (eps_c*f + eps_u*(1-f))*dt [+ noise*s_up]; same operation order as dxdt_cfg + vec_axpy + noise_add_s */
+                  int vparam, float c_out, float c_skip, void* stream);                                                   /* pag 0, factor NULL */
 int mlsd_euler_cfg_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float dt,
-                          const float* noise, float s_up, void* stream);
-/* Perturbed-attention guidance (csrc/hip/guidance.hip; not in the reference): the mix of a plan with a third row group.  eps NHWC [N][HW][ld] with the groups
- * [cond B | uncond B (only at cfg > 1) | perturbed B], so N = (cfg > 1 ? 2B : B) + B.  Per element, c, u, p after the v-prediction rescale:
- *   g = the value mlsd_dxdt_cfg computes, by its very operations;  dx = fadd(g, fmul(pag, fsub(c, p))), each rounded once.
- * pag == 0 takes mlsd_dxdt_cfg's path: the same bytes, and the perturbed rows are not read.  cfg and pag go by value (wave-uniform): they change between launches,
- * and under a captured evaluation, without anything being rebuilt.  ld = 4 (the tiled canvas) and the plan's padded stride alike; 16-byte accesses where C == 4,
- * ld % 4 == 0 and eps is 16-byte aligned (and on the NCHW side where HW % 4 == 0 and the planes are aligned), element by element elsewhere.
- * Refused before any launch: a NULL buffer (x_eval may be NULL without vparam), B, C or HW below 1, ld < C, pag < 0 or NaN, 2^31 elements or more.
- * euler_pag_update: the fused Euler(-ancestral) step with this mix (eps models: no rescale), x updated in place; operation order of mlsd_dxdt_pag + mlsd_vec_axpy +
- * mlsd_noise_add_s, bit for bit (noise NULL: no third part). */
+                          const float* noise, float s_up, void* stream);                                                  /* pag 0, factor NULL */
 int mlsd_dxdt_pag(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag,
-                  int vparam, float c_out, float c_skip, void* stream);
+                  int vparam, float c_out, float c_skip, void* stream);                                                   /* factor NULL */
 int mlsd_euler_pag_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float dt,
-                          const float* noise, float s_up, void* stream);
-/* Guidance rescale (csrc/hip/guidance.hip; "Common Diffusion Noise Schedules and Sample Steps are Flawed", 2023, Algorithm 2; not in the reference).  eps and the row
- * groups as for mlsd_dxdt_pag.  Per image b over its n = C*HW elements, c, u, p the RAW outputs of the groups (a v model's own prediction, before the v map):
- *   g = fadd(fmul(c, cfg), fmul(u, 1 - cfg))  (cfg > 1; else c);   g = fadd(g, fmul(pag, fsub(c, p)))  (pag != 0)
- *   f = phi*sqrt(M2(c) / M2(g)) + (1 - phi),  M2 the sum of squared deviations from the mean (the n - 1 of the standard deviations cancels); formed in double, rounded
- *       once to float; 1 where M2(g) is zero or not finite, where n == 1, and where g is c (cfg <= 1 and pag == 0: the statistics are not launched)
- *   r = fmul(g, f);   dx = vparam ? fadd(fmul(r, c_out), fmul(x, c_skip)) : r
+                          const float* noise, float s_up, void* stream);                                                  /* factor NULL */
+int mlsd_dxdt_rescaled(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag,
+                       const float* factor, int vparam, float c_out, float c_skip, void* stream);                         /* a NULL factor is refused */
+int mlsd_euler_rescaled_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, const float* factor, float dt,
+                               const float* noise, float s_up, void* stream);                                             /* a NULL factor is refused */
+/* The factor of the guidance rescale, per image b over its n = C*HW elements, c, u, p the RAW outputs of the groups (a v model's own prediction, before the v map):
+ *   f = phi*sqrt(M2(c) / M2(guided(c, u, p))) + (1 - phi),  M2 the sum of squared deviations from the mean (the n - 1 of the standard deviations cancels); formed in
+ *       double, rounded once to float; 1 where M2(g) is zero or not finite, where n == 1, and where g is c (cfg <= 1 and pag == 0: the statistics are not launched)
  * guidance_stats writes factor[b] (device, B floats): one launch of (mlsd_guidance_blocks(HW), B) blocks -- a rule of HW alone -- that accumulate sums and sums of
  * squares in double (lanes, then waves, then LDS; each block stores four doubles to scratch[b][block][4]), one launch that sums an image's partials in block order.  No
  * atomics and no block waits on another, so the factors are the same bits on every run.  scratch: mlsd_guidance_scratch_bytes(B, HW) bytes (at most
- * B * MLSD_GUIDANCE_MAX_BLOCKS * 32), 8-byte aligned.
- * dxdt_rescaled / euler_rescaled_update: mlsd_dxdt_pag / mlsd_euler_pag_update with the multiplication by factor[b] (a device pointer), same access pattern; the fused
- * form (eps models) equals dxdt_rescaled + mlsd_vec_axpy + mlsd_noise_add_s bit for bit.
- * Refused before any launch: a NULL buffer (x_eval may be NULL without vparam), B, C or HW below 1, ld < C, pag < 0 or NaN, cfg NaN, phi outside 0 .. 1 or NaN,
- * 2^31 elements or more, a scratch smaller than mlsd_guidance_scratch_bytes. */
+ * B * MLSD_GUIDANCE_MAX_BLOCKS * 32), 8-byte aligned.  A rescaled mix is three launches: these two and the mix.
+ * Refused before any launch: what the mix entries refuse, a NULL scratch or factor, phi outside 0 .. 1 or NaN, a scratch smaller than mlsd_guidance_scratch_bytes. */
 #define MLSD_GUIDANCE_MAX_BLOCKS 64
 int    mlsd_guidance_blocks(int HW);
 size_t mlsd_guidance_scratch_bytes(int B, int HW);
 int mlsd_guidance_stats(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float phi, double* scratch, size_t scratch_bytes,
                         float* factor, void* stream);
-int mlsd_dxdt_rescaled(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg, float pag,
-                       const float* factor, int vparam, float c_out, float c_skip, void* stream);
-int mlsd_euler_rescaled_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, const float* factor, float dt,
-                               const float* noise, float s_up, void* stream);
 int mlsd_vec_axpy(float* out, const float* x, const float* d, float dt, int64_t n, void* stream);     /* out = x + d*dt (solvers.c:86,105,278) */
 int mlsd_solver_heun_corr(float* x, const float* dx, const float* d1, float dt, int64_t n, void* stream);   /* solvers.c:112-113 */
 int mlsd_solver_taylor3(float* x, const float* dx, float* dp1, float* dp2, float dt, float idtp, float f2, float f3,

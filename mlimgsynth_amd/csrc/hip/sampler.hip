@@ -2,55 +2,14 @@
 // Each kernel restates ONE loop of the reference with the SAME fp32 / fp64 operation order (no contraction: explicit
 // _rn intrinsics), so the device sampler is bit-identical to the host arithmetic of
 //   src/solvers.c:82-296 (euler, heun, taylor3, dpmpp2m, dpmpp2s), src/sampling.c:98-117 (mask blend, noise add),
-//   src/mlimgsynth.c:1565-1587 (CFG mix), src/unet.c:490-494 (v-parameterisation rescale), src/vae.c:203-229 (latent sample).
+//   src/vae.c:203-229 (latent sample).  The CFG mix (src/mlimgsynth.c:1565-1587) with the v-parameterisation rescale (src/unet.c:490-494), and the fused Euler
+// step behind it, stand in guidance.hip.
 // All of it is HBM-bound elementwise work over <= 4 MB: negligible next to a UNet evaluation.
 #include <hip/hip_runtime.h>
 #include "common.hpp"
 #include "mlsd_kernels.h"
 
 namespace {
-
-// dx = mix(vparam(eps_c), vparam(eps_u)); eps NHWC [N][HW][ld] (cond rows 0..B-1, uncond B..2B-1), x / dx NCHW [B][C][HW]
-__global__ void dxdt_cfg_kernel(const float* __restrict__ eps, long ld, const float* __restrict__ x, float* __restrict__ dx,
-                                int B, int C, int HW, float cfg, int vparam, float c_out, float c_skip)
-{
-    const long total = (long)B * C * HW;
-    GRID_LOOP(i, total) {
-        const int pix = (int)(i % HW);
-        const long t = i / HW;
-        const int c = (int)(t % C), b = (int)(t / C);
-        float d = eps[((long)b * HW + pix) * ld + c];
-        const float xv = vparam ? x[i] : 0.f;
-        if (vparam) d = __fadd_rn(__fmul_rn(d, c_out), __fmul_rn(xv, c_skip));            // unet.c:493
-        if (cfg > 1.0f) {
-            float u = eps[((long)(b + B) * HW + pix) * ld + c];
-            if (vparam) u = __fadd_rn(__fmul_rn(u, c_out), __fmul_rn(xv, c_skip));
-            d = __fadd_rn(__fmul_rn(d, cfg), __fmul_rn(u, 1.0f - cfg));                    // mlimgsynth.c:1583
-        }
-        dx[i] = d;
-    }
-}
-
-// fused Euler(-ancestral) step with the CFG mix (the headline path: one launch per step):
-//   dx = c*f + u*(1-f) (mlimgsynth.c:1583);  x += dx*dt (solvers.c:86);  x += noise*s_up (sampling.c:115)
-__global__ void euler_cfg_kernel(float* __restrict__ x, const float* __restrict__ eps, long ld, int B, int C, int HW, float cfg,
-                                 float dt, const float* __restrict__ noise, float s_up)
-{
-    const long total = (long)B * C * HW;
-    GRID_LOOP(i, total) {
-        const int pix = (int)(i % HW);
-        const long t = i / HW;
-        const int c = (int)(t % C), b = (int)(t / C);
-        float dx = eps[((long)b * HW + pix) * ld + c];
-        if (cfg > 1.0f) {
-            const float du = eps[((long)(b + B) * HW + pix) * ld + c];
-            dx = __fadd_rn(__fmul_rn(dx, cfg), __fmul_rn(du, 1.0f - cfg));
-        }
-        float v = __fadd_rn(x[i], __fmul_rn(dx, dt));
-        if (noise) v = __fadd_rn(v, __fmul_rn(noise[i], s_up));
-        x[i] = v;
-    }
-}
 
 // out = x + d*dt   (euler step solvers.c:86 with out == x; heun / dpmpp2s predictor :105, :278 with out = x1)
 __global__ void axpy_kernel(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ d, float dt, long n)
@@ -191,23 +150,6 @@ MLSD_API int mlsd_copy_slice2(float* dst, int dw, int dh, const float* src, int 
     hipLaunchKernelGGL(copy_slice2_kernel, dim3(nblk((long)planes * n0 * n1)), dim3(256), 0, (hipStream_t)stream, dst, dw, dh, src, sw, sh,
                        n0, n1, di0, di1, si0, si1, planes);
     return mlsd_check_launch("copy_slice2");
-}
-
-
-MLSD_API int mlsd_dxdt_cfg(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, float cfg,
-                           int vparam, float c_out, float c_skip, void* stream)
-{
-    hipLaunchKernelGGL(dxdt_cfg_kernel, dim3(nblk((long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, eps, (long)ld, x_eval, dx,
-                       B, C, HW, cfg, vparam, c_out, c_skip);
-    return mlsd_check_launch("dxdt_cfg");
-}
-
-MLSD_API int mlsd_euler_cfg_update(float* x, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float dt,
-                                   const float* noise, float s_up, void* stream)
-{
-    hipLaunchKernelGGL(euler_cfg_kernel, dim3(nblk((long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, x, eps, (long)ld, B, C, HW,
-                       cfg, dt, noise, s_up);
-    return mlsd_check_launch("euler_cfg_update");
 }
 
 MLSD_API int mlsd_vec_axpy(float* out, const float* x, const float* d, float dt, int64_t n, void* stream)

@@ -736,27 +736,30 @@ static const float* eps_get(MLIS_AmdCtx* S, int64_t* ld)
 	return mlctx_tensor_device_f32(S->unet_ctx, S->unet.t_out, ld);
 }
 
-/* guidance rescale runs where phi > 0 and the guided prediction is not the cond prediction itself; elsewhere the plain kernels, and their bytes */
+/* guidance rescale runs where phi > 0 and the guided prediction is not the cond prediction itself; elsewhere no factor, and the plain mix's bytes */
 static int rescale_on(const MLIS_AmdCtx* S) { return S->cfg_rescale > 0 && (S->c.cfg_scale > 1 || (S->pag && S->pag_scale != 0)); }
-static int rescale_stats(MLIS_AmdCtx* S, const float* eps, int64_t ld)
+
+/* what the mix entries take beside cfg_scale: the PAG scale and, with the rescale on, the factors of this evaluation's raw outputs (the blended canvas of a tiled
+ * engine: the whole image), whose statistics are enqueued here; < 0 on error */
+static int guidance_args(MLIS_AmdCtx* S, const float* eps, int64_t ld, float* pag, const float** factor)
 {
+	*pag = S->pag ? S->pag_scale : 0;
+	*factor = NULL;
+	if (!rescale_on(S)) return 1;
+	*factor = S->d_gr_factor;
 	S->gr_evals++;
-	return mlsd_guidance_stats(eps, ld, S->B, 4, S->hw, S->c.cfg_scale, S->pag ? S->pag_scale : 0, S->cfg_rescale, S->d_gr_part, S->gr_part_bytes, S->d_gr_factor, S->stream);
+	return mlsd_guidance_stats(eps, ld, S->B, 4, S->hw, S->c.cfg_scale, *pag, S->cfg_rescale, S->d_gr_part, S->gr_part_bytes, S->d_gr_factor, S->stream) ? -1 : 1;
 }
 
-/* dx = CFG mix (+ v-param rescale) of the evaluation just enqueued */
+/* dx = guidance mix (+ v-param rescale) of the evaluation just enqueued */
 static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* dx)
 {
 	int64_t ld = 0;
-	const float *eps = eps_get(S, &ld);
+	const float *eps = eps_get(S, &ld), *factor;
 	const float c_skip = sigma / (sigma*sigma + 1), c_out = 1 / sqrt(sigma*sigma + 1);   /* unet.c:491-492 */
-	if (rescale_on(S)) {      /* statistics of the raw outputs (the blended canvas of a tiled engine: the whole image), then the mix with the factor */
-		const float pag = S->pag ? S->pag_scale : 0;
-		if (rescale_stats(S, eps, ld)) return -1;
-		return mlsd_dxdt_rescaled(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, pag, S->d_gr_factor, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
-	}
-	if (S->pag) return mlsd_dxdt_pag(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->pag_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
-	return mlsd_dxdt_cfg(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
+	float pag;
+	if (guidance_args(S, eps, ld, &pag, &factor) < 0) return -1;
+	return mlsd_dxdt_guided(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, pag, factor, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 }
 
 /* one evaluation for tests and tools: x host [B][4][lh][lw] -> dx = dxdt(x, sigma) host, through the very unet_eval + dxdt_finish the denoising loop uses (plain
@@ -849,15 +852,12 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 			if (unet_eval(S, S->d_x, t0, k_prefetch) < 0) return -1;
 			if (!P->vparam) {   /* fused: CFG mix, x += dx*dt and the ancestral noise of sampling.c:170-172 in one launch */
 				int64_t ld = 0;
-				const float *eps = eps_get(S, &ld);
+				const float *eps = eps_get(S, &ld), *factor;
 				const float *nz = anc_noise ? noise_draw(S, S->k_draw) : NULL;
+				float pag;
 				if (anc_noise && !nz) return -1;
-				if (rescale_on(S)) {
-					if (rescale_stats(S, eps, ld)) return -1;
-					if (mlsd_euler_rescaled_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, S->pag ? S->pag_scale : 0, S->d_gr_factor, t1 - t0, nz, s_up, st)) return -1;
-				} else
-				if (S->pag ? mlsd_euler_pag_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, S->pag_scale, t1 - t0, nz, s_up, st)
-				           : mlsd_euler_cfg_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, t1 - t0, nz, s_up, st)) return -1;
+				if (guidance_args(S, eps, ld, &pag, &factor) < 0) return -1;
+				if (mlsd_euler_guided_update(S->d_x, eps, ld, B, 4, S->hw, S->c.cfg_scale, pag, factor, t1 - t0, nz, s_up, st)) return -1;
 				if (nz) { S->k_draw++; s_up = -1; }                               /* noise already added */
 			} else {
 				if (dxdt_finish(S, S->d_x, t0, S->d_dx) < 0) return -1;

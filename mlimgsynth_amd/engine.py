@@ -693,7 +693,7 @@ class Generator:
         check1(_proto2().mlis_amd_set_prediction(self.h, int(vparam), int(zsnr)), "mlis_amd_set_prediction")
 
     def set_cfg_rescale(self, phi=0.7):
-        """mlis_amd_set_cfg_rescale: phi of the guidance rescale, 0 .. 1; engines start at 0 (the plain mix kernels)"""
+        """mlis_amd_set_cfg_rescale: phi of the guidance rescale, 0 .. 1; engines start at 0 (the mix without a factor)"""
         check1(_proto2().mlis_amd_set_cfg_rescale(self.h, float(phi)), "mlis_amd_set_cfg_rescale")
 
     def last_rows(self):

@@ -346,9 +346,23 @@ def ctrl_add(dst, ld_dst, base, ld_base, ctrl, ld_ctrl, n_img, rows_per_img, C, 
           "mlsd_ctrl_add")
 
 
+def dxdt_guided(eps, ld, x_eval, dx, B, C, HW, cfg, pag=0.0, factor=None, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
+    """mlsd_dxdt_guided: dx [B][C][HW] = the guidance mix of eps NHWC [N][HW][ld] (groups cond | uncond at cfg > 1 | perturbed, read at pag != 0).  factor None:
+    the v map on each group with vparam, then the mix; factor (device, [B]): the mix of the raw outputs * factor[b], then the v map (device pointers)."""
+    f = lib().mlsd_dxdt_guided
+    f.argtypes = [vp, c_i64, vp, vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, c_int, ctypes.c_float, ctypes.c_float, vp]
+    check(f(vp(eps), ld, vp(x_eval), vp(dx), B, C, HW, cfg, pag, vp(factor), int(vparam), c_out, c_skip, vp(stream)), "mlsd_dxdt_guided")
+
+
+def euler_guided_update(x, eps, ld, B, C, HW, cfg, pag=0.0, factor=None, dt=0.0, noise=None, s_up=0.0, stream=None):
+    """mlsd_euler_guided_update: x += mix * dt (+ noise * s_up), the fused Euler(-ancestral) step with the mix of dxdt_guided (eps models), in place"""
+    f = lib().mlsd_euler_guided_update
+    f.argtypes = [vp, vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, ctypes.c_float, vp, ctypes.c_float, vp]
+    check(f(vp(x), vp(eps), ld, B, C, HW, cfg, pag, vp(factor), dt, vp(noise), s_up, vp(stream)), "mlsd_euler_guided_update")
+
+
 def dxdt_pag(eps, ld, x_eval, dx, B, C, HW, cfg, pag, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
-    """mlsd_dxdt_pag: dx [B][C][HW] = the CFG mix of eps NHWC [N][HW][ld] (groups cond | uncond at cfg > 1 | perturbed) + pag * (cond - perturbed), each
-    group after the v-prediction rescale with vparam; pag == 0 is mlsd_dxdt_cfg's path and does not read the perturbed rows (device pointers)."""
+    """mlsd_dxdt_pag: dxdt_guided without a factor (device pointers)"""
     f = lib().mlsd_dxdt_pag
     f.argtypes = [vp, c_i64, vp, vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, ctypes.c_float, ctypes.c_float, vp]
     check(f(vp(eps), ld, vp(x_eval), vp(dx), B, C, HW, cfg, pag, int(vparam), c_out, c_skip, vp(stream)), "mlsd_dxdt_pag")

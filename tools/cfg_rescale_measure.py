@@ -2,7 +2,7 @@
 
 ONE process, per case (model, size, batch): buffers of the mix's shapes (eps NHWC [2B][HW][ld] with the plan's dense ld = 4, x and dx NCHW [B][4][HW]) and, after a
 warm-up of every kernel, --repeats rounds that alternate four timed windows of --launches launches each, a device event on either side:
-  plain      mlsd_dxdt_cfg, the mix without the rescale (the kernel of the commit before the option)
+  plain      mlsd_dxdt_cfg, the mix without the rescale (the guided mix with pag 0 and no factor)
   rescaled   mlsd_guidance_stats (statistics + factor) + mlsd_dxdt_rescaled: the three launches of a rescaled mix
   stats      mlsd_guidance_stats alone
   copy       a device-to-device copy of the bytes the statistics kernel reads (the cond and uncond groups)

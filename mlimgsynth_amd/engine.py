@@ -380,14 +380,18 @@ class Unet:
             f.argtypes = [vp, ctypes.c_size_t]
             check1(f(self.ctx.h, int(stream_weights_mib) << 20), "mlctx_set_weight_streaming")
         self.S = UnetState()
-        if n_ctx_tok == 77:
-            check1(L().unet_denoise_init_n(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch), "unet_denoise_init_n")
-        else:                           # windowed prompt: cond [N][77 W][n_ctx]
-            check1(L().unet_denoise_init_nc(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch, int(n_ctx_tok)),
-                   "unet_denoise_init_nc")
-        check1(L().unet_denoise_build(ctypes.byref(self.S)), "unet_denoise_build")
-        if synth:
-            self.ctx.params_synth(seed)
+        try:
+            if n_ctx_tok == 77:
+                check1(L().unet_denoise_init_n(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch), "unet_denoise_init_n")
+            else:                       # windowed prompt: cond [N][77 W][n_ctx]
+                check1(L().unet_denoise_init_nc(ctypes.byref(self.S), self.ctx.h, ctypes.byref(self.P), lw, lh, n_batch, int(n_ctx_tok)),
+                       "unet_denoise_init_nc")
+            check1(L().unet_denoise_build(ctypes.byref(self.S)), "unet_denoise_build")
+            if synth:
+                self.ctx.params_synth(seed)
+        except Exception:               # a plan that cannot be built (a latent the levels do not halve evenly, memory) leaves no context behind
+            self.ctx.destroy()
+            raise
         self.lw, self.lh, self.n, self.n_ctx_tok = lw, lh, n_batch, int(n_ctx_tok)
 
     def run(self, x, cond, label, sigma):

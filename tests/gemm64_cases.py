@@ -3,6 +3,9 @@ tests/test_ref64_gemm_cpu.py).  A plain module: importable without a GPU.
 
 Every case names the label `kernels.gemm_variant(args)` must return for it, so that a case cannot drift silently to another tile; the
 census (test_gemm_float64_gpu.py::test_every_planned_gemm_path_has_a_float64_case) checks that every path the bench plans pick has a case.
+The two tables at the end hold one case per (tile, split form, epilogue feature set) the plans take, at the bench sizes and at the sizes of
+tests/plan_audit.py SIZE_PLANS (SD1.5 from 40x40 to 96x96, SDXL from 64x64 to 168x96, N = 1 .. 8, the VAEs and TAESD at other sizes);
+tests/test_plan_audit_gpu.py COVERED_ELSEWHERE names them form by form.
 
 Input families (make_operands):
   normal     centred N(0, 1) activations, N(0, 1 / K) weights;
@@ -165,11 +168,16 @@ CASES = [
 
 # ---- the epilogue combinations the bench plans put on each tile (tests/test_plan_audit_gpu.py, COVERED_ELSEWHERE): each case carries EXACTLY the features of one
 # op form -- row bias, residual, column statistics, the fp16 copy beside the fp32 output, the upsampled source -- because each combination selects its own epilogue body
-def _combo(cid, tile, tvn, cout, ksplit=1, ups=0, **f):
-    side = 8 if ups else 16
-    path = ("splitk_reduce_stats" if f.get("stats") else "splitk_reduce") if ksplit > 1 else tile
-    return conv(cid, L(tile, "conv", f",k/{ksplit}" if ksplit > 1 else ""), path, 2, side, side, 64, cout, 3, 1, 1, ups=ups, fam="offset", bias=True, ksplit=ksplit,
-                ws=ksplit > 1, tv=tv(tvn), **f)
+def _combo(cid, tile, tvn, cout, ksplit=1, ups=0, hw=None, lin_mk=None, fam="offset", **f):
+    """a 3x3 convolution of 2 images of hw = (H, W) x 64 channels (16 x 16, 8 x 8 with `ups`), or with lin_mk = (M, K) a Linear of M x cout x K, forced onto `tile`"""
+    H, W = hw or ((8, 8) if ups else (16, 16))
+    red = "splitk_reduce_ln" if f.get("ln") else "splitk_reduce_stats" if f.get("stats") else "splitk_reduce"
+    path = (tile if tile == SK29 else red) if ksplit > 1 else tile + (":geglu" if f.get("act") == 5 else "")
+    ending = ("+layernorm" if f.get("ln") else "") + (f",k/{ksplit}" if ksplit > 1 else "")
+    common = dict(fam=fam, bias=True, ksplit=ksplit, ws=ksplit > 1, tv=tv(tvn), **f)
+    if lin_mk:
+        return lin(cid, L(tile, "linear", ending), path, lin_mk[0], cout, lin_mk[1], **common)
+    return conv(cid, L(tile, "conv", ending), path, 2, H, W, 64, cout, 3, 1, 1, ups=ups, **common)
 
 
 CASES += [
@@ -199,6 +207,57 @@ CASES += [
     lin("p28_sk18_c16", L(P28), "128x320x64ppsk", 256, 320, 5760, fam="offset", sk=True, ws=True, bias=True, c16=True, tv=tv(28)),
     conv("p28_conv_rowbias", L(P28, "conv"), "128x320x64ppsk", 1, 16, 16, 640, 640, 3, 1, 1, fam="offset", sk=True, ws=True, bias=True, rowbias=256, tv=tv(28)),
 ]
+
+# ---- the forms the plans take at sizes other than the bench's (tests/plan_audit.py SIZE_PLANS; the census of tests/test_size_census_cpu.py and
+# tests/test_plan_audit_gpu.py): again EXACTLY the features of one op form, on the tile and split form the census met it on.  Where no feature forbids it the
+# convolutions have one full tile plus a ragged one in M and in N: 2 x (17 x 15) = 510 rows (2 x (9 x 7) upsampled: 504) and a cout that is no multiple of the tile
+# width.  Column statistics need M in whole statistics blocks: those keep 2 x (16 x 16) rows, with a ragged last column tile (as N = 320 and 640 are on 128 and 256).
+ODD, ODD_UPS = (17, 15), (9, 7)
+CASES += [
+    # 128x128, split-K: the reduce pass ends with the LayerNorm (SD1.5 and SDXL at small N: Linear with the residual, 1x1 proj_in convolution without), ...
+    _combo("sk0_ln_res", G0, 0, 640, ksplit=3, lin_mk=(128, 1280), resid=True, ln=True),
+    _combo("sk0_ln", G0, 0, 640, ksplit=3, lin_mk=(128, 1280), ln=True),
+    # ... a row bias alone (the time embedding on a long-K convolution of few rows), all three outputs of a 1x1 convolution, an upsampling convolution of odd extents
+    _combo("sk0_rowbias", G0, 0, 200, ksplit=3, hw=ODD, rowbias=255, fam="scales"),
+    _combo("sk0_c16_stats_res", G0, 0, 192, ksplit=3, c16=True, stats=True, resid=True),
+    _combo("sk0_ups", G0, 0, 200, ksplit=3, ups=1, hw=ODD_UPS, fam="normal"),
+    _combo("sk1_stats", G1, 1, 192, ksplit=3, stats=True),
+    # skinny M with a row bias: two images of 64 rows in the one block
+    _combo("s29_conv_rowbias", SK29, 29, 200, ksplit=3, hw=(8, 8), rowbias=64, fam="scales"),
+    # the general 128x320 tile (wave tile 32 x 160): what every SDXL latent that is not square, and 100 x 100, puts on it
+    _combo("g16_plain", G16, 16, 400, hw=ODD, fam="normal"),
+    _combo("g16_ups", G16, 16, 400, ups=1, hw=ODD_UPS, fam="scales"),
+    _combo("g16_res", G16, 16, 400, hw=ODD, resid=True, fam="scales"),
+    _combo("g16_rowbias", G16, 16, 400, hw=ODD, rowbias=255, fam="normal"),
+    _combo("g16_c16", G16, 16, 400, hw=ODD, c16=True, fam="scales"),
+    _combo("g16_c16_res", G16, 16, 400, hw=ODD, c16=True, resid=True, fam="normal"),
+    # the general 256x256 tile (16 waves of 64 x 64)
+    _combo("g9_geglu16", G9, 9, 640, lin_mk=(300, 320), fam="wideact", act=5, c32=False, c16=True),
+    _combo("g9_rowbias", G9, 9, 320, hw=ODD, rowbias=255, fam="normal"),
+    _combo("g9_stats_rowbias", G9, 9, 320, stats=True, rowbias=256),
+    _combo("g9_ups", G9, 9, 320, ups=1, hw=ODD_UPS, fam="scales"),
+    _combo("g9_res", G9, 9, 320, hw=ODD, resid=True, fam="scales"),
+    _combo("g9_stats_res", G9, 9, 320, stats=True, resid=True),
+    # the ping-pong 256x256 tiles (whole 128-row wave slabs, a row bias in whole tiles of 256 rows): a ragged last column tile; 384 rows = a tile and a half
+    _combo("p17_stats_rowbias", P17, 17, 320, stats=True, rowbias=256),
+    _combo("p21_stats_ups", P21, 21, 320, stats=True, ups=1),
+    _combo("p21_plain", P21, 21, 320, hw=(16, 12), fam="normal"),
+    # 256x128 with the 2-deep and the 3-deep ring: the KL-VAE at other sizes, and TAESD (relu AFTER the residual, fp16 beside fp32, fp16 alone)
+    _combo("g3_plain", G3, 3, 200, hw=ODD, fam="normal"),
+    _combo("g3_stats_res", G3, 3, 192, stats=True, resid=True),
+    _combo("g3_c16_relu_post", G3, 3, 200, hw=ODD, fam="wideact", act=4, resid=True, post=True, c16=True),
+    _combo("g3_c16_ups", G3, 3, 200, ups=1, hw=ODD_UPS, c16=True, fam="scales"),
+    _combo("g4_ups", G4, 4, 200, ups=1, hw=ODD_UPS, fam="scales"),
+    _combo("g4_c16_ups", G4, 4, 200, ups=1, hw=ODD_UPS, c16=True, fam="normal"),
+    _combo("g4_relu_post16", G4, 4, 200, hw=ODD, fam="wideact", act=4, resid=True, post=True, c32=False, c16=True),
+    # forms only the device census meets (stream-K and the in-launch hand-offs ask the device for its CUs; the dry runtime plans their fall-backs): the statistics
+    # epilogues of the four-phase ping-pong tiles with a residual and with a row bias (400 columns: a tile and one wave column of 80), ...
+    _combo("p17_stats_res", P17, 17, 320, stats=True, resid=True),
+    _combo("p18_stats_rowbias", P18, 18, 400, stats=True, rowbias=256),
+    # ... and stream-K on the 256x256 tile with a row bias: 4 tiles x 90 K tiles in shares of 5, 18 contributors per tile
+    conv("p19_conv_rowbias", L(P19, "conv"), "256x256x64ppsk", 2, 16, 16, 640, 320, 3, 1, 1, fam="scales", sk=True, ws=True, bias=True, rowbias=256, tv=tv(19)),
+]
+assert len({c["id"] for c in CASES}) == len(CASES)
 
 BY_ID = {c["id"]: c for c in CASES}
 

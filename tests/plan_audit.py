@@ -17,6 +17,10 @@ the worst ratio to the bound per output; kinds and arguments it does not know FA
 Forms of the option plans: the control sum (cadd: its residuals and its gain live in ANOTHER plan's memory and a driver buffer, declared to Plan as
 external ranges), the two FreeU passes, HyperTile's permuting copy (copy with th > 0) and the phase launches of an upsampling convolution (GEMM with
 out_phase: the write is a strided pixel map, one Range per (image, source row)).
+
+The census: census_key(op) is the form of an op (kind, GEMM tile and split form or attention kernel, epilogue features); unheld_forms() names the forms of a set of
+plans that nothing holds.  It runs over BENCH_PLANS and over SIZE_PLANS, 35 plans at sizes other than the bench's (SD1.5 40x40 .. 96x96, SDXL 64x64 .. 168x96,
+N = 1 .. 8, a long prompt, the VAEs and TAESD at other sizes), in the dry runtime and on the device.
 """
 import bisect
 import ctypes
@@ -866,6 +870,40 @@ VARIANT_PLANS = [
 ]
 # as bench.py builds them: SD1.5 64x64 N = 2 and SDXL 128x128 batch 4 (N = 8), and their KL-VAE decoders
 BENCH_PLANS = [("unet", "sd1", 64, 2), ("unet", "sdxl", 128, 8), ("vae_dec", "sd1", 64, 1), ("vae_dec", "sdxl", 128, 4)]
+
+# Sizes other than the two benchmarks, for the op-form census only (built, never computed): which tile a GEMM takes is a function of its exact shape (an exact hit in
+# the tune table, a neighbour's tile from 1024 rows on, else the launcher's static rule), and each (tile, split form, epilogue features) selects its own epilogue body.
+# N = images x guidance groups: 1 = guidance off, 2 = batch 1, 3 = batch 1 with PAG, 4 = batch 2, ...
+SIZE_PLANS = [
+    # SD1.5: the square bench latent at the other row counts (N = 1 is the API's default with guidance off) ...
+    ("unet", "sd1", 64, 1), ("unet", "sd1", 64, 3), ("unet", "sd1", 64, 4), ("unet", "sd1", 64, 6), ("unet", "sd1", 64, 8),
+    # ... portrait, landscape and 768 x 768; latents whose deepest level has odd extents (9 x 11, 11 x 9); a small latent (deepest level 5 x 5)
+    ("unet", "sd1", (64, 96), 2), ("unet", "sd1", (96, 64), 2), ("unet", "sd1", 96, 2),
+    ("unet", "sd1", (72, 88), 2), ("unet", "sd1", (88, 72), 1), ("unet", "sd1", 40, 2),
+    # SDXL: 1024 x 1024 at the row counts below the bench's ...
+    ("unet", "sdxl", 128, 1), ("unet", "sdxl", 128, 2), ("unet", "sdxl", 128, 3), ("unet", "sdxl", 128, 4), ("unet", "sdxl", 128, 6),
+    # ... the 832 x 1216 bucket both ways and at batch 4, other buckets, small squares ...
+    ("unet", "sdxl", (104, 152), 2), ("unet", "sdxl", (152, 104), 2), ("unet", "sdxl", (104, 152), 8),
+    ("unet", "sdxl", (112, 144), 2), ("unet", "sdxl", (168, 96), 2), ("unet", "sdxl", 96, 2), ("unet", "sdxl", 64, 2), ("unet", "sdxl", (120, 136), 4),
+    # ... a deepest level of 25 x 25 = 625 rows per image (no multiple of 64), and the bench size with a long prompt (two context windows)
+    ("unet", "sdxl", 100, 1), ("unet", "sdxl", 100, 2), ("unet", "sdxl", 128, 8, dict(n_ctx_tok=154)),
+    # the KL-VAE decoders and encoders at other sizes and batches, and TAESD both ways
+    ("vae_dec", "sd1", 96, 1), ("vae_dec", "sdxl", 128, 1), ("vae_dec", "sdxl", 96, 2), ("vae_dec", "sdxl", 100, 1),
+    ("vae_enc", "sdxl", 128, 1), ("vae_enc", "sd1", 64, 1), ("tae_dec", "sd1", 64, 1), ("tae_enc", "sd1", 64, 1),
+]
+# latents that do not halve evenly down the UNet's levels: refused when the plan is built ("concat: shape mismatch")
+REFUSED_LATENTS = [("unet", "sd1", (68, 64), 2), ("unet", "sd1", 65, 2), ("unet", "sdxl", (130, 128), 2)]
+
+
+def unheld_forms(keys_by_plan, held):
+    """{form: [plan ids]} of the census keys that are not in `held`.  keys_by_plan: {plan id: census keys of its ops}; held: the keys met in audited plans or bench
+    plans, and those COVERED_ELSEWHERE lists with the float64 case of exactly that form."""
+    out = {}
+    for pid, keys in keys_by_plan.items():
+        for k in keys:
+            if k not in held:
+                out.setdefault(k, []).append(pid)
+    return {k: out[k] for k in sorted(out, key=str)}
 
 
 def plan_id(spec):

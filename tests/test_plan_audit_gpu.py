@@ -14,6 +14,18 @@ and with seamless tiling, on a poisoned map.  What those plans read from outside
 Measured on MI355X, worst ratio to the bound over these plans: control sum 0.982 (the bound is attained where the base vanishes; gain 0: bit-equal), freeu_backbone
 0.063 (the kept half bit-equal), freeu_skip 0.210, tile / untile copies bit-equal, phase launches against their own operands 0.021, the assembled map against
 upsample + 3x3 with the loaded weight 0.131 (0.069 with seamless tiling), no pixel of another parity or of the poison left.
+
+Two censuses close the file.  The first holds every op form of the bench plans (SD1.5 64x64 N = 2, SDXL 128x128 N = 8, their KL-VAE decoders).  The second holds the
+plans of PA.SIZE_PLANS, sizes nobody tuned: SD1.5 at 64x64 with N = 1, 3, 4, 6, 8, at 64x96, 96x64, 96x96, 72x88, 88x72 and 40x40; SDXL at 128x128 with N = 1, 2, 3,
+4, 6, at 104x152 (N = 2 and 8), 152x104, 112x144, 168x96, 96x96, 64x64, 120x136, 100x100 and at the bench size with a 154-token context; the KL-VAE decoders at 96
+(sd1), 128, 96 x 2 images and 100 (sdxl), the encoders at 128 (sdxl) and 64 (sd1), TAESD both ways at 64.  Each form must be met in an audited plan or a bench plan
+or be listed in COVERED_ELSEWHERE with the float64 case of exactly that form; tests/test_size_census_cpu.py runs the same rule in the dry runtime.
+
+Measured on MI355X: the 35 size plans have 10 to 54 op forms each, 5 to 38 of them met in audited plans; 34 GEMM forms and attn<64x2> are held by the entries added
+for them.  Five of those only the device meets (the dry runtime has no device to ask for its CUs and plans the fall-back of a stream-K tile): 256x256x64ppsk with a
+row bias, 128x320x64ppsk with a residual, 128x320x64pp with (colstats, row bias), 256x256x64pp with (colstats) and (colstats, residual).  Worst ratio over the cases
+written for these forms (tests/gemm64_cases.py): C32 0.204 (s29_conv_rowbias), C16 0.999 (g16_c16; C16 == fp16_rne(C32) bit for bit everywhere), column statistics
+0.059 (g9_stats_res), LayerNorm ending 0.983 (sk0_ln, sk0_ln_res).  Every census parameter builds in under half a second.
 """
 import contextlib
 import os
@@ -249,6 +261,48 @@ COVERED_ELSEWHERE = {
     # the phase launches of the SDXL UNet's upsampling convolutions (128 x 128 latent, N = 8) run on the 128x320 ping-pong tile; the audited plans above meet the form
     # on the 256x256 tile, which is the one the KL-VAE decoders' phase launches take
     ('gemm', ('128x320x64pp', ''), ('phase',)): "test_upsample_phases_gpu.py::test_phase_launches_and_assembled_output_float64[t18_b1_w0_h4]",
+    # ---- forms that only sizes other than the bench's take (PA.SIZE_PLANS, the census at the end of this file and tests/test_size_census_cpu.py).  Small N and SD1.5
+    # with guidance off: split-K whose reduce pass ends with the LayerNorm, a row bias alone on split-K and on the skinny-M kernel
+    ('gemm', ('128x128x64s2', 'layernorm+splitk'), ('LN ending', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_ln_res]",
+    ('gemm', ('128x128x64s2', 'layernorm+splitk'), ('LN ending',)): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_ln]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_rowbias]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('C16 + C32', 'colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_c16_stats_res]",
+    ('gemm', ('128x128x64s2', 'splitk'), ('upsample',)): "test_gemm_float64_gpu.py::test_gemm_float64[sk0_ups]",
+    ('gemm', ('64x128x64s2', 'splitk'), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[sk1_stats]",
+    ('gemm', ('skinny128x64', ''), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[s29_conv_rowbias]",
+    # latents that are not square (and 100 x 100): rows that fill no ping-pong wave slab run on the general tiles of the same shape
+    ('gemm', ('128x320x64s2', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[g16_plain]",
+    ('gemm', ('128x320x64s2', ''), ('upsample',)): "test_gemm_float64_gpu.py::test_gemm_float64[g16_ups]",
+    ('gemm', ('128x320x64s2', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[g16_res]",
+    ('gemm', ('128x320x64s2', ''), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[g16_rowbias]",
+    ('gemm', ('128x320x64s2', ''), ('C16 + C32',)): "test_gemm_float64_gpu.py::test_gemm_float64[g16_c16]",
+    ('gemm', ('128x320x64s2', ''), ('C16 + C32', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g16_c16_res]",
+    ('gemm', ('256x256x64s2w16', ''), ('GEGLU',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_geglu16]",
+    ('gemm', ('256x256x64s2w16', ''), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_rowbias]",
+    ('gemm', ('256x256x64s2w16', ''), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[g9_stats_rowbias]",
+    ('gemm', ('256x256x64s2w16', ''), ('upsample',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_ups]",
+    ('gemm', ('256x256x64s2w16', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[g9_res]",
+    ('gemm', ('256x256x64s2w16', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g9_stats_res]",
+    ('gemm', ('256x256x64pp', ''), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[p17_stats_rowbias]",
+    ('gemm', ('256x256x64pp2', ''), ('colstats', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[p21_stats_ups]",
+    ('gemm', ('256x256x64pp2', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[p21_plain]",
+    # the KL-VAE decoders and encoders at other sizes, and TAESD (relu after the residual; fp16 beside fp32 on the upsampled source)
+    ('gemm', ('256x128x64s2', ''), ()): "test_gemm_float64_gpu.py::test_gemm_float64[g3_plain]",
+    ('gemm', ('256x128x64s2', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g3_stats_res]",
+    ('gemm', ('256x128x64s2', ''), ('C16 + C32', 'act_after_resid', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g3_c16_relu_post]",
+    ('gemm', ('256x128x64s2', ''), ('C16 + C32', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g3_c16_ups]",
+    ('gemm', ('256x128x32s3', ''), ('upsample',)): "test_gemm_float64_gpu.py::test_gemm_float64[g4_ups]",
+    ('gemm', ('256x128x32s3', ''), ('C16 + C32', 'upsample')): "test_gemm_float64_gpu.py::test_gemm_float64[g4_c16_ups]",
+    ('gemm', ('256x128x32s3', ''), ('act_after_resid', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[g4_relu_post16]",
+    # forms only the device census meets: where the dry runtime (no device to ask for its CUs) plans the ping-pong fall-back of a stream-K tile, the device runs
+    # stream-K, and the launches around it take other tiles
+    ('gemm', ('256x256x64ppsk', ''), ('row bias',)): "test_gemm_float64_gpu.py::test_gemm_float64[p19_conv_rowbias]",
+    ('gemm', ('128x320x64ppsk', ''), ('residual',)): "test_gemm_float64_gpu.py::test_gemm_float64[p28_conv]",
+    ('gemm', ('128x320x64pp', ''), ('colstats', 'row bias')): "test_gemm_float64_gpu.py::test_gemm_float64[p18_stats_rowbias]",
+    ('gemm', ('256x256x64pp', ''), ('colstats', 'residual')): "test_gemm_float64_gpu.py::test_gemm_float64[p17_stats_res]",
+    ('gemm', ('256x256x64pp', ''), ('colstats',)): "test_gemm_float64_gpu.py::test_gemm_float64[p17_conv_stats]",
+    # the SDXL cross attention over two context windows (154 keys: two full key tiles and a ragged one, as the case's 333 are five and one)
+    ('attn', 'attn<64x2>', ()): "test_attention_float64_gpu.py::test_attention_float64[cond_x2_lds_dma_64row]",
 }
 
 
@@ -302,3 +356,38 @@ def test_every_op_form_of_the_bench_plans_is_audited_or_covered(E):
     print(f"[plan audit] census: phase forms of the bench plans: {[(k, need[k]) for k in phase]}")
     assert phase and any("unet-sdxl" in p for k in phase for p in need[k]) and any(k[0] == "gemm" and "phase" in k[2] for k in audited)
     assert all(k in audited or COVERED_ELSEWHERE[k].startswith("test_upsample_phases_gpu.py") for k in phase)
+
+
+# ------------------------------------------------------------------ census beyond the bench sizes
+def _device_keys(E, spec, xattn=None):
+    with _built(E, spec, xattn, PA.MLB_F_OPSHAPES, False) as b:
+        return {PA.census_key(o) for o in PA.Plan(b.ctx, external=b.external).ops}
+
+
+@pytest.fixture(scope="module")
+def audited_keys(E):
+    """(census keys met in the AUDITED plans, built on the device under their xattn mode; census keys of the bench plans, whose forms the census above holds)"""
+    met, bench = set(), set()
+    for spec, xattn, _ in AUDITED:
+        met |= _device_keys(E, spec, xattn)
+    for spec in PA.BENCH_PLANS:
+        bench |= _device_keys(E, spec)
+    return met, bench
+
+
+@pytest.mark.parametrize("spec", PA.SIZE_PLANS, ids=[PA.plan_id(s) for s in PA.SIZE_PLANS])
+def test_every_op_form_at_sizes_other_than_the_bench_is_held(E, audited_keys, spec):
+    """PA.SIZE_PLANS: SD1.5 at 64x64 with N = 1, 3, 4, 6, 8, at 64x96, 96x64, 96x96, 72x88, 88x72, 40x40; SDXL at 128x128 with N = 1, 2, 3, 4, 6, at 104x152 (N = 2, 8),
+    152x104, 112x144, 168x96, 96x96, 64x64, 120x136, 100x100 and at the bench size with a 154-token context; the KL-VAE decoders and encoders and TAESD at other sizes.
+    Built on the device (the device answers for its CUs), not computed: every op form must be met in an audited plan or a bench plan, or be listed in
+    COVERED_ELSEWHERE with the float64 case of exactly that form.  A plan that cannot be built fails."""
+    met, bench = audited_keys
+    pid = PA.plan_id(spec)
+    keys = _device_keys(E, spec)
+    assert keys
+    others = sorted((k for k in keys if k not in met), key=str)
+    print(f"\n[size census] {pid}: {len(keys)} op forms, {len(keys) - len(others)} met in audited plans, the others:")
+    for k in others:
+        print(f"  {k}: {COVERED_ELSEWHERE.get(k) or ('a bench plan' if k in bench else None)}")
+    missing = PA.unheld_forms({pid: keys}, met | bench | set(COVERED_ELSEWHERE))
+    assert not missing, "op forms that no audited plan, no bench plan and no COVERED_ELSEWHERE entry holds: " + "; ".join(f"{k} in {', '.join(p)}" for k, p in missing.items())

@@ -253,29 +253,37 @@ void orc_mask_downsize(const float* mask, int w, int h, int f, float* lmask)
 	}
 }
 
-int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw, int lh,
-	const OT* cond, const OT* label, const OT* uncond, const OT* unlabel, const OrcSampleOpts* O,
-	uint64_t seed, uint32_t rng_offset, const float* init_latent, const float* lmask, float* latent_out)
-{
-	/* ---- dnsamp_init */
+int orc_sample_steps(const OrcSampleOpts* O, float* sigmas)
+{	/* dnsamp_init: a 2-evaluation solver takes half the requested steps (src/sampling.c:47-49), then the schedule */
 	int method = O->method > 0 ? O->method : 1;
 	int nfe_solver = (method == 2 || method == 5) ? 2 : 1;
 	int n_req = O->n_step < 1 ? 20 : O->n_step;
 	if (nfe_solver > 1) n_req = (n_req + nfe_solver-1) / nfe_solver;
+	return orc_schedule(n_req, O->sched ? O->sched : 1, O->f_t_ini > 0 ? O->f_t_ini : 1, O->f_t_end, sigmas);
+}
+
+int orc_sample_loop(int n_img, int64_t n_per_img, int hw, const OrcSampleOpts* O, const uint64_t* seeds, uint32_t* rng_offsets, int stop_after,
+	const float* init_latent, const float* lmask, orc_dxdt_fn f, void* user, float* latent_out, float* x_steps)
+{
+	/* ---- dnsamp_init */
+	int method = O->method > 0 ? O->method : 1;
 	float sigmas[1024];
-	int n_step = orc_schedule(n_req, O->sched ? O->sched : 1, O->f_t_ini > 0 ? O->f_t_ini : 1, O->f_t_end, sigmas);
-	OrcRng rng = { seed, rng_offset };
-	const int64_t n = (int64_t)lw*lh*U->n_ch_in;
-	DxCtx D = { P, prefix, U, cond, label, uncond, unlabel, O->cfg_scale, 0, n, lw, lh };
+	int n_step = orc_sample_steps(O, sigmas);
+	if (n_img < 1 || n_img > 64) return -1;
+	OrcRng rng[64];
+	for (int b=0;b<n_img;++b) rng[b] = (OrcRng){ seeds[b], rng_offsets[b] };
+	const int64_t n = (int64_t)n_img*n_per_img;
+	int n_call = 0, r = 0;
 	float *x = (float*)calloc(n, sizeof(float)), *x0 = (float*)calloc(n, sizeof(float)), *noise = (float*)malloc(n*sizeof(float));
 	float *dx = (float*)malloc(n*sizeof(float)), *tmp0 = (float*)calloc(n, sizeof(float)), *tmp1 = (float*)calloc(n, sizeof(float));
 	if (init_latent) memcpy(x, init_latent, (size_t)n*sizeof(float));
 	float S_t = sigmas[0];
 	unsigned S_istep = 0;
 	float dt_prev = 0, h_last = 0;
-	const int hw = lw*lh;
 	#define MASK_APPLY() do { if (lmask) for (int64_t i=0;i<n;++i) { float m = lmask[i % hw]; x[i] = x0[i]*m + x[i]*(1-m); } } while (0)
-	#define NOISE_ADD(SIG) do { orc_rng_randn(&rng, (unsigned)n, noise); for (int64_t i=0;i<n;++i) x[i] += noise[i] * (SIG); } while (0)
+	#define NOISE_ADD(SIG) do { for (int b=0;b<n_img;++b) orc_rng_randn(&rng[b], (unsigned)n_per_img, noise + b*n_per_img); \
+		for (int64_t i=0;i<n;++i) x[i] += noise[i] * (SIG); } while (0)
+	#define DXDT(T, X, DX) do { n_call++; r = f(user, s, (T), (X), (DX)); if (r < 0) goto done; } while (0)
 	for (int s=0; s<n_step; ++s) {
 		float s_up = 0, s_down = sigmas[s+1];
 		if (s == 0) {
@@ -295,24 +303,24 @@ int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw
 		switch (method) {
 		case 1: {   /* solver_euler_step :82-88 */
 			float dt = t - S_t;
-			dxdt_eval(&D, S_t, x, dx);
+			DXDT(S_t, x, dx);
 			for (int64_t i=0;i<n;++i) x[i] += dx[i] * dt;
 		} break;
 		case 2: {   /* solver_heun_step :96-117 */
 			float dt = t - S_t;
 			float *x1 = tmp0, *d1 = tmp1;
-			dxdt_eval(&D, S_t, x, dx);
+			DXDT(S_t, x, dx);
 			for (int64_t i=0;i<n;++i) x1[i] = x[i] + dx[i] * dt;
 			if (!(t > 0)) { for (int64_t i=0;i<n;++i) x[i] = x1[i]; }
 			else {
-				dxdt_eval(&D, t, x1, d1);
+				DXDT(t, x1, d1);
 				for (int64_t i=0;i<n;++i) x[i] += (dx[i] + d1[i]) * 0.5 * dt;
 			}
 		} break;
 		case 3: {   /* solver_taylor3_step :137-168 */
 			float dt = t - S_t;
 			float *dp1 = tmp0, *dp2 = tmp1;
-			dxdt_eval(&D, S_t, x, dx);
+			DXDT(S_t, x, dx);
 			for (int64_t i=0;i<n;++i) x[i] += dx[i] * dt;
 			float idtp = S_istep >= 1 ? 1 / dt_prev : 0, f2 = S_istep >= 1 ? dt*dt/2 : 0, f3 = S_istep >= 2 ? dt*dt*dt/6 : 0;
 			for (int64_t i=0;i<n;++i) {
@@ -326,7 +334,7 @@ int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw
 			float *dprev = tmp0;
 			float a = t / S_t, h = -log(a), c = h / (2*h_last);
 			if (S_istep == 0 || !(t > 0)) c = 0;
-			dxdt_eval(&D, S_t, x, dx);
+			DXDT(S_t, x, dx);
 			for (int64_t i=0;i<n;++i) {
 				float d0 = x[i] - S_t * dx[i], d1 = dprev[i], d = (1+c) * d0 - c * d1;
 				x[i] = a * x[i] + (1-a) * d;
@@ -336,24 +344,46 @@ int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw
 		} break;
 		case 5: {   /* solver_dpmpp2s_step :264-289 */
 			float *x1 = tmp0, *dx1 = tmp1;
-			dxdt_eval(&D, S_t, x, dx);
+			DXDT(S_t, x, dx);
 			if (!(t > 0)) { float dt = t - S_t; for (int64_t i=0;i<n;++i) x[i] += dx[i] * dt; }
 			else {
 				float t1 = sqrt(t * S_t), dt1 = t1 - S_t, a = t / S_t;
 				for (int64_t i=0;i<n;++i) x1[i] = x[i] + dx[i] * dt1;
-				dxdt_eval(&D, t1, x1, dx1);
+				DXDT(t1, x1, dx1);
 				for (int64_t i=0;i<n;++i) { float d = x1[i] - t1 * dx1[i]; x[i] = a * x[i] + (1-a) * d; }
 			}
 		} break;
-		default: free(x); free(x0); free(noise); free(dx); free(tmp0); free(tmp1); return -1;
+		default: r = -1; goto done;
 		}
 		S_t = t; S_istep++;
 		if (s_up > 0 && s+1 != n_step) { NOISE_ADD(s_up); S_t = sigmas[s+1]; }
 		MASK_APPLY();
+		if (x_steps) memcpy(x_steps + (size_t)s*n, x, (size_t)n*sizeof(float));
+		if (stop_after > 0 && s+1 >= stop_after) break;
 	}
 	#undef MASK_APPLY
 	#undef NOISE_ADD
+	#undef DXDT
 	memcpy(latent_out, x, (size_t)n*sizeof(float));
+	for (int b=0;b<n_img;++b) rng_offsets[b] = rng[b].offset;
+done:
 	free(x); free(x0); free(noise); free(dx); free(tmp0); free(tmp1);
-	return D.nfe;
+	return r < 0 ? r : n_call;
+}
+
+static int dxdt_eval_cb(void* user, int i_step, float t, const float* x, float* dx)
+{
+	(void)i_step;
+	dxdt_eval((DxCtx*)user, t, x, dx);
+	return 0;
+}
+
+int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw, int lh,
+	const OT* cond, const OT* label, const OT* uncond, const OT* unlabel, const OrcSampleOpts* O,
+	uint64_t seed, uint32_t rng_offset, const float* init_latent, const float* lmask, float* latent_out)
+{
+	const int64_t n = (int64_t)lw*lh*U->n_ch_in;
+	DxCtx D = { P, prefix, U, cond, label, uncond, unlabel, O->cfg_scale, 0, n, lw, lh };
+	const int r = orc_sample_loop(1, n, lw*lh, O, &seed, &rng_offset, 0, init_latent, lmask, dxdt_eval_cb, &D, latent_out, NULL);
+	return r < 0 ? r : D.nfe;
 }

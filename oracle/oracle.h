@@ -198,6 +198,15 @@ typedef struct { int method, sched, n_step; float cfg_scale, s_ancestral, s_nois
 ORACLE_API int orc_sample_ex(OParams* P, const char* prefix, const OrcUnetParams* U, int lw, int lh,
 	const OT* cond, const OT* label, const OT* uncond, const OT* unlabel, const OrcSampleOpts* O,
 	uint64_t seed, uint32_t rng_offset, const float* init_latent, const float* lmask, float* latent_out);
+/* The loop of orc_sample_ex with the model as a callback: dx = dxdt(x, t) for the n_img images at once, x and dx [n_img][n_per_img]; a negative return aborts
+ * (the loop returns it and writes nothing).  Every update is elementwise with the same scalars for all images; each draw takes n_per_img values per image from
+ * that image's own Philox state (seeds[b], rng_offsets[b]: in the start, out the state after the last draw); the mask is indexed i % hw.  cfg_scale of the
+ * options is not read.  stop_after > 0 ends the loop after that many completed steps.  x_steps, where given, receives the latent after each completed step,
+ * [n_step][n_img][n_per_img].  Returns the number of callback calls.  orc_sample_steps: the step count of the options (sigmas: n_step + 1 values, <= 1024). */
+typedef int (*orc_dxdt_fn)(void* user, int i_step, float t, const float* x, float* dx);
+ORACLE_API int orc_sample_steps(const OrcSampleOpts* O, float* sigmas);
+ORACLE_API int orc_sample_loop(int n_img, int64_t n_per_img, int hw, const OrcSampleOpts* O, const uint64_t* seeds, uint32_t* rng_offsets, int stop_after,
+	const float* init_latent, const float* lmask, orc_dxdt_fn f, void* user, float* latent_out, float* x_steps);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,8 @@ class Rng(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint32)]
 
 
+DXDT_FN = ctypes.CFUNCTYPE(c_int, c_vp, c_int, c_f, FP, FP)      # orc_dxdt_fn(user, i_step, t, x, dx)
+
 _L = None
 
 
@@ -163,6 +165,9 @@ def L():
         l.orc_mask_downsize.argtypes = [FP, c_int, c_int, c_int, FP]
         l.orc_sample_ex.argtypes = [c_vp, ctypes.c_char_p, ctypes.POINTER(UnetParams), c_int, c_int, OTP, OTP, OTP, OTP,
                                     ctypes.POINTER(SampleOpts), ctypes.c_uint64, ctypes.c_uint32, FP, FP, FP]
+        l.orc_sample_steps.argtypes = [ctypes.POINTER(SampleOpts), FP]
+        l.orc_sample_loop.argtypes = [c_int, c_i64, c_int, ctypes.POINTER(SampleOpts), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), c_int,
+                                      FP, FP, DXDT_FN, c_vp, FP, FP]
         _L = l
     return _L
 
@@ -253,6 +258,51 @@ def randn(seed, offset, n):
     out = np.empty(n, np.float32)
     L().orc_rng_randn(ctypes.byref(r), n, fptr(out))
     return out
+
+
+def sample_steps(opts):
+    """(n_step, sigmas[n_step + 1]) of the options, as orc_sample_loop / orc_sample_ex run them"""
+    sig = np.zeros(1024, np.float32)
+    n = L().orc_sample_steps(ctypes.byref(opts), fptr(sig))
+    return n, sig[:n + 1].copy()
+
+
+def sample_loop(opts, shape, hw, seeds, offsets, dxdt, init=None, lmask=None, stop_after=0, want_steps=False):
+    """orc_sample_loop on images of `shape` = (n_img, ...) with the model as the Python function dxdt(i_step, t, x) -> dx (arrays of `shape`; None aborts).
+    Returns (latent, offsets after the last draw, callback calls, per-step latents [n_step][*shape] or None); after an abort (None, None, the negative value, None).
+    An exception raised by dxdt ends the loop and is raised again here."""
+    n_img = shape[0]
+    n_per = int(np.prod(shape[1:]))
+    n_step = sample_steps(opts)[0]
+    out = np.empty(shape, np.float32)
+    steps = np.zeros((n_step,) + tuple(shape), np.float32) if want_steps else None
+    sd = (ctypes.c_uint64 * n_img)(*[int(s) for s in seeds])
+    off = (ctypes.c_uint32 * n_img)(*[int(o) for o in offsets])
+    raised = []
+
+    def cb(user, i_step, t, x, dx):
+        try:
+            d = dxdt(i_step, t, np.ctypeslib.as_array(x, shape=(n_img * n_per,)).reshape(shape).copy())
+            if d is None:
+                return -1
+            d = np.ascontiguousarray(d, np.float32)
+            assert d.shape == tuple(shape), d.shape
+            ctypes.memmove(dx, d.ctypes.data, d.nbytes)
+            return 0
+        except BaseException as e:          # (an exception must not cross the C frames)
+            raised.append(e)
+            return -2
+    init = np.ascontiguousarray(init, np.float32) if init is not None else None
+    lmask = np.ascontiguousarray(lmask, np.float32) if lmask is not None else None
+    assert init is None or init.size == n_img * n_per
+    assert lmask is None or lmask.size == hw
+    r = L().orc_sample_loop(n_img, n_per, hw, ctypes.byref(opts), sd, off, int(stop_after), fptr(init) if init is not None else None,
+                            fptr(lmask) if lmask is not None else None, DXDT_FN(cb), None, fptr(out), fptr(steps) if want_steps else None)
+    if raised:
+        raise raised[0]
+    if r < 0:
+        return None, None, r, None
+    return out, [int(o) for o in off], r, steps
 
 
 def ref_randn(seed, offset, n):

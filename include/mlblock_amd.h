@@ -146,6 +146,7 @@ void* mlctx_input_device_ptr(MLTensor* t);
  * dev_scale[n % n_src] (or scale0), instead of the staging buffer.  Must precede the first consumer.
  * (c_in scaling + cond/uncond duplication of src/unet.c:470-472, src/mlimgsynth.c:1578-1582; mode 1 = TAE clamp) */
 int mlctx_input_bind(MLTensor* t, const float* dev_src, int n_src, const float* dev_scale, float scale0, int mode);
+int mlctx_input_rebind(MLCtx* C, MLTensor* t, const float* dev_src);      /* a bound image input reads another source of the same layout from the next launch on (not for captured plans) */
 /* portable fp16 conversion used by the parameter loader (RNE, as ggml_fp32_to_fp16_row) */
 uint16_t mlb_f32_to_f16_bits(float f);
 float mlb_f16_bits_to_f32(uint16_t h);

@@ -524,10 +524,22 @@ int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float* sigma_
 int mlis_amd_last_rows(MLIS_AmdCtx* S, float* out, size_t nbytes);      /* the raw outputs the last mix read, host [N][4][hw] (tests, tools) */
 int mlis_amd_prediction_resolve(const char* model, int ckpt_v_pred, int ckpt_ztsnr, int opt_prediction, int opt_zsnr, int* vparam, int* zsnr);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
- * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all) */
+ * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all).
+ * set_vae_tile with another size drops the tile plans AND the tile-sized buffers; the next prepare makes them for the new tile.
+ * The tile plans take one image; a batch walks them image by image (tile buffers hold every image's tile), so an image's result does not depend on the batch size.
+ * A deliberate extension of the reference: a dimension that one tile covers while the other is tiled (512 x 768 at vae_tile 512: the latent is 64 wide, a tile
+ * 80) is one tile pasted whole.  The reference pastes only the tile less its margin there and leaves the last 64 pixel columns of the image (8 of the moments)
+ * unwritten, divides by zero at exactly 128 pixels and runs no tile below; every pixel it does write has the same bits here.  Tiles the reference evaluates twice
+ * (its count ceil(full / step) repeats the last, clamped origin) run once: same values on the same pixels.
+ * vae_tile_walk: the walk of one dimension that decode and encode share (lengths in units of `unit` image pixels: f over the latent, 1 over the image; margin 8
+ * resp. 8 f); tile t reads [origin, origin + n) and pastes [src_off, src_off + width) of its result at origin + src_off.  Returns the number of tiles.
+ * vae_tile_info: tile size, allocated bytes of the tile's input / output buffer, tiles per pass and plan evaluations of the last tiled pass of the decode (which 0)
+ * or encode (which 1) tile plan; returns 1 with a plan, 0 without. */
 int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px);
 MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S);
 MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S);                            /* build the encoder plan now (weights: synth or caller-loaded) */
+int mlis_amd_vae_tile_walk(int full, int tile_px, int unit, int margin, int* n_out, int* origin, int* src_off, int* width, int max_tiles);
+int mlis_amd_vae_tile_info(MLIS_AmdCtx* S, int which, int* tile_w, int* tile_h, size_t* in_bytes, size_t* out_bytes, int* n_tiles, int* n_evals);
 int mlis_amd_last_n_step(MLIS_AmdCtx* S);
 /* passes (denoising loop, decode, encode) that were run AGAIN on the hand-off-free plan after an in-launch hand-off (stream-K slab, LayerNorm statistics) timed out --
  * the GPU was shared or the stream CU-masked.  The call that hit it still succeeds; results then come from plain tiles / separate LayerNorm launches. */

@@ -74,6 +74,8 @@ struct MLIS_AmdCtx {
 	MLCtx *dect_ctx, *enct_ctx;
 	MLTensor *t_lat_dect, *t_img_enct;
 	float *d_lat_tile, *d_img_tile, *d_imgin_tile, *d_mom_tile, *d_mom;
+	size_t tile_bytes[4];                             /* allocated bytes of d_lat_tile, d_img_tile, d_imgin_tile, d_mom_tile: they follow the tile size */
+	int n_tile_evals[2];                              /* tile plan evaluations of the last tiled decode / encode */
 	/* tiled diffusion (mlis_amd_create_tiled_packed): the UNet plan has the size of one window (times `pack` in the batch), lw x lh above is the canvas */
 	int n_win;                  /* windows per evaluation; 0: the plan takes the whole latent */
 	int win_w, win_h, win_ox, win_oy;       /* window extent and overlap per axis, latent pixels */
@@ -1174,7 +1176,15 @@ MLB_API int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float
  * sdvae_decode / sdvae_encode with tile_px > 0 (src/vae.c:333-391, 245-300): the latent (image) is cut into overlapping
  * tiles of tile_px (+ a margin of k = 8 latent pixels / 64 image pixels on every side), each tile runs through a tile-sized
  * plan, and the interior of its result is pasted into the output in the reference's order (later tiles overwrite the
- * margins of earlier ones).  TAE codecs are never tiled (the reference only tiles sdvae_*). */
+ * margins of earlier ones).  TAE codecs are never tiled (the reference only tiles sdvae_*).
+ *
+ * A deliberate extension of the reference: where one tile covers a dimension (n == full) while the other dimension is tiled,
+ * the reference's loop (vae.c:262-291, 353-385) gives every tile of that dimension the origin 0 and pastes only n - k of it, so
+ * the last margin of the output is never written (there: whatever realloc returned); at exactly 2k it divides by zero and below
+ * 2k it runs no tile at all.  Here such a dimension is ONE tile at origin 0 pasted whole: the same tile at the same origin as the
+ * reference's, so every pixel the reference writes has the same bits, and the pixels it leaves undefined are defined.  Where a
+ * dimension is tiled (n < full) the rule is the reference's, without the tiles it repeats: ceil(full / step) counts tiles whose
+ * origins all clamp to full - n; they paste the same values onto the same pixels again, so dropping them changes no bit. */
 MLB_API int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px)
 {
 	if (tile_px < 0) tile_px = 0;
@@ -1182,6 +1192,11 @@ MLB_API int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px)
 		mlsd_stream_sync(S->stream);
 		if (S->dect_ctx) { mlctx_destroy(S->dect_ctx); S->dect_ctx = NULL; }
 		if (S->enct_ctx) { mlctx_destroy(S->enct_ctx); S->enct_ctx = NULL; }
+		/* the tile buffers have the size of one tile: the next *_tile_prepare allocates them for the new one */
+		mlsd_free(S->d_lat_tile); mlsd_free(S->d_img_tile); mlsd_free(S->d_imgin_tile); mlsd_free(S->d_mom_tile);
+		S->d_lat_tile = S->d_img_tile = S->d_imgin_tile = S->d_mom_tile = NULL;
+		memset(S->tile_bytes, 0, sizeof(S->tile_bytes));
+		S->tl_w = S->tl_h = S->ti_w = S->ti_h = 0;
 		S->vae_tile = tile_px;
 	}
 	return 1;
@@ -1194,7 +1209,63 @@ static int tile_dims(int tile_px, int margin2, int full, int unit)
 	return n < full ? n : full;
 }
 
-/* builds (once) the decode tile plan; returns NULL with no error when tiling does not apply */
+/* The tile walk of ONE dimension, for decode and encode alike.  Lengths are in units of `unit` image pixels (decode: f, the walk
+ * is over latent pixels; encode: 1): `full` the dimension, `margin` the overlap k (decode 8, encode 8 f), tile_px the option.
+ * *n_out = the tile length min(round_up(tile_px, 64) / unit + 2k, full).  Tile t reads [origin[t], origin[t] + n) of the input and
+ * pastes [src_off[t], src_off[t] + width[t]) of its result at origin[t] + src_off[t] of the output:
+ *   n < full   tile 0 pastes [0, n - k); tile t > 0 at i0 = min(t step, full - n), step = n - 2k, pastes [i0 + k, i0 + n); the
+ *              walk ends with the first tile at full - n (vae.c:269-289, 365-384 without the repeats of that last origin)
+ *   n == full  one tile at 0 pasted whole (see above)
+ * Returns the number of tiles (at most max_tiles of them are written; the arrays may be NULL with max_tiles 0), < 0 for arguments
+ * no walk exists for. */
+MLB_API int mlis_amd_vae_tile_walk(int full, int tile_px, int unit, int margin, int* n_out, int* origin, int* src_off, int* width, int max_tiles)
+{
+	if (full < 1 || tile_px < 1 || tile_px > 65535 || unit < 1 || margin < 0 || margin > 65535) return -1;
+	const int k = margin, n = tile_dims(tile_px, 2*k, full, unit);
+	if (n_out) *n_out = n;
+	if (n == full) {
+		if (max_tiles > 0) { origin[0] = 0; src_off[0] = 0; width[0] = full; }
+		return 1;
+	}
+	const int step = n - 2*k, last = full - n;
+	if (step < 1) return -1;                    /* unit > round_up(tile_px, 64) */
+	int cnt = 0;
+	for (int i0 = 0; ; i0 = i0 + step < last ? i0 + step : last) {
+		if (cnt < max_tiles) { origin[cnt] = i0; src_off[cnt] = i0 ? k : 0; width[cnt] = n - k; }
+		++cnt;
+		if (i0 == last) break;
+	}
+	return cnt;
+}
+
+typedef struct { int n, cnt, *org, *off, *wid; } TileWalk;
+
+static int tile_walk_new(TileWalk* w, int full, int tile_px, int unit, int margin)
+{
+	w->org = NULL;
+	w->cnt = mlis_amd_vae_tile_walk(full, tile_px, unit, margin, &w->n, NULL, NULL, NULL, 0);
+	if (w->cnt < 1) return mlsd_set_error(-1, "VAE tiling: no tile walk for length %d, tile %d", full, tile_px);
+	w->org = (int*)malloc((size_t)3 * w->cnt * sizeof(int));
+	if (!w->org) return mlsd_set_error(-1, "out of host memory");
+	w->off = w->org + w->cnt; w->wid = w->off + w->cnt;
+	mlis_amd_vae_tile_walk(full, tile_px, unit, margin, &w->n, w->org, w->off, w->wid, w->cnt);
+	return 0;
+}
+
+/* (re)allocates one tile buffer when the tile needs more than it holds */
+static int tile_buf(MLIS_AmdCtx* S, float** p, int which, size_t nbytes)
+{
+	if (*p && S->tile_bytes[which] >= nbytes) return 0;
+	mlsd_free(*p); *p = NULL; S->tile_bytes[which] = 0;
+	if (mlsd_malloc((void**)p, nbytes)) return -1;
+	S->tile_bytes[which] = nbytes;
+	return 0;
+}
+
+/* builds (once) the decode tile plan; returns NULL with no error when tiling does not apply.
+ * The tile plans take ONE image: a batch walks them image by image (the tile buffers hold the tile of every image, the plan's input moves from one to the next).
+ * A tile of image b is then computed by the same launches whatever the batch size -- GEMM tiles and K splits are chosen by M = images x pixels, so a plan of
+ * B images would round differently from the plan of one -- and the plan's activations, what tiling is there to bound, do not grow with the batch. */
 MLB_API MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S)
 {
 	if (S->dect_ctx) return S->dect_ctx;
@@ -1203,11 +1274,11 @@ MLB_API MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S)
 	const int n0 = tile_dims(S->vae_tile, 2*k, S->lw, f), n1 = tile_dims(S->vae_tile, 2*k, S->lh, f);
 	if (n0 == S->lw && n1 == S->lh) return NULL;                                      /* one tile: disabled (vae.c:347-348) */
 	const int B = S->B;
-	if (!S->d_lat_tile && mlsd_malloc((void**)&S->d_lat_tile, (size_t)B*4*n0*n1*4)) return NULL;
-	if (!S->d_img_tile && mlsd_malloc((void**)&S->d_img_tile, (size_t)B*3*n0*f*n1*f*4)) return NULL;
+	if (tile_buf(S, &S->d_lat_tile, 0, (size_t)B*4*n0*n1*4)) return NULL;
+	if (tile_buf(S, &S->d_img_tile, 1, (size_t)B*3*n0*f*n1*f*4)) return NULL;
 	MLCtx *C = mlctx_new(S->stream);
-	int ok = sdvae_decode_init(C, &S->vae_p, n0, n1, B, &S->t_lat_dect) >= 0 &&
-	         mlctx_input_bind(S->t_lat_dect, S->d_lat_tile, B, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
+	int ok = sdvae_decode_init(C, &S->vae_p, n0, n1, 1, &S->t_lat_dect) >= 0 &&
+	         mlctx_input_bind(S->t_lat_dect, S->d_lat_tile, 1, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
 	         sdvae_decode_build(C, &S->vae_p, S->t_lat_dect) >= 0;
 	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
 	if (!ok) { mlctx_destroy(C); return NULL; }
@@ -1224,12 +1295,12 @@ MLB_API MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S)
 	if (n0 == W && n1 == H) return NULL;
 	const int B = S->B;
 	if (!S->d_img_in && mlsd_malloc((void**)&S->d_img_in, (size_t)B*3*W*H*4)) return NULL;
-	if (!S->d_imgin_tile && mlsd_malloc((void**)&S->d_imgin_tile, (size_t)B*3*n0*n1*4)) return NULL;
-	if (!S->d_mom_tile && mlsd_malloc((void**)&S->d_mom_tile, (size_t)B*8*(n0/f)*(n1/f)*4)) return NULL;
+	if (tile_buf(S, &S->d_imgin_tile, 2, (size_t)B*3*n0*n1*4)) return NULL;
+	if (tile_buf(S, &S->d_mom_tile, 3, (size_t)B*8*(n0/f)*(n1/f)*4)) return NULL;
 	if (!S->d_mom && mlsd_malloc((void**)&S->d_mom, (size_t)B*8*S->hw*4)) return NULL;
 	MLCtx *C = mlctx_new(S->stream);
-	int ok = sdvae_encode_init(C, &S->vae_p, n0, n1, B, &S->t_img_enct) >= 0 &&
-	         mlctx_input_bind(S->t_img_enct, S->d_imgin_tile, B, NULL, 1.0f, 2) >= 0 &&
+	int ok = sdvae_encode_init(C, &S->vae_p, n0, n1, 1, &S->t_img_enct) >= 0 &&
+	         mlctx_input_bind(S->t_img_enct, S->d_imgin_tile, 1, NULL, 1.0f, 2) >= 0 &&
 	         sdvae_encode_build(C, &S->vae_p, S->t_img_enct) >= 0;
 	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
 	if (!ok) { mlctx_destroy(C); return NULL; }
@@ -1238,29 +1309,38 @@ MLB_API MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S)
 }
 
 static int decode_tiled(MLIS_AmdCtx* S)
-{	/* src/vae.c:351-383 */
+{	/* src/vae.c:351-383, walked by mlis_amd_vae_tile_walk */
 	const int f = S->vae_p.f_down, k = 8, B = S->B;
 	const int lat_n0 = S->lw, lat_n1 = S->lh, n0 = S->tl_w, n1 = S->tl_h;
 	const int img_n0 = lat_n0*f, img_n1 = lat_n1*f;
-	const int step0 = n0 - 2*k, step1 = n1 - 2*k;
-	const int n_tile0 = (lat_n0 + step0 - 1) / step0, n_tile1 = (lat_n1 + step1 - 1) / step1;
 	void *st = S->stream;
 	MLTensor *r = mlctx_result(S->dect_ctx);
 	int64_t ld = 0;
 	const float *y = mlctx_tensor_device_f32(S->dect_ctx, r, &ld);
-	for (int t1=0; t1<n_tile1; ++t1) {
-		const int i1 = t1*step1 < lat_n1 - n1 ? t1*step1 : lat_n1 - n1;
-		for (int t0=0; t0<n_tile0; ++t0) {
-			const int i0 = t0*step0 < lat_n0 - n0 ? t0*step0 : lat_n0 - n0;
-			if (mlsd_copy_slice2(S->d_lat_tile, n0, n1, S->d_x, lat_n0, lat_n1, n0, n1, 0, 0, i0, i1, B*4, st)) return -1;
-			if (mlctx_compute(S->dect_ctx) < 0) return -1;
-			if (mlsd_nhwc_to_nchw_f32(y, ld, B, 3, n0*f*n1*f, S->d_img_tile, 0.5f, 0.5f, st)) return -1;   /* (x+1)/2: elementwise, commutes with the paste */
-			const int d0 = i0 ? k : 0, d1 = i1 ? k : 0;
-			if (mlsd_copy_slice2(S->d_img, img_n0, img_n1, S->d_img_tile, n0*f, n1*f, (n0-k)*f, (n1-k)*f, (i0+d0)*f, (i1+d1)*f,
-					d0*f, d1*f, B*3, st)) return -1;
+	TileWalk w0, w1 = {0};
+	int R = -1;
+	S->n_tile_evals[0] = 0;
+	if (tile_walk_new(&w0, lat_n0, S->vae_tile, f, k) || tile_walk_new(&w1, lat_n1, S->vae_tile, f, k)) goto end;
+	if (w0.n != n0 || w1.n != n1) { mlsd_set_error(-1, "VAE tiling: the decode tile plan is %dx%d, the walk's tile %dx%d", n0, n1, w0.n, w1.n); goto end; }
+	for (int t1=0; t1<w1.cnt; ++t1) {
+		const int i1 = w1.org[t1], d1 = w1.off[t1];
+		for (int t0=0; t0<w0.cnt; ++t0) {
+			const int i0 = w0.org[t0], d0 = w0.off[t0];
+			if (mlsd_copy_slice2(S->d_lat_tile, n0, n1, S->d_x, lat_n0, lat_n1, n0, n1, 0, 0, i0, i1, B*4, st)) goto end;
+			for (int b=0; b<B; ++b) {
+				if (mlctx_input_rebind(S->dect_ctx, S->t_lat_dect, S->d_lat_tile + (size_t)b*4*n0*n1) < 0) goto end;
+				if (mlctx_compute(S->dect_ctx) < 0) goto end;
+				S->n_tile_evals[0]++;
+				if (mlsd_nhwc_to_nchw_f32(y, ld, 1, 3, n0*f*n1*f, S->d_img_tile + (size_t)b*3*n0*f*n1*f, 0.5f, 0.5f, st)) goto end;   /* (x+1)/2: elementwise, commutes with the paste */
+			}
+			if (mlsd_copy_slice2(S->d_img, img_n0, img_n1, S->d_img_tile, n0*f, n1*f, w0.wid[t0]*f, w1.wid[t1]*f, (i0+d0)*f, (i1+d1)*f,
+					d0*f, d1*f, B*3, st)) goto end;
 		}
 	}
-	return 1;
+	R = 1;
+end:
+	free(w0.org); free(w1.org);
+	return R;
 }
 
 static int encode_tiled(MLIS_AmdCtx* S)
@@ -1268,26 +1348,57 @@ static int encode_tiled(MLIS_AmdCtx* S)
 	const int f = S->vae_p.f_down, k = f*8, B = S->B;
 	const int img_n0 = S->c.width, img_n1 = S->c.height, n0 = S->ti_w, n1 = S->ti_h;
 	const int lat_n0 = img_n0/f, lat_n1 = img_n1/f;
-	const int step0 = n0 - 2*k, step1 = n1 - 2*k;
-	const int n_tile0 = (img_n0 + step0 - 1) / step0, n_tile1 = (img_n1 + step1 - 1) / step1;
 	void *st = S->stream;
 	MLTensor *r = mlctx_result(S->enct_ctx);
 	int64_t ld = 0;
 	const float *y = mlctx_tensor_device_f32(S->enct_ctx, r, &ld);
-	for (int t1=0; t1<n_tile1; ++t1) {
-		const int i1 = t1*step1 < img_n1 - n1 ? t1*step1 : img_n1 - n1;
-		for (int t0=0; t0<n_tile0; ++t0) {
-			const int i0 = t0*step0 < img_n0 - n0 ? t0*step0 : img_n0 - n0;
-			if (mlsd_copy_slice2(S->d_imgin_tile, n0, n1, S->d_img_in, img_n0, img_n1, n0, n1, 0, 0, i0, i1, B*3, st)) return -1;
-			if (mlctx_compute(S->enct_ctx) < 0) return -1;
-			if (mlsd_count_nonfinite(y, (size_t)B*(n0/f)*(n1/f)*ld, S->d_nan, st)) return -1;
-			if (mlsd_nhwc_to_nchw_f32(y, ld, B, 8, (n0/f)*(n1/f), S->d_mom_tile, 1.0f, 0.0f, st)) return -1;
-			const int d0 = i0 ? k : 0, d1 = i1 ? k : 0;
-			if (mlsd_copy_slice2(S->d_mom, lat_n0, lat_n1, S->d_mom_tile, n0/f, n1/f, (n0-k)/f, (n1-k)/f, (i0+d0)/f, (i1+d1)/f,
-					d0/f, d1/f, B*8, st)) return -1;
+	TileWalk w0, w1 = {0};
+	int R = -1;
+	S->n_tile_evals[1] = 0;
+	if (tile_walk_new(&w0, img_n0, S->vae_tile, 1, k) || tile_walk_new(&w1, img_n1, S->vae_tile, 1, k)) goto end;
+	if (w0.n != n0 || w1.n != n1) { mlsd_set_error(-1, "VAE tiling: the encode tile plan is %dx%d, the walk's tile %dx%d", n0, n1, w0.n, w1.n); goto end; }
+	for (int t1=0; t1<w1.cnt; ++t1) {
+		const int i1 = w1.org[t1], d1 = w1.off[t1];
+		for (int t0=0; t0<w0.cnt; ++t0) {
+			const int i0 = w0.org[t0], d0 = w0.off[t0];
+			if (mlsd_copy_slice2(S->d_imgin_tile, n0, n1, S->d_img_in, img_n0, img_n1, n0, n1, 0, 0, i0, i1, B*3, st)) goto end;
+			for (int b=0; b<B; ++b) {
+				if (mlctx_input_rebind(S->enct_ctx, S->t_img_enct, S->d_imgin_tile + (size_t)b*3*n0*n1) < 0) goto end;
+				if (mlctx_compute(S->enct_ctx) < 0) goto end;
+				S->n_tile_evals[1]++;
+				if (mlsd_count_nonfinite(y, (size_t)(n0/f)*(n1/f)*ld, S->d_nan, st)) goto end;
+				if (mlsd_nhwc_to_nchw_f32(y, ld, 1, 8, (n0/f)*(n1/f), S->d_mom_tile + (size_t)b*8*(n0/f)*(n1/f), 1.0f, 0.0f, st)) goto end;
+			}
+			if (mlsd_copy_slice2(S->d_mom, lat_n0, lat_n1, S->d_mom_tile, n0/f, n1/f, w0.wid[t0]/f, w1.wid[t1]/f, (i0+d0)/f, (i1+d1)/f,
+					d0/f, d1/f, B*8, st)) goto end;
 		}
 	}
-	return 1;
+	R = 1;
+end:
+	free(w0.org); free(w1.org);
+	return R;
+}
+
+/* the tile plan of the decoder (which 0) or the encoder (which 1) as it stands: the tile size (latent / image pixels; 0 x 0 without a plan), the bytes allocated for
+ * the tile's input and output buffers (the tile of every image of the batch), the tiles one pass walks and the plan evaluations of the last tiled pass (tiles x images).  Returns 1 with a plan, 0 without. */
+MLB_API int mlis_amd_vae_tile_info(MLIS_AmdCtx* S, int which, int* tile_w, int* tile_h, size_t* in_bytes, size_t* out_bytes, int* n_tiles, int* n_evals)
+{
+	if (!S || which < 0 || which > 1) return -1;
+	MLCtx *C = which ? S->enct_ctx : S->dect_ctx;
+	const int f = S->vae_p.f_down;
+	int n = 0;
+	if (C) {
+		const int c0 = mlis_amd_vae_tile_walk(which ? S->c.width : S->lw, S->vae_tile, which ? 1 : f, which ? 8*f : 8, NULL, NULL, NULL, NULL, 0);
+		const int c1 = mlis_amd_vae_tile_walk(which ? S->c.height : S->lh, S->vae_tile, which ? 1 : f, which ? 8*f : 8, NULL, NULL, NULL, NULL, 0);
+		n = c0 > 0 && c1 > 0 ? c0 * c1 : -1;
+	}
+	if (tile_w) *tile_w = C ? (which ? S->ti_w : S->tl_w) : 0;
+	if (tile_h) *tile_h = C ? (which ? S->ti_h : S->tl_h) : 0;
+	if (in_bytes) *in_bytes = S->tile_bytes[which ? 2 : 0];
+	if (out_bytes) *out_bytes = S->tile_bytes[which ? 3 : 1];
+	if (n_tiles) *n_tiles = n;
+	if (n_evals) *n_evals = S->n_tile_evals[which];
+	return C ? 1 : 0;
 }
 
 /* after the launches of a decode / encode were enqueued: if the plan hands data over inside launches, drain and check; 1 = clean, 0 = gave up -> the plan is now

@@ -553,6 +553,23 @@ MLB_API int mlctx_input_bind(MLTensor* t, const float* dev_src, int n_src, const
 	return 1;
 }
 
+/* moves a bound image input to another device source of the same layout (the next image of a batch that a one-image plan walks): the gather that reads it takes
+ * the new pointer from its next launch on.  Not for captured plans, whose launches hold the old one. */
+MLB_API int mlctx_input_rebind(MLCtx* C, MLTensor* t, const float* dev_src)
+{
+	if (!C || !t || !t->is_input || !t->in_src || !dev_src) return mlctx_fail(C, "mlctx_input_rebind: not a bound input");
+	if (C->graph_exec) return mlctx_fail(C, "mlctx_input_rebind(%s): the plan is captured", t->name);
+	int n = 0;
+	for (int i=0;i<C->n_ops;++i) {
+		MLOp *op = &C->ops[i];
+		if (op->kind == OP_NCHW2NHWC && op->u.n2h.src == t->in_src) { op->u.n2h.src = dev_src; ++n; }
+	}
+	if (!n) return mlctx_fail(C, "mlctx_input_rebind(%s): no gather reads it", t->name);
+	t->in_src = dev_src;
+	if (t->dirty) *t->dirty = 0;
+	return 1;
+}
+
 MLB_API void* mlctx_input_device_ptr(MLTensor* t)
 {	/* whoever asks for the staging buffer is about to write it: step-invariant ops fed by it run again */
 	if (t && t->dirty) *t->dirty = 0;

@@ -461,6 +461,11 @@ def _proto2():
     l.mlis_amd_last_n_step.argtypes = [vp]
     l.mlis_amd_sync.argtypes = [vp]
     l.mlis_amd_set_vae_tile.argtypes = [vp, c_int]
+    for f in (l.mlis_amd_decoder_tile_prepare, l.mlis_amd_encoder_tile_prepare):
+        f.restype, f.argtypes = vp, [vp]
+    l.mlis_amd_vae_tile_walk.argtypes = [c_int] * 4 + [ctypes.POINTER(c_int)] * 4 + [c_int]
+    l.mlis_amd_vae_tile_info.argtypes = [vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                         ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     l.mlis_amd_seed.argtypes = [vp, ctypes.POINTER(c_u64)]
     l.mlis_amd_set_init_latent.argtypes = [vp, FP]
     l.mlis_amd_set_lmask.argtypes = [vp, FP]
@@ -523,6 +528,16 @@ def guidance_info(engine, n_batch):
     if r < 0:
         check1(r, "mlis_amd_guidance_info")
     return dict(vparam=v.value, zsnr=z.value, sigma_min=smin.value, sigma_max=smax.value, cfg_rescale=phi.value, n_evals=n.value, factors=fac[:r].copy())
+
+
+def vae_tile_walk(full, tile_px, unit, margin):
+    """mlis_amd_vae_tile_walk: the tile walk of one dimension -> (tile length, origins, source offsets, paste widths); lengths in units of `unit` pixels"""
+    l = _proto2()
+    n = c_int()
+    cnt = check1(l.mlis_amd_vae_tile_walk(int(full), int(tile_px), int(unit), int(margin), ctypes.byref(n), None, None, None, 0), "mlis_amd_vae_tile_walk")
+    a = [(c_int * cnt)() for _ in range(3)]
+    check1(l.mlis_amd_vae_tile_walk(int(full), int(tile_px), int(unit), int(margin), ctypes.byref(n), a[0], a[1], a[2], cnt), "mlis_amd_vae_tile_walk")
+    return (n.value,) + tuple(list(x) for x in a)
 
 
 class Decoder:
@@ -766,6 +781,23 @@ class Generator:
 
     def set_vae_tile(self, tile_px):
         check1(_proto2().mlis_amd_set_vae_tile(self.h, int(tile_px)), "mlis_amd_set_vae_tile")
+
+    def vae_tile_prepare(self, encoder=False):
+        """mlis_amd_decoder_tile_prepare / mlis_amd_encoder_tile_prepare: builds the tile plan; False when tiling does not apply (one tile covers all, TAE, off)"""
+        l = _proto2()
+        return bool((l.mlis_amd_encoder_tile_prepare if encoder else l.mlis_amd_decoder_tile_prepare)(self.h))
+
+    def vae_tile_info(self, encoder=False):
+        """mlis_amd_vae_tile_info of the decode / encode tile plan, or None without one: dict(tile=(w, h) in latent / image pixels, in_bytes, out_bytes
+        (allocated for the tile's input and output buffers), n_tiles (one pass walks), n_evals (plan evaluations of the last tiled pass))"""
+        w, h, n, e = c_int(), c_int(), c_int(), c_int()
+        ib, ob = ctypes.c_size_t(), ctypes.c_size_t()
+        r = _proto2().mlis_amd_vae_tile_info(self.h, int(encoder), *[ctypes.byref(v) for v in (w, h, ib, ob, n, e)])
+        if r < 0:
+            check1(r, "mlis_amd_vae_tile_info")
+        if r == 0:
+            return None
+        return dict(tile=(w.value, h.value), in_bytes=ib.value, out_bytes=ob.value, n_tiles=n.value, n_evals=e.value)
 
     def image(self):
         from ._lib import lib

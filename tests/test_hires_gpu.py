@@ -164,10 +164,10 @@ LONG_TOKS = (np.arange(100, dtype=np.int32) * 37 + 11) % 1000
 STEPS, DENOISE = 4, 0.6
 
 
-def context(lib, model="tiny", batch=1, cfg=7.0, tiling=None, tae=False, vae_tile=0, unet_split=False, seed=42, **_):
+def context(lib, model="tiny", batch=1, cfg=7.0, tiling=None, tae=False, vae_tile=0, unet_split=False, seed=42, dim=64, **_):
     m = F.Mlis(lib)
     m.set("model", f"synth:{model}")
-    m.set("image_dim", 64, 64)
+    m.set("image_dim", dim, dim)
     m.set("steps", STEPS)
     m.set("seed", seed)
     m.set("cfg_scale", cfg)
@@ -195,9 +195,17 @@ def target(l, s):
     return int(np.floor(l * s + 0.5))
 
 
+def has_vae_tile_plan(lib, m):
+    """whether the engine of the last pass holds a tile-sized decoder plan (mlis_amd_ctx_at 3): vae_tile only tiles an image larger than one tile + margins"""
+    lib.mlis_amd_engine_get.restype, lib.mlis_amd_engine_get.argtypes = C.c_void_p, [C.c_void_p]
+    lib.mlis_amd_ctx_at.restype, lib.mlis_amd_ctx_at.argtypes = C.c_void_p, [C.c_void_p, C.c_int]
+    eng = lib.mlis_amd_engine_get(m.ctx)
+    return bool(eng and lib.mlis_amd_ctx_at(eng, 3))
+
+
 def results(lib, m, decoded=True):
     return dict(latent=m.tensor(F.TENSOR["LATENT"]), image=m.tensor(F.TENSOR["IMAGE"]) if decoded else None,
-                info=lib.mlis_infotext_get(m.ctx, 0).decode(), builds=lib.mlis_amd_engine_builds(m.ctx))
+                info=lib.mlis_infotext_get(m.ctx, 0).decode(), builds=lib.mlis_amd_engine_builds(m.ctx), vae_tiled=has_vae_tile_plan(lib, m))
 
 
 def nfe_of(info):
@@ -272,11 +280,17 @@ def test_hires_equals_its_manual_composition(lib, case, cfg, upscaler):
         assert not np.array_equal(h["latent"][0], h["latent"][1])
 
 
-@pytest.mark.parametrize("extra", [dict(tae=True), dict(vae_tile=32), dict(unet_split=True), dict(long=True), dict(tae=True, vae_tile=32, tiling="xy")],
-                         ids=["tae", "vae_tile", "unet_split", "long_prompt", "tae_tiling"])
+@pytest.mark.parametrize("extra", [dict(tae=True), dict(vae_tile=32), dict(unet_split=True), dict(long=True), dict(tae=True, vae_tile=32, tiling="xy"),
+                                   dict(vae_tile=64, dim=128, scale=2)],
+                         ids=["tae", "vae_tile", "unet_split", "long_prompt", "tae_tiling", "vae_tile_256"])
 def test_hires_composes_with_the_other_options(lib, extra):
-    kw = dict(model="tiny", scale=1.5, batch=2, cfg=7.0, upscaler="bicubic", hires_steps=3, **extra)
-    assert_same(hires_generate(lib, **kw), manual_generate(lib, **kw), extra)
+    """vae_tile 32 at 96 x 96 is one VAE tile (the option is taken, the decode is the untiled one); 128 -> 256 x 256 at vae_tile 64 decodes the second pass in 2 x 2 tiles"""
+    kw = dict(dict(model="tiny", scale=1.5, batch=2, cfg=7.0, upscaler="bicubic", hires_steps=3), **extra)
+    h, man = hires_generate(lib, **kw), manual_generate(lib, **kw)
+    assert_same(h, man, extra)
+    assert h["vae_tiled"] == man["vae_tiled"] == (extra.get("dim") == 128)
+    if extra.get("dim") == 128:
+        assert h["image"].shape == (2, 3, 256, 256)
 
 
 def test_hires_wraps_under_tiling(lib):

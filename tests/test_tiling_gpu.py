@@ -330,11 +330,19 @@ def lib():
 TOKS = np.array([5, 17, 300, 42, 7], np.int32)
 
 
-def generate(lib, tiling=None, tae=False, image=None, vae_tile=0, expect=1):
+def has_vae_tile_plan(lib, m):
+    """whether the context's engine holds a tile-sized decoder plan (mlis_amd_ctx_at 3): vae_tile only tiles an image larger than one tile + margins"""
+    lib.mlis_amd_engine_get.restype, lib.mlis_amd_engine_get.argtypes = C.c_void_p, [C.c_void_p]
+    lib.mlis_amd_ctx_at.restype, lib.mlis_amd_ctx_at.argtypes = C.c_void_p, [C.c_void_p, C.c_int]
+    eng = lib.mlis_amd_engine_get(m.ctx)
+    return bool(eng and lib.mlis_amd_ctx_at(eng, 3))
+
+
+def generate(lib, tiling=None, tae=False, image=None, vae_tile=0, expect=1, dim=64, tile_plan=False):
     m = F.Mlis(lib)
     try:
         m.set("model", "synth:tiny")
-        m.set("image_dim", 64, 64)
+        m.set("image_dim", dim, dim)
         m.set("steps", 3)
         m.set("seed", 42)
         m.tokens(TOKS)
@@ -352,6 +360,7 @@ def generate(lib, tiling=None, tae=False, image=None, vae_tile=0, expect=1):
         assert r == expect, (r, m.err())
         if r < 0:
             return None, m.err(), None
+        assert has_vae_tile_plan(lib, m) == tile_plan
         return m.image(0), m.err(), lib.mlis_infotext_get(m.ctx, 0).decode()
     finally:
         m.close()
@@ -376,3 +385,9 @@ def test_public_option_end_to_end(lib):
     assert "tiling" in err and "vae_tile" in err
     out, _, _ = generate(lib, "xy", tae=True, vae_tile=32)           # TAESD is never tiled: it wraps
     assert out is not None
+    # (64 x 64 is one tile for any codec: no tile plan would exist there with the KL-VAE either.)  At 256 x 256 vae_tile 64 tiles the KL-VAE and still not TAESD
+    generate(lib, vae_tile=64, dim=256, tile_plan=True)
+    _, err, _ = generate(lib, "x", vae_tile=64, dim=256, expect=-4)
+    assert "tiling" in err and "vae_tile" in err
+    out, _, _ = generate(lib, "xy", tae=True, vae_tile=64, dim=256)
+    assert out is not None and out.shape[:2] == (256, 256)

@@ -316,9 +316,17 @@ def prompt(m, long=False):
     m.tokens(NTOKS, negative=True)
 
 
+def has_vae_tile_plan(lib, m):
+    """whether the context's engine holds a tile-sized decoder plan (mlis_amd_ctx_at 3): vae_tile only tiles an image larger than one tile + margins"""
+    lib.mlis_amd_engine_get.restype, lib.mlis_amd_engine_get.argtypes = C.c_void_p, [C.c_void_p]
+    lib.mlis_amd_ctx_at.restype, lib.mlis_amd_ctx_at.argtypes = C.c_void_p, [C.c_void_p, C.c_int]
+    eng = lib.mlis_amd_engine_get(m.ctx)
+    return bool(eng and lib.mlis_amd_ctx_at(eng, 3))
+
+
 def results(lib, m, decoded=True):
     return dict(latent=m.tensor(F.TENSOR["LATENT"]), image=m.tensor(F.TENSOR["IMAGE"]) if decoded else None,
-                info=lib.mlis_infotext_get(m.ctx, 0).decode(), builds=lib.mlis_amd_engine_builds(m.ctx))
+                info=lib.mlis_infotext_get(m.ctx, 0).decode(), builds=lib.mlis_amd_engine_builds(m.ctx), vae_tiled=has_vae_tile_plan(lib, m))
 
 
 def generate(lib, setup=None, long=False, decoded=True, **kw):
@@ -387,7 +395,8 @@ def img2img_mask(m):
 COMPOSE = {
     "hires": dict(dim=64, setup=hires_opts),
     "tae": dict(opts=(("tae", "synth"),)),
-    "vae_tile": dict(opts=(("vae_tile", 32),)),
+    "vae_tile": dict(opts=(("vae_tile", 32),)),                     # 96 x 96 is one VAE tile: the option is taken, the decode is the untiled one
+    "vae_tile_256": dict(dim=256, opts=(("vae_tile", 64),)),        # 32 x 32 latent: 2 x 2 VAE tiles of 24 decode the canvas the UNet windows blended
     "unet_split": dict(opts=(("unet_split", 1),)),
     "long_prompt": dict(long=True),
     "img2img_mask": dict(setup=img2img_mask),
@@ -400,9 +409,11 @@ COMPOSE = {
 def test_composes_with_the_other_options(lib, name):
     kw = COMPOSE[name]
     a, b = generate(lib, unet_tile=TILE, **kw), generate(lib, unet_tile=TILE, **kw)
-    assert a["latent"].shape == (2, 4, 12, 12) and np.isfinite(a["latent"]).all()
+    lat = 32 if name == "vae_tile_256" else 12
+    assert a["latent"].shape == (2, 4, lat, lat) and np.isfinite(a["latent"]).all()
     if a["image"] is not None:
-        assert a["image"].shape == (2, 3, 96, 96) and np.isfinite(a["image"]).all()
+        assert a["image"].shape == (2, 3, 8 * lat, 8 * lat) and np.isfinite(a["image"]).all()
+    assert a["vae_tiled"] == b["vae_tiled"] == (name == "vae_tile_256")
     assert same(a, b) and a["info"] == b["info"]
     assert f", Tiled diffusion: {TILE}, Tile overlap: {OVERLAP}, Version: " in a["info"]
     assert a["builds"] == (2 if name == "hires" else 1)                   # hires: the first pass fits the tile and runs on the plain engine

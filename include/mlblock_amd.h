@@ -50,6 +50,8 @@ void   mlctx_set_wtype(MLCtx* C, int wtype);               /* linear weight type
                                                               * device storage and MFMA operands are always F16 */
 void   mlctx_set_conv_wrap(MLCtx* C, int mode);         /* circular padding of the convolutions built from now on (seamless tiling): 0 none, 1 columns (x),
                                                               * 2 rows (y), 3 both; a tap outside the image reads the pixel modulo the image size */
+void   mlctx_set_vae_attn(MLCtx* C, int mode);          /* the mid-block attention of the KL-VAE plans built from now on: 0 (default) scores in memory (GEMM, row softmax,
+                                                              * GEMM per image), 1 one flash launch over all images (mlsd_attention_wide; a 512-wide mid block only) */
 void   mlctx_set_hypertile(MLCtx* C, int tile_px, int depth);   /* HyperTile for the spatial transformers built from now on: tile_px > 0 tiles the self-attention of
                                                               * every level the rule of mlis_amd_hypertile_side cuts (UNet downscale ds, px_per_token = 8 ds) with
                                                               * log2(ds) <= depth; 0: off, the plan is op for op the one without this call */

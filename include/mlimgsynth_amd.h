@@ -540,6 +540,13 @@ MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S);
 MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S);                            /* build the encoder plan now (weights: synth or caller-loaded) */
 int mlis_amd_vae_tile_walk(int full, int tile_px, int unit, int margin, int* n_out, int* origin, int* src_off, int* width, int max_tiles);
 int mlis_amd_vae_tile_info(MLIS_AmdCtx* S, int which, int* tile_w, int* tile_h, size_t* in_bytes, size_t* out_bytes, int* n_tiles, int* n_evals);
+/* The mid-block self attention of the KL-VAE plans (one head of d = 512 over the h w latent tokens): mode 0 (default) GEMM + row softmax + GEMM per image over a
+ * score matrix of 6 T^2 bytes in the plan, mode 1 one flash launch over all images (mlsd_attention_wide), no score matrix.  A field of the engine handed over before
+ * every pass, as mlis_amd_set_prediction is.  A change rebuilds the codec plans only -- the full-size decoder here, the encoder and the tile plans at their next use --
+ * and leaves the UNet plan and its weights alone; with defer_weights the caller loads the new decoder's parameters (mlctx_params_loaded tells).  Returns 1, < 0 for a
+ * mode other than 0 / 1 or a plan that does not build (a mid block that is not 512 wide has no flash kernel).  mlis_amd_vae_attn_mode: the mode. */
+int mlis_amd_set_vae_attn(MLIS_AmdCtx* S, int mode);
+int mlis_amd_vae_attn_mode(const MLIS_AmdCtx* S);
 int mlis_amd_last_n_step(MLIS_AmdCtx* S);
 /* passes (denoising loop, decode, encode) that were run AGAIN on the hand-off-free plan after an in-launch hand-off (stream-K slab, LayerNorm statistics) timed out --
  * the GPU was shared or the stream CU-masked.  The call that hit it still succeeds; results then come from plain tiles / separate LayerNorm launches. */

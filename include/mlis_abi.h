@@ -212,6 +212,15 @@ struct MLIS_AmdCtx* mlis_amd_engine_get(MLIS_Ctx* ctx);
 /* engines constructed by this context so far.  A context keeps its two most recently used engines (one per model / size / batch / ... key),
  * so a workflow that alternates between two sizes -- the hires fix -- rebuilds nothing; mlis_amd_engine_get returns the one used last. */
 int mlis_amd_engine_builds(MLIS_Ctx* ctx);
+/* How the KL-VAE's mid-block self attention (one head of 512 channels over the latent's h w tokens, decoder and encoder) runs.  SCORES (default): as the reference,
+ * a materialised score matrix of 6 T^2 bytes per plan (1.5 GiB at 1024 x 1024).  FLASH: one fused launch, no score matrix.  Not an MLIS_Option: the mode is handed to
+ * the engine before every pass; a change rebuilds the codec plans (full-size and vae_tile) at their next use and no engine (mlis_amd_engine_builds stays).  Composes
+ * with tiling, vae_tile, the hires fix, img2img and inpainting; TAESD has no attention.  Returns 1, MLIS_E_OPT_VALUE for another mode.
+ * mlis_amd_vae_attn_info: *mode = the setting, *plan_mode = the mode the resident engine's decoder plan was built with (-1 without an engine); either may be NULL. */
+#define MLIS_AMD_VAE_ATTN_SCORES 0
+#define MLIS_AMD_VAE_ATTN_FLASH  1
+int mlis_amd_vae_attn(MLIS_Ctx* ctx, int mode);
+int mlis_amd_vae_attn_info(MLIS_Ctx* ctx, int* mode, int* plan_mode);
 /* ControlNet: evaluations of pass 0 / 1 of the last mlis_generate in which the ControlNet ran (a hires generation has two passes); -1 for a pass that did not run */
 int mlis_amd_control_evals(MLIS_Ctx* ctx, int pass);
 /* LoRA bookkeeping, cumulative like mlis_amd_engine_builds.  A change of the LoRA set or of a multiplier while engines or text towers are resident is applied

@@ -331,6 +331,13 @@ void mlsd_attention_tk96(int on, int qb);  /* Tk <= 96 one-pass kernel on/off (A
 void mlsd_attention_wide_stores(int on);  /* diagnostics / A-B timing: 0 = the output in 8-byte pieces per lane */
 void mlsd_attention_vsum(int on);         /* diagnostics / A-B timing: 1 = row sums of the 64-rows-per-wave kernel on the VALU instead of ones.P MFMAs */
 
+/* One head of d_head 512 (the KL-VAE's mid-block self attention, src/vae.c:46-74) as one flash-style launch (attention_wide.hip: attn_wide_kernel, 128 query rows per
+ * workgroup of 8 waves, the scores split over rows and P.V over columns).  n_head == 1, d_head == 512, causal == 0, Tq == Tk >= 1, any n_batch; head 0 at column 0;
+ * strides and alignment as mlsd_attention_ctx states them.  Anything else: an error.  mlsd_attention_wide_variant: the launch's label "attn<wide,d512>", NULL where
+ * the launch would refuse (mlsd_attention_variant's counterpart). */
+int mlsd_attention_wide(const mlsd_attn_args* a, void* stream);
+const char* mlsd_attention_wide_variant(const mlsd_attn_args* a);
+
 /* row softmax over fp32 scores -> fp16 probabilities (VAE mid attention, d=512 single head,
  * src/vae.c:46-74, computed as GEMM + softmax + GEMM).  in [rows][ld_in] f32, out [rows][ld_out] f16 */
 int mlsd_softmax_rows(const float* in, int64_t ld_in, void* out, int64_t ld_out, int rows, int cols,

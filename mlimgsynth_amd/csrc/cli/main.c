@@ -326,6 +326,7 @@ static const char k_usage[] =
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
 "             --unet-tile PX   --unet-tile-overlap PX   --unet-tile-batch N\n"
+"             --vae-attn scores|flash   (the KL-VAE's mid-block attention: over a score matrix in memory, or one flash launch without it)\n"
 "ControlNet:  --control-model PATH|synth[:SEED]   --control-image PATH   --control-strength F   --control-start F   --control-end F\n"
 "             --control-preprocess none|canny|invert   (run on the control image after it was resampled to each pass's size)\n"
 "Canny:       --canny-low F   --canny-high F   --canny-l2 y|n   (thresholds 0 .. 32767, defaults 100 200; l2: sqrt(dx^2 + dy^2) instead of |dx| + |dy|)\n"
@@ -368,6 +369,11 @@ static int cli_option(Cli* C, const char* name, const char* next)
 		char *e = NULL; const double f = strtod(next, &e);
 		if (e == next || *e || !(f > 0 && f <= 4)) FAIL("option '--outscale %s': a factor in (0, 4] is needed", next);
 		C->outscale = f; return 1;
+	}
+	if (!strcmp(name, "vae-attn")) {      /* not an option of the table: the call itself (include/mlis_abi.h) */
+		const int mode = !strcmp(next, "scores") ? MLIS_AMD_VAE_ATTN_SCORES : !strcmp(next, "flash") ? MLIS_AMD_VAE_ATTN_FLASH : -1;
+		if (mode < 0 || mlis_amd_vae_attn(C->ctx, mode) < 0) FAIL("option '--vae-attn %s': scores or flash", next);
+		return 1;
 	}
 	if (mlis_option_set_str(C->ctx, name, next) < 0) FAIL("option '--%s %s': %s", name, next, mlis_errstr_get(C->ctx));
 	return 1;

@@ -72,6 +72,7 @@ struct MLIS_AmdCtx {
 	/* VAE tiling (MLIS_OPT_VAE_TILE; src/vae.c:245-300,333-391): tile-sized plans, built on first use */
 	int vae_tile, tl_w, tl_h, ti_w, ti_h;             /* option (pixels); latent / image tile size of the decode and encode plans */
 	MLCtx *dect_ctx, *enct_ctx;
+	int vae_attn;               /* mlis_amd_set_vae_attn: the mid-block attention of the KL-VAE plans (mlctx_set_vae_attn), full-size and tile-sized alike */
 	MLTensor *t_lat_dect, *t_img_enct;
 	float *d_lat_tile, *d_img_tile, *d_imgin_tile, *d_mom_tile, *d_mom;
 	size_t tile_bytes[4];                             /* allocated bytes of d_lat_tile, d_img_tile, d_imgin_tile, d_mom_tile: they follow the tile size */
@@ -398,6 +399,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	/* ---- decoder plan, latent input bound to the same resident latent */
 	S->dec_ctx = mlctx_new(stream);
 	mlctx_set_conv_wrap(S->dec_ctx, S->tiling);
+	mlctx_set_vae_attn(S->dec_ctx, S->vae_attn);
 	if (S->c.use_tae) {
 		if (sdtae_decode_init(S->dec_ctx, S->lw, S->lh, B, &S->t_lat_dec) < 0) goto err;
 		if (mlctx_input_bind(S->t_lat_dec, S->d_x, B, NULL, 1.0f, 1) < 0) goto err;
@@ -1202,6 +1204,33 @@ MLB_API int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px)
 	return 1;
 }
 
+/* The mid-block attention of the KL-VAE plans: 0 = scores in memory (the default), 1 = one flash launch (mlsd_attention_wide).  A change drops the codec plans
+ * only: the full-size decoder is rebuilt here (its parameters are synthesised again, or left for the caller to load: mlctx_params_loaded, as at creation), the
+ * encoder and the two tile plans at their next use.  The UNet plan, its weights and every device buffer of the engine stay.  TAESD has no attention: nothing to do. */
+MLB_API int mlis_amd_set_vae_attn(MLIS_AmdCtx* S, int mode)
+{
+	if (!S) return fail("mlis_amd_set_vae_attn: no engine");
+	if (mode != 0 && mode != 1) return mlsd_set_error(-1, "mlis_amd_set_vae_attn: mode %d (0 scores, 1 flash)", mode);
+	if (mode == S->vae_attn) return 1;
+	S->vae_attn = mode;
+	if (S->c.use_tae) return 1;
+	mlsd_stream_sync(S->stream);
+	if (S->dect_ctx) { mlctx_destroy(S->dect_ctx); S->dect_ctx = NULL; }
+	if (S->enct_ctx) { mlctx_destroy(S->enct_ctx); S->enct_ctx = NULL; }
+	if (S->enc_ctx) { mlctx_destroy(S->enc_ctx); S->enc_ctx = NULL; }
+	MLCtx *C = mlctx_new(S->stream);
+	mlctx_set_conv_wrap(C, S->tiling);
+	mlctx_set_vae_attn(C, mode);
+	int ok = sdvae_decode_init(C, &S->vae_p, S->lw, S->lh, S->B, &S->t_lat_dec) >= 0 &&
+	         mlctx_input_bind(S->t_lat_dec, S->d_x, S->B, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
+	         sdvae_decode_build(C, &S->vae_p, S->t_lat_dec) >= 0;
+	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
+	mlctx_destroy(S->dec_ctx);
+	S->dec_ctx = C;             /* (a plan that failed to build stays in place: the next decode reports its error) */
+	return ok ? 1 : -1;
+}
+MLB_API int mlis_amd_vae_attn_mode(const MLIS_AmdCtx* S) { return S ? S->vae_attn : -1; }
+
 static int tile_dims(int tile_px, int margin2, int full, int unit)
 {	/* n = min(round_up(tile_px, 64)/unit + 2k, full); returns full when one tile covers everything (tiling disabled) */
 	const int t = (tile_px + 63) / 64 * 64;
@@ -1277,6 +1306,7 @@ MLB_API MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S)
 	if (tile_buf(S, &S->d_lat_tile, 0, (size_t)B*4*n0*n1*4)) return NULL;
 	if (tile_buf(S, &S->d_img_tile, 1, (size_t)B*3*n0*f*n1*f*4)) return NULL;
 	MLCtx *C = mlctx_new(S->stream);
+	mlctx_set_vae_attn(C, S->vae_attn);
 	int ok = sdvae_decode_init(C, &S->vae_p, n0, n1, 1, &S->t_lat_dect) >= 0 &&
 	         mlctx_input_bind(S->t_lat_dect, S->d_lat_tile, 1, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
 	         sdvae_decode_build(C, &S->vae_p, S->t_lat_dect) >= 0;
@@ -1299,6 +1329,7 @@ MLB_API MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S)
 	if (tile_buf(S, &S->d_mom_tile, 3, (size_t)B*8*(n0/f)*(n1/f)*4)) return NULL;
 	if (!S->d_mom && mlsd_malloc((void**)&S->d_mom, (size_t)B*8*S->hw*4)) return NULL;
 	MLCtx *C = mlctx_new(S->stream);
+	mlctx_set_vae_attn(C, S->vae_attn);
 	int ok = sdvae_encode_init(C, &S->vae_p, n0, n1, 1, &S->t_img_enct) >= 0 &&
 	         mlctx_input_bind(S->t_img_enct, S->d_imgin_tile, 1, NULL, 1.0f, 2) >= 0 &&
 	         sdvae_encode_build(C, &S->vae_p, S->t_img_enct) >= 0;
@@ -1449,6 +1480,7 @@ MLB_API MLCtx* mlis_amd_encoder_prepare(MLIS_AmdCtx* S)
 	if (!S->d_img_in && mlsd_malloc((void**)&S->d_img_in, (size_t)B*3*W*H*4)) return NULL;
 	MLCtx *C = mlctx_new(st);
 	mlctx_set_conv_wrap(C, S->tiling);
+	mlctx_set_vae_attn(C, S->vae_attn);
 	int ok = 0;
 	if (S->c.use_tae) {
 		ok = sdtae_encode_init(C, W, H, B, &S->t_img_enc) >= 0 && mlctx_input_bind(S->t_img_enc, S->d_img_in, B, NULL, 1.0f, 0) >= 0 &&

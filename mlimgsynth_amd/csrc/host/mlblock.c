@@ -114,6 +114,7 @@ MLB_API void mlctx_set_tprefix(MLCtx* C, const char* p) { snprintf(C->tprefix, s
 MLB_API void mlctx_set_flags(MLCtx* C, int f) { C->flags = f; }
 MLB_API void mlctx_set_wtype(MLCtx* C, int t) { C->wtype = t; }
 MLB_API void mlctx_set_conv_wrap(MLCtx* C, int mode) { C->conv_wrap = mode & 3; }
+MLB_API void mlctx_set_vae_attn(MLCtx* C, int mode) { C->vae_attn = mode == 1; }
 MLB_API void mlctx_set_hypertile(MLCtx* C, int tile_px, int depth) { C->ht.tile_px = tile_px > 0 ? tile_px : 0; C->ht.depth = depth < 0 ? 0 : depth > 3 ? 3 : depth; }
 MLB_API int mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, int tiles[4][4])
 {

@@ -110,6 +110,7 @@ struct MLCtx {
 	char tprefix[32];
 	int flags, wtype;
 	int conv_wrap;          /* mlctx_set_conv_wrap: mlsd_gemm_args.wrap of the convolutions built from now on */
+	int vae_attn;           /* mlctx_set_vae_attn: 0 = the KL-VAE's mid attention as GEMM + softmax + GEMM over a materialised score matrix, 1 = one flash launch (vae_tae.c) */
 	/* HyperTile (mlctx_set_hypertile; mlb_spatial_transf of unet.c).  nt is set only while a tiled block's transformer layers are being built: mlb_attn_mhead_ex then
 	 * records a SELF-attention as nb x nt batches of Tq / nt tokens (the rows are in tile-major order between the block's two permuting copies); 0 elsewhere */
 	struct { int tile_px, depth, nt, n_tiled, n_untiled, tiles[4][4]; } ht;

@@ -5,7 +5,10 @@
 
 /* ------------------------------------------------------------------ launches */
 static int run_gemm(const MLOp* op, void* st) { return mlsd_gemm(&op->u.gemm, st); }
-static int run_attn(const MLOp* op, void* st) { return mlsd_attention(&op->u.attn, st); }
+static int run_attn(const MLOp* op, void* st)
+{	/* one head of 512 (the KL-VAE's mid block in flash mode, vae_tae.c) has a kernel of its own */
+	return op->u.attn.d_head == 512 ? mlsd_attention_wide(&op->u.attn, st) : mlsd_attention(&op->u.attn, st);
+}
 static int run_attn_ctx(const MLOp* op, void* st) { return mlsd_attention_ctx(&op->u.attn, st); }   /* cross attention over more than 96 context rows (windowed prompt) */
 static int run_gn(const MLOp* op, void* st)
 {

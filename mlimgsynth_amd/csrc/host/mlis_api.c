@@ -58,6 +58,7 @@ struct MLIS_Ctx {
 	int inp_region[4], inp_proc[2], inp_done;
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
+	int vae_attn;                           /* mlis_amd_vae_attn: MLIS_AMD_VAE_ATTN_*, handed to the engine before every pass (never part of the engine key) */
 	float cfg_rescale;                      /* MLIS_OPT_AMD_CFG_RESCALE: phi of the guidance rescale, handed to the engine per generation (never part of the engine key) */
 	int prediction, zsnr;                   /* MLIS_OPT_AMD_PREDICTION (0 auto, 1 eps, 2 v) / MLIS_OPT_AMD_ZSNR (0 auto, 1 off, 2 on): resolved per generation (guidance_resolve) */
 	int ckpt_v_pred, ckpt_ztsnr;            /* the checkpoint's marker tensors (mlts_markers); 0 for the synthetic models */
@@ -311,6 +312,20 @@ MLB_API int mlis_amd_control_evals(MLIS_Ctx* S, int pass)
 	return S->control_evals[pass];
 }
 MLB_API int mlis_amd_engine_builds(MLIS_Ctx* S) { return (S && S->signature == CTX_SIGNATURE) ? S->n_eng_builds : -1; }
+MLB_API int mlis_amd_vae_attn(MLIS_Ctx* S, int mode)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (mode != MLIS_AMD_VAE_ATTN_SCORES && mode != MLIS_AMD_VAE_ATTN_FLASH) return api_error(S, MLIS_E_OPT_VALUE, "vae_attn: mode %d (0 scores, 1 flash)", mode);
+	S->vae_attn = mode;          /* (the engines learn it in engine_get, before their next pass) */
+	return 1;
+}
+MLB_API int mlis_amd_vae_attn_info(MLIS_Ctx* S, int* mode, int* plan_mode)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (mode) *mode = S->vae_attn;
+	if (plan_mode) *plan_mode = S->eng ? mlis_amd_vae_attn_mode(S->eng) : -1;
+	return 1;
+}
 MLB_API int mlis_amd_lora_stats(MLIS_Ctx* S, int* n_restored, int* n_patched, int* n_cold_merges)
 {
 	if (!S || S->signature != CTX_SIGNATURE) return -1;
@@ -1284,6 +1299,10 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	if (mlis_amd_set_sampler(S->eng, n_step, method, sched, S->cfg_scale, S->s_ancestral, S->s_noise, S->f_t_ini, S->f_t_end) < 0)
 		return api_error_lib(S, MLIS_E_OPT_VALUE);
 	/* VAE_TILE (:1318,1345): tile-sized decoder plan, weights loaded like the full-size one */
+	/* the VAE's attention mode: a change rebuilds the codec plans of this engine (never the engine); a rebuilt decoder plan gets its weights like a new one */
+	if (mlis_amd_set_vae_attn(S->eng, S->vae_attn) < 0) return api_error_lib(S, MLIS_E_OPT_VALUE);
+	MLCtx *dc = mlis_amd_decoder_ctx(S->eng);
+	if (dc && !mlctx_params_loaded(dc) && ctx_weights(S, dc, tae) < 0) return -1;
 	mlis_amd_set_vae_tile(S->eng, S->vae_tile);
 	MLCtx *tc = mlis_amd_decoder_tile_prepare(S->eng);
 	if (tc && !mlctx_params_loaded(tc) && ctx_weights(S, tc, 0) < 0) return -1;

@@ -28,7 +28,7 @@ MLB_API int unet_params_get(const char* model, UnetParams* U)
 		int a[4]={4,2,0,0}, m[5]={1,2,4,0,0}, d[5]={1,2,10,0,0};
 		memcpy(U->attn_res,a,sizeof(a)); memcpy(U->ch_mult,m,sizeof(m)); memcpy(U->transf_depth,d,sizeof(d));
 		U->d_head=64; U->n_ctx=2048; U->ch_adm_in=2816; U->cond_label=1; U->uncond_empty_zero=1;
-	} else if (!strcmp(model,"tiny")) {
+	} else if (!strcmp(model,"tiny") || !strcmp(model,"tinyw")) {   /* (tinyw: tiny's UNet beside a KL-VAE whose mid block is 512 wide, vae_params_get) */
 		int a[4]={2,1,0,0}, m[5]={1,2,0,0,0}, d[5]={1,1,0,0,0};
 		memcpy(U->attn_res,a,sizeof(a)); memcpy(U->ch_mult,m,sizeof(m)); memcpy(U->transf_depth,d,sizeof(d));
 		U->n_ch=64; U->n_te=256; U->n_head=2; U->n_ctx=64; U->n_res_blk=1; U->clip_norm=1;

@@ -21,6 +21,10 @@ MLB_API int vae_params_get(const char* model, VaeParams* V)
 	if (!strcmp(model,"sd1") || !strcmp(model,"sd2")) V->scale_factor = 0.18215f;
 	else if (!strcmp(model,"sdxl")) V->scale_factor = 0.13025f;
 	else if (!strcmp(model,"tiny") || !strcmp(model,"tinyxl") || !strcmp(model,"tinyv")) { V->scale_factor = 0.18215f; V->ch = 64; V->n_res_blk = 1; }
+	else if (!strcmp(model,"tinyw")) {   /* a test-size KL-VAE with the published models' 512-wide mid block (64 x 8): the d = 512 attention at the cost of a small codec */
+		int w[5] = {1,2,4,8,0};
+		V->scale_factor = 0.18215f; V->ch = 64; V->n_res_blk = 1; memcpy(V->ch_mult, w, sizeof(w));
+	}
 	else return mlsd_set_error(-1, "unknown VAE model '%s'", model);
 	return 1;
 }
@@ -39,7 +43,35 @@ static void gemm_raw(MLCtx* C, const char* label, const void* A, int64_t lda, co
 /* mlb_attn_2d_self, src/vae.c:46-74: single head over d = C, T = h*w tokens per image.
  * d = 512 does not fit the register-resident flash kernel, and this layer is < 6 % of the decoder's
  * FLOPs, so it runs as GEMM (S = Q.K^T, fp32) -> row softmax (fp16 P) -> GEMM (P.V) per image.
- * V^T is produced directly by swapping the operands of the v projection (V^T = Wv . x^T). */
+ * V^T is produced directly by swapping the operands of the v projection (V^T = Wv . x^T).
+ * Flash mode (mlctx_set_vae_attn 1): q, k and v as 1x1 convolutions under the same parameter names and shapes, then ONE attention launch over all images on the
+ * d = 512 kernel (mlsd_attention_wide, through run_attn): no V^T, no score matrix, no fp16 copy of it in the plan. */
+static MLTensor* attn_2d_self_flash(MLCtx* C, MLTensor* x0, MLTensor* xn)
+{
+	const int c = x0->c, Tn = x0->h * x0->w, nb = x0->n;
+	if (c != 512) { mlctx_fail(C, "vae_attn flash: a mid block of %d channels (the flash kernel takes 512)", c); return NULL; }
+	MLTensor *q = MLN("q", mlb_conv2d_ex(C, xn, c, 1, 1, 0, 0, T, NULL));
+	MLTensor *k = MLN("k", mlb_conv2d_ex(C, xn, c, 1, 1, 0, 0, T, NULL));
+	MLTensor *v = MLN("v", mlb_conv2d_ex(C, xn, c, 1, 1, 0, 0, T, NULL));
+	if (!q || !k || !v) return NULL;
+	const void *qd = mlt_need16(C, q), *kd = mlt_need16(C, k), *vd = mlt_need16(C, v);
+	if (!qd || !kd || !vd) return NULL;
+	MLTensor *a = mlt_new(C, nb, x0->h, x0->w, c);
+	a->sz16 = (size_t)rows_of(x0) * c * 2; a->d16 = mlctx_dalloc(C, a->sz16, 0); a->ld16 = c;
+	MLOp *op = mlctx_op_new(C, OP_ATTN, "vae_attn_flash");
+	mlsd_attn_args *at = &op->u.attn;
+	at->q = qd; at->k = kd; at->v = vd; at->out = a->d16;
+	at->ldq = q->ld16; at->ldk = k->ld16; at->ldv = v->ld16; at->ldo = c;
+	at->bsq = (int64_t)Tn * q->ld16; at->bsk = (int64_t)Tn * k->ld16; at->bsv = (int64_t)Tn * v->ld16; at->bso = (int64_t)Tn * c;
+	at->n_batch = nb; at->n_head = 1; at->d_head = c; at->Tq = Tn; at->Tk = Tn; at->causal = 0;
+	op->flops = 4.0 * nb * (double)Tn * Tn * c;
+	mlb_release(C, q); mlb_release(C, k); mlb_release(C, v); mlb_release(C, xn);
+	MLEpilogue ep = {0}; ep.resid = x0;
+	MLTensor *y = MLN("proj_out", mlb_conv2d_ex(C, a, c, 1, 1, 0, 0, T, &ep));
+	mlb_release(C, a);
+	return y;
+}
+
 static MLTensor* mlb_attn_2d_self(MLCtx* C, MLTensor* x)
 {
 	MLTensor *x0 = x;
@@ -47,6 +79,7 @@ static MLTensor* mlb_attn_2d_self(MLCtx* C, MLTensor* x)
 	const int c = x->c, Tn = x->h * x->w, nb = x->n;
 	MLTensor *xn = MLN("norm", mlb_groupnorm_ex(C, x, 32, 1e-6f, 0, 0, NULL));
 	if (!xn) return NULL;
+	if (C->vae_attn == 1) return attn_2d_self_flash(C, x0, xn);
 	/* q, k: 1x1 convs == linears over channels; parameters keep conv shapes [1,1,c,c] */
 	MLTensor *q = MLN("q", mlb_conv2d_ex(C, xn, c, 1, 1, 0, 0, T, NULL));
 	MLTensor *k = MLN("k", mlb_conv2d_ex(C, xn, c, 1, 1, 0, 0, T, NULL));

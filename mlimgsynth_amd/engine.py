@@ -164,6 +164,14 @@ def fptr(a):
     return a.ctypes.data_as(FP) if a is not None else None
 
 
+def set_vae_attn(ctx, mode):
+    """mlctx_set_vae_attn: 0 scores (default), 1 flash -- the mid-block attention of the KL-VAE plans the context builds from now on."""
+    f = L().mlctx_set_vae_attn
+    f.argtypes = [vp, c_int]
+    f.restype = None
+    f(ctx.h, int(mode))
+
+
 def set_hypertile(ctx, tile_px, depth=3):
     """mlctx_set_hypertile: HyperTile for the spatial transformers the context builds from now on (tile_px 0: off)."""
     f = L().mlctx_set_hypertile
@@ -414,6 +422,9 @@ def _proto2():
     l.sdvae_decode_init.argtypes = [vp, ctypes.POINTER(VaeParams), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(vp)]
     l.sdvae_decode_build.argtypes = [vp, ctypes.POINTER(VaeParams), vp]
     l.sdvae_decode_run.argtypes = [vp, vp, FP, FP]
+    l.sdvae_encode_init.argtypes = [vp, ctypes.POINTER(VaeParams), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(vp)]
+    l.sdvae_encode_build.argtypes = [vp, ctypes.POINTER(VaeParams), vp]
+    l.sdvae_encode_run.argtypes = [vp, vp, FP, FP]
     l.sdtae_decode_init.argtypes = [vp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(vp)]
     l.sdtae_decode_build.argtypes = [vp, vp]
     l.sdtae_decode_run.argtypes = [vp, vp, FP, FP]
@@ -461,6 +472,8 @@ def _proto2():
     l.mlis_amd_last_n_step.argtypes = [vp]
     l.mlis_amd_sync.argtypes = [vp]
     l.mlis_amd_set_vae_tile.argtypes = [vp, c_int]
+    l.mlis_amd_set_vae_attn.argtypes = [vp, c_int]
+    l.mlis_amd_vae_attn_mode.argtypes = [vp]
     for f in (l.mlis_amd_decoder_tile_prepare, l.mlis_amd_encoder_tile_prepare):
         f.restype, f.argtypes = vp, [vp]
     l.mlis_amd_vae_tile_walk.argtypes = [c_int] * 4 + [ctypes.POINTER(c_int)] * 4 + [c_int]
@@ -593,7 +606,7 @@ class Generator:
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
                  defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, freeu=False,
-                 hypertile=0, hypertile_depth=3, pag=False, tiling=0):
+                 hypertile=0, hypertile_depth=3, pag=False, vae_attn="scores", tiling=0):
         l = _proto2()
         self.cfg = AmdControlConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
@@ -611,6 +624,8 @@ class Generator:
             raise MlsdError("mlis_amd_create failed: " + last_error())
         self.model, self.w, self.h_px, self.B = model, width, height, n_batch
         self.P = unet_params(model)
+        if vae_attn != "scores":
+            self.set_vae_attn(vae_attn)
 
     def set_cond(self, cond, label=None, uncond=None, unlabel=None):
         a = [np.ascontiguousarray(x, np.float32) if x is not None else None for x in (cond, label, uncond, unlabel)]
@@ -778,6 +793,16 @@ class Generator:
     def decode(self):
         check1(_proto2().mlis_amd_decode(self.h), "mlis_amd_decode")
         check1(_proto2().mlis_amd_sync(self.h), "mlis_amd_sync")
+
+    VAE_ATTN = {"scores": 0, "flash": 1}
+
+    def set_vae_attn(self, mode):
+        """mlis_amd_set_vae_attn: "scores" (the default) or "flash" -- the KL-VAE's mid-block attention over a score matrix in memory, or as one flash launch; a change
+        rebuilds the codec plans (this one's decoder now, the encoder and the tile plans at their next use), never the UNet plan"""
+        check1(_proto2().mlis_amd_set_vae_attn(self.h, self.VAE_ATTN.get(mode, mode)), "mlis_amd_set_vae_attn")
+
+    def vae_attn(self):
+        return {v: k for k, v in self.VAE_ATTN.items()}[_proto2().mlis_amd_vae_attn_mode(self.h)]
 
     def set_vae_tile(self, tile_px):
         check1(_proto2().mlis_amd_set_vae_tile(self.h, int(tile_px)), "mlis_amd_set_vae_tile")

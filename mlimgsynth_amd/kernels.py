@@ -166,6 +166,20 @@ def attention_ctx(args, stream=None):
     check(lib().mlsd_attention_ctx(ctypes.byref(args), vp(stream)), "mlsd_attention_ctx")
 
 
+def attention_wide(args, stream=None):
+    """mlsd_attention_wide: one head of d_head 512, Tq == Tk, no mask (the KL-VAE's mid-block self attention as one flash launch)."""
+    check(lib().mlsd_attention_wide(ctypes.byref(args), vp(stream)), "mlsd_attention_wide")
+
+
+def attention_wide_variant(args):
+    """mlsd_attention_wide_variant: the launch's label, None where mlsd_attention_wide would refuse."""
+    f = lib().mlsd_attention_wide_variant
+    f.restype = ctypes.c_char_p
+    f.argtypes = [ctypes.POINTER(AttnArgs)]
+    lab = f(ctypes.byref(args))
+    return lab.decode() if lab is not None else None
+
+
 def groupnorm(args, stream=None):
     check(lib().mlsd_groupnorm(ctypes.byref(args), vp(stream)), "mlsd_groupnorm")
 

@@ -86,6 +86,7 @@ _PROTOTYPES = {
     "mlis_mask_encode": (_I, [_V, _TP, _TP, _I]), "mlis_text_tokenize": (_I, [_V, _S, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), _I]),
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
+    "mlis_amd_vae_attn": (_I, [_V, _I]), "mlis_amd_vae_attn_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_canny": (_I, [_V, _TP, _TP, _F, _F, _I, _I]),
@@ -522,6 +523,23 @@ class MLImgSynth:
             if self._lib.mlis_amd_tensor_resample_aa(self._ctx, tout, tout, max(w, 1), max(h, 1), f.value - 1 if f.value else MLIS_AMD_AA_LANCZOS) < 0:   # noqa: F821
                 raise RuntimeError("Failed to resample the upscaled image: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
+
+    # ---- the KL-VAE's mid-block attention
+    VAE_ATTN = {"scores": 0, "flash": 1}
+
+    def vae_attn_set(self, mode="scores"):
+        """mode "scores" (default): the VAE's mid-block self attention over a score matrix in memory, as the reference; "flash": one fused launch without it
+        (6 T^2 bytes less per codec plan, T = latent h x w).  Persists; a change rebuilds the codec plans at their next use and no engine."""
+        if mode not in self.VAE_ATTN or self._lib.mlis_amd_vae_attn(self._ctx, self.VAE_ATTN[mode]) < 0:
+            raise ValueError("vae_attn: 'scores' or 'flash', not %r" % (mode,))
+
+    def vae_attn_info(self):
+        """dict: mode (the setting) and plan_mode (what the resident engine's decoder plan was built with; None without an engine), as "scores" | "flash"."""
+        a, b = _I(), _I()
+        if self._lib.mlis_amd_vae_attn_info(self._ctx, ctypes.byref(a), ctypes.byref(b)) < 0:
+            raise RuntimeError("Failed to read the VAE attention mode: %s" % self.errstr_get())
+        name = {v: k for k, v in self.VAE_ATTN.items()}
+        return dict(mode=name[a.value], plan_mode=name.get(b.value))
 
     def engine_builds(self):
         "Engines this context has constructed so far (it keeps the two used last)."

@@ -523,6 +523,20 @@ int mlis_amd_set_cfg_rescale(MLIS_AmdCtx* S, float phi);
 int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float* sigma_min, float* sigma_max, float* phi, int* n_evals, float* factors, int max_factors);
 int mlis_amd_last_rows(MLIS_AmdCtx* S, float* out, size_t nbytes);      /* the raw outputs the last mix read, host [N][4][hw] (tests, tools) */
 int mlis_amd_prediction_resolve(const char* model, int ckpt_v_pred, int ckpt_ztsnr, int opt_prediction, int opt_zsnr, int* vparam, int* zsnr);
+/* Guidance limiters for cfg_scale well above 7 (not in the reference; the rules are in include/mlsd_kernels.h, both parity-unpinned): fields of the engine as the
+ * rescale's phi, set per generation; nothing is rebuilt or captured again, and with mode 0, or at cfg_scale <= 1, no new launch runs and the bytes are the plain mix's.
+ *   mode 1, dynamic thresholding: a = mimic (>= 1), b = percentile (0.5 .. 1).  Per latent channel the prediction at cfg_scale is centred on its plane mean, clamped
+ *     to t = max(largest |g - mean| at the mimic scale, the percentile of |g - mean| at cfg_scale) and shrunk into the mimic scale's range.  Four launches per mix:
+ *     plane means (2), selection (1), the mix.
+ *   mode 2, APG: a = eta (0 .. 1), b = norm (>= 0, 0 = no cap).  Per image the update cond - uncond is capped in norm and its component parallel to cond is scaled
+ *     by eta.  Three launches per mix.
+ * Where a mode is on, dxdt_finish runs the statistics on the raw outputs (of a tiled engine: the blended canvas) and mlsd_dxdt_limited; the Euler step is then not
+ * fused.  Composes with use_hipgraph, unet_split, ControlNet, FreeU, HyperTile, PAG and the hires fix.  Refused: another mode value (one limiter at a time), a limiter
+ * while a rescale phi > 0 is set, and a rescale while a limiter is set.
+ * guidance_limit_state: the mode, a, b, the limited mixes so far and the last mix's triples [B][4][3] (mean, t, r) or coefficients [B][2] (A, B); returns the number
+ * of floats written. */
+int mlis_amd_set_guidance_limit(MLIS_AmdCtx* S, int mode, float a, float b);
+int mlis_amd_guidance_limit_state(MLIS_AmdCtx* S, int* mode, float* a, float* b, int* n_evals, float* values, int max_values);
 /* VAE tiling (MLIS_OPT_VAE_TILE, src/vae.c:245-300,333-391): tile size in pixels (rounded up to 64; 0 = off).  Decode / encode then
  * run tile by tile through tile-sized plans; *_tile_prepare build them (NULL when tiling does not apply: TAE, or one tile covers all).
  * set_vae_tile with another size drops the tile plans AND the tile-sized buffers; the next prepare makes them for the new tile.

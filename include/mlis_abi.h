@@ -138,7 +138,7 @@ typedef enum {
 	 * generation returns the bytes it returned without them.  `auto` is what the model type says (sd2, tinyv: v) and what the checkpoint says: a tensor named "v_pred"
 	 * makes it v-prediction, one named "ztsnr" selects the rescaled sigma table -- the published checkpoints' marker convention as recalled, parity-unpinned; the
 	 * explicit values always win.  With zsnr the uniform schedule starts at sigma 4518.76 (the clamped last entry).  Not included: trailing / SGM timestep spacing, a
-	 * step window for the rescale, dynamic thresholding, APG, CFG++.  (A block of its own from 211.) */
+	 * step window for the rescale, CFG++ (dynamic thresholding, APG: mlis_amd_guidance_limit below).  (A block of its own from 211.) */
 	MLIS_OPT_AMD_CFG_RESCALE = 211,        /* "cfg_rescale" (float 0 .. 1, default 0 = off; front ends use 0.7): phi of the guidance rescale */
 	MLIS_OPT_AMD_PREDICTION = 212,         /* "prediction" (auto|eps|v or 0 .. 2, default auto) */
 	MLIS_OPT_AMD_ZSNR = 213                /* "zsnr" (auto|off|on or 0 .. 2, default auto; n|y are accepted for off|on) */
@@ -221,6 +221,24 @@ int mlis_amd_engine_builds(MLIS_Ctx* ctx);
 #define MLIS_AMD_VAE_ATTN_FLASH  1
 int mlis_amd_vae_attn(MLIS_Ctx* ctx, int mode);
 int mlis_amd_vae_attn_info(MLIS_Ctx* ctx, int* mode, int* plan_mode);
+/* Guidance limiters for cfg_scale well above 7, where the mix c cfg + u (1 - cfg) burns colours and contrast (neither is in the reference; both AS RECALLED,
+ * parity-unpinned; the rules in full: include/mlsd_kernels.h).  Not MLIS_Options: a call, handed to the engine before every pass, never part of the engine key.
+ *   DYNTHRESH, a = mimic scale (>= 1), b = percentile (0.5 .. 1; 1 = the maximum): dynamic thresholding as the "CFG scale fix" extension's default path -- per latent
+ *     channel, "AD" measure, "MEAN" start point, constant scales, interpolation 1: the prediction at cfg_scale is centred on its channel mean, clamped at the larger
+ *     of the mimic scale's largest deviation and the percentile of its own, and shrunk into the range the mimic scale would have had.
+ *   APG, a = eta (0 .. 1), b = norm (>= 0, 0 = no cap): "Eliminating Oversaturation and Artifacts of High Guidance Scales" (2024) without the momentum buffer: the
+ *     update cond - uncond is capped in norm per image and its component parallel to cond is scaled by eta.
+ * Both act on the raw UNet outputs, as cfg_rescale does, where cfg_scale > 1; elsewhere, and with OFF, no new launch runs.  Compose with use_hipgraph, unet_split,
+ * tiled diffusion (statistics of the blended canvas), ControlNet, FreeU, HyperTile, PAG and the hires fix (both passes).  Returns 1; MLIS_E_OPT_VALUE for a value out
+ * of range, for another mode (one limiter at a time), and together with cfg_rescale > 0 (here, or at mlis_generate when the option was set afterwards).  Not included:
+ * APG's momentum, the extension's scale schedulers and other measures, CFG++.
+ * mlis_amd_guidance_limit_info: the setting, and from the engine used last the limited mixes so far and the last mix's triples [B][4][3] (mean, t, r) or
+ * coefficients [B][2] (A, B), at most max_values floats; returns the number written (0 without an engine or before the first limited mix).  Pointers may be NULL. */
+#define MLIS_AMD_GLIMIT_OFF       0
+#define MLIS_AMD_GLIMIT_DYNTHRESH 1
+#define MLIS_AMD_GLIMIT_APG       2
+int mlis_amd_guidance_limit(MLIS_Ctx* ctx, int mode, float a, float b);
+int mlis_amd_guidance_limit_info(MLIS_Ctx* ctx, int* mode, float* a, float* b, int* n_evals, float* values, int max_values);
 /* ControlNet: evaluations of pass 0 / 1 of the last mlis_generate in which the ControlNet ran (a hires generation has two passes); -1 for a pass that did not run */
 int mlis_amd_control_evals(MLIS_Ctx* ctx, int pass);
 /* LoRA bookkeeping, cumulative like mlis_amd_engine_builds.  A change of the LoRA set or of a multiplier while engines or text towers are resident is applied

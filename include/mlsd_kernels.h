@@ -456,6 +456,45 @@ int    mlsd_guidance_blocks(int HW);
 size_t mlsd_guidance_scratch_bytes(int B, int HW);
 int mlsd_guidance_stats(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag, float phi, double* scratch, size_t scratch_bytes,
                         float* factor, void* stream);
+/* Guidance limiters for high cfg (csrc/hip/guidance_limit.hip; neither is in the reference, both parity-unpinned): dynamic thresholding -- the "CFG scale fix"
+ * extension's default path as recalled: per channel, "AD" measure, "MEAN" start point, constant scales, interpolation 1 -- and APG ("Eliminating Oversaturation and
+ * Artifacts of High Guidance Scales", 2024) as recalled from the paper, without its momentum buffer.  All entries read the RAW outputs eps NHWC [N][HW][ld] with the
+ * groups [cond B | uncond B | perturbed B (only read at pag != 0)], ld = 4 and the plan's padded stride alike; c, u, p are the elements of the three groups.
+ *   mix(s) = fadd(fmul(c, s), fmul(u, 1 - s));   g_cfg = mix(cfg),  g_mim = mix(mimic)
+ * plane_means: means[b][ch][2] (device, 2 B C floats) = the means of g_cfg and of g_mim over the HW pixels of plane (b, ch): the floats summed in double -- lanes,
+ *   waves, LDS, one store of the block's partial to scratch, (mlsd_guidance_blocks(HW), B) blocks, a rule of HW alone -- then one launch that adds a plane's partials
+ *   in block order, divides by HW and rounds once.  No global atomics, no block waits on another.
+ * plane_select: triple[b][ch][3] (device).  With a_i = fabs(fsub(g_cfg_i, mean_cfg)) and the same for g_mim:
+ *     m_ref = max_i a_mim_i;   q_ref = the p-quantile of a_cfg: pos = (double)p (HW - 1), lo = floor(pos), hi = min(lo + 1, HW - 1),
+ *     q_ref = (float)(a_(lo) + (pos - lo) (a_(hi) - a_(lo))) in double, a_(k) the k-th smallest; at p == 1 the maximum (no selection runs)
+ *     triple = { mean_cfg, t = max(m_ref, q_ref), r = (float)((double)m_ref / t) };  { mean_cfg, +inf, 1 } where t == 0, m_ref or q_ref is not finite, or HW == 1
+ *   One workgroup per plane, an exact MSB-first radix select on the bit patterns (four passes of 8 bits, 256-bin LDS histograms with integer atomics: the same bits
+ *   on every run).  The plane's keys are gathered once into LDS where HW * 4 <= mlsd_guidance_select_lds_limit (128 KiB: HW <= 32768); above it every pass forms
+ *   them again from eps.  select_lds_limit(bytes): sets the limit (capped at 128 KiB; negative: only asks) and returns the previous one.
+ * apg_coef: coef[b] = { A_b, B_b } (device, 2 B floats).  Per image over its C HW elements, in double, d = c - u:  S_dd = sum d^2, S_dc = sum d c, S_cc = sum c^2
+ *   (the reduction shape of plane_means);  s = norm > 0 ? min(1, norm / sqrt(S_dd)) : 1;  alpha = S_cc > 0 ? S_dc / S_cc : 0;
+ *   A_b = 1 + (cfg - 1) s (1 - (1 - eta) alpha),  B_b = -(cfg - 1) s, rounded once  -- so that A c + B u = c + (cfg - 1) s (d - (1 - eta) alpha c), the APG
+ *   prediction: the norm of d capped, its component parallel to c damped by eta.  { cfg, 1 - cfg } where a sum is not finite.
+ * dxdt_limited: the pixel-owning mix, with the forms of mlsd_dxdt_guided.  Per element, each operation rounded once:
+ *     mode MLSD_GLIMIT_DYNTHRESH, lim = the triples:  g = fadd(fmul(fmin(fmax(fsub(g_cfg, mean), -t), t), r), mean)
+ *     mode MLSD_GLIMIT_APG, lim = the coefficients:   g = fadd(fmul(c, A_b), fmul(u, B_b))
+ *     pag != 0: g = fadd(g, fmul(pag, fsub(c, p)));   dx = v(g), the v map of the guidance mix once, on the limited mix of the raw outputs (as with a rescale factor)
+ *   At cfg <= 1 there is nothing to limit: lim is not read and the call is mlsd_dxdt_guided without a factor, its bytes.  There is no fused Euler form.
+ * scratch: mlsd_guidance_limit_scratch_bytes(B, C, HW) bytes, 8-byte aligned (plane_means and apg_coef may share it).  Scalars go by value; nothing is rebuilt
+ * between launches.
+ * Refused before any launch: what mlsd_dxdt_guided refuses; by the three statistics also cfg <= 1 (no uncond group); mimic < 1, p outside 0.5 .. 1, eta outside
+ * 0 .. 1, norm < 0, any of them NaN or infinite; a NULL or undersized scratch, a NULL means / triple / coef; by dxdt_limited another mode, and a NULL lim at cfg > 1. */
+#define MLSD_GLIMIT_DYNTHRESH 1
+#define MLSD_GLIMIT_APG 2
+int    mlsd_guidance_select_lds_limit(int bytes);
+size_t mlsd_guidance_limit_scratch_bytes(int B, int C, int HW);
+int mlsd_guidance_plane_means(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float mimic, double* scratch, size_t scratch_bytes, float* means,
+                              void* stream);
+int mlsd_guidance_plane_select(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float mimic, float p, const float* means, float* triple, void* stream);
+int mlsd_guidance_apg_coef(const float* eps, int64_t ld, int B, int C, int HW, float cfg, float eta, float norm, double* scratch, size_t scratch_bytes, float* coef,
+                           void* stream);
+int mlsd_dxdt_limited(const float* eps, int64_t ld, const float* x_eval, float* dx, int B, int C, int HW, int mode, float cfg, float pag, const float* lim,
+                      int vparam, float c_out, float c_skip, void* stream);
 int mlsd_vec_axpy(float* out, const float* x, const float* d, float dt, int64_t n, void* stream);     /* out = x + d*dt (solvers.c:86,105,278) */
 int mlsd_solver_heun_corr(float* x, const float* dx, const float* d1, float dt, int64_t n, void* stream);   /* solvers.c:112-113 */
 int mlsd_solver_taylor3(float* x, const float* dx, float* dp1, float* dp2, float dt, float idtp, float f2, float f3,

@@ -338,6 +338,8 @@ static const char k_usage[] =
 "PAG:         --pag-scale F   (perturbed-attention guidance, 0 .. 20, 0 = off, 3 is the usual value; one more UNet row group per image)\n"
 "Guidance:    --cfg-rescale F   --prediction auto|eps|v   --zsnr auto|y|n   (guidance rescale 0 .. 1, 0 = off, 0.7 is the usual value; prediction type and\n"
 "             zero-terminal-SNR sigma table, auto = what the model type and the checkpoint's v_pred / ztsnr markers say)\n"
+"             --dyn-thresh MIMIC[:PERCENTILE]   --apg ETA[:NORM]   (limiters for --cfg-scale well above 7, one of them and not with --cfg-rescale: dynamic\n"
+"             thresholding towards the range of scale MIMIC >= 1, percentile 0.5 .. 1, default 1; APG with eta 0 .. 1 and a cap NORM on |cond - uncond|, default 0 = none)\n"
 "Sampling:    -S --seed N   -s --steps N   --method NAME   --scheduler NAME   --s-noise F   --s-ancestral F\n"
 "             --cfg-scale F   --clip-skip N   --f-t-ini F   --f-t-end F\n"
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";
@@ -345,6 +347,7 @@ static const char k_usage[] =
 typedef struct {
 	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens, *ctl_img;
 	double outscale;        /* upscale --outscale: 0 = not given */
+	int glimit;             /* --dyn-thresh / --apg: the MLIS_AMD_GLIMIT_* given so far */
 	MLIS_Ctx *ctx;
 } Cli;
 
@@ -373,6 +376,19 @@ static int cli_option(Cli* C, const char* name, const char* next)
 	if (!strcmp(name, "vae-attn")) {      /* not an option of the table: the call itself (include/mlis_abi.h) */
 		const int mode = !strcmp(next, "scores") ? MLIS_AMD_VAE_ATTN_SCORES : !strcmp(next, "flash") ? MLIS_AMD_VAE_ATTN_FLASH : -1;
 		if (mode < 0 || mlis_amd_vae_attn(C->ctx, mode) < 0) FAIL("option '--vae-attn %s': scores or flash", next);
+		return 1;
+	}
+	if (!strcmp(name, "dyn-thresh") || !strcmp(name, "apg")) {      /* A[:B], the call itself as --vae-attn */
+		const int mode = name[0] == 'd' ? MLIS_AMD_GLIMIT_DYNTHRESH : MLIS_AMD_GLIMIT_APG;
+		char *e = NULL;
+		const double a = strtod(next, &e);
+		double b = mode == MLIS_AMD_GLIMIT_DYNTHRESH ? 1.0 : 0.0;
+		int ok = e != next;
+		if (ok && *e == ':') { const char *q = e + 1; b = strtod(q, &e); ok = e != q; }
+		if (!ok || *e) FAIL("option '--%s %s': %s is needed", name, next, mode == MLIS_AMD_GLIMIT_APG ? "ETA[:NORM]" : "MIMIC[:PERCENTILE]");
+		if (C->glimit && C->glimit != mode) FAIL("option '--%s': --dyn-thresh and --apg exclude each other", name);
+		if (mlis_amd_guidance_limit(C->ctx, mode, (float)a, (float)b) < 0) FAIL("option '--%s %s': %s", name, next, mlis_errstr_get(C->ctx));
+		C->glimit = mode;
 		return 1;
 	}
 	if (mlis_option_set_str(C->ctx, name, next) < 0) FAIL("option '--%s %s': %s", name, next, mlis_errstr_get(C->ctx));

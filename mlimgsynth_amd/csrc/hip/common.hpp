@@ -34,6 +34,17 @@ int mlsd_check_launch(const char* what);
         }                                                                                   \
     } while (0)
 
+// ---- what every entry of the guidance mix refuses (guidance.hip, guidance_limit.hip): eps NHWC [N][HW][ld] with the row groups [cond B | uncond B at cfg > 1 |
+// perturbed B at pag != 0]; 0 when the arguments are good
+inline int guidance_args_check(const char* what, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag)
+{
+    if (!eps || B < 1 || C < 1 || HW < 1 || ld < C || !(pag >= 0.0f) || cfg != cfg)
+        return mlsd_set_error(-1, "%s: bad argument (B %d, C %d, HW %d, ld %lld, cfg %g, pag %g)", what, B, C, HW, (long long)ld, (double)cfg, (double)pag);
+    const long n = (long)B * C * HW, rows = (long)B * HW * (1 + (cfg > 1.0f ? 1 : 0) + (pag != 0.0f ? 1 : 0));
+    if (n >= (1L << 31) || rows * ld >= (1L << 31)) return mlsd_set_error(-1, "%s: more than 2^31 elements", what);
+    return 0;
+}
+
 // ---- elementwise launches: 256 threads per block, at most 4096 blocks, each thread striding over the elements
 inline unsigned nblk(long n) { long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 #define GRID_LOOP(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)

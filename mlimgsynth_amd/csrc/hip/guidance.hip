@@ -205,15 +205,8 @@ __global__ void gr_factor_kernel(const double* __restrict__ part, int nb, int B,
 }
 
 // ------------------------------------------------------------------ launching
-// the arguments every entry of this file shares; 0 when they are good
-int gr_check(const char* what, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag)
-{
-    if (!eps || B < 1 || C < 1 || HW < 1 || ld < C || !(pag >= 0.0f) || cfg != cfg)
-        return mlsd_set_error(-1, "%s: bad argument (B %d, C %d, HW %d, ld %lld, cfg %g, pag %g)", what, B, C, HW, (long long)ld, (double)cfg, (double)pag);
-    const long n = (long)B * C * HW, rows = (long)B * HW * (1 + (cfg > 1.0f ? 1 : 0) + (pag != 0.0f ? 1 : 0));
-    if (n >= (1L << 31) || rows * ld >= (1L << 31)) return mlsd_set_error(-1, "%s: more than 2^31 elements", what);
-    return 0;
-}
+// the arguments every entry of this file shares; 0 when they are good (common.hpp: guidance_limit.hip refuses the same)
+int gr_check(const char* what, const float* eps, int64_t ld, int B, int C, int HW, float cfg, float pag) { return guidance_args_check(what, eps, ld, B, C, HW, cfg, pag); }
 
 // the form rule.  x: the evaluation point (dxdt; read only with vparam) or the latent updated in place (EULER); out: dx or that latent
 template <bool EULER, bool RESCALED>

@@ -116,6 +116,16 @@ struct MLIS_AmdCtx {
 	size_t gr_part_bytes;
 	int gr_evals;               /* rescaled mixes since the engine was created */
 	int vparam_model;           /* the model type's own prediction type (mlis_amd_set_prediction with a negative value goes back to it) */
+	/* guidance limiters (mlis_amd_set_guidance_limit): dynamic thresholding or APG on the raw outputs, where cfg_scale > 1.  The buffers exist only once a mode was
+	 * set; like the rescale, none of it is in a plan. */
+	int limit_mode;             /* 0 off, MLSD_GLIMIT_DYNTHRESH, MLSD_GLIMIT_APG */
+	float mimic, percentile;    /* thresholding: the scale whose range is kept (>= 1), the quantile of |g - mean| (0.5 .. 1) */
+	float apg_eta, apg_norm;    /* APG: what is kept of the component parallel to cond (0 .. 1), the cap on |cond - uncond| per image (0: none) */
+	double *d_gl_part;          /* mlsd_guidance_limit_scratch_bytes(B, 4, hw) */
+	float *d_gl_means;          /* [B][4][2] plane means of the last thresholded mix */
+	float *d_gl_lim;            /* [B][4][3] its triples, or [B][2] the coefficients of the last APG mix */
+	size_t gl_part_bytes;
+	int gl_evals, gl_lim_mode;  /* limited mixes since the engine was created; the mode of the last one (whose values d_gl_lim holds) */
 };
 
 static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
@@ -130,6 +140,7 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	mlsd_free(S->d_gain);
 	mlsd_free(S->d_freeu);
 	mlsd_free(S->d_gr_part); mlsd_free(S->d_gr_factor);
+	mlsd_free(S->d_gl_part); mlsd_free(S->d_gl_means); mlsd_free(S->d_gl_lim);
 	if (S->dec_ctx) mlctx_destroy(S->dec_ctx);
 	if (S->enc_ctx) mlctx_destroy(S->enc_ctx);
 	if (S->dect_ctx) mlctx_destroy(S->dect_ctx);
@@ -755,6 +766,21 @@ static int guidance_args(MLIS_AmdCtx* S, const float* eps, int64_t ld, float* pa
 	return mlsd_guidance_stats(eps, ld, S->B, 4, S->hw, S->c.cfg_scale, *pag, S->cfg_rescale, S->d_gr_part, S->gr_part_bytes, S->d_gr_factor, S->stream) ? -1 : 1;
 }
 
+/* a guidance limiter runs where a mode is set and there is guidance to limit; elsewhere no new launch, and the plain mix's bytes */
+static int limit_on(const MLIS_AmdCtx* S) { return S->limit_mode && S->c.cfg_scale > 1; }
+
+/* the statistics of a limited mix on this evaluation's raw outputs (the blended canvas of a tiled engine: the whole image), into d_gl_lim; < 0 on error */
+static int limit_stats(MLIS_AmdCtx* S, const float* eps, int64_t ld)
+{
+	const float cfg = S->c.cfg_scale;
+	if (S->limit_mode == MLSD_GLIMIT_APG) {
+		if (mlsd_guidance_apg_coef(eps, ld, S->B, 4, S->hw, cfg, S->apg_eta, S->apg_norm, S->d_gl_part, S->gl_part_bytes, S->d_gl_lim, S->stream)) return -1;
+	} else if (mlsd_guidance_plane_means(eps, ld, S->B, 4, S->hw, cfg, S->mimic, S->d_gl_part, S->gl_part_bytes, S->d_gl_means, S->stream) ||
+			mlsd_guidance_plane_select(eps, ld, S->B, 4, S->hw, cfg, S->mimic, S->percentile, S->d_gl_means, S->d_gl_lim, S->stream)) return -1;
+	S->gl_evals++; S->gl_lim_mode = S->limit_mode;      /* (only once the launches were accepted: d_gl_lim holds this mode's values from here) */
+	return 1;
+}
+
 /* dx = guidance mix (+ v-param rescale) of the evaluation just enqueued */
 static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* dx)
 {
@@ -762,6 +788,11 @@ static int dxdt_finish(MLIS_AmdCtx* S, const float* x_eval, float sigma, float* 
 	const float *eps = eps_get(S, &ld), *factor;
 	const float c_skip = sigma / (sigma*sigma + 1), c_out = 1 / sqrt(sigma*sigma + 1);   /* unet.c:491-492 */
 	float pag;
+	if (limit_on(S)) {          /* (never together with the rescale: the setters refuse the pair) */
+		if (limit_stats(S, eps, ld) < 0) return -1;
+		return mlsd_dxdt_limited(eps, ld, x_eval, dx, S->B, 4, S->hw, S->limit_mode, S->c.cfg_scale, S->pag ? S->pag_scale : 0, S->d_gl_lim, S->unet_p.vparam, c_out,
+				c_skip, S->stream) ? -1 : 1;
+	}
 	if (guidance_args(S, eps, ld, &pag, &factor) < 0) return -1;
 	return mlsd_dxdt_guided(eps, ld, x_eval, dx, S->B, 4, S->hw, S->c.cfg_scale, pag, factor, S->unet_p.vparam, c_out, c_skip, S->stream) ? -1 : 1;
 }
@@ -854,7 +885,8 @@ static int denoise_body(MLIS_AmdCtx* S, const uint64_t* seeds, int* retry_wanted
 		switch (method) {
 		case SOLVER_METHOD_EULER: {                                           /* :82-88 */
 			if (unet_eval(S, S->d_x, t0, k_prefetch) < 0) return -1;
-			if (!P->vparam) {   /* fused: CFG mix, x += dx*dt and the ancestral noise of sampling.c:170-172 in one launch */
+			/* (a limited mix has no fused form: it goes through dxdt_finish + mlsd_vec_axpy here and mlsd_noise_add_s below, the same bits as a fused step would give) */
+			if (!P->vparam && !limit_on(S)) {   /* fused: CFG mix, x += dx*dt and the ancestral noise of sampling.c:170-172 in one launch */
 				int64_t ld = 0;
 				const float *eps = eps_get(S, &ld), *factor;
 				const float *nz = anc_noise ? noise_draw(S, S->k_draw) : NULL;
@@ -1148,6 +1180,7 @@ MLB_API int mlis_amd_set_cfg_rescale(MLIS_AmdCtx* S, float phi)
 {
 	if (!S) return fail("mlis_amd_set_cfg_rescale: no engine");
 	if (!(phi >= 0 && phi <= 1)) return mlsd_set_error(-1, "guidance rescale %g: 0 .. 1", phi);
+	if (phi > 0 && S->limit_mode) return mlsd_set_error(-1, "guidance rescale %g together with a guidance limiter: one of them", phi);
 	if (phi > 0 && !S->d_gr_part) {
 		const size_t nb = mlsd_guidance_scratch_bytes(S->B, S->hw);
 		if (mlsd_malloc((void**)&S->d_gr_part, nb) || mlsd_malloc((void**)&S->d_gr_factor, (size_t)S->B * 4)) return -1;
@@ -1171,6 +1204,47 @@ MLB_API int mlis_amd_guidance_info(MLIS_AmdCtx* S, int* vparam, int* zsnr, float
 	if (!factors || max_factors < 1 || !S->gr_evals || !S->d_gr_factor) return 0;
 	const int n = max_factors < S->B ? max_factors : S->B;
 	if (mlsd_memcpy(factors, S->d_gr_factor, (size_t)n * 4, 1, S->stream) || mlsd_stream_sync(S->stream)) return -1;
+	return n;
+}
+
+/* ------------------------------------------------------------------ guidance limiters
+ * mode 0: off.  MLSD_GLIMIT_DYNTHRESH: a = mimic (>= 1), b = percentile (0.5 .. 1).  MLSD_GLIMIT_APG: a = eta (0 .. 1), b = norm (>= 0, 0: no cap).  Fields of the
+ * engine, as the rescale's phi: set per generation, nothing is rebuilt or captured again, and the mix reads them by value.  One limiter at a time (any other mode
+ * value is refused), and none beside a rescale: all three answer the same defect and each measures the prediction the others would change. */
+MLB_API int mlis_amd_set_guidance_limit(MLIS_AmdCtx* S, int mode, float a, float b)
+{
+	if (!S) return fail("mlis_amd_set_guidance_limit: no engine");
+	if (mode == 0) { S->limit_mode = 0; return 1; }
+	if (mode == MLSD_GLIMIT_DYNTHRESH) {
+		if (!(a >= 1 && a < INFINITY) || !(b >= 0.5f && b <= 1)) return mlsd_set_error(-1, "dynamic thresholding: mimic %g (>= 1), percentile %g (0.5 .. 1)", a, b);
+	} else if (mode == MLSD_GLIMIT_APG) {
+		if (!(a >= 0 && a <= 1) || !(b >= 0 && b < INFINITY)) return mlsd_set_error(-1, "APG: eta %g (0 .. 1), norm %g (>= 0)", a, b);
+	} else return mlsd_set_error(-1, "guidance limit mode %d: 0 off, 1 dynamic thresholding, 2 APG (one at a time)", mode);
+	if (S->cfg_rescale > 0) return mlsd_set_error(-1, "a guidance limiter together with guidance rescale %g: one of them", S->cfg_rescale);
+	if (!S->d_gl_part) {
+		const size_t nb = mlsd_guidance_limit_scratch_bytes(S->B, 4, S->hw);
+		if (mlsd_malloc((void**)&S->d_gl_part, nb) || mlsd_malloc((void**)&S->d_gl_means, (size_t)S->B * 8 * 4) || mlsd_malloc((void**)&S->d_gl_lim, (size_t)S->B * 12 * 4))
+			return -1;
+		S->gl_part_bytes = nb;
+	}
+	S->limit_mode = mode;
+	if (mode == MLSD_GLIMIT_DYNTHRESH) { S->mimic = a; S->percentile = b; } else { S->apg_eta = a; S->apg_norm = b; }
+	return 1;
+}
+
+/* the mode and its two parameters, the limited mixes so far, and, where the last one ran in this mode, its triples ([B][4][3]: mean, t, r) or coefficients ([B][2]: A, B) -- at
+ * most max_values floats; the stream is synchronised for them.  Returns the number of floats written: 0 before the first limited mix. */
+MLB_API int mlis_amd_guidance_limit_state(MLIS_AmdCtx* S, int* mode, float* a, float* b, int* n_evals, float* values, int max_values)
+{
+	if (!S) return -1;
+	const int apg = S->limit_mode == MLSD_GLIMIT_APG;
+	if (mode) *mode = S->limit_mode;
+	if (a) *a = apg ? S->apg_eta : S->limit_mode ? S->mimic : 0;
+	if (b) *b = apg ? S->apg_norm : S->limit_mode ? S->percentile : 0;
+	if (n_evals) *n_evals = S->gl_evals;
+	if (!values || max_values < 1 || !S->limit_mode || S->gl_lim_mode != S->limit_mode || !S->d_gl_lim) return 0;
+	const int all = S->B * (apg ? 2 : 12), n = max_values < all ? max_values : all;
+	if (mlsd_memcpy(values, S->d_gl_lim, (size_t)n * 4, 1, S->stream) || mlsd_stream_sync(S->stream)) return -1;
 	return n;
 }
 

@@ -59,6 +59,7 @@ struct MLIS_Ctx {
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int vae_attn;                           /* mlis_amd_vae_attn: MLIS_AMD_VAE_ATTN_*, handed to the engine before every pass (never part of the engine key) */
+	int glimit_mode; float glimit_a, glimit_b;      /* mlis_amd_guidance_limit: MLIS_AMD_GLIMIT_* and its two parameters, handed to the engine per generation (never part of the engine key) */
 	float cfg_rescale;                      /* MLIS_OPT_AMD_CFG_RESCALE: phi of the guidance rescale, handed to the engine per generation (never part of the engine key) */
 	int prediction, zsnr;                   /* MLIS_OPT_AMD_PREDICTION (0 auto, 1 eps, 2 v) / MLIS_OPT_AMD_ZSNR (0 auto, 1 off, 2 on): resolved per generation (guidance_resolve) */
 	int ckpt_v_pred, ckpt_ztsnr;            /* the checkpoint's marker tensors (mlts_markers); 0 for the synthetic models */
@@ -325,6 +326,28 @@ MLB_API int mlis_amd_vae_attn_info(MLIS_Ctx* S, int* mode, int* plan_mode)
 	if (mode) *mode = S->vae_attn;
 	if (plan_mode) *plan_mode = S->eng ? mlis_amd_vae_attn_mode(S->eng) : -1;
 	return 1;
+}
+MLB_API int mlis_amd_guidance_limit(MLIS_Ctx* S, int mode, float a, float b)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (mode == MLIS_AMD_GLIMIT_OFF) { S->glimit_mode = 0; return 1; }
+	if (mode == MLIS_AMD_GLIMIT_DYNTHRESH) {
+		if (!(a >= 1 && a < INFINITY) || !(b >= 0.5f && b <= 1)) return api_error(S, MLIS_E_OPT_VALUE, "dynamic thresholding: mimic %g (>= 1), percentile %g (0.5 .. 1)", a, b);
+	} else if (mode == MLIS_AMD_GLIMIT_APG) {
+		if (!(a >= 0 && a <= 1) || !(b >= 0 && b < INFINITY)) return api_error(S, MLIS_E_OPT_VALUE, "APG: eta %g (0 .. 1), norm %g (>= 0)", a, b);
+	} else return api_error(S, MLIS_E_OPT_VALUE, "guidance limit: mode %d (0 off, 1 dynamic thresholding, 2 APG; one at a time)", mode);
+	if (S->cfg_rescale > 0) return api_error(S, MLIS_E_OPT_VALUE, "guidance limit together with cfg_rescale %g: one of them", S->cfg_rescale);
+	S->glimit_mode = mode; S->glimit_a = a; S->glimit_b = b;      /* (the engines learn it in generate_pass, before their next pass) */
+	return 1;
+}
+MLB_API int mlis_amd_guidance_limit_info(MLIS_Ctx* S, int* mode, float* a, float* b, int* n_evals, float* values, int max_values)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (mode) *mode = S->glimit_mode;
+	if (a) *a = S->glimit_mode ? S->glimit_a : 0;
+	if (b) *b = S->glimit_mode ? S->glimit_b : 0;
+	if (n_evals) *n_evals = 0;
+	return S->eng ? mlis_amd_guidance_limit_state(S->eng, NULL, NULL, NULL, n_evals, values, max_values) : 0;
 }
 MLB_API int mlis_amd_lora_stats(MLIS_Ctx* S, int* n_restored, int* n_patched, int* n_cold_merges)
 {
@@ -1896,6 +1919,8 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
 	if (S->pag_scale > 0) ADD(", PAG: %g", S->pag_scale);
 	if (S->cfg_rescale > 0) ADD(", CFG rescale: %g", S->cfg_rescale);
+	if (S->glimit_mode == MLIS_AMD_GLIMIT_DYNTHRESH && S->cfg_scale > 1) ADD(", Dynamic thresholding: %g/%g", S->glimit_a, S->glimit_b);
+	if (S->glimit_mode == MLIS_AMD_GLIMIT_APG && S->cfg_scale > 1) ADD(", APG: %g/%g", S->glimit_a, S->glimit_b);
 	{	/* the prediction type and the schedule, where they are not the model type's own */
 		int vp = 0, zs = 0, vp0 = 0;
 		if (guidance_resolve(S, &vp, &zs) > 0 && mlis_amd_prediction_resolve(S->mname, 0, 0, 0, 0, &vp0, NULL) > 0) {
@@ -1983,8 +2008,11 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	if (S->pag_scale > 0 && mlis_amd_set_pag(S->eng, S->pag_scale) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	{	/* prediction type, sigma table and guidance rescale: fields of the engine, set for every pass (a resident engine may have served other settings) */
 		int vp = 0, zs = 0;
+		/* (the engine refuses the pair, as mlis_generate has: whichever is off is handed over first) */
+		if (!S->glimit_mode && mlis_amd_set_guidance_limit(S->eng, 0, 0, 0) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 		if (guidance_resolve(S, &vp, &zs) < 0 || mlis_amd_set_prediction(S->eng, vp, zs) < 0 || mlis_amd_set_cfg_rescale(S->eng, S->cfg_rescale) < 0)
 			return api_error_lib(S, MLIS_E_UNKNOWN);
+		if (S->glimit_mode && mlis_amd_set_guidance_limit(S->eng, S->glimit_mode, S->glimit_a, S->glimit_b) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
 	}
 	if (mlis_amd_set_cond(S->eng, S->cond.d, tensor_good(&S->label) ? S->label.d : NULL, S->cfg_scale > 1 ? S->ncond.d : NULL,
 			(S->cfg_scale > 1 && tensor_good(&S->nlabel)) ? S->nlabel.d : NULL) < 0) return api_error_lib(S, MLIS_E_UNKNOWN);
@@ -2137,6 +2165,8 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	if (inpaint_on(S)) { int c = inpaint_check(S); if (c < 0) return c; }
 	if (hires_on(S) && S->hires_use_model && str_empty(S->path_upscale))
 		return api_error(S, MLIS_E_OPT_VALUE, "hires_use_model is set but no upscale_model");
+	if (S->glimit_mode && S->cfg_rescale > 0)      /* (mlis_amd_guidance_limit refuses the pair itself; here the option came afterwards) */
+		return api_error(S, MLIS_E_OPT_VALUE, "guidance limit together with cfg_rescale %g: one of them", S->cfg_rescale);
 	int r = mlis_setup(S); if (r < 0) return r;
 	const int B = S->n_batch > 0 ? S->n_batch : 1;
 	if (B > MAX_IMAGES) return api_error(S, MLIS_E_OPT_VALUE, "batch size > %d not supported", MAX_IMAGES);

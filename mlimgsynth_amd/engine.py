@@ -502,6 +502,8 @@ def _proto2():
     l.mlis_amd_set_prediction.argtypes = [vp, c_int, c_int]
     l.mlis_amd_set_cfg_rescale.argtypes = [vp, c_f]
     l.mlis_amd_guidance_info.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), FP, FP, FP, ctypes.POINTER(c_int), FP, c_int]
+    l.mlis_amd_set_guidance_limit.argtypes = [vp, c_int, c_f, c_f]
+    l.mlis_amd_guidance_limit_state.argtypes = [vp, ctypes.POINTER(c_int), FP, FP, ctypes.POINTER(c_int), FP, c_int]
     l._proto2_done = True
     return l
 
@@ -541,6 +543,26 @@ def guidance_info(engine, n_batch):
     if r < 0:
         check1(r, "mlis_amd_guidance_info")
     return dict(vparam=v.value, zsnr=z.value, sigma_min=smin.value, sigma_max=smax.value, cfg_rescale=phi.value, n_evals=n.value, factors=fac[:r].copy())
+
+
+GLIMIT = {"off": 0, "dynthresh": 1, "apg": 2}
+
+
+def guidance_limit_info(engine, n_batch):
+    """mlis_amd_guidance_limit_state of an engine handle as a dict (Generator.guidance_limit_info, MLImgSynth.guidance_limit_info): mode "off" | "dynthresh" | "apg",
+    its parameters under their names, n_evals (limited mixes so far) and values: float32 [B][4][3] (mean, t, r per plane) or [B][2] (A, B per image) of the last
+    limited mix, empty before one"""
+    m, n = c_int(), c_int()
+    a, b = c_f(), c_f()
+    val = np.zeros(max(int(n_batch), 1) * 12, np.float32)
+    r = _proto2().mlis_amd_guidance_limit_state(engine, ctypes.byref(m), ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), fptr(val), val.size)
+    if r < 0:
+        check1(r, "mlis_amd_guidance_limit_state")
+    mode = {v: k for k, v in GLIMIT.items()}[m.value]
+    out = dict(mode=mode, n_evals=n.value, values=val[:r].reshape((-1, 2) if mode == "apg" else (-1, 4, 3)).copy())
+    if mode != "off":
+        out.update(dict(eta=a.value, norm=b.value) if mode == "apg" else dict(mimic=a.value, percentile=b.value))
+    return out
 
 
 def vae_tile_walk(full, tile_px, unit, margin):
@@ -739,6 +761,15 @@ class Generator:
         f.argtypes = [vp, FP, ctypes.c_size_t]
         check1(f(self.h, fptr(out), out.nbytes), "mlis_amd_last_rows")
         return out
+
+    def set_guidance_limit(self, mode="off", mimic=7.0, percentile=1.0, eta=0.0, norm=0.0):
+        """mlis_amd_set_guidance_limit: "off", "dynthresh" (mimic >= 1, percentile 0.5 .. 1) or "apg" (eta 0 .. 1, norm >= 0, 0 = no cap); acts where cfg_scale > 1"""
+        m = GLIMIT.get(mode, mode)
+        a, b = (eta, norm) if m == 2 else (mimic, percentile)
+        check1(_proto2().mlis_amd_set_guidance_limit(self.h, int(m), float(a), float(b)), "mlis_amd_set_guidance_limit")
+
+    def guidance_limit_info(self):
+        return guidance_limit_info(self.h, self.cfg.n_batch)
 
     def guidance_info(self):
         """dict: vparam, zsnr, sigma_min, sigma_max, cfg_rescale, n_evals (rescaled mixes so far), factors (float32 [B] of the last rescaled mix; empty before one)"""

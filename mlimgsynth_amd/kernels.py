@@ -408,6 +408,45 @@ def guidance_stats(eps, ld, B, C, HW, cfg, pag, phi, scratch, scratch_bytes, fac
     check(f(vp(eps), ld, B, C, HW, cfg, pag, phi, vp(scratch), scratch_bytes, vp(factor), vp(stream)), "mlsd_guidance_stats")
 
 
+def guidance_select_lds_limit(nbytes=-1):
+    """mlsd_guidance_select_lds_limit: the largest plane (HW * 4 bytes) whose keys the selection keeps in LDS; sets it where nbytes >= 0 and returns the previous one"""
+    return int(lib().mlsd_guidance_select_lds_limit(int(nbytes)))
+
+
+def guidance_limit_scratch_bytes(B, C, HW):
+    f = lib().mlsd_guidance_limit_scratch_bytes
+    f.restype, f.argtypes = ctypes.c_size_t, [c_int, c_int, c_int]
+    return int(f(int(B), int(C), int(HW)))
+
+
+def guidance_plane_means(eps, ld, B, C, HW, cfg, mimic, scratch, scratch_bytes, means, stream=None):
+    """mlsd_guidance_plane_means: means [B][C][2] = the plane means of the cfg and of the mimic mix of eps NHWC [2B..][HW][ld] (raw outputs; device pointers)"""
+    f = lib().mlsd_guidance_plane_means
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, ctypes.c_size_t, vp, vp]
+    check(f(vp(eps), ld, B, C, HW, cfg, mimic, vp(scratch), scratch_bytes, vp(means), vp(stream)), "mlsd_guidance_plane_means")
+
+
+def guidance_plane_select(eps, ld, B, C, HW, cfg, mimic, p, means, triple, stream=None):
+    """mlsd_guidance_plane_select: triple [B][C][3] = (mean_cfg, t, r) of dynamic thresholding per plane, the p-quantile by an exact radix select (device pointers)"""
+    f = lib().mlsd_guidance_plane_select
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp, vp]
+    check(f(vp(eps), ld, B, C, HW, cfg, mimic, p, vp(means), vp(triple), vp(stream)), "mlsd_guidance_plane_select")
+
+
+def guidance_apg_coef(eps, ld, B, C, HW, cfg, eta, norm, scratch, scratch_bytes, coef, stream=None):
+    """mlsd_guidance_apg_coef: coef [B][2] = (A, B) of APG per image, so that the prediction is A cond + B uncond (device pointers)"""
+    f = lib().mlsd_guidance_apg_coef
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, ctypes.c_size_t, vp, vp]
+    check(f(vp(eps), ld, B, C, HW, cfg, eta, norm, vp(scratch), scratch_bytes, vp(coef), vp(stream)), "mlsd_guidance_apg_coef")
+
+
+def dxdt_limited(eps, ld, x_eval, dx, B, C, HW, mode, cfg, pag, lim, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
+    """mlsd_dxdt_limited: dx = the limited mix of the raw outputs (mode 1: lim = triples, 2: lim = coefficients), PAG, then the v map with vparam (device pointers)"""
+    f = lib().mlsd_dxdt_limited
+    f.argtypes = [vp, c_i64, vp, vp, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, vp, c_int, ctypes.c_float, ctypes.c_float, vp]
+    check(f(vp(eps), ld, vp(x_eval), vp(dx), B, C, HW, int(mode), cfg, pag, vp(lim), int(vparam), c_out, c_skip, vp(stream)), "mlsd_dxdt_limited")
+
+
 def dxdt_rescaled(eps, ld, x_eval, dx, B, C, HW, cfg, pag, factor, vparam=0, c_out=1.0, c_skip=0.0, stream=None):
     """mlsd_dxdt_rescaled: dx = guided mix of the raw outputs * factor[b], then the v map with vparam (device pointers)"""
     f = lib().mlsd_dxdt_rescaled

@@ -86,6 +86,9 @@ _PROTOTYPES = {
     "mlis_mask_encode": (_I, [_V, _TP, _TP, _I]), "mlis_text_tokenize": (_I, [_V, _S, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), _I]),
     "mlis_tensor_resize": (None, [_TP, _I, _I, _I, _I]), "mlis_tensor_free": (None, [_TP]),
     "mlis_amd_tensor_resample": (_I, [_V, _TP, _TP, _I, _I, _I]), "mlis_amd_engine_builds": (_I, [_V]),
+    "mlis_amd_guidance_limit": (_I, [_V, _I, ctypes.c_float, ctypes.c_float]),
+    "mlis_amd_guidance_limit_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I),
+                                          ctypes.POINTER(ctypes.c_float), _I]),
     "mlis_amd_vae_attn": (_I, [_V, _I]), "mlis_amd_vae_attn_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -487,6 +490,33 @@ class MLImgSynth:
             return None
         from . import engine as E
         return E.guidance_info(e, 64)      # (room for the largest batch; the engine writes its own B factors)
+
+    # ---- guidance limiters for high cfg_scale
+    GLIMIT = {"off": 0, "dynthresh": 1, "apg": 2}
+
+    def guidance_limit_set(self, mode="off", mimic=7.0, percentile=1.0, eta=0.0, norm=0.0):
+        """mode "dynthresh": dynamic thresholding towards the range of scale `mimic` (>= 1), clamping at the `percentile` (0.5 .. 1) of each channel's deviations;
+        "apg": adaptive projected guidance, `eta` (0 .. 1) of the update's component parallel to cond and a cap `norm` (0 = none) on |cond - uncond|; "off".  One at
+        a time and not with cfg_rescale; acts where cfg_scale > 1.  Persists across generations and builds no engine."""
+        if mode not in self.GLIMIT:
+            raise ValueError("guidance limit: 'off', 'dynthresh' or 'apg', not %r" % (mode,))
+        a, b = (eta, norm) if mode == "apg" else (mimic, percentile)
+        if self._lib.mlis_amd_guidance_limit(self._ctx, self.GLIMIT[mode], float(a), float(b)) < 0:
+            raise ValueError("guidance limit: %s" % self.errstr_get())
+
+    def guidance_limit_info(self):
+        """dict: mode, its parameters under their names, n_evals (limited mixes of the engine used last) and values (that engine's last triples [B][4][3] =
+        mean, t, r, or coefficients [B][2] = A, B; empty before a limited mix)"""
+        m, n, a, b = _I(), _I(), ctypes.c_float(), ctypes.c_float()
+        val = (ctypes.c_float * (64 * 12))()
+        r = self._lib.mlis_amd_guidance_limit_info(self._ctx, ctypes.byref(m), ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), val, len(val))
+        if r < 0:
+            raise RuntimeError("Failed to read the guidance limit: %s" % self.errstr_get())
+        mode = {v: k for k, v in self.GLIMIT.items()}[m.value]
+        out = dict(mode=mode, n_evals=n.value, values=[val[i] for i in range(r)])
+        if mode != "off":
+            out.update(dict(eta=a.value, norm=b.value) if mode == "apg" else dict(mimic=a.value, percentile=b.value))
+        return out
 
     def tensor_resample(self, tensor, w, h, mode=MLIS_AMD_RESAMPLE_BILINEAR):   # noqa: F821
         "Resample every plane of a tensor to w x h on the GPU (MLIS_AMD_RESAMPLE_*); edges wrap along the axes of the tiling option."

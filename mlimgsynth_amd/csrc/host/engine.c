@@ -16,119 +16,12 @@
  *     generate (mlblock.c:266-292) or per half-graph (--unet-split, unet.c:390-458).
  */
 #define _GNU_SOURCE       /* sched_getaffinity, CPU_COUNT */
-#include "mlblock_int.h"
-#include "mlimgsynth_amd.h"
+#include "engine_int.h"
 #include <math.h>
 #include <pthread.h>
 #include <sched.h>
 #include <stdio.h>
 #include <unistd.h>
-
-
-#define MAX_STEPS 1001     /* the public option STEPS accepts 0..1000 like the reference (mlimgsynth_options_set.c.h); buffers that follow the step count are sized in ensure_steps */
-#define MAX_BATCH 64
-#define MAX_DRAWS (2 * MAX_STEPS + 2)
-#define N_TMP 2
-
-struct MLIS_AmdCtx {
-	MLIS_AmdConfig c;
-	char model[16];
-	void* stream;
-	UnetParams unet_p;
-	VaeParams vae_p;
-	int lw, lh, hw, B, N;
-	MLCtx *unet_ctx, *dec_ctx, *enc_ctx;
-	int tiling;                 /* seamless tiling: mlctx_set_conv_wrap mode of the UNet, decoder and encoder plans (0 none, 1 x, 2 y, 3 xy) */
-	UnetState unet;
-	MLTensor *t_lat_dec, *t_img_enc;
-	/* device state */
-	float *d_x;                 /* latent [B][4][hw] NCHW fp32 */
-	float *d_xsave;             /* copy of a caller-given initial latent while the denoising loop may have to be re-run (hand-off retry) */
-	int n_handoff_retries;      /* denoise / decode / encode passes re-run on the hand-off-free plan after a timed-out in-launch hand-off */
-	float *d_xin;               /* what the UNet plan reads (1 MB d2d copy per evaluation; keeps the plan independent of the solver) */
-	float *d_dx;                /* dxdt */
-	float *d_tmp[N_TMP];        /* solver state vectors (solver_tmp_get, solvers.c:54-76) */
-	float *d_x0, *d_lmask;      /* in-painting: original latent, latent mask [hw] */
-	float *d_img;               /* image  [B][3][H][W] fp32 */
-	float *d_img_in;            /* encoder input image (NCHW fp32 [B][3][H][W], [0,1]) */
-	float *d_cin;               /* [B] current c_in (read by the UNet input conversion) */
-	float *d_noise;             /* [MAX draws][B][4*hw] */
-	float *h_noise;             /* pinned, same shape */
-	void *up_stream;            /* the draws are uploaded on a stream of their own (a 1 MB copy queued on the compute stream waits behind the copy engine's current job:
-	                             * with streamed weights that is a 500 MB upload, 9 ms of an 80 ms evaluation); ev_draw[k] orders draw k before its consumer */
-	void **ev_draw; int n_ev_draw;
-	int32_t *d_nan;
-	void *ev[2 * MAX_STEPS][2];
-	int n_ev;
-	float last_unet_ms;
-	int last_nfe, last_n_step;
-	int cond_set, have_init_latent, have_lmask;
-	int own_stream;
-	RngPhilox rng[MAX_BATCH];
-	int cap_steps;
-	int n_draw_max, n_draw_gen, k_draw;  /* noise draws of the current denoise call: planned / generated so far / consumed so far */
-	int i_eval;
-	mlis_amd_progress_fn cb; void* cb_user;
-	/* VAE tiling (MLIS_OPT_VAE_TILE; src/vae.c:245-300,333-391): tile-sized plans, built on first use */
-	int vae_tile, tl_w, tl_h, ti_w, ti_h;             /* option (pixels); latent / image tile size of the decode and encode plans */
-	MLCtx *dect_ctx, *enct_ctx;
-	int vae_attn;               /* mlis_amd_set_vae_attn: the mid-block attention of the KL-VAE plans (mlctx_set_vae_attn), full-size and tile-sized alike */
-	MLTensor *t_lat_dect, *t_img_enct;
-	float *d_lat_tile, *d_img_tile, *d_imgin_tile, *d_mom_tile, *d_mom;
-	size_t tile_bytes[4];                             /* allocated bytes of d_lat_tile, d_img_tile, d_imgin_tile, d_mom_tile: they follow the tile size */
-	int n_tile_evals[2];                              /* tile plan evaluations of the last tiled decode / encode */
-	/* tiled diffusion (mlis_amd_create_tiled_packed): the UNet plan has the size of one window (times `pack` in the batch), lw x lh above is the canvas */
-	int n_win;                  /* windows per evaluation; 0: the plan takes the whole latent */
-	int win_w, win_h, win_ox, win_oy;       /* window extent and overlap per axis, latent pixels */
-	int tile_px, tile_overlap_px;           /* as asked for (pixels, square): infotext, engine key */
-	int n_win_x, n_win_y, *win_xs, *win_ys; /* starts per axis (mlis_amd_window_starts); window j = (xs[j % n_win_x], ys[j / n_win_x]) */
-	int pack, n_eval;           /* windows per plan evaluation (mlis_amd_tile_pack; 0: not tiled) and plan evaluations per UNet evaluation */
-	int PB, PN;                 /* images and rows of the UNet plan: B and N, times pack when tiled */
-	float *d_eps_canvas;        /* blended UNet output NHWC [N][hw][4] */
-	float *d_wsum;              /* [hw] sum of the blend weights of the windows covering a pixel */
-	/* ControlNet (MLIS_AmdConfig.control): the hint plan runs once per control image at the canvas's pixel size, the ControlNet plan before the UNet plan in every
-	 * controlled evaluation, on the UNet plan's inputs; the UNet plan was built with the residuals' addresses and reads its gain from d_gain */
-	MLCtx *ctl_ctx, *hint_ctx;
-	ControlState ctl;
-	UnetControl ctl_k;
-	MLTensor *t_hint_img;
-	float *d_gain;              /* [1] gain of the evaluation being enqueued: the strength, or 0 (outside the step window, no image, strength 0) */
-	int ctl_image;              /* a control image is set: the hint embedding is current */
-	uint64_t ctl_tag;           /* the caller's mark on that image (mlis_amd_control_tag_set) */
-	float ctl_strength, ctl_start, ctl_end;
-	int ctl_step_on;            /* the current step lies in the window (mlis_amd_control_active); mlis_amd_dxdt has no step: always */
-	int ctl_evals;              /* evaluations of the last denoise / dxdt in which the ControlNet plan ran */
-	/* FreeU (MLIS_AMD_CONTROL_FREEU): the UNet plan was built with the address of d_freeu; mlis_amd_set_freeu writes the four floats */
-	UnetFreeU fu;
-	float *d_freeu;             /* [4] b1, b2, s1, s2; all 1 (the plan's FreeU passes copy) until they are set */
-	float freeu_f[4];
-	/* perturbed-attention guidance (MLIS_AMD_CONTROL_PAG): the UNet plan carries a third row group, [cond | uncond | perturbed] (mlis_amd_eval_rows), whose middle-block
-	 * self-attentions are the identity (mlctx_set_pag); dxdt_finish and the fused Euler step mix it in with pag_scale, a by-value kernel argument */
-	int pag;                    /* the flag */
-	float pag_scale;            /* 0 .. 20 (mlis_amd_set_pag); 0: the plain mix, the perturbed rows are computed and not read */
-	int CN;                     /* rows of the ControlNet plan: PN without the perturbed group (it is never perturbed; the UNet plan's sums hand that group the cond residuals) */
-	int ht_px, ht_depth;        /* HyperTile (MLIS_AMD_CONTROL_HYPERTILE): tile in pixels (0: off) and deepest tiled level, given to the UNet and ControlNet plans before they are built */
-	/* guidance rescale (mlis_amd_set_cfg_rescale): the mix multiplies the guided prediction by a per-image factor (mlsd_guidance_stats).  The buffers exist only once
-	 * a phi > 0 was set; the prediction type and the sigma table (mlis_amd_set_prediction) live in unet_p (vparam, zsnr).  None of it is in a plan. */
-	float cfg_rescale;          /* phi, 0 .. 1; 0: the plain mix kernels */
-	double *d_gr_part;          /* [B][mlsd_guidance_blocks(hw)][4] partial sums */
-	float *d_gr_factor;         /* [B] the factors of the last rescaled mix */
-	size_t gr_part_bytes;
-	int gr_evals;               /* rescaled mixes since the engine was created */
-	int vparam_model;           /* the model type's own prediction type (mlis_amd_set_prediction with a negative value goes back to it) */
-	/* guidance limiters (mlis_amd_set_guidance_limit): dynamic thresholding or APG on the raw outputs, where cfg_scale > 1.  The buffers exist only once a mode was
-	 * set; like the rescale, none of it is in a plan. */
-	int limit_mode;             /* 0 off, MLSD_GLIMIT_DYNTHRESH, MLSD_GLIMIT_APG */
-	float mimic, percentile;    /* thresholding: the scale whose range is kept (>= 1), the quantile of |g - mean| (0.5 .. 1) */
-	float apg_eta, apg_norm;    /* APG: what is kept of the component parallel to cond (0 .. 1), the cap on |cond - uncond| per image (0: none) */
-	double *d_gl_part;          /* mlsd_guidance_limit_scratch_bytes(B, 4, hw) */
-	float *d_gl_means;          /* [B][4][2] plane means of the last thresholded mix */
-	float *d_gl_lim;            /* [B][4][3] its triples, or [B][2] the coefficients of the last APG mix */
-	size_t gl_part_bytes;
-	int gl_evals, gl_lim_mode;  /* limited mixes since the engine was created; the mode of the last one (whose values d_gl_lim holds) */
-};
-
-static int fail(const char* msg) { return mlsd_set_error(-1, "%s", msg); }
 
 MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 {
@@ -141,11 +34,8 @@ MLB_API void mlis_amd_destroy(MLIS_AmdCtx* S)
 	mlsd_free(S->d_freeu);
 	mlsd_free(S->d_gr_part); mlsd_free(S->d_gr_factor);
 	mlsd_free(S->d_gl_part); mlsd_free(S->d_gl_means); mlsd_free(S->d_gl_lim);
-	if (S->dec_ctx) mlctx_destroy(S->dec_ctx);
-	if (S->enc_ctx) mlctx_destroy(S->enc_ctx);
-	if (S->dect_ctx) mlctx_destroy(S->dect_ctx);
-	if (S->enct_ctx) mlctx_destroy(S->enct_ctx);
-	mlsd_free(S->d_lat_tile); mlsd_free(S->d_img_tile); mlsd_free(S->d_imgin_tile); mlsd_free(S->d_mom_tile); mlsd_free(S->d_mom);
+	codec_plans_drop(S, CODEC_DROP_ALL);
+	mlsd_free(S->d_mom);
 	mlsd_free(S->d_xin); mlsd_free(S->d_xsave);
 	mlsd_free(S->d_eps_canvas); mlsd_free(S->d_wsum); free(S->win_xs); free(S->win_ys);
 	mlsd_free(S->d_x); mlsd_free(S->d_dx); mlsd_free(S->d_x0); mlsd_free(S->d_lmask); mlsd_free(S->d_img); mlsd_free(S->d_img_in);
@@ -408,19 +298,7 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
 
 	/* ---- decoder plan, latent input bound to the same resident latent */
-	S->dec_ctx = mlctx_new(stream);
-	mlctx_set_conv_wrap(S->dec_ctx, S->tiling);
-	mlctx_set_vae_attn(S->dec_ctx, S->vae_attn);
-	if (S->c.use_tae) {
-		if (sdtae_decode_init(S->dec_ctx, S->lw, S->lh, B, &S->t_lat_dec) < 0) goto err;
-		if (mlctx_input_bind(S->t_lat_dec, S->d_x, B, NULL, 1.0f, 1) < 0) goto err;
-		if (sdtae_decode_build(S->dec_ctx, S->t_lat_dec) < 0) goto err;
-	} else {
-		if (sdvae_decode_init(S->dec_ctx, &S->vae_p, S->lw, S->lh, B, &S->t_lat_dec) < 0) goto err;
-		if (mlctx_input_bind(S->t_lat_dec, S->d_x, B, NULL, 1 / S->vae_p.scale_factor, 0) < 0) goto err;
-		if (sdvae_decode_build(S->dec_ctx, &S->vae_p, S->t_lat_dec) < 0) goto err;
-	}
-	if (!S->c.defer_weights && mlctx_params_synth(S->dec_ctx, S->c.weight_seed) < 0) goto err;
+	if (!codec_full_prepare(S, CODEC_DEC)) goto err;
 	return S;
 err:
 	mlis_amd_destroy(S);
@@ -656,7 +534,7 @@ static const float* noise_gen(MLIS_AmdCtx* S, int k)
 	}
 	return S->d_noise + (size_t)k*lat_elems;
 }
-static const float* noise_draw(MLIS_AmdCtx* S, int k)
+const float* noise_draw(MLIS_AmdCtx* S, int k)
 {	/* draw k for a consumer enqueued next on the compute stream: that stream waits for the draw's upload */
 	const float *nz = noise_gen(S, k);
 	if (nz && mlsd_stream_wait_event(S->stream, S->ev_draw[k])) return NULL;
@@ -1248,374 +1126,6 @@ MLB_API int mlis_amd_guidance_limit_state(MLIS_AmdCtx* S, int* mode, float* a, f
 	return n;
 }
 
-/* ------------------------------------------------------------------ VAE tiling
- * sdvae_decode / sdvae_encode with tile_px > 0 (src/vae.c:333-391, 245-300): the latent (image) is cut into overlapping
- * tiles of tile_px (+ a margin of k = 8 latent pixels / 64 image pixels on every side), each tile runs through a tile-sized
- * plan, and the interior of its result is pasted into the output in the reference's order (later tiles overwrite the
- * margins of earlier ones).  TAE codecs are never tiled (the reference only tiles sdvae_*).
- *
- * A deliberate extension of the reference: where one tile covers a dimension (n == full) while the other dimension is tiled,
- * the reference's loop (vae.c:262-291, 353-385) gives every tile of that dimension the origin 0 and pastes only n - k of it, so
- * the last margin of the output is never written (there: whatever realloc returned); at exactly 2k it divides by zero and below
- * 2k it runs no tile at all.  Here such a dimension is ONE tile at origin 0 pasted whole: the same tile at the same origin as the
- * reference's, so every pixel the reference writes has the same bits, and the pixels it leaves undefined are defined.  Where a
- * dimension is tiled (n < full) the rule is the reference's, without the tiles it repeats: ceil(full / step) counts tiles whose
- * origins all clamp to full - n; they paste the same values onto the same pixels again, so dropping them changes no bit. */
-MLB_API int mlis_amd_set_vae_tile(MLIS_AmdCtx* S, int tile_px)
-{
-	if (tile_px < 0) tile_px = 0;
-	if (tile_px != S->vae_tile) {
-		mlsd_stream_sync(S->stream);
-		if (S->dect_ctx) { mlctx_destroy(S->dect_ctx); S->dect_ctx = NULL; }
-		if (S->enct_ctx) { mlctx_destroy(S->enct_ctx); S->enct_ctx = NULL; }
-		/* the tile buffers have the size of one tile: the next *_tile_prepare allocates them for the new one */
-		mlsd_free(S->d_lat_tile); mlsd_free(S->d_img_tile); mlsd_free(S->d_imgin_tile); mlsd_free(S->d_mom_tile);
-		S->d_lat_tile = S->d_img_tile = S->d_imgin_tile = S->d_mom_tile = NULL;
-		memset(S->tile_bytes, 0, sizeof(S->tile_bytes));
-		S->tl_w = S->tl_h = S->ti_w = S->ti_h = 0;
-		S->vae_tile = tile_px;
-	}
-	return 1;
-}
-
-/* The mid-block attention of the KL-VAE plans: 0 = scores in memory (the default), 1 = one flash launch (mlsd_attention_wide).  A change drops the codec plans
- * only: the full-size decoder is rebuilt here (its parameters are synthesised again, or left for the caller to load: mlctx_params_loaded, as at creation), the
- * encoder and the two tile plans at their next use.  The UNet plan, its weights and every device buffer of the engine stay.  TAESD has no attention: nothing to do. */
-MLB_API int mlis_amd_set_vae_attn(MLIS_AmdCtx* S, int mode)
-{
-	if (!S) return fail("mlis_amd_set_vae_attn: no engine");
-	if (mode != 0 && mode != 1) return mlsd_set_error(-1, "mlis_amd_set_vae_attn: mode %d (0 scores, 1 flash)", mode);
-	if (mode == S->vae_attn) return 1;
-	S->vae_attn = mode;
-	if (S->c.use_tae) return 1;
-	mlsd_stream_sync(S->stream);
-	if (S->dect_ctx) { mlctx_destroy(S->dect_ctx); S->dect_ctx = NULL; }
-	if (S->enct_ctx) { mlctx_destroy(S->enct_ctx); S->enct_ctx = NULL; }
-	if (S->enc_ctx) { mlctx_destroy(S->enc_ctx); S->enc_ctx = NULL; }
-	MLCtx *C = mlctx_new(S->stream);
-	mlctx_set_conv_wrap(C, S->tiling);
-	mlctx_set_vae_attn(C, mode);
-	int ok = sdvae_decode_init(C, &S->vae_p, S->lw, S->lh, S->B, &S->t_lat_dec) >= 0 &&
-	         mlctx_input_bind(S->t_lat_dec, S->d_x, S->B, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
-	         sdvae_decode_build(C, &S->vae_p, S->t_lat_dec) >= 0;
-	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
-	mlctx_destroy(S->dec_ctx);
-	S->dec_ctx = C;             /* (a plan that failed to build stays in place: the next decode reports its error) */
-	return ok ? 1 : -1;
-}
-MLB_API int mlis_amd_vae_attn_mode(const MLIS_AmdCtx* S) { return S ? S->vae_attn : -1; }
-
-static int tile_dims(int tile_px, int margin2, int full, int unit)
-{	/* n = min(round_up(tile_px, 64)/unit + 2k, full); returns full when one tile covers everything (tiling disabled) */
-	const int t = (tile_px + 63) / 64 * 64;
-	const int n = t / unit + margin2;
-	return n < full ? n : full;
-}
-
-/* The tile walk of ONE dimension, for decode and encode alike.  Lengths are in units of `unit` image pixels (decode: f, the walk
- * is over latent pixels; encode: 1): `full` the dimension, `margin` the overlap k (decode 8, encode 8 f), tile_px the option.
- * *n_out = the tile length min(round_up(tile_px, 64) / unit + 2k, full).  Tile t reads [origin[t], origin[t] + n) of the input and
- * pastes [src_off[t], src_off[t] + width[t]) of its result at origin[t] + src_off[t] of the output:
- *   n < full   tile 0 pastes [0, n - k); tile t > 0 at i0 = min(t step, full - n), step = n - 2k, pastes [i0 + k, i0 + n); the
- *              walk ends with the first tile at full - n (vae.c:269-289, 365-384 without the repeats of that last origin)
- *   n == full  one tile at 0 pasted whole (see above)
- * Returns the number of tiles (at most max_tiles of them are written; the arrays may be NULL with max_tiles 0), < 0 for arguments
- * no walk exists for. */
-MLB_API int mlis_amd_vae_tile_walk(int full, int tile_px, int unit, int margin, int* n_out, int* origin, int* src_off, int* width, int max_tiles)
-{
-	if (full < 1 || tile_px < 1 || tile_px > 65535 || unit < 1 || margin < 0 || margin > 65535) return -1;
-	const int k = margin, n = tile_dims(tile_px, 2*k, full, unit);
-	if (n_out) *n_out = n;
-	if (n == full) {
-		if (max_tiles > 0) { origin[0] = 0; src_off[0] = 0; width[0] = full; }
-		return 1;
-	}
-	const int step = n - 2*k, last = full - n;
-	if (step < 1) return -1;                    /* unit > round_up(tile_px, 64) */
-	int cnt = 0;
-	for (int i0 = 0; ; i0 = i0 + step < last ? i0 + step : last) {
-		if (cnt < max_tiles) { origin[cnt] = i0; src_off[cnt] = i0 ? k : 0; width[cnt] = n - k; }
-		++cnt;
-		if (i0 == last) break;
-	}
-	return cnt;
-}
-
-typedef struct { int n, cnt, *org, *off, *wid; } TileWalk;
-
-static int tile_walk_new(TileWalk* w, int full, int tile_px, int unit, int margin)
-{
-	w->org = NULL;
-	w->cnt = mlis_amd_vae_tile_walk(full, tile_px, unit, margin, &w->n, NULL, NULL, NULL, 0);
-	if (w->cnt < 1) return mlsd_set_error(-1, "VAE tiling: no tile walk for length %d, tile %d", full, tile_px);
-	w->org = (int*)malloc((size_t)3 * w->cnt * sizeof(int));
-	if (!w->org) return mlsd_set_error(-1, "out of host memory");
-	w->off = w->org + w->cnt; w->wid = w->off + w->cnt;
-	mlis_amd_vae_tile_walk(full, tile_px, unit, margin, &w->n, w->org, w->off, w->wid, w->cnt);
-	return 0;
-}
-
-/* (re)allocates one tile buffer when the tile needs more than it holds */
-static int tile_buf(MLIS_AmdCtx* S, float** p, int which, size_t nbytes)
-{
-	if (*p && S->tile_bytes[which] >= nbytes) return 0;
-	mlsd_free(*p); *p = NULL; S->tile_bytes[which] = 0;
-	if (mlsd_malloc((void**)p, nbytes)) return -1;
-	S->tile_bytes[which] = nbytes;
-	return 0;
-}
-
-/* builds (once) the decode tile plan; returns NULL with no error when tiling does not apply.
- * The tile plans take ONE image: a batch walks them image by image (the tile buffers hold the tile of every image, the plan's input moves from one to the next).
- * A tile of image b is then computed by the same launches whatever the batch size -- GEMM tiles and K splits are chosen by M = images x pixels, so a plan of
- * B images would round differently from the plan of one -- and the plan's activations, what tiling is there to bound, do not grow with the batch. */
-MLB_API MLCtx* mlis_amd_decoder_tile_prepare(MLIS_AmdCtx* S)
-{
-	if (S->dect_ctx) return S->dect_ctx;
-	if (S->vae_tile <= 0 || S->c.use_tae) return NULL;
-	const int f = S->vae_p.f_down, k = 8;
-	const int n0 = tile_dims(S->vae_tile, 2*k, S->lw, f), n1 = tile_dims(S->vae_tile, 2*k, S->lh, f);
-	if (n0 == S->lw && n1 == S->lh) return NULL;                                      /* one tile: disabled (vae.c:347-348) */
-	const int B = S->B;
-	if (tile_buf(S, &S->d_lat_tile, 0, (size_t)B*4*n0*n1*4)) return NULL;
-	if (tile_buf(S, &S->d_img_tile, 1, (size_t)B*3*n0*f*n1*f*4)) return NULL;
-	MLCtx *C = mlctx_new(S->stream);
-	mlctx_set_vae_attn(C, S->vae_attn);
-	int ok = sdvae_decode_init(C, &S->vae_p, n0, n1, 1, &S->t_lat_dect) >= 0 &&
-	         mlctx_input_bind(S->t_lat_dect, S->d_lat_tile, 1, NULL, 1 / S->vae_p.scale_factor, 0) >= 0 &&
-	         sdvae_decode_build(C, &S->vae_p, S->t_lat_dect) >= 0;
-	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
-	if (!ok) { mlctx_destroy(C); return NULL; }
-	S->dect_ctx = C; S->tl_w = n0; S->tl_h = n1;
-	return C;
-}
-
-MLB_API MLCtx* mlis_amd_encoder_tile_prepare(MLIS_AmdCtx* S)
-{
-	if (S->enct_ctx) return S->enct_ctx;
-	if (S->vae_tile <= 0 || S->c.use_tae) return NULL;
-	const int f = S->vae_p.f_down, k = f*8, W = S->c.width, H = S->c.height;
-	const int n0 = tile_dims(S->vae_tile, 2*k, W, 1), n1 = tile_dims(S->vae_tile, 2*k, H, 1);
-	if (n0 == W && n1 == H) return NULL;
-	const int B = S->B;
-	if (!S->d_img_in && mlsd_malloc((void**)&S->d_img_in, (size_t)B*3*W*H*4)) return NULL;
-	if (tile_buf(S, &S->d_imgin_tile, 2, (size_t)B*3*n0*n1*4)) return NULL;
-	if (tile_buf(S, &S->d_mom_tile, 3, (size_t)B*8*(n0/f)*(n1/f)*4)) return NULL;
-	if (!S->d_mom && mlsd_malloc((void**)&S->d_mom, (size_t)B*8*S->hw*4)) return NULL;
-	MLCtx *C = mlctx_new(S->stream);
-	mlctx_set_vae_attn(C, S->vae_attn);
-	int ok = sdvae_encode_init(C, &S->vae_p, n0, n1, 1, &S->t_img_enct) >= 0 &&
-	         mlctx_input_bind(S->t_img_enct, S->d_imgin_tile, 1, NULL, 1.0f, 2) >= 0 &&
-	         sdvae_encode_build(C, &S->vae_p, S->t_img_enct) >= 0;
-	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
-	if (!ok) { mlctx_destroy(C); return NULL; }
-	S->enct_ctx = C; S->ti_w = n0; S->ti_h = n1;
-	return C;
-}
-
-static int decode_tiled(MLIS_AmdCtx* S)
-{	/* src/vae.c:351-383, walked by mlis_amd_vae_tile_walk */
-	const int f = S->vae_p.f_down, k = 8, B = S->B;
-	const int lat_n0 = S->lw, lat_n1 = S->lh, n0 = S->tl_w, n1 = S->tl_h;
-	const int img_n0 = lat_n0*f, img_n1 = lat_n1*f;
-	void *st = S->stream;
-	MLTensor *r = mlctx_result(S->dect_ctx);
-	int64_t ld = 0;
-	const float *y = mlctx_tensor_device_f32(S->dect_ctx, r, &ld);
-	TileWalk w0, w1 = {0};
-	int R = -1;
-	S->n_tile_evals[0] = 0;
-	if (tile_walk_new(&w0, lat_n0, S->vae_tile, f, k) || tile_walk_new(&w1, lat_n1, S->vae_tile, f, k)) goto end;
-	if (w0.n != n0 || w1.n != n1) { mlsd_set_error(-1, "VAE tiling: the decode tile plan is %dx%d, the walk's tile %dx%d", n0, n1, w0.n, w1.n); goto end; }
-	for (int t1=0; t1<w1.cnt; ++t1) {
-		const int i1 = w1.org[t1], d1 = w1.off[t1];
-		for (int t0=0; t0<w0.cnt; ++t0) {
-			const int i0 = w0.org[t0], d0 = w0.off[t0];
-			if (mlsd_copy_slice2(S->d_lat_tile, n0, n1, S->d_x, lat_n0, lat_n1, n0, n1, 0, 0, i0, i1, B*4, st)) goto end;
-			for (int b=0; b<B; ++b) {
-				if (mlctx_input_rebind(S->dect_ctx, S->t_lat_dect, S->d_lat_tile + (size_t)b*4*n0*n1) < 0) goto end;
-				if (mlctx_compute(S->dect_ctx) < 0) goto end;
-				S->n_tile_evals[0]++;
-				if (mlsd_nhwc_to_nchw_f32(y, ld, 1, 3, n0*f*n1*f, S->d_img_tile + (size_t)b*3*n0*f*n1*f, 0.5f, 0.5f, st)) goto end;   /* (x+1)/2: elementwise, commutes with the paste */
-			}
-			if (mlsd_copy_slice2(S->d_img, img_n0, img_n1, S->d_img_tile, n0*f, n1*f, w0.wid[t0]*f, w1.wid[t1]*f, (i0+d0)*f, (i1+d1)*f,
-					d0*f, d1*f, B*3, st)) goto end;
-		}
-	}
-	R = 1;
-end:
-	free(w0.org); free(w1.org);
-	return R;
-}
-
-static int encode_tiled(MLIS_AmdCtx* S)
-{	/* src/vae.c:262-299: tiles of the image -> moments tiles -> pasted into the full moments tensor (NCHW [B][8][lh][lw]) */
-	const int f = S->vae_p.f_down, k = f*8, B = S->B;
-	const int img_n0 = S->c.width, img_n1 = S->c.height, n0 = S->ti_w, n1 = S->ti_h;
-	const int lat_n0 = img_n0/f, lat_n1 = img_n1/f;
-	void *st = S->stream;
-	MLTensor *r = mlctx_result(S->enct_ctx);
-	int64_t ld = 0;
-	const float *y = mlctx_tensor_device_f32(S->enct_ctx, r, &ld);
-	TileWalk w0, w1 = {0};
-	int R = -1;
-	S->n_tile_evals[1] = 0;
-	if (tile_walk_new(&w0, img_n0, S->vae_tile, 1, k) || tile_walk_new(&w1, img_n1, S->vae_tile, 1, k)) goto end;
-	if (w0.n != n0 || w1.n != n1) { mlsd_set_error(-1, "VAE tiling: the encode tile plan is %dx%d, the walk's tile %dx%d", n0, n1, w0.n, w1.n); goto end; }
-	for (int t1=0; t1<w1.cnt; ++t1) {
-		const int i1 = w1.org[t1], d1 = w1.off[t1];
-		for (int t0=0; t0<w0.cnt; ++t0) {
-			const int i0 = w0.org[t0], d0 = w0.off[t0];
-			if (mlsd_copy_slice2(S->d_imgin_tile, n0, n1, S->d_img_in, img_n0, img_n1, n0, n1, 0, 0, i0, i1, B*3, st)) goto end;
-			for (int b=0; b<B; ++b) {
-				if (mlctx_input_rebind(S->enct_ctx, S->t_img_enct, S->d_imgin_tile + (size_t)b*3*n0*n1) < 0) goto end;
-				if (mlctx_compute(S->enct_ctx) < 0) goto end;
-				S->n_tile_evals[1]++;
-				if (mlsd_count_nonfinite(y, (size_t)(n0/f)*(n1/f)*ld, S->d_nan, st)) goto end;
-				if (mlsd_nhwc_to_nchw_f32(y, ld, 1, 8, (n0/f)*(n1/f), S->d_mom_tile + (size_t)b*8*(n0/f)*(n1/f), 1.0f, 0.0f, st)) goto end;
-			}
-			if (mlsd_copy_slice2(S->d_mom, lat_n0, lat_n1, S->d_mom_tile, n0/f, n1/f, w0.wid[t0]/f, w1.wid[t1]/f, (i0+d0)/f, (i1+d1)/f,
-					d0/f, d1/f, B*8, st)) goto end;
-		}
-	}
-	R = 1;
-end:
-	free(w0.org); free(w1.org);
-	return R;
-}
-
-/* the tile plan of the decoder (which 0) or the encoder (which 1) as it stands: the tile size (latent / image pixels; 0 x 0 without a plan), the bytes allocated for
- * the tile's input and output buffers (the tile of every image of the batch), the tiles one pass walks and the plan evaluations of the last tiled pass (tiles x images).  Returns 1 with a plan, 0 without. */
-MLB_API int mlis_amd_vae_tile_info(MLIS_AmdCtx* S, int which, int* tile_w, int* tile_h, size_t* in_bytes, size_t* out_bytes, int* n_tiles, int* n_evals)
-{
-	if (!S || which < 0 || which > 1) return -1;
-	MLCtx *C = which ? S->enct_ctx : S->dect_ctx;
-	const int f = S->vae_p.f_down;
-	int n = 0;
-	if (C) {
-		const int c0 = mlis_amd_vae_tile_walk(which ? S->c.width : S->lw, S->vae_tile, which ? 1 : f, which ? 8*f : 8, NULL, NULL, NULL, NULL, 0);
-		const int c1 = mlis_amd_vae_tile_walk(which ? S->c.height : S->lh, S->vae_tile, which ? 1 : f, which ? 8*f : 8, NULL, NULL, NULL, NULL, 0);
-		n = c0 > 0 && c1 > 0 ? c0 * c1 : -1;
-	}
-	if (tile_w) *tile_w = C ? (which ? S->ti_w : S->tl_w) : 0;
-	if (tile_h) *tile_h = C ? (which ? S->ti_h : S->tl_h) : 0;
-	if (in_bytes) *in_bytes = S->tile_bytes[which ? 2 : 0];
-	if (out_bytes) *out_bytes = S->tile_bytes[which ? 3 : 1];
-	if (n_tiles) *n_tiles = n;
-	if (n_evals) *n_evals = S->n_tile_evals[which];
-	return C ? 1 : 0;
-}
-
-/* after the launches of a decode / encode were enqueued: if the plan hands data over inside launches, drain and check; 1 = clean, 0 = gave up -> the plan is now
- * hand-off-free and the caller runs its launches again, < 0 = error */
-static int handoffs_clean(MLIS_AmdCtx* S, MLCtx* C, int attempt)
-{
-	if (!mlctx_handoff_ops(C) && !attempt) return 1;
-	if (mlsd_stream_sync(S->stream)) return -1;
-	if (mlctx_handoff_check(C) == 0) return 1;
-	if (attempt) return -1;
-	mlctx_handoffs_off(C);
-	S->n_handoff_retries++;
-	return 0;
-}
-
-MLB_API int mlis_amd_decode(MLIS_AmdCtx* S)
-{
-	if (S->vae_tile > 0 && !S->c.use_tae && mlis_amd_decoder_tile_prepare(S)) {
-		for (int attempt=0; attempt<2; ++attempt) {
-			if (decode_tiled(S) < 0) return -1;
-			const int ok = handoffs_clean(S, S->dect_ctx, attempt);
-			if (ok) return ok;
-		}
-		return -1;
-	}
-	for (int attempt=0; ; ++attempt) {
-		if (mlctx_compute(S->dec_ctx) < 0) return -1;
-		const int ok = handoffs_clean(S, S->dec_ctx, attempt);
-		if (ok < 0) return -1;
-		if (ok) break;
-	}
-	int64_t ld = 0;
-	MLTensor *r = mlctx_result(S->dec_ctx);
-	const float *y = mlctx_tensor_device_f32(S->dec_ctx, r, &ld);
-	const int HW = S->c.width * S->c.height;
-	/* sdvae_decoder_post (x+1)/2 (vae.h:43-47); TAE output is used as-is */
-	const float mul = S->c.use_tae ? 1.0f : 0.5f, add = S->c.use_tae ? 0.0f : 0.5f;
-	if (mlsd_nhwc_to_nchw_f32(y, ld, S->B, 3, HW, S->d_img, mul, add, S->stream)) return -1;
-	return 1;
-}
-
-/* builds the encoder plan (once) without running it; with defer_weights the caller loads its parameters before the first encode */
-MLB_API MLCtx* mlis_amd_encoder_prepare(MLIS_AmdCtx* S)
-{
-	if (S->enc_ctx) return S->enc_ctx;
-	const int B = S->B, W = S->c.width, H = S->c.height;
-	void *st = S->stream;
-	if (!S->d_img_in && mlsd_malloc((void**)&S->d_img_in, (size_t)B*3*W*H*4)) return NULL;
-	MLCtx *C = mlctx_new(st);
-	mlctx_set_conv_wrap(C, S->tiling);
-	mlctx_set_vae_attn(C, S->vae_attn);
-	int ok = 0;
-	if (S->c.use_tae) {
-		ok = sdtae_encode_init(C, W, H, B, &S->t_img_enc) >= 0 && mlctx_input_bind(S->t_img_enc, S->d_img_in, B, NULL, 1.0f, 0) >= 0 &&
-		     sdtae_encode_build(C, S->t_img_enc) >= 0;
-	} else {
-		ok = sdvae_encode_init(C, &S->vae_p, W, H, B, &S->t_img_enc) >= 0 &&
-		     mlctx_input_bind(S->t_img_enc, S->d_img_in, B, NULL, 1.0f, 2) >= 0 &&       /* mode 2: x*2-1 (vae.h:36-40) */
-		     sdvae_encode_build(C, &S->vae_p, S->t_img_enc) >= 0;
-	}
-	if (ok && !S->c.defer_weights) ok = mlctx_params_synth(C, S->c.weight_seed) >= 0;
-	if (!ok) { mlctx_destroy(C); return NULL; }
-	S->enc_ctx = C;
-	return C;
-}
-
-/* mlis_image_encode (src/mlimgsynth.c:1301-1330): images host NCHW [B][3][H][W] in [0,1] -> the resident latent becomes
- * the sampled (VAE: mean + std*N(0,1), one Philox call per image, src/vae.c:203-229) or direct (TAE) encoding and is
- * marked as the initial latent of the next denoise.  The encoder plan is built on first use. */
-MLB_API int mlis_amd_encode(MLIS_AmdCtx* S, const float* images, int sample)
-{
-	const int B = S->B, W = S->c.width, H = S->c.height;
-	const size_t img_elems = (size_t)B*3*W*H;
-	void *st = S->stream;
-	const int tiled = S->vae_tile > 0 && !S->c.use_tae && mlis_amd_encoder_tile_prepare(S) != NULL;
-	if (!tiled && !S->enc_ctx && !mlis_amd_encoder_prepare(S)) return -1;
-	if (mlsd_memcpy(S->d_img_in, images, img_elems*4, 0, st)) return -1;
-	if (mlsd_memset(S->d_nan, 0, 4, st)) return -1;
-	const float *y; int64_t ld = 0;
-	for (int attempt=0; ; ++attempt) {            /* (second pass only after a timed-out in-launch hand-off: the plan is hand-off-free then) */
-		if (attempt && mlsd_memset(S->d_nan, 0, 4, st)) return -1;
-		if (tiled) {
-			if (encode_tiled(S) < 0) return -1;
-			y = NULL;
-		} else {
-			if (mlctx_compute(S->enc_ctx) < 0) return -1;
-			y = mlctx_tensor_device_f32(S->enc_ctx, mlctx_result(S->enc_ctx), &ld);
-			if (mlsd_count_nonfinite(y, (size_t)B*S->hw*ld, S->d_nan, st)) return -1;
-		}
-		const int ok = handoffs_clean(S, tiled ? S->enct_ctx : S->enc_ctx, attempt);
-		if (ok < 0) return -1;
-		if (ok) break;
-	}
-	if (S->c.use_tae) {
-		if (mlsd_nhwc_to_nchw_f32(y, ld, B, 4, S->hw, S->d_x, 1.0f, 0.0f, st)) return -1;
-	} else {
-		const float *rnd = NULL;
-		if (sample) {   /* sdvae_latent_sample: rng_randn(n) per image, before any denoising draw */
-			S->n_draw_gen = 0;
-			rnd = noise_draw(S, 0);
-			if (!rnd) return -1;
-		}
-		if (tiled) { if (mlsd_latent_sample_nchw(S->d_mom, rnd, S->d_x, B, S->vae_p.ch_z, S->hw, S->vae_p.scale_factor, st)) return -1; }
-		else if (mlsd_latent_sample(y, ld, rnd, S->d_x, B, S->vae_p.ch_z, S->hw, S->vae_p.scale_factor, st)) return -1;
-	}
-	int32_t nan_count = 0;
-	if (mlsd_memcpy(&nan_count, S->d_nan, 4, 1, st) || mlsd_stream_sync(st)) return -1;
-	if (nan_count) return mlsd_set_error(-7, "NaN found in encoded latent");   /* mlimgsynth.c:1323 */
-	S->have_init_latent = 1;
-	return 1;
-}
-
 MLB_API int mlis_amd_generate(MLIS_AmdCtx* S, const uint64_t* seeds, float* latents_out, float* images_out)
 {
 	int r = mlis_amd_denoise(S, seeds);
@@ -1633,14 +1143,14 @@ MLB_API int mlis_amd_sync(MLIS_AmdCtx* S) { return mlsd_stream_sync(S->stream) ?
 MLB_API void* mlis_amd_latent_device(MLIS_AmdCtx* S) { return S->d_x; }
 MLB_API void* mlis_amd_image_device(MLIS_AmdCtx* S) { return S->d_img; }
 MLB_API MLCtx* mlis_amd_unet_ctx(MLIS_AmdCtx* S) { return S->unet_ctx; }
-MLB_API MLCtx* mlis_amd_decoder_ctx(MLIS_AmdCtx* S) { return S->dec_ctx; }
-MLB_API MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S) { return S->enc_ctx; }
+MLB_API MLCtx* mlis_amd_decoder_ctx(MLIS_AmdCtx* S) { return S->codec[CODEC_DEC].full.ctx; }
+MLB_API MLCtx* mlis_amd_encoder_ctx(MLIS_AmdCtx* S) { return S->codec[CODEC_ENC].full.ctx; }
 /* every plan the engine holds, built or not yet: UNet, decoder, encoder, tile decoder, tile encoder, ControlNet, hint block (i < 7; NULL where there is none) */
 MLB_API MLCtx* mlis_amd_ctx_at(MLIS_AmdCtx* S, int i)
 {
 	if (!S) return NULL;
-	switch (i) { case 0: return S->unet_ctx; case 1: return S->dec_ctx; case 2: return S->enc_ctx; case 3: return S->dect_ctx; case 4: return S->enct_ctx;
-	             case 5: return S->ctl_ctx; case 6: return S->hint_ctx; }
+	switch (i) { case 0: return S->unet_ctx; case 1: return S->codec[CODEC_DEC].full.ctx; case 2: return S->codec[CODEC_ENC].full.ctx;
+	             case 3: return S->codec[CODEC_DEC].tile.ctx; case 4: return S->codec[CODEC_ENC].tile.ctx; case 5: return S->ctl_ctx; case 6: return S->hint_ctx; }
 	return NULL;
 }
 MLB_API float mlis_amd_last_unet_ms(MLIS_AmdCtx* S) { return S->last_unet_ms; }
@@ -1651,7 +1161,7 @@ MLB_API int mlis_amd_last_n_step(MLIS_AmdCtx* S) { return S->last_n_step; }
 MLB_API int mlis_amd_info(MLIS_AmdCtx* S, double* unet_flops, double* dec_flops, int* unet_ops, size_t* mem_params, size_t* mem_compute)
 {
 	MLCtxInfo a, b;
-	mlctx_info(S->unet_ctx, &a); mlctx_info(S->dec_ctx, &b);
+	mlctx_info(S->unet_ctx, &a); mlctx_info(S->codec[CODEC_DEC].full.ctx, &b);
 	if (unet_flops) *unet_flops = a.flops * (S->n_win ? S->n_eval : 1);    /* per evaluation of the whole latent: the work done, padded slots of a packed plan included */
 	if (dec_flops) *dec_flops = b.flops;
 	if (unet_ops) *unet_ops = (int)a.n_ops;

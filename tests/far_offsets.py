@@ -39,7 +39,7 @@ import plan_audit as PA
 import ref64 as R
 
 E_REAL = 31
-MAX_IMAGES = 64      # the largest batch mlis_api.c (MAX_IMAGES) and engine.c (MAX_BATCH) admit for one plan; test_far_offsets_cpu.py reads both files
+MAX_IMAGES = 64      # the largest batch mlis_api.c (MAX_IMAGES) and engine_int.h (MAX_BATCH) admit for one plan; test_far_offsets_cpu.py reads both files
 
 FAR_PLANS = [
     ("vae_dec", "sdxl", 256, 1), ("vae_enc", "sdxl", 256, 1), ("vae_dec", "sd1", 256, 1), ("vae_enc", "sd1", 256, 1),

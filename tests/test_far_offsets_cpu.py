@@ -39,7 +39,7 @@ def census():
 
 
 def test_the_batch_limit_is_the_sources():
-    api, eng = open(os.path.join(CSRC, "mlis_api.c")).read(), open(os.path.join(CSRC, "engine.c")).read()
+    api, eng = open(os.path.join(CSRC, "mlis_api.c")).read(), open(os.path.join(CSRC, "engine_int.h")).read()
     assert int(re.search(r"#define MAX_IMAGES (\d+)", api).group(1)) == FO.MAX_IMAGES
     assert int(re.search(r"#define MAX_BATCH (\d+)", eng).group(1)) == FO.MAX_IMAGES
 

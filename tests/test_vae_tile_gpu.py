@@ -1,4 +1,4 @@
-"""Tiled VAE decode and encode (MLIS_OPT_VAE_TILE; decode_tiled / encode_tiled of csrc/host/engine.c) at every tile geometry the walk has, on the model "tiny"
+"""Tiled VAE decode and encode (MLIS_OPT_VAE_TILE; codec_run_tiled of csrc/host/engine_vae.c) at every tile geometry the walk has, on the model "tiny"
 (f_down 8, margin k = 8 latent pixels): the smallest sizes at which each branch exists.
 
 Per geometry, for decode and for encode:
@@ -227,8 +227,32 @@ def test_encode(E, orc, name):
     print(f"{name}: {n} tiles of {n0}x{n1}; worst window rel-L2 {worst:.3e}, whole latent mean {rel(lat_m, ref_m):.3e} sampled {rel(lat_s, ref_s):.3e}")
 
 
+@pytest.mark.parametrize("side", [64, 256])
+def test_taesd_is_never_tiled(E, side):
+    """A TAESD engine of two images: encode, then decode, with vae_tile 0 and with vae_tile 64.  No tile plan exists either way and the two runs give the same bytes,
+    latent and image (the engine's TAESD path: the encoder bound with mode 0, the decoder with mode 1, results used as they are).  64 x 64 is one tile for any codec;
+    at 256 x 256 a KL-VAE engine does build tile plans at vae_tile 64 (row "batch2" above)."""
+    src = np.random.default_rng(side).random((2, 3, side, side)).astype(F32)
+    got = []
+    for tile_px in (0, 64):
+        g = E.Generator("tiny", side, side, 2, n_step=2, use_tae=True)
+        try:
+            g.set_vae_tile(tile_px)
+            lat = g.encode(src, sample=False)
+            poison_image(g)
+            g.decode()
+            got.append((lat, g.image()))
+            assert not g.vae_tile_prepare() and not g.vae_tile_prepare(encoder=True)
+            assert g.vae_tile_info() is None and g.vae_tile_info(encoder=True) is None and g.ctx_at(3) is None and g.ctx_at(4) is None
+        finally:
+            g.destroy()
+    assert np.isfinite(got[0][0]).all() and np.isfinite(got[0][1]).all() and got[0][0].std() > 0 and got[0][1].std() > 0
+    assert not np.array_equal(got[0][0][0], got[0][0][1]) and not np.array_equal(got[0][1][0], got[0][1][1])
+    assert got[0][0].tobytes() == got[1][0].tobytes() and got[0][1].tobytes() == got[1][1].tobytes()
+
+
 # ------------------------------------------------------------------ a tile change on a live engine, through the public API
-TOKS = np.array([5, 17, 300, 42, 7], np.int32)
+TOKS =np.array([5, 17, 300, 42, 7], np.int32)
 
 
 @pytest.fixture(scope="module")

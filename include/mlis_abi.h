@@ -292,6 +292,29 @@ int mlis_amd_inpaint_info(MLIS_Ctx* ctx, int region[4], int proc[2]);
 int mlis_amd_tensor_upscale(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst);
 /* upscalers constructed by this context so far (cumulative, like mlis_amd_engine_builds); *resident = 1 while one is held */
 int mlis_amd_upscaler_builds(MLIS_Ctx* ctx, int* resident);
+/* Colour correction (the kernels and the rules in full: mlsd_colorfix_* in mlsd_kernels.h; all three AS RECALLED from the front ends and their extensions,
+ * parity-unpinned).  A second pass over an existing picture drifts in colour; these bring the colours of `target` back into `content`:
+ *   WAVELET    out = content + Low(target - content), Low = `levels` (1 .. 5; 0 = the default, 5) levels of the a-trous low-pass: content's detail over target's low
+ *              frequencies (StableSR's wavelet colour fix).  target must have content's w x h.
+ *   ADAIN      per image and channel, content's mean and standard deviation are moved to target's.  target may have any size.
+ *   HISTOGRAM  per channel histogram matching on 8-bit levels (skimage's match_histograms on integer images; without the front ends' Lab conversion and luminosity blend).
+ * mlis_amd_tensor_color_fix: content [w][h][c][B], target [tw][th][c][1 or B] -> dst [w][h][c][B], host tensors through the GPU and back; needs no model; dst may be
+ * content or target.  OFF copies content.  Returns 1; MLIS_E_OPT_VALUE for a bad mode, levels outside 0 .. 5, a channel or batch mismatch, a wavelet size mismatch.
+ * mlis_amd_color_fix: the setting mlis_generate applies to its decoded images -- not an MLIS_Option: held in the context, never part of an engine key, a change rebuilds
+ * nothing, and with OFF no new code runs.  Where it applies (a target of another size is first resampled to content's with the resample of the pass):
+ *   img2img and inpainting with inpaint_area whole: target = the input image; before the composite, if there is one
+ *   inpaint_area masked: content = the crop resampled back, target = the same rectangle of the untouched input; before the composite
+ *   hires fix with hires_use_model: target = the decoded first pass
+ * Plain txt2img, a hires fix without the model and no_decode have no target or no image: the setting is ignored.  The infotext gains "Color fix: MODE".
+ * mlis_amd_color_fix_info: the setting, and *applied = the images the last mlis_generate corrected (0 where it was ignored).  Pointers may be NULL.  Returns 1.
+ * Not included: Lab conversion and luminosity blend, fixes per window inside tiled diffusion, a fix without a source image. */
+#define MLIS_AMD_COLORFIX_OFF       0
+#define MLIS_AMD_COLORFIX_WAVELET   1
+#define MLIS_AMD_COLORFIX_ADAIN     2
+#define MLIS_AMD_COLORFIX_HISTOGRAM 3
+int mlis_amd_tensor_color_fix(MLIS_Ctx* ctx, const MLIS_Tensor* content, const MLIS_Tensor* target, MLIS_Tensor* dst, int mode, int levels);
+int mlis_amd_color_fix(MLIS_Ctx* ctx, int mode, int levels);
+int mlis_amd_color_fix_info(MLIS_Ctx* ctx, int* mode, int* levels, int* applied);
 
 #ifdef __cplusplus
 }

@@ -580,6 +580,42 @@ int mlsd_canny(const float* src, int w, int h, int planes, int low, int high, in
 int mlsd_canny_thresholds(double low, double high, int l2, int* lo, int* hi);
 int mlsd_canny_tile(int which);
 int mlsd_invert(const float* src, float* dst, int64_t n, void* stream);
+/* Colour correction of a re-denoised picture (hip/colorfix.hip; not in the reference): img2img, inpainting and the hires fix drift in colour, these bring the colours
+ * of `target` (the picture the pass started from) back into `content` (the picture it produced).  All three rules are AS RECALLED from the front ends and their
+ * extensions, which were not at hand: parity-unpinned, pinned to what is written here (tests/colorfix_ref.py restates them in float64).
+ * Planes are NCHW fp32: content and dst [B][c][h][w], target [nt][c][th][tw] with nt = 1 (shared by every image) or B; values nominally in 0 .. 1, never clamped.
+ * Every w x h plane is handled on its own, plane (b, k) of content against plane (nt == 1 ? 0 : b, k) of target.
+ *  WAVELET (StableSR's wavelet colour fix): the result keeps content's detail and takes target's low frequencies.  target has content's w x h.
+ *    One level i (0-based): L_i(x)[y][x] = sum over dy, dx in {-1, 0, 1} of k[dy] k[dx] x[clamp(y + 2^i dy)][clamp(x + 2^i dx)], k = (1/4, 1/2, 1/4), the indices
+ *    clamped to the plane at every level (a replicated border).  Low = L_(levels-1)(... L_0(x)), levels 1 .. 5 (halo 2^levels - 1).
+ *    The published form is content - Low(content) + Low(target); Low is linear, so in exact arithmetic that is  out = content + Low(target - content),  which is the
+ *    rule here: one filter run instead of two.  d = target - content is rounded once in fp32.  A level is separable and runs as a row pass t[y][x] =
+ *    (1/4 a[y][cx(x - s)] + 1/2 a[y][x]) + 1/4 a[y][cx(x + s)] and a column pass of the same form over t, s = 2^i: the products are exact, the two sums of a pass are
+ *    each rounded once in that order (4 fp32 roundings per level), then out = content + Low, rounded once.  target == content returns content's bits.
+ *    One launch: a workgroup stages d of its 64 x 64 tile plus halo in LDS and runs every level there.  dst may be content or target; the launch then writes ws
+ *    (mlsd_colorfix_ws_bytes, B c w h floats) and a device copy follows; otherwise ws may be NULL.
+ *  ADAIN: per plane, with means and UNBIASED variances in double (n = w h, nT = tw th): a = sqrt(var_t + 1e-5) / sqrt(var_c + 1e-5), b = mean_t - mean_c a, both formed
+ *    in double and rounded to fp32; out = fadd(fmul(content, a), b).  target may have any size.  A plane with n < 2 or nT < 2 has a = 1, b = 0; a plane with a == 1
+ *    and b == 0 is copied, bit for bit.  Sums: per block (x - x[0]) and its square in double, partials added in block order -- the same bits every run.
+ *    coef (device, [B c][2] floats = a, b; may be NULL): where the coefficients are left.
+ *  HISTOGRAM: per-channel histogram matching on 8-bit levels -- what skimage.exposure.match_histograms does for integer images.  It is NOT the front ends' "apply color
+ *    correction" in full: that converts to Lab first and blends the result in luminosity mode; neither is here.  Both pictures are quantised by rule (a) of mlsd_canny;
+ *    256 bins per plane are counted exactly; with q_c[v], q_t[v] the cumulative counts divided by the pixel counts and V the ascending levels present in target,
+ *    lut[v] = interp(q_c[v], q_t[V], V) / 255 in double -- linear between neighbours (slope (V[j+1] - V[j]) / (q_t[V[j+1]] - q_t[V[j]]), times the distance, plus V[j]),
+ *    clamped at both ends -- rounded to fp32; out = lut[quant(content)].  target may have any size.  The LUT is formed on the device (the call never waits).
+ *    counts (device, [B c + nt c][256] unsigned: content's planes, then target's) and lut (device, [B c][256] floats) may be NULL.
+ * ws: mlsd_colorfix_ws_bytes(mode, w, h, tw, th, c, B, nt) bytes of device memory, 8-byte aligned; 0 for arguments the calls refuse.  dst may be content (adain and
+ * histogram are elementwise behind their statistics).  All return -1 before any launch for a NULL buffer, an extent, c or B below 1, nt not 1 or B, a plane of 2^31
+ * bytes or more, more than 65535 planes, levels outside 1 .. 5, buffers that overlap other than as allowed, and a coef, counts or lut that is not 4-byte aligned or overlaps
+ * content, target, dst, ws or the other of the two.
+ * mlsd_colorfix_tile: 0 the wavelet tile's edge, 1 its levels at most, 2 its lanes, 3 its LDS bytes at 5 levels, 4 the blocks per plane of the statistics at most. */
+enum { MLSD_COLORFIX_WAVELET = 1, MLSD_COLORFIX_ADAIN = 2, MLSD_COLORFIX_HISTOGRAM = 3 };
+size_t mlsd_colorfix_ws_bytes(int mode, int w, int h, int tw, int th, int c, int B, int nt);
+int mlsd_colorfix_wavelet(const float* content, const float* target, float* dst, int w, int h, int c, int B, int nt, int levels, void* ws, void* stream);
+int mlsd_colorfix_adain(const float* content, int w, int h, const float* target, int tw, int th, float* dst, int c, int B, int nt, void* ws, float* coef, void* stream);
+int mlsd_colorfix_histogram(const float* content, int w, int h, const float* target, int tw, int th, float* dst, int c, int B, int nt, void* ws, unsigned* counts,
+                            float* lut, void* stream);
+int mlsd_colorfix_tile(int which);
 /* Region inpainting, the image-space pieces (hip/inpaint.hip; not in the reference): fp32 planes [planes][h][w].  wrap: bit 0 the x axis, bit 1 the y axis, as
  * everywhere.  An index outside a plane replicates the border pixel (what OpenCV's BORDER_REPLICATE does; the border mode front ends blur their masks with is
  * BORDER_REFLECT_101 as recalled, which could not be checked when this was written: parity-unpinned, pinned to this rule); on a wrapped axis it is taken modulo

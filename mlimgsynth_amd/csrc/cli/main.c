@@ -315,7 +315,7 @@ static unsigned char* img_from_tensor(const MLIS_Tensor* t)
 /* ------------------------------------------------------------------ options */
 static const char k_usage[] =
 "Usage: mlimgsynth-amd [COMMAND] [OPTIONS]\n\n"
-"Commands: generate | upscale | canny | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
+"Commands: generate | upscale | canny | colorfix | list-backends | vae-encode | vae-decode | vae-test | clip-encode | tokenize | check | convert\n\n"
 "Generation:  -p --prompt TEXT   -n --nprompt TEXT   -d --image-dim W,H   -i --input PATH   --imask PATH\n"
 "             --ilatent PATH   --ilmask PATH   -o --output PATH   --olatent PATH   --no-prompt-parse BOOL\n"
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
@@ -331,6 +331,8 @@ static const char k_usage[] =
 "             --control-preprocess none|canny|invert   (run on the control image after it was resampled to each pass's size)\n"
 "Canny:       --canny-low F   --canny-high F   --canny-l2 y|n   (thresholds 0 .. 32767, defaults 100 200; l2: sqrt(dx^2 + dy^2) instead of |dx| + |dy|)\n"
 "             canny -i IN -o OUT [--canny-low F --canny-high F --canny-l2 y|n --tiling none|x|y|xy] writes the edge map of IN and needs no -m\n"
+"Color fix:   --color-fix none|wavelet|adain|histogram[:LEVELS]   (img2img, inpainting, hires fix with a model: the result takes the colours of the picture it\n"
+"             started from; LEVELS 1 .. 5 of the wavelet, default 5);  colorfix -i IN --target T -o OUT --color-fix MODE needs no -m\n"
 "Inpainting:  --inpaint-area whole|masked   --inpaint-padding PX   --mask-blur SIGMA   --mask-grow PX   --mask-invert y|n   --inpaint-composite y|n\n"
 "             (with -i and --imask; masked: only the padded bounding box of the repainted pixels is processed, at -d, and pasted back; -i may have any size)\n"
 "FreeU:       --freeu BOOL  --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
@@ -345,7 +347,7 @@ static const char k_usage[] =
 "Output:      -v --verbose   -q --quiet   --silent   --debug   -h --help   -V --version\n";
 
 typedef struct {
-	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens, *ctl_img;
+	const char *cmd, *in_img, *in_mask, *in_lat, *in_lmask, *out_img, *out_lat, *tokens, *ntokens, *ctl_img, *target;
 	double outscale;        /* upscale --outscale: 0 = not given */
 	int glimit;             /* --dyn-thresh / --apg: the MLIS_AMD_GLIMIT_* given so far */
 	MLIS_Ctx *ctx;
@@ -366,7 +368,7 @@ static int cli_option(Cli* C, const char* name, const char* next)
 	if (!strcmp(name, "debug")) { g_verbose = 3; mlis_option_set(C->ctx, MLIS_OPT_LOG_LEVEL, MLIS_LOGLVL_DEBUG); return 0; }
 	const struct { const char* n; const char** dst; } paths[] = {
 		{"input",&C->in_img},{"imask",&C->in_mask},{"ilatent",&C->in_lat},{"ilmask",&C->in_lmask},{"output",&C->out_img},
-		{"olatent",&C->out_lat},{"tokens",&C->tokens},{"ntokens",&C->ntokens},{"control-image",&C->ctl_img} };
+		{"olatent",&C->out_lat},{"tokens",&C->tokens},{"ntokens",&C->ntokens},{"control-image",&C->ctl_img},{"target",&C->target} };
 	for (size_t i=0;i<sizeof(paths)/sizeof(*paths);++i) if (!strcmp(name, paths[i].n)) { *paths[i].dst = next; return 1; }
 	if (!strcmp(name, "outscale")) {
 		char *e = NULL; const double f = strtod(next, &e);
@@ -376,6 +378,16 @@ static int cli_option(Cli* C, const char* name, const char* next)
 	if (!strcmp(name, "vae-attn")) {      /* not an option of the table: the call itself (include/mlis_abi.h) */
 		const int mode = !strcmp(next, "scores") ? MLIS_AMD_VAE_ATTN_SCORES : !strcmp(next, "flash") ? MLIS_AMD_VAE_ATTN_FLASH : -1;
 		if (mode < 0 || mlis_amd_vae_attn(C->ctx, mode) < 0) FAIL("option '--vae-attn %s': scores or flash", next);
+		return 1;
+	}
+	if (!strcmp(name, "color-fix")) {      /* MODE[:LEVELS], the call itself as --vae-attn */
+		static const char* const modes[] = { "none", "wavelet", "adain", "histogram" };
+		const char *colon = strchr(next, ':');
+		const size_t len = colon ? (size_t)(colon - next) : strlen(next);
+		int mode = -1, levels = 0;
+		for (int i=0;i<4;++i) if (strlen(modes[i]) == len && !strncmp(next, modes[i], len)) mode = i;
+		if (colon) { char *e = NULL; const long v = strtol(colon + 1, &e, 10); levels = (e == colon + 1 || *e || v < 1 || v > 5) ? -1 : (int)v; }
+		if (mode < 0 || levels < 0 || mlis_amd_color_fix(C->ctx, mode, levels) < 0) FAIL("option '--color-fix %s': none|wavelet|adain|histogram[:LEVELS], LEVELS 1 .. 5", next);
 		return 1;
 	}
 	if (!strcmp(name, "dyn-thresh") || !strcmp(name, "apg")) {      /* A[:B], the call itself as --vae-attn */
@@ -589,6 +601,39 @@ static int cmd_canny(Cli* C)
 	return r < 0 ? -1 : 1;
 }
 
+/* RGB tensor of an image file: grey replicated, alpha dropped */
+static int tensor_read_rgb(const char* path, MLIS_Tensor* t)
+{
+	Img im; if (img_read(path, &im) < 0) return -1;
+	unsigned char *rgb = (unsigned char*)malloc((size_t)im.w * im.h * 3);
+	if (!rgb) { free(im.d); FAIL("out of memory reading '%s'", path); }
+	for (size_t i=0;i<(size_t)im.w*im.h;++i) for (int c=0;c<3;++c) rgb[i*3+c] = im.d[i*im.c + (im.c >= 3 ? c : 0)];
+	Img in3 = im; in3.d = rgb; in3.c = 3;
+	tensor_from_img(t, NULL, &in3);
+	free(rgb); free(im.d);
+	return 1;
+}
+
+/* colorfix: --input with the colours of --target by the --color-fix mode, no SD model involved */
+static int cmd_colorfix(Cli* C)
+{
+	if (!C->in_img || !C->target) FAIL("colorfix needs --input and --target");
+	int mode = 0, levels = 0;
+	mlis_amd_color_fix_info(C->ctx, &mode, &levels, NULL);
+	if (!mode) FAIL("colorfix needs --color-fix wavelet|adain|histogram");
+	MLIS_Tensor t = {0}, g = {0};
+	int r = tensor_read_rgb(C->in_img, &t);
+	if (r >= 0) r = tensor_read_rgb(C->target, &g);
+	if (r >= 0 && (r = mlis_amd_tensor_color_fix(C->ctx, &t, &g, &t, mode, levels)) < 0) fprintf(stderr, "error: colorfix: %s\n", mlis_errstr_get(C->ctx));
+	if (r >= 0) {
+		unsigned char *px = img_from_tensor(&t);
+		r = img_write(C->out_img ? C->out_img : "output.png", px, (unsigned)t.n[0], (unsigned)t.n[1], 3, NULL);
+		free(px);
+	}
+	mlis_tensor_free(&t); mlis_tensor_free(&g);
+	return r < 0 ? -1 : 1;
+}
+
 static int cmd_text(Cli* C, int encode)
 {
 	const char *prompt = NULL;
@@ -623,6 +668,7 @@ int main(int argc, char** argv)
 	if (!strcmp(C.cmd, "generate")) r = cmd_generate(&C);
 	else if (!strcmp(C.cmd, "upscale")) r = cmd_upscale(&C);
 	else if (!strcmp(C.cmd, "canny")) r = cmd_canny(&C);
+	else if (!strcmp(C.cmd, "colorfix")) r = cmd_colorfix(&C);
 	else if (!strcmp(C.cmd, "list-backends")) {
 		r = 1;
 		for (unsigned i=0; ; ++i) {

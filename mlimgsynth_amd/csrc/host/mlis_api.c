@@ -60,6 +60,7 @@ struct MLIS_Ctx {
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
 	int vae_attn;                           /* mlis_amd_vae_attn: MLIS_AMD_VAE_ATTN_*, handed to the engine before every pass (never part of the engine key) */
 	int glimit_mode; float glimit_a, glimit_b;      /* mlis_amd_guidance_limit: MLIS_AMD_GLIMIT_* and its two parameters, handed to the engine per generation (never part of the engine key) */
+	int cfix_mode, cfix_levels, cfix_applied;       /* mlis_amd_color_fix: MLIS_AMD_COLORFIX_*, the wavelet's levels, the images the last generation corrected (never part of the engine key) */
 	float cfg_rescale;                      /* MLIS_OPT_AMD_CFG_RESCALE: phi of the guidance rescale, handed to the engine per generation (never part of the engine key) */
 	int prediction, zsnr;                   /* MLIS_OPT_AMD_PREDICTION (0 auto, 1 eps, 2 v) / MLIS_OPT_AMD_ZSNR (0 auto, 1 off, 2 on): resolved per generation (guidance_resolve) */
 	int ckpt_v_pred, ckpt_ztsnr;            /* the checkpoint's marker tensors (mlts_markers); 0 for the synthetic models */
@@ -348,6 +349,22 @@ MLB_API int mlis_amd_guidance_limit_info(MLIS_Ctx* S, int* mode, float* a, float
 	if (b) *b = S->glimit_mode ? S->glimit_b : 0;
 	if (n_evals) *n_evals = 0;
 	return S->eng ? mlis_amd_guidance_limit_state(S->eng, NULL, NULL, NULL, n_evals, values, max_values) : 0;
+}
+static int color_fix_args_ok(int mode, int levels) { return mode >= MLIS_AMD_COLORFIX_OFF && mode <= MLIS_AMD_COLORFIX_HISTOGRAM && levels >= 0 && levels <= 5; }
+MLB_API int mlis_amd_color_fix(MLIS_Ctx* S, int mode, int levels)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (!color_fix_args_ok(mode, levels)) return api_error(S, MLIS_E_OPT_VALUE, "color fix: mode %d (0 off, 1 wavelet, 2 adain, 3 histogram), levels %d (1 .. 5, 0 = 5)", mode, levels);
+	S->cfix_mode = mode; S->cfix_levels = levels ? levels : 5;      /* (mlis_generate reads it behind its decodes) */
+	return 1;
+}
+MLB_API int mlis_amd_color_fix_info(MLIS_Ctx* S, int* mode, int* levels, int* applied)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (mode) *mode = S->cfix_mode;
+	if (levels) *levels = S->cfix_levels ? S->cfix_levels : 5;
+	if (applied) *applied = S->cfix_applied;
+	return 1;
 }
 MLB_API int mlis_amd_lora_stats(MLIS_Ctx* S, int* n_restored, int* n_patched, int* n_cold_merges)
 {
@@ -1663,6 +1680,49 @@ MLB_API int mlis_amd_tensor_canny(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tens
 	return r;
 }
 
+/* ------------------------------------------------------------------ colour correction (hip/colorfix.hip) */
+/* host tensors -> device, one mlsd_colorfix_ call, -> host tensor; dst may be content or target (both are on the device before dst is resized) */
+static int tensor_color_fix(MLIS_Ctx* S, const MLIS_Tensor* content, const MLIS_Tensor* target, MLIS_Tensor* dst, int mode, int levels)
+{
+	if (!color_fix_args_ok(mode, levels)) return api_error(S, MLIS_E_OPT_VALUE, "color fix: mode %d (0 off, 1 wavelet, 2 adain, 3 histogram), levels %d (1 .. 5, 0 = 5)", mode, levels);
+	if (!content || !target || !dst || !tensor_good(content) || !tensor_good(target) || content->n[0] < 1 || content->n[1] < 1 || content->n[2] < 1 || content->n[3] < 1
+			|| target->n[0] < 1 || target->n[1] < 1 || mlis_tensor_count(content) >= ((size_t)1 << 31) || mlis_tensor_count(target) >= ((size_t)1 << 31))
+		return api_error(S, MLIS_E_OPT_VALUE, "invalid tensor for color fix");
+	const int w = content->n[0], h = content->n[1], c = content->n[2], B = content->n[3], tw = target->n[0], th = target->n[1], nt = target->n[3];
+	if (target->n[2] != c || (nt != 1 && nt != B))
+		return api_error(S, MLIS_E_OPT_VALUE, "color fix: a target of %d channels and %d images for a content of %d channels and %d images (the same channels, 1 or %d images)",
+			target->n[2], nt, c, B, B);
+	if (mode == MLIS_AMD_COLORFIX_WAVELET && (tw != w || th != h))
+		return api_error(S, MLIS_E_OPT_VALUE, "color fix: the wavelet needs a target of the content's size, %dx%d, not %dx%d", w, h, tw, th);
+	if (mode == MLIS_AMD_COLORFIX_OFF) { if (dst != content) mlis_tensor_copy(dst, content); return 1; }
+	if (c * B > 65535) return api_error(S, MLIS_E_OPT_VALUE, "color fix: more than 65535 planes");
+	const size_t n_c = mlis_tensor_count(content), n_t = mlis_tensor_count(target);
+	int r = backend_setup(S); if (r < 0) return r;
+	void *d_c = NULL, *d_t = NULL, *d_dst = NULL, *d_ws = NULL;
+	if (mlsd_malloc(&d_c, n_c * 4) || mlsd_malloc(&d_t, n_t * 4) || mlsd_malloc(&d_dst, n_c * 4)
+			|| (mode != MLIS_AMD_COLORFIX_WAVELET && mlsd_malloc(&d_ws, mlsd_colorfix_ws_bytes(mode, w, h, tw, th, c, B, nt)))
+			|| mlsd_memcpy(d_c, content->d, n_c * 4, 0, NULL) || mlsd_memcpy(d_t, target->d, n_t * 4, 0, NULL)
+			|| (mode == MLIS_AMD_COLORFIX_WAVELET && mlsd_colorfix_wavelet((const float*)d_c, (const float*)d_t, (float*)d_dst, w, h, c, B, nt, levels ? levels : 5, NULL, NULL))
+			|| (mode == MLIS_AMD_COLORFIX_ADAIN && mlsd_colorfix_adain((const float*)d_c, w, h, (const float*)d_t, tw, th, (float*)d_dst, c, B, nt, d_ws, NULL, NULL))
+			|| (mode == MLIS_AMD_COLORFIX_HISTOGRAM && mlsd_colorfix_histogram((const float*)d_c, w, h, (const float*)d_t, tw, th, (float*)d_dst, c, B, nt, d_ws, NULL, NULL, NULL)))
+		r = api_error_lib(S, MLIS_E_UNKNOWN);
+	if (r > 0) {
+		mlis_tensor_resize(dst, w, h, c, B);
+		if (mlsd_memcpy(dst->d, d_dst, n_c * 4, 1, NULL) || mlsd_device_sync()) r = api_error_lib(S, MLIS_E_UNKNOWN);
+	}
+	if (d_c) mlsd_free(d_c);
+	if (d_t) mlsd_free(d_t);
+	if (d_dst) mlsd_free(d_dst);
+	if (d_ws) mlsd_free(d_ws);
+	return r;
+}
+
+MLB_API int mlis_amd_tensor_color_fix(MLIS_Ctx* S, const MLIS_Tensor* content, const MLIS_Tensor* target, MLIS_Tensor* dst, int mode, int levels)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return -1;
+	return tensor_color_fix(S, content, target, dst, mode, levels);
+}
+
 /* ------------------------------------------------------------------ region inpainting, piece by piece (hip/inpaint.hip) */
 /* each: host tensor -> device, one mlsd_ call, -> host tensor; src may be dst (it is on the device before dst is resized) */
 enum { MASK_OP_WEIGHT, MASK_OP_GROW, MASK_OP_BLUR };
@@ -1928,6 +1988,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 			if (zs) ADD(", Schedule: zsnr");
 		}
 	}
+	if (S->cfix_applied) ADD(", Color fix: %s", S->cfix_mode == MLIS_AMD_COLORFIX_WAVELET ? "wavelet" : S->cfix_mode == MLIS_AMD_COLORFIX_ADAIN ? "adain" : "histogram");
 	if (S->downscale_filter) ADD(", Downscale filter: %s", k_downscale[S->downscale_filter]);
 	if (!str_empty(S->path_control) && S->control_preprocess == MLIS_AMD_PREPROCESS_CANNY) ADD(", Control preprocess: canny %g %g%s", S->canny_low, S->canny_high, S->canny_l2 ? " L2" : "");
 	else if (!str_empty(S->path_control) && S->control_preprocess) ADD(", Control preprocess: %s", k_preprocess[S->control_preprocess]);
@@ -2042,6 +2103,30 @@ static int generate_pass(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 	return 1;
 }
 
+/* the colour fix of mlis_generate (mlis_amd_color_fix): the decoded images in S->image against `target` (consumed: brought to their size first, with the resample
+ * a masked pass uses), what a caller gets from mlis_amd_tensor_resample[_aa] + mlis_amd_tensor_color_fix */
+static int inpaint_resample(MLIS_Ctx* S, MLIS_Tensor* t, int w, int h, int mode);
+static int color_fix_apply(MLIS_Ctx* S, MLIS_Tensor* target)
+{
+	int r = 1;
+	if (target->n[0] != S->image.n[0] || target->n[1] != S->image.n[1]) r = inpaint_resample(S, target, S->image.n[0], S->image.n[1], S->hires_upscaler);
+	if (r >= 0) r = tensor_color_fix(S, &S->image, target, &S->image, S->cfix_mode, S->cfix_levels);
+	if (r >= 0) { S->cfix_applied = S->image.n[3]; S->image.flags |= LT_F_READY; }
+	return r;
+}
+
+/* generate_pass with the colour fix behind it where the pass is img2img from an image and decodes: target = the input image */
+static int generate_pass_fixed(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
+{
+	if (!S->cfix_mode || !decode || !(S->tuflags & MLIS_TUF_IMAGE) || !tensor_good(&S->image)) return generate_pass(S, decode, pw_img, ph_img);
+	MLIS_Tensor target = {0};
+	mlis_tensor_copy(&target, &S->image);
+	int r = generate_pass(S, decode, pw_img, ph_img);
+	if (r >= 0) r = color_fix_apply(S, &target);
+	mlis_tensor_free(&target);
+	return r;
+}
+
 /* hires fix: the txt2img pass at IMAGE_DIM (never decoded), its latent upscaled, then the img2img-from-latent pass at the target size with
  * f_t_ini = hires_denoise -- what a caller gets from generate (NO_DECODE) + mlis_amd_tensor_resample + generate (MLIS_TUF_LATENT), with the
  * prompt, the token ids and the prompt's LoRAs in place until the end and the Philox streams running on from the first pass.  With hires_use_model the first pass
@@ -2058,6 +2143,8 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 	if (r >= 0) {
 		const int steps1 = S->last_n_step, lw = S->latent.n[0], lh = S->latent.n[1];
 		const int tw = (int)floor((double)lw * S->hires_scale + 0.5), th = (int)floor((double)lh * S->hires_scale + 0.5);      /* the target latent size, either way */
+		MLIS_Tensor first = {0};      /* the colour fix's target: the decoded first pass */
+		if (use_model && S->cfix_mode && decode) mlis_tensor_copy(&first, &S->image);
 		if (use_model) {
 			/* the decoded first pass upscaled 4x by the model, brought to the target pixel size by a plain resample -- or, with a downscale_filter and an axis that
 			 * shrinks, by that filter --; the second pass encodes it (generate_pass, MLIS_TUF_IMAGE): what a caller gets from generate + mlis_amd_tensor_upscale +
@@ -2075,7 +2162,9 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 			r = generate_pass(S, decode, pw_img, ph_img);
 			S->nfe_base = 0;
 			S->last_n_step = steps1;        /* "Steps" of the infotext: the first pass, the second one is "Hires steps" */
+			if (r >= 0 && tensor_good(&first)) r = color_fix_apply(S, &first);
 		}
+		mlis_tensor_free(&first);
 	}
 	S->f_t_ini = f_t_ini; S->n_step = n_step; S->tuflags = tuflags;
 	return r;
@@ -2119,7 +2208,7 @@ static int inpaint_resample(MLIS_Ctx* S, MLIS_Tensor* t, int w, int h, int mode)
  * with inpaint_composite, its decoded images are composited over the input through p.  Without a mask there is nothing to process: the plain pass. */
 static int generate_inpaint(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 {
-	if (!(S->tuflags & MLIS_TUF_MASK) || !tensor_good(&S->mask)) return generate_pass(S, decode, pw_img, ph_img);
+	if (!(S->tuflags & MLIS_TUF_MASK) || !tensor_good(&S->mask)) return generate_pass_fixed(S, decode, pw_img, ph_img);
 	const int masked = S->inpaint_area == MLIS_AMD_INPAINT_MASKED, composite = inpaint_composites(S);
 	const int W = S->mask.n[0], H = S->mask.n[1];
 	if (S->mask.n[2] != 1 || S->mask.n[3] != 1) return api_error(S, MLIS_E_IMAGE, "the mask must be one plane");
@@ -2145,7 +2234,13 @@ static int generate_inpaint(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img)
 		S->control_rect_on = 0;
 		if (r < 0) goto done;
 		if ((r = inpaint_resample(S, &S->image, cw, ch, S->hires_upscaler)) < 0) goto done;
-	} else if ((r = generate_pass(S, decode, pw_img, ph_img)) < 0) goto done;
+		if (S->cfix_mode) {      /* the crop resampled back against the same rectangle of the untouched input */
+			MLIS_Tensor target = {0};
+			if ((r = tensor_crop(S, &orig, &target, reg[0], reg[1], cw, ch)) >= 0) r = color_fix_apply(S, &target);
+			mlis_tensor_free(&target);
+			if (r < 0) goto done;
+		}
+	} else if ((r = generate_pass_fixed(S, decode, pw_img, ph_img)) < 0) goto done;
 	if (composite) {
 		S->inp_proc[0] = *pw_img; S->inp_proc[1] = *ph_img;
 		if ((r = tensor_composite(S, &S->image, &orig, &S->image, &p, reg[0], reg[1])) < 0) goto done;
@@ -2180,11 +2275,12 @@ MLB_API int mlis_generate(MLIS_Ctx* S)
 	}
 	S->control_evals[0] = S->control_evals[1] = S->control_pass = 0;
 	S->tiled_tile = S->tiled_overlap = S->tiled_pack = 0;
+	S->cfix_applied = 0;
 	S->t_last = now_s(); memset(&S->prg, 0, sizeof(S->prg));
 	int w_img = 0, h_img = 0, hires_n_step = 0;
 	const int decode = !(S->flags & CF_NO_DECODE);
 	r = hires_on(S) ? generate_hires(S, decode, &w_img, &h_img, &hires_n_step)      /* (it refuses image and mask inputs) */
-		: inpaint_on(S) ? generate_inpaint(S, decode, &w_img, &h_img) : generate_pass(S, decode, &w_img, &h_img);
+		: inpaint_on(S) ? generate_inpaint(S, decode, &w_img, &h_img) : generate_pass_fixed(S, decode, &w_img, &h_img);
 	if (r < 0) return r;
 	infotext_update(S, w_img, h_img, hires_n_step);
 	/* mlis_prompt_clear :692-709 */

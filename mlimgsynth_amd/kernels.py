@@ -268,6 +268,40 @@ def invert(src, dst, n, stream=None):
     check(lib().mlsd_invert(vp(src), vp(dst), c_i64(n), vp(stream)), "mlsd_invert")
 
 
+COLORFIX_WAVELET, COLORFIX_ADAIN, COLORFIX_HISTOGRAM = 1, 2, 3
+
+
+def colorfix_tile(which):
+    """mlsd_colorfix_tile: 0 the wavelet tile's edge, 1 its levels at most, 2 its lanes, 3 its LDS bytes at 5 levels, 4 the statistics' blocks per plane at most"""
+    return int(lib().mlsd_colorfix_tile(int(which)))
+
+
+def colorfix_ws_bytes(mode, w, h, tw, th, c, B, nt):
+    """mlsd_colorfix_ws_bytes: device workspace of one colour fix (COLORFIX_*; the wavelet needs it only in place); 0 for arguments the calls refuse."""
+    f = lib().mlsd_colorfix_ws_bytes
+    f.restype = ctypes.c_size_t
+    return int(f(int(mode), int(w), int(h), int(tw), int(th), int(c), int(B), int(nt)))
+
+
+def colorfix_wavelet(content, target, dst, w, h, c, B, nt, levels=5, ws=None, stream=None):
+    """mlsd_colorfix_wavelet: dst = content + Low(target - content), `levels` levels of the a-trous low-pass in one launch (fp32 planes [B][c][h][w], target
+    [nt][c][h][w], nt 1 or B; device pointers).  dst may be content or target with ws of colorfix_ws_bytes."""
+    check(lib().mlsd_colorfix_wavelet(vp(content), vp(target), vp(dst), int(w), int(h), int(c), int(B), int(nt), int(levels), vp(ws), vp(stream)), "mlsd_colorfix_wavelet")
+
+
+def colorfix_adain(content, w, h, target, tw, th, dst, c, B, nt, ws, coef=None, stream=None):
+    """mlsd_colorfix_adain: dst = content a + b per plane, a and b from the planes' means and unbiased variances in double; coef (device, [B c][2]) gets a, b."""
+    check(lib().mlsd_colorfix_adain(vp(content), int(w), int(h), vp(target), int(tw), int(th), vp(dst), int(c), int(B), int(nt), vp(ws), vp(coef), vp(stream)),
+          "mlsd_colorfix_adain")
+
+
+def colorfix_histogram(content, w, h, target, tw, th, dst, c, B, nt, ws, counts=None, lut=None, stream=None):
+    """mlsd_colorfix_histogram: dst = lut[quant(content)], per plane histogram matching on 8-bit levels; counts (device, [B c + nt c][256] uint32) and lut
+    (device, [B c][256] floats) get the histograms and the tables."""
+    check(lib().mlsd_colorfix_histogram(vp(content), int(w), int(h), vp(target), int(tw), int(th), vp(dst), int(c), int(B), int(nt), vp(ws), vp(counts), vp(lut),
+                                        vp(stream)), "mlsd_colorfix_histogram")
+
+
 MASK_GROW_MAX, GAUSS_MAX_SIGMA, GAUSS_MAX_TAPS = 256, 64, 321
 
 

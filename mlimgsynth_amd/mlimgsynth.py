@@ -101,6 +101,8 @@ _PROTOTYPES = {
     "mlis_amd_prompt_tokens_set": (_I, [_V, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_F), _I, _I]),
     "mlis_amd_engine_get": (_V, [_V]), "mlis_amd_hypertile_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_pag_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "mlis_amd_tensor_color_fix": (_I, [_V, _TP, _TP, _TP, _I, _I]), "mlis_amd_color_fix": (_I, [_V, _I, _I]),
+    "mlis_amd_color_fix_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_upscale": (_I, [_V, _TP, _TP]), "mlis_amd_upscaler_builds": (_I, [_V, ctypes.POINTER(_I)]),
 }
 
@@ -552,6 +554,37 @@ class MLImgSynth:
             w, h = int(math.floor(outscale * image.n[0] + 0.5)), int(math.floor(outscale * image.n[1] + 0.5))
             if self._lib.mlis_amd_tensor_resample_aa(self._ctx, tout, tout, max(w, 1), max(h, 1), f.value - 1 if f.value else MLIS_AMD_AA_LANCZOS) < 0:   # noqa: F821
                 raise RuntimeError("Failed to resample the upscaled image: %s" % self.errstr_get())
+        return MLIS_Tensor(tout.contents)
+
+    # ---- colour correction
+    COLOR_FIX = {"none": 0, "wavelet": 1, "adain": 2, "histogram": 3}
+
+    def color_fix_set(self, mode="none", levels=5):
+        """The colour fix a generation applies to its decoded images against the picture it started from (img2img and inpainting: the input; hires fix with the
+        model: the decoded first pass): "wavelet" (the input's low frequencies under the result's detail, `levels` 1 .. 5 of the a-trous low-pass), "adain" (per
+        channel mean and deviation), "histogram" (per channel histogram matching on 8-bit levels) or "none".  All three as recalled from the front ends.
+        Persists across generations and builds no engine; ignored where there is no source image."""
+        if mode not in self.COLOR_FIX:
+            raise ValueError("color fix: 'none', 'wavelet', 'adain' or 'histogram', not %r" % (mode,))
+        if self._lib.mlis_amd_color_fix(self._ctx, self.COLOR_FIX[mode], int(levels)) < 0:
+            raise ValueError("color fix: %s" % self.errstr_get())
+
+    def color_fix_info(self):
+        "dict: mode, levels (of the wavelet) and applied (the images the last generation corrected)"
+        m, n, a = _I(), _I(), _I()
+        if self._lib.mlis_amd_color_fix_info(self._ctx, ctypes.byref(m), ctypes.byref(n), ctypes.byref(a)) < 0:
+            raise RuntimeError("Failed to read the color fix: %s" % self.errstr_get())
+        return dict(mode={v: k for k, v in self.COLOR_FIX.items()}[m.value], levels=n.value, applied=a.value)
+
+    def color_fix(self, content, target, mode="wavelet", levels=5):
+        """content [n,c,h,w] with the colours of target [1 or n,c,th,tw] on the GPU (modes as color_fix_set; the wavelet needs th x tw = h x w).  Returns an
+        MLIS_Tensor [n,c,h,w].  Needs no model."""
+        if mode not in self.COLOR_FIX:
+            raise ValueError("color fix: 'none', 'wavelet', 'adain' or 'histogram', not %r" % (mode,))
+        tc, tt = content._c(), target._c()
+        tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
+        if self._lib.mlis_amd_tensor_color_fix(self._ctx, ctypes.byref(tc), ctypes.byref(tt), tout, self.COLOR_FIX[mode], int(levels)) < 0:
+            raise RuntimeError("Failed to fix the colours: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
 
     # ---- the KL-VAE's mid-block attention

@@ -57,6 +57,13 @@ void   mlctx_set_hypertile(MLCtx* C, int tile_px, int depth);   /* HyperTile for
                                                               * log2(ds) <= depth; 0: off, the plan is op for op the one without this call */
 /* what that rule did to the spatial transformers built so far: how many were tiled / left whole, and th, tw, nh, nw per depth 0..3 (zeros where the depth is not tiled) */
 int    mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, int tiles[4][4]);
+/* Token merging (rule: mlsd_tome_* of mlsd_kernels.h; parity-unpinned) for the spatial transformers built from now on: the self-attention of every transformer layer
+ * on a UNet level with downscale ds <= max_ds -- never the middle block's -- runs on T - r merged rows, r = mlsd_tome_r(H, W, ratio); a level whose r is 0 gets no
+ * op.  ratio 0 .. 0.75 (0: off, the plan is op for op the one without this call; anything else counts as 0); max_ds 1, 2, 4, 8 or 0 = the shallowest level with
+ * transformers (resolved when a UNet is built).  A level HyperTile cuts as well fails the build.
+ * mlctx_tome_info: the ratio, max_ds as resolved, how many self-attentions were merged, and per depth 0 .. 3 T, r, T' (zeros where the depth is not merged). */
+void   mlctx_set_tome(MLCtx* C, float ratio, int max_ds);
+int    mlctx_tome_info(const MLCtx* C, float* ratio, int* max_ds, int* n_merged, int levels[4][3]);
 /* Perturbed-attention guidance: the last n_img images of the UNet plan built from now on are the PERTURBED group -- in the self-attentions of the middle block's
  * spatial transformer their attention matrix is the identity (mlb_attn_mhead_ex); 0: off, the plan is op for op the one without this call.
  * _info: the self-attentions recorded that way so far and the images of the group. */
@@ -202,7 +209,16 @@ typedef struct mlb_temb_args { const float* t; int n, dim; float maxp; void* out
 typedef struct mlb_act_args { const float* x; void* y; size_t n; int act; } mlb_act_args;                                                                  /* mlsd_act_f32_to_f16 */
 typedef struct mlb_cemb_args { const int32_t* tok; int n, T, d; const void* tw; const float* pw; float* out; } mlb_cemb_args;                              /* mlsd_clip_embed */
 typedef struct mlb_smax_args { const float* in; int64_t ld_in; void* out; int64_t ld_out; int rows, cols; float scale; } mlb_smax_args;                    /* mlsd_softmax_rows */
-typedef struct mlb_copy_args { const void* src; void* dst; size_t nbytes; int n_img, H, W, th, tw, row_bytes, inverse; } mlb_copy_args;                    /* device-to-device copy of nbytes; th > 0: mlsd_tile_permute of n_img maps of H x W rows of row_bytes (nbytes is still the whole extent) */
+typedef struct mlb_copy_args { const void* src; void* dst; size_t nbytes; int n_img, H, W, th, tw, row_bytes, inverse;                                     /* device-to-device copy of nbytes; th > 0: mlsd_tile_permute of n_img maps of H x W rows of row_bytes (nbytes is still the whole extent) */
+	int tome, r; const void *aux, *aux2; int64_t ld2; } mlb_copy_args;
+/* mlb_copy_args.tome (0: the forms above; everything zero in the fields behind `inverse`): a token-merging launch on n_img maps of H x W tokens with r merged sources per
+ * map (mlsd_tome_* of mlsd_kernels.h); nbytes is the whole extent written at dst.
+ *   MLB_TOME_MATCH    src = the fp16 rows n (row_bytes / 2 halfs, dense)                 dst = best [n_img][Ns] ints, then score [n_img][Ns] floats
+ *   MLB_TOME_SELECT   src = that best | score block                                      dst = the lists (mlsd_tome_lists_ints per map)
+ *   MLB_TOME_MERGE    src = the rows n, aux = the lists                                  dst = the merged fp16 rows [n_img][T - r]
+ *   MLB_TOME_UNMERGE  src = o, fp32 rows [n_img][T - r] (row_bytes / 4 floats, dense), aux = the lists, aux2 = the residual x at a stride of ld2 floats
+ *                                                                                        dst = y = x + o[slot], dense fp32 rows [n_img][T] */
+enum { MLB_TOME_MATCH = 1, MLB_TOME_SELECT = 2, MLB_TOME_MERGE = 3, MLB_TOME_UNMERGE = 4 };
 typedef struct mlb_cadd_args { float* dst; int64_t ld_dst; const float* base; int64_t ld_base; const float* ctrl; int64_t ld_ctrl; int n_img, rows, C, n_ctrl; const float* gain; } mlb_cadd_args;   /* mlsd_ctrl_add: ctrl and gain are device memory of another plan / the engine */
 typedef struct mlb_freeu_args { float* dst; int64_t ld_dst; const float* src; int64_t ld_src; int n_img, H, W, C; float* ws; const float* f; } mlb_freeu_args;   /* mlsd_freeu_backbone (rows = H W) / mlsd_freeu_skip: ws is plan memory, f one float of the engine's device memory */
 typedef struct mlb_xavt_args { const void* v; int64_t ldv; int n_img, Tk, N; void* vt; } mlb_xavt_args;                                                    /* mlsd_xattn_pack_vt: V^T pack of a cross attention that ends its q projection */

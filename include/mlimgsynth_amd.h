@@ -393,6 +393,8 @@ int mlis_amd_tiling(const MLIS_AmdCtx* S);
  * -- sampler state, noise, RNG streams, codecs, callback, NFE count -- keeps the canvas batch.  mlis_amd_create_tiled is pack = 1. */
 MLIS_AmdCtx* mlis_amd_create_tiled(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, void* stream);
 MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, void* stream);
+/* ... with token merging (ratio, max_ds: see mlis_amd_set_tome below) built into the plans from the start; 0, 0 is mlis_amd_create_tiled_packed */
+MLIS_AmdCtx* mlis_amd_create_tome(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, float ratio, int max_ds, void* stream);
 /* the pack rule (pure): P0 = min(pack, n_win, 16, 64 / n_batch), *n_eval = ceil(n_win / P0) plan evaluations per UNet evaluation, returns P = ceil(n_win / *n_eval);
  * -1 for pack, n_win or n_batch below 1.  _info: the values of an engine; a plain engine reports 0, 1. */
 int mlis_amd_tile_pack(int n_win, int n_batch, int pack, int* n_eval);
@@ -479,6 +481,21 @@ int mlis_amd_freeu_info(const MLIS_AmdCtx* S, int* n_stage1, int* n_stage2);
 int mlis_amd_hypertile_side(int side, int px_per_token, int tile_px);
 int unet_hypertile_cuts(const UnetParams* P, int lw, int lh, int tile_px, int depth);
 int mlis_amd_hypertile_info(const MLIS_AmdCtx* S, int* n_tiled, int* n_untiled, int tiles[4][4]);
+/* Token merging, ToMe ("Token Merging for Fast Stable Diffusion", 2023; not in the reference; parity-unpinned: the rule is the published one as recalled, with its
+ * random destination choice fixed -- stated in full at mlsd_tome_match, mlsd_kernels.h).  The self-attention of every transformer layer on a UNet level with
+ * downscale ds <= max_ds, never the middle block's, runs on T - r merged rows; cross-attention and the feed-forward see all T rows.
+ * mlis_amd_set_tome: ratio 0 .. 0.75 (0: off), max_ds 0, 1, 2, 4 or 8 (0: the shallowest level with transformers).  A changed setting REBUILDS the UNet plan (and the
+ * ControlNet plan, whose encoder copy follows the same rule): their weights are to be loaded again (engines created without defer_weights get their synthetic ones
+ * back), the conditioning set again.  Fails, with the engine as it was, on a value outside the above, and where HyperTile cuts a level the setting would merge; a
+ * rebuild that fails (memory) leaves the engine without a UNet plan, fit only for mlis_amd_destroy.  mlis_amd_create_tome builds an engine with the setting at once.
+ * An engine whose levels all come out with r == 0 has, record for record, the plan without the call.
+ * mlis_amd_tome_plan_info: the ratio, max_ds as resolved, the merged self-attentions of the UNet plan, and T, r, T' per depth 0 .. 3 (zeros where not merged).
+ * unet_tome_max_ds / unet_tome_levels: the same rule from the sizes alone (pure, host; tests/test_tome_cpu.py holds it to built plans). */
+int mlis_amd_set_tome(MLIS_AmdCtx* S, float ratio, int max_ds);
+int mlis_amd_tome_plan_info(const MLIS_AmdCtx* S, float* ratio, int* max_ds, int* n_merged, int levels[4][3]);
+int unet_tome_max_ds(const UnetParams* P, int max_ds);
+int unet_tome_levels(const UnetParams* P, int lw, int lh, float ratio, int max_ds, int levels[4][3]);
+int unet_tome_hypertile_clash(const UnetParams* P, int lw, int lh, float ratio, int max_ds, int tile_px, int depth);      /* 1: HyperTile cuts a level the setting merges */
 /* Perturbed-attention guidance, PAG (engines created with MLIS_AMD_CONTROL_PAG in MLIS_AmdConfig.control; "Self-Rectifying Diffusion Sampling with
  * Perturbed-Attention Guidance", 2024; not in the reference).  The rule, as recalled from the publication and the front ends that ship it -- parity with the published
  * code is NOT pinned by a test, the rule below is:

@@ -221,6 +221,17 @@ int mlis_amd_engine_builds(MLIS_Ctx* ctx);
 #define MLIS_AMD_VAE_ATTN_FLASH  1
 int mlis_amd_vae_attn(MLIS_Ctx* ctx, int mode);
 int mlis_amd_vae_attn_info(MLIS_Ctx* ctx, int* mode, int* plan_mode);
+/* Token merging, ToMe: the front ends' "token merging ratio" (not in the reference; PARITY-UNPINNED: the published rule as recalled, its random destination choice
+ * fixed; in full at mlsd_tome_match, include/mlsd_kernels.h).  Before each self-attention of the merged UNet levels the r most redundant tokens are merged into their
+ * most similar neighbour, the attention block runs on T - r rows and its result is copied back out to all T positions.  Not an MLIS_Option: a call.  ratio 0 .. 0.75
+ * (0: off, the default; front ends use 0.3 .. 0.5), max_ds 0, 1, 2, 4 or 8: levels with UNet downscale <= max_ds are merged, 0 = the shallowest level with
+ * transformers (1 for SD1.5, 2 for SDXL); the middle block never is.  Both are part of the engine key, applied per pass size: a pass none of whose levels has an
+ * r > 0 takes the plain engine under the plain key.  Composes with unet_tile, FreeU, ControlNet, weight streaming and PAG; a pass in which HyperTile cuts a level this
+ * setting merges is refused as a bad value when it is generated.  Returns 1, MLIS_E_OPT_VALUE for a value outside the above.
+ * mlis_amd_tome_info: the setting, max_ds as resolved for the loaded model (as given without one), and T, r, T' per UNet depth 0 .. 3 of the engine used last (zeros
+ * where the depth is not merged or there is no engine); pointers may be NULL. */
+int mlis_amd_tome(MLIS_Ctx* ctx, float ratio, int max_ds);
+int mlis_amd_tome_info(MLIS_Ctx* ctx, float* ratio, int* max_ds, int levels[4][3]);
 /* Guidance limiters for cfg_scale well above 7, where the mix c cfg + u (1 - cfg) burns colours and contrast (neither is in the reference; both AS RECALLED,
  * parity-unpinned; the rules in full: include/mlsd_kernels.h).  Not MLIS_Options: a call, handed to the engine before every pass, never part of the engine key.
  *   DYNTHRESH, a = mimic scale (>= 1), b = percentile (0.5 .. 1; 1 = the maximum): dynamic thresholding as the "CFG scale fix" extension's default path -- per latent

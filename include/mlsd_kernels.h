@@ -718,6 +718,42 @@ int mlsd_freeu_depth(int n_terms);
  *   All offsets are 64-bit.  Refused with an error and no launch: th not dividing H or tw not dividing W, row_bytes not a multiple of 16, a pointer not 16-byte
  *   aligned, src == dst or overlapping ranges (there is no in-place form), a count below 1. */
 int mlsd_tile_permute(const void* src, void* dst, int n_img, int H, int W, int th, int tw, int row_bytes, int inverse, void* stream);
+/* Token merging for the UNet's self-attention (csrc/hip/tome.hip; "Token Merging for Fast Stable Diffusion", 2023; not in the reference).  PARITY-UNPINNED: the rule
+ * below is the published one AS RECALLED, with its random choice of the destination inside a cell fixed to the cell's corner.  For one image the rule works on the
+ * T = H W dense fp16 rows n of C halfs (the output of norm1 of a transformer layer):
+ *   1 partition  cells of 2 x 2 anchored at (0, 0); with H' = 2 floor(H / 2), W' = 2 floor(W / 2) the token (y, x) with y and x even, y + 1 < H', x + 1 < W' is a
+ *                DESTINATION, every other token -- the last row / column of an odd map included -- a SOURCE; both sets in ascending token order:
+ *                Nd = floor(H / 2) floor(W / 2), Ns = T - Nd.
+ *   2 match      s(i, j) = <a_i, b_j> / (|a_i| |b_j|) over source i and destination j: fp16 x fp16 products accumulated in fp32 (MFMA), the norms fp32 sums of the
+ *                squares of the same fp16 values, a zero norm gives the score 0.  best[i] = argmax_j s(i, j), the lowest j on equal values; score[i] that maximum.
+ *                The maximum starts at (-inf, 0) and takes a score only where it compares greater: a NaN score (an inf or NaN among the fp16 values) never
+ *                enters it, and a row all of whose scores are NaN comes out as best 0, score -inf -- the smallest key of rule 3, merged last.
+ *   3 select     r = min(floor(ratio T), Ns) rounded down to a multiple of 16 (mlsd_tome_r: ratio is the fp32 value, the product is formed in double); r == 0: the
+ *                level is not merged.  The merged sources are the r sources of largest score, equal scores by lower source index first: an exact order on
+ *                (key, index), key = the score's bits mapped so that unsigned order is the order of the floats (sign set: all bits inverted, else the sign bit
+ *                set) -- a NaN has its place by its bits, above +inf where its sign is clear.  The kept sources are the rest, in ascending order.
+ *   4 merge      the merged set has T' = T - r rows: the Ns - r kept sources in order, then the Nd destinations in order.  A destination row is the mean of itself
+ *                and the merged sources whose best is that destination: an fp32 sum, the destination first, then its sources in ascending source index, divided
+ *                by their count in fp32, rounded to fp16 once.  slot[t] is the row of the merged set token t ended in (a merged source: its destination's row).
+ *   5 block      attn1 runs on the T' rows: the fused q|k|v projection, the attention with Tq = Tk = T', out_proj with its bias and WITHOUT the residual.
+ *   6 unmerge    y[t] = x[t] + o[slot[t]] in fp32, x the block's residual: the addition out_proj's epilogue made before, made once.
+ * lists (device ints, mlsd_tome_lists_ints(H, W, r) per image, images one after the other):  slot[T] | kept[Ns - r] (token of the k-th kept source) | off[Nd + 1]
+ *   (exclusive prefix of the destinations' member counts, off[Nd] = r) | members[r] (tokens, per destination in ascending source order) | cnt[Nd] (the counts again).
+ *   Every array comes out the same bits in every run: integer atomics count, prefix scans place.
+ * match: n [n_img][T] rows at a stride of ld halfs -> best, score [n_img][Ns].  C a multiple of 32 in 64 .. 1280.  No score matrix is written.
+ * select: score, best [n_img][Ns] -> lists.  One workgroup per image; keys of more than mlsd_tome_select_lds_limit() bytes (96 KiB: Ns <= 24576; select_lds_limit(bytes)
+ *   sets it, capped there; negative only asks; returns the previous one) are formed again from score in every pass.  A best outside 0 .. Nd - 1 is clamped.
+ * merge: n, lists -> m, dense [n_img][T'] rows of C halfs.   unmerge_add: x, y [n_img][T] rows of C floats at strides ldx, ldy, o [n_img][T'] at ldo; y may be x.
+ * Refused by name before any launch: a NULL buffer, n_img < 1, a map below 2 x 2 or above 2^24 tokens, C outside the above (unmerge_add: C % 4), a stride below C or
+ *   not a whole number of 16-byte pieces, a pointer not 16-byte aligned, r not a multiple of 16 in 0 .. Ns. */
+int    mlsd_tome_r(int H, int W, float ratio);
+size_t mlsd_tome_lists_ints(int H, int W, int r);
+int    mlsd_tome_select_lds_limit(int bytes);
+int mlsd_tome_match(const void* n, int64_t ld, int n_img, int H, int W, int C, int* best, float* score, void* stream);
+int mlsd_tome_select(const float* score, const int* best, int n_img, int H, int W, int r, int* lists, void* stream);
+int mlsd_tome_merge(const void* n, int64_t ld, int n_img, int H, int W, int C, int r, const int* lists, void* m, void* stream);
+int mlsd_tome_unmerge_add(const float* x, int64_t ldx, const float* o, int64_t ldo, int n_img, int H, int W, int C, int r, const int* lists, float* y, int64_t ldy,
+                          void* stream);
 /* Dense-block convolution of the ESRGAN upscaler (csrc/hip/upscale.hip; not in the reference): 3x3, stride 1, zero padding 1, Cin in {32, 64, 96, 128, 160, 192} to N in
  * {32, 64} output channels over a channels-last fp16 image [n_img][H][W] with lda halfs between pixels (lda >= Cin: A may be a channel slice of a wider buffer; columns >= Cin
  * are never read).  upsample 1: the output is 2H x 2W and the taps read the nearest-2x upsampled image (folded into the gather, as mlsd_gemm_args.upsample).

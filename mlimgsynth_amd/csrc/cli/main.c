@@ -337,6 +337,7 @@ static const char k_usage[] =
 "             (with -i and --imask; masked: only the padded bounding box of the repainted pixels is processed, at -d, and pasted back; -i may have any size)\n"
 "FreeU:       --freeu BOOL  --freeu-b1 F   --freeu-b2 F   --freeu-s1 F   --freeu-s2 F   (backbone / skip factors of stages 1 and 2, 0 .. 4)\n"
 "HyperTile:   --hypertile PX   --hypertile-depth N   (self-attention inside tiles of PX image pixels, 32 .. 8192 in steps of 8, 0 = off; UNet levels 0 .. N <= 3)\n"
+"ToMe:        --tome RATIO[:MAXDS]   (token merging ratio 0 .. 0.75, 0 = off; UNet levels with downscale <= MAXDS in 1, 2, 4, 8, default the shallowest with transformers)\n"
 "PAG:         --pag-scale F   (perturbed-attention guidance, 0 .. 20, 0 = off, 3 is the usual value; one more UNet row group per image)\n"
 "Guidance:    --cfg-rescale F   --prediction auto|eps|v   --zsnr auto|y|n   (guidance rescale 0 .. 1, 0 = off, 0.7 is the usual value; prediction type and\n"
 "             zero-terminal-SNR sigma table, auto = what the model type and the checkpoint's v_pred / ztsnr markers say)\n"
@@ -378,6 +379,14 @@ static int cli_option(Cli* C, const char* name, const char* next)
 	if (!strcmp(name, "vae-attn")) {      /* not an option of the table: the call itself (include/mlis_abi.h) */
 		const int mode = !strcmp(next, "scores") ? MLIS_AMD_VAE_ATTN_SCORES : !strcmp(next, "flash") ? MLIS_AMD_VAE_ATTN_FLASH : -1;
 		if (mode < 0 || mlis_amd_vae_attn(C->ctx, mode) < 0) FAIL("option '--vae-attn %s': scores or flash", next);
+		return 1;
+	}
+	if (!strcmp(name, "tome")) {      /* RATIO[:MAXDS], the call itself as --vae-attn */
+		char *e = NULL, *e2 = NULL;
+		const double ratio = strtod(next, &e);
+		const long ds = (e != next && *e == ':') ? strtol(e + 1, &e2, 10) : 0;
+		if (e == next || (*e && (*e != ':' || e2 == e + 1 || *e2)) || mlis_amd_tome(C->ctx, (float)ratio, (int)ds) < 0)
+			FAIL("option '--tome %s': RATIO[:MAXDS], RATIO 0 .. 0.75, MAXDS 0, 1, 2, 4 or 8", next);
 		return 1;
 	}
 	if (!strcmp(name, "color-fix")) {      /* MODE[:LEVELS], the call itself as --vae-attn */

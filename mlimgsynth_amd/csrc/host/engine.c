@@ -171,11 +171,21 @@ MLB_API int mlis_amd_tile_windows(const MLIS_AmdCtx* S, int* xs, int* ys, int ca
 	return S->n_win;
 }
 
+static int unet_plans_build(MLIS_AmdCtx* S);
+static int tome_check(const MLIS_AmdCtx* S, float ratio, int max_ds, const char* what);
+
 /* Tiled diffusion (MultiDiffusion): cfg->width x height is the CANVAS -- sampler state, noise, mask, decoder and encoder have its size -- and the UNet plan is built
  * for P windows of min(tile, canvas) per axis, P = mlis_amd_tile_pack(windows, n_batch, pack): the plan of a plain engine for P x n_batch images with the shared
  * prompt.  Every evaluation runs the plan on each group of P windows and blends the outputs (unet_eval).  tile_w, tile_h, overlap in pixels (multiples of 8,
  * 2 x overlap <= tile); a tile of 0, or one that covers the canvas on both axes, gives the plain engine of mlis_amd_create_ex. */
 MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, void* stream)
+{
+	return mlis_amd_create_tome(cfg, tiling, tile_w, tile_h, overlap, pack, 0.0f, 0, stream);
+}
+
+/* ... with token merging built into the UNet and ControlNet plans from the start (mlis_amd_set_tome's values; MLIS_AmdConfig cannot grow): a bad value, or HyperTile on a
+ * level the setting merges, is refused from the sizes alone, before any plan is built */
+MLB_API MLIS_AmdCtx* mlis_amd_create_tome(const MLIS_AmdConfig* cfg, int tiling, int tile_w, int tile_h, int overlap, int pack, float ratio, int max_ds, void* stream)
 {
 	if (pack < 1 || pack > MLSD_WINDOW_MAX_PACK) { mlsd_set_error(-1, "tiled diffusion: %d windows per evaluation: 1 .. %d", pack, MLSD_WINDOW_MAX_PACK); return NULL; }
 	const int tiled = tile_w > 0 && tile_h > 0 && (tile_w < cfg->width || tile_h < cfg->height);
@@ -239,12 +249,10 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	if (mlsd_malloc((void**)&S->d_nan, 256)) goto err;
 	if (ensure_steps(S, ns) < 0) goto err;
 	/* tiled: the plan takes `pack` windows of every image.  It wraps only along an axis its window spans; elsewhere the ring of windows carries the wrap and a window edge pads with zeros */
-	int ulw = S->lw, ulh = S->lh, unet_wrap = S->tiling;
 	if (tiled) {
 		S->tile_px = tile_w; S->tile_overlap_px = overlap;
 		if (windows_init(S, tile_w / S->vae_p.f_down, tile_h / S->vae_p.f_down, overlap / S->vae_p.f_down) < 0) goto err;
-		ulw = S->win_w; ulh = S->win_h;
-		unet_wrap = S->tiling & ((ulw == S->lw ? 1 : 0) | (ulh == S->lh ? 2 : 0));
+		const int ulw = S->win_w, ulh = S->win_h;
 		S->pack = mlis_amd_tile_pack(S->n_win, B, pack, &S->n_eval);
 		S->PB = S->pack * B; S->PN = S->pack * S->N;
 		if (S->PN > MLIS_AMD_MAX_EVAL_ROWS) { mlsd_set_error(-1, "PAG: %d rows per plan evaluation (%d windows of batch %d), at most %d", S->PN, S->pack, B, MLIS_AMD_MAX_EVAL_ROWS); goto err; }
@@ -253,18 +261,40 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	}
 	if (mlsd_malloc((void**)&S->d_cin, (size_t)S->PB*4)) goto err;
 	S->CN = S->PN - (S->pag ? S->PB : 0);
+	if (tome_check(S, ratio, max_ds, "mlis_amd_create_tome") < 0) goto err;
+	S->tome_ratio = ratio; S->tome_max_ds = max_ds;
+	if (unet_plans_build(S) < 0) goto err;
 
+	/* ---- decoder plan, latent input bound to the same resident latent */
+	if (!codec_full_prepare(S, CODEC_DEC)) goto err;
+	return S;
+err:
+	mlis_amd_destroy(S);
+	return NULL;
+}
+
+/* The ControlNet plans and the UNet plan of an engine whose sizes and buffers stand (mlis_amd_create_tiled_packed; again from mlis_amd_set_tome, which destroyed the
+ * ControlNet and UNet contexts first: the hint plan, the gain and the FreeU factors are made once). */
+static int unet_plans_build(MLIS_AmdCtx* S)
+{
+	void *stream = S->stream;
+	/* tiled: the plan takes `pack` windows of every image.  It wraps only along an axis its window spans */
+	const int tiled = S->n_win > 0, ulw = tiled ? S->win_w : S->lw, ulh = tiled ? S->win_h : S->lh;
+	const int unet_wrap = tiled ? S->tiling & ((ulw == S->lw ? 1 : 0) | (ulh == S->lh ? 2 : 0)) : S->tiling;
 	/* ---- ControlNet: the hint plan at the canvas's pixel size and the ControlNet plan on the UNet plan's inputs, both before the UNet plan, which takes the residuals' addresses */
 	if (S->c.control & MLIS_AMD_CONTROL_NET) {
-		if (mlsd_malloc((void**)&S->d_gain, 256) || mlsd_memset(S->d_gain, 0, 256, stream)) goto err;
-		S->hint_ctx = mlctx_new(stream);
-		mlctx_set_conv_wrap(S->hint_ctx, S->tiling);
-		if (control_hint_init(S->hint_ctx, &S->unet_p, S->c.width, S->c.height, &S->t_hint_img) < 0) goto err;
-		if (control_hint_build(S->hint_ctx, &S->unet_p, S->t_hint_img) < 0) goto err;
-		if (!S->c.defer_weights && mlctx_params_synth(S->hint_ctx, S->c.weight_seed) < 0) goto err;
+		if (!S->hint_ctx) {
+			if (mlsd_malloc((void**)&S->d_gain, 256) || mlsd_memset(S->d_gain, 0, 256, stream)) goto err;
+			S->hint_ctx = mlctx_new(stream);
+			mlctx_set_conv_wrap(S->hint_ctx, S->tiling);
+			if (control_hint_init(S->hint_ctx, &S->unet_p, S->c.width, S->c.height, &S->t_hint_img) < 0) goto err;
+			if (control_hint_build(S->hint_ctx, &S->unet_p, S->t_hint_img) < 0) goto err;
+			if (!S->c.defer_weights && mlctx_params_synth(S->hint_ctx, S->c.weight_seed) < 0) goto err;
+		}
 		S->ctl_ctx = mlctx_new(stream);
 		mlctx_set_conv_wrap(S->ctl_ctx, unet_wrap);
 		mlctx_set_hypertile(S->ctl_ctx, S->ht_px, S->ht_depth);
+		mlctx_set_tome(S->ctl_ctx, S->tome_ratio, S->tome_max_ds);
 		if (S->c.use_hipgraph && S->c.unet_split <= 0) mlctx_set_flags(S->ctl_ctx, MLB_F_HIPGRAPH);      /* (its weights stay resident with unet_split too) */
 		if (controlnet_init_nc(&S->ctl, S->ctl_ctx, &S->unet_p, ulw, ulh, S->CN, S->c.n_ctx_tok) < 0) goto err;
 		if (mlctx_input_bind(S->ctl.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
@@ -282,13 +312,14 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	S->unet_ctx = mlctx_new(stream);
 	mlctx_set_conv_wrap(S->unet_ctx, unet_wrap);
 	mlctx_set_hypertile(S->unet_ctx, S->ht_px, S->ht_depth);
+	mlctx_set_tome(S->unet_ctx, S->tome_ratio, S->tome_max_ds);
 	mlctx_set_pag(S->unet_ctx, S->pag ? S->PB : 0);
 	if (S->c.unet_split > 0) {     /* --unet-split: the UNet's weights are streamed through three slabs (mlblock.c "weight streaming"); one evaluation = one pass over them */
 		if (mlctx_set_weight_streaming(S->unet_ctx, S->c.unet_split > 1 ? (size_t)S->c.unet_split << 20 : 0) < 0) goto err;
 	} else if (S->c.use_hipgraph) mlctx_set_flags(S->unet_ctx, MLB_F_HIPGRAPH);
 	if (unet_denoise_init_nc(&S->unet, S->unet_ctx, &S->unet_p, ulw, ulh, S->PN, S->c.n_ctx_tok) < 0) goto err;
 	if (mlctx_input_bind(S->unet.t_x, S->d_xin, S->PB, S->d_cin, 1.0f, 0) < 0) { fail("input bind failed"); goto err; }
-	if (S->c.control & MLIS_AMD_CONTROL_FREEU) {      /* the factors live in device memory from the start: all 1, every FreeU pass of the plan a copy */
+	if ((S->c.control & MLIS_AMD_CONTROL_FREEU) && !S->d_freeu) {      /* the factors live in device memory from the start: all 1, every FreeU pass of the plan a copy */
 		for (int i=0;i<4;++i) S->freeu_f[i] = 1;
 		if (mlsd_malloc((void**)&S->d_freeu, 256) || mlsd_memset(S->d_freeu, 0, 256, stream) || mlsd_memcpy(S->d_freeu, S->freeu_f, sizeof(S->freeu_f), 0, stream)
 				|| mlsd_stream_sync(stream)) goto err;
@@ -296,13 +327,41 @@ MLB_API MLIS_AmdCtx* mlis_amd_create_tiled_packed(const MLIS_AmdConfig* cfg, int
 	}
 	if (unet_denoise_build_freeu(&S->unet, (S->c.control & MLIS_AMD_CONTROL_NET) ? &S->ctl_k : NULL, (S->c.control & MLIS_AMD_CONTROL_FREEU) ? &S->fu : NULL) < 0) goto err;
 	if (!S->c.defer_weights && mlctx_params_synth(S->unet_ctx, S->c.weight_seed) < 0) goto err;
-
-	/* ---- decoder plan, latent input bound to the same resident latent */
-	if (!codec_full_prepare(S, CODEC_DEC)) goto err;
-	return S;
+	return 1;
 err:
-	mlis_amd_destroy(S);
-	return NULL;
+	return -1;
+}
+
+/* ------------------------------------------------------------------ token merging: the setting is built into the UNet (and ControlNet) plan, so a change rebuilds them */
+static int tome_clash(const MLIS_AmdCtx* S, float ratio, int max_ds)
+{	/* a level the setting would merge that HyperTile cuts (the plan's own size: a tiled engine's window) */
+	return unet_tome_hypertile_clash(&S->unet_p, S->n_win ? S->win_w : S->lw, S->n_win ? S->win_h : S->lh, ratio, max_ds, S->ht_px, S->ht_depth);
+}
+
+static int tome_check(const MLIS_AmdCtx* S, float ratio, int max_ds, const char* what)
+{
+	if (!(ratio >= 0 && ratio <= 0.75f)) return mlsd_set_error(-4, "%s: ratio %g (0 .. 0.75)", what, (double)ratio);
+	if (max_ds != 0 && max_ds != 1 && max_ds != 2 && max_ds != 4 && max_ds != 8) return mlsd_set_error(-4, "%s: max_ds %d (0, 1, 2, 4 or 8)", what, max_ds);
+	if (tome_clash(S, ratio, max_ds)) return mlsd_set_error(-4, "%s: HyperTile cuts a level that ratio %g, max_ds %d would merge", what, (double)ratio, max_ds);
+	return 1;
+}
+
+MLB_API int mlis_amd_set_tome(MLIS_AmdCtx* S, float ratio, int max_ds)
+{
+	if (!S || !S->unet_ctx) return fail("mlis_amd_set_tome: no engine");
+	if (tome_check(S, ratio, max_ds, "mlis_amd_set_tome") < 0) return -4;
+	if (ratio == S->tome_ratio && max_ds == S->tome_max_ds) return 1;
+	mlsd_stream_sync(S->stream);
+	mlctx_destroy(S->unet_ctx); S->unet_ctx = NULL;
+	if (S->ctl_ctx) { mlctx_destroy(S->ctl_ctx); S->ctl_ctx = NULL; }
+	S->tome_ratio = ratio; S->tome_max_ds = max_ds;
+	return unet_plans_build(S);
+}
+
+MLB_API int mlis_amd_tome_plan_info(const MLIS_AmdCtx* S, float* ratio, int* max_ds, int* n_merged, int levels[4][3])
+{
+	if (!S || !S->unet_ctx) return fail("mlis_amd_tome_plan_info: no engine");
+	return mlctx_tome_info(S->unet_ctx, ratio, max_ds, n_merged, levels);
 }
 
 /* sampler options may change between generations without rebuilding the plans (the reference re-reads them in dnsamp_init on

@@ -88,6 +88,7 @@ static void ctx_reset_(MLCtx* C)
 	memset(&C->info, 0, sizeof(C->info));
 	C->ht.nt = C->ht.n_tiled = C->ht.n_untiled = 0; memset(C->ht.tiles, 0, sizeof(C->ht.tiles));      /* (tile_px / depth are settings of the context, like conv_wrap) */
 	C->pag.cur = C->pag.n_attn = 0;                                                                   /* (and so is pag.n_img) */
+	C->tome.max_ds_res = C->tome.skip = C->tome.r = C->tome.n_merged = 0; memset(C->tome.levels, 0, sizeof(C->tome.levels));      /* (and tome.ratio / max_ds) */
 }
 
 MLB_API void mlctx_destroy(MLCtx* C)
@@ -122,6 +123,20 @@ MLB_API int mlctx_hypertile_info(const MLCtx* C, int* n_tiled, int* n_untiled, i
 	if (n_tiled) *n_tiled = C->ht.n_tiled;
 	if (n_untiled) *n_untiled = C->ht.n_untiled;
 	if (tiles) memcpy(tiles, C->ht.tiles, sizeof(C->ht.tiles));
+	return 1;
+}
+MLB_API void mlctx_set_tome(MLCtx* C, float ratio, int max_ds)
+{
+	const int ds_ok = max_ds == 0 || max_ds == 1 || max_ds == 2 || max_ds == 4 || max_ds == 8;
+	C->tome.ratio = (ratio > 0 && ratio <= 0.75f && ds_ok) ? ratio : 0; C->tome.max_ds = ds_ok ? max_ds : 0;
+}
+MLB_API int mlctx_tome_info(const MLCtx* C, float* ratio, int* max_ds, int* n_merged, int levels[4][3])
+{
+	if (!C) return -1;
+	if (ratio) *ratio = C->tome.ratio;
+	if (max_ds) *max_ds = C->tome.max_ds_res ? C->tome.max_ds_res : C->tome.max_ds;
+	if (n_merged) *n_merged = C->tome.n_merged;
+	if (levels) memcpy(levels, C->tome.levels, sizeof(C->tome.levels));
 	return 1;
 }
 MLB_API void mlctx_set_pag(MLCtx* C, int n_img) { C->pag.n_img = n_img > 0 ? n_img : 0; }

@@ -118,6 +118,10 @@ struct MLCtx {
 	 * set to it only while the middle block's transformer layers are being built: mlb_attn_mhead_ex then records a SELF-attention without the q, k projections and the
 	 * attention of those images, their attention output is v_proj of their rows (one more GEMM on the v slice of the fused weight); 0 elsewhere.  n_attn counts them */
 	struct { int n_img, cur, n_attn; } pag;
+	/* Token merging (mlctx_set_tome; mlb_spatial_transf of unet.c).  ratio / max_ds are the setting (max_ds 0 is resolved by the UNet builder into max_ds_res); skip is set
+	 * while the middle block is built; r is set only while the transformer layers of a merged level are being built: mlb_basic_transf then records its self-attention on
+	 * T - r rows (match, select, merge; the three launches; unmerge in place of out_proj's residual); 0 elsewhere.  n_merged counts them, levels holds T, r, T' per depth */
+	struct { float ratio; int max_ds, max_ds_res, skip, r, n_merged, levels[4][3]; } tome;
 	int err;
 	/* plan */
 	MLOp* ops; int n_ops, cap_ops;

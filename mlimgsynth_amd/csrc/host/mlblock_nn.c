@@ -550,6 +550,53 @@ MLB_API MLTensor* mlb_attn_mhead(MLCtx* C, MLTensor* q, MLTensor* k, MLTensor* v
 	return mlb_attn_mhead_ex(C, q, k, v, d_out, d_embed, n_head, mask, bias, bias_out, NULL);
 }
 
+/* ------------------------------------------------------------------ token merging (mlctx_set_tome; the rule: mlsd_tome_* of mlsd_kernels.h) */
+/* one token-merging launch on the copy kind (mlb_copy_args.tome): nbytes is the whole extent written at dst */
+static mlb_copy_args* tome_op(MLCtx* C, int form, const char* label, const MLTensor* map, const void* src, void* dst, size_t nbytes, int row_bytes)
+{
+	MLOp *op = mlctx_op_new(C, OP_COPY_F32, label);
+	mlb_copy_args *a = &op->u.copy;
+	a->src = src; a->dst = dst; a->nbytes = nbytes; a->n_img = map->n; a->H = map->h; a->W = map->w; a->row_bytes = row_bytes; a->tome = form; a->r = C->tome.r;
+	return a;
+}
+
+/* attn1 of a transformer layer on a merged level (C->tome.r > 0): match, select and merge on the rows n = norm1(x); the fused q|k|v projection, the attention and
+ * out_proj (bias, no residual) on the T - r merged rows; then x + o[slot] as a fresh fp32 tensor, the addition out_proj's epilogue makes elsewhere.  That tensor has no
+ * producing GEMM: the LayerNorm behind it runs as a launch of its own.  The scratch is plan memory, free again for whatever is recorded behind its last reader. */
+static MLTensor* tome_attn1(MLCtx* C, MLTensor* n, MLTensor* x, int d_out, int d_embed, int n_head)
+{
+	if (!n || C->err) return NULL;
+	const int r = C->tome.r, Tn = n->h * n->w, Ns = Tn - (n->h / 2) * (n->w / 2), Tm = Tn - r, Cn = n->c;
+	const void *nd = mlt_need16(C, n);
+	const float *xd = mlt_need32(C, x);
+	if (!nd || !xd) return NULL;
+	if (n->ld16 != Cn || Cn % 32 || Cn < 64 || Cn > 1280 || d_out != x->c || d_out % 4 || r < 16 || r > Ns) {
+		mlctx_fail(C, "tome: %d of %d x %d tokens of %d halfs at stride %lld into %d columns", r, n->h, n->w, Cn, (long long)n->ld16, d_out); return NULL;
+	}
+	const size_t sz_bs = (size_t)n->n * Ns * 8, sz_l = (size_t)n->n * mlsd_tome_lists_ints(n->h, n->w, r) * 4;
+	void *bs = mlctx_dalloc(C, sz_bs, 0), *lists = mlctx_dalloc(C, sz_l, 0);
+	MLTensor *m = mlt_new(C, n->n, 1, Tm, Cn);
+	m->sz16 = (size_t)n->n * Tm * Cn * 2; m->d16 = mlctx_dalloc(C, m->sz16, 0); m->ld16 = Cn;
+	if (!bs || !lists || !m->d16) return NULL;
+	tome_op(C, MLB_TOME_MATCH, "tome_match", n, nd, bs, sz_bs, Cn * 2);
+	tome_op(C, MLB_TOME_SELECT, "tome_select", n, bs, lists, sz_l, Cn * 2);
+	tome_op(C, MLB_TOME_MERGE, "tome_merge", n, nd, m->d16, m->sz16, Cn * 2)->aux = lists;
+	mlctx_drelease(C, bs, sz_bs);
+	MLTensor *o = mlb_attn_mhead_ex(C, m, m, m, d_out, d_embed, n_head, false, false, true, NULL);
+	const float *od = mlt_need32(C, o);
+	if (!od) return NULL;
+	mlb_release(C, m);
+	MLTensor *y = mlt_new(C, x->n, x->h, x->w, d_out);
+	y->sz32 = (size_t)rows_of(x) * d_out * sizeof(float); y->d32 = (float*)mlctx_dalloc(C, y->sz32, 0); y->ld32 = d_out;
+	if (!y->d32) return NULL;
+	mlb_copy_args *u = tome_op(C, MLB_TOME_UNMERGE, "tome_unmerge", n, od, y->d32, y->sz32, d_out * 4);
+	u->aux = lists; u->aux2 = xd; u->ld2 = x->ld32;
+	mlb_release(C, o);
+	mlctx_drelease(C, lists, sz_l);
+	C->tome.n_merged++;
+	return y;
+}
+
 /* ------------------------------------------------------------------ transformer block (src/mlblock_nn.c:234-253) */
 MLB_API MLTensor* mlb_basic_transf(MLCtx* C, MLTensor* x, MLTensor* c, int d_out, int d_embed, int n_head)
 {
@@ -557,7 +604,8 @@ MLB_API MLTensor* mlb_basic_transf(MLCtx* C, MLTensor* x, MLTensor* c, int d_out
 	mlctx_block_begin(C);
 	MLTensor *r = x, *n, *y;
 	n = MLN("norm1", mlb_layer_norm_ex(C, x, 0, 0));
-	y = MLN("attn1", mlb_attn_mhead_ex(C, n, n, n, d_out, d_embed, n_head, false, false, true, r));
+	if (C->tome.r > 0) y = MLN("attn1", tome_attn1(C, n, r, d_out, d_embed, n_head));
+	else y = MLN("attn1", mlb_attn_mhead_ex(C, n, n, n, d_out, d_embed, n_head, false, false, true, r));
 	mlb_release(C, n);
 	if (!y || !mlt_need32(C, y)) return NULL;
 	mlb_release(C, r);

@@ -50,6 +50,19 @@ static int run_smax(const MLOp* op, void* st)
 static int run_copy(const MLOp* op, void* st)
 {
 	const mlb_copy_args *a = &op->u.copy;
+	if (a->tome) {      /* token merging (mlb_copy_args.tome, mlblock_amd.h; recorded by mlb_basic_transf) */
+		const int Ns = a->H * a->W - (a->H / 2) * (a->W / 2);
+		const int *best = (const int*)(a->tome == MLB_TOME_MATCH ? a->dst : a->src);
+		const float *score = (const float*)(best + (size_t)a->n_img * Ns);
+		switch (a->tome) {
+		case MLB_TOME_MATCH: return mlsd_tome_match(a->src, a->row_bytes / 2, a->n_img, a->H, a->W, a->row_bytes / 2, (int*)a->dst, (float*)score, st);
+		case MLB_TOME_SELECT: return mlsd_tome_select(score, best, a->n_img, a->H, a->W, a->r, (int*)a->dst, st);
+		case MLB_TOME_MERGE: return mlsd_tome_merge(a->src, a->row_bytes / 2, a->n_img, a->H, a->W, a->row_bytes / 2, a->r, (const int*)a->aux, a->dst, st);
+		case MLB_TOME_UNMERGE: return mlsd_tome_unmerge_add((const float*)a->aux2, a->ld2, (const float*)a->src, a->row_bytes / 4, a->n_img, a->H, a->W, a->row_bytes / 4, a->r,
+			(const int*)a->aux, (float*)a->dst, a->row_bytes / 4, st);
+		default: return mlsd_set_error(-1, "copy: token-merging form %d", a->tome);
+		}
+	}
 	if (a->th > 0) return mlsd_tile_permute(a->src, a->dst, a->n_img, a->H, a->W, a->th, a->tw, a->row_bytes, a->inverse, st);      /* HyperTile's row permutation */
 	return mlsd_memcpy(a->dst, a->src, a->nbytes, 2, st);
 }

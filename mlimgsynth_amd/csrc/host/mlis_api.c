@@ -58,6 +58,7 @@ struct MLIS_Ctx {
 	int inp_region[4], inp_proc[2], inp_done;
 	int control_rect_on, control_rect[4], control_rect_W, control_rect_H;      /* the region a masked pass hands to control_apply, of an image of that size */
 	int freeu; float freeu_f[4];            /* MLIS_OPT_AMD_FREEU*: on / off (part of the engine key) and b1, b2, s1, s2 (device data of the engine: never rebuild anything) */
+	float tome_ratio; int tome_max_ds;      /* mlis_amd_tome: token merging ratio (0 = off) and the deepest merged UNet downscale (0 = the shallowest with transformers); both part of the engine key */
 	int vae_attn;                           /* mlis_amd_vae_attn: MLIS_AMD_VAE_ATTN_*, handed to the engine before every pass (never part of the engine key) */
 	int glimit_mode; float glimit_a, glimit_b;      /* mlis_amd_guidance_limit: MLIS_AMD_GLIMIT_* and its two parameters, handed to the engine per generation (never part of the engine key) */
 	int cfix_mode, cfix_levels, cfix_applied;       /* mlis_amd_color_fix: MLIS_AMD_COLORFIX_*, the wavelet's levels, the images the last generation corrected (never part of the engine key) */
@@ -326,6 +327,23 @@ MLB_API int mlis_amd_vae_attn_info(MLIS_Ctx* S, int* mode, int* plan_mode)
 	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
 	if (mode) *mode = S->vae_attn;
 	if (plan_mode) *plan_mode = S->eng ? mlis_amd_vae_attn_mode(S->eng) : -1;
+	return 1;
+}
+MLB_API int mlis_amd_tome(MLIS_Ctx* S, float ratio, int max_ds)
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	if (!(ratio >= 0 && ratio <= 0.75f) || (max_ds != 0 && max_ds != 1 && max_ds != 2 && max_ds != 4 && max_ds != 8))
+		return api_error(S, MLIS_E_OPT_VALUE, "token merging: ratio %g (0 .. 0.75), max_ds %d (0, 1, 2, 4 or 8)", (double)ratio, max_ds);
+	S->tome_ratio = ratio; S->tome_max_ds = max_ds;      /* (part of the engine key: engine_get) */
+	return 1;
+}
+MLB_API int mlis_amd_tome_info(MLIS_Ctx* S, float* ratio, int* max_ds, int levels[4][3])
+{
+	if (!S || S->signature != CTX_SIGNATURE) return MLIS_E_UNKNOWN;
+	UnetParams P;
+	if (ratio) *ratio = S->tome_ratio;
+	if (max_ds) *max_ds = (!str_empty(S->mname) && unet_params_get(S->mname, &P) >= 0) ? unet_tome_max_ds(&P, S->tome_max_ds) : S->tome_max_ds;
+	if (levels) { memset(levels, 0, sizeof(int) * 12); if (S->eng) mlis_amd_tome_plan_info(S->eng, NULL, NULL, NULL, levels); }
 	return 1;
 }
 MLB_API int mlis_amd_guidance_limit(MLIS_Ctx* S, int mode, float a, float b)
@@ -1270,6 +1288,23 @@ static int hypertile_cuts(const char* model, int lw, int lh, int tile_px, int de
 	return unet_hypertile_cuts(&P, lw, lh, tile_px, depth);
 }
 
+/* token merging: a pass none of whose levels comes out with r > 0 takes the plain engine under the plain key (unet_tome_levels, host/unet.c) */
+static int tome_merges(const char* model, int lw, int lh, float ratio, int* max_ds, int tile_px, int depth, int* clash)
+{	/* *max_ds comes back resolved (0 and the model's shallowest level are one engine, one key); *clash: HyperTile cuts a level the setting merges */
+	UnetParams P;
+	*clash = 0;
+	if (!(ratio > 0)) return 0;
+	if (unet_params_get(model, &P) < 0) return 1;
+	*max_ds = unet_tome_max_ds(&P, *max_ds);
+	*clash = unet_tome_hypertile_clash(&P, lw, lh, ratio, *max_ds, tile_px, depth);
+	return unet_tome_levels(&P, lw, lh, ratio, *max_ds, NULL);
+}
+static int engine_has_tome(MLIS_AmdCtx* e, float ratio)
+{	/* (asked of the engine, as engine_has_control is: an engine's setting is 0 or the ratio in its key) */
+	float r = 0;
+	return e && mlis_amd_tome_plan_info(e, &r, NULL, NULL, NULL) > 0 && r == ratio;
+}
+
 static int engine_get(MLIS_Ctx* S, int lw, int lh)
 {
 	const int f = 8, B = S->n_batch > 0 ? S->n_batch : 1, tae = !!(S->flags & CF_USE_TAE);
@@ -1288,6 +1323,10 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	const int plw = tile && tile / f < lw ? tile / f : lw, plh = tile && tile / f < lh ? tile / f : lh;
 	const int hypertile = hypertile_cuts(S->mname, plw, plh, S->hypertile, S->hypertile_depth) ? S->hypertile : 0;
 	if (hypertile && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/h%dd%d", hypertile, S->hypertile_depth);
+	int tome_ds = S->tome_max_ds, tome_clash = 0;
+	const float tome = tome_merges(S->mname, plw, plh, S->tome_ratio, &tome_ds, hypertile, S->hypertile_depth, &tome_clash) ? S->tome_ratio : 0;
+	if (tome_clash) return api_error(S, MLIS_E_OPT_VALUE, "token merging: HyperTile cuts a level that ratio %g, max_ds %d merges at %d x %d", (double)tome, tome_ds, plw * f, plh * f);
+	if (tome > 0 && nk > 0 && nk < (int)sizeof(key)) nk += snprintf(key + nk, sizeof(key) - nk, "/m%.6gd%d", (double)tome, tome_ds);
 	const int pag = S->pag_scale > 0;                     /* (the scale is an argument of the mix kernels: only on / off is built in) */
 	if (pag && nk > 0 && nk < (int)sizeof(key)) snprintf(key + nk, sizeof(key) - nk, "/p1");
 	if (pag) {      /* the third row group must fit what an engine holds per plan evaluation: refused here as a bad option value, before anything is built */
@@ -1302,7 +1341,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 	int n_step, method, sched;
 	sampler_defaults(S, &n_step, &method, &sched);
 	/* (a slot serves when its key matches AND it holds a ControlNet exactly if one is wanted: a key cut short by a long model name cannot pass one for the other) */
-#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control && engine_has_freeu(e) == freeu && engine_has_pag(e) == pag)
+#define SLOT_IS(e, k) ((e) && !strcmp(key, (k)) && engine_has_control(e) == control && engine_has_freeu(e) == freeu && engine_has_pag(e) == pag && engine_has_tome(e, tome))
 	if (!SLOT_IS(S->eng, S->eng_key) && SLOT_IS(S->eng2, S->eng2_key)) {      /* the other resident engine: they change places */
 		MLIS_AmdCtx *e = S->eng; char k[sizeof(S->eng_key)]; memcpy(k, S->eng_key, sizeof(k));
 		S->eng = S->eng2; memcpy(S->eng_key, S->eng2_key, sizeof(k));
@@ -1323,7 +1362,7 @@ static int engine_get(MLIS_Ctx* S, int lw, int lh)
 		c.n_ctx_tok = ctx_tok;                                  /* windowed prompt: the UNet's cross attentions see 77 W context rows */
 		c.control = (control ? MLIS_AMD_CONTROL_NET : 0) | (freeu ? MLIS_AMD_CONTROL_FREEU : 0) | MLIS_AMD_CONTROL_HYPERTILE_OF(hypertile, S->hypertile_depth) |
 			(pag ? MLIS_AMD_CONTROL_PAG : 0);
-		S->eng = mlis_amd_create_tiled_packed(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, NULL);
+		S->eng = mlis_amd_create_tome(&c, S->tiling, tile, tile, overlap, S->unet_tile_batch, tome, tome > 0 ? tome_ds : 0, NULL);
 		if (!S->eng) return api_error_lib(S, MLIS_E_UNKNOWN);
 		S->n_eng_builds++;
 		mlctx_set_wtype(mlis_amd_unet_ctx(S->eng), S->wtype);
@@ -1977,6 +2016,7 @@ static void infotext_update(MLIS_Ctx* S, int w, int h, int hires_n_step)
 	if (!str_empty(S->path_control)) ADD(", ControlNet: %.*s, Control strength: %g, Control window: %g-%g", nb, b, S->control_strength, S->control_start, S->control_end);
 	if (S->freeu) ADD(", FreeU: %g %g %g %g", S->freeu_f[0], S->freeu_f[1], S->freeu_f[2], S->freeu_f[3]);
 	if (S->hypertile) ADD(", HyperTile: %d, HyperTile depth: %d", S->hypertile, S->hypertile_depth);
+	if (S->tome_ratio > 0) ADD(", Token merging ratio: %g", (double)S->tome_ratio);
 	if (S->pag_scale > 0) ADD(", PAG: %g", S->pag_scale);
 	if (S->cfg_rescale > 0) ADD(", CFG rescale: %g", S->cfg_rescale);
 	if (S->glimit_mode == MLIS_AMD_GLIMIT_DYNTHRESH && S->cfg_scale > 1) ADD(", Dynamic thresholding: %g/%g", S->glimit_a, S->glimit_b);

@@ -62,6 +62,42 @@ MLB_API int mlis_amd_hypertile_side(int side, int px_per_token, int tile_px)
 	return m;
 }
 
+/* token merging: max_ds 0 of mlctx_set_tome is the shallowest level of this model that has transformers (1 for SD1.5, 2 for SDXL) */
+MLB_API int unet_tome_max_ds(const UnetParams* P, int max_ds)
+{
+	if (max_ds) return max_ds;
+	for (int ds = 1; ds <= 8; ds *= 2) if (static_vector_in(P->attn_res, ds)) return ds;
+	return 0;
+}
+static void unet_tome_resolve(MLCtx* C, const UnetParams* P) { C->tome.max_ds_res = unet_tome_max_ds(P, C->tome.max_ds); }
+
+/* the levels of a UNet plan of lw x lh latent pixels that token merging would merge with this setting: T, r, T' per depth (the walk of unet_hypertile_cuts below; never
+ * the middle block); returns how many self-attentions that is, 0: the plan is the plain plan */
+MLB_API int unet_tome_levels(const UnetParams* P, int lw, int lh, float ratio, int max_ds, int levels[4][3])
+{
+	int n = 0;
+	if (levels) memset(levels, 0, sizeof(int) * 12);
+	if (!(ratio > 0)) return 0;
+	max_ds = unet_tome_max_ds(P, max_ds);
+	for (int im=0, ds=1, w=lw, h=lh; P->ch_mult[im] && im < 4; ++im, ds*=2, w=(w+1)/2, h=(h+1)/2) {
+		const int r = (static_vector_in(P->attn_res, ds) && ds <= max_ds) ? mlsd_tome_r(h, w, ratio) : 0;
+		if (r <= 0) continue;
+		n += (2 * P->n_res_blk + 1) * P->transf_depth[im];
+		if (levels) { levels[im][0] = h * w; levels[im][1] = r; levels[im][2] = h * w - r; }
+	}
+	return n;
+}
+
+/* 1 where HyperTile (tile_px, depth) cuts a level of that plan which token merging (ratio, max_ds) would merge: such an engine is refused */
+MLB_API int unet_tome_hypertile_clash(const UnetParams* P, int lw, int lh, float ratio, int max_ds, int tile_px, int depth)
+{
+	int lv[4][3];
+	if (tile_px <= 0 || !unet_tome_levels(P, lw, lh, ratio, max_ds, lv)) return 0;
+	for (int im=0, ds=1, w=lw, h=lh; im<4; ++im, ds*=2, w=(w+1)/2, h=(h+1)/2)
+		if (lv[im][1] && im <= depth && (mlis_amd_hypertile_side(h, 8 * ds, tile_px) != h || mlis_amd_hypertile_side(w, 8 * ds, tile_px) != w)) return 1;
+	return 0;
+}
+
 /* one permuting copy of a tiled spatial transformer: the dense fp16 rows of `t` (n maps of h x w tokens) into a fresh fp16 tensor, image order -> tile-major order
  * or back (mlsd_tile_permute).  It rides on the copy kind: nbytes is the whole extent, the geometry says how the rows move. */
 static MLTensor* mlb_tile_permute16(MLCtx* C, MLTensor* t, int th, int tw, int inverse)
@@ -120,12 +156,18 @@ static MLTensor* mlb_spatial_transf(MLCtx* C, MLTensor* x, MLTensor* ctx,
 	if (!x || !mlt_need32(C, x)) return NULL;
 	mlb_release(C, h);
 	if (tiled) C->ht.nt = (x0->h / th) * (x0->w / tw);
+	/* token merging (mlctx_set_tome): the self-attentions of this block run on merged rows where the level is shallow enough, is not the middle block and its r is not 0 */
+	const int tome_max = C->tome.max_ds_res ? C->tome.max_ds_res : C->tome.max_ds;
+	const int tome_r = (C->tome.ratio > 0 && !C->tome.skip && tome_max > 0 && ds <= tome_max) ? mlsd_tome_r(x0->h, x0->w, C->tome.ratio) : 0;
+	if (tome_r > 0 && tiled) { C->ht.nt = 0; mlctx_fail(C, "token merging and HyperTile on the same level (downscale %d)", ds); return NULL; }
+	if (tome_r > 0 && lvl < 4) { int *q = C->tome.levels[lvl]; q[0] = x0->h * x0->w; q[1] = tome_r; q[2] = q[0] - tome_r; }
+	C->tome.r = tome_r;
 	for (int i=0; i<n_depth; ++i) {
 		sprintf(name, "transf.%d", i);
 		x = MLN(name, mlb_basic_transf(C, x, ctx, d_embed, d_embed, n_head));   /* consumes x */
-		if (!x) { C->ht.nt = 0; return NULL; }
+		if (!x) { C->ht.nt = 0; C->tome.r = 0; return NULL; }
 	}
-	C->ht.nt = 0;
+	C->ht.nt = 0; C->tome.r = 0;
 	if (tiled) {
 		MLTensor *xi = mlb_tile_permute16(C, x, th, tw, 1);
 		if (!xi) return NULL;
@@ -278,6 +320,7 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 {
 	char name[64];
 	mlctx_block_begin(C);
+	unet_tome_resolve(C, P);
 	if (mlb_cross_kv_batch(C, ctx, unet_cross_kv_width(P)) < 0) return NULL;
 	MLTensor *emb = mlb_unet__embed(C, time, label, P);
 	if (!emb) return NULL;
@@ -322,9 +365,9 @@ MLB_API MLTensor* mlb_unet_denoise_freeu(MLCtx* C, MLTensor* x, MLTensor* time, 
 		if (!y || !mlt_need32(C, y)) return NULL;
 		x = y;
 		/* perturbed-attention guidance (mlctx_set_pag): the self-attentions of this block, and of no other, treat the plan's last pag.n_img images as perturbed */
-		C->pag.cur = C->pag.n_img;
+		C->pag.cur = C->pag.n_img; C->tome.skip = 1;      /* (token merging never touches this block) */
 		y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
-		C->pag.cur = 0;
+		C->pag.cur = 0; C->tome.skip = 0;
 		if (!y || !mlt_need32(C, y)) return NULL;
 		mlb_release(C, x); x = y;
 		y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));
@@ -644,6 +687,7 @@ MLB_API MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTenso
 {
 	char name[64];
 	mlctx_block_begin(C);
+	unet_tome_resolve(C, P);
 	if (mlb_cross_kv_batch(C, ctx, unet_cross_kv_width_ex(P, 0)) < 0) return NULL;
 	MLTensor *emb = mlb_unet__embed(C, time, label, P);
 	if (!emb) return NULL;
@@ -690,7 +734,9 @@ MLB_API MLTensor* mlb_controlnet(MLCtx* C, ControlState* S, MLTensor* x, MLTenso
 	MLTensor *y = MLN("mid.0", mlb_resnet_ex(C, x, emb, ch));
 	if (!y || !mlt_need32(C, y)) return NULL;
 	mlb_release(C, x); x = y;
+	C->tome.skip = 1;
 	y = MLN("mid.1", mlb_spatial_transf(C, x, ctx, ch, P->d_head, P->n_head, P->transf_depth[im], ds));
+	C->tome.skip = 0;
 	if (!y || !mlt_need32(C, y)) return NULL;
 	mlb_release(C, x); x = y;
 	y = MLN("mid.2", mlb_resnet_ex(C, x, emb, ch));

@@ -172,6 +172,31 @@ def set_vae_attn(ctx, mode):
     f(ctx.h, int(mode))
 
 
+def set_tome(ctx, ratio, max_ds=0):
+    """mlctx_set_tome: token merging for the spatial transformers the context builds from now on (ratio 0: off; a value outside 0 .. 0.75 counts as 0)."""
+    f = L().mlctx_set_tome
+    f.restype, f.argtypes = None, [vp, c_f, c_int]
+    f(ctx.h, float(ratio), int(max_ds))
+
+
+def tome_info(ctx):
+    """mlctx_tome_info: (ratio, max_ds as resolved, merged self-attentions, [(T, r, T') per depth 0 .. 3])"""
+    f = L().mlctx_tome_info
+    f.restype, f.argtypes = c_int, [vp, ctypes.POINTER(c_f), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    a, b, n, t = c_f(), c_int(), c_int(), (c_int * 12)()
+    check1(f(ctx.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), t), "mlctx_tome_info")
+    return a.value, b.value, n.value, [tuple(int(t[3 * i + j]) for j in range(3)) for i in range(4)]
+
+
+def tome_levels(model, lw, lh, ratio, max_ds=0):
+    """unet_tome_levels: (merged self-attentions, [(T, r, T') per depth]) of a UNet plan of lw x lh latent pixels, from the sizes alone"""
+    f = L().unet_tome_levels
+    f.restype, f.argtypes = c_int, [ctypes.POINTER(UnetParams), c_int, c_int, c_f, c_int, ctypes.POINTER(c_int)]
+    P, t = unet_params(model), (c_int * 12)()
+    n = f(ctypes.byref(P), int(lw), int(lh), float(ratio), int(max_ds), t)
+    return int(n), [tuple(int(t[3 * i + j]) for j in range(3)) for i in range(4)]
+
+
 def set_hypertile(ctx, tile_px, depth=3):
     """mlctx_set_hypertile: HyperTile for the spatial transformers the context builds from now on (tile_px 0: off)."""
     f = L().mlctx_set_hypertile
@@ -372,9 +397,11 @@ class Unet:
     """unet_denoise_init_n / unet_denoise_run_n (src/unet.c:336-498) with a batch dimension."""
 
     def __init__(self, model, lw, lh, n_batch, stream=None, flags=0, seed=1234, synth=True, stream_weights_mib=0, n_ctx_tok=77,
-                 hypertile=0, hypertile_depth=3, pag=0, tiling=0):
+                 hypertile=0, hypertile_depth=3, pag=0, tome=0.0, tome_max_ds=0, tiling=0):
         self.P = unet_params(model)
         self.ctx = MLCtx(stream, flags)
+        if tome:                        # token merging: self-attention on T - r merged rows at the levels with downscale <= tome_max_ds (0: the shallowest)
+            set_tome(self.ctx, tome, tome_max_ds)
         if hypertile:                   # HyperTile: self-attention inside tiles of `hypertile` image pixels, UNet levels 0 .. hypertile_depth
             set_hypertile(self.ctx, hypertile, hypertile_depth)
         if pag:                         # perturbed-attention guidance: the plan's last `pag` images are the perturbed group (mlctx_set_pag)
@@ -628,7 +655,7 @@ class Generator:
     def __init__(self, model, width, height, n_batch, n_step=20, cfg_scale=7.0, s_ancestral=1.0, sched=1, use_tae=False,
                  use_hipgraph=False, weight_seed=1234, stream=None, method="euler", s_noise=0.0, f_t_ini=1.0, f_t_end=0.0,
                  defer_weights=False, unet_split=0, n_ctx_tok=77, unet_tile=0, unet_tile_overlap=0, unet_tile_batch=1, control=False, freeu=False,
-                 hypertile=0, hypertile_depth=3, pag=False, vae_attn="scores", tiling=0):
+                 hypertile=0, hypertile_depth=3, pag=False, vae_attn="scores", tome=0.0, tome_max_ds=0, tiling=0):
         l = _proto2()
         self.cfg = AmdControlConfig(model.encode(), width, height, n_batch, n_step, cfg_scale, s_ancestral, sched, int(use_tae),
                              int(use_hipgraph), weight_seed, self.METHODS.get(method, method), s_noise, f_t_ini, f_t_end,
@@ -636,8 +663,13 @@ class Generator:
                              (CONTROL_NET if control else 0) | (CONTROL_FREEU if freeu else 0) |   # control: flags -- a ControlNet (set_control_image / set_control), FreeU (set_freeu),
                              control_hypertile(hypertile, hypertile_depth) |                       # HyperTile with a tile of `hypertile` pixels (hypertile_info),
                              (CONTROL_PAG if pag else 0))                                          # perturbed-attention guidance: a third row group (set_pag, pag_info)
-        if unet_tile:       # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
-            tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)      # times up to unet_tile_batch windows per evaluation
+        tw, th = unet_tile if isinstance(unet_tile, (tuple, list)) else (unet_tile, unet_tile)
+        if tome:            # token merging: the self-attentions of the UNet levels with downscale <= tome_max_ds on T - r merged rows (tome_info)
+            l.mlis_amd_create_tome.restype, l.mlis_amd_create_tome.argtypes = vp, [vp, c_int, c_int, c_int, c_int, c_int, c_f, c_int, vp]
+            self.h = l.mlis_amd_create_tome(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), float(tome),
+                                            int(tome_max_ds), vp(stream))
+        elif unet_tile:     # tiled diffusion: width x height is the canvas, the UNet plan has the size of one window (pixels; a pair gives w, h),
+            # times up to unet_tile_batch windows per evaluation
             self.h = l.mlis_amd_create_tiled_packed(ctypes.byref(self.cfg), int(tiling), int(tw), int(th), int(unet_tile_overlap), int(unet_tile_batch), vp(stream))
         else:
             self.h = l.mlis_amd_create_ex(ctypes.byref(self.cfg), int(tiling), vp(stream))    # tiling: 0 none, 1 x, 2 y, 3 xy (seamless)
@@ -648,6 +680,21 @@ class Generator:
         self.P = unet_params(model)
         if vae_attn != "scores":
             self.set_vae_attn(vae_attn)
+
+    def set_tome(self, ratio=0.5, max_ds=0):
+        """mlis_amd_set_tome: ratio 0 .. 0.75 (0 off), max_ds 0, 1, 2, 4 or 8 (0: the shallowest level with transformers).  A change rebuilds the UNet plan:
+        weights (unless synthetic) and conditioning are to be set again"""
+        f = _proto2().mlis_amd_set_tome
+        f.restype, f.argtypes = c_int, [vp, c_f, c_int]
+        check1(f(self.h, float(ratio), int(max_ds)), "mlis_amd_set_tome")
+
+    def tome_info(self):
+        """(ratio, max_ds as resolved, merged self-attentions of the UNet plan, [(T, r, T') per depth 0 .. 3, zeros where the depth is not merged])"""
+        f = _proto2().mlis_amd_tome_plan_info
+        f.restype, f.argtypes = c_int, [vp, ctypes.POINTER(c_f), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        a, b, n, t = c_f(), c_int(), c_int(), (c_int * 12)()
+        check1(f(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), t), "mlis_amd_tome_plan_info")
+        return a.value, b.value, n.value, [tuple(int(t[3 * i + j]) for j in range(3)) for i in range(4)]
 
     def set_cond(self, cond, label=None, uncond=None, unlabel=None):
         a = [np.ascontiguousarray(x, np.float32) if x is not None else None for x in (cond, label, uncond, unlabel)]

@@ -91,9 +91,13 @@ class SmaxArgs(ctypes.Structure):
 
 
 class CopyArgs(ctypes.Structure):
-    """mlb_copy_args: a device copy of nbytes; th > 0: the HyperTile row permutation (mlsd_tile_permute) of n_img maps of H x W rows of row_bytes"""
+    """mlb_copy_args: a device copy of nbytes; th > 0: the HyperTile row permutation (mlsd_tile_permute) of n_img maps of H x W rows of row_bytes; tome > 0: a
+    token-merging launch (TOME_MATCH .. TOME_UNMERGE; mlblock_amd.h says what src, dst, aux, aux2 are in each) with r merged sources per map"""
     _fields_ = [("src", vp), ("dst", vp), ("nbytes", ctypes.c_size_t), ("n_img", c_int), ("H", c_int), ("W", c_int), ("th", c_int), ("tw", c_int),
-                ("row_bytes", c_int), ("inverse", c_int)]
+                ("row_bytes", c_int), ("inverse", c_int), ("tome", c_int), ("r", c_int), ("aux", vp), ("aux2", vp), ("ld2", c_i64)]
+
+
+TOME_MATCH, TOME_SELECT, TOME_MERGE, TOME_UNMERGE = 1, 2, 3, 4       # mlb_copy_args.tome
 
 
 class CaddArgs(ctypes.Structure):
@@ -499,6 +503,53 @@ def tile_permute(src, dst, n_img, H, W, th, tw, row_bytes, inverse=False, stream
     """mlsd_tile_permute: dense [n_img][H W] rows of row_bytes bytes from image order into tile-major order (tiles of th x tw rows), or back with inverse
     (device pointers; 16-byte aligned, row_bytes a multiple of 16, no overlap)"""
     check(lib().mlsd_tile_permute(vp(src), vp(dst), n_img, H, W, th, tw, row_bytes, 1 if inverse else 0, vp(stream)), "mlsd_tile_permute")
+
+
+def tome_r(H, W, ratio):
+    """mlsd_tome_r: merged sources per map of H x W tokens at this ratio (min(floor(ratio T), Ns) rounded down to a multiple of 16)"""
+    f = lib().mlsd_tome_r
+    f.restype, f.argtypes = c_int, [c_int, c_int, ctypes.c_float]
+    return int(f(H, W, ratio))
+
+
+def tome_lists_ints(H, W, r):
+    """mlsd_tome_lists_ints: ints of one map's lists, slot[T] | kept[Ns - r] | off[Nd + 1] | members[r] | cnt[Nd]"""
+    f = lib().mlsd_tome_lists_ints
+    f.restype, f.argtypes = ctypes.c_size_t, [c_int, c_int, c_int]
+    return int(f(H, W, r))
+
+
+def tome_select_lds_limit(nbytes=-1):
+    """mlsd_tome_select_lds_limit: the most key bytes (Ns * 4) the selection keeps in LDS; sets it where nbytes >= 0 and returns the previous one"""
+    return int(lib().mlsd_tome_select_lds_limit(int(nbytes)))
+
+
+def tome_match(n, ld, n_img, H, W, C, best, score, stream=None):
+    """mlsd_tome_match: fp16 rows n [n_img][H W] at a stride of ld halfs -> best (int32), score (float32) [n_img][Ns] (device pointers)"""
+    f = lib().mlsd_tome_match
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, c_int, vp, vp, vp]
+    check(f(vp(n), ld, n_img, H, W, C, vp(best), vp(score), vp(stream)), "mlsd_tome_match")
+
+
+def tome_select(score, best, n_img, H, W, r, lists, stream=None):
+    """mlsd_tome_select: score, best [n_img][Ns] -> lists (int32, tome_lists_ints per map) (device pointers)"""
+    f = lib().mlsd_tome_select
+    f.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp]
+    check(f(vp(score), vp(best), n_img, H, W, r, vp(lists), vp(stream)), "mlsd_tome_select")
+
+
+def tome_merge(n, ld, n_img, H, W, C, r, lists, m, stream=None):
+    """mlsd_tome_merge: the rows n and the lists -> m, dense fp16 rows [n_img][H W - r] (device pointers)"""
+    f = lib().mlsd_tome_merge
+    f.argtypes = [vp, c_i64, c_int, c_int, c_int, c_int, c_int, vp, vp, vp]
+    check(f(vp(n), ld, n_img, H, W, C, r, vp(lists), vp(m), vp(stream)), "mlsd_tome_merge")
+
+
+def tome_unmerge_add(x, ldx, o, ldo, n_img, H, W, C, r, lists, y, ldy, stream=None):
+    """mlsd_tome_unmerge_add: y[t] = x[t] + o[slot[t]], fp32 rows (device pointers)"""
+    f = lib().mlsd_tome_unmerge_add
+    f.argtypes = [vp, c_i64, vp, c_i64, c_int, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp]
+    check(f(vp(x), ldx, vp(o), ldo, n_img, H, W, C, r, vp(lists), vp(y), ldy, vp(stream)), "mlsd_tome_unmerge_add")
 
 
 def freeu_ws_bytes(n_img, H, W, C):

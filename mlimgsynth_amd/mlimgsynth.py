@@ -89,6 +89,7 @@ _PROTOTYPES = {
     "mlis_amd_guidance_limit": (_I, [_V, _I, ctypes.c_float, ctypes.c_float]),
     "mlis_amd_guidance_limit_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I),
                                           ctypes.POINTER(ctypes.c_float), _I]),
+    "mlis_amd_tome": (_I, [_V, ctypes.c_float, _I]), "mlis_amd_tome_info": (_I, [_V, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_vae_attn": (_I, [_V, _I]), "mlis_amd_vae_attn_info": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "mlis_amd_tensor_resample_aa": (_I, [_V, _TP, _TP, _I, _I, _I]),
     "mlis_amd_lora_stats": (_I, [_V, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -603,6 +604,21 @@ class MLImgSynth:
             raise RuntimeError("Failed to read the VAE attention mode: %s" % self.errstr_get())
         name = {v: k for k, v in self.VAE_ATTN.items()}
         return dict(mode=name[a.value], plan_mode=name.get(b.value))
+
+    # ---- token merging (ToMe)
+    def tome_set(self, ratio=0.5, max_ds=0):
+        """The front ends' token merging ratio: before each self-attention of the UNet levels with downscale <= max_ds (1, 2, 4, 8; 0: the shallowest level with
+        transformers) the r = ratio x tokens most redundant tokens are merged into their most similar neighbour.  ratio 0 .. 0.75, 0 = off (default).  Part of the
+        engine key; parity-unpinned (the published rule as recalled, its random destination choice fixed)."""
+        if self._lib.mlis_amd_tome(self._ctx, float(ratio), int(max_ds)) < 0:
+            raise ValueError("tome: ratio 0 .. 0.75 and max_ds 0, 1, 2, 4 or 8, not %r, %r" % (ratio, max_ds))
+
+    def tome_info(self):
+        """dict: ratio, max_ds (as resolved for the loaded model), levels [(T, r, T') per UNet depth 0 .. 3 of the engine used last, zeros where not merged]."""
+        a, b, t = ctypes.c_float(), _I(), (_I * 12)()
+        if self._lib.mlis_amd_tome_info(self._ctx, ctypes.byref(a), ctypes.byref(b), t) < 0:
+            raise RuntimeError("Failed to read the token merging setting: %s" % self.errstr_get())
+        return dict(ratio=a.value, max_ds=b.value, levels=[tuple(int(t[3 * i + j]) for j in range(3)) for i in range(4)])
 
     def engine_builds(self):
         "Engines this context has constructed so far (it keeps the two used last)."

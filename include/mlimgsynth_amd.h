@@ -301,7 +301,11 @@ int mlctx_tstore_load_key(MLCtx* C, const MLTStore* S, const char* key);      /*
  * RRDBNet x4 (num_feat 64, num_grow_ch 32, num_block from the file) on mlsd_conv3x3_dense.  spec: a safetensors file with BasicSR's names (conv_first,
  * body.{i}.rdb{1..3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr, conv_last, each .weight and .bias; an optional "params_ema." / "params." prefix), or
  * "synth[:seed[:blocks]]" (default seed 1234, 2 blocks).  The x2 pixel-unshuffle variant (conv_first with 12 input channels), a missing tensor and a wrong shape fail
- * with the tensor's name in mlsd_last_error().  run: src [n_img][3][h][w] planar floats in 0..1 on the host -> dst [n_img][3][4h][4w] (not clamped); the work buffers
+ * with the tensor's name in mlsd_last_error().  A file with a four-dimensional body.0.weight and no conv_first.weight is a Real-ESRGAN COMPACT net (SRVGGNetCompact,
+ * include/mlsd_kernels.h at mlsd_conv3x3_compact states it): body.{0, 2, .., 2N+2}.weight / .bias convolutions and body.{1, 3, .., 2N+1}.weight PReLU slopes, N in 1 .. 64,
+ * scale s in 1 .. 4 from the last convolution's 3 s^2 channels, num_feat 64 only; or "synth-compact[:seed[:convs[:scale]]]" (defaults 1234, 32, 4).  info: n_block is
+ * the block count of an RRDBNet, N of a compact net; scale 4 or s.
+ * run: src [n_img][3][h][w] planar floats in 0..1 on the host -> dst [n_img][3][s h][s w], by the model's scale (not clamped); the work buffers
  * are one device allocation kept between calls and grown on demand.  Zero padding at the image border, whatever the context's tiling. */
 typedef struct MLIS_AmdUpscaler MLIS_AmdUpscaler;
 MLIS_AmdUpscaler* mlis_amd_upscaler_create(const char* spec);      /* NULL on error */

@@ -83,10 +83,11 @@ typedef enum {
 	MLIS_OPT_AMD_FREEU_B2 = 143,           /* "freeu_b2" (float 0 .. 4, default 1.4): backbone factor of stage 2 */
 	MLIS_OPT_AMD_FREEU_S1 = 144,           /* "freeu_s1" (float 0 .. 4, default 0.9): skip factor of stage 1 */
 	MLIS_OPT_AMD_FREEU_S2 = 145,           /* "freeu_s2" (float 0 .. 4, default 0.2): skip factor of stage 2.  The four are device data of the engine: a change rebuilds nothing */
-	/* ESRGAN upscaler (RRDBNet x4): a learned pixel-space upscaler for mlis_amd_tensor_upscale and, with hires_use_model, for the hires fix */
-	MLIS_OPT_AMD_UPSCALE_MODEL = 151,      /* "upscale_model" (string): a safetensors RRDBNet in BasicSR's naming, or "synth[:seed[:blocks]]"; empty clears it and frees the
+	/* ESRGAN upscaler (RRDBNet x4, or a Real-ESRGAN compact SRVGG net x1 .. x4): a learned pixel-space upscaler for mlis_amd_tensor_upscale and, with hires_use_model, for the hires fix */
+	MLIS_OPT_AMD_UPSCALE_MODEL = 151,      /* "upscale_model" (string): a safetensors RRDBNet or compact SRVGG net in BasicSR's naming, "synth[:seed[:blocks]]" or
+	                                        * "synth-compact[:seed[:convs[:scale]]]"; empty clears it and frees the
 	                                        * resident upscaler.  The upscaler is built on first use and stays resident, keyed by this string */
-	MLIS_OPT_AMD_HIRES_USE_MODEL = 152,    /* "hires_use_model" (int 0 / 1, default 0): the hires fix decodes its first pass, upscales the IMAGE 4x with upscale_model, resamples it
+	MLIS_OPT_AMD_HIRES_USE_MODEL = 152,    /* "hires_use_model" (int 0 / 1, default 0): the hires fix decodes its first pass, upscales the IMAGE by the model's scale with upscale_model, resamples it
 	                                        * to the target size (in the hires_upscaler mode, a plain resample; with the downscale_filter where that is set) and runs the second
 	                                        * pass as img2img from it */
 	/* antialiased downscaling: the filter of the resamples that shrink an image -- the hires fix's model path to its target size and the control image to a pass's size --,
@@ -297,7 +298,8 @@ int mlis_amd_inpaint_region(int W, int H, const int bbox[4], int padding, int tw
 /* of the last mlis_generate: region = the rectangle composited (the whole image with inpaint_area whole), proc = the size the pass ran at.  Returns 1, or 0 (and zeros) if
  * that generation composited nothing.  Either pointer may be NULL. */
 int mlis_amd_inpaint_info(MLIS_Ctx* ctx, int region[4], int proc[2]);
-/* dst = src upscaled 4x by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 -> dst [4w][4h][3][n] (not clamped).  src == dst is allowed.
+/* dst = src upscaled by the model's scale s (4 for an RRDBNet, 1 .. 4 for a compact net) by the model of the "upscale_model" option: src [w][h][3][n] floats in 0..1 ->
+ * dst [s w][s h][3][n] (not clamped).  src == dst is allowed.
  * The upscaler is built on the first use and stays resident in the context until the option changes (mlis_amd_upscaler_builds counts the builds); the image border is
  * padded with zeros whatever "tiling" says.  Returns 1, MLIS_E_OPT_VALUE when no upscale_model is set or src is not a 3-channel image. */
 int mlis_amd_tensor_upscale(MLIS_Ctx* ctx, const MLIS_Tensor* src, MLIS_Tensor* dst);

@@ -783,6 +783,42 @@ typedef struct mlsd_dconv_args {
 int mlsd_conv3x3_dense(const mlsd_dconv_args* a, void* stream);
 /* label of the kernel instantiation these arguments launch, "dconv3x3<n32,c192[,up]>" (mlsd_gemm_variant's counterpart; valid until the thread's next call) */
 const char* mlsd_dconv_variant(const mlsd_dconv_args* a);
+/* Convolution of the Real-ESRGAN COMPACT upscalers (csrc/hip/upscale_compact.hip; not in the reference): 3x3, stride 1, zero padding 1, over a channels-last fp16 image
+ * [n_img][H][W] with lda halfs between pixels, the layer's whole weight tensor resident in LDS for the launch.
+ *
+ * The network is SRVGGNetCompact as published with Real-ESRGAN / BasicSR (basicsr/archs/srvgg_arch.py), AS RECALLED WHEN THIS WAS WRITTEN AND NOT CHECKED: no weight file and
+ * no publication was at hand.  num_feat 64, num_conv N, upscale s:
+ *   body.0          conv 3x3, 3 -> 64            body.1      PReLU, 64 slopes
+ *   N times:        body.2k  conv 3x3, 64 -> 64  body.2k+1   PReLU, 64 slopes          (k = 1 .. N)
+ *   body.(2N+2)     conv 3x3, 64 -> 3 s^2
+ *   out = pixel_shuffle(body(x), s) + nearest_s(x)
+ * every convolution with zero padding 1; PReLU(z) = z >= 0 ? z : slope[c] z; pixel shuffle as PyTorch's: channel c s^2 + dy s + dx of pixel (y, x) becomes channel c of
+ * pixel (s y + dy, s x + dx).  host/upscaler.c accepts s in 1 .. 4, N in 1 .. 64 and num_feat 64 only.
+ *
+ * Three forms, by Cin, Cout and scale:
+ *   head  Cin 32 (the 3 input channels packed to 32, zero-padded weights), Cout 64, scale 0     body  Cin 64, Cout 64, scale 0      tail  Cin 64, Cout 3 s^2, scale s in 1 .. 4
+ * W_: fp16 [Cout rounded up to a multiple of 16][3][3][Cin], K-contiguous; the rows >= Cout are read and their products dropped.  bias fp32 [Cout].
+ * head, body: slope fp32 [Cout] or NULL (no activation); C16 fp16 with ldc16 halfs between pixels:  z = acc + bias[n];  y = z >= 0 ? z : slope[n] * z;  C16 = y to nearest even.
+ * tail: X32 the planar fp32 input [n_img][3][H][W], Y32 planar fp32 [n_img][3][s H][s W]:  z = acc + bias[n];  Y32[c][s y + dy][s x + dx] = z + X32[c][y][x].
+ * Arithmetic: fp16 operands, fp32 accumulation on MFMA (v_mfma_f32_16x16x32_f16), nothing else rounded; the ending in fp32, each operation rounded once.
+ * grid: 0 = min(tiles of 12 x 16 pixels, CUs of the device) persistent workgroups, > 0 = that many (capped at the tiles): the result does not depend on it.
+ * Deterministic: the same input gives the same bits; no atomics, no workgroup waits on another.
+ * Refused with an error and no launch: Cin / Cout / scale outside the three forms; A or W_ not 16-byte aligned, lda not a multiple of 8 or below Cin; C16 not 16-byte
+ * aligned, ldc16 not a multiple of 8 or below Cout; a missing bias; pointers of the other form set; an output that aliases A or X32. */
+typedef struct mlsd_cconv_args {
+	const void* A; int64_t lda;
+	int n_img, H, W, Cin, Cout;
+	int scale;                  /* 0: head / body; 1 .. 4: tail */
+	const void* W_;
+	const float* bias;
+	const float* slope;         /* PReLU [Cout] or NULL */
+	void* C16; int64_t ldc16;
+	const float* X32; float* Y32;
+	int grid;
+} mlsd_cconv_args;
+int mlsd_conv3x3_compact(const mlsd_cconv_args* a, void* stream);
+/* label of the kernel instantiation these arguments launch: "cconv3x3<head>", "<body>", "<tail,s4>", "<refused>" (valid until the thread's next call) */
+const char* mlsd_cconv_variant(const mlsd_cconv_args* a);
 /* finite check (ltensor_finite_check, src/unet.c:487): counts non-finite values into *count (device int32) */
 int mlsd_count_nonfinite(const float* x, size_t n, int32_t* count, void* stream);
 /* deterministic synthetic parameter fill, bit-identical to oracle/o_core.c orc_synth_fill.

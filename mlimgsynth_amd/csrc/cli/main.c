@@ -321,7 +321,8 @@ static const char k_usage[] =
 "             --batch-size N   --tokens IDS   --ntokens IDS   --tiling none|x|y|xy\n"
 "Hires fix:   --hires-scale F   --hires-denoise F   --hires-steps N   --hires-upscaler nearest|bilinear|bicubic   --hires-use-model y|n\n"
 "Upscaler:    --upscale-model PATH|synth[:SEED[:BLOCKS]]   (ESRGAN RRDBNet x4, safetensors);  upscale -i IN -o OUT --upscale-model PATH needs no -m\n"
-"             --outscale F   (upscale: 0 < F <= 4, the x4 output filtered down to F times the input; lanczos unless --downscale-filter names another)\n"
+"             (also a Real-ESRGAN compact SRVGG net x1 .. x4, or synth-compact[:SEED[:CONVS[:SCALE]]])\n"
+"             --outscale F   (upscale: 0 < F <= 4, the model's output filtered to F times the input; lanczos unless --downscale-filter names another)\n"
 "Downscaling: --downscale-filter none|box|bilinear|bicubic|lanczos   (antialiased: hires fix with a model, control image, --outscale)\n"
 "Models:      -m --model PATH|synth:NAME   --tae PATH   --lora PATH[,MULT]   --lora-dir PATH   -b --backend NAME\n"
 "             -t --threads N   --unet-split BOOL   --vae-tile N   --weight-type NAME   --model-type NAME   --aux-dir PATH\n"
@@ -551,7 +552,7 @@ end:
 	return R;
 }
 
-/* upscale: --input 4x through the --upscale-model, no SD model involved */
+/* upscale: --input through the --upscale-model (by the model's scale), no SD model involved */
 static int cmd_upscale(Cli* C)
 {
 	const char *model = NULL;
@@ -565,13 +566,14 @@ static int cmd_upscale(Cli* C)
 	MLIS_Tensor t = {0};
 	tensor_from_img(&t, NULL, &in3);
 	free(rgb); free(im.d);
+	const int w0 = t.n[0], h0 = t.n[1];
 	int r = mlis_amd_tensor_upscale(C->ctx, &t, &t);
 	if (r < 0) fprintf(stderr, "error: upscale: %s\n", mlis_errstr_get(C->ctx));
-	else if (C->outscale > 0 && C->outscale != 4) {      /* the x4 output filtered down to round(F w) x round(F h) */
+	else if (C->outscale > 0) {      /* the model's output brought to round(F w) x round(F h), unless it has that size */
 		int filter = 0;
 		mlis_option_get(C->ctx, MLIS_OPT_AMD_DOWNSCALE_FILTER, &filter);
-		const int w = (int)floor(C->outscale * (t.n[0] / 4) + 0.5), h = (int)floor(C->outscale * (t.n[1] / 4) + 0.5);
-		r = mlis_amd_tensor_resample_aa(C->ctx, &t, &t, w > 1 ? w : 1, h > 1 ? h : 1, filter ? filter - 1 : MLIS_AMD_AA_LANCZOS);
+		const int w = (int)floor(C->outscale * w0 + 0.5), h = (int)floor(C->outscale * h0 + 0.5);
+		if (w != t.n[0] || h != t.n[1]) r = mlis_amd_tensor_resample_aa(C->ctx, &t, &t, w > 1 ? w : 1, h > 1 ? h : 1, filter ? filter - 1 : MLIS_AMD_AA_LANCZOS);
 		if (r < 0) fprintf(stderr, "error: outscale: %s\n", mlis_errstr_get(C->ctx));
 	}
 	if (r >= 0) {

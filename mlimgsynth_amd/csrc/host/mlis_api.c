@@ -1941,11 +1941,13 @@ static int tensor_upscale(MLIS_Ctx* S, const MLIS_Tensor* src, MLIS_Tensor* dst)
 	const int w = src->n[0], h = src->n[1], b = src->n[3];
 	if ((double)w * h * b * 16 * 3 >= 2147483648.0) return api_error(S, MLIS_E_OPT_VALUE, "image too large to upscale: %dx%d x %d", w, h, b);
 	int r = upscaler_get(S); if (r < 0) return r;
-	float *out = (float*)malloc(sizeof(float) * (size_t)16 * w * h * 3 * b);
+	int s = 4;      /* the model's scale: 4 for RRDBNet, 1 .. 4 for a compact net */
+	mlis_amd_upscaler_info(S->upscaler, NULL, &s);
+	float *out = (float*)malloc(sizeof(float) * (size_t)s * s * w * h * 3 * b);
 	if (!out) return api_error(S, MLIS_E_UNKNOWN, "out of memory");
 	if (mlis_amd_upscaler_run(S->upscaler, src->d, w, h, b, out) < 0) { free(out); return api_error_lib(S, MLIS_E_UNKNOWN); }
-	mlis_tensor_resize(dst, 4 * w, 4 * h, 3, b);
-	memcpy(dst->d, out, sizeof(float) * (size_t)16 * w * h * 3 * b);
+	mlis_tensor_resize(dst, s * w, s * h, 3, b);
+	memcpy(dst->d, out, sizeof(float) * (size_t)s * s * w * h * 3 * b);
 	free(out);
 	return 1;
 }
@@ -2170,7 +2172,7 @@ static int generate_pass_fixed(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img
 /* hires fix: the txt2img pass at IMAGE_DIM (never decoded), its latent upscaled, then the img2img-from-latent pass at the target size with
  * f_t_ini = hires_denoise -- what a caller gets from generate (NO_DECODE) + mlis_amd_tensor_resample + generate (MLIS_TUF_LATENT), with the
  * prompt, the token ids and the prompt's LoRAs in place until the end and the Philox streams running on from the first pass.  With hires_use_model the first pass
- * IS decoded, its image goes 4x through the upscale model and a plain resample to the target size, and the second pass is img2img from that image */
+ * IS decoded, its image goes through the upscale model (by the model's scale) and a plain resample to the target size, and the second pass is img2img from that image */
 static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int* hires_n_step)
 {
 	static const struct { int flag; const char* what; } inputs[] = { {MLIS_TUF_IMAGE, "an input image (image)"}, {MLIS_TUF_LATENT, "an input latent (tensor_use_flags latent)"},
@@ -2186,7 +2188,7 @@ static int generate_hires(MLIS_Ctx* S, int decode, int* pw_img, int* ph_img, int
 		MLIS_Tensor first = {0};      /* the colour fix's target: the decoded first pass */
 		if (use_model && S->cfix_mode && decode) mlis_tensor_copy(&first, &S->image);
 		if (use_model) {
-			/* the decoded first pass upscaled 4x by the model, brought to the target pixel size by a plain resample -- or, with a downscale_filter and an axis that
+			/* the decoded first pass upscaled by the model (by its own scale: a model of less than hires_scale leaves the resample to enlarge), brought to the target pixel size by a plain resample -- or, with a downscale_filter and an axis that
 			 * shrinks, by that filter --; the second pass encodes it (generate_pass, MLIS_TUF_IMAGE): what a caller gets from generate + mlis_amd_tensor_upscale +
 			 * mlis_amd_tensor_resample (or _resample_aa) + generate with an input image */
 			r = tensor_upscale(S, &S->image, &S->image);

@@ -20,7 +20,14 @@
  * mapped as well: up_old_name, unverified); or
  * "synth[:seed[:blocks]]": mlsd_synth_fill with standard deviation 0.1 sqrt(2 / fan_in) for the convolutions of the dense blocks (BasicSR's scaled initialisation of exactly
  * those, as recalled) and sqrt(2 / fan_in) for the seven others -- scaled by 0.1 as well, the five convolutions behind the trunk would shrink it to 1e-5 of their own
- * biases and the output would not depend on the blocks at all (tests/test_upscale_cpu.py asserts that it does); biases of deviation 0.05. */
+ * biases and the output would not depend on the blocks at all (tests/test_upscale_cpu.py asserts that it does); biases of deviation 0.05.
+ *
+ * The COMPACT nets of Real-ESRGAN (SRVGGNetCompact: realesr-general-x4v3, realesr-animevideov3 and the x2 / x3 anime models) run on mlsd_conv3x3_compact
+ * (csrc/hip/upscale_compact.hip); include/mlsd_kernels.h states the network, as recalled and unchecked.  A file with a four-dimensional body.0.weight and no
+ * conv_first.weight is one: N = its convolutions less two (1 .. UP_MAX_BLOCKS), s from the last convolution's 3 s^2 output channels (1 .. 4), num_feat 64 only.
+ * Data flow: the input packed to 32 fp16 channels, two ping-pong fp16 buffers [pixels][64], and the fp32 input kept for the tail, whose ending shuffles the pixels and
+ * adds the input: the planar fp32 result is written by the last launch.  "synth-compact[:seed[:convs[:scale]]]" (defaults 1234, 32, 4): the key derivation above,
+ * deviation sqrt(2 / fan_in) for every convolution, 0.05 for biases, slopes 0.1 with deviation 0.1 (uniform in 0.1 +- 0.173: a fifth of them negative). */
 #include "mlblock_int.h"
 #include "mlimgsynth_amd.h"
 #include <math.h>
@@ -30,11 +37,12 @@
 
 enum { UP_FEAT = 64, UP_GROW = 32, UP_DENSE = 192, UP_MAX_BLOCKS = 64 };
 
-typedef struct { void* w; float* b; int cin, cin_pad, cout; } UpConv;
+typedef struct { void* w; float* b; int cin, cin_pad, cout; float* s /* compact: PReLU slopes or NULL */; } UpConv;
 
 struct MLIS_AmdUpscaler {
-	int n_block;
-	UpConv first, *body /* [n_block][3][5] */, conv_body, up1, up2, hr, last;
+	int n_block;            /* RRDB blocks; compact: N, the 64 -> 64 convolutions */
+	int compact, scale;
+	UpConv first, *body /* [n_block][3][5]; compact: [n_block + 2] */, conv_body, up1, up2, hr, last;
 	void* arena; size_t arena_bytes;
 };
 
@@ -51,7 +59,7 @@ static uint64_t up_key(const char* name, uint64_t seed)
 	return up_mix64(h ^ (seed * 0x9E3779B97F4A7C15ULL));
 }
 
-static void conv_free(UpConv* c) { if (c->w) mlsd_free(c->w); if (c->b) mlsd_free(c->b); c->w = NULL; c->b = NULL; }
+static void conv_free(UpConv* c) { if (c->w) mlsd_free(c->w); if (c->b) mlsd_free(c->b); if (c->s) mlsd_free(c->s); c->w = NULL; c->b = NULL; c->s = NULL; }
 
 static int conv_alloc(UpConv* c, int cin, int cout)
 {
@@ -60,16 +68,20 @@ static int conv_alloc(UpConv* c, int cin, int cout)
 	return 0;
 }
 
-static int conv_synth(UpConv* c, const char* name, uint64_t seed)
+static int conv_synth_dev(UpConv* c, const char* name, uint64_t seed, float ws)
 {
 	char key[96];
-	const float ws = (float)((strncmp(name, "body.", 5) ? 1.0 : 0.1) * sqrt(2.0 / (9.0 * c->cin))), bs = 0.05f;
+	const float bs = 0.05f;
 	if (c->cin_pad != c->cin && mlsd_memset(c->w, 0, (size_t)c->cout * 9 * c->cin_pad * 2, NULL)) return -1;
 	snprintf(key, sizeof(key), "%s.weight", name);
 	if (mlsd_synth_fill(c->w, 1, (int64_t)c->cout * c->cin * 9, up_key(key, seed), 0, (float)((double)ws * 1.7320508075688772 / 65536.0), 1,
 			3, 3, c->cin, c->cout, c->cin_pad, NULL)) return -1;
 	snprintf(key, sizeof(key), "%s.bias", name);
 	return mlsd_synth_fill(c->b, 0, c->cout, up_key(key, seed), 0, (float)((double)bs * 1.7320508075688772 / 65536.0), 0, 0, 0, 0, 0, 0, NULL) ? -1 : 0;
+}
+static int conv_synth(UpConv* c, const char* name, uint64_t seed)
+{
+	return conv_synth_dev(c, name, seed, (float)((strncmp(name, "body.", 5) ? 1.0 : 0.1) * sqrt(2.0 / (9.0 * c->cin))));
 }
 
 /* prefix "model.": the naming of the first ESRGAN release (an nn.Sequential), AS RECALLED AND UNVERIFIED -- no such file was at hand:
@@ -151,7 +163,7 @@ MLB_API void mlis_amd_upscaler_destroy(MLIS_AmdUpscaler* U)
 	if (!U) return;
 	UpConv *fixed[] = { &U->first, &U->conv_body, &U->up1, &U->up2, &U->hr, &U->last };
 	for (int i=0;i<6;++i) conv_free(fixed[i]);
-	if (U->body) for (int i=0;i<U->n_block*15;++i) conv_free(&U->body[i]);
+	if (U->body) for (int i=0;i<(U->compact ? U->n_block+2 : U->n_block*15);++i) conv_free(&U->body[i]);
 	free(U->body);
 	if (U->arena) mlsd_free(U->arena);
 	free(U);
@@ -175,20 +187,127 @@ static int up_parse_synth(const char* spec, uint64_t* seed, int* blocks)
 	return 1;
 }
 
+/* ------------------------------------------------------------------ the compact nets (SRVGGNetCompact) */
+/* "synth-compact[:seed[:convs[:scale]]]" -> 1, 0 for anything else, < 0 for a malformed spec */
+static int cc_parse_synth(const char* spec, uint64_t* seed, int* convs, int* scale)
+{
+	static const char word[] = "synth-compact";
+	const size_t nw = sizeof(word) - 1;
+	*seed = 1234; *convs = 32; *scale = 4;
+	if (strncmp(spec, word, nw) || (spec[nw] && spec[nw] != ':')) return 0;
+	long v[3] = { 1234, 32, 4 };
+	const char *s = spec + nw;
+	for (int i=0;i<3 && *s;++i) {
+		char *end = NULL;
+		const unsigned long long u = strtoull(s + 1, &end, 10);
+		if (end == s + 1 || s[1] == '-' || (*end && *end != ':')) return mlsd_set_error(-1, "upscaler: invalid synthetic model '%s' (synth-compact[:seed[:convs[:scale]]])", spec);
+		if (i == 0) *seed = (uint64_t)u; else v[i] = u > 1000 ? 1000 : (long)u;
+		s = end;
+	}
+	if (*s) return mlsd_set_error(-1, "upscaler: invalid synthetic model '%s' (synth-compact[:seed[:convs[:scale]]])", spec);
+	if (v[1] < 1 || v[1] > UP_MAX_BLOCKS) return mlsd_set_error(-1, "upscaler: invalid convolution count in '%s' (1 .. %d)", spec, UP_MAX_BLOCKS);
+	if (v[2] < 1 || v[2] > 4) return mlsd_set_error(-1, "upscaler: invalid scale in '%s' (1 .. 4)", spec);
+	*convs = (int)v[1]; *scale = (int)v[2];
+	return 1;
+}
+
+/* 1 with the prefix, N and s of a compact file; 0 when the file is none (it has conv_first.weight, the older model.0.weight, or no four-dimensional body.0.weight); < 0 on error */
+static int cc_file_layout(const MLTStore* ts, const char** prefix, int* n_conv, int* scale)
+{
+	static const char* const pre[] = { "", "params_ema.", "params." };
+	char key[160];
+	const MLTSEntry *e = NULL, *last = NULL;
+	if (mlts_find(ts, "model.0.weight")) return 0;
+	for (int i=0;i<3;++i) { snprintf(key, sizeof(key), "%sconv_first.weight", pre[i]); if (mlts_find(ts, key)) return 0; }
+	*prefix = NULL;
+	for (int i=0;i<3 && !*prefix;++i) { snprintf(key, sizeof(key), "%sbody.0.weight", pre[i]); if ((e = mlts_find(ts, key)) && e->n_dim == 4) *prefix = pre[i]; }
+	if (!*prefix) return 0;
+	int total = 0;          /* convolutions: body.0, body.2, ... as far as they go */
+	for (; total <= UP_MAX_BLOCKS + 2; ++total) {
+		snprintf(key, sizeof(key), "%sbody.%d.weight", *prefix, 2 * total);
+		if (!(e = mlts_find(ts, key)) || e->n_dim != 4) break;
+		last = e;
+	}
+	if (total > UP_MAX_BLOCKS + 2) return mlsd_set_error(-1, "upscaler: more than %d convolutions of 64 -> 64", UP_MAX_BLOCKS);
+	if (total < 3) return mlsd_set_error(-1, "upscaler: tensor '%sbody.%d.weight' is missing: a compact net has at least three convolutions", *prefix, 2 * total);
+	const long long co = (long long)last->shape[3];
+	int s = 1;
+	while (s <= 4 && 3 * s * s != co) ++s;
+	if (s > 4) return mlsd_set_error(-1, "upscaler: '%sbody.%d.weight' has %lld output channels, expected 3 s^2 with a scale s in 1 .. 4 (3, 12, 27 or 48)", *prefix, 2 * (total - 1), co);
+	*n_conv = total - 2; *scale = s;
+	return 1;
+}
+
+static int cc_slope_load(UpConv* c, const MLTStore* ts, const char* prefix, const char* name)
+{
+	char key[160];
+	snprintf(key, sizeof(key), "%s%s.weight", prefix, name);
+	const MLTSEntry *e = mlts_find(ts, key);
+	if (!e) return mlsd_set_error(-1, "upscaler: tensor '%s' is missing", key);
+	if (e->shape[0] != UP_FEAT || e->shape[1] * e->shape[2] * e->shape[3] != 1)
+		return mlsd_set_error(-1, "upscaler: '%s' has %lld elements, expected %d PReLU slopes", key, (long long)(e->shape[0] * e->shape[1] * e->shape[2] * e->shape[3]), UP_FEAT);
+	float s[UP_FEAT];
+	if (mlts_entry_to_f32(e, s, UP_FEAT) < 0 || mlsd_memcpy(c->s, s, sizeof(s), 0, NULL)) return -1;
+	return 0;
+}
+
+/* convolution i of n + 2 ("body.2i"), with its slopes ("body.2i+1") unless it is the last: from the file, or synthetic */
+static int cc_conv_build(UpConv* c, int i, int n, int scale, const MLTStore* ts, const char* prefix, uint64_t seed)
+{
+	char name[32], key[64];
+	const int cin = i ? UP_FEAT : 3, cout = i == n + 1 ? 3 * scale * scale : UP_FEAT, cout_pad = (cout + 15) / 16 * 16;
+	c->cin = cin; c->cin_pad = i ? UP_FEAT : 32; c->cout = cout;
+	const size_t wbytes = (size_t)cout_pad * 9 * c->cin_pad * 2;      /* the kernel reads whole groups of 16 rows */
+	if (mlsd_malloc(&c->w, wbytes) || mlsd_malloc((void**)&c->b, (size_t)cout * 4) || mlsd_memset(c->w, 0, wbytes, NULL)) return -1;
+	if (i <= n && mlsd_malloc((void**)&c->s, UP_FEAT * 4)) return -1;
+	snprintf(name, sizeof(name), "body.%d", 2 * i);
+	if (ts ? conv_load(c, ts, prefix, name, 0) : conv_synth_dev(c, name, seed, (float)sqrt(2.0 / (9.0 * cin)))) return -1;
+	if (i > n) return 0;
+	snprintf(name, sizeof(name), "body.%d", 2 * i + 1);
+	if (ts) return cc_slope_load(c, ts, prefix, name);
+	snprintf(key, sizeof(key), "%s.weight", name);
+	return mlsd_synth_fill(c->s, 0, UP_FEAT, up_key(key, seed), 0.1f, (float)((double)0.1f * 1.7320508075688772 / 65536.0), 0, 0, 0, 0, 0, 0, NULL) ? -1 : 0;
+}
+
+static MLIS_AmdUpscaler* cc_create(int n, int scale, const MLTStore* ts, const char* prefix, uint64_t seed)
+{
+	MLIS_AmdUpscaler *U = (MLIS_AmdUpscaler*)calloc(1, sizeof(*U));
+	if (U) { U->compact = 1; U->n_block = n; U->scale = scale; U->body = (UpConv*)calloc((size_t)n + 2, sizeof(UpConv)); }
+	int r = (U && U->body) ? 0 : mlsd_set_error(-1, "upscaler: out of host memory");
+	for (int i=0;i<n+2 && !r;++i) r = cc_conv_build(&U->body[i], i, n, scale, ts, prefix, seed);
+	if (!r && !mlsd_runtime_is_dry() && mlsd_device_sync()) r = -1;
+	if (r) { mlis_amd_upscaler_destroy(U); return NULL; }
+	return U;
+}
+
 MLB_API MLIS_AmdUpscaler* mlis_amd_upscaler_create(const char* spec)
 {
 	if (!spec || !*spec) { mlsd_set_error(-1, "upscaler: no model given"); return NULL; }
 	uint64_t seed; int nb;
+	{
+		int scale;
+		const int cs = cc_parse_synth(spec, &seed, &nb, &scale);
+		if (cs < 0) return NULL;
+		if (cs) return cc_create(nb, scale, NULL, "", seed);
+	}
 	const int synth = up_parse_synth(spec, &seed, &nb);
 	if (synth < 0) return NULL;
 	MLTStore *ts = NULL; const char *prefix = "";
 	if (!synth) {
 		ts = mlts_open(spec, 0);
 		if (!ts) return NULL;
+		int scale = 4;
+		const int cf =cc_file_layout(ts, &prefix, &nb, &scale);
+		if (cf) {
+			MLIS_AmdUpscaler *U = cf < 0 ? NULL : cc_create(nb, scale, ts, prefix, 0);
+			mlts_close(ts);
+			return U;
+		}
+		prefix = "";
 		if ((nb = up_file_layout(ts, &prefix)) < 0) { mlts_close(ts); return NULL; }
 	}
 	MLIS_AmdUpscaler *U = (MLIS_AmdUpscaler*)calloc(1, sizeof(*U));
-	if (U) { U->n_block = nb; U->body = (UpConv*)calloc((size_t)nb * 15, sizeof(UpConv)); }
+	if (U) { U->n_block = nb; U->scale = 4; U->body = (UpConv*)calloc((size_t)nb * 15, sizeof(UpConv)); }
 	int r = (U && U->body) ? 0 : mlsd_set_error(-1, "upscaler: out of host memory");
 	char name[96];
 #define UP_CONV(c, cin, cout, ...) do { if (!r) { snprintf(name, sizeof(name), __VA_ARGS__); \
@@ -214,7 +333,7 @@ MLB_API int mlis_amd_upscaler_info(const MLIS_AmdUpscaler* U, int* n_block, int*
 {
 	if (!U) return -1;
 	if (n_block) *n_block = U->n_block;
-	if (scale) *scale = 4;
+	if (scale) *scale = U->scale;
 	return 1;
 }
 
@@ -229,10 +348,47 @@ static int dconv(const UpConv* c, const void* A, int64_t lda, int n_img, int H, 
 	return mlsd_conv3x3_dense(&a, NULL);
 }
 
-/* src [n_img][3][h][w] planar floats on the HOST -> dst [n_img][3][4h][4w] on the host */
+/* the compact net: head, N body launches between two ping-pong buffers, the tail writing the planar result */
+static int cc_run(MLIS_AmdUpscaler* U, const float* src, int w, int h, int n_img, float* dst)
+{
+	const int s = U->scale, n = U->n_block;
+	if ((double)w * h * n_img * s * s >= 2147483648.0 / 4) return mlsd_set_error(-1, "upscaler: %d images of %dx%d are too large for one pass (tiled upscaling is not implemented)", n_img, w, h);
+	const size_t P = (size_t)n_img * h * w;
+	size_t off = 0;
+#define UP_TAKE(var, bytes) const size_t var = off; off += (((size_t)(bytes)) + 255) & ~(size_t)255
+	UP_TAKE(o_in, P * 3 * 4); UP_TAKE(o_x16, P * 32 * 2); UP_TAKE(o_b0, P * UP_FEAT * 2); UP_TAKE(o_b1, P * UP_FEAT * 2); UP_TAKE(o_out, P * 3 * 4 * s * s);
+#undef UP_TAKE
+	if (U->arena_bytes < off) {
+		if (U->arena) mlsd_free(U->arena);
+		U->arena = NULL; U->arena_bytes = 0;
+		if (mlsd_malloc(&U->arena, off)) return -1;
+		U->arena_bytes = off;
+	}
+	char *base = (char*)U->arena;
+	float *in32 = (float*)(base + o_in), *out = (float*)(base + o_out);
+	void *x16 = base + o_x16, *B[2] = { base + o_b0, base + o_b1 };
+	if (mlsd_memcpy(in32, src, P * 3 * 4, 0, NULL)) return -1;
+	if (mlsd_nchw_to_nhwc_f16(in32, n_img, 3, h * w, x16, n_img, 32, NULL, 1.0f, 0, NULL)) return -1;
+	const void *A = x16;
+	for (int i=0;i<n+2;++i) {
+		const UpConv *c = &U->body[i];
+		mlsd_cconv_args a; memset(&a, 0, sizeof(a));
+		a.A = A; a.lda = c->cin_pad; a.n_img = n_img; a.H = h; a.W = w; a.Cin = c->cin_pad; a.Cout = c->cout;
+		a.W_ = c->w; a.bias = c->b; a.slope = c->s;
+		if (i <= n) { a.C16 = B[i & 1]; a.ldc16 = UP_FEAT; }
+		else { a.scale = s; a.X32 = in32; a.Y32 = out; }
+		if (mlsd_conv3x3_compact(&a, NULL)) return -1;
+		A = B[i & 1];
+	}
+	if (mlsd_memcpy(dst, out, P * 3 * 4 * s * s, 1, NULL) || mlsd_device_sync()) return -1;
+	return 1;
+}
+
+/* src [n_img][3][h][w] planar floats on the HOST -> dst [n_img][3][s h][s w] on the host, s the model's scale */
 MLB_API int mlis_amd_upscaler_run(MLIS_AmdUpscaler* U, const float* src, int w, int h, int n_img, float* dst)
 {
 	if (!U || !src || !dst || w < 1 || h < 1 || n_img < 1) return mlsd_set_error(-1, "upscaler: invalid arguments");
+	if (U->compact) return cc_run(U, src, w, h, n_img, dst);
 	if ((double)w * h * n_img * 16 >= 2147483648.0 / 4) return mlsd_set_error(-1, "upscaler: %d images of %dx%d are too large for one pass (tiled upscaling is not implemented)", n_img, w, h);
 	const size_t P = (size_t)n_img * h * w;
 	/* one arena, grown when a larger job comes: a failed allocation leaves nothing half allocated */

@@ -116,6 +116,12 @@ class DconvArgs(ctypes.Structure):
                 ("scale2", c_f), ("resid2", vp), ("ldr2", c_i64), ("C32", vp), ("ldc32", c_i64), ("C16", vp), ("ldc16", c_i64)]
 
 
+class CconvArgs(ctypes.Structure):
+    """mlsd_cconv_args: the convolution of the Real-ESRGAN compact upscalers, weights resident in LDS (hip/upscale_compact.hip)"""
+    _fields_ = [("A", vp), ("lda", c_i64), ("n_img", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int), ("scale", c_int),
+                ("W_", vp), ("bias", vp), ("slope", vp), ("C16", vp), ("ldc16", c_i64), ("X32", vp), ("Y32", vp), ("grid", c_int)]
+
+
 class XavtArgs(ctypes.Structure):
     _fields_ = [("v", vp), ("ldv", c_i64), ("n_img", c_int), ("Tk", c_int), ("N", c_int), ("vt", vp)]
 
@@ -130,6 +136,16 @@ def conv3x3_dense(args, stream=None):
 
 def dconv_variant(args):
     f = lib().mlsd_dconv_variant
+    f.restype = ctypes.c_char_p
+    return f(ctypes.byref(args)).decode()
+
+
+def conv3x3_compact(args, stream=None):
+    check(lib().mlsd_conv3x3_compact(ctypes.byref(args), vp(stream)), "mlsd_conv3x3_compact")
+
+
+def cconv_variant(args):
+    f = lib().mlsd_cconv_variant
     f.restype = ctypes.c_char_p
     return f(ctypes.byref(args)).decode()
 

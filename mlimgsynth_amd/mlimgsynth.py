@@ -300,7 +300,7 @@ class MLImgSynth:
     def hires_set(self, scale, denoise=None, steps=None, upscaler=None, use_model=None):
         """Two-pass generation: scale 0 or 1 switches it off, else 1 < scale <= 4; denoise in (0, 1] is the second pass's strength,
         steps its step count (0 = the STEPS value), upscaler 'nearest' | 'bilinear' | 'bicubic'; use_model True: the first pass is decoded and
-        upscaled 4x by the "upscale_model" option's ESRGAN model, then resampled to the target size in the `upscaler` mode.  The options persist."""
+        upscaled by the "upscale_model" option's model (4x for an RRDBNet, the model's own scale for a compact net), then resampled to the target size in the `upscaler` mode.  The options persist."""
         self.option_set("hires_scale", scale)
         if denoise is not None:
             self.option_set("hires_denoise", denoise)
@@ -539,20 +539,22 @@ class MLImgSynth:
         return MLIS_Tensor(tout.contents)
 
     def upscale(self, image, outscale=None):
-        """Upscale an image tensor [n,3,h,w] in [0,1] 4x with the ESRGAN model of the "upscale_model" option (a safetensors RRDBNet or
-        "synth[:seed[:blocks]]"); the result is not clamped.  The upscaler is built on first use and stays resident.
-        outscale F in (0, 4]: the x4 output is brought to round(F w) x round(F h) with the "downscale_filter" option's filter, lanczos where that is none
-        (Real-ESRGAN's --outscale); None or 4 is the x4 output itself."""
+        """Upscale an image tensor [n,3,h,w] in [0,1] by the scale of the "upscale_model" option's model (a safetensors RRDBNet x4 or "synth[:seed[:blocks]]";
+        a Real-ESRGAN compact SRVGG net x1 .. x4 or "synth-compact[:seed[:convs[:scale]]]"); the result is not clamped.  The upscaler is built on first use and
+        stays resident.  outscale F in (0, 4]: the model's output is brought to round(F w) x round(F h) with the "downscale_filter" option's filter, lanczos where
+        that is none (Real-ESRGAN's --outscale); None, or an F that gives the output's own size, is the model's output itself."""
         if outscale is not None and not 0 < outscale <= 4:
             raise ValueError("outscale must be in (0, 4]")
         tin = image._c()
         tout = self._lib.mlis_tensor_get(self._ctx, MLIS_TENSOR_TMP + 2)              # noqa: F821
         if self._lib.mlis_amd_tensor_upscale(self._ctx, ctypes.byref(tin), tout) < 0:
             raise RuntimeError("Failed to upscale the image: %s" % self.errstr_get())
-        if outscale is not None and outscale != 4:
+        w, h = tout.contents.n[0], tout.contents.n[1]
+        if outscale is not None:
+            w, h = int(math.floor(outscale * image.n[0] + 0.5)), int(math.floor(outscale * image.n[1] + 0.5))
+        if (w, h) != (tout.contents.n[0], tout.contents.n[1]):
             f = _I()
             self.option_get(MLIS_OPT_AMD_DOWNSCALE_FILTER, f)                          # noqa: F821
-            w, h = int(math.floor(outscale * image.n[0] + 0.5)), int(math.floor(outscale * image.n[1] + 0.5))
             if self._lib.mlis_amd_tensor_resample_aa(self._ctx, tout, tout, max(w, 1), max(h, 1), f.value - 1 if f.value else MLIS_AMD_AA_LANCZOS) < 0:   # noqa: F821
                 raise RuntimeError("Failed to resample the upscaled image: %s" % self.errstr_get())
         return MLIS_Tensor(tout.contents)
